@@ -9,10 +9,16 @@ Step = one pass of the encode hot path over one batch: 1024 synthetic chunks x e
 (BASELINE.json configs[1]: all-mpnet-base-v2 shape, bf16 weights/activations, fp32 accumulate), ids already
 resident in HBM, output = unit-norm fp16 rows written into the rank's HBM corpus shard.
 value = whole-job chunks/s (all ranks; weak scaling: every rank encodes its own batches, no collective on
-the encode path).  Extra objects on the same line:
+the encode path); ms_per_step = wall time of one timed step.
+
+A plain run sets up, warms up, times the K steps and prints the line: beside `value` it carries only
   roofline      dominant kernel (FFN-1 GEMM), algorithmic FLOPs per launch / mean launch time (hipEvents
                 recorded by the library on the launch stream during the timed region), vs 2.5 PFLOP/s bf16
-  encode        whole-forward MFMA fraction + per-kernel-class time split
+  encode        whole-forward MFMA fraction (from `value`)
+--dump-outputs DIR writes what the last timed step returned (its unit-norm rows, float32) as DIR/embeddings.npy
+(DIR/embeddings_rank<r>.npy on rank r > 0); the inputs are a function of the arguments, so two builds compare row for row.
+--full adds every other measurement and check (each is also switched off by its own option):
+  encode        per-kernel-class time split (a separate untimed pass), the 1 M-chunk sustained leg, bge-large
   search        QPS@top-10 over a 10 M x 768 fp16 shard per rank (configs[2]) at several query-batch sizes,
                 pass-A HBM roofline fraction; with N > 1 the per-shard partials are all-gathered over RCCL;
                 search.strong_scaling = configs[3] (ONE 5 M-row corpus cut N ways, merged answer checked against a single index),
@@ -348,6 +354,11 @@ def main():
     ap.add_argument("--batch", type=int, default=1024)
     ap.add_argument("--seq-len", type=int, default=256)
     ap.add_argument("--model", default="all-mpnet-base-v2")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's output rows (float32) to DIR/embeddings.npy (rank r > 0: embeddings_rank<r>.npy)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline figure: per-kernel table, sustained, search, bge-large, e2e, CPU baseline "
+                         "(the options below switch single legs off; without --full they are all off)")
     ap.add_argument("--search-rows", type=int, default=10_000_000, help="configs[2]: corpus rows PER RANK, weak scaling (0 = skip)")
     ap.add_argument("--search-total-rows", type=int, default=5_000_000,
                     help="configs[3]: rows of ONE corpus cut across the ranks with shard_bounds, strong scaling (0 = skip)")
@@ -462,17 +473,23 @@ def main():
     dt = time.perf_counter() - t0
     _lib.prof_enable(False)
     prof_timed = _lib.prof_read()
-    _lib.prof_reset(); _lib.prof_classes(None); _lib.prof_enable(True)
-    for i in range(K):
-        step(W + i, i)
-    barrier()
-    _lib.prof_enable(False)
+    if args.dump_outputs:                                    # what the last timed step returned to its caller: B unit-norm rows
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "embeddings.npy" if rank == 0 else f"embeddings_rank{rank}.npy"),
+                shard[(K - 1) * B:K * B].float().cpu().numpy())
+    prof = {}
+    if args.full:
+        _lib.prof_reset(); _lib.prof_classes(None); _lib.prof_enable(True)
+        for i in range(K):
+            step(W + i, i)
+        barrier()
+        _lib.prof_enable(False)
+        prof = _lib.prof_read()
     if use_dist:
         tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
     chunks_per_s = world * K * B / dt
-    prof = _lib.prof_read()
     norms = shard[:B].float().norm(dim=1)
     assert torch.isfinite(norms).all() and (norms - 1).abs().max() < 2e-3, "encoder output is not unit-norm"
 
@@ -498,16 +515,16 @@ def main():
                 "flops_per_launch": gemm_flops[dom]}
     fpc = flops_per_chunk(cfg, S)
     encode = {"flops_per_chunk": fpc, "mfma_frac_whole_forward": round(chunks_per_s / world * fpc / MFMA_PEAK_BF16, 4),
-              "kernels": kernels, "sustained": None,
+              "kernels": kernels if args.full else None, "sustained": None,
               "kernels_note": "per-kernel table: separate untimed pass over the same batches with every class recording events; "
-                              "roofline.achieved: FFN-1 events inside the timed region"}
+                              "roofline.achieved: FFN-1 events inside the timed region" + ("" if args.full else "; the table is a --full leg")}
 
     mark("start_up+burst")
     # ---- sustained leg: the whole configs[1] job (1 M chunks = 977 batches, ~50 s) back to back, so that a clock droop under
     # sustained load is visible next to the K-step burst `value` is timed on
     sustained = None
     e2e_rows = None
-    if args.sustained_chunks > 0:
+    if args.full and args.sustained_chunks > 0:
         total = args.sustained_chunks
         nb = (total + B - 1) // B
         big = torch.empty((total, cfg.hidden), dtype=torch.float16, device=dev)
@@ -612,7 +629,7 @@ def main():
         return e
 
     search = None
-    if args.search_rows > 0:
+    if args.full and args.search_rows > 0:
         # configs[2] (weak scaling with N > 1: every rank holds its own 10 M rows of ONE world x 10 M-row corpus)
         N, nq_all, D = args.search_rows, args.search_queries, cfg.hidden
         corpus = fill_unit_rows(N, D, seed=7, device=dev, row_base=rank * N)
@@ -687,7 +704,7 @@ def main():
     # ---- configs[3]: ONE corpus of --search-total-rows rows cut across the ranks (strong scaling), the query set replicated; every rank
     # scans its own slice, one all-gather of the [Q, k] partials over RCCL, merge.  Rank 0 then searches the WHOLE corpus as a single
     # index and checks the merged answer of the first 64 queries against it, bit for bit (the rows are a function of (seed, global row)).
-    if args.search_total_rows > 0:
+    if args.full and args.search_total_rows > 0:
         NT_, nq_all, D = args.search_total_rows, args.search_queries, cfg.hidden
         lo, hi = shard_bounds(NT_, world, rank)
         if use_dist:                                            # the ranks' row ranges tile [0, N): checked on every rank before anything is timed
@@ -768,7 +785,7 @@ def main():
     mark("search.strong_scaling+shard_625k")
     # ---- configs[4]'s per-rank slice in the precision that is feasible (fp8 encode: measured infeasible at the 1e-3 bar):
     # a 6.25 M x 1024 fp16 shard (12.8 GB) searched on one GPU
-    if args.d1024_rows > 0 and world == 1:
+    if args.full and args.d1024_rows > 0 and world == 1:
         N4, D4 = args.d1024_rows, 1024
         c4 = fill_unit_rows(N4, D4, seed=7, device=dev)
         q4 = fill_unit_rows(2048, D4, seed=11, device=dev)
@@ -796,7 +813,7 @@ def main():
     # friendliest case for group-max selection and for the int8 bound).  Clusters of ~500 rows around shared centres + 3 hot dimensions;
     # queries are new points of the same mixture.  Reported: QPS per Qb for the fp16 and int8 first passes, how often the certificate's slow
     # path ran, and what an `adaptive` index decides.
-    if args.clustered_rows > 0 and world == 1:
+    if args.full and args.clustered_rows > 0 and world == 1:
         try:                                                   # an extra leg: its failure must not cost the bench line
             from arxiv_rag_amd.index import fill_clustered_rows
             Nc, Dc = args.clustered_rows, cfg.hidden
@@ -1009,7 +1026,7 @@ def main():
     # ---- configs[4]'s encode half in the precision that is feasible (fp8: measured infeasible at the 1e-3 bar): bge-large shape
     # (24 L / 1024 / 16 heads / FFN 4096, CLS pool), bf16, 256 chunks x 256 tokens per step
     bge = None
-    if args.bge_steps > 0 and world == 1:
+    if args.full and args.bge_steps > 0 and world == 1:
         try:
             enc.close()
             cfg_b = C.PRESETS["BAAI/bge-large-en-v1.5"]
@@ -1046,7 +1063,7 @@ def main():
     encode["sustained"] = sustained
     encode["bge_large"] = bge
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.model, cfg, sd, S, args.cpu_budget)
 
     mark("cpu_baseline")
@@ -1064,6 +1081,7 @@ def main():
             "wall_s": dict(wall, total=round(sum(wall.values()), 1)),
         }
         print(json.dumps(out))
+    enc.close()                                              # idempotent (the bge-large leg may have closed it already)
     if use_dist:
         dist.destroy_process_group()
 

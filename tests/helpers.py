@@ -1,12 +1,27 @@
 """Test-only helpers: an oracle-backed stand-in for the encoder so that the host logic (CLI, loader,
 writer, order contract, fallbacks, multi-rank sharding) can be exercised on CPU.  Never imported by
 the product package."""
+import hashlib
 import json
 import numpy as np
 
 from arxiv_rag_amd import config as C
 from arxiv_rag_amd.weights import seeded_state_dict
 from oracle import encoder_oracle as EO
+
+
+def tiny_weights(g, cfg):
+    """The weights of a tiny golden fixture: stored as `w:<name>` arrays, or (tiny-bert-cls) regenerated from the stored
+    `wspec` = (seed, std, bias_std, ln_jitter) and checked bit for bit against the stored sha256 `wdigest`."""
+    if "wspec" not in g.files:
+        return {k[2:]: g[k] for k in g.files if k.startswith("w:")}
+    seed, std, bstd, jit = g["wspec"]
+    sd = seeded_state_dict(cfg, seed=int(seed), std=std, bias_std=bstd, ln_jitter=jit)
+    h = hashlib.sha256()
+    for k in sd:
+        h.update(k.encode()); h.update(np.ascontiguousarray(sd[k]).tobytes())
+    assert h.digest() == bytes(g["wdigest"]), "the fixture's weights do not regenerate from its seed"
+    return sd
 
 
 def synthetic_vocab(cfg, n_words=90):

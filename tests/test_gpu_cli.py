@@ -246,7 +246,7 @@ def test_bench_starts_its_own_rank_and_prints_one_json_line(hip):
     root = Path(__file__).resolve().parents[1]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["ARX_BENCH_FORCE_LAUNCH"] = "1"
-    r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "64",
+    r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "64", "--full",
                         "--sustained-chunks", "4096", "--e2e-rows", "3000", "--clustered-rows", "0", "--bge-steps", "0",
                         "--no-cpu-baseline", "--no-query-leg", "--search-rows", "200000",
                         "--search-total-rows", "100000", "--d1024-rows", "0", "--search-queries", "300"],
@@ -262,6 +262,47 @@ def test_bench_starts_its_own_rank_and_prints_one_json_line(hip):
     assert d["launch"]["backend"] == "nccl" and d["launch"]["ranks_seen"] == [0] and d["launch"]["row_spans"] == [[0, 100000]]
     e2e = d["e2e_rank_slice"]
     assert "error" not in e2e and e2e["vs_oracle"]["top10_sets_equal_oracle"] is True and e2e["results"]["Qb=64"]["qps_pipelined"] > 0
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_last_step(hip, tmp_path):
+    """A plain `bench.py` run times its steps and stops: one JSON line whose value / ms_per_step agree, none of the --full legs.
+    `--dump-outputs DIR` writes the rows the last timed step returned: identical in two runs with the same arguments, and the
+    rows the encoder gives for that step's batch (ids drawn as bench.py draws them)."""
+    import subprocess
+    import sys
+    from pathlib import Path
+    root = Path(__file__).resolve().parents[1]
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT",
+                                                            "ARX_BENCH_FORCE_LAUNCH")}
+    K, W, B, S = 3, 1, 64, 256
+    dumps = []
+    for run in range(2):
+        out = tmp_path / f"run{run}"
+        r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", str(W), "--batch", str(B),
+                            "--dump-outputs", str(out)], env=env, capture_output=True, text=True, timeout=600)
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert r.returncode == 0 and len(lines) == 1, r.stdout[-2000:] + r.stderr[-3000:]
+        d = json.loads(lines[0])
+        assert d["steps"] == K and d["warmup"] == W and d["unit"] == "chunks/s" and d["higher_is_better"] is True and d["dtype"] == "bf16"
+        assert abs(B * 1000.0 / d["ms_per_step"] - d["value"]) / d["value"] < 0.01
+        assert d["search"] is None and d["cpu_baseline"] is None and d["e2e_rank_slice"] is None
+        assert d["encode"]["sustained"] is None and d["encode"]["kernels"] is None
+        assert sorted(p.name for p in out.iterdir()) == ["embeddings.npy"]
+        dumps.append(np.load(out / "embeddings.npy"))
+    cfg = C.PRESETS["all-mpnet-base-v2"]
+    assert dumps[0].dtype == np.float32 and dumps[0].shape == (B, cfg.hidden)
+    assert np.array_equal(dumps[0], dumps[1])
+    assert np.abs(np.linalg.norm(dumps[0], axis=1) - 1).max() < 2e-3
+    from arxiv_rag_amd.encoder import HipEncoder
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev); g.manual_seed(1234)
+    ids = torch.randint(4, cfg.vocab_size - 1, (K + W, B, S), generator=g, device=dev, dtype=torch.int32)
+    ids[:, :, 0] = 0; ids[:, :, S - 1] = 2
+    enc = HipEncoder(cfg, seeded_state_dict(cfg, seed=0), device=dev, max_tokens=B * S, max_seqs=B)
+    rows = torch.empty((B, cfg.hidden), dtype=torch.float16, device=dev)
+    enc.forward_tokens(ids[K + W - 1], torch.full((B,), S, dtype=torch.int32, device=dev), S, B * S, out=None, out_f16=rows, normalize=True)
+    assert np.abs(rows.float().cpu().numpy() - dumps[0]).max() < 1e-3
+    enc.close()
 
 
 def test_cli_init_distributed_nccl_with_gloo_host_group(hip, tmp_path):

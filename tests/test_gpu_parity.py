@@ -11,6 +11,7 @@ from arxiv_rag_amd import config as C
 from arxiv_rag_amd.weights import seeded_state_dict
 from oracle import encoder_oracle as EO
 from oracle import search_oracle as SO
+from tests.helpers import tiny_weights
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -33,7 +34,7 @@ def test_tiny_golden_all_layers(hip, golden_dir, name):
     from arxiv_rag_amd.encoder import HipEncoder
     g = np.load(golden_dir / f"{name}.npz")
     cfg = C.PRESETS[name]
-    sd = {k[2:]: g[k] for k in g.files if k.startswith("w:")}
+    sd = tiny_weights(g, cfg)
     ids, lens = g["ids"], g["lens"]
     enc = HipEncoder(cfg, sd)
     valid = np.arange(ids.shape[1])[None] < lens[:, None]

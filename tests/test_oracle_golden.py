@@ -7,6 +7,7 @@ from arxiv_rag_amd import config as C
 from arxiv_rag_amd.weights import seeded_state_dict
 from oracle import encoder_oracle as EO
 from oracle import search_oracle as SO
+from tests.helpers import tiny_weights
 
 
 def _cos(a, b):
@@ -17,7 +18,7 @@ def _cos(a, b):
 def test_tiny_all_intermediates(golden_dir, name):
     g = np.load(golden_dir / f"{name}.npz")
     cfg = C.PRESETS[name]
-    sd = {k[2:]: g[k] for k in g.files if k.startswith("w:")}
+    sd = tiny_weights(g, cfg)
     ids, lens = g["ids"], g["lens"]
     h, allh = EO.encoder_hidden(sd, cfg, ids, lens, return_all=True)
     valid = (np.arange(ids.shape[1])[None] < lens[:, None])

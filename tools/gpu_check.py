@@ -11,6 +11,7 @@ from arxiv_rag_amd import config as C
 from arxiv_rag_amd.weights import seeded_state_dict
 from arxiv_rag_amd.encoder import HipEncoder
 from arxiv_rag_amd.index import ShardIndex, merge_partials, fill_unit_rows
+from tests.helpers import tiny_weights
 from oracle import encoder_oracle as EO, search_oracle as SO
 
 GOLD = ROOT / "tests" / "golden"
@@ -24,7 +25,7 @@ def tiny(name, glds):
     os.environ["ARX_GEMM_GLDS"] = "1" if glds else "0"
     g = np.load(GOLD / f"{name}.npz")
     cfg = C.PRESETS[name]
-    sd = {k[2:]: g[k] for k in g.files if k.startswith("w:")}
+    sd = tiny_weights(g, cfg)
     ids, lens = g["ids"], g["lens"]
     enc = HipEncoder(cfg, sd)
     valid = (np.arange(ids.shape[1])[None] < lens[:, None])

@@ -140,7 +140,11 @@ class ShardIndex:
         (local row + idx_base); score desc, ties -> lower id; (-inf, -1) pads when k > n_rows.
         `ws`: the device workspace this call uses (default: the index's own, which makes the index one-caller-at-a-time; callers that
         search one index from several host threads or streams pass their own, `alloc_workspace`).  `out = (scores, ids)` preallocated.
-        `tau_mult` / `drop_best`: the certificate's test hooks, `flags`: ARX_TOPK_* (include/arx.h) — all per call."""
+        `tau_mult` / `drop_best`: the certificate's test hooks, `flags`: ARX_TOPK_* (include/arx.h) — all per call; any other keyword is a
+        TypeError (a misspelled hook would otherwise be dropped and leave the caller's test vacuous)."""
+        unknown = set(debug) - {"tau_mult", "drop_best", "flags"}
+        if unknown:
+            raise TypeError(f"ShardIndex.search() got unexpected keyword argument(s): {', '.join(sorted(unknown))}")
         q = queries_f16
         assert q.is_cuda and q.dtype == torch.float16 and q.dim() == 2 and q.shape[1] == self.dim and q.is_contiguous()
         nq = q.shape[0]
@@ -169,15 +173,24 @@ class ShardIndex:
         self._last_ws = ws
         if _opt.flags & (_lib.TOPK_SCAN_ONLY | _lib.TOPK_TAIL_ONLY):
             return scores, ids
-        if use_i8 and self._adaptive and nq <= 1024 and (self._i8_searches < 4 or self._i8_searches % 64 == 0):
+        # the counters describe the int8 pass only where it ran: a batch above the crossover took the fp16 pass, whose counters count
+        # uncertified selections, not overflowing candidate lists (the library decides per call the same way, search.hip use_i8)
+        ran_i8 = use_i8 and nq <= self._i8_nq_limit()
+        if ran_i8 and self._adaptive and (self._i8_searches < 4 or self._i8_searches % 64 == 0):
             flagged, _ = self.certificate_stats()
             if flagged * 4 > nq:
                 import sys
                 print(f"[arx] int8 pre-filter switched off for this index: {flagged} of {nq} queries overflowed their candidate lists "
                       f"(rows on which the int8 bound is too slack); the fp16 pass answers from here on", file=sys.stderr)
                 self.prefilter_disabled = True
-        self._i8_searches += 1 if use_i8 else 0
+        self._i8_searches += 1 if ran_i8 else 0
         return scores, ids
+
+    def _i8_nq_limit(self) -> int:
+        """The largest query batch the int8 pass takes under this index's policy (`i8_max_queries`; None = the library default, 1 024)."""
+        if self.i8_max_queries is None:
+            return 1024
+        return max(0, min(int(self.i8_max_queries), 1024))
 
     def certificate_stats(self, ws: Optional[torch.Tensor] = None) -> Tuple[int, int]:
         """(queries whose first selection could not be certified, extra 64-row groups rescored for them) of the LAST `search`

@@ -79,3 +79,79 @@ def make_chunk_tree(root, n_files=12, chunks_per_file=5, seed=0, words=None):
         (sub / f"{pid}.json").write_text(json.dumps({"paper_id": pid, "chunks": chunks}))
         all_chunks.extend(chunks)
     return all_chunks
+
+
+# ---- exact top-k search checked against float64 -------------------------------------------------------------------------------------
+# The certificate's tolerance (csrc/search.hip topk_search_impl, tau_scale) is the sum of two per-pass rounding budgets, both relative to
+# |q|_2 |c|_2 >= sum |q_i c_i| (csrc/search_tail.h, rescore_kernel step 5), with u = 2^-24:
+#   pass A (f16 MFMA, f32 accumulation; "8 roundings per 32-deep MFMA step"):                  A(D) = 0.25 D u
+#   pass B (exact_row_score: f32 FMA chains of D/16 terms, their sum and a 3-step butterfly):  B(D) = (D/16 + 4) u
+# tau = (A(D) + B(D)) |q| max|c| = (0.3125 D + 4) u |q| max|c|.
+U24 = 2.0 ** -24
+
+
+def pass_a_budget(dim):
+    """A(D): |pass-A score - q.c| <= A(D) |q| |c| for every (query, row)."""
+    return 0.25 * dim * U24
+
+
+def pass_b_budget(dim):
+    """B(D): |pass-B score - q.c| <= B(D) |q| |c| for every (query, row)."""
+    return (dim / 16 + 4) * U24
+
+
+def scores_fp64(q, c):
+    """[nq, n] float64 dot products of the fp16 values (device tensors in, device tensor out), in row chunks whose product stays at or
+    below 2^28 elements: torch's matmul on this stack has written zeros past element 2^29 of a larger result (tools/search_soak.py)."""
+    import torch
+    q64 = q.double()
+    step = max(1, (1 << 28) // max(1, q.shape[0]))
+    return torch.cat([q64 @ c[a:a + step].double().T for a in range(0, c.shape[0], step)], dim=1)
+
+
+def check_topk_fp64(c, q, s, i, k, idx_base=0, e=None, sample_rows=4, what=None):
+    """Assert that (s, i) = search(q, k) over the fp16 rows `c` (device tensors) is an exact top-k by the certificate's own arithmetic.
+    e = q.c in float64 (scores_fp64; a few rows cross-checked against numpy float64 on the host).  Per query:
+      - ids are distinct and inside [idx_base, idx_base + n); the (-inf, -1) padding appears exactly when k > n;
+      - pass B: every returned score s_j satisfies |s_j - e(q, id_j)| <= B(D) |q| |c_j|;
+      - completeness: the answer is the top-k of the pass-B scores (the certificate's claim), so a row r left out has
+        s_r <= min_j s_j, hence e_r - B(D) |q| |c_r| <= min_j (e_j + B(D) |q| |c_j|)   (<= min_j e_j + 2 B(D) |q| max|c|);
+      - scores are non-increasing, and rows whose reported scores are bit-equal come in ascending id order.
+    Returns e."""
+    import torch
+    n, D = c.shape
+    nq = q.shape[0]
+    if e is None:
+        e = scores_fp64(q, c)
+    if sample_rows:                                              # the device's float64 product against numpy's, on sampled queries and rows
+        rows = torch.linspace(0, nq - 1, min(nq, sample_rows)).long()
+        cols = torch.linspace(0, n - 1, min(n, 2048)).long()
+        ref = q[rows].cpu().numpy().astype(np.float64) @ c[cols.to(c.device)].cpu().numpy().astype(np.float64).T
+        got = e[rows][:, cols.to(e.device)].cpu().numpy()
+        assert np.abs(got - ref).max() <= 1e-13 * max(1e-30, float(np.abs(ref).max())), (what, "float64 matmul")
+    B = pass_b_budget(D)
+    qn = q.double().norm(dim=1)                                                  # [nq]
+    cn = c.double().norm(dim=1)                                                  # [n]
+    kk = min(k, n)
+    assert s.shape == (nq, k) and i.shape == (nq, k), what
+    if k > n:
+        assert (i[:, n:] == -1).all() and torch.isinf(s[:, n:]).all() and (s[:, n:] < 0).all(), (what, "padding")
+    ids = i[:, :kk] - idx_base
+    assert ((ids >= 0) & (ids < n)).all(), (what, "ids out of range")
+    srt = ids.sort(dim=1).values
+    assert (srt[:, 1:] != srt[:, :-1]).all(), (what, "duplicate ids")
+    sk = s[:, :kk].double()
+    assert torch.isfinite(sk).all(), (what, "non-finite score")
+    ej = e.gather(1, ids)
+    bj = B * qn[:, None] * cn[ids] * (1 + 1e-3)                                  # (1e-3: the second-order terms of gamma_n)
+    err = (sk - ej).abs()
+    assert (err <= bj).all(), (what, "pass-B score outside B(D)", ((err - bj) / (U24 * qn[:, None] * cn[ids]).clamp_min(1e-300)).max().item())
+    if n > kk:
+        lo = e - B * (1 + 1e-3) * qn[:, None] * cn[None, :]
+        lo.scatter_(1, ids, float("-inf"))
+        worst = lo.max(dim=1).values - (ej + bj).min(dim=1).values
+        assert (worst <= 0).all(), (what, "a row left out beats the k-th", worst.max().item(), int(worst.argmax()))
+    assert (s[:, :kk - 1] >= s[:, 1:kk]).all(), (what, "order")
+    eq = s[:, :kk - 1] == s[:, 1:kk]
+    assert (ids[:, :-1][eq] < ids[:, 1:][eq]).all(), (what, "tie order")
+    return e

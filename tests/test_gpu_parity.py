@@ -1262,26 +1262,28 @@ def test_collection_query_shape_and_ranking(hip, tmp_path):
 
 @pytest.mark.parametrize("variant", [89, 9, 8, 13])
 def test_linear_layer_variants_vs_fp32(hip, variant):
-    """arx_gemm_bf16 (the linear layer of the path) against an fp32 matmul on the same bf16-rounded operands:
-    every main-loop schedule kept in the tree, every epilogue mode it supports, ragged M/N (masked edge tiles)."""
+    """arx_gemm_bf16 (the linear layer of the path) against an fp64 matmul on the same bf16-rounded operands:
+    every main-loop schedule kept in the tree, every epilogue mode it supports, ragged M/N (masked edge tiles), and K = 192 / 320 / 448:
+    an odd number of 64-wide k-tiles (> 1) in the 4-phase loop that pass A of the search shares."""
     lib = hip.load()
     g = torch.Generator(device="cuda"); g.manual_seed(variant)
     st = torch.cuda.current_stream().cuda_stream
-    for (M, N, K) in ((230, 192, 64), (517, 64, 128), (1000, 384, 384), (300, 1536, 384), (777, 768, 768), (2048, 2304, 768)):
+    for (M, N, K) in ((230, 192, 64), (517, 64, 128), (1000, 384, 384), (300, 1536, 384), (777, 768, 768), (2048, 2304, 768),
+                      (300, 256, 192), (777, 768, 320), (517, 384, 448)):
         A = torch.randn((M, K), device="cuda", generator=g).to(torch.bfloat16)
         W = (torch.randn((N, K), device="cuda", generator=g) * 0.05).to(torch.bfloat16)
         b = torch.randn((N,), device="cuda", generator=g)
         R = torch.randn((M, N), device="cuda", generator=g).to(torch.bfloat16)
         for mode in (0, 1, 2):
-            want = A.float() @ W.float().T + b
+            want = A.double() @ W.double().T + b.double()
             if mode == 1:
                 want = torch.nn.functional.gelu(want)
             if mode == 2:
-                want = want + R.float()
+                want = want + R.double()
             out = torch.full((M, N), float("nan"), device="cuda", dtype=torch.bfloat16)
             hip.check(lib.arx_gemm_bf16(A.data_ptr(), W.data_ptr(), b.data_ptr(), R.data_ptr(), out.data_ptr(), M, N, K, mode,
                                         variant, st), "arx_gemm_bf16")
-            err = (out.float() - want).abs().max().item()
+            err = (out.double() - want).abs().max().item()
             assert err < 0.02 * max(1.0, want.abs().max().item()), (variant, M, N, K, mode, err)
 
 
@@ -1398,13 +1400,14 @@ def test_alternative_schedules_agree(hip, golden_dir, env, monkeypatch):
 
 def test_small_batch_gemm_vs_fp32_and_tile_kernels(hip):
     """csrc/gemm_small.h alone (arx_gemm_bf16 variant 70): split-K wave tiles + row-wise epilogue, at every (N, K) the encoders use,
-    at row counts around its 16-row tile (1, 12, 16, 17, 100, 256), modes bias / bias+GELU / bias+residual, against fp32 torch on the
-    same bf16 operands and against the 256 x 256-tile kernels (one bf16 ulp: another summation order)."""
+    at row counts around its 16-row tile (1, 12, 16, 17, 100, 256), modes bias / bias+GELU / bias+residual, against an fp64 matmul of
+    the same bf16 operands and against the 256 x 256-tile kernels (one bf16 ulp: another summation order); K = 192 / 320 / 448:
+    odd numbers of 64-wide k-tiles."""
     lib = hip.load()
     g = torch.Generator(device="cuda"); g.manual_seed(5)
     st = torch.cuda.current_stream().cuda_stream
     for (N, K) in ((2304, 768), (768, 768), (3072, 768), (768, 3072), (1152, 384), (384, 384), (1536, 384), (384, 1536),
-                   (3072, 1024), (1024, 1024), (4096, 1024), (1024, 4096), (192, 64), (128, 64), (64, 128)):
+                   (3072, 1024), (1024, 1024), (4096, 1024), (1024, 4096), (192, 64), (128, 64), (64, 128), (384, 192), (768, 320), (256, 448)):
         W = (torch.randn((N, K), device="cuda", generator=g) * 0.05).to(torch.bfloat16)
         b = torch.randn((N,), device="cuda", generator=g)
         for M in (1, 12, 16, 17, 100, 256):
@@ -1416,14 +1419,14 @@ def test_small_batch_gemm_vs_fp32_and_tile_kernels(hip):
                     out = torch.full((M, N), float("nan"), device="cuda", dtype=torch.bfloat16)
                     hip.check(lib.arx_gemm_bf16(A.data_ptr(), W.data_ptr(), b.data_ptr(), R.data_ptr(), out.data_ptr(), M, N, K, mode,
                                                 variant, st), "arx_gemm_bf16")
-                    outs.append(out.float())
-                want = A.float() @ W.float().T + b
-                want = torch.nn.functional.gelu(want) if mode == 1 else want + R.float() if mode == 2 else want
+                    outs.append(out.double())
+                want = A.double() @ W.double().T + b.double()
+                want = torch.nn.functional.gelu(want) if mode == 1 else want + R.double() if mode == 2 else want
                 tol = 0.01 * max(1.0, want.abs().max().item())
                 assert (outs[0] - want).abs().max().item() < tol, (N, K, M, mode)
                 assert (outs[0] - outs[1]).abs().max().item() < tol, (N, K, M, mode)
     # the medium half of the low-latency schedule (variant 71: 128 x 128 tiles) at row counts between its bounds, ragged edges included
-    for (N, K) in ((2304, 768), (768, 3072), (1152, 384), (1024, 4096), (192, 64)):
+    for (N, K) in ((2304, 768), (768, 3072), (1152, 384), (1024, 4096), (192, 64), (384, 192), (768, 320), (256, 448)):
         W = (torch.randn((N, K), device="cuda", generator=g) * 0.05).to(torch.bfloat16)
         b = torch.randn((N,), device="cuda", generator=g)
         for M in (257, 1000, 4097):
@@ -1432,9 +1435,9 @@ def test_small_batch_gemm_vs_fp32_and_tile_kernels(hip):
             for mode in (0, 1, 2):
                 out = torch.full((M, N), float("nan"), device="cuda", dtype=torch.bfloat16)
                 hip.check(lib.arx_gemm_bf16(A.data_ptr(), W.data_ptr(), b.data_ptr(), R.data_ptr(), out.data_ptr(), M, N, K, mode, 71, st), "arx_gemm_bf16")
-                want = A.float() @ W.float().T + b
-                want = torch.nn.functional.gelu(want) if mode == 1 else want + R.float() if mode == 2 else want
-                assert (out.float() - want).abs().max().item() < 0.01 * max(1.0, want.abs().max().item()), (N, K, M, mode)
+                want = A.double() @ W.double().T + b.double()
+                want = torch.nn.functional.gelu(want) if mode == 1 else want + R.double() if mode == 2 else want
+                assert (out.double() - want).abs().max().item() < 0.01 * max(1.0, want.abs().max().item()), (N, K, M, mode)
     N, K, M, mode = 384, 1536, 256, 2
     W = (torch.randn((N, K), device="cuda", generator=g) * 0.05).to(torch.bfloat16); b = torch.randn((N,), device="cuda", generator=g)
     A = torch.randn((M, K), device="cuda", generator=g).to(torch.bfloat16); R = torch.randn((M, N), device="cuda", generator=g).to(torch.bfloat16)

@@ -242,10 +242,10 @@ class HipEncoder:
         out[order] = dev_out.cpu().numpy()
         return out
 
-    def tap_hidden(self, ids: np.ndarray, lens: np.ndarray, layer: int) -> np.ndarray:
-        """Parity tap: packed hidden state [sum(lens), H] f32 after `layer` (0 = embeddings)."""
+    def tap_hidden(self, ids: np.ndarray, lens: np.ndarray, layer: int, low_latency: bool = False) -> np.ndarray:
+        """Parity tap: packed hidden state [sum(lens), H] f32 after `layer` (0 = embeddings), from a forward of the given schedule."""
         _lib.check(self.lib.arx_encoder_set_tap(self._handle, layer), "arx_encoder_set_tap")
-        self.encode_tokens(ids, lens)
+        self.encode_tokens(ids, lens, low_latency=low_latency)
         T = int(np.asarray(lens).sum())
         dst = torch.empty((T, self.cfg.hidden), dtype=torch.float32, device=self.device)
         _lib.check(self.lib.arx_encoder_debug_hidden(self._handle, layer, dst.data_ptr(), T,

@@ -155,3 +155,183 @@ def check_topk_fp64(c, q, s, i, k, idx_base=0, e=None, sample_rows=4, what=None)
     eq = s[:, :kk - 1] == s[:, 1:kk]
     assert (ids[:, :-1][eq] < ids[:, 1:][eq]).all(), (what, "tie order")
     return e
+
+
+# ---- encoder checked against float64 -------------------------------------------------------------------------------------------------
+# References restate oracle/encoder_oracle.py in float64 (torch, on whatever device the inputs live) on the values the kernels read: bf16
+# activations and matrices, fp32 biases, LayerNorm parameters and bias tables.  The optional `fault` of each reference computes a nearby
+# WRONG operation, so that a test can show its budget would catch that mistake (the analogue of the search tolerance test).
+U8 = 2.0 ** -8
+ATTN_FAULTS = ("extra_key", "missing_key", "bias_shift", "bias_transpose", "query_shift")
+
+
+def _t64(a, device=None):
+    import torch
+    t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
+    return t.to(device=device if device is not None else t.device, dtype=torch.float64)
+
+
+def bias_table_fp64(sd, cfg, S, device="cpu"):
+    """MPNet: [heads, 2S+1] float64 Toeplitz table, entry (key - query) + S, from the oracle's bucket function (wide enough for one key
+    past S and a shift by one); BERT: None."""
+    if cfg.arch != C.ARCH_MPNET:
+        return None
+    d = np.arange(-S, S + 1)
+    bucket = EO.relative_position_bucket(d, cfg.rel_buckets, cfg.rel_max_distance)
+    return _t64(sd["encoder.relative_attention_bias.weight"][bucket].T, device)
+
+
+def attention_fp64(qkv, lens, cfg, sd, fault=None):
+    """Packed qkv [T, 3H] (bf16 or wider; device tensor) -> (ctx [T, H], spv [T, H], serr [T, heads]), all float64:
+      ctx  = softmax(q k^T / sqrt(dh) + bias[key - query], keys < len) v per (sequence, head), the bias from the oracle's bucket function;
+      spv  = sum_j p_ij |v_j| per output element (the scale of the kernel's P and accumulation roundings, see attention_budget);
+      serr = a bound on the kernel's fp32 score error in base-2 units per (row, head), see attention_budget.
+    fault: one of ATTN_FAULTS (a mistake the budget must expose): "extra_key" counts the clamped re-read of row len-1 as key len,
+    "missing_key" drops key len-1, "bias_shift" reads bias[key - query + 1], "bias_transpose" reads bias[query - key], "query_shift"
+    takes query row i+1 (clamped) for output row i."""
+    import torch
+    assert fault in (None,) + ATTN_FAULTS, fault
+    H, nh = cfg.hidden, cfg.heads
+    dh = H // nh
+    x = _t64(qkv)
+    dev = x.device
+    lens = np.asarray(lens, np.int64)
+    cu = np.concatenate([[0], np.cumsum(lens)])
+    S = int(max(lens.max(), 1)) + 1
+    tbl = bias_table_fp64(sd, cfg, S, dev)
+    if tbl is not None and fault == "bias_transpose":
+        tbl = tbl.flip(1)                                        # entry d + S now holds bias[-d]
+    ctx = torch.zeros((int(cu[-1]), H), dtype=torch.float64, device=dev)
+    spv = torch.zeros_like(ctx)
+    serr = torch.zeros((int(cu[-1]), nh), dtype=torch.float64, device=dev)
+    l2e = 1.0 / np.log(2.0)
+    for b in range(len(lens)):
+        L = int(lens[b])
+        if L == 0:
+            continue
+        seg = x[cu[b]:cu[b + 1]].view(L, 3, nh, dh).permute(1, 2, 0, 3)        # [3, nh, L, dh]
+        q, k, v = seg[0], seg[1], seg[2]
+        nk = L
+        if fault == "query_shift":
+            q = q[:, torch.clamp(torch.arange(1, L + 1, device=dev), max=L - 1)]
+        if fault == "extra_key":
+            k = torch.cat([k, k[:, L - 1:]], 1); v = torch.cat([v, v[:, L - 1:]], 1); nk = L + 1
+        if fault == "missing_key" and L > 1:
+            k = k[:, :L - 1]; v = v[:, :L - 1]; nk = L - 1
+        raw = q @ k.transpose(1, 2)                                               # [nh, L, nk]
+        sc = raw / np.sqrt(dh)
+        bias = 0.0
+        if tbl is not None:
+            rel = torch.arange(nk, device=dev)[None, :] - torch.arange(L, device=dev)[:, None] + S
+            if fault == "bias_shift":
+                rel = rel + 1
+            bias = tbl[:, rel]                                                    # [nh, L, nk]
+            sc = sc + bias
+        p = torch.softmax(sc, dim=-1)
+        ctx[cu[b]:cu[b + 1]] = (p @ v).transpose(0, 1).reshape(L, H)
+        spv[cu[b]:cu[b + 1]] = (p @ v.abs()).transpose(0, 1).reshape(L, H)
+        # per key: the fp32 MFMA dot product (dh products, exact, summed in fp32), fma(acc, scale_log2e, bias * log2e) with both
+        # constants rounded to fp32, and the score itself rounded -- in base-2 units
+        dot_err = dh * U24 * (q.abs() @ k.abs().transpose(1, 2)) + 3 * U24 * raw.abs()
+        e = l2e / np.sqrt(dh) * dot_err + 3 * U24 * l2e * (bias.abs() if tbl is not None else 0.0) + U24 * (sc.abs() * l2e)
+        serr[cu[b]:cu[b + 1]] = e.max(dim=-1).values.transpose(0, 1)
+    return ctx, spv, serr
+
+
+def attention_budget(ref, spv, serr, lens, cfg):
+    """Per-element bound on |kernel ctx - ref| for the fused attention kernels (csrc/encoder_kernels.h), float64 [T, H].  bf16 keeps 8
+    significant bits, so round-to-nearest moves a value by at most 2^-8 of itself.
+      score  s~_j = s_j + d_j with |d_j| <= E (serr, base-2 units; plus 2 ulps of exp2, 2^-23 / ln 2) -> each weight exp2(s~_j) is off by a
+             factor within 2^(+-E): the normalised weights move by at most 2 (2^E - 1) relative, so |d ctx| <= 2 ln2 E (1 + ln2 E) spv;
+      P      rounded to bf16 BEFORE both the PV MFMA and the row sum (an MFMA with ones), so the output is a weighted mean whose weights
+             are off by (1 + e_j), |e_j| <= 2^-8: |d ctx| = |sum_j p_j (e_j - mean e) v_j| / (1 + mean e) <= 2 * 2^-8 / (1 - 2^-8) spv;
+      sums   PV and the row sum accumulate L terms in fp32 (L 2^-24 each), the lazy rescale and the final division add a few roundings:
+             (2 L + L / 16 + 4) 2^-24 spv;
+      output rounded to bf16: 2^-8 (|ref| + the terms above).
+    Together: a 2^-8 spv + 2^-8 |ref| + (score term), a = 2 (1 + 2^-7) + (2 L + L / 16 + 4) 2^-16, plus second-order terms."""
+    import torch
+    nh = cfg.heads
+    dh = cfg.hidden // nh
+    lens = np.asarray(lens, np.int64)
+    L = torch.from_numpy(np.repeat(lens, lens).astype(np.float64)).to(ref.device)[:, None]
+    a = 2 * (1 + 2.0 ** -7) + (2 * L + L / 16 + 4) * 2.0 ** -16
+    E = serr.repeat_interleave(dh, dim=1) + 2 * U24 / np.log(2.0)
+    ln2e = np.log(2.0) * E
+    inner = a * U8 * spv + 2 * ln2e * (1 + ln2e) * spv
+    return (U8 * (ref.abs() + inner) + inner) * (1 + 1e-6)
+
+
+def _bf16_64(w, device):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(w, np.float32)).to(torch.bfloat16).to(device=device, dtype=torch.float64)
+
+
+def layer_norm_fp64(x, g, b, eps):
+    mu = x.mean(-1, keepdim=True)
+    var = ((x - mu) ** 2).mean(-1, keepdim=True)
+    return (x - mu) / (var + eps).sqrt() * g + b
+
+
+def embed_ln_fp64(sd, cfg, ids, lens, device="cpu", fault=None):
+    """ids [B, S] right-padded, lens [B] -> packed [sum(lens), H] float64: LN(word[id] + pos[p] (+ token_type[0] for BERT)), MPNet
+    position ids from the count of non-pad tokens so far (pad-aware, oracle mpnet_position_ids), BERT p = 0, 1, ..., both clamped to
+    max_pos - 1.
+    fault: "pos_off_by_one" (MPNet ids one too high), "no_token_type" (BERT without the token-type row)."""
+    import torch
+    ids = np.asarray(ids, np.int64)
+    lens = np.asarray(lens, np.int64)
+    keep = np.arange(ids.shape[1])[None] < lens[:, None]
+    if cfg.arch == C.ARCH_MPNET:
+        pos = EO.mpnet_position_ids(ids, cfg.pad_id) + (1 if fault == "pos_off_by_one" else 0)
+    else:
+        pos = np.broadcast_to(np.arange(ids.shape[1])[None], ids.shape)
+    pos = np.minimum(pos, cfg.max_pos - 1)                      # the kernel clamps as well
+    e = _t64(sd["embeddings.word_embeddings.weight"][ids[keep]], device) + _t64(sd["embeddings.position_embeddings.weight"][pos[keep]], device)
+    if cfg.arch != C.ARCH_MPNET and fault != "no_token_type":
+        e = e + _t64(sd["embeddings.token_type_embeddings.weight"][0], device)
+    return layer_norm_fp64(e, _t64(sd["embeddings.LayerNorm.weight"], device), _t64(sd["embeddings.LayerNorm.bias"], device), cfg.ln_eps)
+
+
+def layer_fp64(sd, cfg, i, x, lens, fault=None):
+    """Encoder layer i on packed hidden rows x [T, H] (device tensor) -> float64 [T, H]: matrices rounded to bf16 as HipEncoder uploads
+    them, biases and LayerNorm parameters fp32, attention by attention_fp64, exact erf GELU, all arithmetic float64.
+    fault: "prev_ln" (both LayerNorms take the previous layer's LN2 gamma / beta; layer 0 the embedding LayerNorm's),
+    "no_oproj_residual" (y1 = ctx Wo^T + b without + x)."""
+    import torch
+    from arxiv_rag_amd.weights import layer_keys
+    dev = x.device
+    x = _t64(x)
+    k = layer_keys(cfg, i)
+    f32 = lambda n: _t64(sd[n], dev)
+    lin = lambda a, n: a @ _bf16_64(sd[n + ".weight"], dev).T + f32(n + ".bias")
+    wqkv = np.concatenate([sd[k[n] + ".weight"] for n in ("q", "k", "v")], 0)
+    bqkv = np.concatenate([sd[k[n] + ".bias"] for n in ("q", "k", "v")], 0)
+    qkv = x @ _bf16_64(wqkv, dev).T + _t64(bqkv, dev)
+    ctx = attention_fp64(qkv, lens, cfg, sd)[0]
+    if fault == "prev_ln":
+        prev = layer_keys(cfg, i - 1)["ln2"] if i > 0 else "embeddings.LayerNorm"
+        ln1 = ln2 = prev
+    else:
+        ln1, ln2 = k["ln1"], k["ln2"]
+    y1 = lin(ctx, k["o"]) + (0.0 if fault == "no_oproj_residual" else x)
+    a = layer_norm_fp64(y1, f32(ln1 + ".weight"), f32(ln1 + ".bias"), cfg.ln_eps)
+    h = torch.nn.functional.gelu(lin(a, k["fc1"]))
+    return layer_norm_fp64(lin(h, k["fc2"]) + a, f32(ln2 + ".weight"), f32(ln2 + ".bias"), cfg.ln_eps)
+
+
+def pool_fp64(x, lens, cfg, fault=None):
+    """Packed last hidden rows x [T, H] -> (pooled [B, H], mean |x| over the pooled rows [B, H]) float64: masked mean or CLS row;
+    an empty sequence pools to zeros.  fault "count_pad_row": the mean divides by len + 1."""
+    import torch
+    x = _t64(x)
+    lens = np.asarray(lens, np.int64)
+    cu = np.concatenate([[0], np.cumsum(lens)])
+    out = torch.zeros((len(lens), x.shape[1]), dtype=torch.float64, device=x.device)
+    mag = torch.zeros_like(out)
+    for b, L in enumerate(lens):
+        if L == 0:
+            continue
+        rows = x[cu[b]:cu[b] + (1 if cfg.pool == C.POOL_CLS else L)]
+        out[b] = rows.sum(0) / (rows.shape[0] + (1 if fault == "count_pad_row" else 0))
+        mag[b] = rows.abs().mean(0)
+    return out, mag

@@ -41,6 +41,16 @@ class TopkOptionsC(C.Structure):
         self.struct_bytes = C.sizeof(TopkOptionsC)
 
 
+class PairHeadC(C.Structure):
+    """arx_pair_head (include/arx.h): the cross-encoder head's device weights."""
+    _fields_ = [("struct_bytes", C.c_int32), ("n_labels", C.c_int32)] \
+               + [(n, C.c_void_p) for n in ("type_emb", "pooler_w", "pooler_b", "cls_w", "cls_b")]
+
+    def __init__(self, **kw):
+        super().__init__(**kw)
+        self.struct_bytes = C.sizeof(PairHeadC)
+
+
 TOPK_NO_PERSISTENT, TOPK_SCAN_ONLY, TOPK_TAIL_ONLY, TOPK_NO_SINGLE_ROW_TAIL, TOPK_I8_CENTRE_QUERY = 1, 2, 4, 8, 16
 
 
@@ -60,6 +70,12 @@ EXPORTS = {
     "arx_encoder_set_tap": (C.c_int32, [C.c_void_p, C.c_int32]),
     "arx_encoder_set_low_latency": (C.c_int32, [C.c_void_p, C.c_int32]),
     "arx_encoder_debug_hidden": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "arx_encoder_set_pair_head": (C.c_int32, [C.c_void_p, C.POINTER(PairHeadC)]),
+    "arx_encoder_score_pairs": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                            C.c_void_p, C.c_int64, C.c_void_p]),
+    "arx_encoder_debug_cls": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "arx_pair_head_forward": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.POINTER(PairHeadC), C.c_void_p, C.c_int64,
+                                          C.c_void_p]),
     "arx_topk_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
     "arx_topk_search": (C.c_int32, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                     C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),

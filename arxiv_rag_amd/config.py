@@ -9,7 +9,7 @@ local-directory loads agree on one description.
 from __future__ import annotations
 
 import json
-from dataclasses import dataclass, asdict
+from dataclasses import dataclass, asdict, replace
 from pathlib import Path
 
 ARCH_MPNET = 0   # relative-position bias, pad-aware position ids, <s>=0 <pad>=1 </s>=2
@@ -97,3 +97,57 @@ def config_from_hf_dir(path: str | Path) -> EncoderConfig:
         ln_eps=cfg.get("layer_norm_eps", 1e-12), pool=pool, max_seq_length=msl, pad_id=pad,
         rel_buckets=cfg.get("relative_attention_num_buckets", 32),
     )
+
+
+# ---- cross-encoders (reranking) ---------------------------------------------------------------------
+ACT_SIGMOID = "sigmoid"
+ACT_IDENTITY = "identity"
+
+
+@dataclass(frozen=True)
+class CrossEncoderConfig:
+    """A BertForSequenceClassification reranker: the encoder (CLS pooled) plus pooler + classifier with `n_labels` outputs, and the
+    activation sentence-transformers' CrossEncoder applies to the logits by default."""
+    encoder: EncoderConfig
+    n_labels: int = 1
+    activation: str = ACT_SIGMOID
+
+    def to_json(self) -> str:
+        return json.dumps({"encoder": asdict(self.encoder), "n_labels": self.n_labels, "activation": self.activation})
+
+
+# cross-encoder/ms-marco-MiniLM-L-6-v2: BertForSequenceClassification 6L/384 (12 heads of 32), one label, sigmoid, max_length 512
+MS_MARCO_MINILM_L6 = CrossEncoderConfig(EncoderConfig(ARCH_BERT, 30522, 384, 6, 12, 1536, 512, 1e-12, POOL_CLS, 512, 0), 1, ACT_SIGMOID)
+
+CROSS_PRESETS = {
+    "cross-encoder/ms-marco-MiniLM-L-6-v2": MS_MARCO_MINILM_L6,
+    "ms-marco-MiniLM-L-6-v2": MS_MARCO_MINILM_L6,
+}
+
+
+def default_activation(n_labels: int) -> str:
+    """CrossEncoder's rule: sigmoid for a single label, identity otherwise."""
+    return ACT_SIGMOID if n_labels == 1 else ACT_IDENTITY
+
+
+def parse_activation(name: str) -> str:
+    """'torch.nn.modules.activation.Sigmoid' / 'torch.nn.modules.linear.Identity' (the dotted class paths sentence-transformers
+    records) or a bare 'sigmoid' / 'identity' -> ACT_*."""
+    short = str(name).rsplit(".", 1)[-1].lower()
+    if short in (ACT_SIGMOID, ACT_IDENTITY):
+        return short
+    raise ValueError(f"unsupported cross-encoder activation {name!r} (sigmoid or identity)")
+
+
+def cross_config_from_hf_dir(path: str | Path) -> CrossEncoderConfig:
+    """Read a local HF BertForSequenceClassification directory (config.json): the encoder shape with CLS pooling, num_labels from
+    id2label, the activation from `sbert_ce_default_activation_function` or `sentence_transformers.activation_fn`."""
+    p = Path(path)
+    cfg = json.loads((p / "config.json").read_text())
+    if "BertForSequenceClassification" not in (cfg.get("architectures") or []):
+        raise ValueError(f"{p/'config.json'}: architectures {cfg.get('architectures')} lack BertForSequenceClassification")
+    enc = replace(config_from_hf_dir(p), pool=POOL_CLS)
+    n_labels = len(cfg["id2label"]) if cfg.get("id2label") else int(cfg.get("num_labels", 1))
+    act = cfg.get("sbert_ce_default_activation_function") or (cfg.get("sentence_transformers") or {}).get("activation_fn")
+    act = parse_activation(act) if act else default_activation(n_labels)
+    return CrossEncoderConfig(enc, n_labels, act)

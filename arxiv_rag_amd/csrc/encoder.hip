@@ -53,6 +53,10 @@ struct arx_encoder {
     int attn_variant = 1;
     int attn_dev_word = 0;                        // dev: probes of attention_tr_kernel (0 in the product path)
     unsigned long long* attn_stamps = nullptr;    // dev: per-block time stamps
+    // cross-encoder head (arx_encoder_set_pair_head): caller-owned device weights + the handle's [max_seqs, H] f32 CLS scratch
+    arx_pair_head pair{};
+    int has_pair = 0;
+    float* cls_ws = nullptr;
 };
 
 struct WsLayout {
@@ -218,6 +222,7 @@ extern "C" void arx_encoder_destroy(arx_encoder* h) {
     if (h->tap) (void)hipFree(h->tap);
     if (h->fold_ws) (void)hipFree(h->fold_ws);
     if (h->small_ws) (void)hipFree(h->small_ws);
+    if (h->cls_ws) (void)hipFree(h->cls_ws);
     delete h;
 }
 
@@ -563,10 +568,11 @@ static void launch_ln_finalize(int T, int nparts, const float* ps, const float* 
 }
 
 // ---- forward ------------------------------------------------------------------------------------
-extern "C" int32_t arx_encoder_forward(arx_encoder* h, const int32_t* ids, int32_t seq_stride, const int32_t* lens,
-                                       int32_t n_seqs, int32_t max_len, int32_t total_tokens, float* out_f32,
-                                       int64_t out_stride, void* out_f16, int64_t out16_stride, int32_t normalize,
-                                       void* stream) {
+// seg_b != null (sentence pairs; BERT with a pair head only): token s of sequence b takes token-type row 1 when s >= seg_b[b]
+static int32_t encoder_run(arx_encoder* h, const int32_t* ids, int32_t seq_stride, const int32_t* lens, const int32_t* seg_b,
+                           int32_t n_seqs, int32_t max_len, int32_t total_tokens, float* out_f32,
+                           int64_t out_stride, void* out_f16, int64_t out16_stride, int32_t normalize,
+                           void* stream) {
     ARX_REQUIRE(h && ids && lens, "null handle/ids/lens");
     ARX_REQUIRE(out_f32 || out_f16, "no output buffer");
     ARX_REQUIRE(n_seqs > 0 && max_len > 0 && max_len <= 512, "n_seqs=%d max_len=%d (max_len must be in 1..512)", n_seqs, max_len);
@@ -591,6 +597,10 @@ extern "C" int32_t arx_encoder_forward(arx_encoder* h, const int32_t* ids, int32
         if (c.arch == ARX_ARCH_MPNET)
             embed_ln_kernel<ARX_ARCH_MPNET><<<grid, 256, 0, st>>>(ids, seq_stride, lens, h->cu, h->w.word_emb, h->w.pos_emb, nullptr,
                                                                   h->w.emb_ln_g, h->w.emb_ln_b, h->x, H, c.vocab_size, c.max_pos, c.pad_id, c.ln_eps);
+        else if (seg_b)
+            embed_ln_kernel<ARX_ARCH_BERT, true><<<grid, 256, 0, st>>>(ids, seq_stride, lens, h->cu, h->w.word_emb, h->w.pos_emb,
+                                                                       h->pair.type_emb, h->w.emb_ln_g, h->w.emb_ln_b, h->x, H,
+                                                                       c.vocab_size, c.max_pos, c.pad_id, c.ln_eps, seg_b);
         else
             embed_ln_kernel<ARX_ARCH_BERT><<<grid, 256, 0, st>>>(ids, seq_stride, lens, h->cu, h->w.word_emb, h->w.pos_emb, h->w.type_emb,
                                                                  h->w.emb_ln_g, h->w.emb_ln_b, h->x, H, c.vocab_size, c.max_pos, c.pad_id, c.ln_eps);
@@ -691,6 +701,77 @@ extern "C" int32_t arx_encoder_forward(arx_encoder* h, const int32_t* ids, int32
         ARX_HIP_CHECK(hipGetLastError());
     }
     return ARX_OK;
+}
+
+extern "C" int32_t arx_encoder_forward(arx_encoder* h, const int32_t* ids, int32_t seq_stride, const int32_t* lens,
+                                       int32_t n_seqs, int32_t max_len, int32_t total_tokens, float* out_f32,
+                                       int64_t out_stride, void* out_f16, int64_t out16_stride, int32_t normalize,
+                                       void* stream) {
+    return encoder_run(h, ids, seq_stride, lens, nullptr, n_seqs, max_len, total_tokens, out_f32, out_stride, out_f16, out16_stride,
+                       normalize, stream);
+}
+
+// ---- cross-encoder head -------------------------------------------------------------------------
+static int check_pair_head(const arx_pair_head* p, int hidden) {
+    ARX_REQUIRE(p, "null pair head");
+    ARX_REQUIRE(p->struct_bytes >= (int32_t)sizeof(arx_pair_head), "arx_pair_head.struct_bytes=%d < %d", p->struct_bytes,
+                (int)sizeof(arx_pair_head));
+    ARX_REQUIRE(p->n_labels >= 1 && p->n_labels <= 16, "n_labels=%d must be in 1..16", p->n_labels);
+    ARX_REQUIRE(p->pooler_w && p->pooler_b && p->cls_w && p->cls_b, "pair head: missing pooler / classifier weights");
+    ARX_REQUIRE(hidden > 0 && hidden <= 1024, "hidden=%d must be in 1..1024", hidden);
+    return ARX_OK;
+}
+
+static int launch_pair_head(const float* cls, int64_t ld, int n, int H, const arx_pair_head& p, float* out, int64_t ld_out,
+                            hipStream_t st) {
+    const int smem = 2 * PH_ROWS * H * (int)sizeof(float);
+    ARX_HIP_CHECK(arx_func_smem((const void*)pair_head_kernel, smem));
+    pair_head_kernel<<<cdiv(n, PH_ROWS), 256, smem, st>>>(cls, ld, n, H, p.pooler_w, p.pooler_b, p.cls_w, p.cls_b, p.n_labels, out,
+                                                            ld_out);
+    ARX_HIP_CHECK(hipGetLastError());
+    return ARX_OK;
+}
+
+extern "C" int32_t arx_encoder_set_pair_head(arx_encoder* h, const arx_pair_head* head) {
+    ARX_REQUIRE(h, "null handle");
+    ARX_REQUIRE(h->cfg.arch == ARX_ARCH_BERT && h->cfg.pool == ARX_POOL_CLS, "a pair head needs a BERT handle with CLS pooling");
+    const int rc = check_pair_head(head, h->cfg.hidden);
+    if (rc != ARX_OK) return rc;
+    ARX_REQUIRE(head->type_emb, "pair head: missing token-type table");
+    if (!h->cls_ws) ARX_HIP_CHECK(hipMalloc((void**)&h->cls_ws, (int64_t)h->max_seqs * h->cfg.hidden * sizeof(float)));
+    h->pair = *head;
+    h->has_pair = 1;
+    return ARX_OK;
+}
+
+extern "C" int32_t arx_encoder_score_pairs(arx_encoder* h, const int32_t* ids, int32_t seq_stride, const int32_t* lens,
+                                           const int32_t* seg_b, int32_t n_seqs, int32_t max_len, int32_t total_tokens,
+                                           float* out_logits, int64_t out_stride, void* stream) {
+    ARX_REQUIRE(h && out_logits, "null handle/out_logits");
+    ARX_REQUIRE(h->has_pair, "no pair head set (arx_encoder_set_pair_head)");
+    ARX_REQUIRE(out_stride >= h->pair.n_labels, "out_stride < n_labels");
+    // CLS rows of the last layer (pool_norm_kernel, CLS, normalize = 0: the final LayerNorm applied, no L2 scaling)
+    int rc = encoder_run(h, ids, seq_stride, lens, seg_b, n_seqs, max_len, total_tokens, h->cls_ws, h->cfg.hidden, nullptr, 0, 0,
+                         stream);
+    if (rc != ARX_OK) return rc;
+    return launch_pair_head(h->cls_ws, h->cfg.hidden, n_seqs, h->cfg.hidden, h->pair, out_logits, out_stride, (hipStream_t)stream);
+}
+
+extern "C" int32_t arx_encoder_debug_cls(arx_encoder* h, float* dst, int32_t n, void* stream) {
+    ARX_REQUIRE(h && h->cls_ws && dst, "no pair head set / null dst");
+    ARX_REQUIRE(n > 0 && n <= h->max_seqs, "n out of range");
+    ARX_HIP_CHECK(hipMemcpyAsync(dst, h->cls_ws, (int64_t)n * h->cfg.hidden * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return ARX_OK;
+}
+
+extern "C" int32_t arx_pair_head_forward(const float* cls_rows, int64_t ld, int32_t n, int32_t hidden, const arx_pair_head* head,
+                                         float* out_logits, int64_t out_stride, void* stream) {
+    const int rc = check_pair_head(head, hidden);
+    if (rc != ARX_OK) return rc;
+    ARX_REQUIRE(n >= 0 && ld >= hidden && out_stride >= head->n_labels, "bad n / ld / out_stride");
+    if (n == 0) return ARX_OK;
+    ARX_REQUIRE(cls_rows && out_logits, "null cls_rows/out_logits");
+    return launch_pair_head(cls_rows, ld, n, hidden, *head, out_logits, out_stride, (hipStream_t)stream);
 }
 
 #ifdef ARX_DEV_VARIANTS

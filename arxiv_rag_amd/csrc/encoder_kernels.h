@@ -32,13 +32,16 @@ __global__ void scan_lens_kernel(const int32_t* __restrict__ lens, int32_t* __re
 // Embedding gather + LayerNorm -> bf16 x[T,H].  One wave per token; grid (ceil(max_len/4), n_seqs), 256 thr.
 // MPNet position id = cumsum(ids != pad)[s] * (ids[s] != pad) + pad  (TF modeling_mpnet.py:873-881);
 // BERT position id = s, plus token-type row 0.
-template <int ARCH>
+// SEG (BERT sentence pairs, the cross-encoder input): `type0` is the [2, H] token-type table and token s of sequence b adds row 1
+// when s >= seg_b[b] (segment B), row 0 otherwise; any seg_b is valid (seg_b[b] >= lens[b]: all row 0, the plain forward's bits).
+template <int ARCH, bool SEG = false>
 __global__ __launch_bounds__(256) void embed_ln_kernel(const int32_t* __restrict__ ids, int seq_stride,
                                                         const int32_t* __restrict__ lens, const int32_t* __restrict__ cu,
                                                         const float* __restrict__ word, const float* __restrict__ pos,
                                                         const float* __restrict__ type0, const float* __restrict__ g,
                                                         const float* __restrict__ bta, uint16_t* __restrict__ x,
-                                                        int H, int vocab, int max_pos, int pad_id, float eps) {
+                                                        int H, int vocab, int max_pos, int pad_id, float eps,
+                                                        const int32_t* __restrict__ seg_b = nullptr) {
     const int b = blockIdx.y, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int s = blockIdx.x * 4 + w;
     const int L = lens[b];
@@ -61,6 +64,8 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const int32_t* __restrict
     pid = pid >= max_pos ? max_pos - 1 : pid;
     const float* wr = word + (int64_t)id * H;
     const float* pr = pos + (int64_t)pid * H;
+    const float* tr = type0;
+    if (SEG) tr += (s >= seg_b[b]) ? H : 0;
     // H <= 1024: each lane holds up to 4 float4 chunks (chunk c covers columns 4*(lane + 64*c) ..)
     f32x4 v[4];
     float sum = 0.f;
@@ -72,7 +77,7 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const int32_t* __restrict
             f32x4 a = *reinterpret_cast<const f32x4*>(wr + ch * 4);
             const f32x4 p4 = *reinterpret_cast<const f32x4*>(pr + ch * 4);
             a += p4;
-            if (ARCH == ARX_ARCH_BERT) a += *reinterpret_cast<const f32x4*>(type0 + ch * 4);
+            if (ARCH == ARX_ARCH_BERT) a += *reinterpret_cast<const f32x4*>(tr + ch * 4);
             v[c] = a;
             sum += a[0] + a[1] + a[2] + a[3];
         } else {
@@ -1513,6 +1518,55 @@ __global__ __launch_bounds__(256) void adjacent_cosine_kernel(const float* __res
     }
     dot = wave_sum(dot); na = wave_sum(na); nb = wave_sum(nb);
     if (lane == 0) out[i] = dot / (sqrtf(na) * sqrtf(nb));
+}
+
+// Cross-encoder head (BertForSequenceClassification): logits[i] = W_c tanh(W_p h_i + b_p) + b_c on f32 CLS rows h_i, f32 weights.
+// One 256-thread block per PH_ROWS pairs: the block's CLS rows are staged in LDS and W_p streams through once per block, one wave
+// per output row j (lane-strided partial dots for all PH_ROWS rows at once, then the wave_sum butterfly); the pooled rows stay in
+// LDS for the classifier dots (one wave per (row, label)).  Every sum runs in one fixed order that does not depend on the row's
+// slot, the block or n, and there are no atomics: a pair's logits are bitwise independent of the other pairs of its launch.
+// Dynamic LDS: 2 * PH_ROWS * H floats (128 KB at H = 1024).
+constexpr int PH_ROWS = 16;
+__global__ __launch_bounds__(256) void pair_head_kernel(const float* __restrict__ cls, int64_t ld, int n, int H,
+                                                         const float* __restrict__ wp, const float* __restrict__ bp,
+                                                         const float* __restrict__ wc, const float* __restrict__ bc, int n_labels,
+                                                         float* __restrict__ out, int64_t ld_out) {
+    extern __shared__ float ph_sm[];
+    float* xs = ph_sm;                     // [PH_ROWS][H] CLS rows (zeros past n)
+    float* ps = ph_sm + PH_ROWS * H;       // [PH_ROWS][H] pooled rows
+    const int r0 = blockIdx.x * PH_ROWS, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int nr = min(PH_ROWS, n - r0);
+    for (int i = tid; i < PH_ROWS * H; i += 256) {
+        const int r = i / H, k = i - r * H;
+        xs[i] = r < nr ? cls[(int64_t)(r0 + r) * ld + k] : 0.f;
+    }
+    __syncthreads();
+    for (int j = w; j < H; j += 4) {
+        const float* wr = wp + (int64_t)j * H;
+        float acc[PH_ROWS];
+#pragma unroll
+        for (int r = 0; r < PH_ROWS; ++r) acc[r] = 0.f;
+        for (int k = lane; k < H; k += 64) {
+            const float wv = wr[k];
+#pragma unroll
+            for (int r = 0; r < PH_ROWS; ++r) acc[r] = fmaf(wv, xs[r * H + k], acc[r]);
+        }
+        const float bj = bp[j];
+#pragma unroll
+        for (int r = 0; r < PH_ROWS; ++r) {
+            const float v = wave_sum(acc[r]);          // the xor butterfly leaves the same bits in every lane
+            if (lane == r) ps[r * H + j] = tanhf(v + bj);
+        }
+    }
+    __syncthreads();
+    for (int o = w; o < nr * n_labels; o += 4) {
+        const int r = o / n_labels, l = o - r * n_labels;
+        const float* wr = wc + (int64_t)l * H;
+        float acc = 0.f;
+        for (int k = lane; k < H; k += 64) acc = fmaf(wr[k], ps[r * H + k], acc);
+        acc = wave_sum(acc);
+        if (lane == 0) out[(int64_t)(r0 + r) * ld_out + l] = acc + bc[l];
+    }
 }
 
 // bf16 [n, H] -> f32 (debug tap)

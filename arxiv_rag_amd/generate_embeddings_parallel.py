@@ -658,14 +658,17 @@ def store_in_chroma_batched(chunks: List[Dict], embeddings: Sequence, db_path: s
 
 # --------------------------------------------------------------------------------------------- search (added step)
 def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[str], top_k: int = 10,
-                   output_dir: str = "./embeddings_saved", chunk_base: int = 0) -> List[Dict]:
+                   output_dir: str = "./embeddings_saved", chunk_base: int = 0, reranker=None, rerank_top_k: int = 32) -> List[Dict]:
     """Brute-force cosine top-k (config.yaml:63-64 `top_k: 10`) over the rank's fp16 rows in HBM; with
     torchrun each rank holds the contiguous row shard it encoded and the partial top-k lists are
     all-gathered over RCCL and merged.  `shard` is the `ShardSink` the encode step filled: rows [lo, hi) are already where they
     will be searched and nothing is uploaded here; the queries are encoded straight into an fp16 device matrix.  (A consumer that
     only has the `.npy` rows on disk builds a `store.HipCollection` instead.)  `chunks[j]` is row `chunk_base + j` of the corpus:
     with per-rank loading a rank only knows the chunk ids of its own rows, so the ids of the merged hits are exchanged (one
-    `all_gather_object` of at most Q x k small entries)."""
+    `all_gather_object` of at most Q x k small entries).
+    `reranker` (a `rerank.HipCrossEncoder`, or anything with its `predict`): the search fetches `rerank_top_k` candidates, each rank
+    scores the (query, candidate) pairs whose texts it holds, the scores are exchanged over the host group, and the best `top_k` by
+    rerank score are kept; every hit then carries `rerank_score` beside its cosine `score`."""
     import torch
     from .index import ShardIndex
     dist = _dist()
@@ -676,8 +679,15 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
     model.encode(queries, batch_size=256, normalize_embeddings=True, convert_to_numpy=True, device_f16_out=qd, low_latency=True)
     # int8 pre-filter (same exact answers; +50 % shard memory, one quantisation pass): 1.5-1.7x the queries per second on small batches
     pre = "int8" if (shard.rows.shape[1] % 128 == 0 and shard.rows.shape[1] <= 1024 and shard.rows.shape[0] > 0) else None
-    s, i = ShardIndex(shard.rows, idx_base=shard.lo, prefilter=pre, adaptive=True).search_distributed(qd, top_k)
+    k_search = rerank_top_k if reranker is not None else top_k
+    s, i = ShardIndex(shard.rows, idx_base=shard.lo, prefilter=pre, adaptive=True).search_distributed(qd, k_search)
     s, i = s.cpu().numpy(), i.cpu().numpy()
+    if reranker is not None:
+        from .rerank import rerank_candidates, reorder_by_rerank
+        texts = {int(j): chunks[int(j) - chunk_base]["text"] for j in np.unique(i) if chunk_base <= j < chunk_base + len(chunks)}
+        scores = rerank_candidates(lambda pairs: reranker.predict(pairs, batch_size=rerank_top_k, convert_to_numpy=True),
+                                   queries, i, texts, dist=dist if world > 1 else None, group=host_group() if world > 1 else None)
+        picked = reorder_by_rerank(i, scores, top_k)
     names = {int(j): chunks[int(j) - chunk_base].get("chunk_id", f"chunk_{int(j)}")
              for j in np.unique(i) if chunk_base <= j < chunk_base + len(chunks)}
     if dist and world > 1:
@@ -687,6 +697,12 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
     results = []
     for qi, text in enumerate(queries):
         hits = []
+        if reranker is not None:
+            for r, (p, j, rs_) in enumerate(picked[qi]):
+                hits.append({"rank": r + 1, "score": float(s[qi, p]), "rerank_score": float(rs_), "index": j,
+                             "chunk_id": names.get(j, f"chunk_{j}")})
+            results.append({"query": text, "results": hits})
+            continue
         for r in range(top_k):
             j = int(i[qi, r])
             if j < 0:
@@ -722,12 +738,34 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--queries", type=str, default=None, help="Text file, one query per line: run the cosine top-k step")
     p.add_argument("--top-k", type=int, default=10, help="Results per query (default: 10)")
     p.add_argument("--skip-chroma", action="store_true", help="Do not attempt ChromaDB ingestion")
+    p.add_argument("--rerank-model", type=str, default=None,
+                   help="Cross-encoder (name resolved to a LOCAL directory, or a directory) that reranks the --queries candidates")
+    p.add_argument("--rerank-top-k", type=int, default=32,
+                   help=f"Candidates the search fetches for the reranker (default: 32; at most {RERANK_MAX_K}, the search's k limit)")
     return p
+
+
+RERANK_MAX_K = 32          # the exact top-k search returns k <= 32 per query (search.hip KMAX)
+
+
+def check_rerank_args(args) -> Optional[str]:
+    """-> an error message for an unusable --rerank-top-k, else None."""
+    if not args.rerank_model:
+        return None
+    if args.rerank_top_k > RERANK_MAX_K:
+        return f"--rerank-top-k {args.rerank_top_k}: the search returns at most k <= {RERANK_MAX_K} candidates per query"
+    if args.rerank_top_k < args.top_k:
+        return f"--rerank-top-k {args.rerank_top_k} is below --top-k {args.top_k}: the reranker must see at least the results it keeps"
+    return None
 
 
 def main(argv: Optional[Sequence[str]] = None, model_factory: Optional[Callable] = None) -> int:
     global _model, _model_name
     args = build_parser().parse_args(argv)
+    err = check_rerank_args(args)
+    if err:
+        print(f"Error: {err}")
+        return 2
     input_dir = Path(args.input_dir)
     if not input_dir.exists():
         print(f"Error: Directory {input_dir} not found")
@@ -807,7 +845,12 @@ def main(argv: Optional[Sequence[str]] = None, model_factory: Optional[Callable]
             if sink is None:
                 print("⚠️  --queries needs the HIP encoder (the search step runs over the shard it leaves in HBM): skipped")
             else:
-                search_queries(_model, chunks, sink, qs, top_k=args.top_k, chunk_base=span[0] if span else 0)
+                reranker = None
+                if args.rerank_model:
+                    from .rerank import HipCrossEncoder
+                    reranker = HipCrossEncoder.from_dir(args.rerank_model, device=_model.encoder.device)
+                search_queries(_model, chunks, sink, qs, top_k=args.top_k, chunk_base=span[0] if span else 0,
+                               reranker=reranker, rerank_top_k=args.rerank_top_k)
         store_time = 0.0
         if rank == 0 and not args.skip_chroma:
             try:

@@ -98,8 +98,17 @@ class HipCollection:
     def count(self) -> int:
         return self.n_total
 
-    def query(self, query_embeddings=None, query_texts: Optional[Sequence[str]] = None, n_results: int = 10) -> Dict:
+    def query(self, query_embeddings=None, query_texts: Optional[Sequence[str]] = None, n_results: int = 10, reranker=None,
+              n_candidates: int = 32) -> Dict:
+        """`reranker` (a `rerank.HipCrossEncoder`; needs `query_texts`): the search fetches `n_candidates` (<= 32) rows per query,
+        the cross-encoder scores (query, document) for each, and the best `n_results` come back in reranked order with an added
+        `rerank_scores` list per query (`scores` / `distances` stay the cosine ones)."""
         import torch
+        if reranker is not None:
+            if query_texts is None:
+                raise ValueError("reranking needs query_texts")
+            if not (n_results <= n_candidates <= 32):
+                raise ValueError(f"n_candidates={n_candidates} must be in [n_results, 32] (the search's k limit)")
         if query_embeddings is None:
             if query_texts is None or self.encoder is None:
                 raise ValueError("pass query_embeddings, or query_texts with an encoder")
@@ -107,8 +116,21 @@ class HipCollection:
         q = torch.from_numpy(np.ascontiguousarray(query_embeddings, dtype=np.float16)).to(self.index.corpus.device)
         if q.dim() == 1:
             q = q[None]
-        s, i = self.index.search_distributed(q, n_results)
+        s, i = self.index.search_distributed(q, n_candidates if reranker is not None else n_results)
         s, i = s.cpu().numpy(), i.cpu().numpy()
+        if reranker is not None:
+            from .rerank import rerank_candidates, reorder_by_rerank
+            texts = {int(j): self.metadata[int(j)].get("text") or "" for j in np.unique(i) if j >= 0}
+            sc = rerank_candidates(lambda pairs: reranker.predict(pairs, batch_size=n_candidates, convert_to_numpy=True),
+                                   list(query_texts), i, texts)
+            picked = reorder_by_rerank(i, sc, n_results)
+            width = max([len(p) for p in picked] + [1])
+            s2 = np.full((len(picked), width), -np.inf, np.float32); i2 = np.full((len(picked), width), -1, np.int64)
+            rr = [[h[2] for h in p] for p in picked]
+            for qi, p in enumerate(picked):
+                for r, (pos, j, _) in enumerate(p):
+                    s2[qi, r], i2[qi, r] = s[qi, pos], j
+            s, i = s2, i2
         out = {"ids": [], "distances": [], "scores": [], "documents": [], "metadatas": [], "indices": []}
         for qi in range(q.shape[0]):
             keep = i[qi] >= 0
@@ -120,4 +142,6 @@ class HipCollection:
             out["distances"].append((2.0 - 2.0 * s[qi][keep]).tolist())
             out["documents"].append([m.get("text") for m in ms])
             out["metadatas"].append([{k: m.get(k) for k in ("paper_id", "section", "quality_score")} for m in ms])
+        if reranker is not None:
+            out["rerank_scores"] = rr
         return out

@@ -148,7 +148,7 @@ class WordPieceTokenizer:
                                             spec["max_chars"], spec["triggers"])
 
     @classmethod
-    def from_dir(cls, path: str | Path, cfg: EncoderConfig) -> "WordPieceTokenizer":
+    def from_dir(cls, path: str | Path, cfg: EncoderConfig, bert_pair: bool = False) -> "WordPieceTokenizer":
         from tokenizers import Tokenizer
         p = Path(path)
         if (p / "tokenizer.json").exists():
@@ -161,11 +161,13 @@ class WordPieceTokenizer:
                 w = line.rstrip("\r")
                 if w != "" or i == 0:
                     vocab.setdefault(w, i)
-            return cls.from_vocab(vocab, cfg)
+            return cls.from_vocab(vocab, cfg, bert_pair=bert_pair)
         raise FileNotFoundError(f"{p}: neither tokenizer.json nor vocab.txt found (tokenizers are never fetched by name)")
 
     @classmethod
-    def from_vocab(cls, vocab: dict, cfg: EncoderConfig, lowercase: bool = True) -> "WordPieceTokenizer":
+    def from_vocab(cls, vocab: dict, cfg: EncoderConfig, lowercase: bool = True, bert_pair: bool = False) -> "WordPieceTokenizer":
+        """`bert_pair` (cross-encoders): the pair template is BERT's "[CLS] $A [SEP] $B:1 [SEP]:1" instead of "bos A eos eos B eos";
+        the single-sentence template is the same either way."""
         from tokenizers import Tokenizer, models, normalizers, pre_tokenizers, processors
         if cfg.arch == ARCH_MPNET:
             bos, eos, unk = "<s>", "</s>", "<unk>" if "<unk>" in vocab else "[UNK]"
@@ -179,7 +181,7 @@ class WordPieceTokenizer:
                                                     lowercase=lowercase)
         tok.pre_tokenizer = pre_tokenizers.BertPreTokenizer()
         tok.post_processor = processors.TemplateProcessing(
-            single=f"{bos} $A {eos}", pair=f"{bos} $A {eos} {eos} $B {eos}",
+            single=f"{bos} $A {eos}", pair=f"{bos} $A {eos} $B:1 {eos}:1" if bert_pair else f"{bos} $A {eos} {eos} $B {eos}",
             special_tokens=[(bos, vocab[bos]), (eos, vocab[eos])])
         return cls(tok, cfg)
 
@@ -215,6 +217,77 @@ class WordPieceTokenizer:
                 ids[i, len(s):] = self.cfg.pad_id
                 lens[i] = len(s)
         return ids, lens
+
+
+    # ---- sentence pairs (cross-encoders) -----------------------------------------------------------------------------------------
+    def _full_pieces(self, texts: Sequence[str]) -> List[List[int]]:
+        self._tok.no_truncation()
+        return [e.ids for e in self._tok.encode_batch(list(texts), add_special_tokens=False)]
+
+    def _pieces(self, texts: Sequence[str], cap: int):
+        """-> (word-piece lists cut to `cap`, exact lengths or -1 where a native row reached `cap` and was cut there)."""
+        texts = list(texts)
+        if self._native is None or not texts:
+            full = self._full_pieces(texts)
+            return [p[:cap] for p in full], [len(p) for p in full]
+        ids, lens, fb = self._native.encode(texts, cap + 2, resolve=self._segment_pieces)
+        pieces = [ids[i, 1:max(int(lens[i]) - 1, 1)].tolist() for i in range(len(texts))]
+        exact = [len(p) if len(p) < cap else -1 for p in pieces]
+        rest = np.flatnonzero(fb)
+        if rest.size:
+            for i, p in zip(rest, self._full_pieces([texts[i] for i in rest])):
+                pieces[i], exact[i] = p[:cap], len(p)
+        return pieces, exact
+
+    @staticmethod
+    def pair_keep(n_a: int, n_b: int, budget: int) -> Tuple[int, int]:
+        """Pieces kept of A and B under `longest_first` truncation to `budget` pieces, HF tokenizers' rule: the shorter side stays
+        whole when the longer one can absorb the whole cut; otherwise both are cut, the shorter side (A on a tie) to budget // 2 and
+        the other to the rest (so an odd budget gives its extra piece to the longer side, to B on a tie)."""
+        if n_a + n_b <= budget:
+            return n_a, n_b
+        swap = n_a > n_b
+        n1, n2 = (n_b, n_a) if swap else (n_a, n_b)
+        n2 = n1 if n1 > budget else max(n1, budget - n1)
+        if n1 + n2 > budget:
+            n1 = budget // 2
+            n2 = n1 + budget % 2
+        return (n2, n1) if swap else (n1, n2)
+
+    def encode_pairs_packed(self, pairs: Sequence[Tuple[str, str]], max_len: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Cross-encoder input: "[CLS] A [SEP] B [SEP]" with `longest_first` truncation to max_len tokens, as HF tokenizers encodes
+        the pair with BERT's template.  -> (ids int32 [n, max_len] right-padded with cfg.pad_id, lens int32 [n], seg_b int32 [n]: the
+        first token of segment B (token type 1 from there on)).  Every distinct text is tokenised once (a query shared by all its
+        candidates), pure-ASCII texts through the native tokenizer, the rest through HF tokenizers."""
+        if max_len < 3:
+            raise ValueError("max_len must leave room for [CLS], [SEP], [SEP]")
+        cls_id, sep_id = self._tok.token_to_id("[CLS]"), self._tok.token_to_id("[SEP]")
+        if cls_id is None or sep_id is None:
+            raise ValueError("the tokenizer has no [CLS] / [SEP]: not a BERT cross-encoder vocabulary")
+        pairs = [(str(a), str(b)) for a, b in pairs]
+        uniq = {}
+        for a, b in pairs:
+            uniq.setdefault(a, len(uniq)); uniq.setdefault(b, len(uniq))
+        texts = list(uniq)
+        pieces, exact = self._pieces(texts, max_len)
+        budget = max_len - 3
+        n = len(pairs)
+        ids = np.full((n, max_len), self.cfg.pad_id, np.int32)
+        lens = np.zeros(n, np.int32)
+        seg_b = np.zeros(n, np.int32)
+        for r, (a, b) in enumerate(pairs):
+            ia, ib = uniq[a], uniq[b]
+            for i, o in ((ia, ib), (ib, ia)):             # both sides >= max_len: the true lengths decide who gets the odd piece
+                if exact[i] < 0 and (exact[o] < 0 or exact[o] >= max_len):
+                    exact[i] = len(self._full_pieces([texts[i]])[0])
+            na = exact[ia] if exact[ia] >= 0 else max_len + 1
+            nb = exact[ib] if exact[ib] >= 0 else max_len + 1
+            ka, kb = self.pair_keep(na, nb, budget)
+            row = [cls_id] + pieces[ia][:ka] + [sep_id] + pieces[ib][:kb] + [sep_id]
+            ids[r, :len(row)] = row
+            lens[r] = len(row)
+            seg_b[r] = ka + 2
+        return ids, lens, seg_b
 
 
 class TokenIdPassthrough:

@@ -114,10 +114,8 @@ def adversarial_state_dict(cfg: EncoderConfig, seed: int = 0, row_offset: float 
     return sd
 
 
-def load_hf_dir(path: str | Path, cfg: EncoderConfig) -> Dict[str, np.ndarray]:
-    """Load model.safetensors (preferred) or pytorch_model.bin (weights_only=True)
-    from a local HF-layout directory; strips an optional 'mpnet.' / 'bert.' prefix."""
-    p = Path(path)
+def _read_dir(p: Path) -> Dict[str, np.ndarray]:
+    """Every tensor of model.safetensors (preferred) or pytorch_model.bin, f32, with an optional 'mpnet.' / 'bert.' prefix stripped."""
     raw: Dict[str, np.ndarray] = {}
     st = p / "model.safetensors"
     if st.exists():
@@ -135,6 +133,14 @@ def load_hf_dir(path: str | Path, cfg: EncoderConfig) -> Dict[str, np.ndarray]:
             if k.startswith(pre):
                 k = k[len(pre):]
         sd[k] = np.ascontiguousarray(v, dtype=np.float32)
+    return sd
+
+
+def load_hf_dir(path: str | Path, cfg: EncoderConfig) -> Dict[str, np.ndarray]:
+    """Load model.safetensors (preferred) or pytorch_model.bin (weights_only=True)
+    from a local HF-layout directory; strips an optional 'mpnet.' / 'bert.' prefix."""
+    p = Path(path)
+    sd = _read_dir(p)
     want = expected_shapes(cfg)
     missing = [k for k in want if k not in sd]
     if missing:
@@ -169,3 +175,53 @@ def save_hf_dir(path: str | Path, cfg: EncoderConfig, sd: Dict[str, np.ndarray])
         "pooling_mode_cls_token": cfg.pool == POOL_CLS,
         "pooling_mode_mean_tokens": cfg.pool != POOL_CLS}))
     save_file({k: np.ascontiguousarray(v) for k, v in sd.items()}, str(p / "model.safetensors"))
+
+
+# ---- cross-encoder head (BertForSequenceClassification) --------------------------------------------------------------------------
+def head_shapes(cfg: EncoderConfig, n_labels: int) -> Dict[str, tuple]:
+    """The keys a reranker adds to the encoder (after the 'bert.' prefix is stripped); the encoder's own
+    embeddings.token_type_embeddings.weight supplies both token-type rows."""
+    H = cfg.hidden
+    return {"pooler.dense.weight": (H, H), "pooler.dense.bias": (H,),
+            "classifier.weight": (n_labels, H), "classifier.bias": (n_labels,)}
+
+
+def seeded_pair_head(cfg: EncoderConfig, n_labels: int = 1, seed: int = 0, std: float = 0.05,
+                     bias_std: float = 0.02) -> Dict[str, np.ndarray]:
+    """Deterministic synthetic head weights (one RandomState stream, `head_shapes` order), as `seeded_state_dict` does for the encoder."""
+    rs = np.random.RandomState(seed)
+    return {k: (rs.standard_normal(shp) * (bias_std if k.endswith(".bias") else std)).astype(np.float32)
+            for k, shp in head_shapes(cfg, n_labels).items()}
+
+
+def load_cross_encoder_dir(path: str | Path, cfg: EncoderConfig, n_labels: int):
+    """-> (encoder state dict as `load_hf_dir` returns it, head state dict).  A missing head key raises KeyError."""
+    p = Path(path)
+    sd = load_hf_dir(p, cfg)
+    raw = _read_dir(p)
+    want = head_shapes(cfg, n_labels)
+    missing = [k for k in want if k not in raw]
+    if missing:
+        raise KeyError(f"{p}: missing cross-encoder head weights {missing}")
+    for k, shp in want.items():
+        if tuple(raw[k].shape) != shp:
+            raise ValueError(f"{p}: {k} has shape {raw[k].shape}, config expects {shp}")
+    return sd, {k: raw[k] for k in want}
+
+
+def save_cross_encoder_dir(path: str | Path, cfg: EncoderConfig, sd: Dict[str, np.ndarray], head: Dict[str, np.ndarray],
+                           n_labels: int = 1) -> None:
+    """A minimal local BertForSequenceClassification directory (HF key names, 'bert.' prefix) — synthetic model dirs for tests."""
+    import json
+    from safetensors.numpy import save_file
+    p = Path(path)
+    p.mkdir(parents=True, exist_ok=True)
+    hf = {"architectures": ["BertForSequenceClassification"], "model_type": "bert",
+          "vocab_size": cfg.vocab_size, "hidden_size": cfg.hidden, "num_hidden_layers": cfg.layers,
+          "num_attention_heads": cfg.heads, "intermediate_size": cfg.ffn, "max_position_embeddings": cfg.max_pos,
+          "layer_norm_eps": cfg.ln_eps, "pad_token_id": cfg.pad_id, "hidden_act": "gelu", "type_vocab_size": 2,
+          "id2label": {str(i): f"LABEL_{i}" for i in range(n_labels)}}
+    (p / "config.json").write_text(json.dumps(hf, indent=2))
+    tensors = {"bert." + k: np.ascontiguousarray(v) for k, v in sd.items()}
+    tensors.update({("bert." + k if k.startswith("pooler.") else k): np.ascontiguousarray(v) for k, v in head.items()})
+    save_file(tensors, str(p / "model.safetensors"))

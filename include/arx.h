@@ -135,6 +135,33 @@ int32_t arx_encoder_set_low_latency(arx_encoder* h, int32_t on);
 /* Ask the next forward() to snapshot the hidden state after `layer` (-1 = off). */
 int32_t arx_encoder_set_tap(arx_encoder* h, int32_t layer);
 
+/* ---- cross-encoder reranking (BertForSequenceClassification, e.g. cross-encoder/ms-marco-MiniLM-L-6-v2) ----------------------
+ * logits = W_c tanh(W_p h + b_p) + b_c on the final CLS row h of "[CLS] A [SEP] B [SEP]", segment B with token type 1.
+ * All pointers: device memory, caller-owned, f32, must outlive the handle. */
+typedef struct {
+    int32_t struct_bytes;          /* sizeof(arx_pair_head) */
+    int32_t n_labels;              /* 1..16 */
+    const float* type_emb;         /* [2, H] token-type table (row 0 should be the handle's arx_encoder_weights.type_emb) */
+    const float* pooler_w; const float* pooler_b;   /* [H, H], [H] (bert.pooler.dense) */
+    const float* cls_w;    const float* cls_b;      /* [n_labels, H], [n_labels] (classifier) */
+} arx_pair_head;
+
+/* Attach a pair head to a BERT handle with CLS pooling (else ARX_ERR_ARG).  Allocates the handle's [max_seqs, H] f32 CLS scratch on
+ * first use (freed by arx_encoder_destroy); arx_encoder_workspace_bytes does not count it. */
+int32_t arx_encoder_set_pair_head(arx_encoder* h, const arx_pair_head* head);
+/* Score sentence pairs: arguments as arx_encoder_forward, plus seg_b device int32 [n_seqs] (first token of segment B; any value is
+ * valid: seg_b[i] >= lens[i] = all type 0; NULL = all type 0) -> out_logits device f32 [n_seqs, out_stride >= n_labels].
+ * A pair's logits are bitwise independent of the other pairs of the call (unless arx_encoder_set_low_latency is on).  The tap of
+ * arx_encoder_set_tap works across this call as across a forward. */
+int32_t arx_encoder_score_pairs(arx_encoder* h, const int32_t* ids, int32_t seq_stride, const int32_t* lens, const int32_t* seg_b,
+                                int32_t n_seqs, int32_t max_len, int32_t total_tokens, float* out_logits, int64_t out_stride,
+                                void* stream);
+/* Parity tap: copy the f32 CLS rows [n, H] the head read in the last arx_encoder_score_pairs call into dst (device; same stream). */
+int32_t arx_encoder_debug_cls(arx_encoder* h, float* dst, int32_t n, void* stream);
+/* The head alone on caller-provided CLS rows f32 [n, ld >= hidden] (parity tap); hidden <= 1024; head->type_emb is not read. */
+int32_t arx_pair_head_forward(const float* cls_rows, int64_t ld, int32_t n, int32_t hidden, const arx_pair_head* head,
+                              float* out_logits, int64_t out_stride, void* stream);
+
 /* Build flags of the loaded library: bit 0 = built with -DARX_DEV_VARIANTS (the A/B schedules of DESIGN.md's negative-result
  * tables are compiled in and selectable through ARX_GEMM_VARIANT / ARX_ATTN_VARIANT); 0 for the shipped build. */
 int32_t arx_build_info(void);

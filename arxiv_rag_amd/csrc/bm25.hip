@@ -1,0 +1,271 @@
+// BM25 keyword top-n over a CSR-by-term impact index resident in HBM (gfx950).
+//
+// Index of one shard: term_ptr int64 [V+1], post_row uint32 [P] (shard-local row, ascending within a term), post_w f32 [P] (the
+// posting's BM25 impact, > 0, computed in float64 on the host and rounded once).  A query is its <= 64 distinct term ids in ascending
+// order; bm25(q, d) = the sum of the impacts of q's terms in d, ADDED IN ASCENDING TERM ORDER IN F32.
+//
+// bm25_search_kernel: grid (blocks, queries), 512 threads.  A block walks row tiles of the shard (tile b, b + blocks, ...).  The f32
+// accumulators of one tile live in LDS.  Per tile: the two ends of every term's posting sub-range inside the tile are found by up to
+// 128 lanes at once (one binary search on post_row per lane), then the terms are applied one after the other with a workgroup barrier
+// between them: rows within a term are distinct, so no two lanes touch one accumulator inside a term, and the barrier fixes the order
+// across terms.  There is no float atomic anywhere: a row's score depends on the index and the query's term list alone, not on the
+// tile size, the block count or the other queries of the launch.  Posting loads are coalesced along a term's list.
+//
+// Top-n: a candidate is the 64-bit key (f32 score bits << 32) | (0xffffffff - row); scores are > 0, so the unsigned order of the keys is
+// (score desc, row asc) and 0 means "none".  While a tile is scanned (which also clears it for the next one) the keys above the block's
+// current n-th best are appended to an LDS list (an INTEGER LDS atomic hands out the slots: the list's order varies, its content and
+// therefore the selected top-n do not); when the list could overflow it is cut back to its n largest keys.  Every block writes one
+// partial list [blocks, nq, n]; arx_topk_merge reduces them (blocks * n <= 4096, its limit).
+#include "arx_common.h"
+
+namespace {
+
+constexpr int BM25_NT = 512;                 // threads per block
+constexpr int BM25_MAXT = 64;                // query terms
+constexpr int BM25_CAP = 2048;               // candidate keys in LDS (16 KiB)
+constexpr int BM25_CHUNK = 2 * BM25_NT;      // rows scanned between two capacity checks (2 per thread)
+constexpr int BM25_TILE_MAX = 12288;         // 48 KiB of accumulators + 16 KiB of keys + ~1.2 KiB: two blocks per 160 KiB CU
+constexpr int BM25_KMAX = 32;
+
+struct Bm25Smem {
+    unsigned long long keys[BM25_CAP];
+    unsigned long long wred[2][BM25_NT / 64];
+    unsigned long long thr;
+    long long lo[BM25_MAXT], hi[BM25_MAXT];
+    int cnt;
+};
+
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long w = __shfl_xor(v, o);
+        v = w > v ? w : v;
+    }
+    return v;
+}
+
+// first posting p in [a, b) with post_row[p] >= row (b if none); post_row ascending in [a, b)
+__device__ __forceinline__ long long lower_bound_row(const uint32_t* __restrict__ post_row, long long a, long long b, uint32_t row) {
+    while (a < b) {
+        const long long m = a + ((b - a) >> 1);
+        if (post_row[m] < row) a = m + 1; else b = m;
+    }
+    return a;
+}
+
+// acc[0 .. tile_rows) (all zero on entry) += impacts of the query's terms for rows [tile_lo, tile_hi), in term order.
+// Ends with a barrier: acc is complete for every thread on return.
+__device__ __forceinline__ void bm25_accumulate_tile(const long long* __restrict__ term_ptr, const uint32_t* __restrict__ post_row,
+                                                     const float* __restrict__ post_w, int vocab, const int32_t* __restrict__ terms, int nt,
+                                                     uint32_t tile_lo, uint32_t tile_hi, int tile_rows, float* acc, Bm25Smem& sm) {
+    const int tid = threadIdx.x;
+    if (tid < 2 * BM25_MAXT) {
+        const int j = tid & (BM25_MAXT - 1);
+        if (j < nt) {
+            const int t = terms[j];
+            long long r = 0;
+            if (t >= 0 && t < vocab) {
+                const long long a = term_ptr[t], b = term_ptr[t + 1];
+                r = lower_bound_row(post_row, a, b, tid < BM25_MAXT ? tile_lo : tile_hi);
+            }
+            if (tid < BM25_MAXT) sm.lo[j] = r; else sm.hi[j] = r;       // a term outside the vocabulary: lo = hi = 0, no postings
+        }
+    }
+    __syncthreads();
+    for (int j = 0; j < nt; ++j) {
+        const long long a = sm.lo[j], b = sm.hi[j];
+#pragma unroll 4
+        for (long long p = a + tid; p < b; p += BM25_NT) {
+            const uint32_t i = post_row[p] - tile_lo;
+            const float w = post_w[p];
+            if (i < (uint32_t)tile_rows) acc[i] += w;       // (always true for a well-formed index: keeps a damaged one inside the tile)
+        }
+        __syncthreads();
+    }
+}
+
+// cut the candidate list (c keys, any order) back to its n largest, sorted descending in keys[0 .. n); updates cnt and thr.
+// Called by the whole block with c uniform; ends with a barrier.
+__device__ __forceinline__ void bm25_select(Bm25Smem& sm, int c, int n) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    constexpr int PER = BM25_CAP / BM25_NT;
+    unsigned long long k[PER];
+#pragma unroll
+    for (int j = 0; j < PER; ++j) k[j] = (tid + j * BM25_NT < c) ? sm.keys[tid + j * BM25_NT] : 0ull;
+    __syncthreads();                                         // every key is in a register before keys[] is rewritten
+    for (int r = 0; r < n; ++r) {
+        unsigned long long m = k[0];
+#pragma unroll
+        for (int j = 1; j < PER; ++j) m = k[j] > m ? k[j] : m;
+        m = wave_max_u64(m);
+        if (lane == 0) sm.wred[r & 1][wave] = m;
+        __syncthreads();
+        unsigned long long g = sm.wred[r & 1][0];
+#pragma unroll
+        for (int w = 1; w < BM25_NT / 64; ++w) { const unsigned long long v = sm.wred[r & 1][w]; g = v > g ? v : g; }
+        if (g != 0ull) {
+#pragma unroll
+            for (int j = 0; j < PER; ++j) if (k[j] == g) k[j] = 0ull;       // keys are distinct (distinct rows)
+        }
+        if (tid == 0) sm.keys[r] = g;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int m = 0;
+        while (m < n && sm.keys[m] != 0ull) ++m;
+        sm.cnt = m;
+        sm.thr = (m == n) ? sm.keys[n - 1] : 0ull;
+    }
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(BM25_NT) void bm25_search_kernel(const long long* __restrict__ term_ptr, const uint32_t* __restrict__ post_row,
+                                                              const float* __restrict__ post_w, int vocab, long long n_rows,
+                                                              const int32_t* __restrict__ q_terms, const int32_t* __restrict__ q_nterms,
+                                                              int n, int tile_rows, float* __restrict__ part_s, long long* __restrict__ part_i,
+                                                              long long idx_base) {
+    extern __shared__ __attribute__((aligned(16))) float acc[];               // [tile_rows] f32, then the block's Bm25Smem (all dynamic LDS)
+    Bm25Smem& sm = *reinterpret_cast<Bm25Smem*>(acc + tile_rows);
+    const int tid = threadIdx.x, q = blockIdx.y, nq = gridDim.y;
+    const int32_t* terms = q_terms + (long long)q * BM25_MAXT;
+    const int nt = min(max(q_nterms[q], 0), BM25_MAXT);
+    for (int i = tid; i < tile_rows; i += BM25_NT) acc[i] = 0.f;
+    if (tid == 0) { sm.cnt = 0; sm.thr = 0ull; }
+    __syncthreads();
+    const long long n_tiles = (n_rows + tile_rows - 1) / tile_rows;
+    for (long long t = blockIdx.x; t < n_tiles && nt > 0; t += gridDim.x) {
+        const long long lo = t * tile_rows;
+        const long long hi = min(lo + (long long)tile_rows, n_rows);
+        bm25_accumulate_tile(term_ptr, post_row, post_w, vocab, terms, nt, (uint32_t)lo, (uint32_t)hi, tile_rows, acc, sm);
+        const int rows = (int)(hi - lo);
+        for (int c0 = 0; c0 < rows; c0 += BM25_CHUNK) {
+            const int c = sm.cnt;
+            __syncthreads();                                 // everyone has read cnt before anyone appends
+            if (c + BM25_CHUNK > BM25_CAP) bm25_select(sm, c, n);
+            const unsigned long long thr = sm.thr;
+            const int i = c0 + 2 * tid;                      // tile_rows is even and acc is zero beyond `rows`
+            if (i < tile_rows) {
+                const float2 v = *reinterpret_cast<const float2*>(acc + i);
+                *reinterpret_cast<float2*>(acc + i) = make_float2(0.f, 0.f);
+                const float s[2] = {v.x, v.y};
+#pragma unroll
+                for (int e = 0; e < 2; ++e) {
+                    if (s[e] > 0.f) {
+                        const unsigned long long key = ((unsigned long long)__float_as_uint(s[e]) << 32) |
+                                                       (unsigned long long)(0xffffffffu - (uint32_t)(lo + i + e));
+                        if (key > thr) {
+                            const int pos = atomicAdd(&sm.cnt, 1);      // integer slot counter; pos < CAP by the check above
+                            if (pos < BM25_CAP) sm.keys[pos] = key;
+                        }
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    }
+    bm25_select(sm, min(sm.cnt, BM25_CAP), n);
+    if (tid < n) {
+        const unsigned long long key = sm.keys[tid];
+        const long long o = ((long long)blockIdx.x * nq + q) * n + tid;
+        part_s[o] = key ? __uint_as_float((uint32_t)(key >> 32)) : -INFINITY;
+        part_i[o] = key ? (long long)(0xffffffffu - (uint32_t)key) + idx_base : -1ll;
+    }
+}
+
+// debug tap: the dense score row of ONE query for rows [row_lo, row_hi), one tile per block, through the same accumulation
+__global__ __launch_bounds__(BM25_NT) void bm25_scores_kernel(const long long* __restrict__ term_ptr, const uint32_t* __restrict__ post_row,
+                                                              const float* __restrict__ post_w, int vocab, const int32_t* __restrict__ terms,
+                                                              int nt, long long row_lo, long long row_hi, int tile_rows, float* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) float acc[];               // [tile_rows] f32, then the block's Bm25Smem (all dynamic LDS)
+    Bm25Smem& sm = *reinterpret_cast<Bm25Smem*>(acc + tile_rows);
+    const int tid = threadIdx.x;
+    for (int i = tid; i < tile_rows; i += BM25_NT) acc[i] = 0.f;
+    __syncthreads();
+    const long long lo = row_lo + (long long)blockIdx.x * tile_rows;
+    const long long hi = min(lo + (long long)tile_rows, row_hi);
+    bm25_accumulate_tile(term_ptr, post_row, post_w, vocab, terms, nt, (uint32_t)lo, (uint32_t)hi, tile_rows, acc, sm);
+    for (int i = tid; i < (int)(hi - lo); i += BM25_NT) out[lo - row_lo + i] = acc[i];
+}
+
+int bm25_default_tile(int64_t n_rows) {
+    // small shards: one tile that just covers them (less LDS to clear and scan); large ones: the largest tile two blocks per CU allow
+    const int64_t need = round_up64(n_rows, BM25_CHUNK);
+    return (int)(need < BM25_TILE_MAX ? need : BM25_TILE_MAX);
+}
+
+int bm25_blocks(int64_t n_rows, int tile_rows, int n, int max_blocks) {
+    const int64_t tiles = (n_rows + tile_rows - 1) / tile_rows;
+    int64_t b = 4096 / n;                                    // arx_topk_merge takes blocks * n <= 4096 candidates per query
+    if (b > 512) b = 512;
+    if (max_blocks > 0 && b > max_blocks) b = max_blocks;
+    return (int)(tiles < b ? tiles : b);
+}
+
+}  // namespace
+
+extern "C" int64_t arx_bm25_workspace_bytes(int64_t n_rows, int32_t n_queries, int32_t n) {
+    if (n_rows <= 0 || n_queries <= 0 || n < 1 || n > BM25_KMAX) return -1;
+    // sized for the smallest tile a tuned call may ask for, so that one workspace serves every tile size / block count
+    const int64_t blocks = bm25_blocks(n_rows, BM25_CHUNK, n, 0);
+    return round_up64(blocks * n_queries * n * 4, 256) + round_up64(blocks * n_queries * n * 8, 256);
+}
+
+extern "C" int32_t arx_bm25_search_tuned(const int64_t* term_ptr, const uint32_t* post_row, const float* post_w, int32_t vocab, int64_t n_rows,
+                                         const int32_t* q_terms, const int32_t* q_nterms, int32_t n_queries, int32_t n, float* out_scores,
+                                         int64_t* out_ids, int64_t idx_base, void* ws, int64_t ws_bytes, int32_t tile_rows, int32_t max_blocks,
+                                         void* stream) {
+    ARX_REQUIRE(term_ptr && post_row && post_w && q_terms && q_nterms && out_scores && out_ids, "null pointer argument");
+    ARX_REQUIRE(vocab > 0, "vocab=%d must be positive", vocab);
+    ARX_REQUIRE(n_rows > 0 && n_rows < (1ll << 31), "n_rows=%lld must be in [1, 2^31)", (long long)n_rows);
+    ARX_REQUIRE(n_queries > 0 && n_queries <= 65535, "n_queries=%d must be in [1, 65535]", n_queries);
+    ARX_REQUIRE(n >= 1 && n <= BM25_KMAX, "n=%d must be in [1, %d]", n, BM25_KMAX);
+    ARX_REQUIRE(idx_base >= 0, "idx_base must be >= 0");
+    ARX_REQUIRE(max_blocks >= 0, "max_blocks must be >= 0 (0 = default)");
+    if (tile_rows == 0) tile_rows = bm25_default_tile(n_rows);
+    ARX_REQUIRE(tile_rows >= BM25_CHUNK && tile_rows <= BM25_TILE_MAX && tile_rows % BM25_CHUNK == 0,
+                "tile_rows=%d must be a multiple of %d in [%d, %d] (0 = default)", tile_rows, BM25_CHUNK, BM25_CHUNK, BM25_TILE_MAX);
+    const int blocks = bm25_blocks(n_rows, tile_rows, n, max_blocks);
+    const int64_t need = arx_bm25_workspace_bytes(n_rows, n_queries, n);
+    ARX_REQUIRE(blocks == 1 || (ws && ws_bytes >= need), "workspace too small: %lld < %lld bytes", (long long)ws_bytes, (long long)need);
+    hipStream_t st = (hipStream_t)stream;
+    const int smem = tile_rows * 4 + (int)sizeof(Bm25Smem);
+    ARX_HIP_CHECK(arx_func_smem((const void*)bm25_search_kernel, smem));
+    float* part_s = out_scores; long long* part_i = (long long*)out_ids;
+    if (blocks > 1) {
+        part_s = (float*)ws;
+        part_i = (long long*)((char*)ws + round_up64((int64_t)blocks * n_queries * n * 4, 256));
+    }
+    bm25_search_kernel<<<dim3(blocks, n_queries), BM25_NT, smem, st>>>((const long long*)term_ptr, post_row, post_w, vocab, n_rows, q_terms,
+                                                                        q_nterms, n, tile_rows, part_s, part_i, idx_base);
+    ARX_HIP_CHECK(hipGetLastError());
+    if (blocks > 1) return arx_topk_merge(part_s, (const int64_t*)part_i, blocks, n_queries, n, out_scores, out_ids, stream);
+    return ARX_OK;
+}
+
+extern "C" int32_t arx_bm25_search(const int64_t* term_ptr, const uint32_t* post_row, const float* post_w, int32_t vocab, int64_t n_rows,
+                                   const int32_t* q_terms, const int32_t* q_nterms, int32_t n_queries, int32_t n, float* out_scores,
+                                   int64_t* out_ids, int64_t idx_base, void* ws, int64_t ws_bytes, void* stream) {
+    return arx_bm25_search_tuned(term_ptr, post_row, post_w, vocab, n_rows, q_terms, q_nterms, n_queries, n, out_scores, out_ids, idx_base,
+                                 ws, ws_bytes, 0, 0, stream);
+}
+
+extern "C" int32_t arx_bm25_scores(const int64_t* term_ptr, const uint32_t* post_row, const float* post_w, int32_t vocab, int64_t n_rows,
+                                   const int32_t* q_terms, int32_t n_terms, int64_t row_lo, int64_t row_hi, int32_t tile_rows, float* out,
+                                   void* stream) {
+    ARX_REQUIRE(term_ptr && post_row && post_w && out && (q_terms || n_terms == 0), "null pointer argument");
+    ARX_REQUIRE(vocab > 0, "vocab=%d must be positive", vocab);
+    ARX_REQUIRE(n_rows > 0 && n_rows < (1ll << 31), "n_rows=%lld must be in [1, 2^31)", (long long)n_rows);
+    ARX_REQUIRE(n_terms >= 0 && n_terms <= BM25_MAXT, "n_terms=%d must be in [0, %d]", n_terms, BM25_MAXT);
+    ARX_REQUIRE(0 <= row_lo && row_lo < row_hi && row_hi <= n_rows, "row range [%lld, %lld) outside [0, %lld)", (long long)row_lo,
+                (long long)row_hi, (long long)n_rows);
+    if (tile_rows == 0) tile_rows = bm25_default_tile(row_hi - row_lo);
+    ARX_REQUIRE(tile_rows >= BM25_CHUNK && tile_rows <= BM25_TILE_MAX && tile_rows % BM25_CHUNK == 0,
+                "tile_rows=%d must be a multiple of %d in [%d, %d] (0 = default)", tile_rows, BM25_CHUNK, BM25_CHUNK, BM25_TILE_MAX);
+    const int64_t blocks = (row_hi - row_lo + tile_rows - 1) / tile_rows;
+    const int smem = tile_rows * 4 + (int)sizeof(Bm25Smem);
+    ARX_HIP_CHECK(arx_func_smem((const void*)bm25_scores_kernel, smem));
+    bm25_scores_kernel<<<(int)blocks, BM25_NT, smem, (hipStream_t)stream>>>((const long long*)term_ptr, post_row, post_w, vocab, q_terms, n_terms,
+                                                                            row_lo, row_hi, tile_rows, out);
+    ARX_HIP_CHECK(hipGetLastError());
+    return ARX_OK;
+}

@@ -658,7 +658,8 @@ def store_in_chroma_batched(chunks: List[Dict], embeddings: Sequence, db_path: s
 
 # --------------------------------------------------------------------------------------------- search (added step)
 def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[str], top_k: int = 10,
-                   output_dir: str = "./embeddings_saved", chunk_base: int = 0, reranker=None, rerank_top_k: int = 32) -> List[Dict]:
+                   output_dir: str = "./embeddings_saved", chunk_base: int = 0, reranker=None, rerank_top_k: int = 32,
+                   hybrid_alpha: Optional[float] = None) -> List[Dict]:
     """Brute-force cosine top-k (config.yaml:63-64 `top_k: 10`) over the rank's fp16 rows in HBM; with
     torchrun each rank holds the contiguous row shard it encoded and the partial top-k lists are
     all-gathered over RCCL and merged.  `shard` is the `ShardSink` the encode step filled: rows [lo, hi) are already where they
@@ -668,7 +669,13 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
     `all_gather_object` of at most Q x k small entries).
     `reranker` (a `rerank.HipCrossEncoder`, or anything with its `predict`): the search fetches `rerank_top_k` candidates, each rank
     scores the (query, candidate) pairs whose texts it holds, the scores are exchanged over the host group, and the best `top_k` by
-    rerank score are kept; every hit then carries `rerank_score` beside its cosine `score`."""
+    rerank score are kept; every hit then carries `rerank_score` beside its cosine `score`.
+    `hybrid_alpha` (a float in [0, 1]; None = cosine only): hybrid search (config.yaml:67-68).  Each rank also builds a BM25
+    `keyword.KeywordIndex` over the word pieces of its own chunks (statistics summed over the ranks); the cosine and the keyword search
+    each fetch HYBRID_CANDIDATES rows per query (`rerank_top_k` with a reranker), `keyword.fuse` ranks their union by
+    `alpha * normalised cosine + (1 - alpha) * normalised BM25`, and the best `top_k` (with a reranker: the fused `rerank_top_k`, then
+    reranked) are kept.  Every hit then carries `hybrid_score` and `keyword_score`; `score` stays the cosine one and is null, like
+    `keyword_score`, where the row was not in that side's candidate list."""
     import torch
     from .index import ShardIndex
     dist = _dist()
@@ -680,8 +687,18 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
     # int8 pre-filter (same exact answers; +50 % shard memory, one quantisation pass): 1.5-1.7x the queries per second on small batches
     pre = "int8" if (shard.rows.shape[1] % 128 == 0 and shard.rows.shape[1] <= 1024 and shard.rows.shape[0] > 0) else None
     k_search = rerank_top_k if reranker is not None else top_k
-    s, i = ShardIndex(shard.rows, idx_base=shard.lo, prefilter=pre, adaptive=True).search_distributed(qd, k_search)
+    n_cand = k_search if hybrid_alpha is None else (rerank_top_k if reranker is not None else HYBRID_CANDIDATES)
+    s, i = ShardIndex(shard.rows, idx_base=shard.lo, prefilter=pre, adaptive=True).search_distributed(qd, n_cand)
     s, i = s.cpu().numpy(), i.cpu().numpy()
+    hyb = kws = None
+    if hybrid_alpha is not None:
+        from .keyword import KeywordIndex, fuse
+        if top_k > n_cand:
+            raise ValueError(f"hybrid search keeps at most {n_cand} results per query (top_k={top_k})")
+        kw = KeywordIndex(texts=[c["text"] for c in chunks], tokenizer=model.tokenizer, stats="global" if world > 1 else None,
+                          idx_base=chunk_base, device=dev)
+        ks, ki = kw.search_distributed(queries, n_cand)
+        hyb, i, s, kws = fuse(s, i, ks.cpu().numpy(), ki.cpu().numpy(), float(hybrid_alpha), k_search)
     if reranker is not None:
         from .rerank import rerank_candidates, reorder_by_rerank
         texts = {int(j): chunks[int(j) - chunk_base]["text"] for j in np.unique(i) if chunk_base <= j < chunk_base + len(chunks)}
@@ -695,19 +712,27 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
         dist.all_gather_object(parts, names, group=host_group())
         names = {k: v for part in parts for k, v in part.items()}
     results = []
+
+    def hybrid_fields(qi, p):                                # (null, not NaN, in the JSON file)
+        if hyb is None:
+            return {}
+        return {"score": None if np.isnan(s[qi, p]) else float(s[qi, p]), "hybrid_score": float(hyb[qi, p]),
+                "keyword_score": None if np.isnan(kws[qi, p]) else float(kws[qi, p])}
+
     for qi, text in enumerate(queries):
         hits = []
         if reranker is not None:
             for r, (p, j, rs_) in enumerate(picked[qi]):
                 hits.append({"rank": r + 1, "score": float(s[qi, p]), "rerank_score": float(rs_), "index": j,
-                             "chunk_id": names.get(j, f"chunk_{j}")})
+                             "chunk_id": names.get(j, f"chunk_{j}"), **hybrid_fields(qi, p)})
             results.append({"query": text, "results": hits})
             continue
         for r in range(top_k):
             j = int(i[qi, r])
             if j < 0:
                 continue
-            hits.append({"rank": r + 1, "score": float(s[qi, r]), "index": j, "chunk_id": names.get(j, f"chunk_{j}")})
+            hits.append({"rank": r + 1, "score": float(s[qi, r]), "index": j, "chunk_id": names.get(j, f"chunk_{j}"),
+                         **hybrid_fields(qi, r)})
         results.append({"query": text, "results": hits})
     if rank == 0:
         with open(Path(output_dir) / "search_results.json", "w", encoding="utf-8") as fh:
@@ -742,6 +767,9 @@ def build_parser() -> argparse.ArgumentParser:
                    help="Cross-encoder (name resolved to a LOCAL directory, or a directory) that reranks the --queries candidates")
     p.add_argument("--rerank-top-k", type=int, default=32,
                    help=f"Candidates the search fetches for the reranker (default: 32; at most {RERANK_MAX_K}, the search's k limit)")
+    p.add_argument("--hybrid-alpha", type=float, default=None,
+                   help="Hybrid search for --queries: weight of the cosine side in [0, 1], the BM25 keyword side gets the rest "
+                        "(config.yaml hybrid_alpha: 0.7; default: off, cosine only)")
     return p
 
 
@@ -759,10 +787,24 @@ def check_rerank_args(args) -> Optional[str]:
     return None
 
 
+HYBRID_CANDIDATES = 32     # rows each side of a hybrid search contributes per query (the candidate lists' length limit)
+
+
+def check_hybrid_args(args) -> Optional[str]:
+    """-> an error message for an unusable --hybrid-alpha, else None."""
+    if args.hybrid_alpha is None:
+        return None
+    if not (0.0 <= args.hybrid_alpha <= 1.0):                 # (also rejects nan)
+        return f"--hybrid-alpha {args.hybrid_alpha}: the weight of the cosine side must be in [0, 1]"
+    if args.top_k > HYBRID_CANDIDATES:
+        return f"--top-k {args.top_k}: hybrid search fuses {HYBRID_CANDIDATES} candidates per side and returns at most that many"
+    return None
+
+
 def main(argv: Optional[Sequence[str]] = None, model_factory: Optional[Callable] = None) -> int:
     global _model, _model_name
     args = build_parser().parse_args(argv)
-    err = check_rerank_args(args)
+    err = check_rerank_args(args) or check_hybrid_args(args)
     if err:
         print(f"Error: {err}")
         return 2
@@ -850,7 +892,7 @@ def main(argv: Optional[Sequence[str]] = None, model_factory: Optional[Callable]
                     from .rerank import HipCrossEncoder
                     reranker = HipCrossEncoder.from_dir(args.rerank_model, device=_model.encoder.device)
                 search_queries(_model, chunks, sink, qs, top_k=args.top_k, chunk_base=span[0] if span else 0,
-                               reranker=reranker, rerank_top_k=args.rerank_top_k)
+                               reranker=reranker, rerank_top_k=args.rerank_top_k, hybrid_alpha=args.hybrid_alpha)
         store_time = 0.0
         if rank == 0 and not args.skip_chroma:
             try:

@@ -1,0 +1,308 @@
+"""Keyword side of hybrid search (`retrieval.use_hybrid_search`, `hybrid_alpha: 0.7`, 3-chunks/pipeline/config.yaml:67-68).
+
+The reference configures hybrid search and has no code for it, so the definition is this project's:
+
+* a term is a word-piece id of the model's own tokenizer (`WordPieceTokenizer._full_pieces`: no specials, no truncation);
+* statistics are global over all ranks: `N` documents, `df(t)`, `avgdl = total_len / N`;
+* a posting's impact is Lucene's BM25 (k1 = 1.2, b = 0.75, non-negative idf), float64 on the host, rounded once to f32:
+  `idf = ln(1 + (N - df + 0.5) / (df + 0.5))`, `w = idf * tf * (k1 + 1) / (tf + k1 * (1 - b + b * dl / avgdl))`;
+* a query is its first 64 distinct word pieces, sorted by id; `bm25(q, d)` = the f32 sum of its terms' impacts in ascending id order;
+* `arx_bm25_search` (csrc/bm25.hip) returns per query the n <= 32 rows with the largest `(score desc, row asc)`;
+* `fuse` is relative-score fusion of the (global) dense and keyword lists: `alpha * normD + (1 - alpha) * normK`.
+
+`KeywordStats`, `build_postings`, `impacts_f64` and `fuse` are numpy only; `KeywordIndex` needs the GPU.
+"""
+from __future__ import annotations
+
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+
+BM25_K1 = 1.2
+BM25_B = 0.75
+MAX_QUERY_TERMS = 64
+MAX_N = 32                     # candidates per query (the merge kernel's list length limit, as for the cosine search)
+
+
+class KeywordStats:
+    """Corpus statistics of BM25: `N` documents, `df` int64 [V] documents containing each term, `total_len` = sum of dl."""
+
+    def __init__(self, N: int, df: np.ndarray, total_len: int):
+        self.N, self.df, self.total_len = int(N), np.asarray(df, np.int64), int(total_len)
+
+    @classmethod
+    def from_postings(cls, term_ptr: np.ndarray, dl: np.ndarray) -> "KeywordStats":
+        return cls(len(dl), np.diff(term_ptr), int(np.sum(dl, dtype=np.int64)))
+
+    @classmethod
+    def from_pieces(cls, piece_lists: Sequence[Sequence[int]], vocab_size: int) -> "KeywordStats":
+        term_ptr, _, _, dl = build_postings(piece_lists, vocab_size)
+        return cls.from_postings(term_ptr, dl)
+
+    @property
+    def avgdl(self) -> float:
+        return float(self.total_len) / float(self.N) if self.N else 0.0
+
+    def merge(self, other: "KeywordStats") -> "KeywordStats":
+        """Statistics of the union of two disjoint document sets."""
+        if self.df.shape != other.df.shape:
+            raise ValueError(f"vocabulary sizes differ: {self.df.shape[0]} vs {other.df.shape[0]}")
+        return KeywordStats(self.N + other.N, self.df + other.df, self.total_len + other.total_len)
+
+    def all_reduce(self, group=None) -> "KeywordStats":
+        """Sum over the ranks of `group` (a gloo host group: CPU tensors, nothing passes through device memory).  Without an
+        initialised process group this is the identity."""
+        import torch
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()):
+            return self
+        buf = torch.from_numpy(np.concatenate([np.array([self.N, self.total_len], np.int64), self.df]))
+        dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=group)
+        a = buf.numpy()
+        return KeywordStats(int(a[0]), a[2:].copy(), int(a[1]))
+
+
+def _host_group():
+    """The gloo group host-side exchanges go through (the default group itself when that is gloo)."""
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_backend() == "gloo":
+        return None
+    from .generate_embeddings_parallel import host_group
+    return host_group()
+
+
+def build_postings(piece_lists: Sequence[Sequence[int]], vocab_size: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """-> (term_ptr int64 [V + 1], rows uint32 [P], tf int32 [P], dl int64 [n_docs]): the postings of every term in CSR order, rows
+    ascending inside a term.  One `unique` over the (term, row) pairs; no Python loop per posting."""
+    n = len(piece_lists)
+    dl = np.fromiter((len(p) for p in piece_lists), np.int64, n)
+    total = int(dl.sum())
+    terms = np.fromiter((t for p in piece_lists for t in p), np.int64, total)
+    if total and (terms.min() < 0 or terms.max() >= vocab_size):
+        raise ValueError(f"term id outside [0, {vocab_size})")
+    rows = np.repeat(np.arange(n, dtype=np.int64), dl)
+    pair, tf = np.unique(terms * max(n, 1) + rows, return_counts=True)          # sorted by (term, row)
+    p_term = pair // max(n, 1)
+    term_ptr = np.zeros(vocab_size + 1, np.int64)
+    np.cumsum(np.bincount(p_term, minlength=vocab_size), out=term_ptr[1:])
+    return term_ptr, (pair % max(n, 1)).astype(np.uint32), tf.astype(np.int32), dl
+
+
+def idf_f64(stats: KeywordStats) -> np.ndarray:
+    df = stats.df.astype(np.float64)
+    return np.log1p((float(stats.N) - df + 0.5) / (df + 0.5))
+
+
+def impacts_f64(term_ptr: np.ndarray, rows: np.ndarray, tf: np.ndarray, dl: np.ndarray, stats: KeywordStats) -> np.ndarray:
+    """float64 impact of every posting, with the (global) statistics `stats`."""
+    p_term = np.repeat(np.arange(len(term_ptr) - 1, dtype=np.int64), np.diff(term_ptr))
+    idf = idf_f64(stats)[p_term]
+    tff = tf.astype(np.float64)
+    avgdl = stats.avgdl
+    norm = BM25_K1 * (1.0 - BM25_B + BM25_B * dl[rows.astype(np.int64)].astype(np.float64) / avgdl) if len(rows) else np.zeros(0)
+    return idf * tff * (BM25_K1 + 1.0) / (tff + norm)
+
+
+def distinct_terms(pieces: Sequence[int], exclude=()) -> List[int]:
+    """The query's term list: distinct ids, the first 64 in order of appearance, sorted ascending."""
+    seen, out = set(exclude), []
+    for t in pieces:
+        t = int(t)
+        if t not in seen:
+            seen.add(t)
+            out.append(t)
+            if len(out) == MAX_QUERY_TERMS:
+                break
+    return sorted(out)
+
+
+def special_ids(tokenizer) -> set:
+    """Ids the tokenizer's template adds around a sentence (bos / eos) plus the pad id: never query terms."""
+    tok = tokenizer._tok
+    tok.no_truncation()
+    ids = set(tok.encode("", add_special_tokens=True).ids)
+    ids.add(int(tokenizer.cfg.pad_id))
+    return ids
+
+
+def query_terms(tokenizer, texts: Sequence[str]) -> List[List[int]]:
+    sp = special_ids(tokenizer)
+    return [distinct_terms(p, exclude=sp) for p in tokenizer._full_pieces(list(texts))]
+
+
+def pack_query_terms(term_lists: Sequence[Sequence[int]], vocab_size: int) -> Tuple[np.ndarray, np.ndarray]:
+    """-> (q_terms int32 [nq, 64] -1 padded, q_nterms int32 [nq]); checks the kernel's contract on the host."""
+    nq = len(term_lists)
+    qt = np.full((nq, MAX_QUERY_TERMS), -1, np.int32)
+    qn = np.zeros(nq, np.int32)
+    for i, t in enumerate(term_lists):
+        t = np.asarray(list(t), np.int64)
+        if len(t) > MAX_QUERY_TERMS:
+            raise ValueError(f"query {i}: {len(t)} terms (at most {MAX_QUERY_TERMS})")
+        if len(t) and (t.min() < 0 or t.max() >= vocab_size):
+            raise ValueError(f"query {i}: term id outside [0, {vocab_size})")
+        if len(t) > 1 and not np.all(np.diff(t) > 0):
+            raise ValueError(f"query {i}: term ids must be strictly ascending")
+        qt[i, :len(t)] = t
+        qn[i] = len(t)
+    return qt, qn
+
+
+def fuse(dense_scores, dense_ids, kw_scores, kw_ids, alpha: float, k: int):
+    """Relative-score fusion of two global candidate lists per query.
+
+    dense_* / kw_*: [nq, n] f32 scores and int64 row ids, unused slots id -1.  Within each list `norm(s) = (s - min) / (max - min)`
+    (1 for every member when max == min); a row absent from a list gets 0 from that side.  `fused = alpha * normD + (1 - alpha) *
+    normK` over the union, in float64, ranked (fused desc, row asc).  -> (fused f64 [nq, k], ids int64 [nq, k], dense f32 [nq, k],
+    keyword f32 [nq, k]); the two score columns are nan where the row was not in that list; unused slots are (-inf, -1, nan, nan)."""
+    if not (0.0 <= float(alpha) <= 1.0):
+        raise ValueError(f"alpha={alpha} must be in [0, 1]")
+    ds, di = np.atleast_2d(np.asarray(dense_scores, np.float32)), np.atleast_2d(np.asarray(dense_ids, np.int64))
+    ks, ki = np.atleast_2d(np.asarray(kw_scores, np.float32)), np.atleast_2d(np.asarray(kw_ids, np.int64))
+    nq = ds.shape[0]
+    if ks.shape[0] != nq or ds.shape != di.shape or ks.shape != ki.shape:
+        raise ValueError("list shapes disagree")
+    out_f = np.full((nq, k), -np.inf, np.float64); out_i = np.full((nq, k), -1, np.int64)
+    out_d = np.full((nq, k), np.nan, np.float32); out_k = np.full((nq, k), np.nan, np.float32)
+
+    def norm(s, ids):
+        keep = ids >= 0
+        s64, rows = s[keep].astype(np.float64), ids[keep]
+        if not len(rows):
+            return {}, {}
+        lo, hi = s64.min(), s64.max()
+        nv = np.ones_like(s64) if hi == lo else (s64 - lo) / (hi - lo)
+        return dict(zip(rows.tolist(), nv.tolist())), dict(zip(rows.tolist(), s[keep].tolist()))
+
+    for q in range(nq):
+        nd, rd = norm(ds[q], di[q])
+        nk, rk = norm(ks[q], ki[q])
+        rows = sorted(set(nd) | set(nk))
+        fused = [(float(alpha) * nd.get(r, 0.0) + (1.0 - float(alpha)) * nk.get(r, 0.0), r) for r in rows]
+        fused.sort(key=lambda fr: (-fr[0], fr[1]))
+        for j, (f, r) in enumerate(fused[:k]):
+            out_f[q, j], out_i[q, j] = f, r
+            out_d[q, j], out_k[q, j] = rd.get(r, np.nan), rk.get(r, np.nan)
+    return out_f, out_i, out_d, out_k
+
+
+class KeywordIndex:
+    """This rank's BM25 impact index in HBM (CSR by term) and its top-n search through `arx_bm25_search`."""
+
+    def __init__(self, pieces: Optional[Sequence[Sequence[int]]] = None, texts: Optional[Sequence[str]] = None, tokenizer=None,
+                 vocab_size: Optional[int] = None, stats: Optional[KeywordStats] = None, idx_base: int = 0, device="cuda:0"):
+        """`pieces` (word-piece id lists) or `texts` + `tokenizer`.  `stats`: the GLOBAL statistics when this index is one shard of a
+        larger corpus (None = this shard's own; "global" = this shard's own summed over all ranks of the host group).  Row r of the
+        index is global row `idx_base + r`."""
+        if pieces is None:
+            if texts is None or tokenizer is None:
+                raise ValueError("pass pieces, or texts with a tokenizer")
+            pieces = tokenizer._full_pieces(list(texts))
+        if vocab_size is None:
+            if tokenizer is None:
+                raise ValueError("vocab_size is needed when no tokenizer is given")
+            vocab_size = int(tokenizer.cfg.vocab_size)
+        term_ptr, rows, tf, dl = build_postings(pieces, int(vocab_size))
+        self._setup(term_ptr, rows, tf, dl, int(vocab_size), stats, idx_base, device, tokenizer)
+
+    @classmethod
+    def from_postings(cls, term_ptr: np.ndarray, rows: np.ndarray, tf: np.ndarray, dl: np.ndarray, stats: Optional[KeywordStats] = None,
+                      idx_base: int = 0, device="cuda:0", tokenizer=None) -> "KeywordIndex":
+        """An index over postings the caller already holds in `build_postings`' layout (synthetic corpora of the benchmark)."""
+        self = cls.__new__(cls)
+        self._setup(np.asarray(term_ptr, np.int64), np.asarray(rows, np.uint32), np.asarray(tf, np.int32), np.asarray(dl, np.int64),
+                    len(term_ptr) - 1, stats, idx_base, device, tokenizer)
+        return self
+
+    def _setup(self, term_ptr, rows, tf, dl, vocab_size, stats, idx_base, device, tokenizer):
+        import torch
+        from . import _lib
+        self.lib = _lib.load()
+        self.tokenizer, self.vocab_size, self.idx_base = tokenizer, int(vocab_size), int(idx_base)
+        self.local_stats = KeywordStats.from_postings(term_ptr, dl)
+        if isinstance(stats, str):
+            if stats != "global":
+                raise ValueError(f"stats={stats!r}: a KeywordStats, None or \"global\"")
+            stats = self.local_stats.all_reduce(_host_group())
+        self.stats = stats if stats is not None else self.local_stats
+        if self.stats.df.shape[0] != self.vocab_size:
+            raise ValueError("statistics are for another vocabulary size")
+        w64 = impacts_f64(term_ptr, rows, tf, dl, self.stats)
+        self.n_rows, self.n_postings = len(dl), len(rows)
+        self.device = torch.device(device)
+        self.term_ptr_host = term_ptr
+        self.term_ptr = torch.from_numpy(term_ptr).to(self.device)
+        # (never zero-sized device buffers: the C ABI wants non-null pointers even for a shard without postings)
+        self.post_row = torch.from_numpy(np.ascontiguousarray(rows if len(rows) else np.zeros(1, np.uint32)).view(np.int32)).to(self.device)
+        self.post_w = torch.from_numpy(np.ascontiguousarray(w64.astype(np.float32) if len(rows) else np.zeros(1, np.float32))).to(self.device)
+        self._ws = None
+
+    # ---- queries ------------------------------------------------------------------------------------------------------------
+    def query_terms(self, texts: Sequence[str]) -> List[List[int]]:
+        if self.tokenizer is None:
+            raise ValueError("this index was built without a tokenizer: pass term lists")
+        return query_terms(self.tokenizer, texts)
+
+    def _term_lists(self, queries) -> List[List[int]]:
+        queries = list(queries)
+        if queries and all(isinstance(q, str) for q in queries):
+            return self.query_terms(queries)
+        return [list(q) for q in queries]
+
+    def posting_bytes(self, term_lists: Sequence[Sequence[int]]) -> np.ndarray:
+        """Bytes of posting lists (row + impact, 8 per posting) each query's terms cover: the kernel's streaming work."""
+        ln = np.diff(self.term_ptr_host)
+        return np.array([8 * int(ln[np.asarray(list(t), np.int64)].sum()) if len(t) else 0 for t in term_lists], np.int64)
+
+    def search(self, queries, n: int = MAX_N, tile_rows: int = 0, max_blocks: int = 0):
+        """`queries`: texts, or term-id lists (strictly ascending).  -> (scores f32 [nq, n], ids int64 [nq, n]) on the device; unused
+        slots are (-inf, -1).  `tile_rows` / `max_blocks` choose the launch shape (tests, tuning): the answer's bits do not depend on it."""
+        import torch
+        from . import _lib
+        if not (1 <= n <= MAX_N):
+            raise ValueError(f"n={n} must be in [1, {MAX_N}]")
+        qt, qn = pack_query_terms(self._term_lists(queries), self.vocab_size)
+        nq = len(qn)
+        out_s = torch.full((nq, n), float("-inf"), dtype=torch.float32, device=self.device)
+        out_i = torch.full((nq, n), -1, dtype=torch.int64, device=self.device)
+        if nq == 0 or self.n_rows == 0:
+            return out_s, out_i
+        qt_d, qn_d = torch.from_numpy(qt).to(self.device), torch.from_numpy(qn).to(self.device)
+        step = 4096
+        need = self.lib.arx_bm25_workspace_bytes(self.n_rows, min(nq, step), n)
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        st = torch.cuda.current_stream(self.device).cuda_stream
+        for a in range(0, nq, step):
+            b = min(nq, a + step)
+            rc = self.lib.arx_bm25_search_tuned(self.term_ptr.data_ptr(), self.post_row.data_ptr(), self.post_w.data_ptr(), self.vocab_size,
+                                                self.n_rows, qt_d[a:b].data_ptr(), qn_d[a:b].data_ptr(), b - a, n, out_s[a:b].data_ptr(),
+                                                out_i[a:b].data_ptr(), self.idx_base, self._ws.data_ptr(), self._ws.numel(),
+                                                int(tile_rows), int(max_blocks), st)
+            _lib.check(rc, "arx_bm25_search")
+        return out_s, out_i
+
+    def search_distributed(self, queries, n: int = MAX_N, group=None):
+        """Every rank passes the SAME queries; returns the global keyword top-n on every rank (local top-n -> all-gather -> merge kernel,
+        as `ShardIndex.search_distributed`)."""
+        import torch.distributed as dist
+        from .index import gather_partials, merge_partials
+        s, i = self.search(queries, n)
+        if not dist.is_initialized() or s.shape[0] == 0:
+            return s, i
+        all_s, all_i = gather_partials(s, i, group)
+        return merge_partials(all_s, all_i, n)
+
+    def scores(self, terms: Sequence[int], row_lo: int = 0, row_hi: Optional[int] = None, tile_rows: int = 0):
+        """Debug tap: the f32 score of every row of [row_lo, row_hi) for ONE query's term list (0 = holds none of its terms)."""
+        import torch
+        from . import _lib
+        row_hi = self.n_rows if row_hi is None else row_hi
+        qt, qn = pack_query_terms([terms], self.vocab_size)
+        out = torch.empty(row_hi - row_lo, dtype=torch.float32, device=self.device)
+        qt_d = torch.from_numpy(qt).to(self.device)
+        rc = self.lib.arx_bm25_scores(self.term_ptr.data_ptr(), self.post_row.data_ptr(), self.post_w.data_ptr(), self.vocab_size, self.n_rows,
+                                      qt_d.data_ptr(), int(qn[0]), row_lo, row_hi, int(tile_rows), out.data_ptr(),
+                                      torch.cuda.current_stream(self.device).cuda_stream)
+        _lib.check(rc, "arx_bm25_scores")
+        return out

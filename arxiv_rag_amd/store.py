@@ -74,7 +74,9 @@ class HipCollection:
     """This rank's shard of the corpus, resident in HBM, with a Chroma-shaped `query`."""
 
     def __init__(self, embeddings: np.ndarray, metadata: Sequence[Dict], device="cuda:0", encoder=None,
-                 rank: int = 0, world: int = 1, chunk_rows: int = 1 << 18):
+                 rank: int = 0, world: int = 1, chunk_rows: int = 1 << 18, keyword: bool = False, tokenizer=None):
+        """`keyword=True`: also build a BM25 `keyword.KeywordIndex` over this shard's `metadata[i]["text"]` (word pieces of `tokenizer`,
+        default the encoder's; corpus statistics summed over all ranks when `world > 1`), which `query(hybrid_alpha=...)` needs."""
         import torch
         from .index import ShardIndex, shard_bounds
         n, d = embeddings.shape
@@ -89,6 +91,14 @@ class HipCollection:
         dim = int(shard.shape[1]) if shard.dim() == 2 else 0
         self.index = ShardIndex(shard, idx_base=lo, prefilter="int8" if (dim % 128 == 0 and 0 < dim <= 1024 and shard.shape[0] > 0) else None,
                                 adaptive=True)
+        self.keyword = None
+        if keyword:
+            from .keyword import KeywordIndex
+            tokenizer = tokenizer if tokenizer is not None else getattr(encoder, "tokenizer", None)
+            if tokenizer is None:
+                raise ValueError("keyword=True needs a tokenizer (or an encoder that has one)")
+            self.keyword = KeywordIndex(texts=[metadata[r].get("text") or "" for r in range(lo, hi)], tokenizer=tokenizer,
+                                        stats="global" if world > 1 else None, idx_base=lo, device=device)
 
     @classmethod
     def from_disk(cls, input_dir, **kw) -> "HipCollection":
@@ -99,11 +109,24 @@ class HipCollection:
         return self.n_total
 
     def query(self, query_embeddings=None, query_texts: Optional[Sequence[str]] = None, n_results: int = 10, reranker=None,
-              n_candidates: int = 32) -> Dict:
+              n_candidates: int = 32, hybrid_alpha: Optional[float] = None) -> Dict:
         """`reranker` (a `rerank.HipCrossEncoder`; needs `query_texts`): the search fetches `n_candidates` (<= 32) rows per query,
         the cross-encoder scores (query, document) for each, and the best `n_results` come back in reranked order with an added
-        `rerank_scores` list per query (`scores` / `distances` stay the cosine ones)."""
+        `rerank_scores` list per query (`scores` / `distances` stay the cosine ones).
+        `hybrid_alpha` (a float in [0, 1]; needs `query_texts` and a collection built with `keyword=True`; None = cosine only): the
+        cosine search and the BM25 keyword search each fetch `n_candidates` (<= 32) rows per query, `keyword.fuse` ranks their union by
+        `alpha * normalised cosine + (1 - alpha) * normalised BM25` and the best `n_results` come back with added `hybrid_scores` and
+        `keyword_scores` lists.  `scores` / `distances` stay the cosine ones where the row came from the dense list and are nan where
+        it came from the keyword list only (`keyword_scores` is nan where the row was not in the keyword list).  With `reranker` as
+        well, the cross-encoder receives the fused top `n_candidates` instead of the dense ones."""
         import torch
+        if hybrid_alpha is not None:
+            if not (0.0 <= float(hybrid_alpha) <= 1.0):
+                raise ValueError(f"hybrid_alpha={hybrid_alpha} must be in [0, 1]")
+            if query_texts is None or self.keyword is None:
+                raise ValueError("hybrid search needs query_texts and a collection built with keyword=True")
+            if not (n_results <= n_candidates <= 32):
+                raise ValueError(f"n_candidates={n_candidates} must be in [n_results, 32] (the candidate lists' length limit)")
         if reranker is not None:
             if query_texts is None:
                 raise ValueError("reranking needs query_texts")
@@ -116,8 +139,14 @@ class HipCollection:
         q = torch.from_numpy(np.ascontiguousarray(query_embeddings, dtype=np.float16)).to(self.index.corpus.device)
         if q.dim() == 1:
             q = q[None]
-        s, i = self.index.search_distributed(q, n_candidates if reranker is not None else n_results)
+        s, i = self.index.search_distributed(q, n_candidates if (reranker is not None or hybrid_alpha is not None) else n_results)
         s, i = s.cpu().numpy(), i.cpu().numpy()
+        hyb = kws = None
+        if hybrid_alpha is not None:
+            from .keyword import fuse
+            ks, ki = self.keyword.search_distributed(list(query_texts), n_candidates)
+            hyb, i, s, kws = fuse(s, i, ks.cpu().numpy(), ki.cpu().numpy(), float(hybrid_alpha),
+                                  n_candidates if reranker is not None else n_results)
         if reranker is not None:
             from .rerank import rerank_candidates, reorder_by_rerank
             texts = {int(j): self.metadata[int(j)].get("text") or "" for j in np.unique(i) if j >= 0}
@@ -130,6 +159,9 @@ class HipCollection:
             for qi, p in enumerate(picked):
                 for r, (pos, j, _) in enumerate(p):
                     s2[qi, r], i2[qi, r] = s[qi, pos], j
+            if hyb is not None:
+                hyb = np.array([[hyb[qi, p[r][0]] if r < len(p) else -np.inf for r in range(width)] for qi, p in enumerate(picked)])
+                kws = np.array([[kws[qi, p[r][0]] if r < len(p) else np.nan for r in range(width)] for qi, p in enumerate(picked)])
             s, i = s2, i2
         out = {"ids": [], "distances": [], "scores": [], "documents": [], "metadatas": [], "indices": []}
         for qi in range(q.shape[0]):
@@ -144,4 +176,7 @@ class HipCollection:
             out["metadatas"].append([{k: m.get(k) for k in ("paper_id", "section", "quality_score")} for m in ms])
         if reranker is not None:
             out["rerank_scores"] = rr
+        if hyb is not None:
+            out["hybrid_scores"] = [hyb[qi][i[qi] >= 0].tolist() for qi in range(q.shape[0])]
+            out["keyword_scores"] = [kws[qi][i[qi] >= 0].tolist() for qi in range(q.shape[0])]
         return out

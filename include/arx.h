@@ -261,6 +261,34 @@ int32_t arx_debug_cu_census(uint32_t* out, int32_t n_blocks, int32_t spin_cycles
 int32_t arx_topk_merge(const float* scores, const int64_t* ids, int32_t n_parts, int32_t n_queries,
                        int32_t k, float* out_scores, int64_t* out_ids, void* stream);
 
+/* ---- BM25 keyword top-n (hybrid search: `retrieval.use_hybrid_search`, 3-chunks/pipeline/config.yaml:67-68) ----------------
+ * Index of one shard, device memory, built by the caller (arxiv_rag_amd/keyword.py):
+ *   term_ptr int64 [vocab + 1]   CSR by term: postings of term t are [term_ptr[t], term_ptr[t + 1])
+ *   post_row uint32 [P]          shard-local row of the posting, strictly ascending within a term
+ *   post_w   f32 [P]             its impact idf(t) * tf * (k1 + 1) / (tf + k1 * (1 - b + b * dl / avgdl)) > 0 (float64 on the host, rounded once)
+ * A query is its distinct term ids: q_terms device int32 [n_queries, 64], strictly ascending, -1 padded; q_nterms device int32
+ * [n_queries], each in 0..64 (ascending order and ids inside [0, vocab) are the caller's contract; a term outside the vocabulary has
+ * no postings).  bm25(q, d) = sum of the impacts of q's terms in d, added in ascending term order in f32 without atomics: a row's
+ * score depends on the index and the query's terms only, never on the tile size, the block count or the other queries of the call.
+ * Output, per query: the n <= 32 rows with the largest (score desc, row asc) among rows holding at least one query term, as
+ * (f32 score, int64 idx_base + row); unused slots are (-inf, -1), the convention of arx_topk_search, so per-shard lists merge
+ * through arx_topk_merge.  ws: device scratch of arx_bm25_workspace_bytes(n_rows, n_queries, n) bytes (the per-block partial lists). */
+int64_t arx_bm25_workspace_bytes(int64_t n_rows, int32_t n_queries, int32_t n);
+int32_t arx_bm25_search(const int64_t* term_ptr, const uint32_t* post_row, const float* post_w, int32_t vocab, int64_t n_rows,
+                        const int32_t* q_terms, const int32_t* q_nterms, int32_t n_queries, int32_t n, float* out_scores,
+                        int64_t* out_ids, int64_t idx_base, void* ws, int64_t ws_bytes, void* stream);
+/* The same search with the launch shape chosen by the caller (tests, tuning): tile_rows = accumulator rows per LDS tile (a multiple
+ * of 1024 in [1024, 12288]; 0 = default), max_blocks = cap on the blocks per query (0 = default).  Same bits for every choice. */
+int32_t arx_bm25_search_tuned(const int64_t* term_ptr, const uint32_t* post_row, const float* post_w, int32_t vocab, int64_t n_rows,
+                              const int32_t* q_terms, const int32_t* q_nterms, int32_t n_queries, int32_t n, float* out_scores,
+                              int64_t* out_ids, int64_t idx_base, void* ws, int64_t ws_bytes, int32_t tile_rows, int32_t max_blocks,
+                              void* stream);
+/* Debug tap: out (device f32 [row_hi - row_lo]) = the score of ONE query (q_terms device int32 [n_terms], ascending) for every row of
+ * [row_lo, row_hi), 0 where the row holds none of its terms; the accumulation is the search's own. */
+int32_t arx_bm25_scores(const int64_t* term_ptr, const uint32_t* post_row, const float* post_w, int32_t vocab, int64_t n_rows,
+                        const int32_t* q_terms, int32_t n_terms, int64_t row_lo, int64_t row_hi, int32_t tile_rows, float* out,
+                        void* stream);
+
 /* Raw linear layer of the path: C[M,N] (bf16) = epi(A[M,K] (bf16) x W[N,K]^T (bf16) + bias[N] (f32)),
  * mode 0 = bias, 1 = bias + erf-GELU, 2 = bias + resid[M,N] (bf16).  K % 64 == 0, N % 8 == 0.
  * `variant` selects the main-loop schedule (see csrc/encoder.hip); exposed for unit tests and tuning. */

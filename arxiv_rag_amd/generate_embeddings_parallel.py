@@ -659,7 +659,7 @@ def store_in_chroma_batched(chunks: List[Dict], embeddings: Sequence, db_path: s
 # --------------------------------------------------------------------------------------------- search (added step)
 def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[str], top_k: int = 10,
                    output_dir: str = "./embeddings_saved", chunk_base: int = 0, reranker=None, rerank_top_k: int = 32,
-                   hybrid_alpha: Optional[float] = None) -> List[Dict]:
+                   hybrid_alpha: Optional[float] = None, where: Optional[Dict] = None) -> List[Dict]:
     """Brute-force cosine top-k (config.yaml:63-64 `top_k: 10`) over the rank's fp16 rows in HBM; with
     torchrun each rank holds the contiguous row shard it encoded and the partial top-k lists are
     all-gathered over RCCL and merged.  `shard` is the `ShardSink` the encode step filled: rows [lo, hi) are already where they
@@ -675,9 +675,14 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
     each fetch HYBRID_CANDIDATES rows per query (`rerank_top_k` with a reranker), `keyword.fuse` ranks their union by
     `alpha * normalised cosine + (1 - alpha) * normalised BM25`, and the best `top_k` (with a reranker: the fused `rerank_top_k`, then
     reranked) are kept.  Every hit then carries `hybrid_score` and `keyword_score`; `score` stays the cosine one and is null, like
-    `keyword_score`, where the row was not in that side's candidate list."""
+    `keyword_score`, where the row was not in that side's candidate list.
+    `where` (a Chroma filter, see `where.compile_where`): only chunks whose `metadata` satisfies it are searched — each rank evaluates it
+    on its own `chunks`, packs the row bitmap and searches with it (`ShardIndex.search(allow=...)`: the exact top-k of the allowed rows,
+    on the fp16 rows).  Not together with `hybrid_alpha`: the keyword search has no row filter."""
     import torch
     from .index import ShardIndex
+    if where is not None and hybrid_alpha is not None:
+        raise ValueError("where cannot be combined with hybrid_alpha: the BM25 keyword search has no row filter")
     dist = _dist()
     rank = dist.get_rank() if dist else 0
     world = dist.get_world_size() if dist else 1
@@ -688,7 +693,16 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
     pre = "int8" if (shard.rows.shape[1] % 128 == 0 and shard.rows.shape[1] <= 1024 and shard.rows.shape[0] > 0) else None
     k_search = rerank_top_k if reranker is not None else top_k
     n_cand = k_search if hybrid_alpha is None else (rerank_top_k if reranker is not None else HYBRID_CANDIDATES)
-    s, i = ShardIndex(shard.rows, idx_base=shard.lo, prefilter=pre, adaptive=True).search_distributed(qd, n_cand)
+    allow = n_allowed = None
+    if where is not None:
+        from .where import compile_where, evaluate, pack_bitmap
+        mask = evaluate(compile_where(where), [c.get("metadata") or {} for c in chunks])
+        if mask.shape[0] != shard.rows.shape[0]:
+            raise ValueError(f"where: {mask.shape[0]} chunks for the shard's {shard.rows.shape[0]} rows")
+        allow, n_allowed = torch.from_numpy(pack_bitmap(mask).view(np.int64)).to(dev), int(mask.sum())
+        pre = None                                           # a filtered search runs on the fp16 rows
+    s, i = ShardIndex(shard.rows, idx_base=shard.lo, prefilter=pre, adaptive=True).search_distributed(qd, n_cand, allow=allow,
+                                                                                                       n_allowed=n_allowed)
     s, i = s.cpu().numpy(), i.cpu().numpy()
     hyb = kws = None
     if hybrid_alpha is not None:
@@ -770,6 +784,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--hybrid-alpha", type=float, default=None,
                    help="Hybrid search for --queries: weight of the cosine side in [0, 1], the BM25 keyword side gets the rest "
                         "(config.yaml hybrid_alpha: 0.7; default: off, cosine only)")
+    p.add_argument("--where", type=str, default=None,
+                   help="Chroma metadata filter for --queries as JSON, e.g. '{\"section\": \"abstract\"}' or "
+                        "'{\"quality_score\": {\"$gte\": 0.95}}': only matching chunks are searched (not with --hybrid-alpha)")
     return p
 
 
@@ -801,10 +818,30 @@ def check_hybrid_args(args) -> Optional[str]:
     return None
 
 
+def check_where_args(args) -> Optional[str]:
+    """-> an error message for an unusable --where, else None.  On success `args.where_filter` holds the parsed filter (None without --where)."""
+    args.where_filter = None
+    if args.where is None:
+        return None
+    if args.hybrid_alpha is not None:
+        return "--where cannot be combined with --hybrid-alpha: the BM25 keyword search has no row filter"
+    try:
+        parsed = json.loads(args.where)
+    except ValueError as e:
+        return f"--where is not valid JSON: {e}"
+    from .where import compile_where
+    try:
+        compile_where(parsed)
+    except ValueError as e:
+        return f"--where: {e}"
+    args.where_filter = parsed
+    return None
+
+
 def main(argv: Optional[Sequence[str]] = None, model_factory: Optional[Callable] = None) -> int:
     global _model, _model_name
     args = build_parser().parse_args(argv)
-    err = check_rerank_args(args) or check_hybrid_args(args)
+    err = check_rerank_args(args) or check_hybrid_args(args) or check_where_args(args)
     if err:
         print(f"Error: {err}")
         return 2
@@ -892,7 +929,8 @@ def main(argv: Optional[Sequence[str]] = None, model_factory: Optional[Callable]
                     from .rerank import HipCrossEncoder
                     reranker = HipCrossEncoder.from_dir(args.rerank_model, device=_model.encoder.device)
                 search_queries(_model, chunks, sink, qs, top_k=args.top_k, chunk_base=span[0] if span else 0,
-                               reranker=reranker, rerank_top_k=args.rerank_top_k, hybrid_alpha=args.hybrid_alpha)
+                               reranker=reranker, rerank_top_k=args.rerank_top_k, hybrid_alpha=args.hybrid_alpha,
+                               where=args.where_filter)
         store_time = 0.0
         if rank == 0 and not args.skip_chroma:
             try:

@@ -42,6 +42,8 @@ class ShardIndex:
         self.idx_base = int(idx_base)
         self._ws: Optional[torch.Tensor] = None            # workspace of plain `search` calls (and of the LAST call: certificate_stats)
         self._last_ws: Optional[torch.Tensor] = None
+        self._ws_filtered: Optional[torch.Tensor] = None   # workspace of `search(allow=...)` calls
+        self._last_ws_filtered: Optional[torch.Tensor] = None
         self._i8: Optional[torch.Tensor] = None
         self._i8_version = -1
         self._adaptive, self._i8_searches, self.prefilter_disabled = bool(adaptive), 0, False
@@ -135,13 +137,22 @@ class ShardIndex:
 
     # ---- one batch ------------------------------------------------------------------------------------------------------
     def search(self, queries_f16: torch.Tensor, k: int = 10, ws: Optional[torch.Tensor] = None, out=None,
-               _opt: Optional["_lib.TopkOptionsC"] = None, _stream: Optional[int] = None, **debug) -> Tuple[torch.Tensor, torch.Tensor]:
+               _opt: Optional["_lib.TopkOptionsC"] = None, _stream: Optional[int] = None, allow: Optional[torch.Tensor] = None,
+               n_allowed: Optional[int] = None, **debug) -> Tuple[torch.Tensor, torch.Tensor]:
         """queries fp16 [Q, D] (device) -> (scores f32 [Q, k], ids int64 [Q, k]); ids are global
         (local row + idx_base); score desc, ties -> lower id; (-inf, -1) pads when k > n_rows.
         `ws`: the device workspace this call uses (default: the index's own, which makes the index one-caller-at-a-time; callers that
         search one index from several host threads or streams pass their own, `alloc_workspace`).  `out = (scores, ids)` preallocated.
         `tau_mult` / `drop_best`: the certificate's test hooks, `flags`: ARX_TOPK_* (include/arx.h) — all per call; any other keyword is a
-        TypeError (a misspelled hook would otherwise be dropped and leave the caller's test vacuous)."""
+        TypeError (a misspelled hook would otherwise be dropped and leave the caller's test vacuous).
+        `allow` (a device int64 / uint64 tensor of ceil(n_rows / 64) words, bit r & 63 of word r >> 6 = local row r may be returned; see
+        `where.pack_bitmap`): the exact top-k of the ALLOWED rows only (`arx_topk_search_filtered`), ids still those of the original
+        rows, (-inf, -1) pads when fewer than k rows are allowed.  `n_allowed`: the number of allowed rows if the caller knows it (the
+        library then scores very selective filters row by row instead of scanning).  A filtered search always runs on the fp16 rows:
+        the int8 pre-filter is not used for it.  Its test hooks are `path` (1 = masked scan, 2 = exhaustive) and `cand_cap`;
+        `filtered_stats` reads its counters.  Without `allow` nothing changes."""
+        if allow is not None:
+            return self._search_filtered(queries_f16, k, allow, n_allowed, ws, out, _stream, debug)
         unknown = set(debug) - {"tau_mult", "drop_best", "flags"}
         if unknown:
             raise TypeError(f"ShardIndex.search() got unexpected keyword argument(s): {', '.join(sorted(unknown))}")
@@ -185,6 +196,53 @@ class ShardIndex:
                 self.prefilter_disabled = True
         self._i8_searches += 1 if ran_i8 else 0
         return scores, ids
+
+    def _search_filtered(self, q, k, allow, n_allowed, ws, out, _stream, debug):
+        unknown = set(debug) - {"path", "cand_cap"}
+        if unknown:
+            raise TypeError(f"ShardIndex.search(allow=...) got unexpected keyword argument(s): {', '.join(sorted(unknown))}")
+        assert q.is_cuda and q.dtype == torch.float16 and q.dim() == 2 and q.shape[1] == self.dim and q.is_contiguous()
+        n_words = (self.n_rows + 63) // 64
+        assert allow.is_cuda and allow.dtype in (torch.int64, torch.uint64) and allow.dim() == 1 and allow.is_contiguous()
+        assert allow.shape[0] == n_words, f"allow has {allow.shape[0]} words, the shard's {self.n_rows} rows need {n_words}"
+        nq = q.shape[0]
+        if out is None:
+            scores = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+            ids = torch.empty((nq, k), dtype=torch.int64, device=q.device)
+        else:
+            scores, ids = out
+            assert scores.shape == (nq, k) and ids.shape == (nq, k) and scores.is_contiguous() and ids.is_contiguous()
+        if nq == 0:
+            return scores, ids
+        if self.n_rows == 0:
+            scores.fill_(float("-inf")); ids.fill_(-1)
+            return scores, ids
+        need = self.lib.arx_topk_filtered_workspace_bytes(self.n_rows, nq, self.dim, k)
+        if need < 0:
+            raise _lib.ArxError(f"unsupported filtered search shape n_rows={self.n_rows} nq={nq} dim={self.dim} k={k}")
+        if ws is None:
+            if self._ws_filtered is None or self._ws_filtered.numel() < need:
+                self._ws_filtered = torch.empty(need, dtype=torch.uint8, device=self.corpus.device)
+            ws = self._ws_filtered
+        norm = max(self.max_row_norm(), 1.0 + 1.0 / 512.0)       # never below the encoder's unit-row bound (as `_options`)
+        st = torch.cuda.current_stream().cuda_stream if _stream is None else _stream
+        rc = self.lib.arx_topk_search_filtered_tuned(self.corpus.data_ptr(), self.n_rows, allow.data_ptr(), -1 if n_allowed is None else int(n_allowed),
+                                                     q.data_ptr(), nq, self.dim, k, scores.data_ptr(), ids.data_ptr(), self.idx_base, norm,
+                                                     ws.data_ptr(), ws.numel(), int(debug.get("path", 0)), int(debug.get("cand_cap", 0)), st)
+        _lib.check(rc, "arx_topk_search_filtered")
+        self._last_ws_filtered = ws
+        return scores, ids
+
+    def filtered_stats(self, ws: Optional[torch.Tensor] = None) -> Tuple[int, int]:
+        """(queries whose candidate list overflowed and were answered by the exhaustive path, candidate groups rescored) of the LAST
+        `search(allow=...)` on this index (or on `ws`).  Synchronises on the current stream."""
+        ws = self._last_ws_filtered if ws is None else ws
+        if ws is None:
+            return (0, 0)
+        a, b = C.c_int64(0), C.c_int64(0)
+        _lib.check(self.lib.arx_topk_filtered_stats(ws.data_ptr(), C.byref(a), C.byref(b), torch.cuda.current_stream().cuda_stream),
+                   "arx_topk_filtered_stats")
+        return (int(a.value), int(b.value))
 
     def _i8_nq_limit(self) -> int:
         """The largest query batch the int8 pass takes under this index's policy (`i8_max_queries`; None = the library default, 1 024)."""
@@ -283,10 +341,12 @@ class ShardIndex:
         self._last_ws = pipe["ws"][(nb - 1) % lanes]
         return out
 
-    def search_distributed(self, queries_f16: torch.Tensor, k: int = 10, group=None):
-        """Every rank passes the SAME queries; returns the global top-k on every rank."""
+    def search_distributed(self, queries_f16: torch.Tensor, k: int = 10, group=None, allow: Optional[torch.Tensor] = None,
+                           n_allowed: Optional[int] = None):
+        """Every rank passes the SAME queries; returns the global top-k on every rank.  `allow` / `n_allowed` (see `search`): each rank
+        filters its OWN shard with its own bitmap; the gather and the merge are the same."""
         import torch.distributed as dist
-        s, i = self.search(queries_f16, k)
+        s, i = self.search(queries_f16, k, allow=allow, n_allowed=n_allowed)
         if not dist.is_initialized():
             return s, i
         # world size 1 takes the same gather + merge path (a 1-part merge is the identity): one code path to test

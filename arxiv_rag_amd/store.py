@@ -83,6 +83,7 @@ class HipCollection:
         lo, hi = shard_bounds(n, world, rank)
         self.n_total, self.dim, self.lo, self.hi = n, d, lo, hi
         self.metadata = metadata
+        self._where_columns: Dict = {}                          # `query(where=...)`: one numpy column per referenced metadata key
         self.encoder = encoder
         shard = torch.empty((hi - lo, d), dtype=torch.float16, device=device)
         for s0 in range(lo, hi, chunk_rows):                   # stream: never a second full copy in host RAM
@@ -109,7 +110,7 @@ class HipCollection:
         return self.n_total
 
     def query(self, query_embeddings=None, query_texts: Optional[Sequence[str]] = None, n_results: int = 10, reranker=None,
-              n_candidates: int = 32, hybrid_alpha: Optional[float] = None) -> Dict:
+              n_candidates: int = 32, hybrid_alpha: Optional[float] = None, where: Optional[Dict] = None) -> Dict:
         """`reranker` (a `rerank.HipCrossEncoder`; needs `query_texts`): the search fetches `n_candidates` (<= 32) rows per query,
         the cross-encoder scores (query, document) for each, and the best `n_results` come back in reranked order with an added
         `rerank_scores` list per query (`scores` / `distances` stay the cosine ones).
@@ -118,8 +119,16 @@ class HipCollection:
         `alpha * normalised cosine + (1 - alpha) * normalised BM25` and the best `n_results` come back with added `hybrid_scores` and
         `keyword_scores` lists.  `scores` / `distances` stay the cosine ones where the row came from the dense list and are nan where
         it came from the keyword list only (`keyword_scores` is nan where the row was not in the keyword list).  With `reranker` as
-        well, the cross-encoder receives the fused top `n_candidates` instead of the dense ones."""
+        well, the cross-encoder receives the fused top `n_candidates` instead of the dense ones.
+        `where` (a Chroma filter: implicit `$eq`, `$eq $ne $gt $gte $lt $lte $in $nin`, `$and` / `$or`; `where.compile_where`): only rows
+        whose metadata satisfies it can be returned.  It is evaluated on this rank's rows, packed into a bitmap and applied INSIDE the
+        search (`ShardIndex.search(allow=...)`), so the result is the exact top-`n_results` of the satisfying rows — shorter lists when
+        fewer satisfy it.  Composes with `reranker` (the cross-encoder sees the filtered candidates).  With `hybrid_alpha` it raises
+        ValueError: the BM25 kernel has no row filter, and fusing a filtered dense list with an unfiltered keyword list would return
+        disallowed rows."""
         import torch
+        if where is not None and hybrid_alpha is not None:
+            raise ValueError("where cannot be combined with hybrid_alpha: the BM25 keyword search has no row filter")
         if hybrid_alpha is not None:
             if not (0.0 <= float(hybrid_alpha) <= 1.0):
                 raise ValueError(f"hybrid_alpha={hybrid_alpha} must be in [0, 1]")
@@ -139,7 +148,13 @@ class HipCollection:
         q = torch.from_numpy(np.ascontiguousarray(query_embeddings, dtype=np.float16)).to(self.index.corpus.device)
         if q.dim() == 1:
             q = q[None]
-        s, i = self.index.search_distributed(q, n_candidates if (reranker is not None or hybrid_alpha is not None) else n_results)
+        allow = n_allowed = None
+        if where is not None:
+            from .where import compile_where, evaluate, pack_bitmap
+            mask = evaluate(compile_where(where), self.metadata, self.lo, self.hi, cache=self._where_columns)
+            allow, n_allowed = torch.from_numpy(pack_bitmap(mask).view(np.int64)).to(q.device), int(mask.sum())
+        s, i = self.index.search_distributed(q, n_candidates if (reranker is not None or hybrid_alpha is not None) else n_results,
+                                             allow=allow, n_allowed=n_allowed)
         s, i = s.cpu().numpy(), i.cpu().numpy()
         hyb = kws = None
         if hybrid_alpha is not None:

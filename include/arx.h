@@ -261,6 +261,29 @@ int32_t arx_debug_cu_census(uint32_t* out, int32_t n_blocks, int32_t spin_cycles
 int32_t arx_topk_merge(const float* scores, const int64_t* ids, int32_t n_parts, int32_t n_queries,
                        int32_t k, float* out_scores, int64_t* out_ids, void* stream);
 
+/* ---- Filtered exact top-k (Chroma's `where`): arx_topk_search over the sub-corpus of ALLOWED rows ------------------------------
+ * allow: device uint64 [ceil(n_rows / 64)], bit (r & 63) of word (r >> 6) set = row r may be returned; bits at or beyond n_rows are
+ * ignored.  One filter per call, shared by its queries.  Semantics exactly those of arx_topk_search over the allowed rows with ids of
+ * the ORIGINAL rows (idx_base + r): score descending, ties to the lower row, (-inf, -1) padding when fewer than k rows are allowed.
+ * n_allowed: the number of set bits below n_rows if the caller knows it, -1 if not.  max_row_norm: what arx_topk_options.max_row_norm is, 0 = unit
+ * rows.  dim % 64 == 0, k <= 32, any n_queries.  Two device paths with the same bits (csrc/filter.hip): the masked scan (pass A with
+ * the filter in front of the group maximum; tiles without an allowed row are not read) and the exhaustive scoring of the compacted
+ * list of allowed rows, which the library takes by itself for small n_allowed * n_queries and for any query whose candidate list
+ * overflows.  ws: device workspace of arx_topk_filtered_workspace_bytes(...) bytes, caller-owned. */
+int64_t arx_topk_filtered_workspace_bytes(int64_t n_rows, int32_t n_queries, int32_t dim, int32_t k);
+int32_t arx_topk_search_filtered(const void* corpus, int64_t n_rows, const uint64_t* allow, int64_t n_allowed, const void* queries,
+                                 int32_t n_queries, int32_t dim, int32_t k, float* out_scores, int64_t* out_ids, int64_t idx_base,
+                                 float max_row_norm, void* ws, int64_t ws_bytes, void* stream);
+/* The same with the path and the candidate capacity chosen by the caller (tests, tuning): path 0 = library's choice, 1 = masked scan,
+ * 2 = exhaustive over the allowed rows; cand_cap = candidate groups a query may list before it goes to the exhaustive path (0 =
+ * default, at most 8192).  Same bits for every choice. */
+int32_t arx_topk_search_filtered_tuned(const void* corpus, int64_t n_rows, const uint64_t* allow, int64_t n_allowed, const void* queries,
+                                       int32_t n_queries, int32_t dim, int32_t k, float* out_scores, int64_t* out_ids, int64_t idx_base,
+                                       float max_row_norm, void* ws, int64_t ws_bytes, int32_t path, int32_t cand_cap, void* stream);
+/* {queries sent to the exhaustive path because their candidate list overflowed, candidate groups rescored} of the LAST filtered
+ * search on this workspace.  Copies 16 bytes to the host and waits on `stream`. */
+int32_t arx_topk_filtered_stats(const void* ws, int64_t* overflowed_queries, int64_t* candidate_groups, void* stream);
+
 /* ---- BM25 keyword top-n (hybrid search: `retrieval.use_hybrid_search`, 3-chunks/pipeline/config.yaml:67-68) ----------------
  * Index of one shard, device memory, built by the caller (arxiv_rag_amd/keyword.py):
  *   term_ptr int64 [vocab + 1]   CSR by term: postings of term t are [term_ptr[t], term_ptr[t + 1])

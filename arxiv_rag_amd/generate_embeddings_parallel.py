@@ -659,7 +659,8 @@ def store_in_chroma_batched(chunks: List[Dict], embeddings: Sequence, db_path: s
 # --------------------------------------------------------------------------------------------- search (added step)
 def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[str], top_k: int = 10,
                    output_dir: str = "./embeddings_saved", chunk_base: int = 0, reranker=None, rerank_top_k: int = 32,
-                   hybrid_alpha: Optional[float] = None, where: Optional[Dict] = None) -> List[Dict]:
+                   hybrid_alpha: Optional[float] = None, where: Optional[Dict] = None,
+                   where_document: Optional[Dict] = None) -> List[Dict]:
     """Brute-force cosine top-k (config.yaml:63-64 `top_k: 10`) over the rank's fp16 rows in HBM; with
     torchrun each rank holds the contiguous row shard it encoded and the partial top-k lists are
     all-gathered over RCCL and merged.  `shard` is the `ShardSink` the encode step filled: rows [lo, hi) are already where they
@@ -678,11 +679,17 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
     `keyword_score`, where the row was not in that side's candidate list.
     `where` (a Chroma filter, see `where.compile_where`): only chunks whose `metadata` satisfies it are searched — each rank evaluates it
     on its own `chunks`, packs the row bitmap and searches with it (`ShardIndex.search(allow=...)`: the exact top-k of the allowed rows,
-    on the fp16 rows).  Not together with `hybrid_alpha`: the keyword search has no row filter."""
+    on the fp16 rows).  Not together with `hybrid_alpha`: the keyword search has no row filter.
+    `where_document` (a Chroma document filter, see `where_document.compile_where_document`): only chunks whose `text` satisfies it
+    (`$contains` / `$not_contains`, case-sensitive substrings) are searched — each rank uploads the texts of its own `chunks`, scans them
+    on the device (`arx_text_contains`) and searches with the resulting bitmap, and-ed with the one of `where` if both are given; nothing
+    new crosses ranks.  Not together with `hybrid_alpha` either."""
     import torch
     from .index import ShardIndex
     if where is not None and hybrid_alpha is not None:
         raise ValueError("where cannot be combined with hybrid_alpha: the BM25 keyword search has no row filter")
+    if where_document is not None and hybrid_alpha is not None:
+        raise ValueError("where_document cannot be combined with hybrid_alpha: the BM25 keyword search has no row filter")
     dist = _dist()
     rank = dist.get_rank() if dist else 0
     world = dist.get_world_size() if dist else 1
@@ -701,6 +708,18 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
             raise ValueError(f"where: {mask.shape[0]} chunks for the shard's {shard.rows.shape[0]} rows")
         allow, n_allowed = torch.from_numpy(pack_bitmap(mask).view(np.int64)).to(dev), int(mask.sum())
         pre = None                                           # a filtered search runs on the fp16 rows
+    if where_document is not None:
+        from .where_document import DocumentStore, compile_where_document
+        doc_tree = compile_where_document(where_document)
+        if len(chunks) != shard.rows.shape[0]:
+            raise ValueError(f"where_document: {len(chunks)} chunks for the shard's {shard.rows.shape[0]} rows")
+        docs = DocumentStore([c["text"] for c in chunks], device=dev)
+        if allow is None:
+            allow, n_allowed = docs.allow(doc_tree)
+        else:
+            allow = (allow & docs.fold(doc_tree)).contiguous()
+            n_allowed = docs.count(allow)
+        pre = None
     s, i = ShardIndex(shard.rows, idx_base=shard.lo, prefilter=pre, adaptive=True).search_distributed(qd, n_cand, allow=allow,
                                                                                                        n_allowed=n_allowed)
     s, i = s.cpu().numpy(), i.cpu().numpy()
@@ -787,6 +806,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--where", type=str, default=None,
                    help="Chroma metadata filter for --queries as JSON, e.g. '{\"section\": \"abstract\"}' or "
                         "'{\"quality_score\": {\"$gte\": 0.95}}': only matching chunks are searched (not with --hybrid-alpha)")
+    p.add_argument("--where-document", type=str, default=None,
+                   help="Chroma document filter for --queries as JSON, e.g. '{\"$contains\": \"Lipschitz\"}' or "
+                        "'{\"$and\": [{\"$contains\": \"graph\"}, {\"$not_contains\": \"lemma\"}]}': only chunks whose text "
+                        "satisfies it are searched (case-sensitive substrings, scanned on the GPU; not with --hybrid-alpha)")
     return p
 
 
@@ -838,10 +861,31 @@ def check_where_args(args) -> Optional[str]:
     return None
 
 
+def check_where_document_args(args) -> Optional[str]:
+    """-> an error message for an unusable --where-document, else None.  On success `args.where_document_filter` holds the parsed filter
+    (None without --where-document)."""
+    args.where_document_filter = None
+    if args.where_document is None:
+        return None
+    if args.hybrid_alpha is not None:
+        return "--where-document cannot be combined with --hybrid-alpha: the BM25 keyword search has no row filter"
+    try:
+        parsed = json.loads(args.where_document)
+    except ValueError as e:
+        return f"--where-document is not valid JSON: {e}"
+    from .where_document import compile_where_document
+    try:
+        compile_where_document(parsed)
+    except ValueError as e:
+        return f"--where-document: {e}"
+    args.where_document_filter = parsed
+    return None
+
+
 def main(argv: Optional[Sequence[str]] = None, model_factory: Optional[Callable] = None) -> int:
     global _model, _model_name
     args = build_parser().parse_args(argv)
-    err = check_rerank_args(args) or check_hybrid_args(args) or check_where_args(args)
+    err = check_rerank_args(args) or check_hybrid_args(args) or check_where_args(args) or check_where_document_args(args)
     if err:
         print(f"Error: {err}")
         return 2
@@ -930,7 +974,7 @@ def main(argv: Optional[Sequence[str]] = None, model_factory: Optional[Callable]
                     reranker = HipCrossEncoder.from_dir(args.rerank_model, device=_model.encoder.device)
                 search_queries(_model, chunks, sink, qs, top_k=args.top_k, chunk_base=span[0] if span else 0,
                                reranker=reranker, rerank_top_k=args.rerank_top_k, hybrid_alpha=args.hybrid_alpha,
-                               where=args.where_filter)
+                               where=args.where_filter, where_document=args.where_document_filter)
         store_time = 0.0
         if rank == 0 and not args.skip_chroma:
             try:

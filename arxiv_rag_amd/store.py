@@ -74,9 +74,12 @@ class HipCollection:
     """This rank's shard of the corpus, resident in HBM, with a Chroma-shaped `query`."""
 
     def __init__(self, embeddings: np.ndarray, metadata: Sequence[Dict], device="cuda:0", encoder=None,
-                 rank: int = 0, world: int = 1, chunk_rows: int = 1 << 18, keyword: bool = False, tokenizer=None):
+                 rank: int = 0, world: int = 1, chunk_rows: int = 1 << 18, keyword: bool = False, tokenizer=None,
+                 documents: bool = False):
         """`keyword=True`: also build a BM25 `keyword.KeywordIndex` over this shard's `metadata[i]["text"]` (word pieces of `tokenizer`,
-        default the encoder's; corpus statistics summed over all ranks when `world > 1`), which `query(hybrid_alpha=...)` needs."""
+        default the encoder's; corpus statistics summed over all ranks when `world > 1`), which `query(hybrid_alpha=...)` needs.
+        `documents=True`: also keep this shard's texts as a UTF-8 blob in HBM (`where_document.DocumentStore`), which
+        `query(where_document=...)` scans."""
         import torch
         from .index import ShardIndex, shard_bounds
         n, d = embeddings.shape
@@ -100,6 +103,10 @@ class HipCollection:
                 raise ValueError("keyword=True needs a tokenizer (or an encoder that has one)")
             self.keyword = KeywordIndex(texts=[metadata[r].get("text") or "" for r in range(lo, hi)], tokenizer=tokenizer,
                                         stats="global" if world > 1 else None, idx_base=lo, device=device)
+        self.documents = None
+        if documents:
+            from .where_document import DocumentStore
+            self.documents = DocumentStore([metadata[r].get("text") or "" for r in range(lo, hi)], device=device)
 
     @classmethod
     def from_disk(cls, input_dir, **kw) -> "HipCollection":
@@ -110,7 +117,8 @@ class HipCollection:
         return self.n_total
 
     def query(self, query_embeddings=None, query_texts: Optional[Sequence[str]] = None, n_results: int = 10, reranker=None,
-              n_candidates: int = 32, hybrid_alpha: Optional[float] = None, where: Optional[Dict] = None) -> Dict:
+              n_candidates: int = 32, hybrid_alpha: Optional[float] = None, where: Optional[Dict] = None,
+              where_document: Optional[Dict] = None) -> Dict:
         """`reranker` (a `rerank.HipCrossEncoder`; needs `query_texts`): the search fetches `n_candidates` (<= 32) rows per query,
         the cross-encoder scores (query, document) for each, and the best `n_results` come back in reranked order with an added
         `rerank_scores` list per query (`scores` / `distances` stay the cosine ones).
@@ -125,8 +133,20 @@ class HipCollection:
         search (`ShardIndex.search(allow=...)`), so the result is the exact top-`n_results` of the satisfying rows — shorter lists when
         fewer satisfy it.  Composes with `reranker` (the cross-encoder sees the filtered candidates).  With `hybrid_alpha` it raises
         ValueError: the BM25 kernel has no row filter, and fusing a filtered dense list with an unfiltered keyword list would return
-        disallowed rows."""
+        disallowed rows.
+        `where_document` (`{"$contains": s}`, `{"$not_contains": s}`, `$and` / `$or`; `where_document.compile_where_document`; needs a
+        collection built with `documents=True`): only rows whose text satisfies it (case-sensitive substring) can be returned.  The texts
+        of this rank's rows are scanned on the device (`arx_text_contains`), the tree is folded over the pattern bitmaps there, and the
+        resulting bitmap goes to the same filtered search as `where`; with `where` as well the two bitmaps are and-ed on the device.
+        Composes with `reranker`; with `hybrid_alpha` it raises ValueError for the same reason as `where`."""
         import torch
+        if where_document is not None:
+            if hybrid_alpha is not None:
+                raise ValueError("where_document cannot be combined with hybrid_alpha: the BM25 keyword search has no row filter")
+            if self.documents is None:
+                raise ValueError("where_document needs a collection built with documents=True")
+            from .where_document import compile_where_document
+            doc_tree = compile_where_document(where_document)
         if where is not None and hybrid_alpha is not None:
             raise ValueError("where cannot be combined with hybrid_alpha: the BM25 keyword search has no row filter")
         if hybrid_alpha is not None:
@@ -153,6 +173,12 @@ class HipCollection:
             from .where import compile_where, evaluate, pack_bitmap
             mask = evaluate(compile_where(where), self.metadata, self.lo, self.hi, cache=self._where_columns)
             allow, n_allowed = torch.from_numpy(pack_bitmap(mask).view(np.int64)).to(q.device), int(mask.sum())
+        if where_document is not None:
+            if allow is None:
+                allow, n_allowed = self.documents.allow(doc_tree)
+            else:
+                allow = (allow & self.documents.fold(doc_tree)).contiguous()
+                n_allowed = self.documents.count(allow)
         s, i = self.index.search_distributed(q, n_candidates if (reranker is not None or hybrid_alpha is not None) else n_results,
                                              allow=allow, n_allowed=n_allowed)
         s, i = s.cpu().numpy(), i.cpu().numpy()

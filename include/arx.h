@@ -284,6 +284,24 @@ int32_t arx_topk_search_filtered_tuned(const void* corpus, int64_t n_rows, const
  * search on this workspace.  Copies 16 bytes to the host and waits on `stream`. */
 int32_t arx_topk_filtered_stats(const void* ws, int64_t* overflowed_queries, int64_t* candidate_groups, void* stream);
 
+/* ---- Substring scan over the chunk texts (Chroma's `where_document`: `$contains` / `$not_contains`) -----------------------------
+ * The producer of the row bitmaps arx_topk_search_filtered takes (csrc/textscan.hip).
+ * out_bits[p][w] bit (r & 63) of word w = r >> 6  <=>  pattern p occurs in row r, entirely inside
+ * [row_off[r], row_off[r+1]).  Bits at or beyond n_rows are written as 0.  Every word of out_bits is written:
+ * the result does not depend on what the buffer held before.  Bytes compare as bytes (case-sensitive; on well-formed UTF-8 a byte
+ * substring is a code-point substring).
+ *   blob     device uint8 [row_off[n_rows]]       the shard's texts, concatenated, no separators (a valid pointer even if empty)
+ *   row_off  device int64 [n_rows + 1]            ascending, row_off[0] == 0; empty rows allowed
+ *   pat_blob device uint8, pat_off device int32 [n_pat + 1]; every pattern 1..256 bytes; 1 <= n_pat <= 32
+ *   out_bits device uint64 [n_pat, ceil(n_rows / 64)]
+ * Pattern lengths are device data and the caller's contract (a length outside 1..256 matches no row); a pattern longer than a row
+ * cannot match it.  One launch on `stream`, no atomics, no workspace. */
+int32_t arx_text_contains(const uint8_t* blob, const int64_t* row_off, int64_t n_rows,
+                          const uint8_t* pat_blob, const int32_t* pat_off, int32_t n_pat,
+                          uint64_t* out_bits, void* stream);
+/* *out_count (ONE device int64) = set bits of bits[0 .. ceil(n_rows/64)) that name rows below n_rows. */
+int32_t arx_bitmap_count(const uint64_t* bits, int64_t n_rows, int64_t* out_count, void* stream);
+
 /* ---- BM25 keyword top-n (hybrid search: `retrieval.use_hybrid_search`, 3-chunks/pipeline/config.yaml:67-68) ----------------
  * Index of one shard, device memory, built by the caller (arxiv_rag_amd/keyword.py):
  *   term_ptr int64 [vocab + 1]   CSR by term: postings of term t are [term_ptr[t], term_ptr[t + 1])

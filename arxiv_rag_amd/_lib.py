@@ -51,6 +51,18 @@ class PairHeadC(C.Structure):
         self.struct_bytes = C.sizeof(PairHeadC)
 
 
+class GemmEpilogueC(C.Structure):
+    """arx_gemm_epilogue (include/arx.h): the epilogue of one arx_gemm_bf16_ex call (parity tap)."""
+    _fields_ = [("struct_bytes", C.c_int32), ("mode", C.c_int32), ("variant", C.c_int32), ("eps", C.c_float)] \
+               + [(n, C.c_void_p) for n in ("bias", "resid", "a_mean", "a_rstd", "s_vec", "r_mean", "r_rstd", "r_gamma", "r_beta")] \
+               + [("row_cap", C.c_int64), ("part_sum", C.c_void_p), ("part_sq", C.c_void_p), ("part_ld", C.c_int64),
+                  ("out_mean", C.c_void_p), ("out_rstd", C.c_void_p), ("n_rows", C.c_void_p)]
+
+    def __init__(self, **kw):
+        super().__init__(**kw)
+        self.struct_bytes = C.sizeof(GemmEpilogueC)
+
+
 TOPK_NO_PERSISTENT, TOPK_SCAN_ONLY, TOPK_TAIL_ONLY, TOPK_NO_SINGLE_ROW_TAIL, TOPK_I8_CENTRE_QUERY = 1, 2, 4, 8, 16
 
 
@@ -114,6 +126,10 @@ EXPORTS = {
                                     C.c_int32, C.c_void_p, C.c_void_p]),
     "arx_gemm_bf16": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                   C.c_int32, C.c_int32, C.c_void_p]),
+    "arx_gemm_bf16_ex": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(GemmEpilogueC),
+                                     C.c_void_p]),
+    "arx_fold_ln": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                C.c_void_p]),
     "arx_prof_classes": (C.c_int32, [C.c_uint32]),
     "arx_wp_create": (C.c_int32, [C.c_char_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                   C.c_char_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]),

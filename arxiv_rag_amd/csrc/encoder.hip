@@ -567,6 +567,89 @@ static void launch_ln_finalize(int T, int nparts, const float* ps, const float* 
     }
 }
 
+// ---- parity taps for the LayerNorm-fold epilogues ---------------------------------------------------------------------------------
+// One linear layer with ANY epilogue mode of gemm.h, through the forward's own launch_gemm<MODE> (and, for the statistics modes on the
+// tile kernels, its launch_ln_finalize with inv_h = 1 / N): what encoder_run does per layer, on caller-provided operands.
+template <int MODE>
+static int gemm_ex_run(int variant, const uint16_t* A, const uint16_t* W, int M, int N, int K, const EpiParams& ep, const arx_gemm_epilogue* e,
+                       hipStream_t st) {
+    constexpr bool STATS = (MODE == EPI_RESID_STATS || MODE == EPI_LNRESID_STATS);
+    int rc;
+    if (variant == 70) {          // a stream-ordered scratch for this call, released behind its kernels (as arx_gemm_bf16)
+        float* ws = nullptr;
+        ARX_HIP_CHECK(hipMallocAsync((void**)&ws, ARX_SMALL_WS_BYTES, st));
+        rc = launch_gemm<MODE>(ARX_K_GEMM_RAW, variant, A, K, W, K, M, N, K, ep, st, ws);
+        (void)hipFreeAsync(ws, st);
+        return rc;
+    }
+    if ((rc = launch_gemm<MODE>(ARX_K_GEMM_RAW, variant, A, K, W, K, M, N, K, ep, st)) != ARX_OK) return rc;
+    if (STATS) {
+        launch_ln_finalize(M, N / 64, e->part_sum, e->part_sq, e->part_ld, e->n_rows, ep.inv_h, ep.eps, e->out_mean, e->out_rstd, st);
+        ARX_HIP_CHECK(hipGetLastError());
+    }
+    return ARX_OK;
+}
+
+extern "C" int32_t arx_gemm_bf16_ex(const void* A, const void* W, void* C, int32_t M, int32_t N, int32_t K, const arx_gemm_epilogue* e,
+                                    void* stream) {
+    ARX_REQUIRE(A && W && C && e, "null pointer argument");
+    ARX_REQUIRE(e->struct_bytes == (int32_t)sizeof(arx_gemm_epilogue), "arx_gemm_epilogue: struct_bytes=%d, this library expects %d",
+                e->struct_bytes, (int)sizeof(arx_gemm_epilogue));
+    ARX_REQUIRE(M > 0 && N > 0 && K > 0, "bad sizes");
+    ARX_REQUIRE(K % 64 == 0 && N % 8 == 0, "gemm: K=%d must be a multiple of 64 and N=%d of 8", K, N);
+    const int mode = e->mode, variant = e->variant;
+    ARX_REQUIRE(mode >= EPI_BIAS && mode <= EPI_LNRESID_STATS, "unknown gemm mode %d", mode);
+    ARX_REQUIRE(variant == 89 || variant == 8 || variant == 9 || variant == 13 || variant == 70 || variant == 71,
+                "gemm variant %d is not a shipped schedule (89, 8, 9, 13, 70, 71)", variant);
+    const bool ln_in = (mode == EPI_LN_BIAS || mode == EPI_LN_BIAS_GELU), stats = (mode == EPI_RESID_STATS || mode == EPI_LNRESID_STATS);
+    const bool staged = (variant == 89 || variant == 8 || variant == 9);      // epilogue v3 stages 256 rows of every row vector at once
+    ARX_REQUIRE(e->bias, "mode %d needs bias", mode);
+    ARX_REQUIRE(!(mode == EPI_BIAS_RESID || stats) || e->resid, "mode %d needs resid", mode);
+    ARX_REQUIRE(!ln_in || (e->a_mean && e->a_rstd && e->s_vec), "mode %d needs a_mean, a_rstd and s_vec", mode);
+    ARX_REQUIRE(mode != EPI_LNRESID_STATS || (e->r_mean && e->r_rstd && e->r_gamma && e->r_beta), "mode 6 needs r_mean, r_rstd, r_gamma and r_beta");
+    if (ln_in || mode == EPI_LNRESID_STATS)
+        ARX_REQUIRE(e->row_cap >= (staged ? round_up64(M, 256) : (int64_t)M),
+                    "row_cap=%lld: the row vectors must be readable up to row %lld (M=%d%s)", (long long)e->row_cap,
+                    (long long)(staged ? round_up64(M, 256) : (int64_t)M), M, staged ? " rounded up to 256: variants 89, 8, 9 stage whole tiles" : "");
+    if (stats) {
+        ARX_REQUIRE(N % 64 == 0, "statistics modes need N %% 64 == 0 (one partial per 64-column slice), N=%d", N);
+        ARX_REQUIRE(e->out_mean && e->out_rstd, "mode %d needs out_mean and out_rstd", mode);
+        if (variant != 70) ARX_REQUIRE(e->part_sum && e->part_sq && e->part_ld >= M && e->n_rows,
+                                       "mode %d on a tile kernel needs part_sum, part_sq, part_ld >= M and n_rows", mode);
+    }
+    if (variant == 70) {
+        ARX_REQUIRE(M <= ARX_SMALL_M && N % 64 == 0, "small-batch gemm: M=%d (<= %d) N=%d (%% 64)", M, ARX_SMALL_M, N);
+        ARX_REQUIRE(!stats || N <= 1024, "small-batch gemm: statistics modes take N <= 1024, N=%d", N);
+    }
+    EpiParams ep{(uint16_t*)C, N, e->bias, (const uint16_t*)e->resid, N};
+    ep.a_sum = e->a_mean; ep.a_sq = e->a_rstd; ep.s_vec = e->s_vec;
+    ep.r_sum = e->r_mean; ep.r_sq = e->r_rstd; ep.r_gamma = e->r_gamma; ep.r_beta = e->r_beta;
+    ep.o_sum = e->part_sum; ep.o_sq = e->part_sq; ep.o_ld = e->part_ld;
+    ep.fin_mean = e->out_mean; ep.fin_rstd = e->out_rstd;
+    ep.inv_h = 1.0f / (float)N; ep.eps = e->eps;
+    hipStream_t st = (hipStream_t)stream;
+    const uint16_t* a = (const uint16_t*)A; const uint16_t* w = (const uint16_t*)W;
+    switch (mode) {
+    case EPI_BIAS: return gemm_ex_run<EPI_BIAS>(variant, a, w, M, N, K, ep, e, st);
+    case EPI_BIAS_GELU: return gemm_ex_run<EPI_BIAS_GELU>(variant, a, w, M, N, K, ep, e, st);
+    case EPI_BIAS_RESID: return gemm_ex_run<EPI_BIAS_RESID>(variant, a, w, M, N, K, ep, e, st);
+    case EPI_LN_BIAS: return gemm_ex_run<EPI_LN_BIAS>(variant, a, w, M, N, K, ep, e, st);
+    case EPI_LN_BIAS_GELU: return gemm_ex_run<EPI_LN_BIAS_GELU>(variant, a, w, M, N, K, ep, e, st);
+    case EPI_RESID_STATS: return gemm_ex_run<EPI_RESID_STATS>(variant, a, w, M, N, K, ep, e, st);
+    default: return gemm_ex_run<EPI_LNRESID_STATS>(variant, a, w, M, N, K, ep, e, st);
+    }
+}
+
+// fold_ln_kernel alone, with the launch shape of arx_encoder_create
+extern "C" int32_t arx_fold_ln(const void* W, const float* gamma, const float* beta, const float* bias, void* Wf, float* s, float* c,
+                               int32_t N, int32_t K, void* stream) {
+    ARX_REQUIRE(W && gamma && beta && bias && Wf && s && c, "null pointer argument");
+    ARX_REQUIRE(N > 0 && K > 0, "bad sizes");
+    fold_ln_kernel<<<cdiv(N, 4), 256, 0, (hipStream_t)stream>>>((const uint16_t*)W, gamma, beta, bias, (uint16_t*)Wf, s, c, (int)N, (int)K);
+    ARX_HIP_CHECK(hipGetLastError());
+    return ARX_OK;
+}
+
 // ---- forward ------------------------------------------------------------------------------------
 // seg_b != null (sentence pairs; BERT with a pair head only): token s of sequence b takes token-type row 1 when s >= seg_b[b]
 static int32_t encoder_run(arx_encoder* h, const int32_t* ids, int32_t seq_stride, const int32_t* lens, const int32_t* seg_b,

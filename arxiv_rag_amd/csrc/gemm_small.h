@@ -161,6 +161,11 @@ static int launch_gemm_small(const uint16_t* A, int64_t lda, const uint16_t* W, 
         arx_set_error("small-batch gemm: statistics modes write the row's mean / rstd (EpiParams::fin_mean / fin_rstd)");
         return ARX_ERR_ARG;
     }
+    constexpr bool STATS = (MODE == EPI_RESID_STATS || MODE == EPI_LNRESID_STATS);
+    if (STATS && N > 1024) {      // refused before anything is launched
+        arx_set_error("small-batch gemm: statistics modes take N <= 1024 (the row is reduced inside one block), N=%d", N);
+        return ARX_ERR_ARG;
+    }
     const int mt = cdiv(M, 16), nt = N / 64, kst = K / 32;
     int S = gemm_small_splits(mt, nt, kst, 768);
     while ((int64_t)S * mt * 16 * N * 4 > ARX_SMALL_WS_BYTES && S > 1) {       // keep the partials inside the workspace
@@ -173,11 +178,6 @@ static int launch_gemm_small(const uint16_t* A, int64_t lda, const uint16_t* W, 
     if (ksteps <= 4) gemm_small_partial_kernel<4><<<grid, 64, 0, st>>>(A, lda, W, ldw, M, N, ksteps, ws);
     else gemm_small_partial_kernel<8><<<grid, 64, 0, st>>>(A, lda, W, ldw, M, N, ksteps, ws);
     ARX_HIP_CHECK(hipGetLastError());
-    constexpr bool STATS = (MODE == EPI_RESID_STATS || MODE == EPI_LNRESID_STATS);
-    if (STATS && N > 1024) {
-        arx_set_error("small-batch gemm: statistics modes take N <= 1024 (the row is reduced inside one block), N=%d", N);
-        return ARX_ERR_ARG;
-    }
     gemm_small_epilogue_kernel<MODE><<<dim3(M, STATS ? 1 : cdiv(N, 1024)), 256, 0, st>>>(ws, S, mt * 16, M, N, ep);
     ARX_HIP_CHECK(hipGetLastError());
     return ARX_OK;

@@ -336,6 +336,43 @@ int32_t arx_bm25_scores(const int64_t* term_ptr, const uint32_t* post_row, const
 int32_t arx_gemm_bf16(const void* A, const void* W, const float* bias, const void* resid, void* C,
                       int32_t M, int32_t N, int32_t K, int32_t mode, int32_t variant, void* stream);
 
+/* Parity tap: the same linear layer with ANY epilogue mode of the forward (csrc/gemm.h), launched exactly as the encoder launches it:
+ *   mode 0-2 as above;
+ *   3 = rstd_m (acc - mean_m s_n) + c_n   (LayerNorm folded into the weights; `bias` is the folded c vector);   4 = GELU of mode 3;
+ *   5 = acc + b_n + resid, and the output rows' LayerNorm statistics;   6 = acc + b_n + LN(resid), LN rebuilt from (r_mean, r_rstd,
+ *   r_gamma, r_beta), and the statistics.
+ * Statistics (modes 5/6; N % 64 == 0) are those of the bf16-ROUNDED output.  Tile kernels (variants 89, 8, 9, 13, 71) write per-row
+ * partial (sum, sum of squares) of 64-column slice j to part_sum / part_sq [j * part_ld + m], j < N / 64, m < M (nothing else of the slabs
+ * is written), then ln_finalize_kernel writes out_mean / out_rstd [m] for m < *n_rows (a device int32, as in the forward) with
+ * mean = sum / N, rstd = rsqrt(max(sumsq / N - mean^2, 0) + eps).  Variant 70 (M <= 256; statistics N <= 1024) writes out_mean / out_rstd
+ * itself and no slab.  Per-row input vectors hold row_cap floats: >= M, and >= M rounded up to 256 for variants 89, 8, 9, which stage a
+ * whole tile's rows at once (rows >= M are read, never used).  A pointer a mode needs and does not get, an unknown mode or variant, or
+ * a shape a kernel refuses is ARX_ERR_ARG, before anything is launched.  Device pointers throughout; no host synchronisation. */
+typedef struct {
+    int32_t struct_bytes;               /* sizeof(arx_gemm_epilogue) */
+    int32_t mode;                       /* 0..6 */
+    int32_t variant;                    /* 89, 8, 9, 13, 70, 71 (csrc/encoder.hip) */
+    float eps;                          /* LayerNorm epsilon of the output statistics (modes 5/6) */
+    const float* bias;                  /* [N]; modes 3/4: the folded c vector */
+    const void* resid;                  /* bf16 [M, N]: modes 2/5/6 */
+    const float *a_mean, *a_rstd;       /* [row_cap]: statistics of the A operand's rows (modes 3/4) */
+    const float* s_vec;                 /* [N]: s_n = sum_k W'[n][k] (modes 3/4) */
+    const float *r_mean, *r_rstd;       /* [row_cap]: statistics of the residual's rows (mode 6) */
+    const float *r_gamma, *r_beta;      /* [N]: LayerNorm affine of the residual (mode 6) */
+    int64_t row_cap;
+    float *part_sum, *part_sq;          /* [N / 64][part_ld] (modes 5/6, tile kernels) */
+    int64_t part_ld;                    /* >= M */
+    float *out_mean, *out_rstd;         /* [M] (modes 5/6) */
+    const int32_t* n_rows;              /* device int32: rows ln_finalize_kernel covers (modes 5/6, tile kernels) */
+} arx_gemm_epilogue;
+int32_t arx_gemm_bf16_ex(const void* A, const void* W, void* C, int32_t M, int32_t N, int32_t K, const arx_gemm_epilogue* e, void* stream);
+
+/* Parity tap: fold_ln_kernel alone, the fold arx_encoder_create applies to the weights that consume a LayerNorm output.
+ * W bf16 [N, K], gamma / beta f32 [K], bias f32 [N] -> Wf bf16 [N, K] = bf16(W[n][k] gamma[k]), s[n] = sum_k Wf[n][k],
+ * c[n] = bias[n] + sum_k beta[k] W[n][k]. */
+int32_t arx_fold_ln(const void* W, const float* gamma, const float* beta, const float* bias, void* Wf, float* s, float* c,
+                    int32_t N, int32_t K, void* stream);
+
 /* out[i] = cos(emb[i], emb[i+1]) for i in [0, n-1): the adjacent-sentence similarity the stage-3 semantic chunker
  * thresholds (/root/reference/3-chunks/pipeline/src/processors/text_processor.py:1555-1561, helper :1601-1605).
  * emb device f32 [n, ld >= dim]; out device f32 [n-1]. */

@@ -335,3 +335,207 @@ def pool_fp64(x, lens, cfg, fault=None):
         out[b] = rows.sum(0) / (rows.shape[0] + (1 if fault == "count_pad_row" else 0))
         mag[b] = rows.abs().mean(0)
     return out, mag
+
+
+# ---- GEMM epilogues (csrc/gemm.h modes 0..6) checked against float64 -------------------------------------------------------------------
+# Per-element budget of one linear layer's bf16 output against the float64 value of the same formula on the same bf16 / f32 inputs, with
+# u = 2^-24 (U24) and 2^-8 (U8: round-to-nearest bf16 moves a value by at most 2^-8 of itself).  Every term is derived from the arithmetic,
+# none is measured from a kernel:
+#   accumulation   K u sum_k |a_k w_k|: bf16 products are exact in fp32, K - 1 fp32 additions in any order; modes 3/4 multiply the
+#                  accumulator by rstd_m, and its error with it;
+#   epilogue       one u of the result's magnitude bound per fp32 operation of the formula, counted without fused multiply-adds:
+#                    modes 0/1  acc + b                                  1 op : 1 u (|acc| + |b|)
+#                    modes 3/4  rstd * (acc - mean * s) + c              4 ops: 4 u (rstd (|acc| + |mean s|) + |c|)
+#                    modes 2/5  (acc + b) + r                            2 ops: u (|acc| + |b|) + u (|acc| + |b| + |r|)
+#                    mode 6     (acc + b) + (((r - mean) rstd) g + beta) 4 ops for the rebuilt residual, each within u L with
+#                               L = |r - mean| rstd |g| + |beta|, then the two additions: u (2 (|acc| + |b|) + 5 L);
+#   GELU           modes 1/4: the input error times max |GELU'| = 1.13, plus 1.75e-4, the bound csrc/gemm.h documents for gelu_poly_pk
+#                  (the one constant taken from the project: the tests turn that comment into a checked contract);
+#   output         U8 |ref|, and U8 of the error above (the rounding acts on the computed value).
+GELU_POLY_BOUND = 1.75e-4
+GELU_MAX_SLOPE = 1.13
+EPI_FAULTS = ("trunc", "drop_k", "bias+4", "bias+8", "row+1", "rstd1", "s_unfolded", "mode6_as_5", "gamma_beta+8")
+STAT_FAULTS = ("stats_unrounded", "partial_miss8", "partial_neighbour", "var_no_mu2")
+
+
+def gelu_fp64(v):
+    import torch
+    return 0.5 * v * (1.0 + torch.erf(v / np.sqrt(2.0)))
+
+
+def bf16_trunc_fp64(v):
+    """float64 -> the bf16 value obtained by dropping the low bits (round toward zero), as float64"""
+    import torch
+    return (v.float().view(torch.int32) & -65536).view(torch.float32).double()
+
+
+def epi_fault_applies(fault, mode, M):
+    if fault in ("trunc", "drop_k", "bias+4", "bias+8"):
+        return True
+    if fault == "row+1":
+        return mode in (3, 4, 6) and M > 1
+    if fault == "rstd1":
+        return mode in (3, 4, 6)
+    if fault == "s_unfolded":
+        return mode in (3, 4)
+    return mode == 6                                            # mode6_as_5, gamma_beta+8
+
+
+def gemm_epilogue_fp64(mode, A, W, bias, resid=None, a_mean=None, a_rstd=None, s_vec=None, r_mean=None, r_rstd=None, r_gamma=None,
+                       r_beta=None, fault=None, s_unfolded=None, acc=None, absacc=None):
+    """One linear layer C = epi(A W^T) of csrc/gemm.h mode 0..6 in float64 on the values the kernel reads (A, W, resid bf16; vectors
+    f32; row vectors may be longer than M) -> (pre, err): the value BEFORE the output rounding and the per-element bound on the kernel's
+    fp32 error before that rounding (see above).  acc / absacc: A W^T and |A| |W|^T in float64 if the caller has them.
+    fault (EPI_FAULTS): a nearby wrong operation the budget must expose; `err` is then meaningless.
+      trunc: the output truncated to bf16 instead of rounded; drop_k: the last k element missing; bias+4 / bias+8: bias (modes 3/4: c)
+      read 4 / 8 columns off; row+1: mean / rstd of row m + 1; rstd1: rstd = 1; s_unfolded: s_n of the unfolded weights; mode6_as_5: the
+      residual not normalised; gamma_beta+8: the residual's gamma / beta read 8 columns off."""
+    assert fault in (None,) + EPI_FAULTS and mode in range(7), (mode, fault)
+    A64, W64 = _t64(A), _t64(W)
+    M, K = A64.shape
+    dev = A64.device
+    acc = A64 @ W64.T if acc is None else acc
+    absacc = A64.abs() @ W64.abs().T if absacc is None else absacc
+    if fault == "drop_k":
+        acc = acc - A64[:, -1:] * W64[:, -1][None, :]
+    b = _t64(bias, dev)
+    if fault in ("bias+4", "bias+8"):
+        b = b.roll(-int(fault[-1]))
+    rows = lambda v: (_t64(v, dev)[:M].roll(-1) if fault == "row+1" else _t64(v, dev)[:M])[:, None]
+    lin = K * U24 * absacc
+    if mode in (3, 4):
+        mean, rstd = rows(a_mean), rows(a_rstd)
+        if fault == "rstd1":
+            rstd = rstd * 0 + 1
+        s = _t64(s_unfolded if fault == "s_unfolded" else s_vec, dev)[None, :]
+        v = rstd * (acc - mean * s) + b
+        mag = rstd * (acc.abs() + (mean * s).abs()) + b.abs()
+        err = rstd * lin + 4 * U24 * mag
+    else:
+        v = acc + b
+        mag = acc.abs() + b.abs()
+        err = lin + U24 * mag
+    if mode in (1, 4):
+        v = gelu_fp64(v)
+        err = GELU_MAX_SLOPE * err + GELU_POLY_BOUND
+    if mode in (2, 5):
+        r = _t64(resid, dev)
+        v = v + r
+        err = lin + U24 * (2 * mag + r.abs())
+    if mode == 6:
+        r = _t64(resid, dev)
+        if fault != "mode6_as_5":
+            mean, rstd = rows(r_mean), rows(r_rstd)
+            if fault == "rstd1":
+                rstd = rstd * 0 + 1
+            g, be = _t64(r_gamma, dev), _t64(r_beta, dev)
+            if fault == "gamma_beta+8":
+                g, be = g.roll(-8), be.roll(-8)
+            ln = (r - mean) * rstd * g + be
+            err = lin + U24 * (2 * mag + 5 * ((r - mean).abs() * rstd * g.abs() + be.abs()))
+            r = ln
+        v = v + r
+    if fault == "trunc":
+        v = bf16_trunc_fp64(v)
+    return v, err
+
+
+def gemm_epilogue_budget(pre, err):
+    """|kernel output - pre| <= U8 |pre| + (1 + U8) err, per element"""
+    return U8 * pre.abs() + (1 + U8) * err
+
+
+def row_stats_fp64(out, eps, pre=None, fault=None):
+    """LayerNorm statistics of the kernel's OWN bf16 output rows `out` [M, N] (so that a legitimate last-bit difference of the output does
+    not move them), in float64 -> dict of (value, budget) per statistic:
+      psum, psq [N / 64, M]: per-row sum / sum of squares of each 64-column slice, within 64 u sum |x| / 64 u sum x^2 (63 fp32 additions
+        in any order; the squares of bf16 values are exact in fp32);
+      mean [M] within (N + 2) u mean |x| (the slices' additions, the N / 64 partials', 1 / N rounded, the product);
+      rstd [M] = 1 / sqrt(max(E[x^2] - mean^2, 0) + eps): an error of (N + 4) u E[x^2] in the variance moves it by the relative
+        0.5 (N + 4) u E[x^2] / (var + eps); 4 u more for the addition of eps and rsqrt.
+    fault (STAT_FAULTS), values only: stats_unrounded: the statistics of `pre` (the values before the output rounding);
+    partial_miss8: a partial without its last 8 columns; partial_neighbour: partials written to the next slice; var_no_mu2: the
+    variance without its - mean^2 term."""
+    assert fault in (None,) + STAT_FAULTS, fault
+    x = _t64(out)
+    M, N = x.shape
+    xs = x.view(M, N // 64, 64)
+    res = {"psum": (xs.sum(-1).T, 64 * U24 * xs.abs().sum(-1).T), "psq": (xs.pow(2).sum(-1).T, 64 * U24 * xs.pow(2).sum(-1).T)}
+    mean, ex2 = x.mean(1), x.pow(2).mean(1)
+    var = (ex2 - mean * mean).clamp_min(0)
+    rstd = (var + eps).rsqrt()
+    res["mean"] = (mean, (N + 2) * U24 * x.abs().mean(1))
+    res["rstd"] = (rstd, rstd * (0.5 * (N + 4) * U24 * ex2 / (var + eps) + 4 * U24))
+    if fault is None:
+        return res
+    y = _t64(pre).view(M, N // 64, 64) if fault == "stats_unrounded" else xs
+    if fault == "partial_miss8":
+        y = y[..., :56]
+    ps, pq = y.sum(-1).T, y.pow(2).sum(-1).T
+    if fault == "partial_neighbour":
+        ps, pq = ps.roll(1, 0), pq.roll(1, 0)
+    mu = ps.sum(0) / N
+    v = pq.sum(0) / N - (0 if fault == "var_no_mu2" else mu * mu)
+    return {"psum": ps, "psq": pq, "mean": mu, "rstd": (v.clamp_min(0) + eps).rsqrt()}
+
+
+def fold_ln_fp64(W, gamma, beta, bias):
+    """fold_ln_kernel in float64 from bf16 W [N, K] and f32 gamma / beta [K], bias [N] -> (prod, c, c_bud): prod = W gamma unrounded
+    (the kernel's W' is the bf16 rounding of the fp32 product: the caller compares bit for bit, and checks s_n against the float64 sum of
+    the device's own W' within K u sum |W'|: K fp32 additions of exact values); c_n = b_n + sum_k beta_k W[n][k], within
+    (K + 1) u (|b_n| + sum |beta W|): K fused multiply-adds and the bias addition."""
+    W64, g, be, b = _t64(W), _t64(gamma, W.device), _t64(beta, W.device), _t64(bias, W.device)
+    K = W64.shape[1]
+    return W64 * g, b + (W64 * be).sum(1), (K + 1) * U24 * (b.abs() + (W64 * be).abs().sum(1))
+
+
+def epilogue_inputs(M, N, K, seed, device="cpu"):
+    """Operands of one linear layer for every epilogue mode, chosen so that the LayerNorm plumbing matters: rows of A and of the residual
+    have means of 1-3 row-rms and scales (hence rstd) spread over a decade, gamma = 1 +- 0.3, and bias, beta, s, c, the residual's gamma /
+    beta are all non-constant and different from each other, so that any swap or shift between them is far outside the budget.
+    W0: the unfolded bf16 matrix (modes 0-2, 5, 6); Wf, s, c: its LayerNorm fold (modes 3/4; fold_ln_kernel's formulas, here by torch);
+    s_unf: sum_k W0 (the s_unfolded fault).  K > 1024 (only FFN-2 has such a K) takes GELU(N(0, 1)) rows for A.  Everything is drawn on
+    the CPU (the same values on every machine) and moved to `device`.  Row vectors are padded to M rounded up to 256 (the tile kernels stage whole tiles)."""
+    import torch
+    g = torch.Generator(device="cpu"); g.manual_seed(seed)
+    rn = lambda *s: torch.randn(s, generator=g).to(device)
+    ru = lambda *s: (torch.rand(s, generator=g) * 2 - 1).to(device)
+    cap = (M + 255) // 256 * 256
+
+    def offset_rows(cols):
+        scale = 10.0 ** (0.5 * ru(M, 1))
+        off = (1 + (ru(M, 1) + 1)) * torch.sign(ru(M, 1))
+        x = scale * (rn(M, cols) + off)
+        x[:, -1] = scale[:, 0] * (1 + rn(M).abs()) * torch.sign(ru(M))      # the last k element is never negligible (the drop_k fault)
+        x = x.to(torch.bfloat16)
+        x64 = x.double()
+        mean = x64.mean(1)
+        rstd = ((x64 - mean[:, None]).pow(2).mean(1) + 1e-5).rsqrt()
+        pad = lambda v: torch.cat([v.float(), torch.full((cap - M,), 777.0, device=device)])
+        return x, pad(mean), pad(rstd)
+
+    d = {"M": M, "N": N, "K": K, "row_cap": cap, "eps": 1e-5}
+    d["A"], d["a_mean"], d["a_rstd"] = offset_rows(K)
+    if K > 1024:                                                 # FFN-2's shape: its A operand is a GELU output, never LayerNorm-folded
+        a = gelu_fp64(rn(M, K).double())
+        a[:, -1] = 1 + rn(M).abs().double()
+        d["A"] = a.to(torch.bfloat16)
+    d["resid"], d["r_mean"], d["r_rstd"] = offset_rows(N)
+    d["W0"] = (0.05 * rn(N, K)).to(torch.bfloat16)
+    gamma, beta = 1 + 0.3 * ru(K), 0.2 + 0.3 * rn(K)
+    d["bias"] = 0.5 + rn(N)
+    w0 = d["W0"].float()
+    d["Wf"] = (w0 * gamma).to(torch.bfloat16)
+    d["s"] = d["Wf"].float().sum(1)
+    d["c"] = d["bias"] + (w0 * beta).sum(1)
+    d["s_unf"] = w0.sum(1)
+    d["r_gamma"], d["r_beta"] = 1 + 0.3 * ru(N), 0.3 + 0.3 * rn(N)
+    return d
+
+
+def epilogue_ref_args(d, mode):
+    """keyword arguments of gemm_epilogue_fp64 for mode `mode` on the operands of epilogue_inputs"""
+    ln_in = mode in (3, 4)
+    return dict(A=d["A"], W=d["Wf"] if ln_in else d["W0"], bias=d["c"] if ln_in else d["bias"], resid=d["resid"], a_mean=d["a_mean"],
+                a_rstd=d["a_rstd"], s_vec=d["s"], r_mean=d["r_mean"], r_rstd=d["r_rstd"], r_gamma=d["r_gamma"], r_beta=d["r_beta"],
+                s_unfolded=d["s_unf"])

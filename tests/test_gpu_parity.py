@@ -11,7 +11,7 @@ from arxiv_rag_amd import config as C
 from arxiv_rag_amd.weights import seeded_state_dict
 from oracle import encoder_oracle as EO
 from oracle import search_oracle as SO
-from tests.helpers import attention_budget, attention_fp64, tiny_weights
+from tests.helpers import attention_budget, attention_fp64, gemm_epilogue_budget, gemm_epilogue_fp64, tiny_weights
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -1249,8 +1249,10 @@ def test_linear_layer_variants_vs_fp32(hip, variant):
             out = torch.full((M, N), float("nan"), device="cuda", dtype=torch.bfloat16)
             hip.check(lib.arx_gemm_bf16(A.data_ptr(), W.data_ptr(), b.data_ptr(), R.data_ptr(), out.data_ptr(), M, N, K, mode,
                                         variant, st), "arx_gemm_bf16")
-            err = (out.double() - want).abs().max().item()
-            assert err < 0.02 * max(1.0, want.abs().max().item()), (variant, M, N, K, mode, err)
+            pre, perr = gemm_epilogue_fp64(mode, A, W, b, resid=R)      # the per-element budget of tests/helpers.py
+            assert (pre - want).abs().max().item() <= 1e-9 * max(1.0, want.abs().max().item())
+            err = ((out.double() - want).abs() / gemm_epilogue_budget(pre, perr)).max().item()
+            assert err <= 1, (variant, M, N, K, mode, err)
 
 
 @pytest.mark.parametrize("variant", [8, 9])
@@ -1275,10 +1277,9 @@ def test_gemm_full_line_stores_stay_inside_the_output(hip, variant):
                                             variant, st), "arx_gemm_bf16")
                 torch.cuda.synchronize()
                 assert (buf[M:] == -7.0).all().item(), (variant, M, N, K, mode, "write past row M")
-                want = A.float() @ W.float().T + b
-                want = torch.nn.functional.gelu(want) if mode == 1 else (want + R.float() if mode == 2 else want)
-                err = (buf[:M].float() - want).abs().max().item()
-                assert err < 0.02 * max(1.0, want.abs().max().item()), (variant, M, N, K, mode, err)
+                want, perr = gemm_epilogue_fp64(mode, A, W, b, resid=R)      # float64, with the per-element budget of tests/helpers.py
+                err = ((buf[:M].double() - want).abs() / gemm_epilogue_budget(want, perr)).max().item()
+                assert err <= 1, (variant, M, N, K, mode, err)
 
 
 def test_persistent_gemm_bitwise_equals_per_tile_kernel(hip):
@@ -1388,9 +1389,12 @@ def test_small_batch_gemm_vs_fp32_and_tile_kernels(hip):
                     outs.append(out.double())
                 want = A.double() @ W.double().T + b.double()
                 want = torch.nn.functional.gelu(want) if mode == 1 else want + R.double() if mode == 2 else want
-                tol = 0.01 * max(1.0, want.abs().max().item())
-                assert (outs[0] - want).abs().max().item() < tol, (N, K, M, mode)
-                assert (outs[0] - outs[1]).abs().max().item() < tol, (N, K, M, mode)
+                pre, perr = gemm_epilogue_fp64(mode, A, W, b, resid=R)
+                bud = gemm_epilogue_budget(pre, perr)               # per element (tests/helpers.py); both kernels inside it: two budgets apart at most
+                assert (pre - want).abs().max().item() <= 1e-9 * max(1.0, want.abs().max().item())
+                assert ((outs[0] - want).abs() <= bud).all().item(), (N, K, M, mode, ((outs[0] - want).abs() / bud).max().item())
+                assert ((outs[1] - want).abs() <= bud).all().item(), (N, K, M, mode, ((outs[1] - want).abs() / bud).max().item())
+                assert ((outs[0] - outs[1]).abs() <= 2 * bud).all().item(), (N, K, M, mode)
     # the medium half of the low-latency schedule (variant 71: 128 x 128 tiles) at row counts between its bounds, ragged edges included
     for (N, K) in ((2304, 768), (768, 3072), (1152, 384), (1024, 4096), (192, 64), (384, 192), (768, 320), (256, 448)):
         W = (torch.randn((N, K), device="cuda", generator=g) * 0.05).to(torch.bfloat16)
@@ -1403,7 +1407,10 @@ def test_small_batch_gemm_vs_fp32_and_tile_kernels(hip):
                 hip.check(lib.arx_gemm_bf16(A.data_ptr(), W.data_ptr(), b.data_ptr(), R.data_ptr(), out.data_ptr(), M, N, K, mode, 71, st), "arx_gemm_bf16")
                 want = A.double() @ W.double().T + b.double()
                 want = torch.nn.functional.gelu(want) if mode == 1 else want + R.double() if mode == 2 else want
-                assert (out.double() - want).abs().max().item() < 0.01 * max(1.0, want.abs().max().item()), (N, K, M, mode)
+                pre, perr = gemm_epilogue_fp64(mode, A, W, b, resid=R)
+                assert (pre - want).abs().max().item() <= 1e-9 * max(1.0, want.abs().max().item())
+                r71 = ((out.double() - want).abs() / gemm_epilogue_budget(pre, perr)).max().item()
+                assert r71 <= 1, (N, K, M, mode, r71)
     N, K, M, mode = 384, 1536, 256, 2
     W = (torch.randn((N, K), device="cuda", generator=g) * 0.05).to(torch.bfloat16); b = torch.randn((N,), device="cuda", generator=g)
     A = torch.randn((M, K), device="cuda", generator=g).to(torch.bfloat16); R = torch.randn((M, N), device="cuda", generator=g).to(torch.bfloat16)

@@ -660,7 +660,7 @@ def store_in_chroma_batched(chunks: List[Dict], embeddings: Sequence, db_path: s
 def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[str], top_k: int = 10,
                    output_dir: str = "./embeddings_saved", chunk_base: int = 0, reranker=None, rerank_top_k: int = 32,
                    hybrid_alpha: Optional[float] = None, where: Optional[Dict] = None,
-                   where_document: Optional[Dict] = None) -> List[Dict]:
+                   where_document: Optional[Dict] = None, *, mmr_lambda: Optional[float] = None, mmr_fetch_k: int = 32) -> List[Dict]:
     """Brute-force cosine top-k (config.yaml:63-64 `top_k: 10`) over the rank's fp16 rows in HBM; with
     torchrun each rank holds the contiguous row shard it encoded and the partial top-k lists are
     all-gathered over RCCL and merged.  `shard` is the `ShardSink` the encode step filled: rows [lo, hi) are already where they
@@ -683,7 +683,18 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
     `where_document` (a Chroma document filter, see `where_document.compile_where_document`): only chunks whose `text` satisfies it
     (`$contains` / `$not_contains`, case-sensitive substrings) are searched — each rank uploads the texts of its own `chunks`, scans them
     on the device (`arx_text_contains`) and searches with the resulting bitmap, and-ed with the one of `where` if both are given; nothing
-    new crosses ranks.  Not together with `hybrid_alpha` either."""
+    new crosses ranks.  Not together with `hybrid_alpha` either.
+    `mmr_lambda` (a float in [0, 1]; None = off): maximal marginal relevance (INTEGRATION.md "MMR").  The search fetches `mmr_fetch_k`
+    (in [top_k, 32]) candidates per query, filters applied as without it; each rank gathers the candidates' rows it owns, the buffers are
+    summed over the ranks (`mmr.exchange_candidate_rows`) and `arx_mmr_select` picks `top_k` of them.  The hits come in pick order and
+    carry `mmr_score` beside the cosine `score`.  Not together with `reranker` or `hybrid_alpha` (out of scope)."""
+    if mmr_lambda is not None:
+        if reranker is not None or hybrid_alpha is not None:
+            raise ValueError("mmr_lambda cannot be combined with reranker or hybrid_alpha: MMR re-orders the cosine search's candidates only")
+        if not (0.0 <= float(mmr_lambda) <= 1.0):
+            raise ValueError(f"mmr_lambda={mmr_lambda} must be in [0, 1]")
+        if not (1 <= top_k <= mmr_fetch_k <= MMR_MAX_FETCH_K):
+            raise ValueError(f"mmr_fetch_k={mmr_fetch_k} must be in [top_k, {MMR_MAX_FETCH_K}] (top_k={top_k})")
     import torch
     from .index import ShardIndex
     if where is not None and hybrid_alpha is not None:
@@ -698,7 +709,7 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
     model.encode(queries, batch_size=256, normalize_embeddings=True, convert_to_numpy=True, device_f16_out=qd, low_latency=True)
     # int8 pre-filter (same exact answers; +50 % shard memory, one quantisation pass): 1.5-1.7x the queries per second on small batches
     pre = "int8" if (shard.rows.shape[1] % 128 == 0 and shard.rows.shape[1] <= 1024 and shard.rows.shape[0] > 0) else None
-    k_search = rerank_top_k if reranker is not None else top_k
+    k_search = rerank_top_k if reranker is not None else (mmr_fetch_k if mmr_lambda is not None else top_k)
     n_cand = k_search if hybrid_alpha is None else (rerank_top_k if reranker is not None else HYBRID_CANDIDATES)
     allow = n_allowed = None
     if where is not None:
@@ -720,8 +731,16 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
             allow = (allow & docs.fold(doc_tree)).contiguous()
             n_allowed = docs.count(allow)
         pre = None
-    s, i = ShardIndex(shard.rows, idx_base=shard.lo, prefilter=pre, adaptive=True).search_distributed(qd, n_cand, allow=allow,
-                                                                                                       n_allowed=n_allowed)
+    index = ShardIndex(shard.rows, idx_base=shard.lo, prefilter=pre, adaptive=True)
+    s, i = index.search_distributed(qd, n_cand, allow=allow, n_allowed=n_allowed)
+    mmr_val = None
+    if mmr_lambda is not None:
+        from .mmr import mmr_select
+        order, mmr_val = mmr_select(index, qd, i, top_k, float(mmr_lambda))
+        pos = order.clamp(min=0).long()                          # (-1 where fewer than top_k rows were found: skipped below)
+        s = torch.where(order >= 0, s.gather(1, pos), torch.full_like(mmr_val, float("-inf")))
+        i = torch.where(order >= 0, i.gather(1, pos), torch.full_like(pos, -1))
+        mmr_val = mmr_val.cpu().numpy()
     s, i = s.cpu().numpy(), i.cpu().numpy()
     hyb = kws = None
     if hybrid_alpha is not None:
@@ -765,7 +784,7 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
             if j < 0:
                 continue
             hits.append({"rank": r + 1, "score": float(s[qi, r]), "index": j, "chunk_id": names.get(j, f"chunk_{j}"),
-                         **hybrid_fields(qi, r)})
+                         **hybrid_fields(qi, r), **({} if mmr_val is None else {"mmr_score": float(mmr_val[qi, r])})})
         results.append({"query": text, "results": hits})
     if rank == 0:
         with open(Path(output_dir) / "search_results.json", "w", encoding="utf-8") as fh:
@@ -810,6 +829,12 @@ def build_parser() -> argparse.ArgumentParser:
                    help="Chroma document filter for --queries as JSON, e.g. '{\"$contains\": \"Lipschitz\"}' or "
                         "'{\"$and\": [{\"$contains\": \"graph\"}, {\"$not_contains\": \"lemma\"}]}': only chunks whose text "
                         "satisfies it are searched (case-sensitive substrings, scanned on the GPU; not with --hybrid-alpha)")
+    p.add_argument("--mmr-lambda", type=float, default=None,
+                   help="Diversify the --queries results by maximal marginal relevance: weight of the relevance term in [0, 1], the "
+                        "penalty on similarity to the rows already picked gets the rest (default: off; not with --rerank-model or "
+                        "--hybrid-alpha)")
+    p.add_argument("--mmr-fetch-k", type=int, default=32,
+                   help="Candidates the search fetches for --mmr-lambda to pick --top-k from (default: 32, the search's k limit)")
     return p
 
 
@@ -838,6 +863,26 @@ def check_hybrid_args(args) -> Optional[str]:
         return f"--hybrid-alpha {args.hybrid_alpha}: the weight of the cosine side must be in [0, 1]"
     if args.top_k > HYBRID_CANDIDATES:
         return f"--top-k {args.top_k}: hybrid search fuses {HYBRID_CANDIDATES} candidates per side and returns at most that many"
+    return None
+
+
+MMR_MAX_FETCH_K = 32       # candidate slots of arx_mmr_select = the search's k limit
+
+
+def check_mmr_args(args) -> Optional[str]:
+    """-> an error message for an unusable --mmr-lambda / --mmr-fetch-k, else None."""
+    if args.mmr_lambda is None:
+        return None
+    if not (0.0 <= args.mmr_lambda <= 1.0):                   # (also rejects nan)
+        return f"--mmr-lambda {args.mmr_lambda}: the weight of the relevance term must be in [0, 1]"
+    if args.rerank_model:
+        return "--mmr-lambda cannot be combined with --rerank-model: MMR re-orders the cosine search's candidates only"
+    if args.hybrid_alpha is not None:
+        return "--mmr-lambda cannot be combined with --hybrid-alpha: MMR re-orders the cosine search's candidates only"
+    if args.mmr_fetch_k > MMR_MAX_FETCH_K:
+        return f"--mmr-fetch-k {args.mmr_fetch_k}: the search returns at most k <= {MMR_MAX_FETCH_K} candidates per query"
+    if args.top_k < 1 or args.mmr_fetch_k < args.top_k:
+        return f"--mmr-fetch-k {args.mmr_fetch_k} is below --top-k {args.top_k}: MMR picks its results among the candidates"
     return None
 
 
@@ -885,7 +930,8 @@ def check_where_document_args(args) -> Optional[str]:
 def main(argv: Optional[Sequence[str]] = None, model_factory: Optional[Callable] = None) -> int:
     global _model, _model_name
     args = build_parser().parse_args(argv)
-    err = check_rerank_args(args) or check_hybrid_args(args) or check_where_args(args) or check_where_document_args(args)
+    err = (check_rerank_args(args) or check_hybrid_args(args) or check_where_args(args) or check_where_document_args(args)
+           or check_mmr_args(args))
     if err:
         print(f"Error: {err}")
         return 2
@@ -974,7 +1020,8 @@ def main(argv: Optional[Sequence[str]] = None, model_factory: Optional[Callable]
                     reranker = HipCrossEncoder.from_dir(args.rerank_model, device=_model.encoder.device)
                 search_queries(_model, chunks, sink, qs, top_k=args.top_k, chunk_base=span[0] if span else 0,
                                reranker=reranker, rerank_top_k=args.rerank_top_k, hybrid_alpha=args.hybrid_alpha,
-                               where=args.where_filter, where_document=args.where_document_filter)
+                               where=args.where_filter, where_document=args.where_document_filter,
+                               mmr_lambda=args.mmr_lambda, mmr_fetch_k=args.mmr_fetch_k)
         store_time = 0.0
         if rank == 0 and not args.skip_chroma:
             try:

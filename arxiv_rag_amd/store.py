@@ -118,7 +118,7 @@ class HipCollection:
 
     def query(self, query_embeddings=None, query_texts: Optional[Sequence[str]] = None, n_results: int = 10, reranker=None,
               n_candidates: int = 32, hybrid_alpha: Optional[float] = None, where: Optional[Dict] = None,
-              where_document: Optional[Dict] = None) -> Dict:
+              where_document: Optional[Dict] = None, mmr_lambda: Optional[float] = None) -> Dict:
         """`reranker` (a `rerank.HipCrossEncoder`; needs `query_texts`): the search fetches `n_candidates` (<= 32) rows per query,
         the cross-encoder scores (query, document) for each, and the best `n_results` come back in reranked order with an added
         `rerank_scores` list per query (`scores` / `distances` stay the cosine ones).
@@ -138,8 +138,21 @@ class HipCollection:
         collection built with `documents=True`): only rows whose text satisfies it (case-sensitive substring) can be returned.  The texts
         of this rank's rows are scanned on the device (`arx_text_contains`), the tree is folded over the pattern bitmaps there, and the
         resulting bitmap goes to the same filtered search as `where`; with `where` as well the two bitmaps are and-ed on the device.
-        Composes with `reranker`; with `hybrid_alpha` it raises ValueError for the same reason as `where`."""
+        Composes with `reranker`; with `hybrid_alpha` it raises ValueError for the same reason as `where`.
+        `mmr_lambda` (a float in [0, 1]; None = off, nothing changes): maximal marginal relevance (INTEGRATION.md "MMR").  The search
+        fetches `n_candidates` (in [n_results, 32]) rows per query, with `where` / `where_document` applied as without it, and
+        `mmr.mmr_select` picks `n_results` of them on the device: first the most relevant, then each time the row that maximises
+        `lambda * cos(q, row) - (1 - lambda) * max cos(row, picked row)`.  The lists come back in pick order; `scores` / `distances` stay
+        the search's cosine values of the picked rows and an added `mmr_scores` list per query holds the objective at each pick.
+        Together with `reranker` or `hybrid_alpha` it raises ValueError: diversifying a reranked or a fused list is out of scope."""
         import torch
+        if mmr_lambda is not None:
+            if reranker is not None or hybrid_alpha is not None:
+                raise ValueError("mmr_lambda cannot be combined with reranker or hybrid_alpha: MMR re-orders the cosine search's candidates only")
+            if not (0.0 <= float(mmr_lambda) <= 1.0):
+                raise ValueError(f"mmr_lambda={mmr_lambda} must be in [0, 1]")
+            if not (1 <= n_results <= n_candidates <= 32):
+                raise ValueError(f"n_candidates={n_candidates} must be in [n_results, 32] (the search's k limit) and n_results at least 1")
         if where_document is not None:
             if hybrid_alpha is not None:
                 raise ValueError("where_document cannot be combined with hybrid_alpha: the BM25 keyword search has no row filter")
@@ -179,8 +192,16 @@ class HipCollection:
             else:
                 allow = (allow & self.documents.fold(doc_tree)).contiguous()
                 n_allowed = self.documents.count(allow)
-        s, i = self.index.search_distributed(q, n_candidates if (reranker is not None or hybrid_alpha is not None) else n_results,
-                                             allow=allow, n_allowed=n_allowed)
+        wide = reranker is not None or hybrid_alpha is not None or mmr_lambda is not None
+        s, i = self.index.search_distributed(q, n_candidates if wide else n_results, allow=allow, n_allowed=n_allowed)
+        mmr_val = None
+        if mmr_lambda is not None:
+            from .mmr import mmr_select
+            order, mmr_val = mmr_select(self.index, q, i, n_results, float(mmr_lambda))
+            pos = order.clamp(min=0).long()                      # (-1 where fewer than n_results rows were found: masked below)
+            s = torch.where(order >= 0, s.gather(1, pos), torch.full_like(mmr_val, float("-inf")))
+            i = torch.where(order >= 0, i.gather(1, pos), torch.full_like(pos, -1))
+            mmr_val = mmr_val.cpu().numpy()
         s, i = s.cpu().numpy(), i.cpu().numpy()
         hyb = kws = None
         if hybrid_alpha is not None:
@@ -215,6 +236,8 @@ class HipCollection:
             out["distances"].append((2.0 - 2.0 * s[qi][keep]).tolist())
             out["documents"].append([m.get("text") for m in ms])
             out["metadatas"].append([{k: m.get(k) for k in ("paper_id", "section", "quality_score")} for m in ms])
+        if mmr_val is not None:
+            out["mmr_scores"] = [mmr_val[qi][i[qi] >= 0].tolist() for qi in range(q.shape[0])]
         if reranker is not None:
             out["rerank_scores"] = rr
         if hyb is not None:

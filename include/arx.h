@@ -302,6 +302,25 @@ int32_t arx_text_contains(const uint8_t* blob, const int64_t* row_off, int64_t n
 /* *out_count (ONE device int64) = set bits of bits[0 .. ceil(n_rows/64)) that name rows below n_rows. */
 int32_t arx_bitmap_count(const uint64_t* bits, int64_t n_rows, int64_t* out_count, void* stream);
 
+/* ---- MMR diversified re-ordering of a query's search candidates (csrc/mmr.hip; the definition is INTEGRATION.md "MMR") -----------
+ * arx_gather_rows: out[s] (device fp16 [count, dim]) = shard row ids[s] - idx_base where that row lies in [0, n_rows), all zeros
+ * otherwise (id -1, a row another rank owns: the ranks' buffers then add up to the rows, arxiv_rag_amd/mmr.py).  shard device fp16
+ * [n_rows, dim], ids device int64 [count] (the [Q, n] list of a search, global ids), dim % 8 == 0.  Every output element is written once
+ * with a plain 16-byte store: the result does not depend on what the buffer held before.  One launch on `stream`, no atomics. */
+int32_t arx_gather_rows(const void* shard, int64_t n_rows, int32_t dim, int64_t idx_base, const int64_t* ids, int64_t count,
+                        void* out, void* stream);
+/* arx_mmr_select: per query, greedy maximal marginal relevance over its n <= 32 candidate slots (in search order).
+ *   q device fp16 [n_queries, dim]; cand device fp16 [n_queries, n, dim] (what arx_gather_rows wrote); ids device int64 [n_queries, n]:
+ *   a slot with id < 0 is never picked and counts as a zero row.  dim % 64 == 0, dim <= 8192, 1 <= m <= n <= 32, lambda in [0, 1].
+ *   rel[i] = cos(q, c_i), sim[i][j] = cos(c_i, c_j): true cosines (rows of any norm; 0 where a norm is 0), every dot product an f32 sum
+ *   of exact fp16 products.  Pick 0 = argmax lambda rel[i]; pick t = argmax over valid unpicked i of
+ *   lambda rel[i] - (1 - lambda) max_{j picked} sim[i][j]; ties to the lower slot.
+ *   order device int32 [n_queries, m]: the picked SLOT positions; mmr device f32 [n_queries, m]: the objective at the time of the pick;
+ *   (-1, -inf) in the tail when fewer than m slots are valid.
+ * One block per query, no atomics, no workspace: a query's outputs depend on its own row of q, cand and ids alone, bit for bit. */
+int32_t arx_mmr_select(const void* q, const void* cand, const int64_t* ids, int32_t n_queries, int32_t n, int32_t dim, int32_t m,
+                       float lambda, int32_t* order, float* mmr, void* stream);
+
 /* ---- BM25 keyword top-n (hybrid search: `retrieval.use_hybrid_search`, 3-chunks/pipeline/config.yaml:67-68) ----------------
  * Index of one shard, device memory, built by the caller (arxiv_rag_amd/keyword.py):
  *   term_ptr int64 [vocab + 1]   CSR by term: postings of term t are [term_ptr[t], term_ptr[t + 1])

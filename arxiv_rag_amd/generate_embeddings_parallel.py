@@ -660,7 +660,8 @@ def store_in_chroma_batched(chunks: List[Dict], embeddings: Sequence, db_path: s
 def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[str], top_k: int = 10,
                    output_dir: str = "./embeddings_saved", chunk_base: int = 0, reranker=None, rerank_top_k: int = 32,
                    hybrid_alpha: Optional[float] = None, where: Optional[Dict] = None,
-                   where_document: Optional[Dict] = None, *, mmr_lambda: Optional[float] = None, mmr_fetch_k: int = 32) -> List[Dict]:
+                   where_document: Optional[Dict] = None, *, mmr_lambda: Optional[float] = None, mmr_fetch_k: int = 32,
+                   keep_mask: Optional[np.ndarray] = None) -> List[Dict]:
     """Brute-force cosine top-k (config.yaml:63-64 `top_k: 10`) over the rank's fp16 rows in HBM; with
     torchrun each rank holds the contiguous row shard it encoded and the partial top-k lists are
     all-gathered over RCCL and merged.  `shard` is the `ShardSink` the encode step filled: rows [lo, hi) are already where they
@@ -687,7 +688,12 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
     `mmr_lambda` (a float in [0, 1]; None = off): maximal marginal relevance (INTEGRATION.md "MMR").  The search fetches `mmr_fetch_k`
     (in [top_k, 32]) candidates per query, filters applied as without it; each rank gathers the candidates' rows it owns, the buffers are
     summed over the ranks (`mmr.exchange_candidate_rows`) and `arx_mmr_select` picks `top_k` of them.  The hits come in pick order and
-    carry `mmr_score` beside the cosine `score`.  Not together with `reranker` or `hybrid_alpha` (out of scope)."""
+    carry `mmr_score` beside the cosine `score`.  Not together with `reranker` or `hybrid_alpha` (out of scope).
+    `keep_mask` (bool, one entry per row of the shard; None = every row): rows to search at all — `--dedup-threshold` passes the rows that
+    are not near-duplicates (`find_shard_duplicates`).  It is and-ed into the bitmap of `where` / `where_document`, or is the bitmap
+    when neither is given.  Not together with `hybrid_alpha`, for the reason `where` is not."""
+    if keep_mask is not None and hybrid_alpha is not None:
+        raise ValueError("keep_mask cannot be combined with hybrid_alpha: the BM25 keyword search has no row filter")
     if mmr_lambda is not None:
         if reranker is not None or hybrid_alpha is not None:
             raise ValueError("mmr_lambda cannot be combined with reranker or hybrid_alpha: MMR re-orders the cosine search's candidates only")
@@ -719,6 +725,15 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
             raise ValueError(f"where: {mask.shape[0]} chunks for the shard's {shard.rows.shape[0]} rows")
         allow, n_allowed = torch.from_numpy(pack_bitmap(mask).view(np.int64)).to(dev), int(mask.sum())
         pre = None                                           # a filtered search runs on the fp16 rows
+    if keep_mask is not None:
+        from .where import pack_bitmap
+        keep_mask = np.asarray(keep_mask, dtype=bool)
+        if keep_mask.shape[0] != shard.rows.shape[0]:
+            raise ValueError(f"keep_mask: {keep_mask.shape[0]} entries for the shard's {shard.rows.shape[0]} rows")
+        keep = torch.from_numpy(pack_bitmap(keep_mask).view(np.int64)).to(dev)
+        allow = keep if allow is None else (allow & keep).contiguous()
+        n_allowed = int(keep_mask.sum()) if where is None else int((mask & keep_mask).sum())
+        pre = None
     if where_document is not None:
         from .where_document import DocumentStore, compile_where_document
         doc_tree = compile_where_document(where_document)
@@ -835,6 +850,10 @@ def build_parser() -> argparse.ArgumentParser:
                         "--hybrid-alpha)")
     p.add_argument("--mmr-fetch-k", type=int, default=32,
                    help="Candidates the search fetches for --mmr-lambda to pick --top-k from (default: 32, the search's k limit)")
+    p.add_argument("--dedup-threshold", type=float, default=None,
+                   help="Near-duplicate detection: a chunk whose embedding scores at least this cosine, in (0, 1], against ANY earlier "
+                        "chunk is listed in duplicates.json with its nearest earlier chunk, and a --queries search skips it (default: "
+                        "off; one GPU rank only; not with --hybrid-alpha and --queries)")
     return p
 
 
@@ -886,6 +905,35 @@ def check_mmr_args(args) -> Optional[str]:
     return None
 
 
+def check_dedup_args(args) -> Optional[str]:
+    """-> an error message for an unusable --dedup-threshold, else None."""
+    if args.dedup_threshold is None:
+        return None
+    if not (0.0 < args.dedup_threshold <= 1.0):               # (also rejects nan)
+        return f"--dedup-threshold {args.dedup_threshold}: the cosine at which a chunk counts as a duplicate must be in (0, 1]"
+    if args.hybrid_alpha is not None and args.queries:
+        return "--dedup-threshold cannot be combined with --hybrid-alpha and --queries: the BM25 keyword search has no row filter"
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        return "--dedup-threshold needs a single GPU rank: a rank sees only its own rows, and a cross-rank join is out of scope"
+    return None
+
+
+def find_shard_duplicates(shard: "ShardSink", chunks: List[Dict], threshold: float, output_dir: str = "./embeddings_saved") -> np.ndarray:
+    """`--dedup-threshold`: the self-join over the fp16 rows the encode step left in HBM (`dedup.find_duplicates`), `duplicates.json`
+    beside the other output files (`threshold`, `n_chunks`, `n_duplicates`, `duplicates`: one `{index, chunk_id, duplicate_of_index,
+    duplicate_of, score}` per flagged chunk, pointing at its nearest earlier chunk) -> the rows to keep, bool [n]."""
+    from .dedup import duplicate_entries, find_duplicates
+    from .index import ShardIndex
+    n = int(shard.rows.shape[0])
+    dup_of, scores = find_duplicates(ShardIndex(shard.rows, idx_base=0), threshold) if n else (np.zeros(0, np.int64), np.zeros(0, np.float32))
+    entries = duplicate_entries(dup_of, scores, [c.get("chunk_id", f"chunk_{shard.lo + j}") for j, c in enumerate(chunks)], base=shard.lo)
+    with open(Path(output_dir) / "duplicates.json", "w", encoding="utf-8") as fh:
+        json.dump({"threshold": float(threshold), "n_chunks": n, "n_duplicates": len(entries), "duplicates": entries}, fh, indent=2,
+                  ensure_ascii=False)
+    print(f"✅ Near-duplicates at cosine >= {threshold}: {len(entries):,} of {n:,} chunks listed in {Path(output_dir) / 'duplicates.json'}")
+    return dup_of < 0
+
+
 def check_where_args(args) -> Optional[str]:
     """-> an error message for an unusable --where, else None.  On success `args.where_filter` holds the parsed filter (None without --where)."""
     args.where_filter = None
@@ -931,7 +979,7 @@ def main(argv: Optional[Sequence[str]] = None, model_factory: Optional[Callable]
     global _model, _model_name
     args = build_parser().parse_args(argv)
     err = (check_rerank_args(args) or check_hybrid_args(args) or check_where_args(args) or check_where_document_args(args)
-           or check_mmr_args(args))
+           or check_mmr_args(args) or check_dedup_args(args))
     if err:
         print(f"Error: {err}")
         return 2
@@ -991,7 +1039,7 @@ def main(argv: Optional[Sequence[str]] = None, model_factory: Optional[Callable]
         if args.queries:
             qs = [ln.strip() for ln in Path(args.queries).read_text(encoding="utf-8").splitlines() if ln.strip()]
         # the search step works on the rows where the encoder leaves them: an fp16 shard in this rank's HBM
-        sink = make_shard_sink(_model, n_chunks, args.chunks_per_worker, world, rank) if qs else None
+        sink = make_shard_sink(_model, n_chunks, args.chunks_per_worker, world, rank) if (qs or args.dedup_threshold is not None) else None
         if world > 1:
             # one process per GPU: every rank encodes, keeps and writes its own contiguous row range
             embeddings, lo, hi = generate_embeddings_sharded(chunks, args.model, args.batch_size, args.chunks_per_worker, sink=sink, span=span)
@@ -1010,6 +1058,12 @@ def main(argv: Optional[Sequence[str]] = None, model_factory: Optional[Callable]
                                              prefetch=meta_prefetch)
             print()
         meta_prefetch = None
+        keep_mask = None
+        if args.dedup_threshold is not None:
+            if sink is None:
+                print("⚠️  --dedup-threshold needs the HIP encoder (the self-join runs over the shard it leaves in HBM): skipped")
+            else:
+                keep_mask = find_shard_duplicates(sink, chunks, args.dedup_threshold)
         if qs:
             if sink is None:
                 print("⚠️  --queries needs the HIP encoder (the search step runs over the shard it leaves in HBM): skipped")
@@ -1021,7 +1075,7 @@ def main(argv: Optional[Sequence[str]] = None, model_factory: Optional[Callable]
                 search_queries(_model, chunks, sink, qs, top_k=args.top_k, chunk_base=span[0] if span else 0,
                                reranker=reranker, rerank_top_k=args.rerank_top_k, hybrid_alpha=args.hybrid_alpha,
                                where=args.where_filter, where_document=args.where_document_filter,
-                               mmr_lambda=args.mmr_lambda, mmr_fetch_k=args.mmr_fetch_k)
+                               mmr_lambda=args.mmr_lambda, mmr_fetch_k=args.mmr_fetch_k, keep_mask=keep_mask)
         store_time = 0.0
         if rank == 0 and not args.skip_chroma:
             try:

@@ -44,6 +44,8 @@ class ShardIndex:
         self._last_ws: Optional[torch.Tensor] = None
         self._ws_filtered: Optional[torch.Tensor] = None   # workspace of `search(allow=...)` calls
         self._last_ws_filtered: Optional[torch.Tensor] = None
+        self._ws_prefix: Optional[torch.Tensor] = None     # workspace of `search_prefix` / `nearest_earlier` calls
+        self._last_ws_prefix: Optional[torch.Tensor] = None
         self._i8: Optional[torch.Tensor] = None
         self._i8_version = -1
         self._adaptive, self._i8_searches, self.prefilter_disabled = bool(adaptive), 0, False
@@ -243,6 +245,66 @@ class ShardIndex:
         _lib.check(self.lib.arx_topk_filtered_stats(ws.data_ptr(), C.byref(a), C.byref(b), torch.cuda.current_stream().cuda_stream),
                    "arx_topk_filtered_stats")
         return (int(a.value), int(b.value))
+
+    # ---- a row limit per query (near-duplicate detection) -----------------------------------------------------------------
+    def search_prefix(self, queries_f16: torch.Tensor, row_limit: torch.Tensor, k: int = 10, ws: Optional[torch.Tensor] = None,
+                      **debug) -> Tuple[torch.Tensor, torch.Tensor]:
+        """queries fp16 [Q, D] and `row_limit` int64 [Q] (both on the device) -> (scores f32 [Q, k], ids int64 [Q, k]): for query q the exact
+        top-k of the LOCAL rows r < row_limit[q] (`arx_topk_search_prefix`; the limit is clamped to [0, n_rows]), score desc, ties -> lower
+        row, ids = local row + idx_base, (-inf, -1) pads when fewer than k rows lie below the limit.  A (query, row) score has the bits
+        `search` gives it.  `queries_f16` may be a view of the shard's own rows.  Runs on the fp16 rows (no int8 pre-filter).  Test hooks
+        as for `search(allow=...)`: `path` (1 = masked scan, 2 = exhaustive) and `cand_cap`; `prefix_stats` reads the counters."""
+        unknown = set(debug) - {"path", "cand_cap"}
+        if unknown:
+            raise TypeError(f"ShardIndex.search_prefix() got unexpected keyword argument(s): {', '.join(sorted(unknown))}")
+        q = queries_f16
+        assert q.is_cuda and q.dtype == torch.float16 and q.dim() == 2 and q.shape[1] == self.dim and q.is_contiguous()
+        nq = q.shape[0]
+        assert row_limit.is_cuda and row_limit.dtype == torch.int64 and row_limit.shape == (nq,) and row_limit.is_contiguous()
+        scores = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+        ids = torch.empty((nq, k), dtype=torch.int64, device=q.device)
+        if nq == 0:
+            return scores, ids
+        if self.n_rows == 0:
+            scores.fill_(float("-inf")); ids.fill_(-1)
+            return scores, ids
+        need = self.lib.arx_topk_prefix_workspace_bytes(self.n_rows, nq, self.dim, k)
+        if need < 0:
+            raise _lib.ArxError(f"unsupported prefix search shape n_rows={self.n_rows} nq={nq} dim={self.dim} k={k}")
+        if ws is None:
+            if self._ws_prefix is None or self._ws_prefix.numel() < need:
+                self._ws_prefix = torch.empty(need, dtype=torch.uint8, device=self.corpus.device)
+            ws = self._ws_prefix
+        norm = max(self.max_row_norm(), 1.0 + 1.0 / 512.0)       # never below the encoder's unit-row bound (as `_search_filtered`)
+        rc = self.lib.arx_topk_search_prefix_tuned(self.corpus.data_ptr(), self.n_rows, q.data_ptr(), row_limit.data_ptr(), nq, self.dim, k,
+                                                   scores.data_ptr(), ids.data_ptr(), self.idx_base, norm, ws.data_ptr(), ws.numel(),
+                                                   int(debug.get("path", 0)), int(debug.get("cand_cap", 0)),
+                                                   torch.cuda.current_stream().cuda_stream)
+        _lib.check(rc, "arx_topk_search_prefix")
+        self._last_ws_prefix = ws
+        return scores, ids
+
+    def prefix_stats(self, ws: Optional[torch.Tensor] = None) -> Tuple[int, int]:
+        """(queries whose candidate list overflowed and were answered by the exhaustive path, candidate groups rescored) of the LAST
+        `search_prefix` / `nearest_earlier` on this index (or on `ws`).  Synchronises on the current stream."""
+        ws = self._last_ws_prefix if ws is None else ws
+        if ws is None:
+            return (0, 0)
+        a, b = C.c_int64(0), C.c_int64(0)
+        _lib.check(self.lib.arx_topk_prefix_stats(ws.data_ptr(), C.byref(a), C.byref(b), torch.cuda.current_stream().cuda_stream),
+                   "arx_topk_prefix_stats")
+        return (int(a.value), int(b.value))
+
+    def nearest_earlier(self, row_lo: int = 0, row_hi: Optional[int] = None, k: int = 1, **debug) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The self-join: for every local row r in [row_lo, row_hi) the exact top-k of the rows BEFORE it (local rows < r) ->
+        (scores f32 [m, k], ids int64 [m, k]) on the device, m = row_hi - row_lo; row 0 has no earlier row: (-inf, -1).  The queries are a
+        view of the shard (no copy).  A row's answer does not depend on the range it was asked in."""
+        row_hi = self.n_rows if row_hi is None else int(row_hi)
+        row_lo = int(row_lo)
+        if not (0 <= row_lo <= row_hi <= self.n_rows):
+            raise ValueError(f"rows [{row_lo}, {row_hi}) are not a range of the shard's {self.n_rows} rows")
+        limit = torch.arange(row_lo, row_hi, dtype=torch.int64, device=self.corpus.device)
+        return self.search_prefix(self.corpus[row_lo:row_hi], limit, k, **debug)
 
     def _i8_nq_limit(self) -> int:
         """The largest query batch the int8 pass takes under this index's policy (`i8_max_queries`; None = the library default, 1 024)."""

@@ -75,13 +75,24 @@ class HipCollection:
 
     def __init__(self, embeddings: np.ndarray, metadata: Sequence[Dict], device="cuda:0", encoder=None,
                  rank: int = 0, world: int = 1, chunk_rows: int = 1 << 18, keyword: bool = False, tokenizer=None,
-                 documents: bool = False):
+                 documents: bool = False, dedup_threshold: Optional[float] = None):
         """`keyword=True`: also build a BM25 `keyword.KeywordIndex` over this shard's `metadata[i]["text"]` (word pieces of `tokenizer`,
         default the encoder's; corpus statistics summed over all ranks when `world > 1`), which `query(hybrid_alpha=...)` needs.
         `documents=True`: also keep this shard's texts as a UTF-8 blob in HBM (`where_document.DocumentStore`), which
-        `query(where_document=...)` scans."""
+        `query(where_document=...)` scans.
+        `dedup_threshold` (a float in (0, 1]; None = off, nothing changes): near-duplicate detection (`dedup.find_duplicates`,
+        INTEGRATION.md "Near-duplicate chunks") runs once, here: a row is a duplicate when any EARLIER row scores >= the threshold against
+        it (the search's dot product = the cosine on unit rows).  `self.duplicates` lists them
+        (`{index, chunk_id, duplicate_of_index, duplicate_of, score}`, the nearest earlier row each) and every `query` skips them: the
+        keep-bitmap is and-ed into the filter of `where` / `where_document`, or is the filter when neither is given.  With `world > 1` it
+        raises ValueError: a rank sees only its own rows, and a cross-rank join is out of scope."""
         import torch
         from .index import ShardIndex, shard_bounds
+        if dedup_threshold is not None:
+            from .dedup import check_threshold
+            dedup_threshold = check_threshold(dedup_threshold)
+            if world > 1:
+                raise ValueError("dedup_threshold needs world == 1: a rank sees only its own rows, and a cross-rank join is out of scope")
         n, d = embeddings.shape
         lo, hi = shard_bounds(n, world, rank)
         self.n_total, self.dim, self.lo, self.hi = n, d, lo, hi
@@ -107,6 +118,14 @@ class HipCollection:
         if documents:
             from .where_document import DocumentStore
             self.documents = DocumentStore([metadata[r].get("text") or "" for r in range(lo, hi)], device=device)
+        self.dedup_threshold, self.duplicates = dedup_threshold, []
+        self._keep_mask = self._keep = None                     # rows that are not duplicates: host bool [n], device bitmap words
+        if dedup_threshold is not None and hi > lo:
+            from .dedup import duplicate_entries, find_duplicates, keep_bitmap
+            dup_of, scores = find_duplicates(self.index, dedup_threshold)
+            self.duplicates = duplicate_entries(dup_of, scores, [metadata[r].get("chunk_id", f"chunk_{r}") for r in range(lo, hi)], base=lo)
+            self._keep_mask = dup_of < 0
+            self._keep = torch.from_numpy(keep_bitmap(dup_of).view(np.int64)).to(device)
 
     @classmethod
     def from_disk(cls, input_dir, **kw) -> "HipCollection":
@@ -144,8 +163,13 @@ class HipCollection:
         `mmr.mmr_select` picks `n_results` of them on the device: first the most relevant, then each time the row that maximises
         `lambda * cos(q, row) - (1 - lambda) * max cos(row, picked row)`.  The lists come back in pick order; `scores` / `distances` stay
         the search's cosine values of the picked rows and an added `mmr_scores` list per query holds the objective at each pick.
-        Together with `reranker` or `hybrid_alpha` it raises ValueError: diversifying a reranked or a fused list is out of scope."""
+        Together with `reranker` or `hybrid_alpha` it raises ValueError: diversifying a reranked or a fused list is out of scope.
+        A collection built with `dedup_threshold` never returns a row it flagged as a duplicate, whatever the other parameters; with
+        `hybrid_alpha` it raises ValueError for the same reason as `where`."""
         import torch
+        if self._keep is not None and hybrid_alpha is not None:
+            raise ValueError("a collection built with dedup_threshold cannot be queried with hybrid_alpha: the BM25 keyword search has no "
+                             "row filter")
         if mmr_lambda is not None:
             if reranker is not None or hybrid_alpha is not None:
                 raise ValueError("mmr_lambda cannot be combined with reranker or hybrid_alpha: MMR re-orders the cosine search's candidates only")
@@ -185,12 +209,20 @@ class HipCollection:
         if where is not None:
             from .where import compile_where, evaluate, pack_bitmap
             mask = evaluate(compile_where(where), self.metadata, self.lo, self.hi, cache=self._where_columns)
+            if self._keep_mask is not None:
+                mask = mask & self._keep_mask
             allow, n_allowed = torch.from_numpy(pack_bitmap(mask).view(np.int64)).to(q.device), int(mask.sum())
         if where_document is not None:
             if allow is None:
                 allow, n_allowed = self.documents.allow(doc_tree)
             else:
                 allow = (allow & self.documents.fold(doc_tree)).contiguous()
+                n_allowed = self.documents.count(allow)
+        if self._keep is not None:
+            if where is None and where_document is None:
+                allow, n_allowed = self._keep, int(self._keep_mask.sum())
+            elif where is None:                                  # (with `where` the host mask above already holds it)
+                allow = (allow & self._keep).contiguous()
                 n_allowed = self.documents.count(allow)
         wide = reranker is not None or hybrid_alpha is not None or mmr_lambda is not None
         s, i = self.index.search_distributed(q, n_candidates if wide else n_results, allow=allow, n_allowed=n_allowed)

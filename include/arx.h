@@ -284,6 +284,31 @@ int32_t arx_topk_search_filtered_tuned(const void* corpus, int64_t n_rows, const
  * search on this workspace.  Copies 16 bytes to the host and waits on `stream`. */
 int32_t arx_topk_filtered_stats(const void* ws, int64_t* overflowed_queries, int64_t* candidate_groups, void* stream);
 
+/* ---- Exact top-k with a row limit per query (the self-join of near-duplicate detection) ----------------------------------------------
+ * row_limit: device int64 [n_queries]; query q may return only the local rows r < row_limit[q] (clamped to [0, n_rows]).  The answer is
+ * the exact top-k of those rows, score descending, ties to the lower row, ids = local row + idx_base, (-inf, -1) padding when fewer than
+ * k rows lie below the limit (limit 0 included).  A (query, row) score has the bits it has in arx_topk_search and
+ * arx_topk_search_filtered.  `queries` may point into `corpus` itself: with row_limit[q] = the query's own row number that is "the
+ * nearest earlier rows of every row".  A query's output depends on the query, its limit and the corpus alone — not on the batch, the
+ * other limits, the path or cand_cap.  max_row_norm as for the filtered search, 0 = unit rows.  dim % 64 == 0, k <= 32, any n_queries
+ * (batches above 1 024 queries are processed in slices).  Two device paths with the same bits (csrc/prefix.hip): the masked scan (pass A
+ * with `row < limit` in front of the group maximum; tiles at or beyond the largest limit of a query tile are not read) and the
+ * exhaustive scoring of rows [0, limit), which also answers any query whose candidate list overflows.
+ * ws: device workspace of arx_topk_prefix_workspace_bytes(...) bytes, caller-owned. */
+int64_t arx_topk_prefix_workspace_bytes(int64_t n_rows, int32_t n_queries, int32_t dim, int32_t k);
+int32_t arx_topk_search_prefix(const void* corpus, int64_t n_rows, const void* queries, const int64_t* row_limit, int32_t n_queries,
+                               int32_t dim, int32_t k, float* out_scores, int64_t* out_ids, int64_t idx_base, float max_row_norm,
+                               void* ws, int64_t ws_bytes, void* stream);
+/* The same with the path and the candidate capacity chosen by the caller (tests, tuning): path 0 = library's choice, 1 = masked scan,
+ * 2 = exhaustive; cand_cap = candidate groups a query may list before it goes to the exhaustive path (0 = default 1 024, at most
+ * 8192).  Same bits for every choice. */
+int32_t arx_topk_search_prefix_tuned(const void* corpus, int64_t n_rows, const void* queries, const int64_t* row_limit, int32_t n_queries,
+                                     int32_t dim, int32_t k, float* out_scores, int64_t* out_ids, int64_t idx_base, float max_row_norm,
+                                     void* ws, int64_t ws_bytes, int32_t path, int32_t cand_cap, void* stream);
+/* {queries sent to the exhaustive path because their candidate list overflowed, candidate groups rescored} of the LAST prefix search
+ * on this workspace.  Copies 16 bytes to the host and waits on `stream`. */
+int32_t arx_topk_prefix_stats(const void* ws, int64_t* overflowed_queries, int64_t* candidate_groups, void* stream);
+
 /* ---- Substring scan over the chunk texts (Chroma's `where_document`: `$contains` / `$not_contains`) -----------------------------
  * The producer of the row bitmaps arx_topk_search_filtered takes (csrc/textscan.hip).
  * out_bits[p][w] bit (r & 63) of word w = r >> 6  <=>  pattern p occurs in row r, entirely inside

@@ -1,4 +1,5 @@
-// Constants of arx_topk_* shared by search.hip and filter.hip: both include this, then search_pass_a.h and search_tail.h.
+// Constants of arx_topk_* shared by search.hip and the masked searches (filter.hip, prefix.hip): each includes this, then search_pass_a.h and
+// search_tail.h (the masked searches also masked_topk.h).
 #pragma once
 
 #define GROUP_ROWS 64

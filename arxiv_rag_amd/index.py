@@ -42,10 +42,8 @@ class ShardIndex:
         self.idx_base = int(idx_base)
         self._ws: Optional[torch.Tensor] = None            # workspace of plain `search` calls (and of the LAST call: certificate_stats)
         self._last_ws: Optional[torch.Tensor] = None
-        self._ws_filtered: Optional[torch.Tensor] = None   # workspace of `search(allow=...)` calls
-        self._last_ws_filtered: Optional[torch.Tensor] = None
-        self._ws_prefix: Optional[torch.Tensor] = None     # workspace of `search_prefix` / `nearest_earlier` calls
-        self._last_ws_prefix: Optional[torch.Tensor] = None
+        self._ws_masked = {}                               # the index's own workspaces of `search(allow=...)` ("filtered") and of
+        self._last_ws_masked = {}                          # `search_prefix` / `nearest_earlier` ("prefix") calls, and those of the LAST calls
         self._i8: Optional[torch.Tensor] = None
         self._i8_version = -1
         self._adaptive, self._i8_searches, self.prefilter_disabled = bool(adaptive), 0, False
@@ -199,15 +197,16 @@ class ShardIndex:
         self._i8_searches += 1 if ran_i8 else 0
         return scores, ids
 
-    def _search_filtered(self, q, k, allow, n_allowed, ws, out, _stream, debug):
+    def _search_masked(self, kind, who, workspace_bytes, q, k, ws, out, _stream, debug, check_mask, call):
+        """What the masked searches share (csrc/masked_topk.h).  `kind`: "filtered" / "prefix", the key of the cached workspace and the
+        word in messages; `who`: the public spelling; `workspace_bytes`: the library's arx_topk_<kind>_workspace_bytes; `check_mask(nq)`
+        asserts the mask's tensors, `call(...)` is arx_topk_search_<kind>_tuned with its leading (corpus, mask, queries) arguments bound."""
         unknown = set(debug) - {"path", "cand_cap"}
         if unknown:
-            raise TypeError(f"ShardIndex.search(allow=...) got unexpected keyword argument(s): {', '.join(sorted(unknown))}")
+            raise TypeError(f"ShardIndex.{who} got unexpected keyword argument(s): {', '.join(sorted(unknown))}")
         assert q.is_cuda and q.dtype == torch.float16 and q.dim() == 2 and q.shape[1] == self.dim and q.is_contiguous()
-        n_words = (self.n_rows + 63) // 64
-        assert allow.is_cuda and allow.dtype in (torch.int64, torch.uint64) and allow.dim() == 1 and allow.is_contiguous()
-        assert allow.shape[0] == n_words, f"allow has {allow.shape[0]} words, the shard's {self.n_rows} rows need {n_words}"
         nq = q.shape[0]
+        check_mask(nq)
         if out is None:
             scores = torch.empty((nq, k), dtype=torch.float32, device=q.device)
             ids = torch.empty((nq, k), dtype=torch.int64, device=q.device)
@@ -219,32 +218,46 @@ class ShardIndex:
         if self.n_rows == 0:
             scores.fill_(float("-inf")); ids.fill_(-1)
             return scores, ids
-        need = self.lib.arx_topk_filtered_workspace_bytes(self.n_rows, nq, self.dim, k)
+        need = workspace_bytes(self.n_rows, nq, self.dim, k)
         if need < 0:
-            raise _lib.ArxError(f"unsupported filtered search shape n_rows={self.n_rows} nq={nq} dim={self.dim} k={k}")
+            raise _lib.ArxError(f"unsupported {kind} search shape n_rows={self.n_rows} nq={nq} dim={self.dim} k={k}")
         if ws is None:
-            if self._ws_filtered is None or self._ws_filtered.numel() < need:
-                self._ws_filtered = torch.empty(need, dtype=torch.uint8, device=self.corpus.device)
-            ws = self._ws_filtered
+            ws = self._ws_masked.get(kind)
+            if ws is None or ws.numel() < need:
+                ws = self._ws_masked[kind] = torch.empty(need, dtype=torch.uint8, device=self.corpus.device)
         norm = max(self.max_row_norm(), 1.0 + 1.0 / 512.0)       # never below the encoder's unit-row bound (as `_options`)
         st = torch.cuda.current_stream().cuda_stream if _stream is None else _stream
-        rc = self.lib.arx_topk_search_filtered_tuned(self.corpus.data_ptr(), self.n_rows, allow.data_ptr(), -1 if n_allowed is None else int(n_allowed),
-                                                     q.data_ptr(), nq, self.dim, k, scores.data_ptr(), ids.data_ptr(), self.idx_base, norm,
-                                                     ws.data_ptr(), ws.numel(), int(debug.get("path", 0)), int(debug.get("cand_cap", 0)), st)
-        _lib.check(rc, "arx_topk_search_filtered")
-        self._last_ws_filtered = ws
+        rc = call(nq, self.dim, k, scores.data_ptr(), ids.data_ptr(), self.idx_base, norm, ws.data_ptr(), ws.numel(),
+                  int(debug.get("path", 0)), int(debug.get("cand_cap", 0)), st)
+        _lib.check(rc, f"arx_topk_search_{kind}")
+        self._last_ws_masked[kind] = ws
         return scores, ids
+
+    def _masked_stats(self, kind, stats, ws):
+        """`stats`: the library's arx_topk_<kind>_stats."""
+        ws = self._last_ws_masked.get(kind) if ws is None else ws
+        if ws is None:
+            return (0, 0)
+        a, b = C.c_int64(0), C.c_int64(0)
+        _lib.check(stats(ws.data_ptr(), C.byref(a), C.byref(b), torch.cuda.current_stream().cuda_stream), f"arx_topk_{kind}_stats")
+        return (int(a.value), int(b.value))
+
+    def _search_filtered(self, q, k, allow, n_allowed, ws, out, _stream, debug):
+        def check_mask(nq):
+            n_words = (self.n_rows + 63) // 64
+            assert allow.is_cuda and allow.dtype in (torch.int64, torch.uint64) and allow.dim() == 1 and allow.is_contiguous()
+            assert allow.shape[0] == n_words, f"allow has {allow.shape[0]} words, the shard's {self.n_rows} rows need {n_words}"
+
+        def call(*rest):
+            return self.lib.arx_topk_search_filtered_tuned(self.corpus.data_ptr(), self.n_rows, allow.data_ptr(),
+                                                           -1 if n_allowed is None else int(n_allowed), q.data_ptr(), *rest)
+        return self._search_masked("filtered", "search(allow=...)", self.lib.arx_topk_filtered_workspace_bytes, q, k, ws, out, _stream, debug,
+                                   check_mask, call)
 
     def filtered_stats(self, ws: Optional[torch.Tensor] = None) -> Tuple[int, int]:
         """(queries whose candidate list overflowed and were answered by the exhaustive path, candidate groups rescored) of the LAST
         `search(allow=...)` on this index (or on `ws`).  Synchronises on the current stream."""
-        ws = self._last_ws_filtered if ws is None else ws
-        if ws is None:
-            return (0, 0)
-        a, b = C.c_int64(0), C.c_int64(0)
-        _lib.check(self.lib.arx_topk_filtered_stats(ws.data_ptr(), C.byref(a), C.byref(b), torch.cuda.current_stream().cuda_stream),
-                   "arx_topk_filtered_stats")
-        return (int(a.value), int(b.value))
+        return self._masked_stats("filtered", self.lib.arx_topk_filtered_stats, ws)
 
     # ---- a row limit per query (near-duplicate detection) -----------------------------------------------------------------
     def search_prefix(self, queries_f16: torch.Tensor, row_limit: torch.Tensor, k: int = 10, ws: Optional[torch.Tensor] = None,
@@ -254,46 +267,20 @@ class ShardIndex:
         row, ids = local row + idx_base, (-inf, -1) pads when fewer than k rows lie below the limit.  A (query, row) score has the bits
         `search` gives it.  `queries_f16` may be a view of the shard's own rows.  Runs on the fp16 rows (no int8 pre-filter).  Test hooks
         as for `search(allow=...)`: `path` (1 = masked scan, 2 = exhaustive) and `cand_cap`; `prefix_stats` reads the counters."""
-        unknown = set(debug) - {"path", "cand_cap"}
-        if unknown:
-            raise TypeError(f"ShardIndex.search_prefix() got unexpected keyword argument(s): {', '.join(sorted(unknown))}")
         q = queries_f16
-        assert q.is_cuda and q.dtype == torch.float16 and q.dim() == 2 and q.shape[1] == self.dim and q.is_contiguous()
-        nq = q.shape[0]
-        assert row_limit.is_cuda and row_limit.dtype == torch.int64 and row_limit.shape == (nq,) and row_limit.is_contiguous()
-        scores = torch.empty((nq, k), dtype=torch.float32, device=q.device)
-        ids = torch.empty((nq, k), dtype=torch.int64, device=q.device)
-        if nq == 0:
-            return scores, ids
-        if self.n_rows == 0:
-            scores.fill_(float("-inf")); ids.fill_(-1)
-            return scores, ids
-        need = self.lib.arx_topk_prefix_workspace_bytes(self.n_rows, nq, self.dim, k)
-        if need < 0:
-            raise _lib.ArxError(f"unsupported prefix search shape n_rows={self.n_rows} nq={nq} dim={self.dim} k={k}")
-        if ws is None:
-            if self._ws_prefix is None or self._ws_prefix.numel() < need:
-                self._ws_prefix = torch.empty(need, dtype=torch.uint8, device=self.corpus.device)
-            ws = self._ws_prefix
-        norm = max(self.max_row_norm(), 1.0 + 1.0 / 512.0)       # never below the encoder's unit-row bound (as `_search_filtered`)
-        rc = self.lib.arx_topk_search_prefix_tuned(self.corpus.data_ptr(), self.n_rows, q.data_ptr(), row_limit.data_ptr(), nq, self.dim, k,
-                                                   scores.data_ptr(), ids.data_ptr(), self.idx_base, norm, ws.data_ptr(), ws.numel(),
-                                                   int(debug.get("path", 0)), int(debug.get("cand_cap", 0)),
-                                                   torch.cuda.current_stream().cuda_stream)
-        _lib.check(rc, "arx_topk_search_prefix")
-        self._last_ws_prefix = ws
-        return scores, ids
+
+        def check_mask(nq):
+            assert row_limit.is_cuda and row_limit.dtype == torch.int64 and row_limit.shape == (nq,) and row_limit.is_contiguous()
+
+        def call(*rest):
+            return self.lib.arx_topk_search_prefix_tuned(self.corpus.data_ptr(), self.n_rows, q.data_ptr(), row_limit.data_ptr(), *rest)
+        return self._search_masked("prefix", "search_prefix()", self.lib.arx_topk_prefix_workspace_bytes, q, k, ws, None, None, debug,
+                                   check_mask, call)
 
     def prefix_stats(self, ws: Optional[torch.Tensor] = None) -> Tuple[int, int]:
         """(queries whose candidate list overflowed and were answered by the exhaustive path, candidate groups rescored) of the LAST
         `search_prefix` / `nearest_earlier` on this index (or on `ws`).  Synchronises on the current stream."""
-        ws = self._last_ws_prefix if ws is None else ws
-        if ws is None:
-            return (0, 0)
-        a, b = C.c_int64(0), C.c_int64(0)
-        _lib.check(self.lib.arx_topk_prefix_stats(ws.data_ptr(), C.byref(a), C.byref(b), torch.cuda.current_stream().cuda_stream),
-                   "arx_topk_prefix_stats")
-        return (int(a.value), int(b.value))
+        return self._masked_stats("prefix", self.lib.arx_topk_prefix_stats, ws)
 
     def nearest_earlier(self, row_lo: int = 0, row_hi: Optional[int] = None, k: int = 1, **debug) -> Tuple[torch.Tensor, torch.Tensor]:
         """The self-join: for every local row r in [row_lo, row_hi) the exact top-k of the rows BEFORE it (local rows < r) ->

@@ -215,9 +215,9 @@ def test_filter_kernels_do_not_spill_or_use_scratch():
     if not f.exists():
         pytest.skip("no _build/filter.resources.txt (library not built by csrc/build.sh in this tree)")
     ks = {m.group(1): (int(m.group(4)), int(m.group(7))) for m in PAT.finditer(f.read_text())}
-    for name in ("filtered_groupmax_kernel", "filtered_tail_kernel", "filter_scan_kernel", "filter_scatter_kernel", "filter_exhaustive_kernel",
+    for name in ("masked_groupmax_kernel", "masked_tail_kernel", "filter_scan_kernel", "filter_scatter_kernel", "masked_exhaustive_kernel",
                  "filter_merge_kernel"):
         assert any(name in k for k in ks), name
-    assert sum("filtered_groupmax_kernel" in k for k in ks) == 3      # 64-, 128- and 256-query tiles
+    assert sum("masked_groupmax_kernel" in k for k in ks) == 3        # 64-, 128- and 256-query tiles
     bad = {k: v for k, v in ks.items() if v[0] or v[1]}
     assert not bad, bad

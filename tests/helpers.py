@@ -157,6 +157,44 @@ def check_topk_fp64(c, q, s, i, k, idx_base=0, e=None, sample_rows=4, what=None)
     return e
 
 
+def check_prefix_answer(s, i, lim_c, k, base, what=None):
+    """(s, i) = search_prefix with the limits `lim_c` (numpy int64, already clamped to the shard): no id at or beyond its query's limit,
+    and the (-inf, -1) padding is exactly the missing rows."""
+    import torch
+    lim_t = torch.from_numpy(np.ascontiguousarray(lim_c)).to(i.device)[:, None]
+    found = i >= 0
+    assert (i[found] >= base).all() and (i < lim_t + base)[found].all(), (what, "an id at or beyond the limit")
+    assert (i[~found] == -1).all() and (s[~found] == float("-inf")).all() and torch.isfinite(s[found]).all(), what
+    assert torch.equal(found.sum(1), torch.clamp(lim_t[:, 0], max=k)), (what, "padding")
+
+
+def allow_below(limit, n):
+    """the bitmap (device int64 words, `where.pack_bitmap`) of the rows < limit of an n-row shard"""
+    import torch
+    from arxiv_rag_amd.where import pack_bitmap
+    return torch.from_numpy(pack_bitmap(np.arange(n) < limit).view(np.int64)).cuda()
+
+
+def check_against_filtered_and_fp64(idx, C_, Q_, lim_c, s, i, k, sample, what):
+    """(s, i) = idx.search_prefix(Q_, limits, k).  For the sampled queries: bit-equal to the filtered search over the bitmap of rows < limit
+    (queries that share a limit in one call), and an exact top-k of C[:limit] by float64."""
+    import torch
+    n, base = C_.shape[0], idx.idx_base
+    by_limit = {}
+    for j in sample:
+        by_limit.setdefault(int(lim_c[j]), []).append(int(j))
+    for limit, js in by_limit.items():
+        jt = torch.tensor(js, device="cuda")
+        q = Q_[jt].contiguous()
+        fs, fi = idx.search(q, k, allow=allow_below(limit, n), n_allowed=limit)
+        assert torch.equal(fi, i[jt]) and torch.equal(fs.view(torch.int32), s[jt].view(torch.int32)), \
+            (what, "differs from the filtered search", limit, js[:4])
+        if limit == 0:
+            assert (i[jt] == -1).all() and (s[jt] == float("-inf")).all(), (what, "limit 0")
+        else:
+            check_topk_fp64(C_[:limit], q, s[jt], i[jt], k, idx_base=base, sample_rows=1, what=(what, limit))
+
+
 # ---- encoder checked against float64 -------------------------------------------------------------------------------------------------
 # References restate oracle/encoder_oracle.py in float64 (torch, on whatever device the inputs live) on the values the kernels read: bf16
 # activations and matrices, fp32 biases, LayerNorm parameters and bias tables.  The optional `fault` of each reference computes a nearby

@@ -5,7 +5,8 @@ with a one-entry candidate list = the fallback) must return the same bits, and a
 import numpy as np
 import pytest
 
-from tests.helpers import check_topk_fp64
+from tests.helpers import allow_below as _allow_below, check_against_filtered_and_fp64 as _check_against_filtered_and_fp64
+from tests.helpers import check_prefix_answer
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -73,29 +74,6 @@ def _bits(t):
     return t.view(torch.int32)
 
 
-def _allow_below(limit, n):
-    from arxiv_rag_amd.where import pack_bitmap
-    return torch.from_numpy(pack_bitmap(np.arange(n) < limit).view(np.int64)).cuda()
-
-
-def _check_against_filtered_and_fp64(idx, C_, Q_, lim_c, s, i, k, sample, what):
-    """For the sampled queries: bit-equal to the filtered search over the bitmap of rows < limit (queries that share a limit in one call),
-    and an exact top-k of C[:limit] by float64."""
-    n, base = C_.shape[0], idx.idx_base
-    by_limit = {}
-    for j in sample:
-        by_limit.setdefault(int(lim_c[j]), []).append(int(j))
-    for limit, js in by_limit.items():
-        jt = torch.tensor(js, device="cuda")
-        q = Q_[jt].contiguous()
-        fs, fi = idx.search(q, k, allow=_allow_below(limit, n), n_allowed=limit)
-        assert torch.equal(fi, i[jt]) and torch.equal(_bits(fs), _bits(s[jt])), (what, "differs from the filtered search", limit, js[:4])
-        if limit == 0:
-            assert (i[jt] == -1).all() and (s[jt] == float("-inf")).all(), (what, "limit 0")
-        else:
-            check_topk_fp64(C_[:limit], q, s[jt], i[jt], k, idx_base=base, sample_rows=1, what=(what, limit))
-
-
 @pytest.mark.parametrize("kind", KINDS)
 @pytest.mark.parametrize("case", CASES, ids=[c["id"] for c in CASES])
 def test_prefix_search_every_path_same_bits_equal_to_the_filtered_search_and_fp64(hip, case, kind):
@@ -125,11 +103,7 @@ def test_prefix_search_every_path_same_bits_equal_to_the_filtered_search_and_fp6
         assert over <= two_groups, (what, over, two_groups)
     assert over0 <= two_groups
     # no id at or beyond the limit, over ALL queries; the padding is exactly the missing rows
-    lim_t = torch.from_numpy(lim_c).cuda()[:, None]
-    found = i >= 0
-    assert ((i[found] >= base)).all() and (i < lim_t + base)[found].all(), (what, "an id at or beyond the limit")
-    assert (i[~found] == -1).all() and (s[~found] == float("-inf")).all() and torch.isfinite(s[found]).all(), what
-    assert torch.equal(found.sum(1), torch.clamp(lim_t[:, 0], max=k)), (what, "padding")
+    check_prefix_answer(s, i, lim_c, k, base, what)
     if kind == "all":                                             # the whole batch against the filtered search with every row allowed
         ones = torch.full(((n + 63) // 64,), -1, dtype=torch.int64, device="cuda")
         fs, fi = idx.search(Q_, k, allow=ones)

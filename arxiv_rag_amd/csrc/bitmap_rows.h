@@ -1,0 +1,42 @@
+// What the row-bitmap mask policies share (filter.hip: one bitmap per call; filter_multi.hip: a set of them): which bits of a word name rows
+// of the shard, and the exclusive scan of the words' popcounts that turns a bitmap into positions of a row list.
+// Included inside the including file's anonymous namespace after masked_topk.h; not a stand-alone header.
+#pragma once
+
+__device__ __forceinline__ uint64_t valid_bits(int64_t n_rows, int64_t g) {      // the bits of word g that name rows of the shard
+    const int64_t rem = n_rows - g * GROUP_ROWS;
+    return rem >= GROUP_ROWS ? ~0ull : ((1ull << rem) - 1ull);
+}
+
+// ---- the row list of the exhaustive path --------------------------------------------------------------------------------------------------
+// offsets of the words' rows in the compacted list (exclusive scan of the popcounts; off[n_words] = the number of allowed rows).  One
+// block per bitmap (block b: words allow[b * n_words ...], offsets off[b * (n_words + 1) ...]); thread t owns a contiguous run of words.
+// `gate`: run only if *gate != 0 (the masked scan's "some query overflowed").
+__global__ __launch_bounds__(1024) void filter_scan_kernel(const uint64_t* __restrict__ allow, int64_t n_words, int64_t n_rows,
+                                                            int64_t* __restrict__ off, const int* __restrict__ gate) {
+    if (gate && !*gate) return;
+    __shared__ int64_t wave_tot[16];
+    allow += (int64_t)blockIdx.x * n_words;
+    off += (int64_t)blockIdx.x * (n_words + 1);
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int64_t per = (n_words + 1023) / 1024;
+    const int64_t a = (int64_t)tid * per, b = (a + per < n_words) ? a + per : n_words;
+    int64_t mine = 0;
+    for (int64_t i = a; i < b; ++i) mine += __popcll(allow[i] & valid_bits(n_rows, i));
+    int64_t inc = mine;                                        // inclusive scan inside the wave
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int64_t up = __shfl_up(inc, o);
+        inc += lane >= o ? up : 0;
+    }
+    if (lane == 63) wave_tot[w] = inc;
+    __syncthreads();
+    int64_t base = 0;
+    for (int ww = 0; ww < w; ++ww) base += wave_tot[ww];
+    int64_t run = base + inc - mine;
+    for (int64_t i = a; i < b; ++i) {
+        off[i] = run;
+        run += __popcll(allow[i] & valid_bits(n_rows, i));
+    }
+    if (tid == 1023) off[n_words] = base + inc;
+}

@@ -19,6 +19,7 @@ namespace {      // the headers also define non-template kernels: internal linka
 #include "search_pass_a.h"
 #include "search_tail.h"
 #include "masked_topk.h"
+#include "bitmap_rows.h"
 
 // path = 0 with n_allowed known: the exhaustive path below this many (allowed row, query) pairs.  Measured (profiles/filter_bench.json:
 // 1 M x 768 unit rows, k = 10, ms per batch, exhaustive against masked scan): 64 queries — 0.239 / 0.321 at 0.67 M pairs, 0.287 / 0.334 at
@@ -28,40 +29,6 @@ namespace {      // the headers also define non-template kernels: internal linka
 #define FILT_EXHAUSTIVE_MAX_PAIRS (1ll << 18)
 #define FILT_WIDE_NQ 64
 
-__device__ __forceinline__ uint64_t valid_bits(int64_t n_rows, int64_t g) {      // the bits of word g that name rows of the shard
-    const int64_t rem = n_rows - g * GROUP_ROWS;
-    return rem >= GROUP_ROWS ? ~0ull : ((1ull << rem) - 1ull);
-}
-
-// ---- the row list of the exhaustive path --------------------------------------------------------------------------------------------------
-// offsets of the words' rows in the compacted list (exclusive scan of the popcounts; off[n_words] = the number of allowed rows).  One
-// block: thread t owns a contiguous run of words.  `gate`: run only if *gate != 0 (the masked scan's "some query overflowed").
-__global__ __launch_bounds__(1024) void filter_scan_kernel(const uint64_t* __restrict__ allow, int64_t n_words, int64_t n_rows,
-                                                            int64_t* __restrict__ off, const int* __restrict__ gate) {
-    if (gate && !*gate) return;
-    __shared__ int64_t wave_tot[16];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int64_t per = (n_words + 1023) / 1024;
-    const int64_t a = (int64_t)tid * per, b = (a + per < n_words) ? a + per : n_words;
-    int64_t mine = 0;
-    for (int64_t i = a; i < b; ++i) mine += __popcll(allow[i] & valid_bits(n_rows, i));
-    int64_t inc = mine;                                        // inclusive scan inside the wave
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int64_t up = __shfl_up(inc, o);
-        inc += lane >= o ? up : 0;
-    }
-    if (lane == 63) wave_tot[w] = inc;
-    __syncthreads();
-    int64_t base = 0;
-    for (int ww = 0; ww < w; ++ww) base += wave_tot[ww];
-    int64_t run = base + inc - mine;
-    for (int64_t i = a; i < b; ++i) {
-        off[i] = run;
-        run += __popcll(allow[i] & valid_bits(n_rows, i));
-    }
-    if (tid == 1023) off[n_words] = base + inc;
-}
 // one lane per row: the allowed rows in ascending order
 __global__ __launch_bounds__(256) void filter_scatter_kernel(const uint64_t* __restrict__ allow, int64_t n_words, int64_t n_rows,
                                                               const int64_t* __restrict__ off, int64_t* __restrict__ rows,
@@ -122,7 +89,7 @@ struct BitmapMask {
     // exhaustive
     __device__ __forceinline__ int64_t list_total(int) const { return *n_list; }
     static constexpr bool kListInMemory = true;
-    __device__ __forceinline__ int64_t list_row(int64_t pos) const { return rows[pos]; }
+    __device__ __forceinline__ int64_t list_row(int, int64_t pos) const { return rows[pos]; }
 
     // host
     static constexpr const char* kWorkspaceFn = "arx_topk_filtered_workspace_bytes";

@@ -1,5 +1,6 @@
 // The masked exact top-k search: exact top-k over the rows of an fp16 shard that a mask lets a query see.  One definition, with the kind
-// of mask as a compile-time policy (filter.hip: one bitmap per call; prefix.hip: one row limit per query).  Two device paths, same bits:
+// of mask as a compile-time policy (filter.hip: one bitmap per call; prefix.hip: one row limit per query; filter_multi.hip: a set of
+// bitmaps and one filter index per query).  Two device paths, same bits:
 //   masked scan   pass A as in search.hip (fp16 MFMA, f32 accumulate; BM = 64 / 128 / 256 queries by batch size, one wave column = one
 //                 64-row group) with the mask applied in the epilogue BEFORE the maximum over a group's 64 rows: a masked row's value is
 //                 replaced by -inf (a select), gmax[group][query] is the maximum over the rows the query may see, -inf for a group with
@@ -16,7 +17,7 @@
 //                                      `.of_query(m, nq)` narrows that to query m, and the result called with (j, r) says whether
 //                                      row j*16 + (lane>>4)*4 + r is kept
 //   query(q, n_rows, n_groups)         the tail: `.n_groups` the query reads and `.word(g)`, its visible rows of group g as 64 bits
-//   list_total(q), list_row(pos)       exhaustive: the length of query q's row list and the row at a position of it; kListInMemory:
+//   list_total(q), list_row(q, pos)    exhaustive: the length of query q's row list and the row at a position of it; kListInMemory:
 //                                      list_row is a load
 // and on the host
 //   given(), check(n_rows)             its own arguments: non-null, in range
@@ -272,11 +273,11 @@ __global__ __launch_bounds__(256) void masked_exhaustive_kernel(const Mask mask,
     const int nch = D >> 3, l8 = lane & 7, rsub = lane >> 3;
     float cs = -INFINITY; int64_t ci = -1;
     for (int64_t base = lo + (int64_t)w * 64; base < hi; base += NW * 64) {
-        const int64_t mine = base + lane < hi ? mask.list_row(base + lane) : -1;
+        const int64_t mine = base + lane < hi ? mask.list_row(q, base + lane) : -1;
         for (int r8 = 0; r8 < 64; r8 += 8) {
             if (base + r8 >= hi) break;                        // wave-uniform
             // a list kept in memory was read once for the 64 entries and is handed round; a computed one is computed again
-            const int64_t row = Mask::kListInMemory ? __shfl(mine, r8 + rsub) : (base + r8 + rsub < hi ? mask.list_row(base + r8 + rsub) : -1);
+            const int64_t row = Mask::kListInMemory ? __shfl(mine, r8 + rsub) : (base + r8 + rsub < hi ? mask.list_row(q, base + r8 + rsub) : -1);
             const bool ok = row >= 0;
             const float a = exact_row_score(C + (ok ? row : 0) * D, qs, nch, l8, ok);
             if (l8 == 0) sc[r8 + rsub] = a;

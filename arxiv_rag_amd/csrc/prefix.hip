@@ -92,7 +92,7 @@ struct PrefixMask {
     // exhaustive
     __device__ __forceinline__ int64_t list_total(int q) const { return lim[q]; }
     static constexpr bool kListInMemory = false;
-    __device__ __forceinline__ int64_t list_row(int64_t pos) const { return pos; }
+    __device__ __forceinline__ int64_t list_row(int, int64_t pos) const { return pos; }
 
     // host
     static constexpr const char* kWorkspaceFn = "arx_topk_prefix_workspace_bytes";

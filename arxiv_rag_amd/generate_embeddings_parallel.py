@@ -659,7 +659,7 @@ def store_in_chroma_batched(chunks: List[Dict], embeddings: Sequence, db_path: s
 # --------------------------------------------------------------------------------------------- search (added step)
 def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[str], top_k: int = 10,
                    output_dir: str = "./embeddings_saved", chunk_base: int = 0, reranker=None, rerank_top_k: int = 32,
-                   hybrid_alpha: Optional[float] = None, where: Optional[Dict] = None,
+                   hybrid_alpha: Optional[float] = None, where=None,
                    where_document: Optional[Dict] = None, *, mmr_lambda: Optional[float] = None, mmr_fetch_k: int = 32,
                    keep_mask: Optional[np.ndarray] = None) -> List[Dict]:
     """Brute-force cosine top-k (config.yaml:63-64 `top_k: 10`) over the rank's fp16 rows in HBM; with
@@ -680,7 +680,9 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
     `keyword_score`, where the row was not in that side's candidate list.
     `where` (a Chroma filter, see `where.compile_where`): only chunks whose `metadata` satisfies it are searched — each rank evaluates it
     on its own `chunks`, packs the row bitmap and searches with it (`ShardIndex.search(allow=...)`: the exact top-k of the allowed rows,
-    on the fp16 rows).  Not together with `hybrid_alpha`: the keyword search has no row filter.
+    on the fp16 rows).  Not together with `hybrid_alpha`: the keyword search has no row filter.  A LIST with one filter or None per
+    query (`--where-file`) restricts every query to its own filter: one bitmap per distinct filter, and-ed with `keep_mask` and
+    `where_document`, and one `ShardIndex.search_filtered_many` per 64 distinct filters instead of one search per filter.
     `where_document` (a Chroma document filter, see `where_document.compile_where_document`): only chunks whose `text` satisfies it
     (`$contains` / `$not_contains`, case-sensitive substrings) are searched — each rank uploads the texts of its own `chunks`, scans them
     on the device (`arx_text_contains`) and searches with the resulting bitmap, and-ed with the one of `where` if both are given; nothing
@@ -718,6 +720,11 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
     k_search = rerank_top_k if reranker is not None else (mmr_fetch_k if mmr_lambda is not None else top_k)
     n_cand = k_search if hybrid_alpha is None else (rerank_top_k if reranker is not None else HYBRID_CANDIDATES)
     allow = n_allowed = None
+    where_each = None                                        # `where` as one entry per query: the bitmaps are built below, per distinct filter
+    if isinstance(where, (list, tuple)):
+        from .filter_sets import per_query_list
+        where_each, where = per_query_list(where, len(queries), "where"), None
+        pre = None
     if where is not None:
         from .where import compile_where, evaluate, pack_bitmap
         mask = evaluate(compile_where(where), [c.get("metadata") or {} for c in chunks])
@@ -747,7 +754,30 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
             n_allowed = docs.count(allow)
         pre = None
     index = ShardIndex(shard.rows, idx_base=shard.lo, prefilter=pre, adaptive=True)
-    s, i = index.search_distributed(qd, n_cand, allow=allow, n_allowed=n_allowed)
+    if where_each is not None:
+        from .filter_sets import distinct_filters
+        from .index import search_filtered_grouped
+        from .where import compile_where, evaluate, pack_bitmap
+        if len(chunks) != shard.rows.shape[0]:
+            raise ValueError(f"where: {len(chunks)} chunks for the shard's {shard.rows.shape[0]} rows")
+        pairs, filter_of = distinct_filters(where_each, [None] * len(queries))
+        metas = [c.get("metadata") or {} for c in chunks]
+        n_words = (len(chunks) + 63) // 64
+        bitmaps, counts = [], []
+        for w, _ in pairs:                                   # `allow` so far: the keep-mask and `where_document`, shared by every query
+            if w is None:
+                words = allow if allow is not None else torch.full((n_words,), -1, dtype=torch.int64, device=dev)
+                count = n_allowed if allow is not None else len(chunks)
+            else:
+                mask = evaluate(compile_where(w), metas)
+                words = torch.from_numpy(pack_bitmap(mask).view(np.int64)).to(dev)
+                words = words if allow is None else (words & allow).contiguous()
+                count = int(mask.sum()) if allow is None else None      # (counted only where it is free: it merely steers the path)
+            bitmaps.append(words)
+            counts.append(count)
+        s, i = search_filtered_grouped(index, qd, n_cand, bitmaps, filter_of, counts)
+    else:
+        s, i = index.search_distributed(qd, n_cand, allow=allow, n_allowed=n_allowed)
     mmr_val = None
     if mmr_lambda is not None:
         from .mmr import mmr_select
@@ -840,6 +870,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--where", type=str, default=None,
                    help="Chroma metadata filter for --queries as JSON, e.g. '{\"section\": \"abstract\"}' or "
                         "'{\"quality_score\": {\"$gte\": 0.95}}': only matching chunks are searched (not with --hybrid-alpha)")
+    p.add_argument("--where-file", type=str, default=None,
+                   help="A different --where filter per query: a JSON-lines file with one filter object or null (no filter) per line, "
+                        "one line per query of --queries; the batch is searched in one pass over the rows (not with --where or "
+                        "--hybrid-alpha)")
     p.add_argument("--where-document", type=str, default=None,
                    help="Chroma document filter for --queries as JSON, e.g. '{\"$contains\": \"Lipschitz\"}' or "
                         "'{\"$and\": [{\"$contains\": \"graph\"}, {\"$not_contains\": \"lemma\"}]}': only chunks whose text "
@@ -954,6 +988,49 @@ def check_where_args(args) -> Optional[str]:
     return None
 
 
+def read_query_lines(path) -> List[str]:
+    """The queries of --queries: the file's non-empty lines, stripped."""
+    return [ln.strip() for ln in Path(path).read_text(encoding="utf-8").splitlines() if ln.strip()]
+
+
+def check_where_file_args(args) -> Optional[str]:
+    """-> an error message for an unusable --where-file, else None.  On success `args.where_filters` holds one parsed filter or None per
+    query of --queries (None without --where-file)."""
+    args.where_filters = None
+    if getattr(args, "where_file", None) is None:
+        return None
+    if args.where is not None:
+        return "--where-file cannot be combined with --where: the file holds the filter of every query"
+    if args.hybrid_alpha is not None:
+        return "--where-file cannot be combined with --hybrid-alpha: the BM25 keyword search has no row filter"
+    if not args.queries:
+        return "--where-file needs --queries: it holds one filter per query"
+    try:
+        lines = [ln.strip() for ln in Path(args.where_file).read_text(encoding="utf-8").splitlines() if ln.strip()]
+        n_queries = len(read_query_lines(args.queries))
+    except OSError as e:
+        return f"--where-file: {e}"
+    from .where import compile_where
+    filters = []
+    for no, ln in enumerate(lines, 1):
+        try:
+            parsed = json.loads(ln)
+        except ValueError as e:
+            return f"--where-file line {no} is not valid JSON: {e}"
+        if parsed is not None:
+            if not isinstance(parsed, dict):
+                return f"--where-file line {no}: a filter object or null, got {ln}"
+            try:
+                compile_where(parsed)
+            except ValueError as e:
+                return f"--where-file line {no}: {e}"
+        filters.append(parsed)
+    if len(filters) != n_queries:
+        return f"--where-file holds {len(filters)} filters for the {n_queries} queries of --queries: it needs one line per query"
+    args.where_filters = filters
+    return None
+
+
 def check_where_document_args(args) -> Optional[str]:
     """-> an error message for an unusable --where-document, else None.  On success `args.where_document_filter` holds the parsed filter
     (None without --where-document)."""
@@ -978,7 +1055,7 @@ def check_where_document_args(args) -> Optional[str]:
 def main(argv: Optional[Sequence[str]] = None, model_factory: Optional[Callable] = None) -> int:
     global _model, _model_name
     args = build_parser().parse_args(argv)
-    err = (check_rerank_args(args) or check_hybrid_args(args) or check_where_args(args) or check_where_document_args(args)
+    err = (check_rerank_args(args) or check_hybrid_args(args) or check_where_args(args) or check_where_file_args(args) or check_where_document_args(args)
            or check_mmr_args(args) or check_dedup_args(args))
     if err:
         print(f"Error: {err}")
@@ -1037,7 +1114,7 @@ def main(argv: Optional[Sequence[str]] = None, model_factory: Optional[Callable]
         t0 = time.time()
         qs = []
         if args.queries:
-            qs = [ln.strip() for ln in Path(args.queries).read_text(encoding="utf-8").splitlines() if ln.strip()]
+            qs = read_query_lines(args.queries)
         # the search step works on the rows where the encoder leaves them: an fp16 shard in this rank's HBM
         sink = make_shard_sink(_model, n_chunks, args.chunks_per_worker, world, rank) if (qs or args.dedup_threshold is not None) else None
         if world > 1:
@@ -1074,7 +1151,7 @@ def main(argv: Optional[Sequence[str]] = None, model_factory: Optional[Callable]
                     reranker = HipCrossEncoder.from_dir(args.rerank_model, device=_model.encoder.device)
                 search_queries(_model, chunks, sink, qs, top_k=args.top_k, chunk_base=span[0] if span else 0,
                                reranker=reranker, rerank_top_k=args.rerank_top_k, hybrid_alpha=args.hybrid_alpha,
-                               where=args.where_filter, where_document=args.where_document_filter,
+                               where=args.where_filters if args.where_filters is not None else args.where_filter, where_document=args.where_document_filter,
                                mmr_lambda=args.mmr_lambda, mmr_fetch_k=args.mmr_fetch_k, keep_mask=keep_mask)
         store_time = 0.0
         if rank == 0 and not args.skip_chroma:

@@ -42,8 +42,9 @@ class ShardIndex:
         self.idx_base = int(idx_base)
         self._ws: Optional[torch.Tensor] = None            # workspace of plain `search` calls (and of the LAST call: certificate_stats)
         self._last_ws: Optional[torch.Tensor] = None
-        self._ws_masked = {}                               # the index's own workspaces of `search(allow=...)` ("filtered") and of
-        self._last_ws_masked = {}                          # `search_prefix` / `nearest_earlier` ("prefix") calls, and those of the LAST calls
+        self._ws_masked = {}                               # the index's own workspaces of `search(allow=...)` ("filtered"), of
+        self._last_ws_masked = {}                          # `search_prefix` / `nearest_earlier` ("prefix") and of `search_filtered_many`
+                                                           # ("filtered_multi") calls, and those of the LAST calls
         self._i8: Optional[torch.Tensor] = None
         self._i8_version = -1
         self._adaptive, self._i8_searches, self.prefilter_disabled = bool(adaptive), 0, False
@@ -198,7 +199,7 @@ class ShardIndex:
         return scores, ids
 
     def _search_masked(self, kind, who, workspace_bytes, q, k, ws, out, _stream, debug, check_mask, call):
-        """What the masked searches share (csrc/masked_topk.h).  `kind`: "filtered" / "prefix", the key of the cached workspace and the
+        """What the masked searches share (csrc/masked_topk.h).  `kind`: "filtered" / "prefix" / "filtered_multi", the key of the cached workspace and the
         word in messages; `who`: the public spelling; `workspace_bytes`: the library's arx_topk_<kind>_workspace_bytes; `check_mask(nq)`
         asserts the mask's tensors, `call(...)` is arx_topk_search_<kind>_tuned with its leading (corpus, mask, queries) arguments bound."""
         unknown = set(debug) - {"path", "cand_cap"}
@@ -258,6 +259,48 @@ class ShardIndex:
         """(queries whose candidate list overflowed and were answered by the exhaustive path, candidate groups rescored) of the LAST
         `search(allow=...)` on this index (or on `ws`).  Synchronises on the current stream."""
         return self._masked_stats("filtered", self.lib.arx_topk_filtered_stats, ws)
+
+    # ---- a different filter per query in one call -------------------------------------------------------------------------
+    def search_filtered_many(self, queries_f16: torch.Tensor, allows: torch.Tensor, filter_of: torch.Tensor, k: int = 10, n_allowed=None,
+                             ws: Optional[torch.Tensor] = None, out=None, **debug) -> Tuple[torch.Tensor, torch.Tensor]:
+        """queries fp16 [Q, D], `allows` int64 / uint64 [F, ceil(n_rows / 64)] (F <= 64 bitmaps in the convention of `search(allow=...)`)
+        and `filter_of` int32 [Q], all on the device -> (scores f32 [Q, k], ids int64 [Q, k]): for query q the exact top-k of the rows
+        `allows[filter_of[q]]` allows (`arx_topk_search_filtered_multi`), bit for bit what `search(q, allow=allows[filter_of[q]])` returns
+        for that query alone, with the shard read once for the whole batch instead of once per filter.  A `filter_of[q]` outside [0, F)
+        means the query sees no row: all (-inf, -1).  `n_allowed`: a sequence of F counts of allowed rows (None or -1 = unknown) if the
+        caller knows them.  Runs on the fp16 rows.  Test hooks as for `search(allow=...)`: `path` and `cand_cap`;
+        `filtered_many_stats` reads the counters."""
+        q = queries_f16
+        if not (torch.is_tensor(allows) and allows.dim() == 2):
+            raise ValueError("allows must be a 2-d device tensor [F, ceil(n_rows / 64)]")
+        n_filters, n_words = int(allows.shape[0]), (self.n_rows + 63) // 64
+        if not (1 <= n_filters <= 64):
+            raise ValueError(f"allows holds {n_filters} filters: one call takes 1..64")
+        if n_allowed is not None:
+            counts = [-1 if c is None else int(c) for c in n_allowed]
+            if len(counts) != n_filters:
+                raise ValueError(f"n_allowed has {len(counts)} entries for {n_filters} filters")
+            n_allowed_c = (C.c_int64 * n_filters)(*counts)
+        else:
+            n_allowed_c = None
+
+        def check_mask(nq):
+            assert allows.is_cuda and allows.dtype in (torch.int64, torch.uint64) and allows.is_contiguous()
+            assert allows.shape[1] == n_words, f"allows has {allows.shape[1]} words per filter, the shard's {self.n_rows} rows need {n_words}"
+            assert filter_of.is_cuda and filter_of.dtype == torch.int32 and filter_of.shape == (nq,) and filter_of.is_contiguous()
+
+        def workspace_bytes(n_rows, nq, dim, kk):
+            return self.lib.arx_topk_filtered_multi_workspace_bytes(n_rows, nq, n_filters, dim, kk)
+
+        def call(*rest):
+            return self.lib.arx_topk_search_filtered_multi_tuned(self.corpus.data_ptr(), self.n_rows, allows.data_ptr(), n_filters, n_allowed_c,
+                                                                 filter_of.data_ptr(), q.data_ptr(), *rest)
+        return self._search_masked("filtered_multi", "search_filtered_many()", workspace_bytes, q, k, ws, out, None, debug, check_mask, call)
+
+    def filtered_many_stats(self, ws: Optional[torch.Tensor] = None) -> Tuple[int, int]:
+        """(queries whose candidate list overflowed and were answered by the exhaustive path, candidate groups rescored) of the LAST
+        `search_filtered_many` on this index (or on `ws`).  Synchronises on the current stream."""
+        return self._masked_stats("filtered_multi", self.lib.arx_topk_filtered_multi_stats, ws)
 
     # ---- a row limit per query (near-duplicate detection) -----------------------------------------------------------------
     def search_prefix(self, queries_f16: torch.Tensor, row_limit: torch.Tensor, k: int = 10, ws: Optional[torch.Tensor] = None,
@@ -391,16 +434,47 @@ class ShardIndex:
         return out
 
     def search_distributed(self, queries_f16: torch.Tensor, k: int = 10, group=None, allow: Optional[torch.Tensor] = None,
-                           n_allowed: Optional[int] = None):
+                           n_allowed=None, allows: Optional[torch.Tensor] = None, filter_of: Optional[torch.Tensor] = None):
         """Every rank passes the SAME queries; returns the global top-k on every rank.  `allow` / `n_allowed` (see `search`): each rank
-        filters its OWN shard with its own bitmap; the gather and the merge are the same."""
+        filters its OWN shard with its own bitmap; the gather and the merge are the same.  `allows` + `filter_of` (see
+        `search_filtered_many`; `n_allowed` is then its sequence of counts): a filter per query, again each rank's own bitmaps."""
         import torch.distributed as dist
-        s, i = self.search(queries_f16, k, allow=allow, n_allowed=n_allowed)
+        if (allows is None) != (filter_of is None):
+            raise ValueError("allows and filter_of go together")
+        if allows is not None:
+            if allow is not None:
+                raise ValueError("pass allow (one filter for the call) or allows + filter_of (one per query), not both")
+            s, i = self.search_filtered_many(queries_f16, allows, filter_of, k, n_allowed=n_allowed)
+        else:
+            s, i = self.search(queries_f16, k, allow=allow, n_allowed=n_allowed)
         if not dist.is_initialized():
             return s, i
         # world size 1 takes the same gather + merge path (a 1-part merge is the identity): one code path to test
         all_s, all_i = gather_partials(s, i, group)
         return merge_partials(all_s, all_i, k)
+
+
+def search_filtered_grouped(index: ShardIndex, queries_f16: torch.Tensor, k: int, bitmaps, filter_of, counts=None, group=None):
+    """`ShardIndex.search_filtered_many` (through `search_distributed`) for ANY number of distinct filters: `bitmaps` is a list of device
+    int64 [ceil(n_rows / 64)] tensors, `filter_of` a host sequence with the index of every query's bitmap, `counts` the bitmaps' allowed
+    rows (or None).  The batch is cut into calls of at most 64 distinct filters (`filter_sets.filter_groups`) and the rows are put back
+    in query order -> (scores [Q, k], ids [Q, k]) as one call would return them."""
+    from .filter_sets import filter_groups
+    q = queries_f16
+    dev = q.device
+    groups = filter_groups(filter_of)
+    scores = torch.empty((q.shape[0], k), dtype=torch.float32, device=dev)
+    ids = torch.empty((q.shape[0], k), dtype=torch.int64, device=dev)
+    for positions, filters, local_of in groups:
+        allows = torch.stack([bitmaps[f] for f in filters]).contiguous()
+        fo = torch.tensor(local_of, dtype=torch.int32, device=dev)
+        n_allowed = None if counts is None else [counts[f] for f in filters]
+        if len(groups) == 1:                                   # the whole batch, already in order
+            return index.search_distributed(q, k, group, n_allowed=n_allowed, allows=allows, filter_of=fo)
+        pos = torch.tensor(positions, dtype=torch.int64, device=dev)
+        s, i = index.search_distributed(q[pos].contiguous(), k, group, n_allowed=n_allowed, allows=allows, filter_of=fo)
+        scores[pos], ids[pos] = s, i
+    return scores, ids
 
 
 _CU_STREAMS = {}

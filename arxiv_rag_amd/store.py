@@ -135,9 +135,58 @@ class HipCollection:
     def count(self) -> int:
         return self.n_total
 
+    def _allow_of(self, where, doc_tree, device):
+        """(row bitmap on the device, number of allowed rows) of a `where` dict, a compiled `where_document` tree and the dedup
+        keep-bitmap, and-ed; (None, None) when there is none of the three."""
+        import torch
+        allow = n_allowed = None
+        if where is not None:
+            from .where import compile_where, evaluate, pack_bitmap
+            mask = evaluate(compile_where(where), self.metadata, self.lo, self.hi, cache=self._where_columns)
+            if self._keep_mask is not None:
+                mask = mask & self._keep_mask
+            allow, n_allowed = torch.from_numpy(pack_bitmap(mask).view(np.int64)).to(device), int(mask.sum())
+        if doc_tree is not None:
+            if allow is None:
+                allow, n_allowed = self.documents.allow(doc_tree)
+            else:
+                allow = (allow & self.documents.fold(doc_tree)).contiguous()
+                n_allowed = self.documents.count(allow)
+        if self._keep is not None:
+            if where is None and doc_tree is None:
+                allow, n_allowed = self._keep, int(self._keep_mask.sum())
+            elif where is None:                                  # (with `where` the host mask above already holds it)
+                allow = (allow & self._keep).contiguous()
+                n_allowed = self.documents.count(allow)
+        return allow, n_allowed
+
+    def _search_per_query(self, q, k, where, where_document):
+        """The search of `query` when `where` / `where_document` hold one entry per query: one bitmap per distinct pair, one
+        `search_filtered_many` per 64 of them."""
+        import torch
+        from .filter_sets import distinct_filters, per_query_list
+        from .index import search_filtered_grouped
+        nq = q.shape[0]
+        pairs, filter_of = distinct_filters(per_query_list(where, nq, "where"), per_query_list(where_document, nq, "where_document"))
+        if any(d is not None for _, d in pairs) and self.documents is None:
+            raise ValueError("where_document needs a collection built with documents=True")
+        bitmaps, counts = [], []
+        for w, d in pairs:
+            doc_tree = None
+            if d is not None:
+                from .where_document import compile_where_document
+                doc_tree = compile_where_document(d)
+            allow, n_allowed = self._allow_of(w, doc_tree, q.device)
+            if allow is None:                                    # no filter for these queries: every row of the shard
+                allow = torch.full(((self.hi - self.lo + 63) // 64,), -1, dtype=torch.int64, device=q.device)
+                n_allowed = self.hi - self.lo
+            bitmaps.append(allow)
+            counts.append(n_allowed)
+        return search_filtered_grouped(self.index, q, k, bitmaps, filter_of, counts)
+
     def query(self, query_embeddings=None, query_texts: Optional[Sequence[str]] = None, n_results: int = 10, reranker=None,
-              n_candidates: int = 32, hybrid_alpha: Optional[float] = None, where: Optional[Dict] = None,
-              where_document: Optional[Dict] = None, mmr_lambda: Optional[float] = None) -> Dict:
+              n_candidates: int = 32, hybrid_alpha: Optional[float] = None, where=None, where_document=None,
+              mmr_lambda: Optional[float] = None) -> Dict:
         """`reranker` (a `rerank.HipCrossEncoder`; needs `query_texts`): the search fetches `n_candidates` (<= 32) rows per query,
         the cross-encoder scores (query, document) for each, and the best `n_results` come back in reranked order with an added
         `rerank_scores` list per query (`scores` / `distances` stay the cosine ones).
@@ -165,8 +214,21 @@ class HipCollection:
         the search's cosine values of the picked rows and an added `mmr_scores` list per query holds the objective at each pick.
         Together with `reranker` or `hybrid_alpha` it raises ValueError: diversifying a reranked or a fused list is out of scope.
         A collection built with `dedup_threshold` never returns a row it flagged as a duplicate, whatever the other parameters; with
-        `hybrid_alpha` it raises ValueError for the same reason as `where`."""
+        `hybrid_alpha` it raises ValueError for the same reason as `where`.
+        `where` and `where_document` may each also be a list or tuple with ONE ENTRY PER QUERY, a filter dict or None (no filter for that
+        query); a list of another length is a ValueError.  Each query is then restricted to its own filter (and-ed with the other
+        argument's entry, or its single dict, and with the dedup keep-bitmap): the bitmap of every distinct (where, where_document) pair
+        is built once and the whole batch is answered by `ShardIndex.search_filtered_many`, which reads the shard once, not once per
+        filter; a batch with more than 64 distinct pairs is cut into calls of at most 64.  Query by query the result is what the same
+        call with that query alone and its own dict returns; `reranker` and `mmr_lambda` compose as before, `hybrid_alpha` raises the
+        same ValueError.  A single dict (or None) means what it meant."""
         import torch
+        from .filter_sets import is_per_query
+        per_query = None
+        if is_per_query(where) or is_per_query(where_document):
+            if hybrid_alpha is not None:
+                raise ValueError("where cannot be combined with hybrid_alpha: the BM25 keyword search has no row filter")
+            per_query, where, where_document = (where, where_document), None, None
         if self._keep is not None and hybrid_alpha is not None:
             raise ValueError("a collection built with dedup_threshold cannot be queried with hybrid_alpha: the BM25 keyword search has no "
                              "row filter")
@@ -205,27 +267,12 @@ class HipCollection:
         q = torch.from_numpy(np.ascontiguousarray(query_embeddings, dtype=np.float16)).to(self.index.corpus.device)
         if q.dim() == 1:
             q = q[None]
-        allow = n_allowed = None
-        if where is not None:
-            from .where import compile_where, evaluate, pack_bitmap
-            mask = evaluate(compile_where(where), self.metadata, self.lo, self.hi, cache=self._where_columns)
-            if self._keep_mask is not None:
-                mask = mask & self._keep_mask
-            allow, n_allowed = torch.from_numpy(pack_bitmap(mask).view(np.int64)).to(q.device), int(mask.sum())
-        if where_document is not None:
-            if allow is None:
-                allow, n_allowed = self.documents.allow(doc_tree)
-            else:
-                allow = (allow & self.documents.fold(doc_tree)).contiguous()
-                n_allowed = self.documents.count(allow)
-        if self._keep is not None:
-            if where is None and where_document is None:
-                allow, n_allowed = self._keep, int(self._keep_mask.sum())
-            elif where is None:                                  # (with `where` the host mask above already holds it)
-                allow = (allow & self._keep).contiguous()
-                n_allowed = self.documents.count(allow)
         wide = reranker is not None or hybrid_alpha is not None or mmr_lambda is not None
-        s, i = self.index.search_distributed(q, n_candidates if wide else n_results, allow=allow, n_allowed=n_allowed)
+        if per_query is not None:
+            s, i = self._search_per_query(q, n_candidates if wide else n_results, *per_query)
+        else:
+            allow, n_allowed = self._allow_of(where, doc_tree if where_document is not None else None, q.device)
+            s, i = self.index.search_distributed(q, n_candidates if wide else n_results, allow=allow, n_allowed=n_allowed)
         mmr_val = None
         if mmr_lambda is not None:
             from .mmr import mmr_select

@@ -284,6 +284,38 @@ int32_t arx_topk_search_filtered_tuned(const void* corpus, int64_t n_rows, const
  * search on this workspace.  Copies 16 bytes to the host and waits on `stream`. */
 int32_t arx_topk_filtered_stats(const void* ws, int64_t* overflowed_queries, int64_t* candidate_groups, void* stream);
 
+/* ---- Filtered exact top-k with a different filter per query in one call (csrc/filter_multi.hip) ---------------------------------------
+ * allow: device uint64 [n_filters][ceil(n_rows / 64)], each row a bitmap in the convention of arx_topk_search_filtered (bits at or
+ * beyond n_rows are ignored and may be garbage); 1 <= n_filters <= 64.  filter_of: device int32 [n_queries]; query q may return only
+ * the rows of allow[filter_of[q]].  A filter_of[q] outside [0, n_filters) means query q sees no row: its output is all (-inf, -1), and
+ * nothing is read out of range (the kernels test the index; the host never sees it).  n_allowed: HOST int64 [n_filters], the number of
+ * set bits below n_rows of each bitmap, -1 where unknown, or NULL = all unknown; it only steers path 0.
+ * Query q's scores and ids are those of arx_topk_search_filtered called with that query alone and allow[filter_of[q]], bit for bit: a
+ * query's output depends on the query, its own bitmap and the corpus alone - not on the other queries, their filters, the order of the
+ * batch, n_filters, the path or cand_cap.  The shard is read once per call, not once per filter: a 256-row tile is skipped only when
+ * no filter used by the block's 64 / 128 / 256 queries has a bit in it.  max_row_norm, dim % 64 == 0, k <= 32, any n_queries (sliced
+ * above 1 024), output conventions and the two device paths as for arx_topk_search_filtered; the exhaustive path computes a query's row
+ * list from per-filter popcount offsets instead of storing it, and path 0 takes it only when every n_allowed[f] is given and
+ * max_f n_allowed[f] * n_queries < 2^18.  n_filters outside 1..64 or a null pointer: ARX_ERR_ARG before any launch.
+ * ws: device workspace of arx_topk_filtered_multi_workspace_bytes(...) bytes, caller-owned; with qb = min(n_queries, 1 024), ldg = qb
+ * rounded up to 64, G = ceil(n_rows / 64) and P = min(ceil(n_rows / 256), 128) it is the sum, each term rounded up to 256 bytes, of
+ * 64 + 4 G ldg + (4 ldg + 12 ldg / 64) + 8 * 64 (G + 1) + 4 qb + 4 P qb k + 8 P qb k: the offsets are laid out for 64 filters
+ * whatever n_filters is (n_filters outside 1..64 returns -1). */
+int64_t arx_topk_filtered_multi_workspace_bytes(int64_t n_rows, int32_t n_queries, int32_t n_filters, int32_t dim, int32_t k);
+int32_t arx_topk_search_filtered_multi(const void* corpus, int64_t n_rows, const uint64_t* allow, int32_t n_filters,
+                                       const int64_t* n_allowed, const int32_t* filter_of, const void* queries, int32_t n_queries,
+                                       int32_t dim, int32_t k, float* out_scores, int64_t* out_ids, int64_t idx_base, float max_row_norm,
+                                       void* ws, int64_t ws_bytes, void* stream);
+/* The same with the path and the candidate capacity chosen by the caller (tests, tuning), as arx_topk_search_filtered_tuned.  Same
+ * bits for every choice. */
+int32_t arx_topk_search_filtered_multi_tuned(const void* corpus, int64_t n_rows, const uint64_t* allow, int32_t n_filters,
+                                             const int64_t* n_allowed, const int32_t* filter_of, const void* queries, int32_t n_queries,
+                                             int32_t dim, int32_t k, float* out_scores, int64_t* out_ids, int64_t idx_base,
+                                             float max_row_norm, void* ws, int64_t ws_bytes, int32_t path, int32_t cand_cap, void* stream);
+/* {queries sent to the exhaustive path because their candidate list overflowed, candidate groups rescored} of the LAST multi-filter
+ * search on this workspace.  Copies 16 bytes to the host and waits on `stream`. */
+int32_t arx_topk_filtered_multi_stats(const void* ws, int64_t* overflowed_queries, int64_t* candidate_groups, void* stream);
+
 /* ---- Exact top-k with a row limit per query (the self-join of near-duplicate detection) ----------------------------------------------
  * row_limit: device int64 [n_queries]; query q may return only the local rows r < row_limit[q] (clamped to [0, n_rows]).  The answer is
  * the exact top-k of those rows, score descending, ties to the lower row, ids = local row + idx_base, (-inf, -1) padding when fewer than

@@ -41,6 +41,15 @@ class TopkOptionsC(C.Structure):
         self.struct_bytes = C.sizeof(TopkOptionsC)
 
 
+class EncoderOptionsC(C.Structure):
+    """arx_encoder_options (include/arx.h): the kernels a handle runs, chosen when it is created."""
+    _fields_ = [("struct_bytes", C.c_int32), ("gemm_schedule", C.c_int32), ("attn_kernel", C.c_int32), ("flags", C.c_int32)]
+
+    def __init__(self, **kw):
+        super().__init__(**kw)
+        self.struct_bytes = C.sizeof(EncoderOptionsC)
+
+
 class PairHeadC(C.Structure):
     """arx_pair_head (include/arx.h): the cross-encoder head's device weights."""
     _fields_ = [("struct_bytes", C.c_int32), ("n_labels", C.c_int32)] \
@@ -64,6 +73,9 @@ class GemmEpilogueC(C.Structure):
 
 
 TOPK_NO_PERSISTENT, TOPK_SCAN_ONLY, TOPK_TAIL_ONLY, TOPK_NO_SINGLE_ROW_TAIL, TOPK_I8_CENTRE_QUERY = 1, 2, 4, 8, 16
+GEMM_DEFAULT, GEMM_PER_TILE, GEMM_PERSISTENT, GEMM_2STAGE, GEMM_SPLIT_K, GEMM_TILE_128 = 89, 8, 9, 13, 70, 71          # ARX_GEMM_*
+ATTN_TRANSPOSED, ATTN_RING, ATTN_RING16, ATTN_STAGED = 1, 2, 4, 8                                                     # ARX_ATTN_*
+ENC_EXPLICIT_LAYERNORM = 1
 
 
 EXPORTS = {
@@ -75,6 +87,8 @@ EXPORTS = {
     "arx_encoder_workspace_bytes": (C.c_int64, [C.POINTER(EncoderConfigC), C.c_int32, C.c_int32]),
     "arx_encoder_create": (C.c_int32, [C.POINTER(EncoderConfigC), C.POINTER(EncoderWeightsC), C.c_int32, C.c_int32,
                                        C.POINTER(C.c_void_p)]),
+    "arx_encoder_create_opt": (C.c_int32, [C.POINTER(EncoderConfigC), C.POINTER(EncoderWeightsC), C.c_int32, C.c_int32,
+                                           C.POINTER(EncoderOptionsC), C.POINTER(C.c_void_p)]),
     "arx_encoder_destroy": (None, [C.c_void_p]),
     "arx_encoder_forward": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                         C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),

@@ -47,10 +47,10 @@ struct arx_encoder {
     std::vector<float*> s_qkv, c_qkv, s_fc1, c_fc1;
     float *st1_sum = nullptr, *st1_sq = nullptr, *st2_sum = nullptr, *st2_sq = nullptr;   // row mean / rstd of y1 / y2
     float *part_s = nullptr, *part_q = nullptr;                                              // [H/64][tok_pad] partial slabs
-    int variant = 89;
+    int variant = ARX_GEMM_DEFAULT;
     int low_latency = 0;                          // arx_encoder_set_low_latency: forwards of <= ARX_SMALL_M rows take gemm_small.h
     float* small_ws = nullptr;                    // its split-K partial sums (ARX_SMALL_WS_BYTES, allocated when the option is first set)
-    int attn_variant = 1;
+    int attn_variant = ARX_ATTN_TRANSPOSED;
     int attn_dev_word = 0;                        // dev: probes of attention_tr_kernel (0 in the product path)
     unsigned long long* attn_stamps = nullptr;    // dev: per-block time stamps
     // cross-encoder head (arx_encoder_set_pair_head): caller-owned device weights + the handle's [max_seqs, H] f32 CLS scratch
@@ -98,10 +98,35 @@ extern "C" int64_t arx_encoder_workspace_bytes(const arx_encoder_config* cfg, in
     return ws_layout(*cfg, max_tokens, max_seqs).total;
 }
 
+// ids a handle may be created with: the shipped schedules that serve a forward of any size (70 is the <= 256-row half of
+// arx_encoder_set_low_latency), the round-1 A/B schedules and the streaming attention kernels in a dev build only
+static int check_options(const arx_encoder_options* o) {
+    if (!o) return ARX_OK;
+    ARX_REQUIRE(o->struct_bytes == (int32_t)sizeof(arx_encoder_options), "arx_encoder_options: struct_bytes=%d, this library expects %d",
+                o->struct_bytes, (int)sizeof(arx_encoder_options));
+    const int g = o->gemm_schedule, a = o->attn_kernel;
+    bool gemm_ok = g == 0 || g == ARX_GEMM_DEFAULT || g == ARX_GEMM_PER_TILE || g == ARX_GEMM_PERSISTENT || g == ARX_GEMM_2STAGE || g == ARX_GEMM_TILE_128;
+    bool attn_ok = a == 0 || a == ARX_ATTN_TRANSPOSED || a == ARX_ATTN_STAGED;
+#ifdef ARX_DEV_VARIANTS
+    gemm_ok = gemm_ok || g == 1 || g == 2 || g == 3 || g == 4 || g == 15 || g == 33 || g == 34;
+    attn_ok = attn_ok || a == ARX_ATTN_RING || a == ARX_ATTN_RING16;
+#endif
+    ARX_REQUIRE(gemm_ok, "arx_encoder_options.gemm_schedule=%d is not a whole-forward GEMM schedule of this build (ARX_GEMM_* in arx.h)", g);
+    ARX_REQUIRE(attn_ok, "arx_encoder_options.attn_kernel=%d is not an attention kernel of this build (ARX_ATTN_* in arx.h)", a);
+    ARX_REQUIRE((o->flags & ~ARX_ENC_EXPLICIT_LAYERNORM) == 0, "arx_encoder_options.flags=0x%x has unknown bits", o->flags);
+    return ARX_OK;
+}
+
 extern "C" int32_t arx_encoder_create(const arx_encoder_config* cfg, const arx_encoder_weights* w, int32_t max_tokens,
                                       int32_t max_seqs, arx_encoder** out) {
+    return arx_encoder_create_opt(cfg, w, max_tokens, max_seqs, nullptr, out);
+}
+
+extern "C" int32_t arx_encoder_create_opt(const arx_encoder_config* cfg, const arx_encoder_weights* w, int32_t max_tokens,
+                                          int32_t max_seqs, const arx_encoder_options* opt, arx_encoder** out) {
     int rc = check_cfg(cfg);
     if (rc != ARX_OK) return rc;
+    if ((rc = check_options(opt)) != ARX_OK) return rc;
     ARX_REQUIRE(w && out, "null weights/out");
     ARX_REQUIRE(max_tokens > 0 && max_seqs > 0, "max_tokens/max_seqs must be positive");
     ARX_REQUIRE(w->word_emb && w->pos_emb && w->emb_ln_g && w->emb_ln_b && w->layers, "missing embedding weights");
@@ -126,14 +151,9 @@ extern "C" int32_t arx_encoder_create(const arx_encoder_config* cfg, const arx_e
     h->max_tokens = max_tokens;
     h->max_seqs = max_seqs;
     h->tok_pad = (int)round_up64(max_tokens, 256);
-    const char* e = getenv("ARX_GEMM_VARIANT");
-    h->variant = e ? atoi(e) : 89;
-    const char* av = getenv("ARX_ATTN_VARIANT");
-    h->attn_variant = av ? atoi(av) : 1;
-#ifdef ARX_DEV_VARIANTS
-    const char* g = getenv("ARX_GEMM_GLDS");          // dev switch: 0 = register-staged reference loop
-    if (g && g[0] == '0') h->variant = 4;
-#endif
+    if (opt && opt->gemm_schedule) h->variant = opt->gemm_schedule;
+    if (opt && opt->attn_kernel) h->attn_variant = opt->attn_kernel;
+    h->ln_fold = !(opt && (opt->flags & ARX_ENC_EXPLICIT_LAYERNORM));
     const WsLayout l = ws_layout(*cfg, max_tokens, max_seqs);
     hipError_t he = hipMalloc((void**)&h->ws, l.total);
     if (he != hipSuccess) {
@@ -158,8 +178,6 @@ extern "C" int32_t arx_encoder_create(const arx_encoder_config* cfg, const arx_e
         h->st1_sum = st; h->st1_sq = st + tp; h->st2_sum = st + 2 * tp; h->st2_sq = st + 3 * tp;
         h->part_s = st + 4 * tp; h->part_q = h->part_s + (int64_t)(cfg->hidden / 64) * tp;
     }
-    const char* lf = getenv("ARX_LN_FOLD");
-    h->ln_fold = lf ? atoi(lf) : 1;
     if (h->ln_fold) {
         // derived weights: per layer  W_fc1 o gamma1 (+ s, c), and for layers >= 1  W_qkv o gamma2 of the previous layer
         const int64_t H = cfg->hidden, F = cfg->ffn, Lc = cfg->layers;
@@ -294,21 +312,21 @@ int arx_launch_gemm(int variant, const uint16_t* A, int64_t lda, const uint16_t*
     // 71: the 2-stage loop on 128 x 128 tiles (4 waves, two blocks per CU) — the medium-batch half of the opt-in low-latency schedule:
     // between 256 and 8192 token rows a 256 x 256 grid leaves most CUs idle while each tile walks its whole K (17 us at K = 768, 70 us at
     // K = 3072 whatever the row count); four times the tiles, a quarter of the work each
-    if (variant == 71)
+    if (variant == ARX_GEMM_TILE_128)
         return launch_gemm_kernel(gemm_v0e2_kernel<128, 128, 2, 2, MODE, 67>, GemmMainloop<bf16_t, 128, 128, 2, 2, true, 67>::SMEM_BYTES, 256, 128, 128, A, lda, W, ldw, M, N, K, ep, st);
     // 89 = DEFAULT: persistent kernel for the short-K shapes (K <= 1024: QKV, O-projection, FFN-1 — the per-tile first-load latency is
     // 10-14 % of such a tile; +2..4 % measured in situ, same box), per-tile kernel for the long-K one (FFN-2: -3 % when persistent)
-    if (variant == 89) variant = (K <= 1024) ? 9 : 8;
-    if (variant == 9 && (K / 64) % 2 != 0) variant = 8;          // the persistent form needs an even number of k-tiles (buffer parity)
-    if ((variant == 8 || variant == 9) && wide8 && !fits_u32_offsets(M, lda, N, ldw, ep)) {
+    if (variant == ARX_GEMM_DEFAULT) variant = (K <= 1024) ? ARX_GEMM_PERSISTENT : ARX_GEMM_PER_TILE;
+    if (variant == ARX_GEMM_PERSISTENT && (K / 64) % 2 != 0) variant = ARX_GEMM_PER_TILE;          // the persistent form needs an even number of k-tiles (buffer parity)
+    if ((variant == ARX_GEMM_PER_TILE || variant == ARX_GEMM_PERSISTENT) && wide8 && !fits_u32_offsets(M, lda, N, ldw, ep)) {
         static bool said = false;                                // once per process: the shape is served, by the slower kernel
         if (!said) {
             said = true;
             fprintf(stderr, "[arx] gemm M=%d N=%d K=%d: operand or output offsets exceed 32 bits, using the 2-stage kernel (64-bit offsets)\n", M, N, K);
         }
-        variant = 13;
+        variant = ARX_GEMM_2STAGE;
     }
-    if (variant == 9 && wide8) {                                 // persistent 4-phase schedule
+    if (variant == ARX_GEMM_PERSISTENT && wide8) {                                 // persistent 4-phase schedule
         auto kern = gemm_8phase_persistent_kernel<MODE>;
         ARX_HIP_CHECK(arx_func_smem((const void*)kern, Gemm8Phase<bf16_t, 0>::SMEM_BYTES));
         const int n_cu = arx_device_cus();
@@ -319,7 +337,7 @@ int arx_launch_gemm(int variant, const uint16_t* A, int64_t lda, const uint16_t*
         ARX_HIP_CHECK(hipGetLastError());
         return ARX_OK;
     }
-    if (variant == 8 && wide8) {                                 // 4-phase-per-k-tile schedule (gemm8.h)
+    if (variant == ARX_GEMM_PER_TILE && wide8) {                                 // 4-phase-per-k-tile schedule (gemm8.h)
         auto kern = gemm_8phase_kernel<MODE>;
         ARX_HIP_CHECK(arx_func_smem((const void*)kern, Gemm8Phase<bf16_t, 0>::SMEM_BYTES));
         const int tm = cdiv(M, 256), tn = cdiv(N, 256);
@@ -353,7 +371,7 @@ template <int MODE>
 static int launch_gemm(int cls, int variant, const uint16_t* A, int64_t lda, const uint16_t* W, int64_t ldw, int M, int N, int K,
                        const EpiParams& ep, hipStream_t st, float* small_ws = nullptr) {
     ProfScope ps(cls, st);
-    if (variant == 70) return launch_gemm_small<MODE>(A, lda, W, ldw, M, N, K, ep, small_ws, st);      // small-batch path (gemm_small.h)
+    if (variant == ARX_GEMM_SPLIT_K) return launch_gemm_small<MODE>(A, lda, W, ldw, M, N, K, ep, small_ws, st);      // small-batch path (gemm_small.h)
 #ifdef ARX_DEV_VARIANTS
     static const int dev_bw = getenv("ARX_DEV_BW") ? atoi(getenv("ARX_DEV_BW")) : 0;      // dev A/B in situ: tile-walk band width
     const char* stg = getenv("ARX_DEV_STAGGER");      // "cycles[,slots[,store]]"
@@ -427,7 +445,7 @@ extern "C" int32_t arx_gemm_bf16(const void* A, const void* W, const float* bias
     }
 #endif
     ProfScope ps(ARX_K_GEMM_RAW, st);       // its own class: a raw call has whatever shape the caller chose, not FFN-1's
-    if (variant == 70) {          // small-batch path alone (tests / tuning): a stream-ordered scratch for this call, released behind its kernels
+    if (variant == ARX_GEMM_SPLIT_K) {          // small-batch path alone (tests / tuning): a stream-ordered scratch for this call, released behind its kernels
         float* ws = nullptr;
         ARX_HIP_CHECK(hipMallocAsync((void**)&ws, ARX_SMALL_WS_BYTES, st));
         int rc = ARX_ERR_ARG;
@@ -515,14 +533,14 @@ static int launch_attn(arx_encoder* h, int n_seqs, int max_len, hipStream_t st) 
     const int dh = h->cfg.hidden / h->cfg.heads;
     const bool hb = h->cfg.arch == ARX_ARCH_MPNET;
 #ifdef ARX_DEV_VARIANTS
-    if (h->attn_variant == 4 && dh == 64 && max_len > 128 && max_len <= 256)      // 16-wave ring kernel (encoder_kernels.h "attention v4")
+    if (h->attn_variant == ARX_ATTN_RING16 && dh == 64 && max_len > 128 && max_len <= 256)      // 16-wave ring kernel (encoder_kernels.h "attention v4")
         return hb ? launch_attn_ring16_cfg<true>(h, n_seqs, max_len, st) : launch_attn_ring16_cfg<false>(h, n_seqs, max_len, st);
-    if (h->attn_variant == 2 && max_len > 128 && max_len <= 256) {      // streaming ring kernel (encoder_kernels.h "attention v3"), one block per CU
+    if (h->attn_variant == ARX_ATTN_RING && max_len > 128 && max_len <= 256) {      // streaming ring kernel (encoder_kernels.h "attention v3"), one block per CU
         if (dh == 64) return hb ? launch_attn_ring_cfg<64, true, 8>(h, n_seqs, max_len, st) : launch_attn_ring_cfg<64, false, 8>(h, n_seqs, max_len, st);
         return hb ? launch_attn_ring_cfg<32, true, 8>(h, n_seqs, max_len, st) : launch_attn_ring_cfg<32, false, 8>(h, n_seqs, max_len, st);
     }
 #endif
-    if (h->attn_variant >= 1) {      // transposing-read kernel; 8 waves cover 256 queries, 4 waves for short batches
+    if (h->attn_variant != ARX_ATTN_STAGED) {      // transposing-read kernel; 8 waves cover 256 queries, 4 waves for short batches
         const bool w8 = max_len > 128;
         if (dh == 64) {
             if (hb) return w8 ? launch_attn_tr_cfg<64, true, 8>(h, n_seqs, max_len, st) : launch_attn_tr_cfg<64, true, 4>(h, n_seqs, max_len, st);
@@ -575,7 +593,7 @@ static int gemm_ex_run(int variant, const uint16_t* A, const uint16_t* W, int M,
                        hipStream_t st) {
     constexpr bool STATS = (MODE == EPI_RESID_STATS || MODE == EPI_LNRESID_STATS);
     int rc;
-    if (variant == 70) {          // a stream-ordered scratch for this call, released behind its kernels (as arx_gemm_bf16)
+    if (variant == ARX_GEMM_SPLIT_K) {          // a stream-ordered scratch for this call, released behind its kernels (as arx_gemm_bf16)
         float* ws = nullptr;
         ARX_HIP_CHECK(hipMallocAsync((void**)&ws, ARX_SMALL_WS_BYTES, st));
         rc = launch_gemm<MODE>(ARX_K_GEMM_RAW, variant, A, K, W, K, M, N, K, ep, st, ws);
@@ -599,10 +617,11 @@ extern "C" int32_t arx_gemm_bf16_ex(const void* A, const void* W, void* C, int32
     ARX_REQUIRE(K % 64 == 0 && N % 8 == 0, "gemm: K=%d must be a multiple of 64 and N=%d of 8", K, N);
     const int mode = e->mode, variant = e->variant;
     ARX_REQUIRE(mode >= EPI_BIAS && mode <= EPI_LNRESID_STATS, "unknown gemm mode %d", mode);
-    ARX_REQUIRE(variant == 89 || variant == 8 || variant == 9 || variant == 13 || variant == 70 || variant == 71,
+    ARX_REQUIRE(variant == ARX_GEMM_DEFAULT || variant == ARX_GEMM_PER_TILE || variant == ARX_GEMM_PERSISTENT || variant == ARX_GEMM_2STAGE ||
+                    variant == ARX_GEMM_SPLIT_K || variant == ARX_GEMM_TILE_128,
                 "gemm variant %d is not a shipped schedule (89, 8, 9, 13, 70, 71)", variant);
     const bool ln_in = (mode == EPI_LN_BIAS || mode == EPI_LN_BIAS_GELU), stats = (mode == EPI_RESID_STATS || mode == EPI_LNRESID_STATS);
-    const bool staged = (variant == 89 || variant == 8 || variant == 9);      // epilogue v3 stages 256 rows of every row vector at once
+    const bool staged = (variant == ARX_GEMM_DEFAULT || variant == ARX_GEMM_PER_TILE || variant == ARX_GEMM_PERSISTENT);      // epilogue v3 stages 256 rows of every row vector at once
     ARX_REQUIRE(e->bias, "mode %d needs bias", mode);
     ARX_REQUIRE(!(mode == EPI_BIAS_RESID || stats) || e->resid, "mode %d needs resid", mode);
     ARX_REQUIRE(!ln_in || (e->a_mean && e->a_rstd && e->s_vec), "mode %d needs a_mean, a_rstd and s_vec", mode);
@@ -614,10 +633,10 @@ extern "C" int32_t arx_gemm_bf16_ex(const void* A, const void* W, void* C, int32
     if (stats) {
         ARX_REQUIRE(N % 64 == 0, "statistics modes need N %% 64 == 0 (one partial per 64-column slice), N=%d", N);
         ARX_REQUIRE(e->out_mean && e->out_rstd, "mode %d needs out_mean and out_rstd", mode);
-        if (variant != 70) ARX_REQUIRE(e->part_sum && e->part_sq && e->part_ld >= M && e->n_rows,
+        if (variant != ARX_GEMM_SPLIT_K) ARX_REQUIRE(e->part_sum && e->part_sq && e->part_ld >= M && e->n_rows,
                                        "mode %d on a tile kernel needs part_sum, part_sq, part_ld >= M and n_rows", mode);
     }
-    if (variant == 70) {
+    if (variant == ARX_GEMM_SPLIT_K) {
         ARX_REQUIRE(M <= ARX_SMALL_M && N % 64 == 0, "small-batch gemm: M=%d (<= %d) N=%d (%% 64)", M, ARX_SMALL_M, N);
         ARX_REQUIRE(!stats || N <= 1024, "small-batch gemm: statistics modes take N <= 1024, N=%d", N);
     }
@@ -730,7 +749,7 @@ static int32_t encoder_run(arx_encoder* h, const int32_t* ids, int32_t seq_strid
     //   x1 : PRE-LN1 sum y1 of the current layer;  (st1, st2) : row sums / sums of squares of y1 / y2
     const float inv_h = 1.0f / (float)H;
     // opt-in low-latency schedule: a query batch takes split-K wave tiles (<= 256 rows) or 128 x 128 tiles (<= 8192 rows) instead of 256 x 256 tiles
-    const int gv = !h->low_latency ? h->variant : (T <= ARX_SMALL_M ? 70 : (T <= ARX_MEDIUM_M ? 71 : h->variant));
+    const int gv = !h->low_latency ? h->variant : (T <= ARX_SMALL_M ? ARX_GEMM_SPLIT_K : (T <= ARX_MEDIUM_M ? ARX_GEMM_TILE_128 : h->variant));
     if (h->tap_layer == 0 && h->tap) ARX_HIP_CHECK(hipMemcpyAsync(h->tap, h->x, (int64_t)T * H * 2, hipMemcpyDeviceToDevice, st));
     for (int li = 0; li < c.layers; ++li) {
         const arx_layer_weights& L = h->layers[li];
@@ -755,7 +774,7 @@ static int32_t encoder_run(arx_encoder* h, const int32_t* ids, int32_t seq_strid
             ep.r_sum = h->st2_sum; ep.r_sq = h->st2_sq; ep.r_gamma = P.ln2_g; ep.r_beta = P.ln2_b;
             if ((rc = launch_gemm<EPI_LNRESID_STATS>(ARX_K_GEMM_OPROJ, gv, h->ctx, H, (const uint16_t*)L.w_o, H, T, H, H, ep, st, h->small_ws)) != ARX_OK) return rc;
         }
-        if (gv != 70) { ProfScope ps(ARX_K_LAYERNORM, st);
+        if (gv != ARX_GEMM_SPLIT_K) { ProfScope ps(ARX_K_LAYERNORM, st);
           launch_ln_finalize(T, H / 64, h->part_s, h->part_q, tp, h->cu + n_seqs, inv_h, c.ln_eps, h->st1_sum, h->st1_sq, st); }
         ARX_HIP_CHECK(hipGetLastError());
         // hbuf = gelu(LN1(y1) W1^T + b1)   (gamma1 folded into W1')
@@ -768,7 +787,7 @@ static int32_t encoder_run(arx_encoder* h, const int32_t* ids, int32_t seq_strid
         ep.o_sum = h->part_s; ep.o_sq = h->part_q; ep.o_ld = tp; ep.inv_h = inv_h; ep.eps = c.ln_eps;
         ep.fin_mean = h->st2_sum; ep.fin_rstd = h->st2_sq;
         if ((rc = launch_gemm<EPI_LNRESID_STATS>(ARX_K_GEMM_FC2, gv, h->hbuf, F, (const uint16_t*)L.w_fc2, F, T, H, F, ep, st, h->small_ws)) != ARX_OK) return rc;
-        if (gv != 70) { ProfScope ps(ARX_K_LAYERNORM, st);
+        if (gv != ARX_GEMM_SPLIT_K) { ProfScope ps(ARX_K_LAYERNORM, st);
           launch_ln_finalize(T, H / 64, h->part_s, h->part_q, tp, h->cu + n_seqs, inv_h, c.ln_eps, h->st2_sum, h->st2_sq, st); }
         ARX_HIP_CHECK(hipGetLastError());
         if (h->tap_layer == li + 1 && h->tap) {       // parity tap: materialise LN2(y2) with the stand-alone kernel

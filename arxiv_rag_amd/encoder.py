@@ -28,14 +28,20 @@ def _dev_ptr(t: Optional[torch.Tensor]) -> Optional[int]:
 
 
 class HipEncoder:
-    """Token ids -> unit-norm sentence embeddings on one GPU (one handle, one stream user)."""
+    """Token ids -> unit-norm sentence embeddings on one GPU (one handle, one stream user).
+
+    `gemm_schedule` / `attn_kernel` (`_lib.GEMM_*` / `_lib.ATTN_*` ids) and `ln_fold=False` (the two-pass LayerNorm kernels) select
+    the alternatives kept beside the default kernels (`arx_encoder_options`); the handle runs them for its whole life, an id the
+    loaded build does not contain raises, and the three attributes say what was chosen."""
 
     def __init__(self, cfg: EncoderConfig, state_dict: Dict[str, np.ndarray], device: Union[str, torch.device] = "cuda:0",
-                 max_tokens: int = 32 * 512, max_seqs: int = 32):
+                 max_tokens: int = 32 * 512, max_seqs: int = 32, *, gemm_schedule: int = _lib.GEMM_DEFAULT,
+                 attn_kernel: int = _lib.ATTN_TRANSPOSED, ln_fold: bool = True):
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise _lib.ArxError("no HIP device visible: the encoder has no CPU path")
         self.cfg = cfg
+        self.gemm_schedule, self.attn_kernel, self.ln_fold = int(gemm_schedule), int(attn_kernel), bool(ln_fold)
         self.device = torch.device(device)
         torch.cuda.set_device(self.device)
         self._w: List[torch.Tensor] = []          # keeps device weights alive
@@ -97,8 +103,10 @@ class HipEncoder:
         max_tokens = max(max_tokens, self._cap[0]); max_seqs = max(max_seqs, self._cap[1])
         self.close()
         h = C.c_void_p(None)
-        _lib.check(self.lib.arx_encoder_create(C.byref(self._cfg_c), C.byref(self._weights_c), max_tokens, max_seqs,
-                                               C.byref(h)), "arx_encoder_create")
+        opt = _lib.EncoderOptionsC(gemm_schedule=self.gemm_schedule, attn_kernel=self.attn_kernel,
+                                   flags=0 if self.ln_fold else _lib.ENC_EXPLICIT_LAYERNORM)
+        _lib.check(self.lib.arx_encoder_create_opt(C.byref(self._cfg_c), C.byref(self._weights_c), max_tokens, max_seqs,
+                                                   C.byref(opt), C.byref(h)), "arx_encoder_create_opt")
         self._handle = h
         self._cap = (max_tokens, max_seqs)
         self._low_latency = False

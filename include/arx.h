@@ -18,9 +18,11 @@
  *   - an opaque handle owns only its private workspace (create/destroy).
  *   - every launch goes on the caller's hipStream_t (passed as void*); no hidden synchronisation.
  *   - return 0 on success, negative on error; arx_last_error() gives the thread-local message.
- *   - one host thread per handle.  The search entry points keep NO process-wide state: everything a call depends on is in its
- *     arguments (arx_topk_options) and its workspace, so different host threads may search different (or the same) shards at once,
- *     each with its own workspace and stream.  The only process-wide state in the library is the opt-in arx_prof_* timing facility.
+ *   - one host thread per handle.  The library keeps NO process-wide policy and reads no environment variable: what a search does is
+ *     in its arguments (arx_topk_options) and its workspace, what an encoder handle runs is fixed by the arguments of its create call
+ *     (arx_encoder_options), so different host threads may search different (or the same) shards at once, each with its own workspace
+ *     and stream.  The only process-wide state in the library is the opt-in arx_prof_* timing facility.  (A -DARX_DEV_VARIANTS build
+ *     additionally reads a few ARX_DEV_* / ARX_STAMP_* measurement switches.)
  */
 #ifndef ARX_H
 #define ARX_H
@@ -31,7 +33,8 @@
 extern "C" {
 #endif
 
-#define ARX_VERSION 111            /* 0.1.1: search policy per call (arx_topk_options), no process-wide search state; 111: the int8 index is centred (layout + 4 dim bytes) */
+#define ARX_VERSION 112            /* 0.1.1: search policy per call (arx_topk_options), no process-wide search state; 111: the int8 index is centred (layout + 4 dim bytes);
+                                      112: encoder schedules per handle (arx_encoder_options), no environment variable is read */
 
 #define ARX_OK            0
 #define ARX_ERR_ARG      -1        /* bad argument / unsupported shape */
@@ -100,6 +103,32 @@ int32_t arx_encoder_create(const arx_encoder_config* cfg, const arx_encoder_weig
                            int32_t max_tokens, int32_t max_seqs, arx_encoder** out);
 void    arx_encoder_destroy(arx_encoder* h);
 
+/* Which kernels a handle runs, fixed for its life at create (round <= 4: environment variables).  Zero-initialise, set struct_bytes =
+ * sizeof(arx_encoder_options), fill what differs from the defaults.  The schedules agree to rounding, not bit for bit. */
+/* GEMM main-loop schedules: gemm_schedule here, `variant` of arx_gemm_bf16 and of arx_gemm_epilogue; dispatch in csrc/encoder.hip */
+#define ARX_GEMM_DEFAULT    89     /* the persistent 4-phase kernel for K <= 1024, the per-tile 4-phase kernel above */
+#define ARX_GEMM_PER_TILE    8     /* 4-phase kernel, one 256 x 256 tile per block, wherever it applies */
+#define ARX_GEMM_PERSISTENT  9     /* 4-phase kernel, one block per CU walking the tiles, wherever it applies */
+#define ARX_GEMM_2STAGE     13     /* 2-stage loop, 64-bit offsets, any N % 8 == 0: what the 4-phase kernels fall back to */
+#define ARX_GEMM_SPLIT_K    70     /* split-K wave tiles for <= 256 rows; in a handle only through arx_encoder_set_low_latency */
+#define ARX_GEMM_TILE_128   71     /* 2-stage loop on 128 x 128 tiles: the medium-batch half of arx_encoder_set_low_latency */
+/* (a -DARX_DEV_VARIANTS build also holds the round-1 A/B schedules 1, 2, 3, 4, 15, 33, 34 of DESIGN.md's negative-result tables) */
+#define ARX_ATTN_TRANSPOSED  1     /* default: the transposing-read kernel, 4-wave blocks up to 128 tokens and 8-wave blocks above */
+#define ARX_ATTN_RING        2     /* -DARX_DEV_VARIANTS builds only: the streaming ring kernel, batches of 129..256 tokens */
+#define ARX_ATTN_RING16      4     /* -DARX_DEV_VARIANTS builds only: the 16-wave ring kernel, head dim 64, batches of 129..256 tokens */
+#define ARX_ATTN_STAGED      8     /* the first kernel: V transposed while it is staged into LDS, a running maximum in every tile */
+#define ARX_ENC_EXPLICIT_LAYERNORM 1   /* flags: the two-pass LayerNorm kernels between the GEMMs instead of the LayerNorm-fold epilogues */
+typedef struct {
+    int32_t struct_bytes;          /* sizeof(arx_encoder_options) */
+    int32_t gemm_schedule;         /* 0 = ARX_GEMM_DEFAULT; else ARX_GEMM_PER_TILE, _PERSISTENT, _2STAGE or _TILE_128 (or a dev schedule) */
+    int32_t attn_kernel;           /* 0 = ARX_ATTN_TRANSPOSED; else an ARX_ATTN_* id */
+    int32_t flags;                 /* ARX_ENC_* */
+} arx_encoder_options;
+/* arx_encoder_create with an explicit choice; opt == NULL = defaults (what arx_encoder_create passes).  A wrong struct_bytes, an id this
+ * build does not contain or an unknown flag is ARX_ERR_ARG naming the field and its value: nothing is allocated, *out is not written. */
+int32_t arx_encoder_create_opt(const arx_encoder_config* cfg, const arx_encoder_weights* w, int32_t max_tokens, int32_t max_seqs,
+                               const arx_encoder_options* opt, arx_encoder** out);
+
 /* Encode one batch of token sequences -> unit-norm sentence embeddings.
  *   ids   device int32 [n_seqs, seq_stride]: right-padded token ids (pad beyond lens[i] is ignored)
  *   lens  device int32 [n_seqs]: valid tokens per row (0 <= lens[i] <= max_len <= 512)
@@ -163,7 +192,7 @@ int32_t arx_pair_head_forward(const float* cls_rows, int64_t ld, int32_t n, int3
                               float* out_logits, int64_t out_stride, void* stream);
 
 /* Build flags of the loaded library: bit 0 = built with -DARX_DEV_VARIANTS (the A/B schedules of DESIGN.md's negative-result
- * tables are compiled in and selectable through ARX_GEMM_VARIANT / ARX_ATTN_VARIANT); 0 for the shipped build. */
+ * tables are compiled in and arx_encoder_options accepts their ids); 0 for the shipped build. */
 int32_t arx_build_info(void);
 
 /* ---- brute-force cosine top-k over an HBM-resident fp16 shard ------------------------------------
@@ -408,7 +437,7 @@ int32_t arx_bm25_scores(const int64_t* term_ptr, const uint32_t* post_row, const
 
 /* Raw linear layer of the path: C[M,N] (bf16) = epi(A[M,K] (bf16) x W[N,K]^T (bf16) + bias[N] (f32)),
  * mode 0 = bias, 1 = bias + erf-GELU, 2 = bias + resid[M,N] (bf16).  K % 64 == 0, N % 8 == 0.
- * `variant` selects the main-loop schedule (see csrc/encoder.hip); exposed for unit tests and tuning. */
+ * `variant` selects the main-loop schedule (ARX_GEMM_*); exposed for unit tests and tuning. */
 int32_t arx_gemm_bf16(const void* A, const void* W, const float* bias, const void* resid, void* C,
                       int32_t M, int32_t N, int32_t K, int32_t mode, int32_t variant, void* stream);
 
@@ -427,7 +456,7 @@ int32_t arx_gemm_bf16(const void* A, const void* W, const float* bias, const voi
 typedef struct {
     int32_t struct_bytes;               /* sizeof(arx_gemm_epilogue) */
     int32_t mode;                       /* 0..6 */
-    int32_t variant;                    /* 89, 8, 9, 13, 70, 71 (csrc/encoder.hip) */
+    int32_t variant;                    /* ARX_GEMM_*: 89, 8, 9, 13, 70, 71 */
     float eps;                          /* LayerNorm epsilon of the output statistics (modes 5/6) */
     const float* bias;                  /* [N]; modes 3/4: the folded c vector */
     const void* resid;                  /* bf16 [M, N]: modes 2/5/6 */

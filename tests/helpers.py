@@ -4,10 +4,20 @@ the product package."""
 import hashlib
 import json
 import numpy as np
+import pytest
 
+from arxiv_rag_amd import _lib
 from arxiv_rag_amd import config as C
 from arxiv_rag_amd.weights import seeded_state_dict
 from oracle import encoder_oracle as EO
+
+# the attention kernels under the labels the parametrised tests carry in their ids -> `HipEncoder(attn_kernel=...)`
+ATTN_KERNELS = {"0": _lib.ATTN_STAGED, "1": _lib.ATTN_TRANSPOSED, "2": _lib.ATTN_RING, "4": _lib.ATTN_RING16}
+
+
+def need_dev(hip, attn_kernel):
+    if attn_kernel in (_lib.ATTN_RING, _lib.ATTN_RING16) and not (hip.load().arx_build_info() & 1):
+        pytest.skip("streaming attention kernels are compiled only with ARX_HIPCC_EXTRA=-DARX_DEV_VARIANTS (csrc/build.sh)")
 
 
 def tiny_weights(g, cfg):

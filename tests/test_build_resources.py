@@ -4,12 +4,16 @@
 build.sh keeps that text in `arxiv_rag_amd/_build/<file>.resources.txt`.  A hot kernel that spills stores its registers to
 memory once per wave: the first shipped build of the round-2 attention kernel spilled 16 registers that only its fallback path
 needed — 0.4 GB of extra writes per launch, invisible to every parity test (found in the WRITE_SIZE counter pass)."""
+import ctypes
 import re
+import shutil
+import subprocess
 from pathlib import Path
 
 import pytest
 
-BUILD = Path(__file__).resolve().parents[1] / "arxiv_rag_amd" / "_build"
+ROOT = Path(__file__).resolve().parents[1]
+BUILD = ROOT / "arxiv_rag_amd" / "_build"
 PAT = re.compile(r"Function Name: (\S+).*?VGPRs: (\d+).*?AGPRs: (\d+).*?ScratchSize \[bytes/lane\]: (\d+).*?Occupancy \[waves/SIMD\]: (\d+)"
                  r".*?SGPRs Spill: (\d+).*?VGPRs Spill: (\d+)", re.S)
 
@@ -45,3 +49,32 @@ def test_hot_kernels_keep_their_occupancy():
     assert gemm and all(v["occupancy"] >= 2 for v in gemm.values()), gemm
     srch = {k: v for k, v in ks.items() if "search_groupmax_kernel" in k}
     assert srch and all(v["occupancy"] >= 2 for v in srch.values()), srch
+
+
+def test_shipped_library_does_not_import_getenv():
+    """include/arx.h: the library reads no environment variable (what a handle or a search runs is in its arguments).  A dev build
+    (-DARX_DEV_VARIANTS, marked by its arx_dev_attn_set export) keeps a few measurement switches and is not held to this."""
+    from arxiv_rag_amd import _lib
+    nm = shutil.which("nm")
+    if nm is None:
+        pytest.skip("no nm on this machine")
+    assert _lib.LIB_PATH.exists(), "libarx_hip.so not built (run __graft_entry__.build())"
+    if hasattr(ctypes.CDLL(str(_lib.LIB_PATH)), "arx_dev_attn_set"):
+        pytest.skip("a dev build is loaded")
+    undefined = subprocess.run([nm, "-D", "--undefined-only", str(_lib.LIB_PATH)], check=True, capture_output=True, text=True).stdout
+    assert len(undefined.split()) > 20, "nm listed no imports"
+    assert "getenv" not in undefined, [l for l in undefined.splitlines() if "getenv" in l]
+
+
+def test_encoder_options_struct_matches_the_header():
+    from arxiv_rag_amd import _lib
+    body = re.search(r"typedef struct \{([^}]*)\} arx_encoder_options;", (ROOT / "include" / "arx.h").read_text()).group(1)
+    fields = re.findall(r"^\s*(\w+)\s+(\w+);", body, re.M)
+    assert fields and all(t == "int32_t" for t, _ in fields), fields
+    assert [n for _, n in fields] == [n for n, _ in _lib.EncoderOptionsC._fields_]
+    assert all(t is ctypes.c_int32 for _, t in _lib.EncoderOptionsC._fields_)
+    assert ctypes.sizeof(_lib.EncoderOptionsC) == 4 * len(fields) == _lib.EncoderOptionsC().struct_bytes
+    hdr = (ROOT / "include" / "arx.h").read_text()
+    for name in ("GEMM_DEFAULT", "GEMM_PER_TILE", "GEMM_PERSISTENT", "GEMM_2STAGE", "GEMM_SPLIT_K", "GEMM_TILE_128", "ATTN_TRANSPOSED",
+                 "ATTN_RING", "ATTN_RING16", "ATTN_STAGED", "ENC_EXPLICIT_LAYERNORM"):
+        assert int(re.search(rf"#define ARX_{name}\s+(\d+)", hdr).group(1)) == getattr(_lib, name), name

@@ -14,7 +14,7 @@ import pytest
 
 from arxiv_rag_amd import config as C
 from arxiv_rag_amd.weights import adversarial_state_dict, seeded_state_dict
-from tests.helpers import (ATTN_FAULTS, U8, attention_budget, attention_fp64, embed_ln_fp64, layer_fp64, pool_fp64)
+from tests.helpers import (ATTN_FAULTS, ATTN_KERNELS, U8, attention_budget, attention_fp64, embed_ln_fp64, layer_fp64, need_dev, pool_fp64)
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -29,11 +29,6 @@ def hip():
     assert torch.cuda.is_available()
     _lib.load()
     return _lib
-
-
-def _need_dev(hip, attn):
-    if attn in ("2", "4") and not (hip.load().arx_build_info() & 1):
-        pytest.skip("streaming attention kernels are compiled only with ARX_HIPCC_EXTRA=-DARX_DEV_VARIANTS (csrc/build.sh)")
 
 
 # ---- 1. attention -------------------------------------------------------------------------------------------------------------------
@@ -59,7 +54,7 @@ def _attn_cells():
     return cells
 
 
-def _attn_encoder(hip, cfg, lens, seed):
+def _attn_encoder(hip, cfg, lens, seed, attn):
     """A one-layer handle of the head shape (the attention call reads only its bias table); MPNet bias entries ~ N(0, 1.5^2), the size
     of a trained model's, so that every bucket matters."""
     from arxiv_rag_amd.encoder import HipEncoder
@@ -68,7 +63,7 @@ def _attn_encoder(hip, cfg, lens, seed):
     if cfg.arch == C.ARCH_MPNET:
         rs = np.random.RandomState(seed + 1)
         sd["encoder.relative_attention_bias.weight"] = (rs.standard_normal((cfg.rel_buckets, cfg.heads)) * 1.5).astype(np.float32)
-    enc = HipEncoder(cfg1, sd, max_tokens=int(np.sum(lens)) + 256, max_seqs=len(lens))
+    enc = HipEncoder(cfg1, sd, max_tokens=int(np.sum(lens)) + 256, max_seqs=len(lens), attn_kernel=ATTN_KERNELS[attn])
     return enc, cfg1, sd
 
 
@@ -135,15 +130,14 @@ def _per_seq_head_ratio(a, ref, bud, lens, cfg):
 
 
 @pytest.mark.parametrize("head,lc,attn", _attn_cells())
-def test_attention_fp64_every_launch_shape(hip, head, lc, attn, monkeypatch):
+def test_attention_fp64_every_launch_shape(hip, head, lc, attn):
     """One cell of the dispatch matrix: worst error inside the budget, finite rows, guard rows untouched; each fault of ATTN_FAULTS
     (bias faults on bias heads) breaks the budget on at least one (sequence, head) of the same data."""
-    _need_dev(hip, attn)
-    monkeypatch.setenv("ARX_ATTN_VARIANT", attn)
+    need_dev(hip, ATTN_KERNELS[attn])
     cfg = HEADS[head]
     lens = np.array(LEN_CLASSES[lc], np.int32)
     seed = 1000 + 17 * list(HEADS).index(head) + list(LEN_CLASSES).index(lc)
-    enc, cfg1, sd = _attn_encoder(hip, cfg, lens, seed)
+    enc, cfg1, sd = _attn_encoder(hip, cfg, lens, seed, attn)
     q16 = torch.from_numpy(_spotlight_qkv(cfg, lens, seed)).to(torch.bfloat16).cuda()
     got, guard_ok = _run_attention(hip, enc, q16, lens, int(lens.max()))
     enc.close()
@@ -171,9 +165,9 @@ LAYER_K = 8
 # y2 and the LN1 output (each 2^-8 of an element of up to ~4 row rms, mostly averaged out by the next product); the folded schedule also
 # reads bf16(W gamma) and takes its residual LN2(y2) unrounded where the reference reads the rounded tap (one more 2^-8 per element).
 EMBED_K = 0.05            # tap 0: fp32 gather + LayerNorm, one bf16 rounding: 2^-8 |ref| + fp32 terms far below 0.05 2^-8 rms
-SCHEDULES = {             # env, low_latency, lengths
+SCHEDULES = {             # HipEncoder options, low_latency, lengths
     "fold": ({}, False, [512, 1, 300, 129, 33, 2, 64]),
-    "explicit": ({"ARX_LN_FOLD": "0"}, False, [512, 1, 300, 129, 33, 2, 64]),
+    "explicit": ({"ln_fold": False}, False, [512, 1, 300, 129, 33, 2, 64]),
     "ll-splitk": ({}, True, [1, 2, 100, 33, 64, 50]),                # <= 256 rows: split-K GEMMs, statistics in the GEMM epilogue
     "ll-128tiles": ({}, True, [512, 1, 300, 129, 33, 2, 64]),       # 257..8192 rows: 128 x 128 tiles
 }
@@ -221,16 +215,14 @@ def layer_errors(enc, sd, cfg, ids, lens, low_latency, faults=False):
 
 @pytest.mark.parametrize("sched", list(SCHEDULES))
 @pytest.mark.parametrize("name", list(LAYER_CFGS))
-def test_each_layer_vs_fp64(hip, name, sched, monkeypatch):
+def test_each_layer_vs_fp64(hip, name, sched):
     from arxiv_rag_amd.encoder import HipEncoder
-    env, ll, lens = SCHEDULES[sched]
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
+    opts, ll, lens = SCHEDULES[sched]
     cfg = LAYER_CFGS[name]
     sd = seeded_state_dict(cfg, seed=31 + list(LAYER_CFGS).index(name), std=0.04, bias_std=0.03, ln_jitter=0.1)
     lens = np.array(lens, np.int32)
     ids = _ids(cfg, lens, 5)
-    enc = HipEncoder(cfg, sd, max_tokens=int(lens.sum()) + 64, max_seqs=len(lens))
+    enc = HipEncoder(cfg, sd, max_tokens=int(lens.sum()) + 64, max_seqs=len(lens), **opts)
     worst, taps, fault_r = layer_errors(enc, sd, cfg, ids, lens, ll, faults=True)
     raw = enc.encode_tokens(ids, lens, normalize=False, low_latency=ll).double()
     unit = enc.encode_tokens(ids, lens, normalize=True, low_latency=ll).double()
@@ -257,7 +249,7 @@ def test_each_layer_vs_fp64(hip, name, sched, monkeypatch):
 
 
 @pytest.mark.parametrize("name", ["mpnet", "minilm"])
-def test_fused_row_statistics_vs_two_pass_layernorm(hip, name, monkeypatch):
+def test_fused_row_statistics_vs_two_pass_layernorm(hip, name):
     """Row-offset sweep on adversarial weights: every pre-LN row offset by 0, 4, 16, 64 (|mean| >> spread at the top).  The LN-fold schedule
     derives each row's mean / rstd from per-64-column partial sums (ln_finalize_kernel; the split-K path in its GEMM epilogue), the explicit
     schedule runs the two-pass layernorm_kernel; both read the same bf16 pre-LN stream, whose rounding costs them alike.  The fold
@@ -271,9 +263,8 @@ def test_fused_row_statistics_vs_two_pass_layernorm(hip, name, monkeypatch):
         sd = adversarial_state_dict(cfg, seed=77, row_offset=off)
         res = {}
         for fold in ("1", "0"):
-            monkeypatch.setenv("ARX_LN_FOLD", fold)
             for size, lens in runs.items():
-                enc = HipEncoder(cfg, sd, max_tokens=int(lens.sum()) + 64, max_seqs=len(lens))
+                enc = HipEncoder(cfg, sd, max_tokens=int(lens.sum()) + 64, max_seqs=len(lens), ln_fold=(fold == "1"))
                 ids = _ids(cfg, lens, 9)
                 res[fold, size] = max(layer_errors(enc, sd, cfg, ids, lens, low_latency=(fold == "1" and size == "small"))[0][1:])
                 enc.close()

@@ -11,7 +11,7 @@ from arxiv_rag_amd import config as C
 from arxiv_rag_amd.weights import seeded_state_dict
 from oracle import encoder_oracle as EO
 from oracle import search_oracle as SO
-from tests.helpers import attention_budget, attention_fp64, gemm_epilogue_budget, gemm_epilogue_fp64, tiny_weights
+from tests.helpers import ATTN_KERNELS, attention_budget, attention_fp64, gemm_epilogue_budget, gemm_epilogue_fp64, need_dev, tiny_weights
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -84,21 +84,20 @@ def test_full_shape_golden(hip, golden_dir, name, key):
 
 @pytest.mark.parametrize("fold", ["1", "0"])
 @pytest.mark.parametrize("name", ["all-mpnet-base-v2", "all-MiniLM-L6-v2", "BAAI/bge-large-en-v1.5"])
-def test_full_shape_adversarial_statistics(hip, golden_dir, name, fold, monkeypatch):
+def test_full_shape_adversarial_statistics(hip, golden_dir, name, fold):
     """The regime seeded N(0, sigma) weights never reach (VERDICT r1 / ADVICE): LayerNorm gamma log-uniform in [0.25, 4] with
     outlier channels at 10, beta with +-5 outliers, every pre-LN row offset by 4 (|mean| >> spread: the one-pass variance
     E[y^2] - mean^2 cancels, the bf16 pre-LN stream sits on a coarse grid), Student-t matrices.  Both the LN-fold schedule and
     the explicit-LayerNorm schedule must hold the north-star bar against the transformers outputs in full_shapes_adv.npz."""
     from arxiv_rag_amd.encoder import HipEncoder
     from arxiv_rag_amd.weights import adversarial_state_dict
-    monkeypatch.setenv("ARX_LN_FOLD", fold)
     g = np.load(golden_dir / "full_shapes_adv.npz")
     cfg = C.PRESETS[name]
     key = name.replace("/", "_") + ":adv"
     seed, off = g[key + ":wspec"]
     sd = adversarial_state_dict(cfg, seed=int(seed), row_offset=float(off))
     ids, lens, ref = g[key + ":ids"], g[key + ":lens"], g[key + ":emb"]
-    enc = HipEncoder(cfg, sd)
+    enc = HipEncoder(cfg, sd, ln_fold=(fold == "1"))
     emb = enc.encode_tokens(ids, lens).cpu().numpy()
     enc.close()
     c = _cos(emb, ref)
@@ -1042,24 +1041,18 @@ def test_int8_index_follows_writes_to_the_corpus(hip):
     assert i[2, 0].item() == 12345 and abs(s[2, 0].item() - 1) < 2e-3
 
 
-def _need_dev(hip, attn):
-    if attn in ("2", "4") and not (hip.load().arx_build_info() & 1):
-        pytest.skip("streaming attention kernels are compiled only with ARX_HIPCC_EXTRA=-DARX_DEV_VARIANTS (csrc/build.sh)")
-
-
 @pytest.mark.parametrize("attn", ["1", "2", "4"])
 @pytest.mark.parametrize("preset", ["all-mpnet-base-v2", "all-MiniLM-L6-v2"])
-def test_attention_block_forced_rescale(hip, preset, attn, monkeypatch):
-    _need_dev(hip, attn)
+def test_attention_block_forced_rescale(hip, preset, attn):
+    need_dev(hip, ATTN_KERNELS[attn])
     """The fused attention kernel alone on crafted q/k/v: (a) ordinary scores, (b) a late key whose score jumps far
     above everything before it (forces the lazy-reference rescale branch, cdna guide rule 26), (c) a first tile of very
     negative scores followed by large ones, (d) ragged lengths incl. 1 and a 33-token row (masked last tile).
     Reference: fp64 softmax attention on the same bf16-rounded inputs, MPNet bias from the oracle's Toeplitz table."""
     from arxiv_rag_amd.encoder import HipEncoder
-    monkeypatch.setenv("ARX_ATTN_VARIANT", attn)             # 1 = whole-(sequence, head) staging, 2 = streaming ring (persistent blocks)
     cfg = C.PRESETS[preset]
     sd = seeded_state_dict(cfg, seed=9, std=0.02)
-    enc = HipEncoder(cfg, sd, max_tokens=4096, max_seqs=16)
+    enc = HipEncoder(cfg, sd, max_tokens=4096, max_seqs=16, attn_kernel=ATTN_KERNELS[attn])
     H, nh = cfg.hidden, cfg.heads
     dh = H // nh
     lens = np.array([256, 200, 33, 1, 64, 255, 97], np.int32)
@@ -1161,14 +1154,14 @@ def test_attention_optimistic_pass_range_check(hip, preset):
 
 
 @pytest.mark.parametrize("preset", ["all-mpnet-base-v2", "all-MiniLM-L6-v2"])
-def test_attention_ring_stream_many_items(hip, preset, monkeypatch):
+def test_attention_ring_stream_many_items(hip, preset):
     """The streaming attention kernel with MORE (sequence, head) items than persistent blocks, so that every block's slot
     stream runs through item boundaries, the ring wraps many times and the counted waits see output stores between slot-loads:
     600 ragged sequences (lengths 0, 1, 31..33, 63..65, 127..129, 191..193, 255, 256 and random ones), 200 launches apart from
     one another in nothing but data.  Against the whole-item kernel (same tiles and MFMA order; another softmax reference) and, for
     every (sequence, head), against the fp64 budget."""
     from arxiv_rag_amd.encoder import HipEncoder
-    _need_dev(hip, "2")
+    need_dev(hip, ATTN_KERNELS["2"])
     cfg = C.PRESETS[preset]
     sd = seeded_state_dict(cfg, seed=9, std=0.02)
     H = cfg.hidden
@@ -1183,8 +1176,7 @@ def test_attention_ring_stream_many_items(hip, preset, monkeypatch):
     dlens = torch.from_numpy(lens).cuda()
     outs = {}
     for attn in ("1", "2", "4"):
-        monkeypatch.setenv("ARX_ATTN_VARIANT", attn)
-        enc = HipEncoder(cfg, sd, max_tokens=T + 256, max_seqs=len(lens))
+        enc = HipEncoder(cfg, sd, max_tokens=T + 256, max_seqs=len(lens), attn_kernel=ATTN_KERNELS[attn])
         res = []
         for rep in range(3):
             ctx = torch.full((T, H), float("nan"), dtype=torch.bfloat16, device="cuda")
@@ -1340,14 +1332,14 @@ def test_gemm_counted_wait_schedule_race_screen(hip, variant):
         torch.cuda.synchronize()
 
 
-@pytest.mark.parametrize("env", [{"ARX_LN_FOLD": "0"}, {"ARX_ATTN_VARIANT": "0"}, {"ARX_ATTN_VARIANT": "1"}, {"ARX_ATTN_VARIANT": "2"}, {"ARX_ATTN_VARIANT": "4"},
-                                 {"ARX_GEMM_VARIANT": "13"}, {"ARX_GEMM_VARIANT": "8"}, {"ARX_GEMM_VARIANT": "9"}])
-def test_alternative_schedules_agree(hip, golden_dir, env, monkeypatch):
+@pytest.mark.parametrize("opts", [{"ln_fold": False}] + [{"attn_kernel": ATTN_KERNELS[a]} for a in ("0", "1", "2", "4")]
+                         + [{"gemm_schedule": g} for g in (13, 8, 9)], ids=[f"env{i}" for i in range(8)])
+def test_alternative_schedules_agree(hip, golden_dir, opts):
     """The schedules shipped beside the default (explicit LayerNorm kernels, first attention kernel, 2-stage / per-tile /
     persistent GEMM everywhere) against the same
     golden vectors as the default path, and against the default path itself."""
     from arxiv_rag_amd.encoder import HipEncoder
-    _need_dev(hip, env.get("ARX_ATTN_VARIANT", "1"))
+    need_dev(hip, opts.get("attn_kernel"))
     g = np.load(golden_dir / "full_shapes.npz")
     key, cfg = "all-mpnet-base-v2:w05", C.MPNET_BASE
     seed, std, bstd, jit = g[key + ":wspec"]
@@ -1356,9 +1348,7 @@ def test_alternative_schedules_agree(hip, golden_dir, env, monkeypatch):
     base = HipEncoder(cfg, sd)
     e0 = base.encode_tokens(ids, lens).cpu().numpy()
     base.close()
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
-    alt = HipEncoder(cfg, sd)
+    alt = HipEncoder(cfg, sd, **opts)
     e1 = alt.encode_tokens(ids, lens).cpu().numpy()
     alt.close()
     assert _cos(e1, ref).min() > 1 - 1e-3

@@ -207,18 +207,14 @@ EMPTY_BATCHES = {"first-middle-last": [0, 5, 64, 0, 17, 1, 0], "all-but-one": [0
 @pytest.mark.parametrize("ll", [False, True], ids=["default", "low-latency"])
 @pytest.mark.parametrize("fold", ["1", "0"], ids=["fold", "explicit"])
 @pytest.mark.parametrize("name", list(POOL_CFGS))
-def test_empty_sequences_and_the_fp16_row(hip, name, fold, ll, monkeypatch):
+def test_empty_sequences_and_the_fp16_row(hip, name, fold, ll):
     """Zero-length sequences give exact zeros under every schedule and pooling mode (the LN-fold pool must not return beta), normalised or
     not; the fp16 row a shard receives is the f32 row rounded, of norm <= 1 + 2^-9; and (default schedules) the other rows are the bits
     of the same sequences encoded without the empty ones."""
     from arxiv_rag_amd.encoder import HipEncoder
-    if fold == "0":
-        monkeypatch.setenv("ARX_LN_FOLD", "0")
-    else:
-        monkeypatch.delenv("ARX_LN_FOLD", raising=False)
     cfg = POOL_CFGS[name]
     sd = seeded_state_dict(cfg, seed=11, std=0.05, bias_std=0.05, ln_jitter=0.1)
-    enc = HipEncoder(cfg, sd)
+    enc = HipEncoder(cfg, sd, ln_fold=(fold == "1"))
     worst = 0.0
     for bname, lens in EMPTY_BATCHES.items():
         lens = np.array(lens, np.int32)
@@ -237,10 +233,9 @@ def test_empty_sequences_and_the_fp16_row(hip, name, fold, ll, monkeypatch):
 
 
 @pytest.mark.parametrize("name", list(WIDE_CFGS))
-def test_full_width_fp16_rows_keep_the_default_row_norm(hip, name, monkeypatch):
+def test_full_width_fp16_rows_keep_the_default_row_norm(hip, name):
     """the search's default max_row_norm = 0 stands for rows of norm <= 1 + 2^-9: full-width rows as the encoder writes them"""
     from arxiv_rag_amd.encoder import HipEncoder
-    monkeypatch.delenv("ARX_LN_FOLD", raising=False)
     cfg = WIDE_CFGS[name]
     sd = seeded_state_dict(cfg, seed=41, std=0.04, bias_std=0.03, ln_jitter=0.1)
     lens = np.array([256, 1, 33, 100, 0, 7], np.int32)
@@ -252,11 +247,10 @@ def test_full_width_fp16_rows_keep_the_default_row_norm(hip, name, monkeypatch):
 
 
 @pytest.mark.parametrize("n_seqs", [255, 256, 257, 1025, 3001])
-def test_packing_offsets_beyond_256_sequences(hip, n_seqs, monkeypatch):
+def test_packing_offsets_beyond_256_sequences(hip, n_seqs):
     """scan_lens_kernel is one block of 256 threads, each summing ceil(n / 256) lengths: every row of a batch of n sequences (lengths
     0, 1, 2, 3, 7) is the bits of the same sequence encoded inside its own 64-sequence slice; empty rows are zero."""
     from arxiv_rag_amd.encoder import HipEncoder
-    monkeypatch.delenv("ARX_LN_FOLD", raising=False)
     cfg = C.TINY_MPNET
     sd = seeded_state_dict(cfg, seed=12, std=0.05, bias_std=0.05, ln_jitter=0.1)
     rs = np.random.RandomState(n_seqs)
@@ -275,11 +269,10 @@ def test_packing_offsets_beyond_256_sequences(hip, n_seqs, monkeypatch):
 
 
 @pytest.mark.parametrize("name", ["tiny-mpnet-mean", "tiny-bert-cls"])
-def test_out_of_range_ids_are_clamped(hip, name, monkeypatch):
+def test_out_of_range_ids_are_clamped(hip, name):
     """embed_ln_kernel clamps ids to [0, vocab): -5, vocab_size and 2^31 - 1 inside the valid length give the bits of 0, vocab_size - 1 and
     vocab_size - 1, in the layer-0 tap and in the output"""
     from arxiv_rag_amd.encoder import HipEncoder
-    monkeypatch.delenv("ARX_LN_FOLD", raising=False)
     cfg = POOL_CFGS[name]
     sd = seeded_state_dict(cfg, seed=13, std=0.05, bias_std=0.05, ln_jitter=0.1)
     lens = np.array([10, 64, 3, 1], np.int32)

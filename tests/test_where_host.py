@@ -201,7 +201,7 @@ def test_library_exports_the_filtered_search_and_header_and_bindings_agree():
     for name in new:
         assert hasattr(lib, name), name
     bound = _lib.load()
-    assert bound.arx_version() == 111
+    assert bound.arx_version() == 112
     # host-only argument checks (no GPU involved): shapes the filtered search refuses
     f = bound.arx_topk_filtered_workspace_bytes
     assert f(1000, 64, 768, 10) > 0 and f(1000, 64, 768, 33) == -1 and f(1000, 64, 100, 10) == -1 and f(0, 1, 64, 1) == -1

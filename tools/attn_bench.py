@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""Same-process A/B of the attention kernels (ARX_ATTN_VARIANT is read when a handle is created): the fused attention block
+"""Same-process A/B of the attention kernels (one handle per `HipEncoder(attn_kernel=...)` id, include/arx.h ARX_ATTN_*): the fused attention block
 alone on a bench-shaped batch (B x S tokens, mpnet-base heads), interleaved rounds, hipEvent times on the launch stream.
-  python tools/attn_bench.py [variants ...]      e.g.  1 2"""
+  python tools/attn_bench.py [ids ...]      e.g.  1 2   (2 and 4 need a dev build)"""
 import os, sys, json
 import numpy as np
 import torch
@@ -24,8 +24,7 @@ lens_h[0] = S
 lens = torch.from_numpy(lens_h).cuda()
 encs = {}
 for v in variants:
-    os.environ["ARX_ATTN_VARIANT"] = v
-    encs[v] = HipEncoder(cfg, sd, max_tokens=B * S, max_seqs=B)
+    encs[v] = HipEncoder(cfg, sd, max_tokens=B * S, max_seqs=B, attn_kernel=int(v))
 ctx = {v: torch.empty((B * S, H), dtype=torch.bfloat16, device="cuda") for v in variants}
 st = torch.cuda.current_stream().cuda_stream
 def run(v):

@@ -1,0 +1,546 @@
+// arx_topk_search_grouped: the exact top-P PAPERS of an fp16 shard with the m best chunks of each (C ABI in include/arx.h; field
+// collapsing by paper).  group_of[r] (device int32, non-decreasing, non-negative, not necessarily dense) names the paper of row r: a paper
+// is a contiguous run of rows.  An optional bitmap in the convention of arx_topk_search_filtered says which rows a query may see.
+//   score(q, r)    exact_row_score (search_tail.h): the bits arx_topk_search and arx_topk_search_filtered give the pair
+//   paper score    the maximum of score(q, r) over the paper's visible rows; a paper without a visible row does not exist for the query
+//   answer         the P best papers by (paper score desc, row of the best chunk asc), and of each the m best visible chunks by (score desc,
+//                  row asc); (-inf, -1) / -1 padding
+// Pass A is masked_topk.h's masked_groupmax_kernel with a bitmap policy (allow == NULL: an all-ones bitmap in the workspace), unchanged.
+// The tail (grouped_tail_kernel, one block per query) is new.  With R = max_run_rows an upper bound on the rows of any run, a run touches
+// at most S = floor((R + 62) / 64) + 1 of the 64-row groups; K = P S.
+// Why the tail is exact: let t be the K-th largest group maximum of the query.  The K groups at or above t each hold a visible row whose
+// pass-A score is >= t; a paper touches at most S of them, so at least P distinct papers have a visible row whose pass-A score is >= t,
+// hence whose exact score is >= t - tau (pass A and exact_row_score differ by at most tau = tau_scale |q|, the masked tail's own bound).
+// So the P-th best paper score is >= t - tau, and every paper of the true top-P - ties at the P-th score included - has its best row at
+// an exact score >= t - tau, a pass-A score >= t - 2 tau: that row lies in a group with gmax >= t - 2 tau.  Candidates = every non-empty
+// group with gmax >= t - 2 tau; their visible rows are rescored exactly and folded by group_of (maximum per paper, ties to the lower row).
+// A paper outside the true top-P may be folded from a part of its rows only: its partial maximum is <= its score, so it cannot displace a
+// true one.  With fewer than K non-empty groups t = -inf and every non-empty group is a candidate.  The K-th largest of up to n_rows / 64
+// values is a block-wide radix select over order_key, one bit per step (the wave selection of k <= 32 does not stretch to K <= 512).
+// The chunks: for each selected paper every visible row of its WHOLE run is scored (its other chunks need not lie in candidate groups);
+// the run's ends come from two binary searches in group_of.
+// The exhaustive path (a query whose candidate list overflows cand_cap; the whole call when K > 512; path 2): every visible row scored by
+// the same function in parts cut at run boundaries - no paper straddles two parts, so the per-part top-P paper lists merge as plain
+// lists - then the same chunk step.  Same bits.
+// No float atomics; integer atomics only where the result does not depend on their order (a counter, a maximum, the slots of a list that
+// is read as a set); plain vector stores.  A query's output depends on the query, the mask, group_of and the corpus alone.
+#include <math.h>
+
+#include "arx_common.h"
+#include "gemm.h"
+#include "gemm8.h"
+#include "search_consts.h"
+
+namespace {      // the headers also define non-template kernels: internal linkage keeps this object's copies apart from search.hip's
+#include "search_pass_a.h"
+#include "search_tail.h"
+#include "masked_topk.h"
+#include "bitmap_rows.h"
+
+#define GRP_KSEL_MAX 512             // largest K = P S the scan path selects for; beyond: the exhaustive path
+#define GRP_CHUNKS_MAX 8             // largest m
+
+// ---- pass A's mask policy: the bitmap of the call, as filter.hip's ------------------------------------------------------------------------
+struct GroupedBitmap {
+    const uint64_t* allow;
+    struct LaneRows {
+        bool on[GROUP_ROWS / 16][4];
+        __device__ __forceinline__ const LaneRows& of_query(int, int) const { return *this; }
+        __device__ __forceinline__ bool operator()(int j, int r) const { return on[j][r]; }
+    };
+    struct Tile {
+        bool empty; uint64_t mine;
+        __device__ __forceinline__ LaneRows lane_rows(int64_t, int lane) const {
+            const uint32_t lrow = (uint32_t)(lane >> 4) * 4u;
+            LaneRows s;
+#pragma unroll
+            for (int j = 0; j < GROUP_ROWS / 16; ++j)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) s.on[j][r] = (mine >> ((uint32_t)(j * 16 + r) + lrow)) & 1ull;
+            return s;
+        }
+    };
+    template <int BM>
+    __device__ __forceinline__ Tile tile(int64_t n0, int wn, int, int, int64_t n_rows) const {
+        const int64_t n_groups = (n_rows + GROUP_ROWS - 1) / GROUP_ROWS;
+        uint64_t any = 0, mine = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int64_t gj = (n0 >> 6) + j;
+            const uint64_t w = gj < n_groups ? (allow[gj] & valid_bits(n_rows, gj)) : 0ull;
+            any |= w;
+            mine = j == wn ? w : mine;
+        }
+        return {any == 0ull, mine};
+    }
+};
+
+__global__ __launch_bounds__(256) void grouped_ones_kernel(uint64_t* __restrict__ words, int64_t n_words) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n_words) words[i] = ~0ull;
+}
+
+// ---- runs of group_of ---------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int64_t run_lower(const int32_t* __restrict__ g, int64_t n, int32_t v) {      // first row with g[row] >= v
+    int64_t lo = 0, hi = n;
+    while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (g[mid] < v) lo = mid + 1; else hi = mid; }
+    return lo;
+}
+__device__ __forceinline__ int64_t run_upper(const int32_t* __restrict__ g, int64_t from, int64_t n, int32_t v) {      // first row >= from with g[row] > v
+    int64_t lo = from, hi = n;
+    while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (g[mid] <= v) lo = mid + 1; else hi = mid; }
+    return lo;
+}
+// the bits of word g that name rows of [a, b)
+__device__ __forceinline__ uint64_t range_bits(int64_t a, int64_t b, int64_t g) {
+    const int64_t base = g * GROUP_ROWS;
+    const int64_t l = a > base ? a - base : 0, h = b - base < GROUP_ROWS ? b - base : GROUP_ROWS;
+    if (h <= l) return 0ull;
+    return (h >= GROUP_ROWS ? ~0ull : ((1ull << h) - 1ull)) & ~((1ull << l) - 1ull);
+}
+
+// out[0] = the longest run (all ones = -1 as int64: group_of decreases somewhere or holds a negative value), out[1] = the number of runs;
+// both start at zero.  A maximum and a counter: the order of the atomics does not matter.  The thread of a run's first row finds the run's
+// end by binary search (on unsorted input the search still ends, and the answer is -1 whatever it finds).
+__global__ __launch_bounds__(256) void group_runs_kernel(const int32_t* __restrict__ g, int64_t n, unsigned long long* __restrict__ out) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const int32_t v = g[i];
+        const bool first = i == 0;
+        const int32_t prev = first ? v : g[i - 1];
+        if (v < 0 || prev > v) atomicMax(&out[0], ~0ull);
+        if (first || prev != v) {
+            atomicMax(&out[0], (unsigned long long)(run_upper(g, i + 1, n, v) - i));
+            atomicAdd(&out[1], 1ull);
+        }
+    }
+}
+
+// ---- the fold by paper ----------------------------------------------------------------------------------------------------------------------
+// Every lane holds R candidates (score, row, paper) in registers, row < 0 = empty.  P rounds: the best remaining candidate by (score desc,
+// row asc) is the next paper's best chunk, and every candidate of that paper retires.  Entry r of (out_s, out_i, out_g) = the r-th paper,
+// (-inf, -1, -1) when fewer than P papers are held.
+template <int R>
+__device__ __forceinline__ void wave_top_papers(float (&s)[R], int64_t (&id)[R], int32_t (&pg)[R], int P, int lane, float* out_s,
+                                                int64_t* out_i, int32_t* out_g) {
+    for (int r = 0; r < P; ++r) {
+        float bs = -INFINITY; int64_t bi = INT64_MAX; int bj = -1; int32_t bp = -1;
+#pragma unroll
+        for (int j = 0; j < R; ++j)
+            if (id[j] >= 0 && (bj < 0 || s[j] > bs || (s[j] == bs && id[j] < bi))) { bs = s[j]; bi = id[j]; bj = j; bp = pg[j]; }
+        float ws = bj >= 0 ? bs : -INFINITY; int64_t wi = bj >= 0 ? bi : INT64_MAX;
+        wave_argbest(ws, wi);
+        const bool found = wi != INT64_MAX;                     // wave-uniform
+        const unsigned long long own = __ballot(found && bj >= 0 && bi == wi);      // rows are distinct: one lane
+        const int32_t wp = found ? __shfl(bp, own ? __ffsll((long long)own) - 1 : 0) : -1;
+#pragma unroll
+        for (int j = 0; j < R; ++j)
+            if (found && pg[j] == wp) id[j] = -1;
+        if (lane == 0) { out_s[r] = found ? ws : -INFINITY; out_i[r] = found ? wi : -1; out_g[r] = wp; }
+    }
+}
+// one wave: fold 64 new (score, row, paper) into the wave's running list of the P best papers, kept as entry `lane` of (cs, ci, cp) for
+// lanes < P.  Skipped when no new score reaches the P-th kept one (ties included: they may win on the row number): the list holds P
+// distinct papers that all rank before such a row.
+__device__ __forceinline__ void wave_merge_papers(float& cs, int64_t& ci, int32_t& cp, float ns, int64_t ni, int32_t np, int P, int lane,
+                                                  float* w_s, int64_t* w_i, int32_t* w_g) {
+    const float pth = __shfl(cs, P - 1);
+    if (!__any(ni >= 0 && ns >= pth)) return;                  // wave-uniform
+    float s2[2] = {cs, ns};
+    int64_t i2[2] = {ci, ni};
+    int32_t g2[2] = {cp, np};
+    wave_top_papers<2>(s2, i2, g2, P, lane, w_s, w_i, w_g);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    cs = lane < P ? w_s[lane] : -INFINITY;
+    ci = lane < P ? w_i[lane] : -1;
+    cp = lane < P ? w_g[lane] : -1;
+}
+// the block's NW per-wave paper lists (entries of lanes < P) -> the final P, by wave 0
+template <int NW>
+__device__ __forceinline__ void block_merge_papers(const float (*w_s)[KMAX], const int64_t (*w_i)[KMAX], const int32_t (*w_g)[KMAX], int P,
+                                                   int lane, float* fin_s, int64_t* fin_i, int32_t* fin_g) {
+    constexpr int R4 = (NW * KMAX + 63) / 64;
+    float s[R4]; int64_t id[R4]; int32_t pg[R4];
+#pragma unroll
+    for (int j = 0; j < R4; ++j) {
+        const int i = j * 64 + lane;
+        s[j] = i < NW * P ? w_s[i / P][i % P] : -INFINITY;
+        id[j] = i < NW * P ? w_i[i / P][i % P] : -1;
+        pg[j] = i < NW * P ? w_g[i / P][i % P] : -1;
+    }
+    wave_top_papers<R4>(s, id, pg, P, lane, fin_s, fin_i, fin_g);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+}
+
+// one wave: the exact scores of the rows of group g that `word` names -> sc[0..64) (entries of other rows are not written)
+__device__ __forceinline__ void score_word_rows(const f16_t* __restrict__ C, int64_t g, uint64_t word, const f16_t* qs, int D, int lane,
+                                                float* sc) {
+    const int nch = D >> 3, l8 = lane & 7, rsub = lane >> 3;
+    for (int r8 = 0; r8 < GROUP_ROWS; r8 += 8) {
+        if (((word >> r8) & 0xffull) == 0ull) continue;          // wave-uniform
+        const int rr = r8 + rsub;
+        const bool ok = (word >> rr) & 1ull;
+        const float a = exact_row_score(C + (g * GROUP_ROWS + rr) * D, qs, nch, l8, ok);
+        if (l8 == 0) sc[rr] = a;
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+}
+
+// ---- the chunk step: wave w of NW takes papers w, w + NW, ... of the query's P selected ones (fin_i: the row of the best chunk, < 0 = no
+// such paper; fin_g: its group_of value): the run's ends, every visible row of the run scored, the m best kept ---------------------------
+__device__ __forceinline__ void paper_chunks(int w, int NW, int lane, const int64_t* fin_i, const int32_t* fin_g, int P, int m,
+                                             const uint64_t* __restrict__ allow, const int32_t* __restrict__ group_of,
+                                             const f16_t* __restrict__ C, int64_t n_rows, int D, const f16_t* qs, float* sc, float* w_s,
+                                             int64_t* w_i, int64_t idx_base, float* __restrict__ out_s, int64_t* __restrict__ out_i,
+                                             int32_t* __restrict__ out_g) {
+    for (int p = w; p < P; p += NW) {
+        const int64_t best = fin_i[p];
+        float cs = -INFINITY; int64_t ci = -1;
+        if (best >= 0) {                                        // wave-uniform
+            const int32_t gv = fin_g[p];
+            const int64_t lo = run_lower(group_of, best, gv), hi = run_upper(group_of, best + 1, n_rows, gv);
+            for (int64_t g = lo >> 6; g <= ((hi - 1) >> 6); ++g) {
+                const uint64_t word = allow[g] & valid_bits(n_rows, g) & range_bits(lo, hi, g);
+                if (word == 0ull) continue;
+                score_word_rows(C, g, word, qs, D, lane, sc);
+                const bool mine = (word >> lane) & 1ull;
+                wave_merge64(cs, ci, mine ? sc[lane] : -INFINITY, mine ? g * GROUP_ROWS + lane : -1, m, lane, w_s, w_i);
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            }
+        }
+        if (lane < m) {
+            out_s[(int64_t)p * m + lane] = cs;
+            out_i[(int64_t)p * m + lane] = ci >= 0 ? ci + idx_base : -1;
+        }
+        if (lane == 0) out_g[p] = best >= 0 ? fin_g[p] : -1;
+    }
+}
+
+// ---- the tail: one block per query ----------------------------------------------------------------------------------------------------------
+// ksel = K of the header comment.  stats: [0] queries sent to the exhaustive path, [1] candidate groups rescored, [2] (low word) "some
+// query of this call overflowed".  out_* point at this batch's first query.
+__global__ __launch_bounds__(FILT_TAIL_NT) void grouped_tail_kernel(const float* __restrict__ gmax, int64_t ldg, int64_t n_groups,
+                                                                     const uint64_t* __restrict__ allow, const int32_t* __restrict__ group_of,
+                                                                     const f16_t* __restrict__ Q, const f16_t* __restrict__ C, int64_t n_rows,
+                                                                     int D, int P, int m, int ksel, float* __restrict__ out_s,
+                                                                     int64_t* __restrict__ out_i, int32_t* __restrict__ out_g, int64_t idx_base,
+                                                                     float tau_scale, int cand_cap, int32_t* __restrict__ redo,
+                                                                     unsigned long long* __restrict__ stats) {
+    constexpr int NT = FILT_TAIL_NT, NW = NT / 64;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    __shared__ float w_s[NW][KMAX];
+    __shared__ int64_t w_i[NW][KMAX];
+    __shared__ int32_t w_g[NW][KMAX];
+    __shared__ float fin_s[KMAX];
+    __shared__ int64_t fin_i[KMAX];
+    __shared__ int32_t fin_g[KMAX];
+    __shared__ int red[NW];
+    __shared__ int n_c;
+    __shared__ float sh_qn;
+    const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    f16_t* qs = reinterpret_cast<f16_t*>(smem);                                                  // [D] query row
+    float* sc_all = reinterpret_cast<float*>(smem + (((size_t)D * 2 + 15) & ~(size_t)15));      // [NW][64] row scores of the group a wave is at
+    int32_t* list = reinterpret_cast<int32_t*>(sc_all + NW * GROUP_ROWS);                        // [cand_cap] candidate groups
+    for (int i = tid; i < (D >> 3); i += NT)
+        reinterpret_cast<u32x4*>(qs)[i] = reinterpret_cast<const u32x4*>(Q + (int64_t)q * D)[i];
+    if (tid == 0) n_c = 0;
+    // this query's column of group maxima, as ordered keys: the first FILT_REG_GROUPS per thread stay in registers
+    const float* col = gmax + q;
+    uint32_t kv[FILT_REG_GROUPS];
+#pragma unroll
+    for (int j = 0; j < FILT_REG_GROUPS; ++j) {
+        const int64_t g = (int64_t)j * NT + tid;
+        kv[j] = g < n_groups ? order_key(col[g * ldg]) : 0u;
+    }
+    __syncthreads();
+    if (w == 0) {
+        float qq = 0.f;
+        for (int i = lane; i < D; i += 64) { const float v = (float)qs[i]; qq = fmaf(v, v, qq); }
+        qq = wave_sum(qq);
+        if (lane == 0) sh_qn = sqrtf(qq);
+    }
+    // T = the largest key that at least ksel groups reach = the ksel-th largest group maximum: a radix select, one bit per step
+    uint32_t T = 0u;
+    for (int bit = 31; bit >= 0; --bit) {
+        const uint32_t cand = T | (1u << bit);
+        int c = 0;
+#pragma unroll
+        for (int j = 0; j < FILT_REG_GROUPS; ++j) c += __popcll(__ballot(kv[j] >= cand));
+        for (int64_t g0 = (int64_t)FILT_REG_GROUPS * NT + w * 64; g0 < n_groups; g0 += NT) {          // (wave-uniform bounds)
+            const int64_t g = g0 + lane;
+            c += __popcll(__ballot(g < n_groups && order_key(col[(g < n_groups ? g : 0) * ldg]) >= cand));
+        }
+        if (lane == 0) red[w] = c;
+        __syncthreads();
+        int tot = 0;
+#pragma unroll
+        for (int ww = 0; ww < NW; ++ww) tot += red[ww];
+        __syncthreads();
+        T = tot >= ksel ? cand : T;
+    }
+    const float thr = key_value(T) - 2.0f * tau_scale * sh_qn;      // -inf when fewer than ksel groups hold a visible row
+    auto consider = [&](int64_t g, float v) {
+        if (v >= thr && v > -INFINITY) {
+            const int sl = atomicAdd(&n_c, 1);
+            if (sl < cand_cap) list[sl] = (int32_t)g;
+        }
+    };
+#pragma unroll
+    for (int j = 0; j < FILT_REG_GROUPS; ++j) {
+        const int64_t g = (int64_t)j * NT + tid;
+        if (g < n_groups) consider(g, key_value(kv[j]));
+    }
+    for (int64_t g = (int64_t)FILT_REG_GROUPS * NT + tid; g < n_groups; g += NT) consider(g, col[g * ldg]);
+    __syncthreads();
+    const int nc = n_c;
+    if (nc > cand_cap) {                                       // block-uniform: never an answer from a truncated list
+        if (tid == 0) {
+            redo[q] = 1;
+            atomicAdd(&stats[0], 1ull);
+            reinterpret_cast<int*>(stats + 2)[0] = 1;
+        }
+        return;
+    }
+    if (tid == 0) { redo[q] = 0; if (nc) atomicAdd(&stats[1], (unsigned long long)nc); }
+    // the visible rows of the candidate groups, exactly, folded by paper: a group per wave at a time
+    float* sc = sc_all + w * GROUP_ROWS;
+    float cs = -INFINITY; int64_t ci = -1; int32_t cp = -1;
+    for (int p = w; p < nc; p += NW) {
+        const int64_t gsel = list[p];
+        const uint64_t word = allow[gsel] & valid_bits(n_rows, gsel);
+        score_word_rows(C, gsel, word, qs, D, lane, sc);
+        const bool mine = (word >> lane) & 1ull;
+        const int64_t row = gsel * GROUP_ROWS + lane;
+        wave_merge_papers(cs, ci, cp, mine ? sc[lane] : -INFINITY, mine ? row : -1, mine ? group_of[row] : -1, P, lane, w_s[w], w_i[w], w_g[w]);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    }
+    if (lane < P) { w_s[w][lane] = cs; w_i[w][lane] = ci; w_g[w][lane] = cp; }
+    __syncthreads();
+    if (w == 0) block_merge_papers<NW>(w_s, w_i, w_g, P, lane, fin_s, fin_i, fin_g);
+    __syncthreads();
+    paper_chunks(w, NW, lane, fin_i, fin_g, P, m, allow, group_of, C, n_rows, D, qs, sc, w_s[w], w_i[w], idx_base,
+                 out_s + (int64_t)q * P * m, out_i + (int64_t)q * P * m, out_g + (int64_t)q * P);
+}
+
+// ---- exhaustive path: block (part p, query q) folds the visible rows of part p by paper -> part_s / part_i [parts][nq][P] (local rows).
+// Part p starts at the first row of the run that row p * per lies in: no paper straddles two parts.  only_if / gate as masked_topk.h's.
+__device__ __forceinline__ int64_t part_cut(const int32_t* __restrict__ group_of, int64_t n_rows, int64_t per, int p) {
+    const int64_t s = (int64_t)p * per;
+    if (p == 0) return 0;
+    if (s >= n_rows) return n_rows;
+    return run_lower(group_of, s, group_of[s]);
+}
+__global__ __launch_bounds__(256) void grouped_exhaustive_kernel(const uint64_t* __restrict__ allow, const int32_t* __restrict__ group_of,
+                                                                  const f16_t* __restrict__ Q, const f16_t* __restrict__ C, int64_t n_rows,
+                                                                  int D, int nq, int P, float* __restrict__ part_s,
+                                                                  int64_t* __restrict__ part_i, const int32_t* __restrict__ only_if,
+                                                                  const int* __restrict__ gate) {
+    if (gate && !*gate) return;
+    const int q = blockIdx.y, p = blockIdx.x, parts = gridDim.x;
+    if (only_if && !only_if[q]) return;
+    constexpr int NW = 4;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    __shared__ float w_s[NW][KMAX];
+    __shared__ int64_t w_i[NW][KMAX];
+    __shared__ int32_t w_g[NW][KMAX];
+    __shared__ float fin_s[KMAX];
+    __shared__ int64_t fin_i[KMAX];
+    __shared__ int32_t fin_g[KMAX];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    f16_t* qs = reinterpret_cast<f16_t*>(smem);
+    float* sc = reinterpret_cast<float*>(smem + (((size_t)D * 2 + 15) & ~(size_t)15)) + w * GROUP_ROWS;
+    for (int i = tid; i < (D >> 3); i += 256)
+        reinterpret_cast<u32x4*>(qs)[i] = reinterpret_cast<const u32x4*>(Q + (int64_t)q * D)[i];
+    __syncthreads();
+    const int64_t per = ((n_rows + parts - 1) / parts + 63) / 64 * 64;
+    const int64_t a = part_cut(group_of, n_rows, per, p), b = p + 1 < parts ? part_cut(group_of, n_rows, per, p + 1) : n_rows;
+    float cs = -INFINITY; int64_t ci = -1; int32_t cp = -1;
+    if (a < b)
+        for (int64_t g = (a >> 6) + w; g <= ((b - 1) >> 6); g += NW) {
+            const uint64_t word = allow[g] & valid_bits(n_rows, g) & range_bits(a, b, g);
+            if (word == 0ull) continue;                        // wave-uniform
+            score_word_rows(C, g, word, qs, D, lane, sc);
+            const bool mine = (word >> lane) & 1ull;
+            const int64_t row = g * GROUP_ROWS + lane;
+            wave_merge_papers(cs, ci, cp, mine ? sc[lane] : -INFINITY, mine ? row : -1, mine ? group_of[row] : -1, P, lane, w_s[w], w_i[w], w_g[w]);
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        }
+    if (lane < P) { w_s[w][lane] = cs; w_i[w][lane] = ci; w_g[w][lane] = cp; }
+    __syncthreads();
+    if (w == 0) {
+        block_merge_papers<NW>(w_s, w_i, w_g, P, lane, fin_s, fin_i, fin_g);
+        if (lane < P) {
+            const int64_t o = ((int64_t)p * nq + q) * P + lane;
+            part_s[o] = fin_s[lane];
+            part_i[o] = fin_i[lane];
+        }
+    }
+}
+
+// the chunk step of the queries the exhaustive path answered: sel_i [nq][P] = the merged lists' rows (best chunk of each selected paper)
+__global__ __launch_bounds__(FILT_TAIL_NT) void grouped_chunks_kernel(const int64_t* __restrict__ sel_i, const uint64_t* __restrict__ allow,
+                                                                       const int32_t* __restrict__ group_of, const f16_t* __restrict__ Q,
+                                                                       const f16_t* __restrict__ C, int64_t n_rows, int D, int P, int m,
+                                                                       float* __restrict__ out_s, int64_t* __restrict__ out_i,
+                                                                       int32_t* __restrict__ out_g, int64_t idx_base,
+                                                                       const int32_t* __restrict__ only_if, const int* __restrict__ gate) {
+    if (gate && !*gate) return;
+    const int q = blockIdx.x;
+    if (only_if && !only_if[q]) return;
+    constexpr int NT = FILT_TAIL_NT, NW = NT / 64;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    __shared__ float w_s[NW][KMAX];
+    __shared__ int64_t w_i[NW][KMAX];
+    __shared__ int64_t fin_i[KMAX];
+    __shared__ int32_t fin_g[KMAX];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    f16_t* qs = reinterpret_cast<f16_t*>(smem);
+    float* sc = reinterpret_cast<float*>(smem + (((size_t)D * 2 + 15) & ~(size_t)15)) + w * GROUP_ROWS;
+    for (int i = tid; i < (D >> 3); i += NT)
+        reinterpret_cast<u32x4*>(qs)[i] = reinterpret_cast<const u32x4*>(Q + (int64_t)q * D)[i];
+    if (tid < P) {
+        const int64_t row = sel_i[(int64_t)q * P + tid];
+        fin_i[tid] = row;
+        fin_g[tid] = row >= 0 ? group_of[row] : -1;
+    }
+    __syncthreads();
+    paper_chunks(w, NW, lane, fin_i, fin_g, P, m, allow, group_of, C, n_rows, D, qs, sc, w_s[w], w_i[w], idx_base,
+                 out_s + (int64_t)q * P * m, out_i + (int64_t)q * P * m, out_g + (int64_t)q * P);
+}
+
+// ---- host ---------------------------------------------------------------------------------------------------------------------------------
+struct GroupedWs { int64_t stats, gmax, ones, redo, sel_s, sel_i, part_s, part_i, total, ldg, n_groups; int parts; };
+GroupedWs grouped_layout(int64_t n_rows, int nq, int P) {
+    GroupedWs w;
+    const int qb = nq < QBATCH_MAX ? nq : QBATCH_MAX;
+    w.ldg = round_up64(qb, 64);
+    w.n_groups = (n_rows + GROUP_ROWS - 1) / GROUP_ROWS;
+    const int64_t want = (n_rows + 255) / 256;
+    w.parts = (int)(want < FILT_PARTS_MAX ? want : FILT_PARTS_MAX);
+    int64_t o = 0;
+    auto take = [&](int64_t b) { int64_t r = o; o += round_up64(b, 256); return r; };
+    w.stats = take(64);                                         // at the allocation's start: masked_stats reads it
+    w.gmax = take(w.n_groups * w.ldg * 4);
+    w.ones = take(w.n_groups * 8);
+    w.redo = take((int64_t)qb * 4);
+    w.sel_s = take((int64_t)qb * P * 4);
+    w.sel_i = take((int64_t)qb * P * 8);
+    w.part_s = take((int64_t)w.parts * qb * P * 4);
+    w.part_i = take((int64_t)w.parts * qb * P * 8);
+    w.total = o;
+    return w;
+}
+}      // namespace
+
+extern "C" int64_t arx_topk_grouped_workspace_bytes(int64_t n_rows, int32_t n_queries, int32_t dim, int32_t n_groups, int32_t chunks_per_group) {
+    if (n_rows <= 0 || n_rows >= (1ll << 36) || n_queries <= 0 || dim <= 0 || dim % 64 != 0 || dim > 8192 || n_groups <= 0 || n_groups > KMAX ||
+        chunks_per_group <= 0 || chunks_per_group > GRP_CHUNKS_MAX)
+        return -1;
+    return grouped_layout(n_rows, n_queries, n_groups).total;
+}
+
+extern "C" int32_t arx_group_runs_info(const int32_t* group_of, int64_t n_rows, int64_t* out, void* stream) {
+    ARX_REQUIRE(group_of && out, "null pointer argument");
+    ARX_REQUIRE(n_rows >= 0, "n_rows=%lld must not be negative", (long long)n_rows);
+    hipStream_t st = (hipStream_t)stream;
+    ARX_HIP_CHECK(hipMemsetAsync(out, 0, 16, st));
+    if (n_rows == 0) return ARX_OK;
+    const int64_t blocks = (n_rows + 255) / 256;
+    group_runs_kernel<<<(int)(blocks < 4096 ? blocks : 4096), 256, 0, st>>>(group_of, n_rows, (unsigned long long*)out);
+    ARX_HIP_CHECK(hipGetLastError());
+    return ARX_OK;
+}
+
+extern "C" int32_t arx_topk_search_grouped_tuned(const void* corpus, int64_t n_rows, const int32_t* group_of, int64_t max_run_rows,
+                                                 const uint64_t* allow, int64_t n_allowed, const void* queries, int32_t n_queries, int32_t dim,
+                                                 int32_t n_groups, int32_t chunks_per_group, float* out_scores, int64_t* out_ids,
+                                                 int32_t* out_groups, int64_t idx_base, float max_row_norm, void* ws, int64_t ws_bytes,
+                                                 int32_t path, int32_t cand_cap, void* stream) {
+    const int P = n_groups, m = chunks_per_group;
+    ARX_REQUIRE(corpus && group_of && queries && out_scores && out_ids && out_groups && ws, "null pointer argument");
+    ARX_REQUIRE(n_rows > 0 && n_queries > 0, "empty corpus or query set");
+    ARX_REQUIRE(n_rows < (1ll << 36), "n_rows=%lld: group numbers are 32-bit", (long long)n_rows);
+    ARX_REQUIRE(dim > 0 && dim % 64 == 0 && dim <= 8192, "dim=%d must be a multiple of 64", dim);
+    ARX_REQUIRE(P >= 1 && P <= KMAX, "n_groups=%d out of range 1..%d", P, KMAX);
+    ARX_REQUIRE(m >= 1 && m <= GRP_CHUNKS_MAX, "chunks_per_group=%d out of range 1..%d", m, GRP_CHUNKS_MAX);
+    ARX_REQUIRE(max_run_rows >= 1, "max_run_rows=%lld must be at least 1", (long long)max_run_rows);
+    ARX_REQUIRE(n_allowed >= -1 && n_allowed <= n_rows, "n_allowed=%lld", (long long)n_allowed);
+    ARX_REQUIRE(path >= 0 && path <= 2, "path=%d: 0 (library's choice), 1 (scan) or 2 (exhaustive)", path);
+    ARX_REQUIRE(cand_cap >= 0 && cand_cap <= FILT_CAND_CAP_MAX, "cand_cap=%d out of range 0..%d", cand_cap, FILT_CAND_CAP_MAX);
+    ARX_REQUIRE(max_row_norm >= 0.0f && max_row_norm < INFINITY, "max_row_norm=%g: must be a finite bound (0 = unit rows)", (double)max_row_norm);
+    const GroupedWs L = grouped_layout(n_rows, n_queries, P);
+    ARX_REQUIRE(ws_bytes >= L.total, "workspace too small: %lld < %lld (arx_topk_grouped_workspace_bytes)", (long long)ws_bytes, (long long)L.total);
+    hipStream_t st = (hipStream_t)stream;
+    // S = the 64-row groups a run of at most max_run_rows rows can touch, K = P S (the clamp only keeps the arithmetic in range)
+    const int64_t R = max_run_rows < (1ll << 40) ? max_run_rows : (1ll << 40);
+    const int64_t ksel = (int64_t)P * ((R + 62) / 64 + 1);
+    if (path == 0) path = 1;
+    if (ksel > GRP_KSEL_MAX) path = 2;                          // the whole call
+    if (cand_cap == 0) cand_cap = FILT_CAND_CAP_DEFAULT;
+    const f16_t* C = (const f16_t*)corpus;
+    char* wsb = (char*)ws;
+    unsigned long long* stats = (unsigned long long*)(wsb + L.stats);
+    const int* gate = path == 1 ? (const int*)(stats + 2) : nullptr;      // scan: the exhaustive kernels run only after an overflow
+    float* gmax = (float*)(wsb + L.gmax);
+    int32_t* redo = (int32_t*)(wsb + L.redo);
+    float* sel_s = (float*)(wsb + L.sel_s);
+    int64_t* sel_i = (int64_t*)(wsb + L.sel_i);
+    float* part_s = (float*)(wsb + L.part_s);
+    int64_t* part_i = (int64_t*)(wsb + L.part_i);
+    const float tau_scale = (0.3125f * (float)dim + 4.0f) * 5.9604645e-8f * (max_row_norm > 0.0f ? max_row_norm : 1.0f + 1.0f / 512.0f);
+    ARX_HIP_CHECK(hipMemsetAsync(stats, 0, 64, st));
+    if (!allow) {                                               // every row: an all-ones bitmap of the call's own
+        uint64_t* ones = (uint64_t*)(wsb + L.ones);
+        grouped_ones_kernel<<<cdiv(L.n_groups, 256), 256, 0, st>>>(ones, L.n_groups);
+        ARX_HIP_CHECK(hipGetLastError());
+        allow = ones;
+    }
+    const GroupedBitmap mask{allow};
+    const size_t smem_q = ((size_t)dim * 2 + 15) & ~(size_t)15;
+    for (int q0 = 0; q0 < n_queries; q0 += QBATCH_MAX) {
+        const int nq = (n_queries - q0) < QBATCH_MAX ? (n_queries - q0) : QBATCH_MAX;
+        const f16_t* Q = (const f16_t*)queries + (int64_t)q0 * dim;
+        float* os = out_scores + (int64_t)q0 * P * m;
+        int64_t* oi = out_ids + (int64_t)q0 * P * m;
+        int32_t* og = out_groups + (int64_t)q0 * P;
+        if (path == 1) {
+            {
+                ProfScope ps(ARX_K_SEARCH_GROUPMAX, st);
+                const int rc = nq <= 64 ? launch_masked_groupmax<64>(Q, nq, C, n_rows, dim, mask, gmax, L.ldg, st)
+                             : nq <= 128 ? launch_masked_groupmax<128>(Q, nq, C, n_rows, dim, mask, gmax, L.ldg, st)
+                                         : launch_masked_groupmax<256>(Q, nq, C, n_rows, dim, mask, gmax, L.ldg, st);
+                if (rc != ARX_OK) return rc;
+            }
+            ProfScope ps(ARX_K_SEARCH_RESCORE, st);
+            const size_t smem = smem_q + (size_t)(FILT_TAIL_NT / 64) * GROUP_ROWS * 4 + (size_t)cand_cap * 4;
+            if (smem > 48 * 1024) ARX_HIP_CHECK(arx_func_smem((const void*)grouped_tail_kernel, (int)smem));
+            grouped_tail_kernel<<<nq, FILT_TAIL_NT, smem, st>>>(gmax, L.ldg, L.n_groups, allow, group_of, Q, C, n_rows, dim, P, m, (int)ksel, os, oi,
+                                                                og, idx_base, tau_scale, cand_cap, redo, stats);
+            ARX_HIP_CHECK(hipGetLastError());
+        }
+        // exhaustive over the visible rows: every query (path 2) or the queries the tail flagged (the kernels return at once if none)
+        const int32_t* only_if = path == 1 ? redo : nullptr;
+        const size_t smem_x = smem_q + 4 * GROUP_ROWS * 4;
+        if (smem_x > 48 * 1024) ARX_HIP_CHECK(arx_func_smem((const void*)grouped_exhaustive_kernel, (int)smem_x));
+        grouped_exhaustive_kernel<<<dim3(L.parts, nq), 256, smem_x, st>>>(allow, group_of, Q, C, n_rows, dim, nq, P, part_s, part_i, only_if, gate);
+        ARX_HIP_CHECK(hipGetLastError());
+        filter_merge_kernel<<<cdiv(nq, 4), 256, 0, st>>>(part_s, part_i, L.parts, nq, P, sel_s, sel_i, only_if, gate);
+        ARX_HIP_CHECK(hipGetLastError());
+        const size_t smem_c = smem_q + (size_t)(FILT_TAIL_NT / 64) * GROUP_ROWS * 4;
+        if (smem_c > 48 * 1024) ARX_HIP_CHECK(arx_func_smem((const void*)grouped_chunks_kernel, (int)smem_c));
+        grouped_chunks_kernel<<<nq, FILT_TAIL_NT, smem_c, st>>>(sel_i, allow, group_of, Q, C, n_rows, dim, P, m, os, oi, og, idx_base, only_if, gate);
+        ARX_HIP_CHECK(hipGetLastError());
+    }
+    return ARX_OK;
+}
+
+extern "C" int32_t arx_topk_search_grouped(const void* corpus, int64_t n_rows, const int32_t* group_of, int64_t max_run_rows,
+                                           const uint64_t* allow, int64_t n_allowed, const void* queries, int32_t n_queries, int32_t dim,
+                                           int32_t n_groups, int32_t chunks_per_group, float* out_scores, int64_t* out_ids,
+                                           int32_t* out_groups, int64_t idx_base, float max_row_norm, void* ws, int64_t ws_bytes, void* stream) {
+    return arx_topk_search_grouped_tuned(corpus, n_rows, group_of, max_run_rows, allow, n_allowed, queries, n_queries, dim, n_groups,
+                                         chunks_per_group, out_scores, out_ids, out_groups, idx_base, max_row_norm, ws, ws_bytes, 0, 0, stream);
+}
+
+extern "C" int32_t arx_topk_grouped_stats(const void* ws, int64_t* overflowed_queries, int64_t* candidate_groups, void* stream) {
+    return masked_stats(ws, overflowed_queries, candidate_groups, stream);
+}

@@ -661,7 +661,7 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
                    output_dir: str = "./embeddings_saved", chunk_base: int = 0, reranker=None, rerank_top_k: int = 32,
                    hybrid_alpha: Optional[float] = None, where=None,
                    where_document: Optional[Dict] = None, *, mmr_lambda: Optional[float] = None, mmr_fetch_k: int = 32,
-                   keep_mask: Optional[np.ndarray] = None) -> List[Dict]:
+                   keep_mask: Optional[np.ndarray] = None, group_by_paper: bool = False, chunks_per_paper: int = 1) -> List[Dict]:
     """Brute-force cosine top-k (config.yaml:63-64 `top_k: 10`) over the rank's fp16 rows in HBM; with
     torchrun each rank holds the contiguous row shard it encoded and the partial top-k lists are
     all-gathered over RCCL and merged.  `shard` is the `ShardSink` the encode step filled: rows [lo, hi) are already where they
@@ -693,7 +693,16 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
     carry `mmr_score` beside the cosine `score`.  Not together with `reranker` or `hybrid_alpha` (out of scope).
     `keep_mask` (bool, one entry per row of the shard; None = every row): rows to search at all — `--dedup-threshold` passes the rows that
     are not near-duplicates (`find_shard_duplicates`).  It is and-ed into the bitmap of `where` / `where_document`, or is the bitmap
-    when neither is given.  Not together with `hybrid_alpha`, for the reason `where` is not."""
+    when neither is given.  Not together with `hybrid_alpha`, for the reason `where` is not.
+    `group_by_paper` (False = nothing changes): grouped results (INTEGRATION.md "Grouped results").  `top_k` (<= 32) then counts PAPERS:
+    consecutive chunks with equal `metadata["paper_id"]` are one paper (`grouping.runs_from_keys`), and the search returns the exact
+    best papers by their best chunk, each with its `chunks_per_paper` (<= 8) best chunks (`ShardIndex.search_grouped`), filters applied
+    as without it.  The hits come paper by paper, best paper first, and carry `paper_rank` and `paper_id`.  Not together with
+    `reranker`, `hybrid_alpha`, `mmr_lambda`, a per-query `where` list or more than one rank (a paper may straddle ranks)."""
+    if group_by_paper:
+        from .grouping import check_grouped_query
+        check_grouped_query(top_k, chunks_per_paper, grouped=True, reranker=reranker, hybrid_alpha=hybrid_alpha, mmr_lambda=mmr_lambda,
+                            per_query_filters=isinstance(where, (list, tuple)), world=int(os.environ.get("WORLD_SIZE", "1")))
     if keep_mask is not None and hybrid_alpha is not None:
         raise ValueError("keep_mask cannot be combined with hybrid_alpha: the BM25 keyword search has no row filter")
     if mmr_lambda is not None:
@@ -753,8 +762,21 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
             allow = (allow & docs.fold(doc_tree)).contiguous()
             n_allowed = docs.count(allow)
         pre = None
+    if group_by_paper:
+        from .grouping import runs_from_keys
+        if len(chunks) != shard.rows.shape[0]:
+            raise ValueError(f"group_by_paper: {len(chunks)} chunks for the shard's {shard.rows.shape[0]} rows")
+        group_of, paper_ids = runs_from_keys([(c.get("metadata") or {}).get("paper_id") for c in chunks], base=chunk_base)
+        pre = None                                           # a grouped search runs on the fp16 rows
     index = ShardIndex(shard.rows, idx_base=shard.lo, prefilter=pre, adaptive=True)
-    if where_each is not None:
+    grp = None
+    if group_by_paper:
+        if world > 1:
+            raise ValueError("group_by_paper needs a single GPU rank: a paper may straddle two ranks, and a cross-rank fold is out of scope")
+        index.set_groups(group_of)
+        s, i, grp = index.search_grouped(qd, top_k, chunks_per_paper, allow=allow, n_allowed=n_allowed)
+        s, i, grp = s.reshape(len(queries), -1), i.reshape(len(queries), -1), grp.cpu().numpy()
+    elif where_each is not None:
         from .filter_sets import distinct_filters
         from .index import search_filtered_grouped
         from .where import compile_where, evaluate, pack_bitmap
@@ -824,6 +846,14 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
                              "chunk_id": names.get(j, f"chunk_{j}"), **hybrid_fields(qi, p)})
             results.append({"query": text, "results": hits})
             continue
+        if grp is not None:                                   # paper by paper; the padding of short papers is skipped
+            for r in range(i.shape[1]):
+                j, p = int(i[qi, r]), r // chunks_per_paper
+                if j >= 0:
+                    hits.append({"rank": len(hits) + 1, "paper_rank": p + 1, "paper_id": paper_ids[int(grp[qi, p])], "score": float(s[qi, r]),
+                                 "index": j, "chunk_id": names.get(j, f"chunk_{j}")})
+            results.append({"query": text, "results": hits})
+            continue
         for r in range(top_k):
             j = int(i[qi, r])
             if j < 0:
@@ -834,7 +864,7 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
     if rank == 0:
         with open(Path(output_dir) / "search_results.json", "w", encoding="utf-8") as fh:
             json.dump(results, fh, indent=2, ensure_ascii=False)
-        print(f"✅ Saved top-{top_k} results for {len(queries)} queries to {Path(output_dir) / 'search_results.json'}")
+        print(f"✅ Saved top-{top_k} {'papers' if group_by_paper else 'results'} for {len(queries)} queries to {Path(output_dir) / 'search_results.json'}")
     return results
 
 
@@ -888,6 +918,12 @@ def build_parser() -> argparse.ArgumentParser:
                    help="Near-duplicate detection: a chunk whose embedding scores at least this cosine, in (0, 1], against ANY earlier "
                         "chunk is listed in duplicates.json with its nearest earlier chunk, and a --queries search skips it (default: "
                         "off; one GPU rank only; not with --hybrid-alpha and --queries)")
+    p.add_argument("--group-by-paper", action="store_true",
+                   help="Grouped results for --queries: --top-k counts PAPERS (consecutive chunks with equal paper_id), the exact best "
+                        "by their best chunk, each with its --chunks-per-paper best chunks (one GPU rank only; not with --rerank-model, "
+                        "--hybrid-alpha, --mmr-lambda or --where-file)")
+    p.add_argument("--chunks-per-paper", type=int, default=1,
+                   help="Chunks returned for each paper of --group-by-paper (default: 1; at most 8)")
     return p
 
 
@@ -966,6 +1002,34 @@ def find_shard_duplicates(shard: "ShardSink", chunks: List[Dict], threshold: flo
                   ensure_ascii=False)
     print(f"✅ Near-duplicates at cosine >= {threshold}: {len(entries):,} of {n:,} chunks listed in {Path(output_dir) / 'duplicates.json'}")
     return dup_of < 0
+
+
+GROUP_MAX_PAPERS, GROUP_MAX_CHUNKS = 32, 8      # arx_topk_search_grouped: papers per query (the search's k limit), chunks per paper
+
+
+def check_group_args(args) -> Optional[str]:
+    """-> an error message for an unusable --group-by-paper / --chunks-per-paper, else None."""
+    if not args.group_by_paper:
+        if args.chunks_per_paper != 1:
+            return f"--chunks-per-paper {args.chunks_per_paper} needs --group-by-paper: it counts the chunks returned for each paper"
+        return None
+    if not args.queries:
+        return "--group-by-paper needs --queries: it groups the results of the search step"
+    if args.rerank_model:
+        return "--group-by-paper cannot be combined with --rerank-model: the cross-encoder ranks chunks, not papers"
+    if args.hybrid_alpha is not None:
+        return "--group-by-paper cannot be combined with --hybrid-alpha: the BM25 keyword search has no groups"
+    if args.mmr_lambda is not None:
+        return "--group-by-paper cannot be combined with --mmr-lambda: MMR re-orders the cosine search's chunk candidates only"
+    if getattr(args, "where_file", None) is not None:
+        return "--group-by-paper cannot be combined with --where-file: the grouped search takes one filter per call"
+    if not (1 <= args.top_k <= GROUP_MAX_PAPERS):
+        return f"--top-k {args.top_k}: the grouped search returns between 1 and {GROUP_MAX_PAPERS} papers per query"
+    if not (1 <= args.chunks_per_paper <= GROUP_MAX_CHUNKS):
+        return f"--chunks-per-paper {args.chunks_per_paper}: the grouped search returns between 1 and {GROUP_MAX_CHUNKS} chunks per paper"
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        return "--group-by-paper needs a single GPU rank: a paper may straddle two ranks, and a cross-rank fold is out of scope"
+    return None
 
 
 def check_where_args(args) -> Optional[str]:
@@ -1056,7 +1120,7 @@ def main(argv: Optional[Sequence[str]] = None, model_factory: Optional[Callable]
     global _model, _model_name
     args = build_parser().parse_args(argv)
     err = (check_rerank_args(args) or check_hybrid_args(args) or check_where_args(args) or check_where_file_args(args) or check_where_document_args(args)
-           or check_mmr_args(args) or check_dedup_args(args))
+           or check_mmr_args(args) or check_dedup_args(args) or check_group_args(args))
     if err:
         print(f"Error: {err}")
         return 2
@@ -1152,7 +1216,8 @@ def main(argv: Optional[Sequence[str]] = None, model_factory: Optional[Callable]
                 search_queries(_model, chunks, sink, qs, top_k=args.top_k, chunk_base=span[0] if span else 0,
                                reranker=reranker, rerank_top_k=args.rerank_top_k, hybrid_alpha=args.hybrid_alpha,
                                where=args.where_filters if args.where_filters is not None else args.where_filter, where_document=args.where_document_filter,
-                               mmr_lambda=args.mmr_lambda, mmr_fetch_k=args.mmr_fetch_k, keep_mask=keep_mask)
+                               mmr_lambda=args.mmr_lambda, mmr_fetch_k=args.mmr_fetch_k, keep_mask=keep_mask,
+                               **({"group_by_paper": True, "chunks_per_paper": args.chunks_per_paper} if args.group_by_paper else {}))
         store_time = 0.0
         if rank == 0 and not args.skip_chroma:
             try:

@@ -336,6 +336,78 @@ class ShardIndex:
         limit = torch.arange(row_lo, row_hi, dtype=torch.int64, device=self.corpus.device)
         return self.search_prefix(self.corpus[row_lo:row_hi], limit, k, **debug)
 
+    # ---- grouped search: the top papers with their best chunks --------------------------------------------------------------
+    def set_groups(self, group_of) -> "ShardIndex":
+        """`group_of`: int32 [n_rows] (a tensor, on the host or the device, or anything numpy converts), the group (the paper) of every
+        local row: non-decreasing, non-negative, not necessarily dense, so that a group is a contiguous run of rows.  Uploads it and
+        measures its runs once (`arx_group_runs_info`): ValueError when it decreases somewhere or holds a negative value; the longest
+        run is cached as `max_run_rows`, the number of runs as `n_runs`.  `search_grouped` needs it."""
+        g = group_of if torch.is_tensor(group_of) else torch.as_tensor(group_of)
+        if g.dim() != 1 or g.shape[0] != self.n_rows:
+            raise ValueError(f"group_of has shape {tuple(g.shape)}, the shard's {self.n_rows} rows need ({self.n_rows},)")
+        if g.dtype.is_floating_point or g.dtype == torch.bool:
+            raise ValueError(f"group_of must hold integers, got {g.dtype}")
+        if g.numel() and g.dtype != torch.int32 and (int(g.max()) > 2 ** 31 - 1 or int(g.min()) < -2 ** 31):
+            raise ValueError("group_of holds a value outside int32")
+        g = g.to(device=self.corpus.device, dtype=torch.int32).contiguous()
+        info = torch.zeros(2, dtype=torch.int64, device=self.corpus.device)
+        if self.n_rows:
+            _lib.check(self.lib.arx_group_runs_info(g.data_ptr(), self.n_rows, info.data_ptr(), torch.cuda.current_stream().cuda_stream),
+                       "arx_group_runs_info")
+        longest, runs = (int(v) for v in info.tolist())
+        if longest < 0:
+            raise ValueError("group_of must be non-decreasing and non-negative: a group is a contiguous run of rows")
+        self.group_of, self.max_run_rows, self.n_runs = g, max(longest, 1), runs
+        return self
+
+    def search_grouped(self, queries_f16: torch.Tensor, n_groups: int, chunks_per_group: int = 1, allow: Optional[torch.Tensor] = None,
+                       n_allowed: Optional[int] = None, path: int = 0, cand_cap: int = 0, ws: Optional[torch.Tensor] = None,
+                       max_run_rows: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """queries fp16 [Q, D] (device) -> (scores f32 [Q, P, m], ids int64 [Q, P, m], groups int32 [Q, P]) on the device, P = `n_groups`
+        <= 32, m = `chunks_per_group` <= 8 (`arx_topk_search_grouped`; `set_groups` first).  A group's score is the best score of its
+        visible rows; the P best groups come by (score desc, row of the best chunk asc), each with its m best visible chunks by (score
+        desc, row asc); ids = local row + idx_base, `groups` = the `group_of` value; (-inf, -1) and -1 pad.  A (query, row) score has the
+        bits `search` gives it.  `allow` / `n_allowed` as for `search(allow=...)`, None = every row.  Runs on the fp16 rows.  Test hooks:
+        `path` (1 = scan, 2 = exhaustive), `cand_cap`, and `max_run_rows` (default: the measured one; a smaller one voids exactness);
+        `grouped_stats` reads the counters."""
+        if getattr(self, "group_of", None) is None:
+            raise ValueError("search_grouped needs set_groups(group_of) first")
+        q, P, m = queries_f16, int(n_groups), int(chunks_per_group)
+        assert q.is_cuda and q.dtype == torch.float16 and q.dim() == 2 and q.shape[1] == self.dim and q.is_contiguous()
+        nq = q.shape[0]
+        if allow is not None:
+            n_words = (self.n_rows + 63) // 64
+            assert allow.is_cuda and allow.dtype in (torch.int64, torch.uint64) and allow.dim() == 1 and allow.is_contiguous()
+            assert allow.shape[0] == n_words, f"allow has {allow.shape[0]} words, the shard's {self.n_rows} rows need {n_words}"
+        need = self.lib.arx_topk_grouped_workspace_bytes(max(self.n_rows, 1), max(nq, 1), self.dim, P, m)
+        if need < 0:
+            raise _lib.ArxError(f"unsupported grouped search shape n_rows={self.n_rows} nq={nq} dim={self.dim} n_groups={P} "
+                                f"chunks_per_group={m}")
+        scores = torch.full((nq, P, m), float("-inf"), dtype=torch.float32, device=q.device)
+        ids = torch.full((nq, P, m), -1, dtype=torch.int64, device=q.device)
+        groups = torch.full((nq, P), -1, dtype=torch.int32, device=q.device)
+        if nq == 0 or self.n_rows == 0:
+            return scores, ids, groups
+        if ws is None:
+            ws = self._ws_masked.get("grouped")
+            if ws is None or ws.numel() < need:
+                ws = self._ws_masked["grouped"] = torch.empty(need, dtype=torch.uint8, device=self.corpus.device)
+        norm = max(self.max_row_norm(), 1.0 + 1.0 / 512.0)       # never below the encoder's unit-row bound (as `_options`)
+        rc = self.lib.arx_topk_search_grouped_tuned(self.corpus.data_ptr(), self.n_rows, self.group_of.data_ptr(),
+                                                    int(self.max_run_rows if max_run_rows is None else max_run_rows),
+                                                    None if allow is None else allow.data_ptr(), -1 if n_allowed is None else int(n_allowed),
+                                                    q.data_ptr(), nq, self.dim, P, m, scores.data_ptr(), ids.data_ptr(), groups.data_ptr(),
+                                                    self.idx_base, norm, ws.data_ptr(), ws.numel(), int(path), int(cand_cap),
+                                                    torch.cuda.current_stream().cuda_stream)
+        _lib.check(rc, "arx_topk_search_grouped")
+        self._last_ws_masked["grouped"] = ws
+        return scores, ids, groups
+
+    def grouped_stats(self, ws: Optional[torch.Tensor] = None) -> Tuple[int, int]:
+        """(queries whose candidate list overflowed and were answered by the exhaustive path, candidate groups rescored) of the LAST
+        `search_grouped` on this index (or on `ws`).  Synchronises on the current stream."""
+        return self._masked_stats("grouped", self.lib.arx_topk_grouped_stats, ws)
+
     def _i8_nq_limit(self) -> int:
         """The largest query batch the int8 pass takes under this index's policy (`i8_max_queries`; None = the library default, 1 024)."""
         if self.i8_max_queries is None:

@@ -75,7 +75,7 @@ class HipCollection:
 
     def __init__(self, embeddings: np.ndarray, metadata: Sequence[Dict], device="cuda:0", encoder=None,
                  rank: int = 0, world: int = 1, chunk_rows: int = 1 << 18, keyword: bool = False, tokenizer=None,
-                 documents: bool = False, dedup_threshold: Optional[float] = None):
+                 documents: bool = False, dedup_threshold: Optional[float] = None, group_key: Optional[str] = None):
         """`keyword=True`: also build a BM25 `keyword.KeywordIndex` over this shard's `metadata[i]["text"]` (word pieces of `tokenizer`,
         default the encoder's; corpus statistics summed over all ranks when `world > 1`), which `query(hybrid_alpha=...)` needs.
         `documents=True`: also keep this shard's texts as a UTF-8 blob in HBM (`where_document.DocumentStore`), which
@@ -85,7 +85,10 @@ class HipCollection:
         it (the search's dot product = the cosine on unit rows).  `self.duplicates` lists them
         (`{index, chunk_id, duplicate_of_index, duplicate_of, score}`, the nearest earlier row each) and every `query` skips them: the
         keep-bitmap is and-ed into the filter of `where` / `where_document`, or is the filter when neither is given.  With `world > 1` it
-        raises ValueError: a rank sees only its own rows, and a cross-rank join is out of scope."""
+        raises ValueError: a rank sees only its own rows, and a cross-rank join is out of scope.
+        `group_key` (a metadata key, e.g. "paper_id"; None = off, nothing changes): consecutive rows of this rank with equal
+        `metadata[i][group_key]` are one group (`grouping.runs_from_keys`; a key that reappears after its run ended is a ValueError naming
+        the key and the two rows), uploaded once (`ShardIndex.set_groups`); `query(group_by=True)` needs it."""
         import torch
         from .index import ShardIndex, shard_bounds
         if dedup_threshold is not None:
@@ -96,6 +99,11 @@ class HipCollection:
         n, d = embeddings.shape
         lo, hi = shard_bounds(n, world, rank)
         self.n_total, self.dim, self.lo, self.hi = n, d, lo, hi
+        self.world = world
+        self.group_key, self.group_keys = group_key, None       # the key of every run of this rank's rows, by `group_of` value
+        if group_key is not None:
+            from .grouping import runs_from_keys
+            group_of, self.group_keys = runs_from_keys([metadata[r].get(group_key) for r in range(lo, hi)], base=lo)
         self.metadata = metadata
         self._where_columns: Dict = {}                          # `query(where=...)`: one numpy column per referenced metadata key
         self.encoder = encoder
@@ -106,6 +114,8 @@ class HipCollection:
         dim = int(shard.shape[1]) if shard.dim() == 2 else 0
         self.index = ShardIndex(shard, idx_base=lo, prefilter="int8" if (dim % 128 == 0 and 0 < dim <= 1024 and shard.shape[0] > 0) else None,
                                 adaptive=True)
+        if group_key is not None and hi > lo:
+            self.index.set_groups(group_of)
         self.keyword = None
         if keyword:
             from .keyword import KeywordIndex
@@ -186,7 +196,7 @@ class HipCollection:
 
     def query(self, query_embeddings=None, query_texts: Optional[Sequence[str]] = None, n_results: int = 10, reranker=None,
               n_candidates: int = 32, hybrid_alpha: Optional[float] = None, where=None, where_document=None,
-              mmr_lambda: Optional[float] = None) -> Dict:
+              mmr_lambda: Optional[float] = None, group_by=None, chunks_per_group: int = 1) -> Dict:
         """`reranker` (a `rerank.HipCrossEncoder`; needs `query_texts`): the search fetches `n_candidates` (<= 32) rows per query,
         the cross-encoder scores (query, document) for each, and the best `n_results` come back in reranked order with an added
         `rerank_scores` list per query (`scores` / `distances` stay the cosine ones).
@@ -221,9 +231,20 @@ class HipCollection:
         is built once and the whole batch is answered by `ShardIndex.search_filtered_many`, which reads the shard once, not once per
         filter; a batch with more than 64 distinct pairs is cut into calls of at most 64.  Query by query the result is what the same
         call with that query alone and its own dict returns; `reranker` and `mmr_lambda` compose as before, `hybrid_alpha` raises the
-        same ValueError.  A single dict (or None) means what it meant."""
+        same ValueError.  A single dict (or None) means what it meant.
+        `group_by=True` (needs a collection built with `group_key`; absent / None / False = nothing changes): grouped results
+        (INTEGRATION.md "Grouped results").  `n_results` (<= 32) then counts PAPERS: the exact best papers by their best visible chunk,
+        each with its `chunks_per_group` (<= 8) best visible chunks (`ShardIndex.search_grouped`).  The usual lists are flattened paper
+        by paper, best paper first and within a paper the best chunk first; added `group_keys` holds the papers' keys per query and
+        `group_sizes` the chunks returned for each.  Composes with a single `where`, `where_document` and the dedup keep-bitmap (one
+        bitmap per call).  ValueError with `reranker`, `hybrid_alpha`, `mmr_lambda`, per-query filter lists, `world > 1` (a paper may
+        straddle ranks) or a collection built without `group_key`."""
         import torch
         from .filter_sets import is_per_query
+        from .grouping import check_grouped_query
+        check_grouped_query(n_results, chunks_per_group, grouped=bool(group_by), has_group_key=getattr(self, "group_key", None) is not None,
+                            reranker=reranker, hybrid_alpha=hybrid_alpha, mmr_lambda=mmr_lambda,
+                            per_query_filters=is_per_query(where) or is_per_query(where_document), world=getattr(self, "world", 1))
         per_query = None
         if is_per_query(where) or is_per_query(where_document):
             if hybrid_alpha is not None:
@@ -268,7 +289,14 @@ class HipCollection:
         if q.dim() == 1:
             q = q[None]
         wide = reranker is not None or hybrid_alpha is not None or mmr_lambda is not None
-        if per_query is not None:
+        grp = None
+        if group_by:
+            allow, n_allowed = self._allow_of(where, doc_tree if where_document is not None else None, q.device)
+            s, i, grp = self.index.search_grouped(q, n_results, chunks_per_group, allow=allow, n_allowed=n_allowed)
+            grp = grp.cpu().numpy()
+            sizes = (i >= 0).sum(dim=2).cpu().numpy()
+            s, i = s.reshape(q.shape[0], -1), i.reshape(q.shape[0], -1)      # paper by paper; the padding is dropped below
+        elif per_query is not None:
             s, i = self._search_per_query(q, n_candidates if wide else n_results, *per_query)
         else:
             allow, n_allowed = self._allow_of(where, doc_tree if where_document is not None else None, q.device)
@@ -315,6 +343,9 @@ class HipCollection:
             out["distances"].append((2.0 - 2.0 * s[qi][keep]).tolist())
             out["documents"].append([m.get("text") for m in ms])
             out["metadatas"].append([{k: m.get(k) for k in ("paper_id", "section", "quality_score")} for m in ms])
+        if grp is not None:
+            out["group_keys"] = [[self.group_keys[int(v)] for v in grp[qi] if v >= 0] for qi in range(q.shape[0])]
+            out["group_sizes"] = [[int(n) for n, v in zip(sizes[qi], grp[qi]) if v >= 0] for qi in range(q.shape[0])]
         if mmr_val is not None:
             out["mmr_scores"] = [mmr_val[qi][i[qi] >= 0].tolist() for qi in range(q.shape[0])]
         if reranker is not None:

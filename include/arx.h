@@ -370,6 +370,49 @@ int32_t arx_topk_search_prefix_tuned(const void* corpus, int64_t n_rows, const v
  * on this workspace.  Copies 16 bytes to the host and waits on `stream`. */
 int32_t arx_topk_prefix_stats(const void* ws, int64_t* overflowed_queries, int64_t* candidate_groups, void* stream);
 
+/* ---- Grouped exact search: the top papers with their best chunks (field collapsing; csrc/grouped.hip) --------------------------------
+ * group_of: device int32 [n_rows], non-decreasing and non-negative, not necessarily dense: a group (a paper) is a contiguous run of
+ * rows.  allow: a row bitmap in the convention of arx_topk_search_filtered, NULL = every row; n_allowed as there (-1 = unknown).
+ * For query q, score(q, r) has the bits it has in arx_topk_search and arx_topk_search_filtered.  A group's score is the maximum of
+ * score(q, r) over its visible rows; a group with no visible row does not exist for the query.  The answer is the n_groups best groups
+ * by (group score desc, row of the best chunk asc) and, for each, its chunks_per_group best visible chunks by (score desc, row asc): the
+ * first chunk is the one that gave the group its score.
+ *   out_scores f32 [n_queries, n_groups, chunks_per_group], out_ids int64 (same shape) = idx_base + row,
+ *   out_groups int32 [n_queries, n_groups] = the group_of value;
+ * padding (-inf, -1) for chunks and -1 for groups when fewer than n_groups groups are visible or a group has fewer than
+ * chunks_per_group visible rows.  1 <= n_groups <= 32, 1 <= chunks_per_group <= 8, dim % 64 == 0, any n_queries (sliced above 1 024).
+ * max_run_rows: an upper bound on the rows of any run, the caller's contract as max_row_norm is (arx_group_runs_info measures it): too
+ * small voids the exactness proof, too large only raises K = n_groups * (floor((max_run_rows + 62) / 64) + 1), the number of 64-row
+ * group maxima the scan selects among (the proof is in csrc/grouped.hip).  K > 512: the whole call takes the exhaustive path.
+ * A query's output depends on the query, the mask, group_of and the corpus alone - not on the batch, its order, the path or cand_cap.
+ * A null pointer, n_groups or chunks_per_group out of range, max_run_rows < 1 or dim % 64 != 0: ARX_ERR_ARG before any launch, the
+ * message naming the field and its value.
+ * ws: device workspace of arx_topk_grouped_workspace_bytes(...) bytes, caller-owned; with qb = min(n_queries, 1 024), ldg = qb rounded
+ * up to 64, G = ceil(n_rows / 64), P = n_groups and T = min(ceil(n_rows / 256), 128) it is the sum, each term rounded up to 256 bytes,
+ * of 64 + 4 G ldg + 8 G + 4 qb + 4 qb P + 8 qb P + 4 T qb P + 8 T qb P (chunks_per_group does not enter; -1 for an unsupported
+ * shape: n_rows outside 1 .. 2^36 - 1, n_queries < 1, dim not a multiple of 64 in 64 .. 8192, n_groups or chunks_per_group out of
+ * range). */
+int64_t arx_topk_grouped_workspace_bytes(int64_t n_rows, int32_t n_queries, int32_t dim, int32_t n_groups, int32_t chunks_per_group);
+int32_t arx_topk_search_grouped(const void* corpus, int64_t n_rows, const int32_t* group_of, int64_t max_run_rows, const uint64_t* allow,
+                                int64_t n_allowed, const void* queries, int32_t n_queries, int32_t dim, int32_t n_groups,
+                                int32_t chunks_per_group, float* out_scores, int64_t* out_ids, int32_t* out_groups, int64_t idx_base,
+                                float max_row_norm, void* ws, int64_t ws_bytes, void* stream);
+/* The same with the path and the candidate capacity chosen by the caller (tests, tuning): path 0 = library's choice, 1 = the scan,
+ * 2 = exhaustive over the visible rows; cand_cap = candidate groups a query may list before it goes to the exhaustive path (0 =
+ * default 1 024, at most 8192).  Same bits for every choice. */
+int32_t arx_topk_search_grouped_tuned(const void* corpus, int64_t n_rows, const int32_t* group_of, int64_t max_run_rows,
+                                      const uint64_t* allow, int64_t n_allowed, const void* queries, int32_t n_queries, int32_t dim,
+                                      int32_t n_groups, int32_t chunks_per_group, float* out_scores, int64_t* out_ids, int32_t* out_groups,
+                                      int64_t idx_base, float max_row_norm, void* ws, int64_t ws_bytes, int32_t path, int32_t cand_cap,
+                                      void* stream);
+/* {queries sent to the exhaustive path because their candidate list overflowed, candidate groups rescored} of the LAST grouped search
+ * on this workspace.  Copies 16 bytes to the host and waits on `stream`. */
+int32_t arx_topk_grouped_stats(const void* ws, int64_t* overflowed_queries, int64_t* candidate_groups, void* stream);
+/* out (device int64 [2], written by the kernels on `stream`) = {rows of the longest run of group_of, number of runs}; the longest run is
+ * -1 when group_of decreases somewhere or holds a negative value.  What max_run_rows wants, as arx_rows_max_norm_f16 is what
+ * max_row_norm wants. */
+int32_t arx_group_runs_info(const int32_t* group_of, int64_t n_rows, int64_t* out, void* stream);
+
 /* ---- Substring scan over the chunk texts (Chroma's `where_document`: `$contains` / `$not_contains`) -----------------------------
  * The producer of the row bitmaps arx_topk_search_filtered takes (csrc/textscan.hip).
  * out_bits[p][w] bit (r & 63) of word w = r >> 6  <=>  pattern p occurs in row r, entirely inside

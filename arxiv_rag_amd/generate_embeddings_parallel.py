@@ -661,7 +661,8 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
                    output_dir: str = "./embeddings_saved", chunk_base: int = 0, reranker=None, rerank_top_k: int = 32,
                    hybrid_alpha: Optional[float] = None, where=None,
                    where_document: Optional[Dict] = None, *, mmr_lambda: Optional[float] = None, mmr_fetch_k: int = 32,
-                   keep_mask: Optional[np.ndarray] = None, group_by_paper: bool = False, chunks_per_paper: int = 1) -> List[Dict]:
+                   keep_mask: Optional[np.ndarray] = None, group_by_paper: bool = False, chunks_per_paper: int = 1,
+                   where_on_device: bool = False) -> List[Dict]:
     """Brute-force cosine top-k (config.yaml:63-64 `top_k: 10`) over the rank's fp16 rows in HBM; with
     torchrun each rank holds the contiguous row shard it encoded and the partial top-k lists are
     all-gathered over RCCL and merged.  `shard` is the `ShardSink` the encode step filled: rows [lo, hi) are already where they
@@ -698,7 +699,12 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
     consecutive chunks with equal `metadata["paper_id"]` are one paper (`grouping.runs_from_keys`), and the search returns the exact
     best papers by their best chunk, each with its `chunks_per_paper` (<= 8) best chunks (`ShardIndex.search_grouped`), filters applied
     as without it.  The hits come paper by paper, best paper first, and carry `paper_rank` and `paper_id`.  Not together with
-    `reranker`, `hybrid_alpha`, `mmr_lambda`, a per-query `where` list or more than one rank (a paper may straddle ranks)."""
+    `reranker`, `hybrid_alpha`, `mmr_lambda`, a per-query `where` list or more than one rank (a paper may straddle ranks).
+    `where_on_device` (False = nothing changes; needs `where`): the `where` filters are evaluated on the device from metadata columns
+    uploaded once (`where_device.MetadataColumns` over this rank's `chunks`), `keep_mask` and `where_document` and-ed in by the same
+    kernel, a per-query list in one launch per 64 distinct filters.  Same hits as without it."""
+    if where_on_device and where is None:
+        raise ValueError("where_on_device needs where: it chooses where the where filters are evaluated")
     if group_by_paper:
         from .grouping import check_grouped_query
         check_grouped_query(top_k, chunks_per_paper, grouped=True, reranker=reranker, hybrid_alpha=hybrid_alpha, mmr_lambda=mmr_lambda,
@@ -734,7 +740,13 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
         from .filter_sets import per_query_list
         where_each, where = per_query_list(where, len(queries), "where"), None
         pre = None
-    if where is not None:
+    where_tree = None                                        # where_on_device: evaluated below, once the bitmap to and in is known
+    if where is not None and where_on_device:
+        from .where import compile_where
+        where_tree = compile_where(where)
+        if len(chunks) != shard.rows.shape[0]:
+            raise ValueError(f"where: {len(chunks)} chunks for the shard's {shard.rows.shape[0]} rows")
+    elif where is not None:
         from .where import compile_where, evaluate, pack_bitmap
         mask = evaluate(compile_where(where), [c.get("metadata") or {} for c in chunks])
         if mask.shape[0] != shard.rows.shape[0]:
@@ -748,7 +760,7 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
             raise ValueError(f"keep_mask: {keep_mask.shape[0]} entries for the shard's {shard.rows.shape[0]} rows")
         keep = torch.from_numpy(pack_bitmap(keep_mask).view(np.int64)).to(dev)
         allow = keep if allow is None else (allow & keep).contiguous()
-        n_allowed = int(keep_mask.sum()) if where is None else int((mask & keep_mask).sum())
+        n_allowed = int(keep_mask.sum()) if (where is None or where_tree is not None) else int((mask & keep_mask).sum())
         pre = None
     if where_document is not None:
         from .where_document import DocumentStore, compile_where_document
@@ -762,6 +774,12 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
             allow = (allow & docs.fold(doc_tree)).contiguous()
             n_allowed = docs.count(allow)
         pre = None
+    if where_on_device:
+        from .where_device import MetadataColumns
+        columns = MetadataColumns([c.get("metadata") or {} for c in chunks], 0, len(chunks), dev)
+    if where_tree is not None:
+        bits, cnt = columns.allow_many([where_tree], allow)
+        allow, n_allowed, pre = bits[0], cnt[0], None
     if group_by_paper:
         from .grouping import runs_from_keys
         if len(chunks) != shard.rows.shape[0]:
@@ -786,8 +804,15 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
         metas = [c.get("metadata") or {} for c in chunks]
         n_words = (len(chunks) + 63) // 64
         bitmaps, counts = [], []
-        for w, _ in pairs:                                   # `allow` so far: the keep-mask and `where_document`, shared by every query
-            if w is None:
+        on_device = {}
+        if where_on_device:                                  # every distinct filter of the batch in one launch per 64, `allow` and-ed in
+            mine = [j for j, (w, _) in enumerate(pairs) if w is not None]
+            bits, cnt = columns.allow_many([compile_where(pairs[j][0]) for j in mine], allow)
+            on_device = {j: (bits[t], cnt[t] if allow is None else None) for t, j in enumerate(mine)}
+        for j, (w, _) in enumerate(pairs):                   # `allow` so far: the keep-mask and `where_document`, shared by every query
+            if j in on_device:
+                words, count = on_device[j]
+            elif w is None:
                 words = allow if allow is not None else torch.full((n_words,), -1, dtype=torch.int64, device=dev)
                 count = n_allowed if allow is not None else len(chunks)
             else:
@@ -904,6 +929,9 @@ def build_parser() -> argparse.ArgumentParser:
                    help="A different --where filter per query: a JSON-lines file with one filter object or null (no filter) per line, "
                         "one line per query of --queries; the batch is searched in one pass over the rows (not with --where or "
                         "--hybrid-alpha)")
+    p.add_argument("--where-on-device", action="store_true",
+                   help="Evaluate the --where / --where-file filters on the GPU from metadata columns kept in HBM, not with numpy on "
+                        "the host (same results; needs --where or --where-file)")
     p.add_argument("--where-document", type=str, default=None,
                    help="Chroma document filter for --queries as JSON, e.g. '{\"$contains\": \"Lipschitz\"}' or "
                         "'{\"$and\": [{\"$contains\": \"graph\"}, {\"$not_contains\": \"lemma\"}]}': only chunks whose text "
@@ -1095,6 +1123,15 @@ def check_where_file_args(args) -> Optional[str]:
     return None
 
 
+def check_where_device_args(args) -> Optional[str]:
+    """-> an error message for an unusable --where-on-device, else None."""
+    if not getattr(args, "where_on_device", False):
+        return None
+    if args.where is None and getattr(args, "where_file", None) is None:
+        return "--where-on-device needs --where or --where-file: it chooses where those filters are evaluated"
+    return None
+
+
 def check_where_document_args(args) -> Optional[str]:
     """-> an error message for an unusable --where-document, else None.  On success `args.where_document_filter` holds the parsed filter
     (None without --where-document)."""
@@ -1119,7 +1156,8 @@ def check_where_document_args(args) -> Optional[str]:
 def main(argv: Optional[Sequence[str]] = None, model_factory: Optional[Callable] = None) -> int:
     global _model, _model_name
     args = build_parser().parse_args(argv)
-    err = (check_rerank_args(args) or check_hybrid_args(args) or check_where_args(args) or check_where_file_args(args) or check_where_document_args(args)
+    err = (check_rerank_args(args) or check_hybrid_args(args) or check_where_args(args) or check_where_file_args(args) or check_where_device_args(args)
+           or check_where_document_args(args)
            or check_mmr_args(args) or check_dedup_args(args) or check_group_args(args))
     if err:
         print(f"Error: {err}")
@@ -1217,7 +1255,8 @@ def main(argv: Optional[Sequence[str]] = None, model_factory: Optional[Callable]
                                reranker=reranker, rerank_top_k=args.rerank_top_k, hybrid_alpha=args.hybrid_alpha,
                                where=args.where_filters if args.where_filters is not None else args.where_filter, where_document=args.where_document_filter,
                                mmr_lambda=args.mmr_lambda, mmr_fetch_k=args.mmr_fetch_k, keep_mask=keep_mask,
-                               **({"group_by_paper": True, "chunks_per_paper": args.chunks_per_paper} if args.group_by_paper else {}))
+                               **({"group_by_paper": True, "chunks_per_paper": args.chunks_per_paper} if args.group_by_paper else {}),
+                               **({"where_on_device": True} if args.where_on_device else {}))
         store_time = 0.0
         if rank == 0 and not args.skip_chroma:
             try:

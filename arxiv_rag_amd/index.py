@@ -528,8 +528,8 @@ class ShardIndex:
 
 def search_filtered_grouped(index: ShardIndex, queries_f16: torch.Tensor, k: int, bitmaps, filter_of, counts=None, group=None):
     """`ShardIndex.search_filtered_many` (through `search_distributed`) for ANY number of distinct filters: `bitmaps` is a list of device
-    int64 [ceil(n_rows / 64)] tensors, `filter_of` a host sequence with the index of every query's bitmap, `counts` the bitmaps' allowed
-    rows (or None).  The batch is cut into calls of at most 64 distinct filters (`filter_sets.filter_groups`) and the rows are put back
+    int64 [ceil(n_rows / 64)] tensors (or one contiguous [F, ceil(n_rows / 64)] tensor, whose rows a call then reads in place),
+    `filter_of` a host sequence with the index of every query's bitmap, `counts` the bitmaps' allowed rows (or None).  The batch is cut into calls of at most 64 distinct filters (`filter_sets.filter_groups`) and the rows are put back
     in query order -> (scores [Q, k], ids [Q, k]) as one call would return them."""
     from .filter_sets import filter_groups
     q = queries_f16
@@ -538,7 +538,10 @@ def search_filtered_grouped(index: ShardIndex, queries_f16: torch.Tensor, k: int
     scores = torch.empty((q.shape[0], k), dtype=torch.float32, device=dev)
     ids = torch.empty((q.shape[0], k), dtype=torch.int64, device=dev)
     for positions, filters, local_of in groups:
-        allows = torch.stack([bitmaps[f] for f in filters]).contiguous()
+        if torch.is_tensor(bitmaps) and filters == list(range(filters[0], filters[-1] + 1)):
+            allows = bitmaps[filters[0]:filters[-1] + 1]
+        else:
+            allows = torch.stack([bitmaps[f] for f in filters]).contiguous()
         fo = torch.tensor(local_of, dtype=torch.int32, device=dev)
         n_allowed = None if counts is None else [counts[f] for f in filters]
         if len(groups) == 1:                                   # the whole batch, already in order

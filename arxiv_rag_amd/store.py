@@ -75,7 +75,8 @@ class HipCollection:
 
     def __init__(self, embeddings: np.ndarray, metadata: Sequence[Dict], device="cuda:0", encoder=None,
                  rank: int = 0, world: int = 1, chunk_rows: int = 1 << 18, keyword: bool = False, tokenizer=None,
-                 documents: bool = False, dedup_threshold: Optional[float] = None, group_key: Optional[str] = None):
+                 documents: bool = False, dedup_threshold: Optional[float] = None, group_key: Optional[str] = None,
+                 where_on_device: bool = False):
         """`keyword=True`: also build a BM25 `keyword.KeywordIndex` over this shard's `metadata[i]["text"]` (word pieces of `tokenizer`,
         default the encoder's; corpus statistics summed over all ranks when `world > 1`), which `query(hybrid_alpha=...)` needs.
         `documents=True`: also keep this shard's texts as a UTF-8 blob in HBM (`where_document.DocumentStore`), which
@@ -88,7 +89,12 @@ class HipCollection:
         raises ValueError: a rank sees only its own rows, and a cross-rank join is out of scope.
         `group_key` (a metadata key, e.g. "paper_id"; None = off, nothing changes): consecutive rows of this rank with equal
         `metadata[i][group_key]` are one group (`grouping.runs_from_keys`; a key that reappears after its run ended is a ValueError naming
-        the key and the two rows), uploaded once (`ShardIndex.set_groups`); `query(group_by=True)` needs it."""
+        the key and the two rows), uploaded once (`ShardIndex.set_groups`); `query(group_by=True)` needs it.
+        `where_on_device` (False = nothing changes): `query(where=...)` evaluates the filter on the device from metadata columns kept in
+        HBM (`where_device.MetadataColumns`: 9 bytes per row and referenced key, a column built on first use), not with numpy on the
+        host; the dedup keep-bitmap and the `where_document` bitmap are and-ed in by the same kernel, so no mask is built or uploaded,
+        and a per-query `where` list is evaluated in one launch per 64 distinct filters.  The results are the default path's, bit for
+        bit (INTEGRATION.md "where on the device")."""
         import torch
         from .index import ShardIndex, shard_bounds
         if dedup_threshold is not None:
@@ -106,6 +112,7 @@ class HipCollection:
             group_of, self.group_keys = runs_from_keys([metadata[r].get(group_key) for r in range(lo, hi)], base=lo)
         self.metadata = metadata
         self._where_columns: Dict = {}                          # `query(where=...)`: one numpy column per referenced metadata key
+        self.where_on_device, self._device_columns = bool(where_on_device), None
         self.encoder = encoder
         shard = torch.empty((hi - lo, d), dtype=torch.float16, device=device)
         for s0 in range(lo, hi, chunk_rows):                   # stream: never a second full copy in host RAM
@@ -150,6 +157,10 @@ class HipCollection:
         keep-bitmap, and-ed; (None, None) when there is none of the three."""
         import torch
         allow = n_allowed = None
+        if where is not None and getattr(self, "where_on_device", False):
+            from .where import compile_where
+            bits, counts = self._columns().allow_many([compile_where(where)], self._and_with_of(doc_tree))
+            return bits[0], counts[0]
         if where is not None:
             from .where import compile_where, evaluate, pack_bitmap
             mask = evaluate(compile_where(where), self.metadata, self.lo, self.hi, cache=self._where_columns)
@@ -170,6 +181,62 @@ class HipCollection:
                 n_allowed = self.documents.count(allow)
         return allow, n_allowed
 
+    def _columns(self):
+        if self._device_columns is None:
+            from .where_device import MetadataColumns
+            self._device_columns = MetadataColumns(self.metadata, self.lo, self.hi, self.index.corpus.device)
+        return self._device_columns
+
+    def _and_with_of(self, doc_tree):
+        """What `where_on_device` and-s into a `where` bitmap: the folded `where_document` bitmap and the dedup keep-bitmap (None: neither)."""
+        words = self.documents.fold(doc_tree) if doc_tree is not None else None
+        if self._keep is not None:
+            words = self._keep if words is None else (words & self._keep).contiguous()
+        return words
+
+    def _bitmaps_on_device(self, pairs, device):
+        """`where_on_device`: (bitmaps, counts) of the distinct (where, where_document) pairs of a per-query batch.  Every `where` is
+        lowered, and all of them are evaluated by one `arx_where_eval` per 64, each with its own `where_document` / keep bitmap and-ed in;
+        when every pair has a `where`, the [F, W] tensor the kernel wrote is what the search reads, without a copy."""
+        import torch
+        from .where import compile_where
+        from .where_document import compile_where_document
+        n_words = (self.hi - self.lo + 63) // 64
+        trees, ands, folded, rest = [], [], {}, {}
+        for j, (w, d) in enumerate(pairs):                       # (compiled in the default path's order: the same refusal comes first)
+            doc_tree = compile_where_document(d) if d is not None else None
+            if w is None:
+                rest[j] = doc_tree
+                continue
+            trees.append(compile_where(w))
+            key = None if d is None else json.dumps(d, sort_keys=True)
+            if key not in folded:                                # one fold per distinct where_document
+                folded[key] = self._and_with_of(doc_tree)
+            ands.append(folded[key])
+        bits, counts = None, []
+        if trees:
+            if len(folded) == 1:
+                and_with = ands[0]
+            else:
+                ones = torch.full((n_words,), -1, dtype=torch.int64, device=device)
+                and_with = torch.stack([ones if a is None else a for a in ands]).contiguous()
+            bits, counts = self._columns().allow_many(trees, and_with)
+        if not rest:
+            return bits, counts
+        bitmaps, cnt, t = [], [], 0
+        for j in range(len(pairs)):
+            if j not in rest:
+                bitmaps.append(bits[t])
+                cnt.append(counts[t])
+                t += 1
+                continue
+            allow, n_allowed = self._allow_of(None, rest[j], device)
+            if allow is None:
+                allow, n_allowed = torch.full((n_words,), -1, dtype=torch.int64, device=device), self.hi - self.lo
+            bitmaps.append(allow)
+            cnt.append(n_allowed)
+        return bitmaps, cnt
+
     def _search_per_query(self, q, k, where, where_document):
         """The search of `query` when `where` / `where_document` hold one entry per query: one bitmap per distinct pair, one
         `search_filtered_many` per 64 of them."""
@@ -180,6 +247,9 @@ class HipCollection:
         pairs, filter_of = distinct_filters(per_query_list(where, nq, "where"), per_query_list(where_document, nq, "where_document"))
         if any(d is not None for _, d in pairs) and self.documents is None:
             raise ValueError("where_document needs a collection built with documents=True")
+        if getattr(self, "where_on_device", False) and self.hi > self.lo:
+            bitmaps, counts = self._bitmaps_on_device(pairs, q.device)
+            return search_filtered_grouped(self.index, q, k, bitmaps, filter_of, counts)
         bitmaps, counts = [], []
         for w, d in pairs:
             doc_tree = None

@@ -431,6 +431,50 @@ int32_t arx_text_contains(const uint8_t* blob, const int64_t* row_off, int64_t n
 /* *out_count (ONE device int64) = set bits of bits[0 .. ceil(n_rows/64)) that name rows below n_rows. */
 int32_t arx_bitmap_count(const uint64_t* bits, int64_t n_rows, int64_t* out_count, void* stream);
 
+/* ---- Chroma `where` filters over metadata columns in HBM (csrc/where_eval.hip; the lowering is arxiv_rag_amd/where_device.py) ----
+ * A column is one metadata key over the shard's rows: kind uint8 [n_rows] (0 = absent or another type, 1 = number, 2 = string,
+ * 3 = bool) and val f64 [n_rows] (the number; a string's rank in the sorted distinct strings of the key; 0.0 / 1.0 for a bool; 0.0
+ * otherwise): 9 bytes per row and key.  col_table holds the two device addresses of every column of the call.
+ * A filter is a postfix program over its own leaves.  Token = (arg << 2) | code, int32:
+ *   code 0  LEAF i   push leaf i of this filter (i counts from the filter's first leaf)
+ *   code 1  AND n    pop n entries, push 1 if all are 1          (1 <= n <= 32)
+ *   code 2  OR n     pop n entries, push 1 if any is 1
+ * The stack never holds more than 32 entries and ends with one, the row's result: the CALLER's contract (the arrays are device data).
+ * A leaf is true for row r when  (kind[r] == want_kind && cmp(val[r], operand)) != (negate != 0), compared in f64:
+ *   op 0 EQ ==   1 GT >   2 GE >=   3 LT <   4 LE <=   5 IN val[r] is one of set_vals[set_off, set_off + set_len)   6 NEVER false
+ * A set slice is ascending, distinct and NaN-free; it is searched by value (-0.0 finds 0.0).
+ * The layout of a leaf, 32 bytes, no padding: */
+typedef struct {
+    double  operand;      /* offset  0: the right-hand side of EQ..LE; unused by IN and NEVER */
+    int32_t column;       /* offset  8: index into col_table, 0 <= column < n_cols */
+    int32_t want_kind;    /* offset 12: 1 number, 2 string, 3 bool */
+    int32_t op;           /* offset 16 */
+    int32_t negate;       /* offset 20: 0 or 1 ($ne, $nin) */
+    int32_t set_off;      /* offset 24: IN: first entry of the leaf's slice of set_vals */
+    int32_t set_len;      /* offset 28: IN: its length */
+} arx_where_leaf;
+/*   col_table  device int64 [n_cols][2]            {address of kind, address of val} per column; n_cols >= 1
+ *   leaves     device arx_where_leaf [leaf_off[n_filters]];  leaf_off  device int32 [n_filters + 1], ascending from 0
+ *   tokens     device int32 [token_off[n_filters]];          token_off device int32 [n_filters + 1], ascending from 0
+ *   set_vals   device f64 [n_set_vals], 0 <= n_set_vals <= 2^20 (may be NULL when 0)
+ *   and_with   NULL, or device uint64 bitmaps and-ed into the result: filter f uses the words at and_with + f * and_stride
+ *              (and_stride in words; 0 = one bitmap for all filters)
+ *   out_bits   device uint64 [n_filters][ceil(n_rows / 64)]: bit (r & 63) of word r >> 6 of bitmap f <=> row r satisfies filter f
+ *              (and and_with allows it).  Bits at or beyond n_rows are written as 0.  The layout arx_topk_search_filtered_multi takes.
+ *   out_counts device int64 [n_filters]: the set bits of each bitmap, written by the kernels on `stream`.
+ * Every word of out_bits and every count is written: neither depends on what the buffers held before.  Two launches on `stream` (all
+ * bitmaps, then the counts), no atomics, no workspace, no host synchronisation.  1 <= n_filters <= 64, 1 <= n_rows < 2^36.
+ * A null pointer, n_filters, n_rows, n_cols or n_set_vals out of range or a negative and_stride: ARX_ERR_ARG before any launch, the
+ * message names the field.  What the leaves and offsets hold is device data: where_device.py validates it on the host before the
+ * upload (a column index outside [0, n_cols) is refused there), and the kernel clamps leaf, column and set indices to the ranges the
+ * call declares, so a damaged program yields wrong bits but reads nothing out of range. */
+int32_t arx_where_eval(const int64_t* col_table, int32_t n_cols, int64_t n_rows,
+                       const arx_where_leaf* leaves, const int32_t* leaf_off,
+                       const int32_t* tokens, const int32_t* token_off,
+                       const double* set_vals, int64_t n_set_vals, int32_t n_filters,
+                       const uint64_t* and_with, int64_t and_stride,
+                       uint64_t* out_bits, int64_t* out_counts, void* stream);
+
 /* ---- MMR diversified re-ordering of a query's search candidates (csrc/mmr.hip; the definition is INTEGRATION.md "MMR") -----------
  * arx_gather_rows: out[s] (device fp16 [count, dim]) = shard row ids[s] - idx_base where that row lies in [0, n_rows), all zeros
  * otherwise (id -1, a row another rank owns: the ranks' buffers then add up to the rows, arxiv_rag_amd/mmr.py).  shard device fp16

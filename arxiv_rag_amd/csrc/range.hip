@@ -1,0 +1,475 @@
+// arx_range_search: score-threshold search over an fp16 shard (C ABI in include/arx.h; LangChain's similarity_score_threshold, LlamaIndex's
+// similarity_cutoff, and candidate lists longer than the top-k searches' 32).  For query q with threshold min_score[q] and an optional
+// bitmap in the convention of arx_topk_search_filtered:
+//   score(q, r)    exact_row_score (search_tail.h): the bits arx_topk_search and arx_topk_search_filtered give the pair
+//   qualifies      a visible row with score(q, r) >= min_score[q], compared in f32 (-inf: every visible row; +inf or NaN: none)
+//   answer         the best min(count, M) qualifying rows by (score desc, row asc), M = max_results <= 1024, (-inf, -1) padding, and
+//                  out_counts[q] = the number of qualifying rows when that is <= M, M + 1 when more qualify (the list is truncated)
+// Pass A is masked_topk.h's masked_groupmax_kernel with a bitmap policy (allow == NULL: an all-ones bitmap in the workspace), unchanged.
+// The tail (range_tail_kernel, one block per query) is new: it keeps a variable, long, ordered list instead of a k <= 32 wave list.
+// Why the tail is exact: pass A and exact_row_score differ by at most tau = tau_scale |q| (the masked tail's own bound), so a qualifying
+// row has a pass-A score >= min_score - tau and its group's maximum is at least that.  Let t be the (M + 1)-th largest group maximum of
+// the query (-inf when fewer than M + 1 groups hold a visible row).  A qualifying row in a group with gmax < t - 2 tau has an exact score
+// below t - tau, while M + 1 distinct groups each hold a visible row whose pass-A score is >= t, hence whose exact score is >= t - tau:
+// those M + 1 rows all qualify (they beat a qualifying row) and all beat it, so it is not among the best M.  Candidates = every non-empty
+// group with gmax >= max(min_score - tau, t - 2 tau): they hold every row of the answer, and whenever more than M rows qualify they
+// alone hold M + 1 qualifying rows.  So "qualifying rows among the candidates <= M" means the list and the count are complete, and
+// ">= M + 1" means truncated: the count is reported as M + 1 and nothing more is known (an exact total would make a loose threshold
+// cost a full exact scan).  The (M + 1)-th largest of up to n_rows / 64 values is the block-wide radix select over order_key of the
+// masked and grouped tails.
+// The list: a qualifying row is the 64-bit key (order_key(score) << 32) | (0xffffffff - row), whose unsigned order is (score desc, row
+// asc); 0 = none (n_rows < 2^32).  The waves append keys to RANGE_CAP = 2048 slots in LDS (an INTEGER LDS atomic hands out the slots:
+// the list's order varies, its content does not); every qualifying row is counted apart.  Before a round of 16 groups that could
+// overflow the slots, the list is cut back to its M largest keys by a block-wide bitonic sort and the M-th key becomes the append
+// threshold, as bm25.hip keeps its candidates.  At the end the list is sorted once more and its best min(count, M) keys are stored.
+// The exhaustive path (a query whose candidate list overflows cand_cap; path 2): the shard's groups cut into T parts, block (part, query)
+// keeps the same list over every visible row of its part, scored by the same function, and stores its best M keys and its count; one
+// block per query then merges the T lists (at most T M <= 4096 keys, T - 1 rounds of at most one cut-back sort each: tens of
+// microseconds per flagged query) and adds the counts.  Same bits.
+// No float atomics; integer LDS atomics only as slot or plain counters whose order cannot reach the output; plain vector stores.  Every
+// output element of a query is written.  A query's output depends on the query, its threshold, the bitmap and the corpus alone.
+#include <math.h>
+
+#include "arx_common.h"
+#include "gemm.h"
+#include "gemm8.h"
+#include "search_consts.h"
+
+namespace {      // the headers also define non-template kernels: internal linkage keeps this object's copies apart from search.hip's
+#include "search_pass_a.h"
+#include "search_tail.h"
+#include "masked_topk.h"
+#include "bitmap_rows.h"
+
+#define RANGE_MAX_RESULTS 1024       // largest M
+#define RANGE_CAP 2048               // key slots of a block's list (16 KB of LDS): M kept keys + one round of 16 groups x 64 rows
+#define RANGE_NT FILT_TAIL_NT        // threads of every block that keeps a list
+#define RANGE_PART_KEYS 4096         // T M <= this: bounds the exhaustive path's per-part lists (and the workspace)
+
+// ---- pass A's mask policy: the bitmap of the call, as filter.hip's ------------------------------------------------------------------------
+struct RangeBitmap {
+    const uint64_t* allow;
+    struct LaneRows {
+        bool on[GROUP_ROWS / 16][4];
+        __device__ __forceinline__ const LaneRows& of_query(int, int) const { return *this; }
+        __device__ __forceinline__ bool operator()(int j, int r) const { return on[j][r]; }
+    };
+    struct Tile {
+        bool empty; uint64_t mine;
+        __device__ __forceinline__ LaneRows lane_rows(int64_t, int lane) const {
+            const uint32_t lrow = (uint32_t)(lane >> 4) * 4u;
+            LaneRows s;
+#pragma unroll
+            for (int j = 0; j < GROUP_ROWS / 16; ++j)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) s.on[j][r] = (mine >> ((uint32_t)(j * 16 + r) + lrow)) & 1ull;
+            return s;
+        }
+    };
+    template <int BM>
+    __device__ __forceinline__ Tile tile(int64_t n0, int wn, int, int, int64_t n_rows) const {
+        const int64_t n_groups = (n_rows + GROUP_ROWS - 1) / GROUP_ROWS;
+        uint64_t any = 0, mine = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int64_t gj = (n0 >> 6) + j;
+            const uint64_t w = gj < n_groups ? (allow[gj] & valid_bits(n_rows, gj)) : 0ull;
+            any |= w;
+            mine = j == wn ? w : mine;
+        }
+        return {any == 0ull, mine};
+    }
+};
+
+__global__ __launch_bounds__(256) void range_ones_kernel(uint64_t* __restrict__ words, int64_t n_words) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n_words) words[i] = ~0ull;
+}
+
+// ---- the list of a block ------------------------------------------------------------------------------------------------------------------
+struct RangeList {
+    unsigned long long keys[RANGE_CAP];
+    unsigned long long thr;      // keys at or below it are not appended: 0, then the M-th key of the last cut
+    int cnt;                     // slots handed out
+    int n_qual;                  // qualifying rows seen, appended or not
+};
+
+__device__ __forceinline__ unsigned long long range_key(float s, int64_t row) {
+    return ((unsigned long long)order_key(s) << 32) | (unsigned long long)(0xffffffffu - (uint32_t)row);
+}
+
+// keys[0 .. c) -> descending order (bitonic, over the next power of two >= max(c, 64), the slots beyond c zeroed).  The whole block, c
+// block-uniform and <= RANGE_CAP; every thread's earlier writes to keys[] are behind a barrier already; ends with a barrier.
+__device__ __forceinline__ void range_sort_desc(unsigned long long* keys, int c) {
+    const int tid = threadIdx.x;
+    int n = 64;
+    while (n < c) n <<= 1;
+    for (int i = c + tid; i < n; i += RANGE_NT) keys[i] = 0ull;
+    __syncthreads();
+    for (int k = 2; k <= n; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            if (tid < (n >> 1)) {                              // n / 2 <= RANGE_CAP / 2 = RANGE_NT pairs
+                const int i = ((tid & ~(j - 1)) << 1) | (tid & (j - 1)), p = i | j;
+                const unsigned long long a = keys[i], b = keys[p];
+                if (((i & k) == 0) ? a < b : a > b) { keys[i] = b; keys[p] = a; }
+            }
+            __syncthreads();
+        }
+}
+
+// cut the list (c keys, any order) back to its M largest, sorted; updates cnt and thr.  The whole block, c uniform; ends with a barrier.
+__device__ __forceinline__ void range_cut(RangeList& L, int c, int M) {
+    range_sort_desc(L.keys, c);
+    if (threadIdx.x == 0) {
+        L.cnt = c < M ? c : M;
+        L.thr = c >= M ? L.keys[M - 1] : 0ull;
+    }
+    __syncthreads();
+}
+
+// one wave: the exact scores of the rows of group g that `word` names -> sc[0..64) (entries of other rows are not written)
+__device__ __forceinline__ void score_word_rows(const f16_t* __restrict__ C, int64_t g, uint64_t word, const f16_t* qs, int D, int lane,
+                                                float* sc) {
+    const int nch = D >> 3, l8 = lane & 7, rsub = lane >> 3;
+    for (int r8 = 0; r8 < GROUP_ROWS; r8 += 8) {
+        if (((word >> r8) & 0xffull) == 0ull) continue;          // wave-uniform
+        const int rr = r8 + rsub;
+        const bool ok = (word >> rr) & 1ull;
+        const float a = exact_row_score(C + (g * GROUP_ROWS + rr) * D, qs, nch, l8, ok);
+        if (l8 == 0) sc[rr] = a;
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+}
+
+// one wave: the visible rows `word` of group g scored; those at or above ms counted, and appended where their key is above thr
+__device__ __forceinline__ void range_take_group(RangeList& L, const f16_t* __restrict__ C, int64_t g, uint64_t word, const f16_t* qs, int D,
+                                                 int lane, float* sc, float ms, unsigned long long thr) {
+    score_word_rows(C, g, word, qs, D, lane, sc);
+    const bool mine = (word >> lane) & 1ull;
+    const float s = mine ? sc[lane] : 0.f;
+    const bool qual = mine && s >= ms;
+    const unsigned long long qm = __ballot(qual);
+    if (qm == 0ull) return;                                     // wave-uniform
+    const unsigned long long key = range_key(s, g * GROUP_ROWS + lane);
+    const bool app = qual && key > thr;
+    const unsigned long long am = __ballot(app);
+    int base = 0;
+    if (lane == 0) {
+        atomicAdd(&L.n_qual, __popcll(qm));                     // a plain counter
+        if (am) base = atomicAdd(&L.cnt, __popcll(am));         // a slot counter: the list is read as a set
+    }
+    base = __shfl(base, 0);
+    if (app) {
+        const int sl = base + __popcll(am & ((1ull << lane) - 1ull));
+        if (sl < RANGE_CAP) L.keys[sl] = key;                   // (always: the caller cuts the list before a round that could overflow)
+    }
+}
+
+// the rounds of a block: in round r wave w takes item r * NW + w of `n_items`; group_of_item(item) names its group (< 0: none) and
+// word_of(g) its visible rows.  Before a round that could overflow the slots the list is cut back.  Ends with a barrier.
+template <class GroupOf, class WordOf>
+__device__ __forceinline__ void range_rounds(RangeList& L, int64_t n_items, GroupOf group_of_item, WordOf word_of, const f16_t* __restrict__ C,
+                                             const f16_t* qs, int D, float* sc, float ms, int M) {
+    constexpr int NW = RANGE_NT / 64;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    for (int64_t base = 0; base < n_items; base += NW) {       // block-uniform
+        const int c = L.cnt;
+        __syncthreads();                                         // everyone has read cnt before anyone appends
+        if (c + NW * GROUP_ROWS > RANGE_CAP) range_cut(L, c < RANGE_CAP ? c : RANGE_CAP, M);
+        const unsigned long long thr = L.thr;
+        const int64_t g = base + w < n_items ? group_of_item(base + w) : -1;
+        if (g >= 0) {                                            // wave-uniform
+            const uint64_t word = word_of(g);
+            if (word) range_take_group(L, C, g, word, qs, D, lane, sc, ms, thr);
+        }
+        __syncthreads();
+    }
+}
+
+// the sorted list's best min(c, M) keys -> this query's M output slots (the rest padded) and its count
+__device__ __forceinline__ void range_store(const RangeList& L, int c, int n_qual, int M, int64_t idx_base, float* __restrict__ out_s,
+                                            int64_t* __restrict__ out_i, int32_t* __restrict__ out_c) {
+    for (int r = threadIdx.x; r < M; r += RANGE_NT) {
+        const unsigned long long key = r < c ? L.keys[r] : 0ull;
+        out_s[r] = key ? key_value((uint32_t)(key >> 32)) : -INFINITY;
+        out_i[r] = key ? (int64_t)(0xffffffffu - (uint32_t)key) + idx_base : -1;
+    }
+    if (threadIdx.x == 0) *out_c = n_qual < M + 1 ? n_qual : M + 1;
+}
+
+// ---- the tail: one block per query ----------------------------------------------------------------------------------------------------------
+// stats: [0] queries sent to the exhaustive path, [1] candidate groups rescored, [2] (low word) "some query of this call overflowed".
+// out_* / min_score point at this batch's first query.
+__global__ __launch_bounds__(RANGE_NT) void range_tail_kernel(const float* __restrict__ gmax, int64_t ldg, int64_t n_groups,
+                                                               const uint64_t* __restrict__ allow, const f16_t* __restrict__ Q,
+                                                               const float* __restrict__ min_score, const f16_t* __restrict__ C, int64_t n_rows,
+                                                               int D, int M, float* __restrict__ out_s, int64_t* __restrict__ out_i,
+                                                               int32_t* __restrict__ out_c, int64_t idx_base, float tau_scale, int cand_cap,
+                                                               int32_t* __restrict__ redo, unsigned long long* __restrict__ stats) {
+    constexpr int NT = RANGE_NT, NW = NT / 64;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    __shared__ RangeList L;
+    __shared__ int red[NW];
+    __shared__ int n_c;
+    __shared__ float sh_qn;
+    const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const float ms = min_score[q];
+    out_s += (int64_t)q * M; out_i += (int64_t)q * M; out_c += q;
+    if (tid == 0) { n_c = 0; L.cnt = 0; L.n_qual = 0; L.thr = 0ull; }
+    if (!(ms < INFINITY)) {                                     // block-uniform: +inf or NaN, no row qualifies
+        __syncthreads();
+        range_store(L, 0, 0, M, idx_base, out_s, out_i, out_c);
+        if (tid == 0) redo[q] = 0;
+        return;
+    }
+    f16_t* qs = reinterpret_cast<f16_t*>(smem);                                                  // [D] query row
+    float* sc_all = reinterpret_cast<float*>(smem + (((size_t)D * 2 + 15) & ~(size_t)15));      // [NW][64] row scores of the group a wave is at
+    int32_t* list = reinterpret_cast<int32_t*>(sc_all + NW * GROUP_ROWS);                        // [cand_cap] candidate groups
+    for (int i = tid; i < (D >> 3); i += NT)
+        reinterpret_cast<u32x4*>(qs)[i] = reinterpret_cast<const u32x4*>(Q + (int64_t)q * D)[i];
+    // this query's column of group maxima, as ordered keys: the first FILT_REG_GROUPS per thread stay in registers
+    const float* col = gmax + q;
+    uint32_t kv[FILT_REG_GROUPS];
+#pragma unroll
+    for (int j = 0; j < FILT_REG_GROUPS; ++j) {
+        const int64_t g = (int64_t)j * NT + tid;
+        kv[j] = g < n_groups ? order_key(col[g * ldg]) : 0u;
+    }
+    __syncthreads();
+    if (w == 0) {
+        float qq = 0.f;
+        for (int i = lane; i < D; i += 64) { const float v = (float)qs[i]; qq = fmaf(v, v, qq); }
+        qq = wave_sum(qq);
+        if (lane == 0) sh_qn = sqrtf(qq);
+    }
+    // T = the largest key that at least M + 1 groups reach = the (M + 1)-th largest group maximum: a radix select, one bit per step
+    const int ksel = M + 1;
+    uint32_t T = 0u;
+    for (int bit = 31; bit >= 0; --bit) {
+        const uint32_t cand = T | (1u << bit);
+        int c = 0;
+#pragma unroll
+        for (int j = 0; j < FILT_REG_GROUPS; ++j) c += __popcll(__ballot(kv[j] >= cand));
+        for (int64_t g0 = (int64_t)FILT_REG_GROUPS * NT + w * 64; g0 < n_groups; g0 += NT) {          // (wave-uniform bounds)
+            const int64_t g = g0 + lane;
+            c += __popcll(__ballot(g < n_groups && order_key(col[(g < n_groups ? g : 0) * ldg]) >= cand));
+        }
+        if (lane == 0) red[w] = c;
+        __syncthreads();
+        int tot = 0;
+#pragma unroll
+        for (int ww = 0; ww < NW; ++ww) tot += red[ww];
+        __syncthreads();
+        T = tot >= ksel ? cand : T;
+    }
+    const float tau = tau_scale * sh_qn;
+    const float thr = fmaxf(ms - tau, key_value(T) - 2.0f * tau);      // key_value(T) = -inf when fewer than M + 1 groups hold a visible row
+    auto consider = [&](int64_t g, float v) {
+        if (v >= thr && v > -INFINITY) {
+            const int sl = atomicAdd(&n_c, 1);
+            if (sl < cand_cap) list[sl] = (int32_t)g;
+        }
+    };
+#pragma unroll
+    for (int j = 0; j < FILT_REG_GROUPS; ++j) {
+        const int64_t g = (int64_t)j * NT + tid;
+        if (g < n_groups) consider(g, key_value(kv[j]));
+    }
+    for (int64_t g = (int64_t)FILT_REG_GROUPS * NT + tid; g < n_groups; g += NT) consider(g, col[g * ldg]);
+    __syncthreads();
+    const int nc = n_c;
+    if (nc > cand_cap) {                                       // block-uniform: never an answer from a truncated list
+        if (tid == 0) {
+            redo[q] = 1;
+            atomicAdd(&stats[0], 1ull);
+            reinterpret_cast<int*>(stats + 2)[0] = 1;
+        }
+        return;
+    }
+    if (tid == 0) { redo[q] = 0; if (nc) atomicAdd(&stats[1], (unsigned long long)nc); }
+    // the visible rows of the candidate groups, exactly: a group per wave at a time
+    range_rounds(L, nc, [&](int64_t item) { return (int64_t)list[item]; },
+                 [&](int64_t g) { return allow[g] & valid_bits(n_rows, g); }, C, qs, D, sc_all + w * GROUP_ROWS, ms, M);
+    const int c = L.cnt < RANGE_CAP ? L.cnt : RANGE_CAP;
+    range_sort_desc(L.keys, c);
+    range_store(L, c, L.n_qual, M, idx_base, out_s, out_i, out_c);
+}
+
+// ---- exhaustive path: block (part p, query q) keeps the list over the visible rows of groups [p per, (p + 1) per) -> its best M keys
+// part_k [parts][nq][M] (0 = none) and its count of qualifying rows part_c [parts][nq].  only_if / gate as masked_topk.h's.
+__global__ __launch_bounds__(RANGE_NT) void range_exhaustive_kernel(const uint64_t* __restrict__ allow, const f16_t* __restrict__ Q,
+                                                                     const float* __restrict__ min_score, const f16_t* __restrict__ C,
+                                                                     int64_t n_rows, int64_t n_groups, int D, int nq, int M,
+                                                                     unsigned long long* __restrict__ part_k, int32_t* __restrict__ part_c,
+                                                                     const int32_t* __restrict__ only_if, const int* __restrict__ gate) {
+    if (gate && !*gate) return;
+    const int q = blockIdx.y, p = blockIdx.x, parts = gridDim.x;
+    if (only_if && !only_if[q]) return;
+    constexpr int NT = RANGE_NT, NW = NT / 64;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    __shared__ RangeList L;
+    const int tid = threadIdx.x, w = tid >> 6;
+    f16_t* qs = reinterpret_cast<f16_t*>(smem);
+    float* sc = reinterpret_cast<float*>(smem + (((size_t)D * 2 + 15) & ~(size_t)15)) + w * GROUP_ROWS;
+    for (int i = tid; i < (D >> 3); i += NT)
+        reinterpret_cast<u32x4*>(qs)[i] = reinterpret_cast<const u32x4*>(Q + (int64_t)q * D)[i];
+    if (tid == 0) { L.cnt = 0; L.n_qual = 0; L.thr = 0ull; }
+    __syncthreads();
+    const float ms = min_score[q];
+    const int64_t per = (n_groups + parts - 1) / parts;
+    const int64_t ga = (int64_t)p * per, gb = ga + per < n_groups ? ga + per : n_groups;
+    range_rounds(L, gb > ga ? gb - ga : 0, [&](int64_t item) { return ga + item; },
+                 [&](int64_t g) { return allow[g] & valid_bits(n_rows, g); }, C, qs, D, sc, ms, M);
+    const int c = L.cnt < RANGE_CAP ? L.cnt : RANGE_CAP;
+    range_sort_desc(L.keys, c);
+    unsigned long long* pk = part_k + ((int64_t)p * nq + q) * M;
+    for (int r = tid; r < M; r += NT) pk[r] = r < c ? L.keys[r] : 0ull;
+    if (tid == 0) part_c[(int64_t)p * nq + q] = L.n_qual;
+}
+
+// one block per query the exhaustive path answered: its parts' sorted lists merged (a part per round, its at most M <= RANGE_NT keys
+// appended, the list cut back before a round that could overflow), the counts added
+__global__ __launch_bounds__(RANGE_NT) void range_merge_kernel(const unsigned long long* __restrict__ part_k, const int32_t* __restrict__ part_c,
+                                                                int parts, int nq, int M, float* __restrict__ out_s, int64_t* __restrict__ out_i,
+                                                                int32_t* __restrict__ out_c, int64_t idx_base,
+                                                                const int32_t* __restrict__ only_if, const int* __restrict__ gate) {
+    if (gate && !*gate) return;
+    const int q = blockIdx.x, tid = threadIdx.x;
+    if (only_if && !only_if[q]) return;
+    __shared__ RangeList L;
+    if (tid == 0) { L.cnt = 0; L.n_qual = 0; L.thr = 0ull; }
+    __syncthreads();
+    int64_t total = 0;
+    for (int p = 0; p < parts; ++p) {                           // block-uniform
+        total += part_c[(int64_t)p * nq + q];
+        const int c = L.cnt;
+        __syncthreads();                                         // everyone has read cnt before anyone appends
+        if (c + M > RANGE_CAP) range_cut(L, c < RANGE_CAP ? c : RANGE_CAP, M);
+        const unsigned long long thr = L.thr;
+        if (tid < M) {
+            const unsigned long long key = part_k[((int64_t)p * nq + q) * M + tid];
+            if (key > thr) {                                     // (thr >= 0: an empty slot is never appended)
+                const int sl = atomicAdd(&L.cnt, 1);             // a slot counter: the list is read as a set
+                if (sl < RANGE_CAP) L.keys[sl] = key;
+            }
+        }
+        __syncthreads();
+    }
+    const int c = L.cnt < RANGE_CAP ? L.cnt : RANGE_CAP;
+    range_sort_desc(L.keys, c);
+    range_store(L, c, (int)(total < M + 1 ? total : M + 1), M, idx_base, out_s + (int64_t)q * M, out_i + (int64_t)q * M, out_c + q);
+}
+
+// ---- host ---------------------------------------------------------------------------------------------------------------------------------
+struct RangeWs { int64_t stats, gmax, ones, redo, part_k, part_c, total, ldg, n_groups; int parts; };
+RangeWs range_layout(int64_t n_rows, int nq, int M) {
+    RangeWs w;
+    const int qb = nq < QBATCH_MAX ? nq : QBATCH_MAX;
+    w.ldg = round_up64(qb, 64);
+    w.n_groups = (n_rows + GROUP_ROWS - 1) / GROUP_ROWS;
+    int64_t want = (n_rows + 255) / 256;
+    want = want < FILT_PARTS_MAX ? want : FILT_PARTS_MAX;
+    w.parts = (int)(want < RANGE_PART_KEYS / M ? want : RANGE_PART_KEYS / M);
+    int64_t o = 0;
+    auto take = [&](int64_t b) { int64_t r = o; o += round_up64(b, 256); return r; };
+    w.stats = take(64);                                         // at the allocation's start: masked_stats reads it
+    w.gmax = take(w.n_groups * w.ldg * 4);
+    w.ones = take(w.n_groups * 8);
+    w.redo = take((int64_t)qb * 4);
+    w.part_k = take((int64_t)w.parts * qb * M * 8);
+    w.part_c = take((int64_t)w.parts * qb * 4);
+    w.total = o;
+    return w;
+}
+}      // namespace
+
+extern "C" int64_t arx_range_workspace_bytes(int64_t n_rows, int32_t n_queries, int32_t dim, int32_t max_results) {
+    if (n_rows <= 0 || n_rows >= (1ll << 32) || n_queries <= 0 || dim <= 0 || dim % 64 != 0 || dim > 8192 || max_results <= 0 ||
+        max_results > RANGE_MAX_RESULTS)
+        return -1;
+    return range_layout(n_rows, n_queries, max_results).total;
+}
+
+extern "C" int32_t arx_range_search_tuned(const void* corpus, int64_t n_rows, const uint64_t* allow, int64_t n_allowed, const void* queries,
+                                          const float* min_score, int32_t n_queries, int32_t dim, int32_t max_results, float* out_scores,
+                                          int64_t* out_ids, int32_t* out_counts, int64_t idx_base, float max_row_norm, void* ws,
+                                          int64_t ws_bytes, int32_t path, int32_t cand_cap, void* stream) {
+    const int M = max_results;
+    ARX_REQUIRE(corpus && queries && min_score && out_scores && out_ids && out_counts && ws, "null pointer argument");
+    ARX_REQUIRE(n_rows > 0 && n_queries > 0, "empty corpus or query set");
+    ARX_REQUIRE(n_rows < (1ll << 32), "n_rows=%lld: a row is 32 bits of a sort key (at most 2^32 - 1 rows per shard)", (long long)n_rows);
+    ARX_REQUIRE(dim > 0 && dim % 64 == 0 && dim <= 8192, "dim=%d must be a multiple of 64", dim);
+    ARX_REQUIRE(M >= 1 && M <= RANGE_MAX_RESULTS, "max_results=%d out of range 1..%d", M, RANGE_MAX_RESULTS);
+    ARX_REQUIRE(n_allowed >= -1 && n_allowed <= n_rows, "n_allowed=%lld", (long long)n_allowed);
+    ARX_REQUIRE(path >= 0 && path <= 2, "path=%d: 0 (library's choice), 1 (scan) or 2 (exhaustive)", path);
+    ARX_REQUIRE(cand_cap >= 0 && cand_cap <= FILT_CAND_CAP_MAX, "cand_cap=%d out of range 0..%d", cand_cap, FILT_CAND_CAP_MAX);
+    ARX_REQUIRE(max_row_norm >= 0.0f && max_row_norm < INFINITY, "max_row_norm=%g: must be a finite bound (0 = unit rows)", (double)max_row_norm);
+    const RangeWs L = range_layout(n_rows, n_queries, M);
+    ARX_REQUIRE(ws_bytes >= L.total, "workspace too small: %lld < %lld (arx_range_workspace_bytes)", (long long)ws_bytes, (long long)L.total);
+    hipStream_t st = (hipStream_t)stream;
+    if (path == 0) path = 1;
+    if (cand_cap == 0) cand_cap = 2 * (M + 1) + FILT_CAND_CAP_DEFAULT;      // M + 1 groups reach t by definition: twice that and the masked tail's slack
+    const f16_t* C = (const f16_t*)corpus;
+    char* wsb = (char*)ws;
+    unsigned long long* stats = (unsigned long long*)(wsb + L.stats);
+    const int* gate = path == 1 ? (const int*)(stats + 2) : nullptr;      // scan: the exhaustive kernels run only after an overflow
+    float* gmax = (float*)(wsb + L.gmax);
+    int32_t* redo = (int32_t*)(wsb + L.redo);
+    unsigned long long* part_k = (unsigned long long*)(wsb + L.part_k);
+    int32_t* part_c = (int32_t*)(wsb + L.part_c);
+    const float tau_scale = (0.3125f * (float)dim + 4.0f) * 5.9604645e-8f * (max_row_norm > 0.0f ? max_row_norm : 1.0f + 1.0f / 512.0f);
+    ARX_HIP_CHECK(hipMemsetAsync(stats, 0, 64, st));
+    if (!allow) {                                               // every row: an all-ones bitmap of the call's own
+        uint64_t* ones = (uint64_t*)(wsb + L.ones);
+        range_ones_kernel<<<cdiv(L.n_groups, 256), 256, 0, st>>>(ones, L.n_groups);
+        ARX_HIP_CHECK(hipGetLastError());
+        allow = ones;
+    }
+    const RangeBitmap mask{allow};
+    const size_t smem_q = ((size_t)dim * 2 + 15) & ~(size_t)15;
+    for (int q0 = 0; q0 < n_queries; q0 += QBATCH_MAX) {
+        const int nq = (n_queries - q0) < QBATCH_MAX ? (n_queries - q0) : QBATCH_MAX;
+        const f16_t* Q = (const f16_t*)queries + (int64_t)q0 * dim;
+        const float* ms = min_score + q0;
+        float* os = out_scores + (int64_t)q0 * M;
+        int64_t* oi = out_ids + (int64_t)q0 * M;
+        int32_t* oc = out_counts + q0;
+        if (path == 1) {
+            {
+                ProfScope ps(ARX_K_SEARCH_GROUPMAX, st);
+                const int rc = nq <= 64 ? launch_masked_groupmax<64>(Q, nq, C, n_rows, dim, mask, gmax, L.ldg, st)
+                             : nq <= 128 ? launch_masked_groupmax<128>(Q, nq, C, n_rows, dim, mask, gmax, L.ldg, st)
+                                         : launch_masked_groupmax<256>(Q, nq, C, n_rows, dim, mask, gmax, L.ldg, st);
+                if (rc != ARX_OK) return rc;
+            }
+            ProfScope ps(ARX_K_SEARCH_RESCORE, st);
+            const size_t smem = smem_q + (size_t)(RANGE_NT / 64) * GROUP_ROWS * 4 + (size_t)cand_cap * 4;
+            if (smem > 32 * 1024) ARX_HIP_CHECK(arx_func_smem((const void*)range_tail_kernel, (int)smem));
+            range_tail_kernel<<<nq, RANGE_NT, smem, st>>>(gmax, L.ldg, L.n_groups, allow, Q, ms, C, n_rows, dim, M, os, oi, oc, idx_base, tau_scale,
+                                                          cand_cap, redo, stats);
+            ARX_HIP_CHECK(hipGetLastError());
+        }
+        // exhaustive over the visible rows: every query (path 2) or the queries the tail flagged (the kernels return at once if none)
+        const int32_t* only_if = path == 1 ? redo : nullptr;
+        const size_t smem_x = smem_q + (size_t)(RANGE_NT / 64) * GROUP_ROWS * 4;
+        if (smem_x > 32 * 1024) ARX_HIP_CHECK(arx_func_smem((const void*)range_exhaustive_kernel, (int)smem_x));
+        range_exhaustive_kernel<<<dim3(L.parts, nq), RANGE_NT, smem_x, st>>>(allow, Q, ms, C, n_rows, L.n_groups, dim, nq, M, part_k, part_c, only_if,
+                                                                             gate);
+        ARX_HIP_CHECK(hipGetLastError());
+        range_merge_kernel<<<nq, RANGE_NT, 0, st>>>(part_k, part_c, L.parts, nq, M, os, oi, oc, idx_base, only_if, gate);
+        ARX_HIP_CHECK(hipGetLastError());
+    }
+    return ARX_OK;
+}
+
+extern "C" int32_t arx_range_search(const void* corpus, int64_t n_rows, const uint64_t* allow, int64_t n_allowed, const void* queries,
+                                    const float* min_score, int32_t n_queries, int32_t dim, int32_t max_results, float* out_scores,
+                                    int64_t* out_ids, int32_t* out_counts, int64_t idx_base, float max_row_norm, void* ws, int64_t ws_bytes,
+                                    void* stream) {
+    return arx_range_search_tuned(corpus, n_rows, allow, n_allowed, queries, min_score, n_queries, dim, max_results, out_scores, out_ids,
+                                  out_counts, idx_base, max_row_norm, ws, ws_bytes, 0, 0, stream);
+}
+
+extern "C" int32_t arx_range_stats(const void* ws, int64_t* overflowed_queries, int64_t* candidate_groups, void* stream) {
+    return masked_stats(ws, overflowed_queries, candidate_groups, stream);
+}

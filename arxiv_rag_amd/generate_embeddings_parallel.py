@@ -662,7 +662,7 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
                    hybrid_alpha: Optional[float] = None, where=None,
                    where_document: Optional[Dict] = None, *, mmr_lambda: Optional[float] = None, mmr_fetch_k: int = 32,
                    keep_mask: Optional[np.ndarray] = None, group_by_paper: bool = False, chunks_per_paper: int = 1,
-                   where_on_device: bool = False) -> List[Dict]:
+                   where_on_device: bool = False, min_score: Optional[float] = None) -> List[Dict]:
     """Brute-force cosine top-k (config.yaml:63-64 `top_k: 10`) over the rank's fp16 rows in HBM; with
     torchrun each rank holds the contiguous row shard it encoded and the partial top-k lists are
     all-gathered over RCCL and merged.  `shard` is the `ShardSink` the encode step filled: rows [lo, hi) are already where they
@@ -702,7 +702,18 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
     `reranker`, `hybrid_alpha`, `mmr_lambda`, a per-query `where` list or more than one rank (a paper may straddle ranks).
     `where_on_device` (False = nothing changes; needs `where`): the `where` filters are evaluated on the device from metadata columns
     uploaded once (`where_device.MetadataColumns` over this rank's `chunks`), `keep_mask` and `where_document` and-ed in by the same
-    kernel, a per-query list in one launch per 64 distinct filters.  Same hits as without it."""
+    kernel, a per-query list in one launch per 64 distinct filters.  Same hits as without it.
+    `min_score` (a float; None = nothing changes): a score threshold (INTEGRATION.md "Score threshold").  Only chunks whose cosine to the
+    query is >= it are returned, the best `top_k` of them, `top_k` then in 1..1024 (`ShardIndex.search_range`), `where` /
+    `where_document` / `keep_mask` applied as without it; every entry of the results then carries `truncated`: more chunks qualified than
+    `top_k`.  Not together with `reranker`, `hybrid_alpha`, `mmr_lambda`, `group_by_paper`, a per-query `where` list or more than one
+    rank (reranking and a cross-rank merge of long lists are out of scope here)."""
+    if min_score is not None:
+        from .ranging import check_range_query
+        if reranker is not None:
+            raise ValueError("min_score cannot be combined with reranker here: reranking a long range list is out of scope for search_queries")
+        check_range_query(top_k, ranged=True, hybrid_alpha=hybrid_alpha, mmr_lambda=mmr_lambda, group_by=group_by_paper,
+                          per_query_filters=isinstance(where, (list, tuple)), world=int(os.environ.get("WORLD_SIZE", "1")))
     if where_on_device and where is None:
         raise ValueError("where_on_device needs where: it chooses where the where filters are evaluated")
     if group_by_paper:
@@ -786,9 +797,16 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
             raise ValueError(f"group_by_paper: {len(chunks)} chunks for the shard's {shard.rows.shape[0]} rows")
         group_of, paper_ids = runs_from_keys([(c.get("metadata") or {}).get("paper_id") for c in chunks], base=chunk_base)
         pre = None                                           # a grouped search runs on the fp16 rows
+    if min_score is not None:
+        pre = None                                           # a range search runs on the fp16 rows
     index = ShardIndex(shard.rows, idx_base=shard.lo, prefilter=pre, adaptive=True)
-    grp = None
-    if group_by_paper:
+    grp = truncated = None
+    if min_score is not None:
+        if world > 1:
+            raise ValueError("min_score needs a single GPU rank: a cross-rank merge of lists of up to 1024 rows is out of scope")
+        s, i, counts = index.search_range(qd, float(min_score), top_k, allow=allow, n_allowed=n_allowed)
+        truncated = (counts > top_k).cpu().tolist()
+    elif group_by_paper:
         if world > 1:
             raise ValueError("group_by_paper needs a single GPU rank: a paper may straddle two ranks, and a cross-rank fold is out of scope")
         index.set_groups(group_of)
@@ -885,7 +903,7 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
                 continue
             hits.append({"rank": r + 1, "score": float(s[qi, r]), "index": j, "chunk_id": names.get(j, f"chunk_{j}"),
                          **hybrid_fields(qi, r), **({} if mmr_val is None else {"mmr_score": float(mmr_val[qi, r])})})
-        results.append({"query": text, "results": hits})
+        results.append({"query": text, "results": hits, **({} if truncated is None else {"truncated": bool(truncated[qi])})})
     if rank == 0:
         with open(Path(output_dir) / "search_results.json", "w", encoding="utf-8") as fh:
             json.dump(results, fh, indent=2, ensure_ascii=False)
@@ -950,6 +968,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help="Grouped results for --queries: --top-k counts PAPERS (consecutive chunks with equal paper_id), the exact best "
                         "by their best chunk, each with its --chunks-per-paper best chunks (one GPU rank only; not with --rerank-model, "
                         "--hybrid-alpha, --mmr-lambda or --where-file)")
+    p.add_argument("--min-score", type=float, default=None,
+                   help="Score threshold for --queries: only chunks whose cosine to the query is at least this are returned, the best "
+                        "--top-k of them, --top-k then in 1..1024; every query's entry carries `truncated` (default: off; one GPU rank "
+                        "only; not with --rerank-model, --hybrid-alpha, --mmr-lambda, --group-by-paper or --where-file)")
     p.add_argument("--chunks-per-paper", type=int, default=1,
                    help="Chunks returned for each paper of --group-by-paper (default: 1; at most 8)")
     return p
@@ -1060,6 +1082,36 @@ def check_group_args(args) -> Optional[str]:
     return None
 
 
+RANGE_MAX_TOP_K = 1024     # arx_range_search: rows per query
+
+
+def check_range_args(args) -> Optional[str]:
+    """-> an error message for an unusable --min-score, else None.  (The other flags are read with getattr: absent = off.)"""
+    min_score = getattr(args, "min_score", None)
+    if min_score is None:
+        return None
+    if min_score != min_score:
+        return f"--min-score {min_score}: the threshold must be a number (use -inf for \"every chunk\")"
+    if not getattr(args, "queries", None):
+        return "--min-score needs --queries: it is a threshold on the results of the search step"
+    if getattr(args, "rerank_model", None):
+        return "--min-score cannot be combined with --rerank-model: reranking a long range list is out of scope for the CLI"
+    if getattr(args, "hybrid_alpha", None) is not None:
+        return "--min-score cannot be combined with --hybrid-alpha: the BM25 keyword search has no score threshold"
+    if getattr(args, "mmr_lambda", None) is not None:
+        return "--min-score cannot be combined with --mmr-lambda: MMR picks among at most 32 candidates of the top-k search"
+    if getattr(args, "group_by_paper", False):
+        return "--min-score cannot be combined with --group-by-paper: the grouped search ranks papers, not chunks above a threshold"
+    if getattr(args, "where_file", None) is not None:
+        return "--min-score cannot be combined with --where-file: the range search takes one filter per call"
+    top_k = getattr(args, "top_k", 10)
+    if not (1 <= top_k <= RANGE_MAX_TOP_K):
+        return f"--top-k {top_k}: with --min-score the search returns between 1 and {RANGE_MAX_TOP_K} chunks per query"
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        return "--min-score needs a single GPU rank: a cross-rank merge of lists of up to 1024 rows is out of scope"
+    return None
+
+
 def check_where_args(args) -> Optional[str]:
     """-> an error message for an unusable --where, else None.  On success `args.where_filter` holds the parsed filter (None without --where)."""
     args.where_filter = None
@@ -1158,7 +1210,7 @@ def main(argv: Optional[Sequence[str]] = None, model_factory: Optional[Callable]
     args = build_parser().parse_args(argv)
     err = (check_rerank_args(args) or check_hybrid_args(args) or check_where_args(args) or check_where_file_args(args) or check_where_device_args(args)
            or check_where_document_args(args)
-           or check_mmr_args(args) or check_dedup_args(args) or check_group_args(args))
+           or check_mmr_args(args) or check_dedup_args(args) or check_group_args(args) or check_range_args(args))
     if err:
         print(f"Error: {err}")
         return 2
@@ -1256,7 +1308,8 @@ def main(argv: Optional[Sequence[str]] = None, model_factory: Optional[Callable]
                                where=args.where_filters if args.where_filters is not None else args.where_filter, where_document=args.where_document_filter,
                                mmr_lambda=args.mmr_lambda, mmr_fetch_k=args.mmr_fetch_k, keep_mask=keep_mask,
                                **({"group_by_paper": True, "chunks_per_paper": args.chunks_per_paper} if args.group_by_paper else {}),
-                               **({"where_on_device": True} if args.where_on_device else {}))
+                               **({"where_on_device": True} if args.where_on_device else {}),
+                               **({"min_score": args.min_score} if args.min_score is not None else {}))
         store_time = 0.0
         if rank == 0 and not args.skip_chroma:
             try:

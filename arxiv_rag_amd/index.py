@@ -408,6 +408,63 @@ class ShardIndex:
         `search_grouped` on this index (or on `ws`).  Synchronises on the current stream."""
         return self._masked_stats("grouped", self.lib.arx_topk_grouped_stats, ws)
 
+    # ---- score threshold: every row at or above a cosine, up to 1 024 per query ---------------------------------------------
+    def search_range(self, queries_f16: torch.Tensor, min_score, max_results: int, allow: Optional[torch.Tensor] = None, n_allowed: int = -1,
+                     ws: Optional[torch.Tensor] = None, path: int = 0, cand_cap: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """queries fp16 [Q, D] (device) -> (scores f32 [Q, M], ids int64 [Q, M], counts int32 [Q]) on the device, M = `max_results` in
+        1..1024 (`arx_range_search`).  `min_score`: a float, or one per query (a tensor on the host or the device, or anything numpy
+        converts).  A visible row qualifies when its score is >= the query's threshold, compared in f32 (-inf: every visible row; +inf or
+        NaN: none); the best min(count, M) qualifying rows come by (score desc, row asc), ids = local row + idx_base, (-inf, -1) pads.
+        `counts[q]` is the number of qualifying rows when that is <= M and exactly M + 1 when more qualify: the list then holds the best
+        M (an exact total above M is not offered: it would cost a full exact scan).  A (query, row) score has the bits `search` gives
+        it.  `allow` / `n_allowed` as for `search(allow=...)`, None = every row.  Runs on the fp16 rows: the int8 index plays no part.
+        Test hooks: `path` (1 = scan, 2 = exhaustive) and `cand_cap`; `range_stats` reads the counters."""
+        q, M = queries_f16, int(max_results)
+        assert q.is_cuda and q.dtype == torch.float16 and q.dim() == 2 and q.shape[1] == self.dim and q.is_contiguous()
+        nq = q.shape[0]
+        if torch.is_tensor(min_score):
+            ms = min_score.to(device=q.device, dtype=torch.float32)
+        else:
+            import numpy as np
+            ms = torch.from_numpy(np.asarray(min_score, dtype=np.float32)).to(q.device)
+        if ms.dim() == 0:
+            ms = ms.expand(nq)
+        if ms.shape != (nq,):
+            raise ValueError(f"min_score has shape {tuple(ms.shape)}: a float or one entry per query ({nq},)")
+        ms = ms.contiguous()
+        if allow is not None:
+            n_words = (self.n_rows + 63) // 64
+            assert allow.is_cuda and allow.dtype in (torch.int64, torch.uint64) and allow.dim() == 1 and allow.is_contiguous()
+            assert allow.shape[0] == n_words, f"allow has {allow.shape[0]} words, the shard's {self.n_rows} rows need {n_words}"
+        need = self.lib.arx_range_workspace_bytes(max(self.n_rows, 1), max(nq, 1), self.dim, M)
+        if need < 0:
+            raise _lib.ArxError(f"unsupported range search shape n_rows={self.n_rows} nq={nq} dim={self.dim} max_results={M}")
+        scores = torch.empty((nq, M), dtype=torch.float32, device=q.device)
+        ids = torch.empty((nq, M), dtype=torch.int64, device=q.device)
+        counts = torch.empty((nq,), dtype=torch.int32, device=q.device)
+        if nq == 0:
+            return scores, ids, counts
+        if self.n_rows == 0:
+            scores.fill_(float("-inf")); ids.fill_(-1); counts.zero_()
+            return scores, ids, counts
+        if ws is None:
+            ws = self._ws_masked.get("range")
+            if ws is None or ws.numel() < need:
+                ws = self._ws_masked["range"] = torch.empty(need, dtype=torch.uint8, device=self.corpus.device)
+        norm = max(self.max_row_norm(), 1.0 + 1.0 / 512.0)       # never below the encoder's unit-row bound (as `_options`)
+        rc = self.lib.arx_range_search_tuned(self.corpus.data_ptr(), self.n_rows, None if allow is None else allow.data_ptr(),
+                                             -1 if n_allowed is None else int(n_allowed), q.data_ptr(), ms.data_ptr(), nq, self.dim, M,
+                                             scores.data_ptr(), ids.data_ptr(), counts.data_ptr(), self.idx_base, norm, ws.data_ptr(),
+                                             ws.numel(), int(path), int(cand_cap), torch.cuda.current_stream().cuda_stream)
+        _lib.check(rc, "arx_range_search")
+        self._last_ws_masked["range"] = ws
+        return scores, ids, counts
+
+    def range_stats(self, ws: Optional[torch.Tensor] = None) -> Tuple[int, int]:
+        """(queries whose candidate list overflowed and were answered by the exhaustive path, candidate groups rescored) of the LAST
+        `search_range` on this index (or on `ws`).  Synchronises on the current stream."""
+        return self._masked_stats("range", self.lib.arx_range_stats, ws)
+
     def _i8_nq_limit(self) -> int:
         """The largest query batch the int8 pass takes under this index's policy (`i8_max_queries`; None = the library default, 1 024)."""
         if self.i8_max_queries is None:

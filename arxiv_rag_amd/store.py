@@ -266,7 +266,7 @@ class HipCollection:
 
     def query(self, query_embeddings=None, query_texts: Optional[Sequence[str]] = None, n_results: int = 10, reranker=None,
               n_candidates: int = 32, hybrid_alpha: Optional[float] = None, where=None, where_document=None,
-              mmr_lambda: Optional[float] = None, group_by=None, chunks_per_group: int = 1) -> Dict:
+              mmr_lambda: Optional[float] = None, group_by=None, chunks_per_group: int = 1, min_score=None) -> Dict:
         """`reranker` (a `rerank.HipCrossEncoder`; needs `query_texts`): the search fetches `n_candidates` (<= 32) rows per query,
         the cross-encoder scores (query, document) for each, and the best `n_results` come back in reranked order with an added
         `rerank_scores` list per query (`scores` / `distances` stay the cosine ones).
@@ -308,10 +308,23 @@ class HipCollection:
         by paper, best paper first and within a paper the best chunk first; added `group_keys` holds the papers' keys per query and
         `group_sizes` the chunks returned for each.  Composes with a single `where`, `where_document` and the dedup keep-bitmap (one
         bitmap per call).  ValueError with `reranker`, `hybrid_alpha`, `mmr_lambda`, per-query filter lists, `world > 1` (a paper may
-        straddle ranks) or a collection built without `group_key`."""
+        straddle ranks) or a collection built without `group_key`.
+        `min_score` (a float or one float per query; None = nothing changes): a score threshold (INTEGRATION.md "Score threshold").  Every
+        row whose cosine to the query is >= its threshold, compared in f32, qualifies (-inf: every row; +inf or NaN: none), and the best
+        `n_results` qualifying rows come back, `n_results` then in 1..1024 (`ShardIndex.search_range`).  The usual lists have their
+        natural, variable lengths, and an added `truncated` list holds one bool per query: True when more rows qualified than the
+        search was asked for (how many more is not known: counting them would cost a full exact scan).  Composes with a single `where`,
+        `where_document` and the dedup keep-bitmap (one bitmap per call), and with `reranker`: `n_candidates` may then be up to 1024, the
+        cross-encoder receives the range list (`truncated` refers to it) and scores its pairs in batches of at most 32, so
+        `min_score=float("-inf"), n_candidates=50` is "re-rank the top 50".  ValueError with `hybrid_alpha`, `mmr_lambda`, `group_by`,
+        per-query filter lists and `world > 1` (a cross-rank merge of long lists is out of scope)."""
         import torch
         from .filter_sets import is_per_query
         from .grouping import check_grouped_query
+        from .ranging import RERANK_BATCH, check_range_query, thresholds
+        check_range_query(n_results, ranged=min_score is not None, reranker=reranker, n_candidates=n_candidates, hybrid_alpha=hybrid_alpha,
+                          mmr_lambda=mmr_lambda, group_by=group_by, per_query_filters=is_per_query(where) or is_per_query(where_document),
+                          world=getattr(self, "world", 1))
         check_grouped_query(n_results, chunks_per_group, grouped=bool(group_by), has_group_key=getattr(self, "group_key", None) is not None,
                             reranker=reranker, hybrid_alpha=hybrid_alpha, mmr_lambda=mmr_lambda,
                             per_query_filters=is_per_query(where) or is_per_query(where_document), world=getattr(self, "world", 1))
@@ -349,7 +362,7 @@ class HipCollection:
         if reranker is not None:
             if query_texts is None:
                 raise ValueError("reranking needs query_texts")
-            if not (n_results <= n_candidates <= 32):
+            if min_score is None and not (n_results <= n_candidates <= 32):
                 raise ValueError(f"n_candidates={n_candidates} must be in [n_results, 32] (the search's k limit)")
         if query_embeddings is None:
             if query_texts is None or self.encoder is None:
@@ -359,8 +372,13 @@ class HipCollection:
         if q.dim() == 1:
             q = q[None]
         wide = reranker is not None or hybrid_alpha is not None or mmr_lambda is not None
-        grp = None
-        if group_by:
+        grp = truncated = None
+        if min_score is not None:
+            allow, n_allowed = self._allow_of(where, doc_tree if where_document is not None else None, q.device)
+            s, i, counts = self.index.search_range(q, thresholds(min_score, q.shape[0]), n_candidates if reranker is not None else n_results,
+                                                   allow=allow, n_allowed=n_allowed)
+            truncated = (counts > s.shape[1]).cpu().tolist()
+        elif group_by:
             allow, n_allowed = self._allow_of(where, doc_tree if where_document is not None else None, q.device)
             s, i, grp = self.index.search_grouped(q, n_results, chunks_per_group, allow=allow, n_allowed=n_allowed)
             grp = grp.cpu().numpy()
@@ -389,7 +407,8 @@ class HipCollection:
         if reranker is not None:
             from .rerank import rerank_candidates, reorder_by_rerank
             texts = {int(j): self.metadata[int(j)].get("text") or "" for j in np.unique(i) if j >= 0}
-            sc = rerank_candidates(lambda pairs: reranker.predict(pairs, batch_size=n_candidates, convert_to_numpy=True),
+            sc = rerank_candidates(lambda pairs: reranker.predict(pairs, batch_size=n_candidates if min_score is None else min(n_candidates, RERANK_BATCH),
+                                                                convert_to_numpy=True),
                                    list(query_texts), i, texts)
             picked = reorder_by_rerank(i, sc, n_results)
             width = max([len(p) for p in picked] + [1])
@@ -416,6 +435,8 @@ class HipCollection:
         if grp is not None:
             out["group_keys"] = [[self.group_keys[int(v)] for v in grp[qi] if v >= 0] for qi in range(q.shape[0])]
             out["group_sizes"] = [[int(n) for n, v in zip(sizes[qi], grp[qi]) if v >= 0] for qi in range(q.shape[0])]
+        if truncated is not None:
+            out["truncated"] = truncated
         if mmr_val is not None:
             out["mmr_scores"] = [mmr_val[qi][i[qi] >= 0].tolist() for qi in range(q.shape[0])]
         if reranker is not None:

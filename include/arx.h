@@ -413,6 +413,42 @@ int32_t arx_topk_grouped_stats(const void* ws, int64_t* overflowed_queries, int6
  * max_row_norm wants. */
 int32_t arx_group_runs_info(const int32_t* group_of, int64_t n_rows, int64_t* out, void* stream);
 
+/* ---- Score threshold (`min_score`): every row at or above a cosine, up to 1 024 exact rows per query (csrc/range.hip) ------------------
+ * min_score: device f32 [n_queries], one threshold per query.  allow: a row bitmap in the convention of arx_topk_search_filtered, NULL =
+ * every row; n_allowed as there (-1 = unknown).  For query q a visible row r QUALIFIES when score(q, r) >= min_score[q], compared in
+ * f32; score(q, r) has the bits arx_topk_search and arx_topk_search_filtered give the pair.  min_score[q] = -inf: every visible row
+ * qualifies; +inf or NaN: none does.  The answer is the best min(count, M) qualifying rows by (score desc, row asc), M = max_results,
+ * 1 <= M <= 1024:
+ *   out_scores f32 [n_queries, M], out_ids int64 [n_queries, M] = idx_base + row, (-inf, -1) padding;
+ *   out_counts int32 [n_queries] = the number of qualifying rows when that is <= M, and exactly M + 1 when more than M rows qualify.
+ * M + 1 means "the list is truncated: it holds the best M".  An exact total above M is deliberately not offered: it would make a loose
+ * threshold cost a full exact scan of the shard.  Every element of the three outputs is written.
+ * A query's outputs depend on the query, its threshold, the bitmap and the corpus alone - not on the batch, its order, the path or
+ * cand_cap.  dim % 64 == 0, 64 .. 8192; any n_queries (sliced above 1 024); n_rows < 2^32 (a row is 32 bits of a sort key; a larger
+ * shard: ARX_ERR_ARG naming n_rows).  max_row_norm as for the filtered search, 0 = unit rows.  Two device paths with the same bits: the
+ * scan (pass A of the filtered search, then a tail that rescores the groups a proved bound selects; the proof is in csrc/range.hip) and
+ * the exhaustive scoring of every visible row, which also answers any query whose candidate list overflows.
+ * A null pointer, max_results outside 1 .. 1024, dim % 64 != 0 or a non-finite max_row_norm: ARX_ERR_ARG before any launch, the message
+ * naming the field and its value.
+ * ws: device workspace of arx_range_workspace_bytes(...) bytes, caller-owned; with qb = min(n_queries, 1 024), ldg = qb rounded up to 64,
+ * G = ceil(n_rows / 64), M = max_results and T = min(ceil(n_rows / 256), 128, floor(4096 / M)) it is the sum, each term rounded up to 256
+ * bytes, of 64 + 4 G ldg + 8 G + 4 qb + 8 T qb M + 4 T qb (-1 for an unsupported shape: n_rows outside 1 .. 2^32 - 1, n_queries < 1,
+ * dim not a multiple of 64 in 64 .. 8192, max_results outside 1 .. 1024). */
+int64_t arx_range_workspace_bytes(int64_t n_rows, int32_t n_queries, int32_t dim, int32_t max_results);
+int32_t arx_range_search(const void* corpus, int64_t n_rows, const uint64_t* allow, int64_t n_allowed, const void* queries,
+                         const float* min_score, int32_t n_queries, int32_t dim, int32_t max_results, float* out_scores, int64_t* out_ids,
+                         int32_t* out_counts, int64_t idx_base, float max_row_norm, void* ws, int64_t ws_bytes, void* stream);
+/* The same with the path and the candidate capacity chosen by the caller (tests, tuning): path 0 = library's choice, 1 = the scan,
+ * 2 = exhaustive over the visible rows; cand_cap = candidate groups a query may list before it goes to the exhaustive path (0 =
+ * default 2 (max_results + 1) + 1 024, at most 8192).  Same bits for every choice. */
+int32_t arx_range_search_tuned(const void* corpus, int64_t n_rows, const uint64_t* allow, int64_t n_allowed, const void* queries,
+                               const float* min_score, int32_t n_queries, int32_t dim, int32_t max_results, float* out_scores,
+                               int64_t* out_ids, int32_t* out_counts, int64_t idx_base, float max_row_norm, void* ws, int64_t ws_bytes,
+                               int32_t path, int32_t cand_cap, void* stream);
+/* {queries sent to the exhaustive path because their candidate list overflowed, candidate groups rescored} of the LAST range search on
+ * this workspace.  Copies 16 bytes to the host and waits on `stream`. */
+int32_t arx_range_stats(const void* ws, int64_t* overflowed_queries, int64_t* candidate_groups, void* stream);
+
 /* ---- Substring scan over the chunk texts (Chroma's `where_document`: `$contains` / `$not_contains`) -----------------------------
  * The producer of the row bitmaps arx_topk_search_filtered takes (csrc/textscan.hip).
  * out_bits[p][w] bit (r & 63) of word w = r >> 6  <=>  pattern p occurs in row r, entirely inside

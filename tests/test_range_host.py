@@ -1,0 +1,196 @@
+"""Host side of the score-threshold search (CPU): the C ABI's four new symbols, the workspace formula of include/arx.h and its -1 cases,
+every argument error of the C call before any launch, the refusals of `HipCollection.query(min_score=...)`, of
+`search_queries(min_score=...)` and of the CLI's --min-score checks, and the existing checks left as they were without the flag."""
+import argparse
+import ctypes
+import re
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+from arxiv_rag_amd.ranging import check_range_query, thresholds
+
+ROOT = Path(__file__).resolve().parents[1]
+NEW = {"arx_range_workspace_bytes", "arx_range_search", "arx_range_search_tuned", "arx_range_stats"}
+
+
+def test_library_exports_the_range_search_and_header_and_bindings_agree():
+    from arxiv_rag_amd import _lib
+    hdr = (ROOT / "include" / "arx.h").read_text()
+    declared = set(re.findall(r"\b(arx_[a-z0-9_]+)\s*\(", hdr))
+    assert NEW <= declared and NEW <= set(_lib.EXPORTS)
+    assert declared == set(_lib.EXPORTS), declared ^ set(_lib.EXPORTS)
+    assert _lib.LIB_PATH.exists(), "libarx_hip.so not built (run __graft_entry__.build())"
+    lib = ctypes.CDLL(str(_lib.LIB_PATH))
+    for name in NEW:
+        assert hasattr(lib, name), name
+    assert len(_lib.EXPORTS["arx_range_search"][1]) == 17 and len(_lib.EXPORTS["arx_range_search_tuned"][1]) == 19
+    assert _lib.load().arx_version() == 112                    # purely additive
+    assert "Score threshold (`min_score`)" in hdr and "Score threshold (`min_score`)" in (ROOT / "INTEGRATION.md").read_text()
+
+
+def test_workspace_formula_of_the_header_and_the_unsupported_shapes():
+    from arxiv_rag_amd import _lib
+    f = _lib.load().arx_range_workspace_bytes
+
+    def formula(n, nq, M):
+        qb = min(nq, 1024); ldg = (qb + 63) // 64 * 64; G = (n + 63) // 64; T = min((n + 255) // 256, 128, 4096 // M)
+        return sum((b + 255) // 256 * 256 for b in (64, 4 * G * ldg, 8 * G, 4 * qb, 8 * T * qb * M, 4 * T * qb))
+    for n, nq, M in ((1000, 64, 10), (1, 1, 1), (12805, 1100, 1024), (1 << 20, 64, 50), (1 << 20, 1, 32), (2200, 1100, 33)):
+        assert f(n, nq, 768, M) == formula(n, nq, M), (n, nq, M)
+    assert f(1000, 5000, 64, 32) == f(1000, 1024, 64, 32)      # internal batches of at most 1 024 queries
+    for bad in ((1000, 64, 768, 0), (1000, 64, 768, 1025), (1000, 64, 100, 10), (1000, 64, 0, 10), (1000, 64, 8256, 10), (0, 1, 64, 1),
+                (1000, 0, 64, 1), (1 << 32, 1, 64, 1)):
+        assert f(*bad) == -1, bad
+    assert f((1 << 32) - 1, 1, 64, 1) > 0
+
+
+def test_every_argument_error_is_refused_before_any_launch_with_the_field_named():
+    """Nothing is launched: the pointers are never followed and the stream is null."""
+    from arxiv_rag_amd import _lib
+    lib = _lib.load()
+    one = ctypes.c_void_p(16)
+    big = 1 << 40
+
+    def call(corpus=one, n_rows=1000, allow=None, n_allowed=-1, queries=one, min_score=one, nq=4, dim=128, M=50, out_s=one, out_i=one,
+             out_c=one, idx_base=0, norm=0.0, ws=one, ws_bytes=big, path=0, cand_cap=0, tuned=True):
+        head = (corpus, n_rows, allow, n_allowed, queries, min_score, nq, dim, M, out_s, out_i, out_c, idx_base, norm, ws, ws_bytes)
+        rc = lib.arx_range_search_tuned(*head, path, cand_cap, None) if tuned else lib.arx_range_search(*head, None)
+        return rc, lib.arx_last_error().decode()
+    for kw in (dict(corpus=None), dict(queries=None), dict(min_score=None), dict(out_s=None), dict(out_i=None), dict(out_c=None), dict(ws=None)):
+        for tuned in (True, False):
+            rc, msg = call(tuned=tuned, **kw)
+            assert rc == -1 and "null pointer" in msg, (kw, msg)
+    for kw, text in ((dict(M=0), "max_results=0"), (dict(M=1025), "max_results=1025"), (dict(M=-3), "max_results=-3"), (dict(dim=100), "dim=100"),
+                     (dict(dim=0), "dim=0"), (dict(dim=8256), "dim=8256"), (dict(norm=float("inf")), "max_row_norm=inf"),
+                     (dict(norm=float("nan")), "max_row_norm=nan"), (dict(norm=-1.0), "max_row_norm=-1"), (dict(n_rows=1 << 32), "n_rows=4294967296"),
+                     (dict(n_rows=0), "empty"), (dict(nq=0), "empty"), (dict(n_allowed=1001), "n_allowed=1001"), (dict(path=3), "path=3"),
+                     (dict(cand_cap=8193), "cand_cap=8193"), (dict(cand_cap=-1), "cand_cap=-1"), (dict(ws_bytes=64), "workspace too small")):
+        rc, msg = call(**kw)
+        assert rc == -1 and text in msg, (kw, msg)
+    rc, msg = call(tuned=False, M=1025)
+    assert rc == -1 and "max_results=1025" in msg
+    a, b = ctypes.c_int64(0), ctypes.c_int64(0)
+    assert lib.arx_range_stats(None, ctypes.byref(a), ctypes.byref(b), None) == -1 and "null pointer" in lib.arx_last_error().decode()
+
+
+def test_thresholds_take_a_float_or_one_per_query():
+    assert thresholds(0.7, 3).tolist() == [np.float32(0.7)] * 3 and thresholds(0.7, 3).dtype == np.float32
+    assert np.isneginf(thresholds(float("-inf"), 2)).all()
+    assert thresholds([0.1, 0.2], 2).tolist() == [np.float32(0.1), np.float32(0.2)]
+    with pytest.raises(ValueError, match="min_score has shape"):
+        thresholds([0.1, 0.2], 3)
+
+
+def test_check_range_query_is_silent_without_min_score():
+    check_range_query(100000, ranged=False, reranker=object(), n_candidates=5, hybrid_alpha=0.5, mmr_lambda=0.5, group_by=True,
+                      per_query_filters=True, world=8)
+
+
+def _collection_without_a_device(**attrs):
+    from arxiv_rag_amd.store import HipCollection
+    coll = object.__new__(HipCollection)
+    coll.group_key, coll.world, coll._keep, coll.documents = "paper_id", 1, None, None
+    for k, v in attrs.items():
+        setattr(coll, k, v)
+    return coll
+
+
+def test_query_refuses_what_min_score_does_not_compose_with():
+    q = np.zeros((2, 64), np.float16)
+    coll = _collection_without_a_device()
+    for kw, text in ((dict(hybrid_alpha=0.5, query_texts=["a", "b"]), "hybrid_alpha"), (dict(mmr_lambda=0.5), "mmr_lambda"),
+                     (dict(group_by=True), "group_by"), (dict(where=[{"a": 1}, None]), "per-query filter lists"),
+                     (dict(where_document=[{"$contains": "a"}, None]), "per-query filter lists"), (dict(n_results=1025), "n_results=1025"),
+                     (dict(n_results=0), "n_results=0"),
+                     (dict(reranker=object(), query_texts=["a", "b"], n_results=10, n_candidates=1025), "n_candidates=1025"),
+                     (dict(reranker=object(), query_texts=["a", "b"], n_results=10, n_candidates=5), "n_candidates=5")):
+        with pytest.raises(ValueError) as e:
+            coll.query(query_embeddings=q, min_score=0.5, **kw)
+        assert text in str(e.value) and "min_score" in str(e.value), (kw, str(e.value))
+    with pytest.raises(ValueError, match="min_score needs world == 1"):
+        _collection_without_a_device(world=2).query(query_embeddings=q, min_score=0.5)
+    # without min_score the limits are the old ones
+    with pytest.raises(ValueError, match=r"n_candidates=50 must be in \[n_results, 32\]"):
+        coll.query(query_embeddings=q, query_texts=["a", "b"], reranker=object(), n_candidates=50)
+
+
+def test_search_queries_refuses_the_same(monkeypatch):
+    from arxiv_rag_amd import generate_embeddings_parallel as GEN
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    for kw, text in ((dict(reranker=object()), "reranker"), (dict(hybrid_alpha=0.5), "hybrid_alpha"), (dict(mmr_lambda=0.5), "mmr_lambda"),
+                     (dict(group_by_paper=True), "group_by"), (dict(where=[{"a": 1}]), "per-query filter lists"), (dict(top_k=1025), "n_results=1025"),
+                     (dict(top_k=0), "n_results=0")):
+        with pytest.raises(ValueError) as e:
+            GEN.search_queries(None, [], None, ["q"], min_score=0.5, **kw)
+        assert text in str(e.value) and "min_score" in str(e.value), (kw, str(e.value))
+    monkeypatch.setenv("WORLD_SIZE", "2")
+    with pytest.raises(ValueError, match="min_score needs world == 1"):
+        GEN.search_queries(None, [], None, ["q"], min_score=0.5)
+
+
+def _boom(name):
+    raise AssertionError("the model must not be loaded")
+
+
+def test_cli_min_score_is_off_by_default_and_checked_before_any_model_is_loaded(tmp_path, capsys, monkeypatch):
+    from arxiv_rag_amd import generate_embeddings_parallel as GEN
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    args = GEN.build_parser().parse_args(["in"])
+    assert args.min_score is None and GEN.check_range_args(args) is None
+    args = GEN.build_parser().parse_args(["in", "--queries", "q.txt", "--min-score", "0.7", "--top-k", "50"])
+    assert args.min_score == 0.7 and args.top_k == 50 and GEN.check_range_args(args) is None
+    args = GEN.build_parser().parse_args(["in", "--queries", "q.txt", "--min-score=-inf", "--top-k", "1024"])
+    assert args.min_score == float("-inf") and GEN.check_range_args(args) is None
+    # partial namespaces, as other tests build them: absent flags are off
+    assert GEN.check_range_args(argparse.Namespace()) is None
+    assert GEN.check_range_args(argparse.Namespace(min_score=0.5, queries="q.txt")) is None
+    assert "--queries" in GEN.check_range_args(argparse.Namespace(min_score=0.5))
+    (tmp_path / "in").mkdir()
+    (tmp_path / "w.jsonl").write_text("null\n")
+    (tmp_path / "q.txt").write_text("one query\n")
+    q = ["--queries", str(tmp_path / "q.txt"), "--min-score", "0.5"]
+    for extra, msg in ((["--min-score", "0.5"], "needs --queries"),
+                       (q + ["--rerank-model", "x"], "--rerank-model"),
+                       (q + ["--hybrid-alpha", "0.7"], "--hybrid-alpha"),
+                       (q + ["--mmr-lambda", "0.5"], "--mmr-lambda"),
+                       (q + ["--group-by-paper"], "--group-by-paper"),
+                       (q + ["--where-file", str(tmp_path / "w.jsonl")], "--where-file"),
+                       (q + ["--top-k", "1025"], "--top-k 1025"),
+                       (q + ["--top-k", "0"], "--top-k 0"),
+                       (["--queries", str(tmp_path / "q.txt"), "--min-score", "nan"], "--min-score nan")):
+        rc = GEN.main([str(tmp_path / "in"), "--skip-chroma"] + extra, model_factory=_boom)
+        out = capsys.readouterr().out
+        assert rc == 2 and msg in out and "--min-score" in out, (extra, out)
+    monkeypatch.setenv("WORLD_SIZE", "2")
+    assert GEN.main([str(tmp_path / "in"), "--skip-chroma"] + q, model_factory=_boom) == 2
+    assert "single GPU rank" in capsys.readouterr().out
+
+
+def test_existing_checks_are_unaffected_without_the_flag(monkeypatch):
+    """Every check_*_args gives what it gave: on the parser's defaults, and on the refusals that pin the k <= 32 limits."""
+    from arxiv_rag_amd import generate_embeddings_parallel as GEN
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    P = GEN.build_parser()
+    checks = (GEN.check_rerank_args, GEN.check_hybrid_args, GEN.check_where_args, GEN.check_where_file_args, GEN.check_where_device_args,
+              GEN.check_where_document_args, GEN.check_mmr_args, GEN.check_dedup_args, GEN.check_group_args, GEN.check_range_args)
+    assert all(c(P.parse_args(["in"])) is None for c in checks)
+    assert "at most k <= 32" in GEN.check_rerank_args(P.parse_args(["in", "--rerank-model", "x", "--rerank-top-k", "50"]))
+    assert "--top-k 33" in GEN.check_hybrid_args(P.parse_args(["in", "--hybrid-alpha", "0.5", "--top-k", "33"]))
+    assert "--mmr-fetch-k 33" in GEN.check_mmr_args(P.parse_args(["in", "--mmr-lambda", "0.5", "--mmr-fetch-k", "33"]))
+    assert "--top-k 33" in GEN.check_group_args(P.parse_args(["in", "--queries", "q", "--group-by-paper", "--top-k", "33"]))
+
+
+def test_range_kernels_do_not_spill_or_use_scratch():
+    """What csrc/build.sh recorded for range.hip (as tests/test_build_resources.py reads it for every object)."""
+    from tests.test_build_resources import BUILD, PAT
+    f = BUILD / "range.resources.txt"
+    if not f.exists():
+        pytest.skip("no _build/range.resources.txt (library not built by csrc/build.sh in this tree)")
+    ks = {m.group(1): (int(m.group(4)), int(m.group(7))) for m in PAT.finditer(f.read_text())}
+    for name in ("masked_groupmax_kernel", "range_tail_kernel", "range_exhaustive_kernel", "range_merge_kernel", "range_ones_kernel"):
+        assert any(name in k for k in ks), name
+    assert sum("masked_groupmax_kernel" in k for k in ks) == 3        # 64-, 128- and 256-query tiles
+    bad = {k: v for k, v in ks.items() if v[0] or v[1]}
+    assert not bad, bad

@@ -16,6 +16,15 @@
 // current n-th best are appended to an LDS list (an INTEGER LDS atomic hands out the slots: the list's order varies, its content and
 // therefore the selected top-n do not); when the list could overflow it is cut back to its n largest keys.  Every block writes one
 // partial list [blocks, nq, n]; arx_topk_merge reduces them (blocks * n <= 4096, its limit).
+//
+// Row filter (bm25_search_kernel<true>, arx_bm25_search_filtered): a block serves one query, so a filter per query is a bitmap base
+// pointer per block (allow + filter_of[q] * words; an index outside [0, n_filters) leaves the block without a bitmap and its query without
+// rows).  A tile is a multiple of 1024 rows and therefore covers whole 64-bit bitmap words: per tile its first tile_rows / 64 threads
+// load them into LDS (bounded by ceil(n_rows / 64), the last word masked to n_rows) and a block-wide OR tells whether any row is
+// allowed.  A tile without one is skipped before the binary searches and the posting reads; in the scan a key is appended only when
+// its row's bit is set, and the accumulator is cleared either way.  Scores and idf are untouched, so an allowed row has the bits the
+// unfiltered search gives it.  Out of scope: a doc-at-a-time path for very selective SCATTERED filters.  Such a filter still streams
+// the postings of every tile it touches; only filters that leave whole tiles empty (contiguous ranges) save bandwidth.
 #include "arx_common.h"
 
 namespace {
@@ -33,6 +42,12 @@ struct Bm25Smem {
     unsigned long long thr;
     long long lo[BM25_MAXT], hi[BM25_MAXT];
     int cnt;
+};
+
+// the filtered kernel's extra LDS, behind Bm25Smem: the bitmap words of the current tile (1.5 KiB: two blocks still fit a 160 KiB CU
+// at the 12288-row tile, 2 * (48 KiB + ~17.2 KiB + 1.5 KiB) = 133.4 KiB)
+struct Bm25FilterSmem {
+    unsigned long long bits[BM25_TILE_MAX / 64];
 };
 
 __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
@@ -119,16 +134,28 @@ __device__ __forceinline__ void bm25_select(Bm25Smem& sm, int c, int n) {
     __syncthreads();
 }
 
+// FILTERED: allow = uint64 [n_filters][n_words] row bitmaps, filter_of = the bitmap of each query (null: bitmap 0)
+template <bool FILTERED>
 __global__ __launch_bounds__(BM25_NT) void bm25_search_kernel(const long long* __restrict__ term_ptr, const uint32_t* __restrict__ post_row,
                                                               const float* __restrict__ post_w, int vocab, long long n_rows,
-                                                              const int32_t* __restrict__ q_terms, const int32_t* __restrict__ q_nterms,
-                                                              int n, int tile_rows, float* __restrict__ part_s, long long* __restrict__ part_i,
-                                                              long long idx_base) {
+                                                              const unsigned long long* __restrict__ allow, int n_filters,
+                                                              const int32_t* __restrict__ filter_of, const int32_t* __restrict__ q_terms,
+                                                              const int32_t* __restrict__ q_nterms, int n, int tile_rows,
+                                                              float* __restrict__ part_s, long long* __restrict__ part_i, long long idx_base) {
     extern __shared__ __attribute__((aligned(16))) float acc[];               // [tile_rows] f32, then the block's Bm25Smem (all dynamic LDS)
     Bm25Smem& sm = *reinterpret_cast<Bm25Smem*>(acc + tile_rows);
     const int tid = threadIdx.x, q = blockIdx.y, nq = gridDim.y;
     const int32_t* terms = q_terms + (long long)q * BM25_MAXT;
-    const int nt = min(max(q_nterms[q], 0), BM25_MAXT);
+    int nt = min(max(q_nterms[q], 0), BM25_MAXT);
+    [[maybe_unused]] Bm25FilterSmem* fs = nullptr;
+    [[maybe_unused]] const unsigned long long* bitmap = nullptr;
+    [[maybe_unused]] const long long n_words = (n_rows + 63) >> 6;
+    if constexpr (FILTERED) {
+        fs = reinterpret_cast<Bm25FilterSmem*>(&sm + 1);
+        const int f = filter_of ? filter_of[q] : 0;
+        if (f >= 0 && f < n_filters) bitmap = allow + (long long)f * n_words;
+        else nt = 0;                                         // no such filter: the query sees no row and nothing is read
+    }
     for (int i = tid; i < tile_rows; i += BM25_NT) acc[i] = 0.f;
     if (tid == 0) { sm.cnt = 0; sm.thr = 0ull; }
     __syncthreads();
@@ -136,6 +163,20 @@ __global__ __launch_bounds__(BM25_NT) void bm25_search_kernel(const long long* _
     for (long long t = blockIdx.x; t < n_tiles && nt > 0; t += gridDim.x) {
         const long long lo = t * tile_rows;
         const long long hi = min(lo + (long long)tile_rows, n_rows);
+        if constexpr (FILTERED) {
+            // the tile's bitmap words -> LDS (the previous tile's scan ended with a barrier); lo is a multiple of 1024
+            unsigned long long w = 0ull;
+            if (tid < (tile_rows >> 6)) {
+                const long long wi = (lo >> 6) + tid;
+                if (wi < n_words) {
+                    w = bitmap[wi];
+                    const long long left = n_rows - (wi << 6);                  // >= 1 rows of this word are inside the shard
+                    if (left < 64) w &= ~0ull >> (64 - (int)left);
+                }
+                fs->bits[tid] = w;
+            }
+            if (!__syncthreads_or(w != 0ull)) continue;     // no allowed row: no binary searches, no posting reads; acc is still zero
+        }
         bm25_accumulate_tile(term_ptr, post_row, post_w, vocab, terms, nt, (uint32_t)lo, (uint32_t)hi, tile_rows, acc, sm);
         const int rows = (int)(hi - lo);
         for (int c0 = 0; c0 < rows; c0 += BM25_CHUNK) {
@@ -148,9 +189,11 @@ __global__ __launch_bounds__(BM25_NT) void bm25_search_kernel(const long long* _
                 const float2 v = *reinterpret_cast<const float2*>(acc + i);
                 *reinterpret_cast<float2*>(acc + i) = make_float2(0.f, 0.f);
                 const float s[2] = {v.x, v.y};
+                [[maybe_unused]] unsigned int ok = 3u;      // the two rows' bits: i is even, so both lie in one bitmap word
+                if constexpr (FILTERED) ok = (unsigned int)(fs->bits[i >> 6] >> (i & 63)) & 3u;
 #pragma unroll
                 for (int e = 0; e < 2; ++e) {
-                    if (s[e] > 0.f) {
+                    if (s[e] > 0.f && (!FILTERED || ((ok >> e) & 1u))) {
                         const unsigned long long key = ((unsigned long long)__float_as_uint(s[e]) << 32) |
                                                        (unsigned long long)(0xffffffffu - (uint32_t)(lo + i + e));
                         if (key > thr) {
@@ -210,11 +253,19 @@ extern "C" int64_t arx_bm25_workspace_bytes(int64_t n_rows, int32_t n_queries, i
     return round_up64(blocks * n_queries * n * 4, 256) + round_up64(blocks * n_queries * n * 8, 256);
 }
 
-extern "C" int32_t arx_bm25_search_tuned(const int64_t* term_ptr, const uint32_t* post_row, const float* post_w, int32_t vocab, int64_t n_rows,
-                                         const int32_t* q_terms, const int32_t* q_nterms, int32_t n_queries, int32_t n, float* out_scores,
-                                         int64_t* out_ids, int64_t idx_base, void* ws, int64_t ws_bytes, int32_t tile_rows, int32_t max_blocks,
-                                         void* stream) {
+namespace {
+
+// the unfiltered and the filtered search: the same checks in the same order, then bm25_search_kernel<FILTERED> and the merge
+template <bool FILTERED>
+int32_t bm25_search_launch(const int64_t* term_ptr, const uint32_t* post_row, const float* post_w, int32_t vocab, int64_t n_rows,
+                           const uint64_t* allow, int32_t n_filters, const int32_t* filter_of, const int32_t* q_terms, const int32_t* q_nterms,
+                           int32_t n_queries, int32_t n, float* out_scores, int64_t* out_ids, int64_t idx_base, void* ws, int64_t ws_bytes,
+                           int32_t tile_rows, int32_t max_blocks, void* stream) {
     ARX_REQUIRE(term_ptr && post_row && post_w && q_terms && q_nterms && out_scores && out_ids, "null pointer argument");
+    if (FILTERED) {
+        ARX_REQUIRE(allow, "allow must not be null (one row bitmap per filter)");
+        ARX_REQUIRE(n_filters >= 1, "n_filters=%d must be at least 1", n_filters);
+    }
     ARX_REQUIRE(vocab > 0, "vocab=%d must be positive", vocab);
     ARX_REQUIRE(n_rows > 0 && n_rows < (1ll << 31), "n_rows=%lld must be in [1, 2^31)", (long long)n_rows);
     ARX_REQUIRE(n_queries > 0 && n_queries <= 65535, "n_queries=%d must be in [1, 65535]", n_queries);
@@ -228,18 +279,29 @@ extern "C" int32_t arx_bm25_search_tuned(const int64_t* term_ptr, const uint32_t
     const int64_t need = arx_bm25_workspace_bytes(n_rows, n_queries, n);
     ARX_REQUIRE(blocks == 1 || (ws && ws_bytes >= need), "workspace too small: %lld < %lld bytes", (long long)ws_bytes, (long long)need);
     hipStream_t st = (hipStream_t)stream;
-    const int smem = tile_rows * 4 + (int)sizeof(Bm25Smem);
-    ARX_HIP_CHECK(arx_func_smem((const void*)bm25_search_kernel, smem));
+    const int smem = tile_rows * 4 + (int)sizeof(Bm25Smem) + (FILTERED ? (int)sizeof(Bm25FilterSmem) : 0);
+    ARX_HIP_CHECK(arx_func_smem((const void*)bm25_search_kernel<FILTERED>, smem));
     float* part_s = out_scores; long long* part_i = (long long*)out_ids;
     if (blocks > 1) {
         part_s = (float*)ws;
         part_i = (long long*)((char*)ws + round_up64((int64_t)blocks * n_queries * n * 4, 256));
     }
-    bm25_search_kernel<<<dim3(blocks, n_queries), BM25_NT, smem, st>>>((const long long*)term_ptr, post_row, post_w, vocab, n_rows, q_terms,
-                                                                        q_nterms, n, tile_rows, part_s, part_i, idx_base);
+    bm25_search_kernel<FILTERED><<<dim3(blocks, n_queries), BM25_NT, smem, st>>>(
+        (const long long*)term_ptr, post_row, post_w, vocab, n_rows, (const unsigned long long*)allow, n_filters, filter_of, q_terms, q_nterms, n,
+        tile_rows, part_s, part_i, idx_base);
     ARX_HIP_CHECK(hipGetLastError());
     if (blocks > 1) return arx_topk_merge(part_s, (const int64_t*)part_i, blocks, n_queries, n, out_scores, out_ids, stream);
     return ARX_OK;
+}
+
+}  // namespace
+
+extern "C" int32_t arx_bm25_search_tuned(const int64_t* term_ptr, const uint32_t* post_row, const float* post_w, int32_t vocab, int64_t n_rows,
+                                         const int32_t* q_terms, const int32_t* q_nterms, int32_t n_queries, int32_t n, float* out_scores,
+                                         int64_t* out_ids, int64_t idx_base, void* ws, int64_t ws_bytes, int32_t tile_rows, int32_t max_blocks,
+                                         void* stream) {
+    return bm25_search_launch<false>(term_ptr, post_row, post_w, vocab, n_rows, nullptr, 0, nullptr, q_terms, q_nterms, n_queries, n, out_scores,
+                                     out_ids, idx_base, ws, ws_bytes, tile_rows, max_blocks, stream);
 }
 
 extern "C" int32_t arx_bm25_search(const int64_t* term_ptr, const uint32_t* post_row, const float* post_w, int32_t vocab, int64_t n_rows,
@@ -247,6 +309,23 @@ extern "C" int32_t arx_bm25_search(const int64_t* term_ptr, const uint32_t* post
                                    int64_t* out_ids, int64_t idx_base, void* ws, int64_t ws_bytes, void* stream) {
     return arx_bm25_search_tuned(term_ptr, post_row, post_w, vocab, n_rows, q_terms, q_nterms, n_queries, n, out_scores, out_ids, idx_base,
                                  ws, ws_bytes, 0, 0, stream);
+}
+
+extern "C" int32_t arx_bm25_search_filtered_tuned(const int64_t* term_ptr, const uint32_t* post_row, const float* post_w, int32_t vocab,
+                                                  int64_t n_rows, const uint64_t* allow, int32_t n_filters, const int32_t* filter_of,
+                                                  const int32_t* q_terms, const int32_t* q_nterms, int32_t n_queries, int32_t n,
+                                                  float* out_scores, int64_t* out_ids, int64_t idx_base, void* ws, int64_t ws_bytes,
+                                                  int32_t tile_rows, int32_t max_blocks, void* stream) {
+    return bm25_search_launch<true>(term_ptr, post_row, post_w, vocab, n_rows, allow, n_filters, filter_of, q_terms, q_nterms, n_queries, n,
+                                    out_scores, out_ids, idx_base, ws, ws_bytes, tile_rows, max_blocks, stream);
+}
+
+extern "C" int32_t arx_bm25_search_filtered(const int64_t* term_ptr, const uint32_t* post_row, const float* post_w, int32_t vocab, int64_t n_rows,
+                                            const uint64_t* allow, int32_t n_filters, const int32_t* filter_of, const int32_t* q_terms,
+                                            const int32_t* q_nterms, int32_t n_queries, int32_t n, float* out_scores, int64_t* out_ids,
+                                            int64_t idx_base, void* ws, int64_t ws_bytes, void* stream) {
+    return arx_bm25_search_filtered_tuned(term_ptr, post_row, post_w, vocab, n_rows, allow, n_filters, filter_of, q_terms, q_nterms, n_queries, n,
+                                          out_scores, out_ids, idx_base, ws, ws_bytes, 0, 0, stream);
 }
 
 extern "C" int32_t arx_bm25_scores(const int64_t* term_ptr, const uint32_t* post_row, const float* post_w, int32_t vocab, int64_t n_rows,

@@ -662,7 +662,7 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
                    hybrid_alpha: Optional[float] = None, where=None,
                    where_document: Optional[Dict] = None, *, mmr_lambda: Optional[float] = None, mmr_fetch_k: int = 32,
                    keep_mask: Optional[np.ndarray] = None, group_by_paper: bool = False, chunks_per_paper: int = 1,
-                   where_on_device: bool = False, min_score: Optional[float] = None) -> List[Dict]:
+                   where_on_device: bool = False, min_score: Optional[float] = None, hybrid_filters: bool = False) -> List[Dict]:
     """Brute-force cosine top-k (config.yaml:63-64 `top_k: 10`) over the rank's fp16 rows in HBM; with
     torchrun each rank holds the contiguous row shard it encoded and the partial top-k lists are
     all-gathered over RCCL and merged.  `shard` is the `ShardSink` the encode step filled: rows [lo, hi) are already where they
@@ -707,7 +707,11 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
     query is >= it are returned, the best `top_k` of them, `top_k` then in 1..1024 (`ShardIndex.search_range`), `where` /
     `where_document` / `keep_mask` applied as without it; every entry of the results then carries `truncated`: more chunks qualified than
     `top_k`.  Not together with `reranker`, `hybrid_alpha`, `mmr_lambda`, `group_by_paper`, a per-query `where` list or more than one
-    rank (reranking and a cross-rank merge of long lists are out of scope here)."""
+    rank (reranking and a cross-rank merge of long lists are out of scope here).
+    `hybrid_filters` (False = nothing changes, every refusal above stays): `hybrid_alpha` then composes with `where` (a dict or a per-query
+    list), `where_document`, `keep_mask` and `where_on_device`: the bitmaps the cosine search uses go to the keyword search unchanged
+    (`KeywordIndex.search(allow=...)`, `arx_bm25_search_filtered`), so both candidate lists hold allowed rows only and the fusion is what it
+    was.  The BM25 statistics stay those of the whole corpus (INTEGRATION.md "Hybrid search with filters")."""
     if min_score is not None:
         from .ranging import check_range_query
         if reranker is not None:
@@ -720,7 +724,7 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
         from .grouping import check_grouped_query
         check_grouped_query(top_k, chunks_per_paper, grouped=True, reranker=reranker, hybrid_alpha=hybrid_alpha, mmr_lambda=mmr_lambda,
                             per_query_filters=isinstance(where, (list, tuple)), world=int(os.environ.get("WORLD_SIZE", "1")))
-    if keep_mask is not None and hybrid_alpha is not None:
+    if keep_mask is not None and hybrid_alpha is not None and not hybrid_filters:
         raise ValueError("keep_mask cannot be combined with hybrid_alpha: the BM25 keyword search has no row filter")
     if mmr_lambda is not None:
         if reranker is not None or hybrid_alpha is not None:
@@ -731,9 +735,9 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
             raise ValueError(f"mmr_fetch_k={mmr_fetch_k} must be in [top_k, {MMR_MAX_FETCH_K}] (top_k={top_k})")
     import torch
     from .index import ShardIndex
-    if where is not None and hybrid_alpha is not None:
+    if where is not None and hybrid_alpha is not None and not hybrid_filters:
         raise ValueError("where cannot be combined with hybrid_alpha: the BM25 keyword search has no row filter")
-    if where_document is not None and hybrid_alpha is not None:
+    if where_document is not None and hybrid_alpha is not None and not hybrid_filters:
         raise ValueError("where_document cannot be combined with hybrid_alpha: the BM25 keyword search has no row filter")
     dist = _dist()
     rank = dist.get_rank() if dist else 0
@@ -801,6 +805,7 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
         pre = None                                           # a range search runs on the fp16 rows
     index = ShardIndex(shard.rows, idx_base=shard.lo, prefilter=pre, adaptive=True)
     grp = truncated = None
+    kw_allow, kw_filter_of = allow, None                     # hybrid_filters: what the keyword side is restricted to (the dense side's bitmaps)
     if min_score is not None:
         if world > 1:
             raise ValueError("min_score needs a single GPU rank: a cross-rank merge of lists of up to 1024 rows is out of scope")
@@ -841,6 +846,8 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
             bitmaps.append(words)
             counts.append(count)
         s, i = search_filtered_grouped(index, qd, n_cand, bitmaps, filter_of, counts)
+        if hybrid_alpha is not None:
+            kw_allow, kw_filter_of = torch.stack(bitmaps).contiguous(), torch.tensor(list(filter_of), dtype=torch.int32, device=dev)
     else:
         s, i = index.search_distributed(qd, n_cand, allow=allow, n_allowed=n_allowed)
     mmr_val = None
@@ -859,7 +866,7 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
             raise ValueError(f"hybrid search keeps at most {n_cand} results per query (top_k={top_k})")
         kw = KeywordIndex(texts=[c["text"] for c in chunks], tokenizer=model.tokenizer, stats="global" if world > 1 else None,
                           idx_base=chunk_base, device=dev)
-        ks, ki = kw.search_distributed(queries, n_cand)
+        ks, ki = kw.search_distributed(queries, n_cand, allow=kw_allow, filter_of=kw_filter_of)
         hyb, i, s, kws = fuse(s, i, ks.cpu().numpy(), ki.cpu().numpy(), float(hybrid_alpha), k_search)
     if reranker is not None:
         from .rerank import rerank_candidates, reorder_by_rerank
@@ -940,20 +947,23 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--hybrid-alpha", type=float, default=None,
                    help="Hybrid search for --queries: weight of the cosine side in [0, 1], the BM25 keyword side gets the rest "
                         "(config.yaml hybrid_alpha: 0.7; default: off, cosine only)")
+    p.add_argument("--hybrid-filters", action="store_true",
+                   help="Let --hybrid-alpha compose with --where, --where-file, --where-document and --dedup-threshold: the BM25 keyword "
+                        "search reads the same row bitmaps as the cosine search (default: off, those combinations are refused)")
     p.add_argument("--where", type=str, default=None,
                    help="Chroma metadata filter for --queries as JSON, e.g. '{\"section\": \"abstract\"}' or "
-                        "'{\"quality_score\": {\"$gte\": 0.95}}': only matching chunks are searched (not with --hybrid-alpha)")
+                        "'{\"quality_score\": {\"$gte\": 0.95}}': only matching chunks are searched (with --hybrid-alpha only next to --hybrid-filters)")
     p.add_argument("--where-file", type=str, default=None,
                    help="A different --where filter per query: a JSON-lines file with one filter object or null (no filter) per line, "
-                        "one line per query of --queries; the batch is searched in one pass over the rows (not with --where or "
-                        "--hybrid-alpha)")
+                        "one line per query of --queries; the batch is searched in one pass over the rows (not with --where; "
+                        "with --hybrid-alpha only next to --hybrid-filters)")
     p.add_argument("--where-on-device", action="store_true",
                    help="Evaluate the --where / --where-file filters on the GPU from metadata columns kept in HBM, not with numpy on "
                         "the host (same results; needs --where or --where-file)")
     p.add_argument("--where-document", type=str, default=None,
                    help="Chroma document filter for --queries as JSON, e.g. '{\"$contains\": \"Lipschitz\"}' or "
                         "'{\"$and\": [{\"$contains\": \"graph\"}, {\"$not_contains\": \"lemma\"}]}': only chunks whose text "
-                        "satisfies it are searched (case-sensitive substrings, scanned on the GPU; not with --hybrid-alpha)")
+                        "satisfies it are searched (case-sensitive substrings, scanned on the GPU; with --hybrid-alpha only next to --hybrid-filters)")
     p.add_argument("--mmr-lambda", type=float, default=None,
                    help="Diversify the --queries results by maximal marginal relevance: weight of the relevance term in [0, 1], the "
                         "penalty on similarity to the rows already picked gets the rest (default: off; not with --rerank-model or "
@@ -963,7 +973,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--dedup-threshold", type=float, default=None,
                    help="Near-duplicate detection: a chunk whose embedding scores at least this cosine, in (0, 1], against ANY earlier "
                         "chunk is listed in duplicates.json with its nearest earlier chunk, and a --queries search skips it (default: "
-                        "off; one GPU rank only; not with --hybrid-alpha and --queries)")
+                        "off; one GPU rank only; with --hybrid-alpha and --queries only next to --hybrid-filters)")
     p.add_argument("--group-by-paper", action="store_true",
                    help="Grouped results for --queries: --top-k counts PAPERS (consecutive chunks with equal paper_id), the exact best "
                         "by their best chunk, each with its --chunks-per-paper best chunks (one GPU rank only; not with --rerank-model, "
@@ -1008,6 +1018,18 @@ def check_hybrid_args(args) -> Optional[str]:
 MMR_MAX_FETCH_K = 32       # candidate slots of arx_mmr_select = the search's k limit
 
 
+def check_hybrid_filters_args(args) -> Optional[str]:
+    """-> an error message for an unusable --hybrid-filters, else None.  (The other flags are read with getattr: absent = off.)"""
+    if not getattr(args, "hybrid_filters", False):
+        return None
+    if getattr(args, "hybrid_alpha", None) is None:
+        return "--hybrid-filters needs --hybrid-alpha: it lets the hybrid search take the row filters"
+    if all(getattr(args, name, None) is None for name in ("where", "where_file", "where_document", "dedup_threshold")):
+        return ("--hybrid-filters needs --where, --where-file, --where-document or --dedup-threshold: it passes their row bitmaps to the "
+                "BM25 keyword search")
+    return None
+
+
 def check_mmr_args(args) -> Optional[str]:
     """-> an error message for an unusable --mmr-lambda / --mmr-fetch-k, else None."""
     if args.mmr_lambda is None:
@@ -1031,7 +1053,7 @@ def check_dedup_args(args) -> Optional[str]:
         return None
     if not (0.0 < args.dedup_threshold <= 1.0):               # (also rejects nan)
         return f"--dedup-threshold {args.dedup_threshold}: the cosine at which a chunk counts as a duplicate must be in (0, 1]"
-    if args.hybrid_alpha is not None and args.queries:
+    if args.hybrid_alpha is not None and args.queries and not getattr(args, "hybrid_filters", False):
         return "--dedup-threshold cannot be combined with --hybrid-alpha and --queries: the BM25 keyword search has no row filter"
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         return "--dedup-threshold needs a single GPU rank: a rank sees only its own rows, and a cross-rank join is out of scope"
@@ -1117,7 +1139,7 @@ def check_where_args(args) -> Optional[str]:
     args.where_filter = None
     if args.where is None:
         return None
-    if args.hybrid_alpha is not None:
+    if args.hybrid_alpha is not None and not getattr(args, "hybrid_filters", False):
         return "--where cannot be combined with --hybrid-alpha: the BM25 keyword search has no row filter"
     try:
         parsed = json.loads(args.where)
@@ -1145,7 +1167,7 @@ def check_where_file_args(args) -> Optional[str]:
         return None
     if args.where is not None:
         return "--where-file cannot be combined with --where: the file holds the filter of every query"
-    if args.hybrid_alpha is not None:
+    if args.hybrid_alpha is not None and not getattr(args, "hybrid_filters", False):
         return "--where-file cannot be combined with --hybrid-alpha: the BM25 keyword search has no row filter"
     if not args.queries:
         return "--where-file needs --queries: it holds one filter per query"
@@ -1190,7 +1212,7 @@ def check_where_document_args(args) -> Optional[str]:
     args.where_document_filter = None
     if args.where_document is None:
         return None
-    if args.hybrid_alpha is not None:
+    if args.hybrid_alpha is not None and not getattr(args, "hybrid_filters", False):
         return "--where-document cannot be combined with --hybrid-alpha: the BM25 keyword search has no row filter"
     try:
         parsed = json.loads(args.where_document)
@@ -1208,7 +1230,7 @@ def check_where_document_args(args) -> Optional[str]:
 def main(argv: Optional[Sequence[str]] = None, model_factory: Optional[Callable] = None) -> int:
     global _model, _model_name
     args = build_parser().parse_args(argv)
-    err = (check_rerank_args(args) or check_hybrid_args(args) or check_where_args(args) or check_where_file_args(args) or check_where_device_args(args)
+    err = (check_rerank_args(args) or check_hybrid_args(args) or check_hybrid_filters_args(args) or check_where_args(args) or check_where_file_args(args) or check_where_device_args(args)
            or check_where_document_args(args)
            or check_mmr_args(args) or check_dedup_args(args) or check_group_args(args) or check_range_args(args))
     if err:
@@ -1309,7 +1331,8 @@ def main(argv: Optional[Sequence[str]] = None, model_factory: Optional[Callable]
                                mmr_lambda=args.mmr_lambda, mmr_fetch_k=args.mmr_fetch_k, keep_mask=keep_mask,
                                **({"group_by_paper": True, "chunks_per_paper": args.chunks_per_paper} if args.group_by_paper else {}),
                                **({"where_on_device": True} if args.where_on_device else {}),
-                               **({"min_score": args.min_score} if args.min_score is not None else {}))
+                               **({"min_score": args.min_score} if args.min_score is not None else {}),
+                               **({"hybrid_filters": True} if args.hybrid_filters else {}))
         store_time = 0.0
         if rank == 0 and not args.skip_chroma:
             try:

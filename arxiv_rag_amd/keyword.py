@@ -8,6 +8,7 @@ The reference configures hybrid search and has no code for it, so the definition
   `idf = ln(1 + (N - df + 0.5) / (df + 0.5))`, `w = idf * tf * (k1 + 1) / (tf + k1 * (1 - b + b * dl / avgdl))`;
 * a query is its first 64 distinct word pieces, sorted by id; `bm25(q, d)` = the f32 sum of its terms' impacts in ascending id order;
 * `arx_bm25_search` (csrc/bm25.hip) returns per query the n <= 32 rows with the largest `(score desc, row asc)`;
+* `arx_bm25_search_filtered` does so among the rows a bitmap allows (one bitmap per query); scores, idf and avgdl are unchanged;
 * `fuse` is relative-score fusion of the (global) dense and keyword lists: `alpha * normD + (1 - alpha) * normK`.
 
 `KeywordStats`, `build_postings`, `impacts_f64` and `fuse` are numpy only; `KeywordIndex` needs the GPU.
@@ -254,40 +255,79 @@ class KeywordIndex:
         ln = np.diff(self.term_ptr_host)
         return np.array([8 * int(ln[np.asarray(list(t), np.int64)].sum()) if len(t) else 0 for t in term_lists], np.int64)
 
-    def search(self, queries, n: int = MAX_N, tile_rows: int = 0, max_blocks: int = 0):
+    def _check_filters(self, allow, filter_of, nq: int):
+        """-> (allow as a contiguous [F, W] tensor, filter_of or None); ValueError for a wrong shape, dtype or device."""
+        import torch
+        n_words = (self.n_rows + 63) // 64
+
+        def here(t):                                             # ("cuda" names the current device: only a stated index is compared)
+            return t.device.type == self.device.type and (self.device.index is None or t.device.index == self.device.index)
+        if not isinstance(allow, torch.Tensor) or allow.dtype != torch.int64 or not here(allow):
+            raise ValueError(f"allow must be an int64 tensor on {self.device} (row bitmaps, [W] or [F, W])")
+        if allow.dim() == 1:
+            allow = allow[None]
+        if allow.dim() != 2 or allow.shape[0] < 1 or allow.shape[1] != n_words:
+            raise ValueError(f"allow has shape {tuple(allow.shape)}; expected [{n_words}] or [F, {n_words}] (ceil(n_rows / 64) words per filter)")
+        if filter_of is not None:
+            if not isinstance(filter_of, torch.Tensor) or filter_of.dtype != torch.int32 or not here(filter_of):
+                raise ValueError(f"filter_of must be an int32 tensor on {self.device}")
+            if tuple(filter_of.shape) != (nq,):
+                raise ValueError(f"filter_of has shape {tuple(filter_of.shape)}; expected [{nq}] (one bitmap index per query)")
+            filter_of = filter_of.contiguous()
+        return allow.contiguous(), filter_of
+
+    QUERY_STEP = 4096              # queries per kernel call (the grid's y extent is limited to 65535)
+
+    def search(self, queries, n: int = MAX_N, tile_rows: int = 0, max_blocks: int = 0, allow=None, filter_of=None):
         """`queries`: texts, or term-id lists (strictly ascending).  -> (scores f32 [nq, n], ids int64 [nq, n]) on the device; unused
-        slots are (-inf, -1).  `tile_rows` / `max_blocks` choose the launch shape (tests, tuning): the answer's bits do not depend on it."""
+        slots are (-inf, -1).  `tile_rows` / `max_blocks` choose the launch shape (tests, tuning): the answer's bits do not depend on it.
+        `allow` (None = every row, today's call): row bitmaps of this index's rows as an int64 device tensor [W] or [F, W],
+        W = ceil(n_rows / 64), in `ShardIndex.search(allow=...)`'s convention; only allowed rows are returned, with the scores they have
+        without a filter (`arx_bm25_search_filtered`).  `filter_of`: int32 device tensor [nq], the bitmap of each query (None = bitmap 0
+        for all; an index outside [0, F) leaves that query without rows)."""
         import torch
         from . import _lib
         if not (1 <= n <= MAX_N):
             raise ValueError(f"n={n} must be in [1, {MAX_N}]")
+        if allow is None and filter_of is not None:
+            raise ValueError("filter_of needs allow")
         qt, qn = pack_query_terms(self._term_lists(queries), self.vocab_size)
         nq = len(qn)
+        if allow is not None:
+            allow, filter_of = self._check_filters(allow, filter_of, nq)
         out_s = torch.full((nq, n), float("-inf"), dtype=torch.float32, device=self.device)
         out_i = torch.full((nq, n), -1, dtype=torch.int64, device=self.device)
         if nq == 0 or self.n_rows == 0:
             return out_s, out_i
         qt_d, qn_d = torch.from_numpy(qt).to(self.device), torch.from_numpy(qn).to(self.device)
-        step = 4096
+        step = self.QUERY_STEP
         need = self.lib.arx_bm25_workspace_bytes(self.n_rows, min(nq, step), n)
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         st = torch.cuda.current_stream(self.device).cuda_stream
         for a in range(0, nq, step):
             b = min(nq, a + step)
-            rc = self.lib.arx_bm25_search_tuned(self.term_ptr.data_ptr(), self.post_row.data_ptr(), self.post_w.data_ptr(), self.vocab_size,
-                                                self.n_rows, qt_d[a:b].data_ptr(), qn_d[a:b].data_ptr(), b - a, n, out_s[a:b].data_ptr(),
-                                                out_i[a:b].data_ptr(), self.idx_base, self._ws.data_ptr(), self._ws.numel(),
-                                                int(tile_rows), int(max_blocks), st)
-            _lib.check(rc, "arx_bm25_search")
+            if allow is None:
+                rc = self.lib.arx_bm25_search_tuned(self.term_ptr.data_ptr(), self.post_row.data_ptr(), self.post_w.data_ptr(), self.vocab_size,
+                                                    self.n_rows, qt_d[a:b].data_ptr(), qn_d[a:b].data_ptr(), b - a, n, out_s[a:b].data_ptr(),
+                                                    out_i[a:b].data_ptr(), self.idx_base, self._ws.data_ptr(), self._ws.numel(),
+                                                    int(tile_rows), int(max_blocks), st)
+                _lib.check(rc, "arx_bm25_search")
+            else:
+                rc = self.lib.arx_bm25_search_filtered_tuned(
+                    self.term_ptr.data_ptr(), self.post_row.data_ptr(), self.post_w.data_ptr(), self.vocab_size, self.n_rows, allow.data_ptr(),
+                    int(allow.shape[0]), None if filter_of is None else filter_of[a:b].data_ptr(), qt_d[a:b].data_ptr(), qn_d[a:b].data_ptr(),
+                    b - a, n, out_s[a:b].data_ptr(), out_i[a:b].data_ptr(), self.idx_base, self._ws.data_ptr(), self._ws.numel(),
+                    int(tile_rows), int(max_blocks), st)
+                _lib.check(rc, "arx_bm25_search_filtered")
         return out_s, out_i
 
-    def search_distributed(self, queries, n: int = MAX_N, group=None):
+    def search_distributed(self, queries, n: int = MAX_N, group=None, allow=None, filter_of=None):
         """Every rank passes the SAME queries; returns the global keyword top-n on every rank (local top-n -> all-gather -> merge kernel,
-        as `ShardIndex.search_distributed`)."""
+        as `ShardIndex.search_distributed`).  `allow` / `filter_of`: THIS rank's own bitmaps, as in `search`; the merge is unchanged."""
         import torch.distributed as dist
         from .index import gather_partials, merge_partials
-        s, i = self.search(queries, n)
+        s, i = self.search(queries, n, allow=allow, filter_of=filter_of)
         if not dist.is_initialized() or s.shape[0] == 0:
             return s, i
         all_s, all_i = gather_partials(s, i, group)

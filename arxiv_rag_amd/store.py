@@ -76,7 +76,7 @@ class HipCollection:
     def __init__(self, embeddings: np.ndarray, metadata: Sequence[Dict], device="cuda:0", encoder=None,
                  rank: int = 0, world: int = 1, chunk_rows: int = 1 << 18, keyword: bool = False, tokenizer=None,
                  documents: bool = False, dedup_threshold: Optional[float] = None, group_key: Optional[str] = None,
-                 where_on_device: bool = False):
+                 where_on_device: bool = False, hybrid_filters: bool = False):
         """`keyword=True`: also build a BM25 `keyword.KeywordIndex` over this shard's `metadata[i]["text"]` (word pieces of `tokenizer`,
         default the encoder's; corpus statistics summed over all ranks when `world > 1`), which `query(hybrid_alpha=...)` needs.
         `documents=True`: also keep this shard's texts as a UTF-8 blob in HBM (`where_document.DocumentStore`), which
@@ -94,9 +94,17 @@ class HipCollection:
         HBM (`where_device.MetadataColumns`: 9 bytes per row and referenced key, a column built on first use), not with numpy on the
         host; the dedup keep-bitmap and the `where_document` bitmap are and-ed in by the same kernel, so no mask is built or uploaded,
         and a per-query `where` list is evaluated in one launch per 64 distinct filters.  The results are the default path's, bit for
-        bit (INTEGRATION.md "where on the device")."""
+        bit (INTEGRATION.md "where on the device").
+        `hybrid_filters` (False = nothing changes; needs `keyword=True`): `query(hybrid_alpha=...)` composes with `where`,
+        `where_document`, per-query lists of either, the dedup keep-bitmap and `where_on_device` instead of raising: the bitmaps the
+        cosine search is given go to the keyword search unchanged (`KeywordIndex.search(allow=...)`, `arx_bm25_search_filtered`), so
+        both candidate lists hold allowed rows only.  The BM25 statistics stay those of the whole corpus (INTEGRATION.md "Hybrid search
+        with filters")."""
         import torch
         from .index import ShardIndex, shard_bounds
+        if hybrid_filters and not keyword:
+            raise ValueError("hybrid_filters=True needs keyword=True: it passes the row filters to the BM25 keyword search")
+        self.hybrid_filters = bool(hybrid_filters)
         if dedup_threshold is not None:
             from .dedup import check_threshold
             dedup_threshold = check_threshold(dedup_threshold)
@@ -240,29 +248,34 @@ class HipCollection:
     def _search_per_query(self, q, k, where, where_document):
         """The search of `query` when `where` / `where_document` hold one entry per query: one bitmap per distinct pair, one
         `search_filtered_many` per 64 of them."""
+        from .index import search_filtered_grouped
+        bitmaps, filter_of, counts = self._per_query_bitmaps(q.shape[0], where, where_document, q.device)
+        return search_filtered_grouped(self.index, q, k, bitmaps, filter_of, counts)
+
+    def _per_query_bitmaps(self, nq, where, where_document, device):
+        """-> (bitmaps, filter_of, counts) of a per-query batch: the bitmap of every distinct (where, where_document) pair (a list of
+        device tensors or one [F, W] tensor), the index of each query's bitmap (host) and the bitmaps' allowed rows."""
         import torch
         from .filter_sets import distinct_filters, per_query_list
-        from .index import search_filtered_grouped
-        nq = q.shape[0]
         pairs, filter_of = distinct_filters(per_query_list(where, nq, "where"), per_query_list(where_document, nq, "where_document"))
         if any(d is not None for _, d in pairs) and self.documents is None:
             raise ValueError("where_document needs a collection built with documents=True")
         if getattr(self, "where_on_device", False) and self.hi > self.lo:
-            bitmaps, counts = self._bitmaps_on_device(pairs, q.device)
-            return search_filtered_grouped(self.index, q, k, bitmaps, filter_of, counts)
+            bitmaps, counts = self._bitmaps_on_device(pairs, device)
+            return bitmaps, filter_of, counts
         bitmaps, counts = [], []
         for w, d in pairs:
             doc_tree = None
             if d is not None:
                 from .where_document import compile_where_document
                 doc_tree = compile_where_document(d)
-            allow, n_allowed = self._allow_of(w, doc_tree, q.device)
+            allow, n_allowed = self._allow_of(w, doc_tree, device)
             if allow is None:                                    # no filter for these queries: every row of the shard
-                allow = torch.full(((self.hi - self.lo + 63) // 64,), -1, dtype=torch.int64, device=q.device)
+                allow = torch.full(((self.hi - self.lo + 63) // 64,), -1, dtype=torch.int64, device=device)
                 n_allowed = self.hi - self.lo
             bitmaps.append(allow)
             counts.append(n_allowed)
-        return search_filtered_grouped(self.index, q, k, bitmaps, filter_of, counts)
+        return bitmaps, filter_of, counts
 
     def query(self, query_embeddings=None, query_texts: Optional[Sequence[str]] = None, n_results: int = 10, reranker=None,
               n_candidates: int = 32, hybrid_alpha: Optional[float] = None, where=None, where_document=None,
@@ -317,7 +330,11 @@ class HipCollection:
         `where_document` and the dedup keep-bitmap (one bitmap per call), and with `reranker`: `n_candidates` may then be up to 1024, the
         cross-encoder receives the range list (`truncated` refers to it) and scores its pairs in batches of at most 32, so
         `min_score=float("-inf"), n_candidates=50` is "re-rank the top 50".  ValueError with `hybrid_alpha`, `mmr_lambda`, `group_by`,
-        per-query filter lists and `world > 1` (a cross-rank merge of long lists is out of scope)."""
+        per-query filter lists and `world > 1` (a cross-rank merge of long lists is out of scope).
+        On a collection built with `hybrid_filters=True` every "raises ValueError with `hybrid_alpha`" above that is about a row filter
+        (`where`, `where_document`, per-query lists, `dedup_threshold`) is lifted: the keyword search is restricted by the very bitmaps
+        of the cosine search, query by query, `fuse` and `reranker` work as without a filter, and idf / avgdl stay corpus-wide.
+        `mmr_lambda`, `group_by` and `min_score` stay refused with `hybrid_alpha`."""
         import torch
         from .filter_sets import is_per_query
         from .grouping import check_grouped_query
@@ -328,12 +345,13 @@ class HipCollection:
         check_grouped_query(n_results, chunks_per_group, grouped=bool(group_by), has_group_key=getattr(self, "group_key", None) is not None,
                             reranker=reranker, hybrid_alpha=hybrid_alpha, mmr_lambda=mmr_lambda,
                             per_query_filters=is_per_query(where) or is_per_query(where_document), world=getattr(self, "world", 1))
+        filtered_hybrid = hybrid_alpha is not None and getattr(self, "hybrid_filters", False)
         per_query = None
         if is_per_query(where) or is_per_query(where_document):
-            if hybrid_alpha is not None:
+            if hybrid_alpha is not None and not filtered_hybrid:
                 raise ValueError("where cannot be combined with hybrid_alpha: the BM25 keyword search has no row filter")
             per_query, where, where_document = (where, where_document), None, None
-        if self._keep is not None and hybrid_alpha is not None:
+        if self._keep is not None and hybrid_alpha is not None and not filtered_hybrid:
             raise ValueError("a collection built with dedup_threshold cannot be queried with hybrid_alpha: the BM25 keyword search has no "
                              "row filter")
         if mmr_lambda is not None:
@@ -344,13 +362,13 @@ class HipCollection:
             if not (1 <= n_results <= n_candidates <= 32):
                 raise ValueError(f"n_candidates={n_candidates} must be in [n_results, 32] (the search's k limit) and n_results at least 1")
         if where_document is not None:
-            if hybrid_alpha is not None:
+            if hybrid_alpha is not None and not filtered_hybrid:
                 raise ValueError("where_document cannot be combined with hybrid_alpha: the BM25 keyword search has no row filter")
             if self.documents is None:
                 raise ValueError("where_document needs a collection built with documents=True")
             from .where_document import compile_where_document
             doc_tree = compile_where_document(where_document)
-        if where is not None and hybrid_alpha is not None:
+        if where is not None and hybrid_alpha is not None and not filtered_hybrid:
             raise ValueError("where cannot be combined with hybrid_alpha: the BM25 keyword search has no row filter")
         if hybrid_alpha is not None:
             if not (0.0 <= float(hybrid_alpha) <= 1.0):
@@ -373,6 +391,7 @@ class HipCollection:
             q = q[None]
         wide = reranker is not None or hybrid_alpha is not None or mmr_lambda is not None
         grp = truncated = None
+        kw_allow = kw_filter_of = None                           # hybrid_filters: the dense side's bitmaps, for the keyword side
         if min_score is not None:
             allow, n_allowed = self._allow_of(where, doc_tree if where_document is not None else None, q.device)
             s, i, counts = self.index.search_range(q, thresholds(min_score, q.shape[0]), n_candidates if reranker is not None else n_results,
@@ -384,11 +403,18 @@ class HipCollection:
             grp = grp.cpu().numpy()
             sizes = (i >= 0).sum(dim=2).cpu().numpy()
             s, i = s.reshape(q.shape[0], -1), i.reshape(q.shape[0], -1)      # paper by paper; the padding is dropped below
+        elif per_query is not None and filtered_hybrid:
+            from .index import search_filtered_grouped
+            bitmaps, filter_of, counts = self._per_query_bitmaps(q.shape[0], *per_query, q.device)
+            s, i = search_filtered_grouped(self.index, q, n_candidates, bitmaps, filter_of, counts)
+            kw_allow = bitmaps if torch.is_tensor(bitmaps) else torch.stack(list(bitmaps)).contiguous()
+            kw_filter_of = torch.tensor(list(filter_of), dtype=torch.int32, device=q.device)
         elif per_query is not None:
             s, i = self._search_per_query(q, n_candidates if wide else n_results, *per_query)
         else:
             allow, n_allowed = self._allow_of(where, doc_tree if where_document is not None else None, q.device)
             s, i = self.index.search_distributed(q, n_candidates if wide else n_results, allow=allow, n_allowed=n_allowed)
+            kw_allow = allow if filtered_hybrid else None
         mmr_val = None
         if mmr_lambda is not None:
             from .mmr import mmr_select
@@ -401,7 +427,7 @@ class HipCollection:
         hyb = kws = None
         if hybrid_alpha is not None:
             from .keyword import fuse
-            ks, ki = self.keyword.search_distributed(list(query_texts), n_candidates)
+            ks, ki = self.keyword.search_distributed(list(query_texts), n_candidates, allow=kw_allow, filter_of=kw_filter_of)
             hyb, i, s, kws = fuse(s, i, ks.cpu().numpy(), ki.cpu().numpy(), float(hybrid_alpha),
                                   n_candidates if reranker is not None else n_results)
         if reranker is not None:

@@ -552,6 +552,31 @@ int32_t arx_bm25_search_tuned(const int64_t* term_ptr, const uint32_t* post_row,
                               const int32_t* q_terms, const int32_t* q_nterms, int32_t n_queries, int32_t n, float* out_scores,
                               int64_t* out_ids, int64_t idx_base, void* ws, int64_t ws_bytes, int32_t tile_rows, int32_t max_blocks,
                               void* stream);
+/* Filtered BM25 top-n (hybrid search under `where` / `where_document` / the dedup keep-bitmap; opt-in: `hybrid_filters=True`,
+ * --hybrid-filters).  arx_bm25_search restricted to allowed rows, with a filter per query:
+ *   allow     device uint64 [n_filters][ceil(n_rows / 64)], the bitmap convention of arx_topk_search_filtered (bit r & 63 of word
+ *             r >> 6 = row r allowed); bits at or beyond n_rows may be garbage and are ignored.  n_filters >= 1, and the 64-filter
+ *             limit of arx_topk_search_filtered_multi does not apply: each block of the kernel serves one query.
+ *   filter_of device int32 [n_queries]: the bitmap of each query; NULL = every query uses bitmap 0.  A query whose filter_of lies
+ *             outside [0, n_filters) sees no row: its output is all (-inf, -1) and nothing is read out of range (tested on the device).
+ * Output, per query q: the n <= 32 rows with the largest (score desc, row asc) among rows that hold at least one query term AND are
+ * allowed by allow[filter_of[q]].  A row's score has exactly the bits arx_bm25_search / arx_bm25_scores give it: the impacts are
+ * untouched, so idf and avgdl stay statistics of the WHOLE corpus, as a Lucene filter clause leaves them.  A query's output depends
+ * on the query, its own bitmap and the index only: not on the other queries, their filters, n_filters, tile_rows or max_blocks.
+ * Padding, merge and workspace (arx_bm25_workspace_bytes) are those of arx_bm25_search.  ARX_ERR_ARG before any launch: a null
+ * allow, n_filters < 1, and every argument error of arx_bm25_search.
+ * Cost: a tile (<= 12288 rows) without an allowed row is skipped, with its binary searches and posting reads; a tile with one is
+ * streamed whole.  So a contiguous filter saves bandwidth and a scattered one does not, however selective: a doc-at-a-time path for
+ * those is out of scope. */
+int32_t arx_bm25_search_filtered(const int64_t* term_ptr, const uint32_t* post_row, const float* post_w, int32_t vocab, int64_t n_rows,
+                                 const uint64_t* allow, int32_t n_filters, const int32_t* filter_of, const int32_t* q_terms,
+                                 const int32_t* q_nterms, int32_t n_queries, int32_t n, float* out_scores, int64_t* out_ids,
+                                 int64_t idx_base, void* ws, int64_t ws_bytes, void* stream);
+int32_t arx_bm25_search_filtered_tuned(const int64_t* term_ptr, const uint32_t* post_row, const float* post_w, int32_t vocab,
+                                       int64_t n_rows, const uint64_t* allow, int32_t n_filters, const int32_t* filter_of,
+                                       const int32_t* q_terms, const int32_t* q_nterms, int32_t n_queries, int32_t n,
+                                       float* out_scores, int64_t* out_ids, int64_t idx_base, void* ws, int64_t ws_bytes,
+                                       int32_t tile_rows, int32_t max_blocks, void* stream);
 /* Debug tap: out (device f32 [row_hi - row_lo]) = the score of ONE query (q_terms device int32 [n_terms], ascending) for every row of
  * [row_lo, row_hi), 0 where the row holds none of its terms; the accumulation is the search's own. */
 int32_t arx_bm25_scores(const int64_t* term_ptr, const uint32_t* post_row, const float* post_w, int32_t vocab, int64_t n_rows,

@@ -657,6 +657,15 @@ def store_in_chroma_batched(chunks: List[Dict], embeddings: Sequence, db_path: s
 
 
 # --------------------------------------------------------------------------------------------- search (added step)
+def check_chunk_count(n_rows: int, chunks, *, where=None, keep_mask=None, where_document=None, group_by_paper: bool = False) -> None:
+    """`search_queries`: every mode that reads `chunks` (or `keep_mask`) row by row needs one entry per row of the shard; the first such
+    mode that is on names the mismatch."""
+    for mode, on, per_row in (("where", where is not None, chunks), ("keep_mask", keep_mask is not None, keep_mask),
+                              ("where_document", where_document is not None, chunks), ("group_by_paper", group_by_paper, chunks)):
+        if on and len(per_row) != n_rows:
+            raise ValueError(f"{mode}: {len(per_row)} {'chunks' if per_row is chunks else 'entries'} for the shard's {n_rows} rows")
+
+
 def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[str], top_k: int = 10,
                    output_dir: str = "./embeddings_saved", chunk_base: int = 0, reranker=None, rerank_top_k: int = 32,
                    hybrid_alpha: Optional[float] = None, where=None,
@@ -669,7 +678,8 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
     will be searched and nothing is uploaded here; the queries are encoded straight into an fp16 device matrix.  (A consumer that
     only has the `.npy` rows on disk builds a `store.HipCollection` instead.)  `chunks[j]` is row `chunk_base + j` of the corpus:
     with per-rank loading a rank only knows the chunk ids of its own rows, so the ids of the merged hits are exchanged (one
-    `all_gather_object` of at most Q x k small entries).
+    `all_gather_object` of at most Q x k small entries).  Between the encoded queries and the rerank step this is the pipeline
+    `HipCollection.query` runs too: `retrieval.RowFilters` builds the row bitmaps, `retrieval.retrieve` searches, picks by MMR and fuses.
     `reranker` (a `rerank.HipCrossEncoder`, or anything with its `predict`): the search fetches `rerank_top_k` candidates, each rank
     scores the (query, candidate) pairs whose texts it holds, the scores are exchanged over the host group, and the best `top_k` by
     rerank score are kept; every hit then carries `rerank_score` beside its cosine `score`.
@@ -712,6 +722,7 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
     list), `where_document`, `keep_mask` and `where_on_device`: the bitmaps the cosine search uses go to the keyword search unchanged
     (`KeywordIndex.search(allow=...)`, `arx_bm25_search_filtered`), so both candidate lists hold allowed rows only and the fusion is what it
     was.  The BM25 statistics stay those of the whole corpus (INTEGRATION.md "Hybrid search with filters")."""
+    from .retrieval import RowFilters, check_shared_query, retrieve
     if min_score is not None:
         from .ranging import check_range_query
         if reranker is not None:
@@ -724,150 +735,52 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
         from .grouping import check_grouped_query
         check_grouped_query(top_k, chunks_per_paper, grouped=True, reranker=reranker, hybrid_alpha=hybrid_alpha, mmr_lambda=mmr_lambda,
                             per_query_filters=isinstance(where, (list, tuple)), world=int(os.environ.get("WORLD_SIZE", "1")))
-    if keep_mask is not None and hybrid_alpha is not None and not hybrid_filters:
-        raise ValueError("keep_mask cannot be combined with hybrid_alpha: the BM25 keyword search has no row filter")
-    if mmr_lambda is not None:
-        if reranker is not None or hybrid_alpha is not None:
-            raise ValueError("mmr_lambda cannot be combined with reranker or hybrid_alpha: MMR re-orders the cosine search's candidates only")
-        if not (0.0 <= float(mmr_lambda) <= 1.0):
-            raise ValueError(f"mmr_lambda={mmr_lambda} must be in [0, 1]")
-        if not (1 <= top_k <= mmr_fetch_k <= MMR_MAX_FETCH_K):
-            raise ValueError(f"mmr_fetch_k={mmr_fetch_k} must be in [top_k, {MMR_MAX_FETCH_K}] (top_k={top_k})")
+    check_shared_query(top_k, hybrid_alpha=hybrid_alpha, hybrid_filters=hybrid_filters, reranker=reranker, mmr_lambda=mmr_lambda,
+                       n_fetch=mmr_fetch_k, fetch_refusal=f"mmr_fetch_k={mmr_fetch_k} must be in [top_k, {MMR_MAX_FETCH_K}] (top_k={top_k})",
+                       filters_first=(("keep_mask cannot be combined", keep_mask is not None),),
+                       filters=(("where cannot be combined", where is not None), ("where_document cannot be combined", where_document is not None)))
     import torch
     from .index import ShardIndex
-    if where is not None and hybrid_alpha is not None and not hybrid_filters:
-        raise ValueError("where cannot be combined with hybrid_alpha: the BM25 keyword search has no row filter")
-    if where_document is not None and hybrid_alpha is not None and not hybrid_filters:
-        raise ValueError("where_document cannot be combined with hybrid_alpha: the BM25 keyword search has no row filter")
     dist = _dist()
     rank = dist.get_rank() if dist else 0
     world = dist.get_world_size() if dist else 1
     dev = model.encoder.device
     qd = torch.empty((len(queries), model.get_sentence_embedding_dimension()), dtype=torch.float16, device=dev)
     model.encode(queries, batch_size=256, normalize_embeddings=True, convert_to_numpy=True, device_f16_out=qd, low_latency=True)
-    # int8 pre-filter (same exact answers; +50 % shard memory, one quantisation pass): 1.5-1.7x the queries per second on small batches
-    pre = "int8" if (shard.rows.shape[1] % 128 == 0 and shard.rows.shape[1] <= 1024 and shard.rows.shape[0] > 0) else None
-    k_search = rerank_top_k if reranker is not None else (mmr_fetch_k if mmr_lambda is not None else top_k)
-    n_cand = k_search if hybrid_alpha is None else (rerank_top_k if reranker is not None else HYBRID_CANDIDATES)
-    allow = n_allowed = None
-    where_each = None                                        # `where` as one entry per query: the bitmaps are built below, per distinct filter
-    if isinstance(where, (list, tuple)):
-        from .filter_sets import per_query_list
-        where_each, where = per_query_list(where, len(queries), "where"), None
-        pre = None
-    where_tree = None                                        # where_on_device: evaluated below, once the bitmap to and in is known
-    if where is not None and where_on_device:
-        from .where import compile_where
-        where_tree = compile_where(where)
-        if len(chunks) != shard.rows.shape[0]:
-            raise ValueError(f"where: {len(chunks)} chunks for the shard's {shard.rows.shape[0]} rows")
-    elif where is not None:
-        from .where import compile_where, evaluate, pack_bitmap
-        mask = evaluate(compile_where(where), [c.get("metadata") or {} for c in chunks])
-        if mask.shape[0] != shard.rows.shape[0]:
-            raise ValueError(f"where: {mask.shape[0]} chunks for the shard's {shard.rows.shape[0]} rows")
-        allow, n_allowed = torch.from_numpy(pack_bitmap(mask).view(np.int64)).to(dev), int(mask.sum())
-        pre = None                                           # a filtered search runs on the fp16 rows
-    if keep_mask is not None:
-        from .where import pack_bitmap
-        keep_mask = np.asarray(keep_mask, dtype=bool)
-        if keep_mask.shape[0] != shard.rows.shape[0]:
-            raise ValueError(f"keep_mask: {keep_mask.shape[0]} entries for the shard's {shard.rows.shape[0]} rows")
-        keep = torch.from_numpy(pack_bitmap(keep_mask).view(np.int64)).to(dev)
-        allow = keep if allow is None else (allow & keep).contiguous()
-        n_allowed = int(keep_mask.sum()) if (where is None or where_tree is not None) else int((mask & keep_mask).sum())
-        pre = None
-    if where_document is not None:
-        from .where_document import DocumentStore, compile_where_document
-        doc_tree = compile_where_document(where_document)
-        if len(chunks) != shard.rows.shape[0]:
-            raise ValueError(f"where_document: {len(chunks)} chunks for the shard's {shard.rows.shape[0]} rows")
-        docs = DocumentStore([c["text"] for c in chunks], device=dev)
-        if allow is None:
-            allow, n_allowed = docs.allow(doc_tree)
-        else:
-            allow = (allow & docs.fold(doc_tree)).contiguous()
-            n_allowed = docs.count(allow)
-        pre = None
-    if where_on_device:
-        from .where_device import MetadataColumns
-        columns = MetadataColumns([c.get("metadata") or {} for c in chunks], 0, len(chunks), dev)
-    if where_tree is not None:
-        bits, cnt = columns.allow_many([where_tree], allow)
-        allow, n_allowed, pre = bits[0], cnt[0], None
+    n_rows, dim = shard.rows.shape
+    check_chunk_count(n_rows, chunks, where=where, keep_mask=keep_mask, where_document=where_document, group_by_paper=group_by_paper)
+    if where_document is not None:                           # (one dict for the call: a list is refused, as anything else that is no filter)
+        from .where_document import compile_where_document
+        compile_where_document(where_document)
+    # int8 pre-filter (same exact answers; +50 % shard memory, one quantisation pass): 1.5-1.7x the queries per second on small batches;
+    # a filtered, a grouped and a range search run on the fp16 rows
+    masked = where is not None or keep_mask is not None or where_document is not None or group_by_paper or min_score is not None
+    index = ShardIndex(shard.rows, idx_base=shard.lo, prefilter="int8" if (dim % 128 == 0 and dim <= 1024 and n_rows > 0 and not masked) else None,
+                       adaptive=True)
+    if min_score is not None and world > 1:
+        raise ValueError("min_score needs a single GPU rank: a cross-rank merge of lists of up to 1024 rows is out of scope")
     if group_by_paper:
         from .grouping import runs_from_keys
-        if len(chunks) != shard.rows.shape[0]:
-            raise ValueError(f"group_by_paper: {len(chunks)} chunks for the shard's {shard.rows.shape[0]} rows")
-        group_of, paper_ids = runs_from_keys([(c.get("metadata") or {}).get("paper_id") for c in chunks], base=chunk_base)
-        pre = None                                           # a grouped search runs on the fp16 rows
-    if min_score is not None:
-        pre = None                                           # a range search runs on the fp16 rows
-    index = ShardIndex(shard.rows, idx_base=shard.lo, prefilter=pre, adaptive=True)
-    grp = truncated = None
-    kw_allow, kw_filter_of = allow, None                     # hybrid_filters: what the keyword side is restricted to (the dense side's bitmaps)
-    if min_score is not None:
-        if world > 1:
-            raise ValueError("min_score needs a single GPU rank: a cross-rank merge of lists of up to 1024 rows is out of scope")
-        s, i, counts = index.search_range(qd, float(min_score), top_k, allow=allow, n_allowed=n_allowed)
-        truncated = (counts > top_k).cpu().tolist()
-    elif group_by_paper:
         if world > 1:
             raise ValueError("group_by_paper needs a single GPU rank: a paper may straddle two ranks, and a cross-rank fold is out of scope")
+        group_of, paper_ids = runs_from_keys([(c.get("metadata") or {}).get("paper_id") for c in chunks], base=chunk_base)
         index.set_groups(group_of)
-        s, i, grp = index.search_grouped(qd, top_k, chunks_per_paper, allow=allow, n_allowed=n_allowed)
-        s, i, grp = s.reshape(len(queries), -1), i.reshape(len(queries), -1), grp.cpu().numpy()
-    elif where_each is not None:
-        from .filter_sets import distinct_filters
-        from .index import search_filtered_grouped
-        from .where import compile_where, evaluate, pack_bitmap
-        if len(chunks) != shard.rows.shape[0]:
-            raise ValueError(f"where: {len(chunks)} chunks for the shard's {shard.rows.shape[0]} rows")
-        pairs, filter_of = distinct_filters(where_each, [None] * len(queries))
-        metas = [c.get("metadata") or {} for c in chunks]
-        n_words = (len(chunks) + 63) // 64
-        bitmaps, counts = [], []
-        on_device = {}
-        if where_on_device:                                  # every distinct filter of the batch in one launch per 64, `allow` and-ed in
-            mine = [j for j, (w, _) in enumerate(pairs) if w is not None]
-            bits, cnt = columns.allow_many([compile_where(pairs[j][0]) for j in mine], allow)
-            on_device = {j: (bits[t], cnt[t] if allow is None else None) for t, j in enumerate(mine)}
-        for j, (w, _) in enumerate(pairs):                   # `allow` so far: the keep-mask and `where_document`, shared by every query
-            if j in on_device:
-                words, count = on_device[j]
-            elif w is None:
-                words = allow if allow is not None else torch.full((n_words,), -1, dtype=torch.int64, device=dev)
-                count = n_allowed if allow is not None else len(chunks)
-            else:
-                mask = evaluate(compile_where(w), metas)
-                words = torch.from_numpy(pack_bitmap(mask).view(np.int64)).to(dev)
-                words = words if allow is None else (words & allow).contiguous()
-                count = int(mask.sum()) if allow is None else None      # (counted only where it is free: it merely steers the path)
-            bitmaps.append(words)
-            counts.append(count)
-        s, i = search_filtered_grouped(index, qd, n_cand, bitmaps, filter_of, counts)
-        if hybrid_alpha is not None:
-            kw_allow, kw_filter_of = torch.stack(bitmaps).contiguous(), torch.tensor(list(filter_of), dtype=torch.int32, device=dev)
-    else:
-        s, i = index.search_distributed(qd, n_cand, allow=allow, n_allowed=n_allowed)
-    mmr_val = None
-    if mmr_lambda is not None:
-        from .mmr import mmr_select
-        order, mmr_val = mmr_select(index, qd, i, top_k, float(mmr_lambda))
-        pos = order.clamp(min=0).long()                          # (-1 where fewer than top_k rows were found: skipped below)
-        s = torch.where(order >= 0, s.gather(1, pos), torch.full_like(mmr_val, float("-inf")))
-        i = torch.where(order >= 0, i.gather(1, pos), torch.full_like(pos, -1))
-        mmr_val = mmr_val.cpu().numpy()
-    s, i = s.cpu().numpy(), i.cpu().numpy()
-    hyb = kws = None
-    if hybrid_alpha is not None:
-        from .keyword import KeywordIndex, fuse
+    # candidates per query where something picks among them afterwards: the reranker, MMR, or the fusion (each side's list)
+    n_cand = rerank_top_k if reranker is not None else (mmr_fetch_k if mmr_lambda is not None else HYBRID_CANDIDATES)
+
+    def keyword_index():                                     # (built per call, after the cosine search)
+        from .keyword import KeywordIndex
         if top_k > n_cand:
             raise ValueError(f"hybrid search keeps at most {n_cand} results per query (top_k={top_k})")
-        kw = KeywordIndex(texts=[c["text"] for c in chunks], tokenizer=model.tokenizer, stats="global" if world > 1 else None,
-                          idx_base=chunk_base, device=dev)
-        ks, ki = kw.search_distributed(queries, n_cand, allow=kw_allow, filter_of=kw_filter_of)
-        hyb, i, s, kws = fuse(s, i, ks.cpu().numpy(), ki.cpu().numpy(), float(hybrid_alpha), k_search)
+        return KeywordIndex(texts=[c["text"] for c in chunks], tokenizer=model.tokenizer, stats="global" if world > 1 else None,
+                            idx_base=chunk_base, device=dev)
+    # (a count the device would have to be waited for is left unknown for per-query lists: it merely steers the search's path)
+    filters = RowFilters([c.get("metadata") or {} for c in chunks] if where is not None else (), dev, 0, n_rows, keep_mask=keep_mask,
+                         texts=lambda: [c["text"] for c in chunks], where_on_device=where_on_device, count_both=False)
+    hit = retrieve(index, qd, filters, top_k, n_candidates=n_cand, reranked=reranker is not None, where=where, where_document=where_document,
+                   min_score=None if min_score is None else float(min_score), grouped=group_by_paper, chunks_per_group=chunks_per_paper, mmr_lambda=mmr_lambda,
+                   hybrid_alpha=hybrid_alpha, keyword=keyword_index, query_texts=queries)
+    s, i, grp, truncated, mmr_val, hyb, kws = hit.scores, hit.ids, hit.groups, hit.truncated, hit.mmr, hit.hybrid, hit.keyword
     if reranker is not None:
         from .rerank import rerank_candidates, reorder_by_rerank
         texts = {int(j): chunks[int(j) - chunk_base]["text"] for j in np.unique(i) if chunk_base <= j < chunk_base + len(chunks)}

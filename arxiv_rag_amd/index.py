@@ -113,7 +113,7 @@ class ShardIndex:
     def _options(self, cu_limit: int = 0, flags: int = 0, **debug) -> "_lib.TopkOptionsC":
         o = _lib.TopkOptionsC()
         o.i8_max_queries = 0 if self.i8_max_queries is None else (-1 if self.i8_max_queries <= 0 else int(self.i8_max_queries))
-        o.max_row_norm = max(self.max_row_norm(), 1.0 + 1.0 / 512.0)      # never below the encoder's unit-row bound
+        o.max_row_norm = self._norm_bound()
         o.cu_limit, o.flags = int(cu_limit), int(flags) | (_lib.TOPK_I8_CENTRE_QUERY if (self.centre_query and self._use_i8()) else 0)
         o.debug_tau_mult = float(debug.get("tau_mult", 0.0))
         o.debug_drop_best = int(debug.get("drop_best", 0))
@@ -135,6 +135,22 @@ class ShardIndex:
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.corpus.device)
         return self._ws
+
+    def _norm_bound(self) -> float:
+        """The rows' norm bound the searches pass to the library: never below the encoder's unit-row bound."""
+        return max(self.max_row_norm(), 1.0 + 1.0 / 512.0)
+
+    def _check_allow(self, allow: torch.Tensor):
+        n_words = (self.n_rows + 63) // 64
+        assert allow.is_cuda and allow.dtype in (torch.int64, torch.uint64) and allow.dim() == 1 and allow.is_contiguous()
+        assert allow.shape[0] == n_words, f"allow has {allow.shape[0]} words, the shard's {self.n_rows} rows need {n_words}"
+
+    def _masked_workspace(self, kind: str, need: int) -> torch.Tensor:
+        """The index's cached workspace of the masked searches of `kind`, at least `need` bytes."""
+        ws = self._ws_masked.get(kind)
+        if ws is None or ws.numel() < need:
+            ws = self._ws_masked[kind] = torch.empty(need, dtype=torch.uint8, device=self.corpus.device)
+        return ws
 
     # ---- one batch ------------------------------------------------------------------------------------------------------
     def search(self, queries_f16: torch.Tensor, k: int = 10, ws: Optional[torch.Tensor] = None, out=None,
@@ -223,12 +239,9 @@ class ShardIndex:
         if need < 0:
             raise _lib.ArxError(f"unsupported {kind} search shape n_rows={self.n_rows} nq={nq} dim={self.dim} k={k}")
         if ws is None:
-            ws = self._ws_masked.get(kind)
-            if ws is None or ws.numel() < need:
-                ws = self._ws_masked[kind] = torch.empty(need, dtype=torch.uint8, device=self.corpus.device)
-        norm = max(self.max_row_norm(), 1.0 + 1.0 / 512.0)       # never below the encoder's unit-row bound (as `_options`)
+            ws = self._masked_workspace(kind, need)
         st = torch.cuda.current_stream().cuda_stream if _stream is None else _stream
-        rc = call(nq, self.dim, k, scores.data_ptr(), ids.data_ptr(), self.idx_base, norm, ws.data_ptr(), ws.numel(),
+        rc = call(nq, self.dim, k, scores.data_ptr(), ids.data_ptr(), self.idx_base, self._norm_bound(), ws.data_ptr(), ws.numel(),
                   int(debug.get("path", 0)), int(debug.get("cand_cap", 0)), st)
         _lib.check(rc, f"arx_topk_search_{kind}")
         self._last_ws_masked[kind] = ws
@@ -244,16 +257,11 @@ class ShardIndex:
         return (int(a.value), int(b.value))
 
     def _search_filtered(self, q, k, allow, n_allowed, ws, out, _stream, debug):
-        def check_mask(nq):
-            n_words = (self.n_rows + 63) // 64
-            assert allow.is_cuda and allow.dtype in (torch.int64, torch.uint64) and allow.dim() == 1 and allow.is_contiguous()
-            assert allow.shape[0] == n_words, f"allow has {allow.shape[0]} words, the shard's {self.n_rows} rows need {n_words}"
-
         def call(*rest):
             return self.lib.arx_topk_search_filtered_tuned(self.corpus.data_ptr(), self.n_rows, allow.data_ptr(),
                                                            -1 if n_allowed is None else int(n_allowed), q.data_ptr(), *rest)
         return self._search_masked("filtered", "search(allow=...)", self.lib.arx_topk_filtered_workspace_bytes, q, k, ws, out, _stream, debug,
-                                   check_mask, call)
+                                   lambda nq: self._check_allow(allow), call)
 
     def filtered_stats(self, ws: Optional[torch.Tensor] = None) -> Tuple[int, int]:
         """(queries whose candidate list overflowed and were answered by the exhaustive path, candidate groups rescored) of the LAST
@@ -376,9 +384,7 @@ class ShardIndex:
         assert q.is_cuda and q.dtype == torch.float16 and q.dim() == 2 and q.shape[1] == self.dim and q.is_contiguous()
         nq = q.shape[0]
         if allow is not None:
-            n_words = (self.n_rows + 63) // 64
-            assert allow.is_cuda and allow.dtype in (torch.int64, torch.uint64) and allow.dim() == 1 and allow.is_contiguous()
-            assert allow.shape[0] == n_words, f"allow has {allow.shape[0]} words, the shard's {self.n_rows} rows need {n_words}"
+            self._check_allow(allow)
         need = self.lib.arx_topk_grouped_workspace_bytes(max(self.n_rows, 1), max(nq, 1), self.dim, P, m)
         if need < 0:
             raise _lib.ArxError(f"unsupported grouped search shape n_rows={self.n_rows} nq={nq} dim={self.dim} n_groups={P} "
@@ -389,15 +395,12 @@ class ShardIndex:
         if nq == 0 or self.n_rows == 0:
             return scores, ids, groups
         if ws is None:
-            ws = self._ws_masked.get("grouped")
-            if ws is None or ws.numel() < need:
-                ws = self._ws_masked["grouped"] = torch.empty(need, dtype=torch.uint8, device=self.corpus.device)
-        norm = max(self.max_row_norm(), 1.0 + 1.0 / 512.0)       # never below the encoder's unit-row bound (as `_options`)
+            ws = self._masked_workspace("grouped", need)
         rc = self.lib.arx_topk_search_grouped_tuned(self.corpus.data_ptr(), self.n_rows, self.group_of.data_ptr(),
                                                     int(self.max_run_rows if max_run_rows is None else max_run_rows),
                                                     None if allow is None else allow.data_ptr(), -1 if n_allowed is None else int(n_allowed),
                                                     q.data_ptr(), nq, self.dim, P, m, scores.data_ptr(), ids.data_ptr(), groups.data_ptr(),
-                                                    self.idx_base, norm, ws.data_ptr(), ws.numel(), int(path), int(cand_cap),
+                                                    self.idx_base, self._norm_bound(), ws.data_ptr(), ws.numel(), int(path), int(cand_cap),
                                                     torch.cuda.current_stream().cuda_stream)
         _lib.check(rc, "arx_topk_search_grouped")
         self._last_ws_masked["grouped"] = ws
@@ -433,9 +436,7 @@ class ShardIndex:
             raise ValueError(f"min_score has shape {tuple(ms.shape)}: a float or one entry per query ({nq},)")
         ms = ms.contiguous()
         if allow is not None:
-            n_words = (self.n_rows + 63) // 64
-            assert allow.is_cuda and allow.dtype in (torch.int64, torch.uint64) and allow.dim() == 1 and allow.is_contiguous()
-            assert allow.shape[0] == n_words, f"allow has {allow.shape[0]} words, the shard's {self.n_rows} rows need {n_words}"
+            self._check_allow(allow)
         need = self.lib.arx_range_workspace_bytes(max(self.n_rows, 1), max(nq, 1), self.dim, M)
         if need < 0:
             raise _lib.ArxError(f"unsupported range search shape n_rows={self.n_rows} nq={nq} dim={self.dim} max_results={M}")
@@ -448,13 +449,10 @@ class ShardIndex:
             scores.fill_(float("-inf")); ids.fill_(-1); counts.zero_()
             return scores, ids, counts
         if ws is None:
-            ws = self._ws_masked.get("range")
-            if ws is None or ws.numel() < need:
-                ws = self._ws_masked["range"] = torch.empty(need, dtype=torch.uint8, device=self.corpus.device)
-        norm = max(self.max_row_norm(), 1.0 + 1.0 / 512.0)       # never below the encoder's unit-row bound (as `_options`)
+            ws = self._masked_workspace("range", need)
         rc = self.lib.arx_range_search_tuned(self.corpus.data_ptr(), self.n_rows, None if allow is None else allow.data_ptr(),
                                              -1 if n_allowed is None else int(n_allowed), q.data_ptr(), ms.data_ptr(), nq, self.dim, M,
-                                             scores.data_ptr(), ids.data_ptr(), counts.data_ptr(), self.idx_base, norm, ws.data_ptr(),
+                                             scores.data_ptr(), ids.data_ptr(), counts.data_ptr(), self.idx_base, self._norm_bound(), ws.data_ptr(),
                                              ws.numel(), int(path), int(cand_cap), torch.cuda.current_stream().cuda_stream)
         _lib.check(rc, "arx_range_search")
         self._last_ws_masked["range"] = ws

@@ -1,0 +1,235 @@
+"""The retrieval pipeline `HipCollection.query` and `search_queries` share, between "the queries are an fp16 device matrix" and "rerank":
+
+    check_shared_query(...)                  the refusals both front ends state (each front end adds its own)
+    filters = RowFilters(metadata, device, keep_mask=..., documents=..., columns=...)
+    hit = retrieve(index, q, filters, n_results, where=..., mmr_lambda=..., hybrid_alpha=..., keyword=...)
+
+`RowFilters` turns `where`, `where_document` and the keep-mask into the row bitmaps of the masked searches; `retrieve` picks the search
+(`search_range`, `search_grouped`, `search_filtered_grouped`, `search_distributed`), re-orders by MMR and fuses with BM25, the keyword
+side restricted by the dense side's bitmaps.  Index construction, reranking and the shape of the results stay with the front ends.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Callable, Dict, Optional, Sequence, Tuple
+
+import numpy as np
+
+
+def check_shared_query(n_results: int, *, hybrid_alpha, hybrid_filters: bool, reranker, mmr_lambda, n_fetch: int, fetch_refusal: str,
+                       filters_first: Sequence[Tuple[str, bool]] = (), filters: Sequence[Tuple[str, bool]] = ()) -> None:
+    """The refusals both front ends have, each a ValueError: a row filter with `hybrid_alpha` (lifted by `hybrid_filters`), and the
+    `mmr_lambda` checks.  `filters_first` / `filters`: the front end's row filters as (the subject of its refusal, e.g. "where cannot be
+    combined" or "a collection built with dedup_threshold cannot be queried"; whether that filter is given), in the front end's order:
+    those it refuses before the `mmr_lambda` checks and those after.  `n_fetch`: the candidates MMR picks from, `fetch_refusal`: what
+    the front end says when it is not in [n_results, 32]."""
+    def refuse_filters(subjects):
+        for subject, given in subjects:
+            if given and hybrid_alpha is not None and not hybrid_filters:
+                raise ValueError(f"{subject} with hybrid_alpha: the BM25 keyword search has no row filter")
+    refuse_filters(filters_first)
+    if mmr_lambda is not None:
+        if reranker is not None or hybrid_alpha is not None:
+            raise ValueError("mmr_lambda cannot be combined with reranker or hybrid_alpha: MMR re-orders the cosine search's candidates only")
+        if not (0.0 <= float(mmr_lambda) <= 1.0):
+            raise ValueError(f"mmr_lambda={mmr_lambda} must be in [0, 1]")
+        if not (1 <= n_results <= n_fetch <= 32):
+            raise ValueError(fetch_refusal)
+    refuse_filters(filters)
+
+
+class RowFilters:
+    """The row bitmaps of one shard: `where` (evaluated on the host, or on the device with `where_on_device`), `where_document` and the
+    keep-mask, and-ed.  A bitmap is a device int64 tensor of ceil(n_rows / 64) words in the convention of `where.pack_bitmap`; whichever
+    way it is built, its bits are the same.  The count that comes with it only steers which path the masked search takes.
+
+    `metadata`: the dicts `where` reads, rows [lo, hi) of it being the shard's.  `keep_mask`: host bool [n_rows], the rows to search at
+    all (`keep_words`: its bitmap, where the front end has it on the device already).  `documents` / `columns`: callables returning the
+    shard's `where_document.DocumentStore` / `where_device.MetadataColumns`, for a front end that keeps its own (one without texts
+    raises its refusal there); without them the store is built from `texts()` and the columns from `metadata` when a filter first
+    needs them.  `cache`: the dict `where.evaluate` keeps its columns in.  `count_both`: False leaves the count of a per-query bitmap
+    that and-s a `where` with a `where_document` unknown (None) instead of waiting for the device to count it."""
+
+    def __init__(self, metadata: Sequence[Dict], device, lo: int = 0, hi: Optional[int] = None, *, keep_mask=None, keep_words=None,
+                 documents: Optional[Callable] = None, texts: Optional[Callable] = None, columns: Optional[Callable] = None,
+                 where_on_device: bool = False, cache: Optional[Dict] = None, count_both: bool = True):
+        self.metadata, self.device, self.lo, self.hi = metadata, device, lo, len(metadata) if hi is None else hi
+        self.n_rows = self.hi - self.lo
+        self.keep_mask = None if keep_mask is None else np.asarray(keep_mask, dtype=bool)
+        self._keep_words = keep_words
+        self._documents, self._texts, self._columns, self.where_on_device = documents, texts, columns, bool(where_on_device)
+        self.cache = {} if cache is None else cache
+        self.count_both = count_both
+
+    def documents(self):
+        if self._documents is None:
+            from .where_document import DocumentStore
+            store = DocumentStore(self._texts(), device=self.device)
+            self._documents = lambda: store
+        return self._documents()
+
+    def columns(self):
+        if self._columns is None:
+            from .where_device import MetadataColumns
+            cols = MetadataColumns(self.metadata, self.lo, self.hi, self.device)
+            self._columns = lambda: cols
+        return self._columns()
+
+    def _upload(self, mask):
+        import torch
+        from .where import pack_bitmap
+        return torch.from_numpy(pack_bitmap(mask).view(np.int64)).to(self.device)
+
+    def keep_words(self):
+        if self._keep_words is None and self.keep_mask is not None:
+            self._keep_words = self._upload(self.keep_mask)
+        return self._keep_words
+
+    def _doc_words(self, doc_tree, folds):
+        """The bitmap of a compiled `where_document` (None: None), folded once per distinct tree and call (`folds`)."""
+        if doc_tree is not None and doc_tree not in folds:
+            folds[doc_tree] = self.documents().fold(doc_tree)
+        return folds.get(doc_tree)
+
+    def _and_with(self, doc_tree, folds):
+        """What the device evaluation and-s into a `where` bitmap: the `where_document` bitmap and the keep-bitmap (None: neither)."""
+        key = ("&", doc_tree)
+        if key not in folds:
+            docs, keep = self._doc_words(doc_tree, folds), self.keep_words()
+            folds[key] = (docs & keep).contiguous() if docs is not None and keep is not None else (keep if docs is None else docs)
+        return folds[key]
+
+    def _allow(self, tree, doc_tree, folds, count=True):
+        """(bitmap, allowed rows) of a compiled `where`, a compiled `where_document` and the keep-mask; (None, None): none of the three."""
+        if tree is not None and self.where_on_device:
+            bits, counts = self.columns().allow_many([tree], self._and_with(doc_tree, folds))
+            return bits[0], counts[0]
+        if tree is None:
+            words = self._and_with(doc_tree, folds)
+            if doc_tree is not None:
+                return words, self.documents().count(words)
+            return words, None if words is None else int(self.keep_mask.sum())
+        from .where import evaluate
+        mask = evaluate(tree, self.metadata, self.lo, self.hi, cache=self.cache)
+        if self.keep_mask is not None:
+            mask = mask & self.keep_mask
+        words, n_allowed = self._upload(mask), int(mask.sum())
+        if doc_tree is not None:
+            words = (words & self._doc_words(doc_tree, folds)).contiguous()
+            n_allowed = self.documents().count(words) if count else None
+        return words, n_allowed
+
+    def allow_of(self, where, where_document=None):
+        """-> (bitmap or None, n_allowed or None) of one `where` dict, one `where_document` dict (either may be None) and the keep-mask."""
+        from .where import compile_where
+        from .where_document import compile_where_document
+        tree = compile_where(where) if where is not None else None
+        return self._allow(tree, compile_where_document(where_document) if where_document is not None else None, {})
+
+    def per_query(self, nq: int, where, where_document=None):
+        """`where` / `where_document` with one entry per query (a list or tuple of `nq` dicts or Nones; a dict or None is repeated) ->
+        (bitmaps, filter_of, counts): the bitmap of every distinct (where, where_document) pair, the keep-mask and-ed in (a list of
+        device tensors, or the one [F, W] tensor the device evaluation wrote when every pair has a `where`), for each query the index
+        of its bitmap (host), and the bitmaps' allowed rows.  A pair without any filter gets every row of the shard."""
+        import torch
+        from .filter_sets import distinct_filters, per_query_list
+        from .where import compile_where
+        from .where_document import compile_where_document
+        pairs, filter_of = distinct_filters(per_query_list(where, nq, "where"), per_query_list(where_document, nq, "where_document"))
+        if any(d is not None for _, d in pairs):
+            self.documents()
+        trees = []
+        for w, d in pairs:                                       # (a pair's where_document first: the same refusal comes first as ever)
+            doc_tree = compile_where_document(d) if d is not None else None
+            trees.append((compile_where(w) if w is not None else None, doc_tree))
+        folds, evaluated = {}, {}
+        mine = [j for j, (tree, _) in enumerate(trees) if tree is not None]
+        if self.where_on_device and self.n_rows > 0 and mine:
+            # every `where` of the batch in one `arx_where_eval` per 64, each with its own where_document / keep bitmap and-ed in
+            ands = [self._and_with(trees[j][1], folds) for j in mine]
+            if len({trees[j][1] for j in mine}) == 1:
+                and_with = ands[0]
+            else:
+                ones = torch.full(((self.n_rows + 63) // 64,), -1, dtype=torch.int64, device=self.device)
+                and_with = torch.stack([ones if a is None else a for a in ands]).contiguous()
+            bits, counts = self.columns().allow_many([trees[j][0] for j in mine], and_with)
+            if len(mine) == len(pairs):                          # the [F, W] tensor the kernel wrote is what the search reads, without a copy
+                return bits, filter_of, counts
+            evaluated = {j: (bits[t], counts[t]) for t, j in enumerate(mine)}
+        bitmaps, counts = [], []
+        for j, (tree, doc_tree) in enumerate(trees):
+            words, n_allowed = evaluated[j] if j in evaluated else self._allow(tree, doc_tree, folds, count=self.count_both)
+            if words is None:                                    # no filter for these queries: every row of the shard
+                words, n_allowed = torch.full(((self.n_rows + 63) // 64,), -1, dtype=torch.int64, device=self.device), self.n_rows
+            bitmaps.append(words)
+            counts.append(n_allowed)
+        return bitmaps, filter_of, counts
+
+
+@dataclass
+class Retrieved:
+    """What `retrieve` found, as numpy arrays on the host: `scores` f32 / `ids` int64 [Q, width], (-inf or nan, -1) padded; the others
+    None unless their mode ran."""
+    scores: np.ndarray
+    ids: np.ndarray
+    groups: Optional[np.ndarray] = None          # grouped: int32 [Q, P], the `group_of` value of every returned group (-1 pads)
+    group_sizes: Optional[np.ndarray] = None     # grouped: [Q, P], the chunks returned for each
+    truncated: Optional[list] = None             # min_score: one bool per query, more rows qualified than were asked for
+    mmr: Optional[np.ndarray] = None             # mmr_lambda: the objective at each pick
+    hybrid: Optional[np.ndarray] = None          # hybrid_alpha: the fused scores ...
+    keyword: Optional[np.ndarray] = None         # ... and the BM25 ones (nan where the row was not in the keyword list)
+
+
+def retrieve(index, q, filters: RowFilters, n_results: int, *, n_candidates: int = 32, reranked: bool = False, where=None, where_document=None,
+             min_score=None, grouped: bool = False, chunks_per_group: int = 1, mmr_lambda: Optional[float] = None,
+             hybrid_alpha: Optional[float] = None, keyword=None, query_texts: Optional[Sequence[str]] = None) -> Retrieved:
+    """One search of the fp16 device queries `q` over `index` (a `ShardIndex`), in the mode the arguments name, every refusal behind it.
+    The width: a range search (`min_score`) returns up to `n_candidates` rows with `reranked` and `n_results` without, a grouped search
+    `n_results` groups, every other search `n_candidates` rows when something picks among them afterwards (`reranked`, `mmr_lambda`,
+    `hybrid_alpha`) and `n_results` otherwise.  `where` / `where_document`: a dict each, or a list with one entry per query.
+    `mmr_lambda`: `mmr.mmr_select` picks `n_results` of the candidates, which come back in pick order.  `hybrid_alpha`: `keyword` (a
+    `keyword.KeywordIndex`, or a callable that builds one) fetches `n_candidates` rows for `query_texts`, restricted by the bitmaps the
+    cosine search was given, and `keyword.fuse` keeps the best `n_candidates` (`reranked`) or `n_results`."""
+    import torch
+    from .filter_sets import is_per_query
+    nq = q.shape[0]
+    k = n_candidates if (reranked or hybrid_alpha is not None or mmr_lambda is not None) else n_results
+    out = Retrieved(None, None)
+    kw_filter_of = None
+    if is_per_query(where) or is_per_query(where_document):
+        from .index import search_filtered_grouped
+        bitmaps, filter_of, counts = filters.per_query(nq, where, where_document)
+        s, i = search_filtered_grouped(index, q, k, bitmaps, filter_of, counts)
+        if hybrid_alpha is not None:
+            allow = bitmaps if torch.is_tensor(bitmaps) else torch.stack(list(bitmaps)).contiguous()
+            kw_filter_of = torch.tensor(list(filter_of), dtype=torch.int32, device=q.device)
+    else:
+        allow, n_allowed = filters.allow_of(where, where_document)
+        if min_score is not None:
+            from .ranging import thresholds
+            s, i, counts = index.search_range(q, thresholds(min_score, nq), n_candidates if reranked else n_results, allow=allow,
+                                              n_allowed=n_allowed)
+            out.truncated = (counts > s.shape[1]).cpu().tolist()
+        elif grouped:
+            s, i, grp = index.search_grouped(q, n_results, chunks_per_group, allow=allow, n_allowed=n_allowed)
+            out.groups = grp.cpu().numpy()
+            s, i = s.reshape(nq, -1), i.reshape(nq, -1)          # group by group; the padding stays (-inf, -1)
+        else:
+            s, i = index.search_distributed(q, k, allow=allow, n_allowed=n_allowed)
+    if mmr_lambda is not None:
+        from .mmr import mmr_select
+        order, mmr_val = mmr_select(index, q, i, n_results, float(mmr_lambda))
+        pos = order.clamp(min=0).long()                          # (-1 where fewer than n_results rows were found: masked here)
+        s = torch.where(order >= 0, s.gather(1, pos), torch.full_like(mmr_val, float("-inf")))
+        i = torch.where(order >= 0, i.gather(1, pos), torch.full_like(pos, -1))
+        out.mmr = mmr_val.cpu().numpy()
+    out.scores, out.ids = s.cpu().numpy(), i.cpu().numpy()
+    if grouped:
+        out.group_sizes = (out.ids.reshape(nq, n_results, chunks_per_group) >= 0).sum(axis=2)
+    if hybrid_alpha is not None:
+        from .keyword import fuse
+        kw = keyword() if callable(keyword) else keyword
+        ks, ki = kw.search_distributed(list(query_texts), n_candidates, allow=allow, filter_of=kw_filter_of)
+        out.hybrid, out.ids, out.scores, out.keyword = fuse(out.scores, out.ids, ks.cpu().numpy(), ki.cpu().numpy(), float(hybrid_alpha),
+                                                            n_candidates if reranked else n_results)
+    return out

@@ -160,127 +160,30 @@ class HipCollection:
     def count(self) -> int:
         return self.n_total
 
-    def _allow_of(self, where, doc_tree, device):
-        """(row bitmap on the device, number of allowed rows) of a `where` dict, a compiled `where_document` tree and the dedup
-        keep-bitmap, and-ed; (None, None) when there is none of the three."""
-        import torch
-        allow = n_allowed = None
-        if where is not None and getattr(self, "where_on_device", False):
-            from .where import compile_where
-            bits, counts = self._columns().allow_many([compile_where(where)], self._and_with_of(doc_tree))
-            return bits[0], counts[0]
-        if where is not None:
-            from .where import compile_where, evaluate, pack_bitmap
-            mask = evaluate(compile_where(where), self.metadata, self.lo, self.hi, cache=self._where_columns)
-            if self._keep_mask is not None:
-                mask = mask & self._keep_mask
-            allow, n_allowed = torch.from_numpy(pack_bitmap(mask).view(np.int64)).to(device), int(mask.sum())
-        if doc_tree is not None:
-            if allow is None:
-                allow, n_allowed = self.documents.allow(doc_tree)
-            else:
-                allow = (allow & self.documents.fold(doc_tree)).contiguous()
-                n_allowed = self.documents.count(allow)
-        if self._keep is not None:
-            if where is None and doc_tree is None:
-                allow, n_allowed = self._keep, int(self._keep_mask.sum())
-            elif where is None:                                  # (with `where` the host mask above already holds it)
-                allow = (allow & self._keep).contiguous()
-                n_allowed = self.documents.count(allow)
-        return allow, n_allowed
-
     def _columns(self):
         if self._device_columns is None:
             from .where_device import MetadataColumns
             self._device_columns = MetadataColumns(self.metadata, self.lo, self.hi, self.index.corpus.device)
         return self._device_columns
 
-    def _and_with_of(self, doc_tree):
-        """What `where_on_device` and-s into a `where` bitmap: the folded `where_document` bitmap and the dedup keep-bitmap (None: neither)."""
-        words = self.documents.fold(doc_tree) if doc_tree is not None else None
-        if self._keep is not None:
-            words = self._keep if words is None else (words & self._keep).contiguous()
-        return words
-
-    def _bitmaps_on_device(self, pairs, device):
-        """`where_on_device`: (bitmaps, counts) of the distinct (where, where_document) pairs of a per-query batch.  Every `where` is
-        lowered, and all of them are evaluated by one `arx_where_eval` per 64, each with its own `where_document` / keep bitmap and-ed in;
-        when every pair has a `where`, the [F, W] tensor the kernel wrote is what the search reads, without a copy."""
-        import torch
-        from .where import compile_where
-        from .where_document import compile_where_document
-        n_words = (self.hi - self.lo + 63) // 64
-        trees, ands, folded, rest = [], [], {}, {}
-        for j, (w, d) in enumerate(pairs):                       # (compiled in the default path's order: the same refusal comes first)
-            doc_tree = compile_where_document(d) if d is not None else None
-            if w is None:
-                rest[j] = doc_tree
-                continue
-            trees.append(compile_where(w))
-            key = None if d is None else json.dumps(d, sort_keys=True)
-            if key not in folded:                                # one fold per distinct where_document
-                folded[key] = self._and_with_of(doc_tree)
-            ands.append(folded[key])
-        bits, counts = None, []
-        if trees:
-            if len(folded) == 1:
-                and_with = ands[0]
-            else:
-                ones = torch.full((n_words,), -1, dtype=torch.int64, device=device)
-                and_with = torch.stack([ones if a is None else a for a in ands]).contiguous()
-            bits, counts = self._columns().allow_many(trees, and_with)
-        if not rest:
-            return bits, counts
-        bitmaps, cnt, t = [], [], 0
-        for j in range(len(pairs)):
-            if j not in rest:
-                bitmaps.append(bits[t])
-                cnt.append(counts[t])
-                t += 1
-                continue
-            allow, n_allowed = self._allow_of(None, rest[j], device)
-            if allow is None:
-                allow, n_allowed = torch.full((n_words,), -1, dtype=torch.int64, device=device), self.hi - self.lo
-            bitmaps.append(allow)
-            cnt.append(n_allowed)
-        return bitmaps, cnt
-
-    def _search_per_query(self, q, k, where, where_document):
-        """The search of `query` when `where` / `where_document` hold one entry per query: one bitmap per distinct pair, one
-        `search_filtered_many` per 64 of them."""
-        from .index import search_filtered_grouped
-        bitmaps, filter_of, counts = self._per_query_bitmaps(q.shape[0], where, where_document, q.device)
-        return search_filtered_grouped(self.index, q, k, bitmaps, filter_of, counts)
-
-    def _per_query_bitmaps(self, nq, where, where_document, device):
-        """-> (bitmaps, filter_of, counts) of a per-query batch: the bitmap of every distinct (where, where_document) pair (a list of
-        device tensors or one [F, W] tensor), the index of each query's bitmap (host) and the bitmaps' allowed rows."""
-        import torch
-        from .filter_sets import distinct_filters, per_query_list
-        pairs, filter_of = distinct_filters(per_query_list(where, nq, "where"), per_query_list(where_document, nq, "where_document"))
-        if any(d is not None for _, d in pairs) and self.documents is None:
+    def _documents(self):
+        if self.documents is None:
             raise ValueError("where_document needs a collection built with documents=True")
-        if getattr(self, "where_on_device", False) and self.hi > self.lo:
-            bitmaps, counts = self._bitmaps_on_device(pairs, device)
-            return bitmaps, filter_of, counts
-        bitmaps, counts = [], []
-        for w, d in pairs:
-            doc_tree = None
-            if d is not None:
-                from .where_document import compile_where_document
-                doc_tree = compile_where_document(d)
-            allow, n_allowed = self._allow_of(w, doc_tree, device)
-            if allow is None:                                    # no filter for these queries: every row of the shard
-                allow = torch.full(((self.hi - self.lo + 63) // 64,), -1, dtype=torch.int64, device=device)
-                n_allowed = self.hi - self.lo
-            bitmaps.append(allow)
-            counts.append(n_allowed)
-        return bitmaps, filter_of, counts
+        return self.documents
+
+    def _row_filters(self):
+        """This shard's `retrieval.RowFilters`: the bitmaps of `where`, `where_document` and the dedup keep-bitmap."""
+        from .retrieval import RowFilters
+        return RowFilters(self.metadata, self.index.corpus.device, self.lo, self.hi, keep_mask=self._keep_mask, keep_words=self._keep,
+                          documents=self._documents, columns=self._columns, where_on_device=getattr(self, "where_on_device", False),
+                          cache=self._where_columns)
 
     def query(self, query_embeddings=None, query_texts: Optional[Sequence[str]] = None, n_results: int = 10, reranker=None,
               n_candidates: int = 32, hybrid_alpha: Optional[float] = None, where=None, where_document=None,
               mmr_lambda: Optional[float] = None, group_by=None, chunks_per_group: int = 1, min_score=None) -> Dict:
-        """`reranker` (a `rerank.HipCrossEncoder`; needs `query_texts`): the search fetches `n_candidates` (<= 32) rows per query,
+        """Between the encoded queries and the rerank step this is the pipeline `search_queries` runs too: `retrieval.RowFilters` builds
+        the row bitmaps, `retrieval.retrieve` searches, picks by MMR and fuses.
+        `reranker` (a `rerank.HipCrossEncoder`; needs `query_texts`): the search fetches `n_candidates` (<= 32) rows per query,
         the cross-encoder scores (query, document) for each, and the best `n_results` come back in reranked order with an added
         `rerank_scores` list per query (`scores` / `distances` stay the cosine ones).
         `hybrid_alpha` (a float in [0, 1]; needs `query_texts` and a collection built with `keyword=True`; None = cosine only): the
@@ -338,38 +241,26 @@ class HipCollection:
         import torch
         from .filter_sets import is_per_query
         from .grouping import check_grouped_query
-        from .ranging import RERANK_BATCH, check_range_query, thresholds
+        from .ranging import RERANK_BATCH, check_range_query
+        from .retrieval import check_shared_query, retrieve
+        per_query = is_per_query(where) or is_per_query(where_document)
         check_range_query(n_results, ranged=min_score is not None, reranker=reranker, n_candidates=n_candidates, hybrid_alpha=hybrid_alpha,
-                          mmr_lambda=mmr_lambda, group_by=group_by, per_query_filters=is_per_query(where) or is_per_query(where_document),
-                          world=getattr(self, "world", 1))
+                          mmr_lambda=mmr_lambda, group_by=group_by, per_query_filters=per_query, world=getattr(self, "world", 1))
         check_grouped_query(n_results, chunks_per_group, grouped=bool(group_by), has_group_key=getattr(self, "group_key", None) is not None,
-                            reranker=reranker, hybrid_alpha=hybrid_alpha, mmr_lambda=mmr_lambda,
-                            per_query_filters=is_per_query(where) or is_per_query(where_document), world=getattr(self, "world", 1))
-        filtered_hybrid = hybrid_alpha is not None and getattr(self, "hybrid_filters", False)
-        per_query = None
-        if is_per_query(where) or is_per_query(where_document):
-            if hybrid_alpha is not None and not filtered_hybrid:
-                raise ValueError("where cannot be combined with hybrid_alpha: the BM25 keyword search has no row filter")
-            per_query, where, where_document = (where, where_document), None, None
-        if self._keep is not None and hybrid_alpha is not None and not filtered_hybrid:
-            raise ValueError("a collection built with dedup_threshold cannot be queried with hybrid_alpha: the BM25 keyword search has no "
-                             "row filter")
-        if mmr_lambda is not None:
-            if reranker is not None or hybrid_alpha is not None:
-                raise ValueError("mmr_lambda cannot be combined with reranker or hybrid_alpha: MMR re-orders the cosine search's candidates only")
-            if not (0.0 <= float(mmr_lambda) <= 1.0):
-                raise ValueError(f"mmr_lambda={mmr_lambda} must be in [0, 1]")
-            if not (1 <= n_results <= n_candidates <= 32):
-                raise ValueError(f"n_candidates={n_candidates} must be in [n_results, 32] (the search's k limit) and n_results at least 1")
-        if where_document is not None:
-            if hybrid_alpha is not None and not filtered_hybrid:
-                raise ValueError("where_document cannot be combined with hybrid_alpha: the BM25 keyword search has no row filter")
-            if self.documents is None:
-                raise ValueError("where_document needs a collection built with documents=True")
+                            reranker=reranker, hybrid_alpha=hybrid_alpha, mmr_lambda=mmr_lambda, per_query_filters=per_query,
+                            world=getattr(self, "world", 1))
+        check_shared_query(
+            n_results, hybrid_alpha=hybrid_alpha, hybrid_filters=getattr(self, "hybrid_filters", False), reranker=reranker,
+            mmr_lambda=mmr_lambda, n_fetch=n_candidates,
+            fetch_refusal=f"n_candidates={n_candidates} must be in [n_results, 32] (the search's k limit) and n_results at least 1",
+            filters_first=(("where cannot be combined", per_query),           # (a per-query list of either argument is refused as `where`)
+                           ("a collection built with dedup_threshold cannot be queried", self._keep is not None)),
+            filters=(("where_document cannot be combined", where_document is not None and not per_query),
+                     ("where cannot be combined", where is not None and not per_query)))
+        if where_document is not None and not per_query:         # (refused here, before the queries are encoded)
             from .where_document import compile_where_document
-            doc_tree = compile_where_document(where_document)
-        if where is not None and hybrid_alpha is not None and not filtered_hybrid:
-            raise ValueError("where cannot be combined with hybrid_alpha: the BM25 keyword search has no row filter")
+            self._documents()
+            compile_where_document(where_document)
         if hybrid_alpha is not None:
             if not (0.0 <= float(hybrid_alpha) <= 1.0):
                 raise ValueError(f"hybrid_alpha={hybrid_alpha} must be in [0, 1]")
@@ -389,47 +280,10 @@ class HipCollection:
         q = torch.from_numpy(np.ascontiguousarray(query_embeddings, dtype=np.float16)).to(self.index.corpus.device)
         if q.dim() == 1:
             q = q[None]
-        wide = reranker is not None or hybrid_alpha is not None or mmr_lambda is not None
-        grp = truncated = None
-        kw_allow = kw_filter_of = None                           # hybrid_filters: the dense side's bitmaps, for the keyword side
-        if min_score is not None:
-            allow, n_allowed = self._allow_of(where, doc_tree if where_document is not None else None, q.device)
-            s, i, counts = self.index.search_range(q, thresholds(min_score, q.shape[0]), n_candidates if reranker is not None else n_results,
-                                                   allow=allow, n_allowed=n_allowed)
-            truncated = (counts > s.shape[1]).cpu().tolist()
-        elif group_by:
-            allow, n_allowed = self._allow_of(where, doc_tree if where_document is not None else None, q.device)
-            s, i, grp = self.index.search_grouped(q, n_results, chunks_per_group, allow=allow, n_allowed=n_allowed)
-            grp = grp.cpu().numpy()
-            sizes = (i >= 0).sum(dim=2).cpu().numpy()
-            s, i = s.reshape(q.shape[0], -1), i.reshape(q.shape[0], -1)      # paper by paper; the padding is dropped below
-        elif per_query is not None and filtered_hybrid:
-            from .index import search_filtered_grouped
-            bitmaps, filter_of, counts = self._per_query_bitmaps(q.shape[0], *per_query, q.device)
-            s, i = search_filtered_grouped(self.index, q, n_candidates, bitmaps, filter_of, counts)
-            kw_allow = bitmaps if torch.is_tensor(bitmaps) else torch.stack(list(bitmaps)).contiguous()
-            kw_filter_of = torch.tensor(list(filter_of), dtype=torch.int32, device=q.device)
-        elif per_query is not None:
-            s, i = self._search_per_query(q, n_candidates if wide else n_results, *per_query)
-        else:
-            allow, n_allowed = self._allow_of(where, doc_tree if where_document is not None else None, q.device)
-            s, i = self.index.search_distributed(q, n_candidates if wide else n_results, allow=allow, n_allowed=n_allowed)
-            kw_allow = allow if filtered_hybrid else None
-        mmr_val = None
-        if mmr_lambda is not None:
-            from .mmr import mmr_select
-            order, mmr_val = mmr_select(self.index, q, i, n_results, float(mmr_lambda))
-            pos = order.clamp(min=0).long()                      # (-1 where fewer than n_results rows were found: masked below)
-            s = torch.where(order >= 0, s.gather(1, pos), torch.full_like(mmr_val, float("-inf")))
-            i = torch.where(order >= 0, i.gather(1, pos), torch.full_like(pos, -1))
-            mmr_val = mmr_val.cpu().numpy()
-        s, i = s.cpu().numpy(), i.cpu().numpy()
-        hyb = kws = None
-        if hybrid_alpha is not None:
-            from .keyword import fuse
-            ks, ki = self.keyword.search_distributed(list(query_texts), n_candidates, allow=kw_allow, filter_of=kw_filter_of)
-            hyb, i, s, kws = fuse(s, i, ks.cpu().numpy(), ki.cpu().numpy(), float(hybrid_alpha),
-                                  n_candidates if reranker is not None else n_results)
+        hit = retrieve(self.index, q, self._row_filters(), n_results, n_candidates=n_candidates, reranked=reranker is not None, where=where,
+                       where_document=where_document, min_score=min_score, grouped=bool(group_by), chunks_per_group=chunks_per_group,
+                       mmr_lambda=mmr_lambda, hybrid_alpha=hybrid_alpha, keyword=self.keyword, query_texts=query_texts)
+        s, i, hyb, kws = hit.scores, hit.ids, hit.hybrid, hit.keyword
         if reranker is not None:
             from .rerank import rerank_candidates, reorder_by_rerank
             texts = {int(j): self.metadata[int(j)].get("text") or "" for j in np.unique(i) if j >= 0}
@@ -458,13 +312,13 @@ class HipCollection:
             out["distances"].append((2.0 - 2.0 * s[qi][keep]).tolist())
             out["documents"].append([m.get("text") for m in ms])
             out["metadatas"].append([{k: m.get(k) for k in ("paper_id", "section", "quality_score")} for m in ms])
-        if grp is not None:
-            out["group_keys"] = [[self.group_keys[int(v)] for v in grp[qi] if v >= 0] for qi in range(q.shape[0])]
-            out["group_sizes"] = [[int(n) for n, v in zip(sizes[qi], grp[qi]) if v >= 0] for qi in range(q.shape[0])]
-        if truncated is not None:
-            out["truncated"] = truncated
-        if mmr_val is not None:
-            out["mmr_scores"] = [mmr_val[qi][i[qi] >= 0].tolist() for qi in range(q.shape[0])]
+        if hit.groups is not None:
+            out["group_keys"] = [[self.group_keys[int(v)] for v in hit.groups[qi] if v >= 0] for qi in range(q.shape[0])]
+            out["group_sizes"] = [[int(n) for n, v in zip(hit.group_sizes[qi], hit.groups[qi]) if v >= 0] for qi in range(q.shape[0])]
+        if hit.truncated is not None:
+            out["truncated"] = hit.truncated
+        if hit.mmr is not None:
+            out["mmr_scores"] = [hit.mmr[qi][i[qi] >= 0].tolist() for qi in range(q.shape[0])]
         if reranker is not None:
             out["rerank_scores"] = rr
         if hyb is not None:

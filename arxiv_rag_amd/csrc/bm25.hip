@@ -25,6 +25,9 @@
 // its row's bit is set, and the accumulator is cleared either way.  Scores and idf are untouched, so an allowed row has the bits the
 // unfiltered search gives it.  Out of scope: a doc-at-a-time path for very selective SCATTERED filters.  Such a filter still streams
 // the postings of every tile it touches; only filters that leave whole tiles empty (contiguous ranges) save bandwidth.
+//
+// Wide lists (bm25_wide_kernel, arx_bm25_search_wide; at the end of this file): n up to 1024 through the same accumulation and keys, with
+// a longer LDS list cut back by a bitonic sort and a merge kernel of its own.  The kernels above and their n <= 32 limit are untouched.
 #include "arx_common.h"
 
 namespace {
@@ -69,10 +72,11 @@ __device__ __forceinline__ long long lower_bound_row(const uint32_t* __restrict_
 }
 
 // acc[0 .. tile_rows) (all zero on entry) += impacts of the query's terms for rows [tile_lo, tile_hi), in term order.
-// Ends with a barrier: acc is complete for every thread on return.
+// Ends with a barrier: acc is complete for every thread on return.  Smem: Bm25Smem or Bm25WideSmem (its lo[] / hi[] are used).
+template <class Smem>
 __device__ __forceinline__ void bm25_accumulate_tile(const long long* __restrict__ term_ptr, const uint32_t* __restrict__ post_row,
                                                      const float* __restrict__ post_w, int vocab, const int32_t* __restrict__ terms, int nt,
-                                                     uint32_t tile_lo, uint32_t tile_hi, int tile_rows, float* acc, Bm25Smem& sm) {
+                                                     uint32_t tile_lo, uint32_t tile_hi, int tile_rows, float* acc, Smem& sm) {
     const int tid = threadIdx.x;
     if (tid < 2 * BM25_MAXT) {
         const int j = tid & (BM25_MAXT - 1);
@@ -346,5 +350,247 @@ extern "C" int32_t arx_bm25_scores(const int64_t* term_ptr, const uint32_t* post
     bm25_scores_kernel<<<(int)blocks, BM25_NT, smem, (hipStream_t)stream>>>((const long long*)term_ptr, post_row, post_w, vocab, q_terms, n_terms,
                                                                             row_lo, row_hi, tile_rows, out);
     ARX_HIP_CHECK(hipGetLastError());
+    return ARX_OK;
+}
+
+// ---- wide top-n: n <= 1024 (arx_bm25_search_wide; hybrid search with long candidate lists, opt-in: hybrid_on_device) ---------------------
+// The same walk over row tiles, the same accumulation (bm25_accumulate_tile) and the same 64-bit keys as bm25_search_kernel; what differs
+// is how the candidate list is kept and how the per-block lists are merged:
+//   list     BM25_WIDE_CAP = 4096 keys (32 KiB).  A chunk appends at most 1024 keys, so after a cut to n <= 1024 keys at least
+//            (4096 - 1024) / 1024 = 3 chunks pass before the next cut can be needed; once the n-th key has risen most chunks append little.
+//   cut      a block-wide bitonic sort of the list (descending, over the next power of two >= its length, 64 at least), as range.hip cuts
+//            its list: log2(m) (log2(m) + 1) / 2 barriers (78 at m = 4096) instead of n rounds of a max-reduction.  The compare-exchange
+//            steps with a distance below 32 keys read two 8-byte words per lane at a stride of two: a 2-way LDS bank conflict on 15 of the
+//            78 steps, accepted.
+//   LDS      tile_rows * 4 + sizeof(Bm25WideSmem) (32 KiB keys + ~1.1 KiB) [+ 1.5 KiB bitmap words when filtered].  The default tile is
+//            BM25_WIDE_TILE = 10240 rows: 40 + 33.1 + 1.5 = 74.6 KiB, TWO blocks per 160 KiB CU (149.2 KiB).  A tuned call may still ask
+//            for up to 12288 rows (82.6 KiB: one block per CU).
+//   partial  every block writes its n best keys [blocks, nq, n] as 64-bit keys (0 = none), sorted; blocks <= min(512, 65536 / n), so a
+//            query spreads over 64 blocks at n = 1024.
+//   merge    bm25_wide_merge_kernel, one block per query: the blocks * n keys stream through the same 4096-key LDS list, 1024 per round,
+//            with the same sort-and-cut; its result is the exact n largest keys of the union whatever the block count.
+// The keys are distinct (distinct rows), so "the n largest keys" is one well-defined set and order: for n <= 32 the output has the bits of
+// arx_bm25_search / arx_bm25_search_filtered, and the m-list is a prefix of the n-list.  No float atomics, no global atomics; the LDS
+// slot counter is an integer atomic whose order cannot reach the output.
+namespace {
+
+constexpr int BM25_WIDE_KMAX = 1024;
+constexpr int BM25_WIDE_CAP = 4096;             // candidate keys in LDS (32 KiB)
+constexpr int BM25_WIDE_TILE = 10240;           // default tile: two blocks per CU (see above)
+constexpr int BM25_WIDE_PART_KEYS = 65536;      // blocks * n <= this: bounds the partial lists of a query (512 KiB)
+
+struct Bm25WideSmem {
+    unsigned long long keys[BM25_WIDE_CAP];
+    unsigned long long thr;
+    long long lo[BM25_MAXT], hi[BM25_MAXT];
+    int cnt;
+};
+
+// keys[0 .. c) -> descending order (bitonic over m = the next power of two >= max(c, 64), the slots in [c, m) zeroed).  The whole block,
+// c block-uniform and <= BM25_WIDE_CAP; earlier writes to keys[] are behind a barrier already; ends with a barrier.
+__device__ __forceinline__ void bm25_wide_sort_desc(unsigned long long* keys, int c) {
+    const int tid = threadIdx.x;
+    int m = 64;
+    while (m < c) m <<= 1;
+    for (int i = c + tid; i < m; i += BM25_NT) keys[i] = 0ull;
+    __syncthreads();
+    for (int k = 2; k <= m; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int t = tid; t < (m >> 1); t += BM25_NT) {
+                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), p = i | j;          // p < m <= BM25_WIDE_CAP
+                const unsigned long long a = keys[i], b = keys[p];
+                if (((i & k) == 0) ? a < b : a > b) { keys[i] = b; keys[p] = a; }
+            }
+            __syncthreads();
+        }
+}
+
+// cut the list (c keys, any order) back to its n largest, sorted; updates cnt and thr.  The whole block, c uniform; ends with a barrier.
+__device__ __forceinline__ void bm25_wide_cut(Bm25WideSmem& sm, int c, int n) {
+    bm25_wide_sort_desc(sm.keys, c);
+    if (threadIdx.x == 0) {
+        sm.cnt = c < n ? c : n;
+        sm.thr = c >= n ? sm.keys[n - 1] : 0ull;
+    }
+    __syncthreads();
+}
+
+__device__ __forceinline__ void bm25_wide_append(Bm25WideSmem& sm, unsigned long long key, unsigned long long thr) {
+    if (key > thr) {
+        const int pos = atomicAdd(&sm.cnt, 1);               // integer slot counter; pos < CAP: the caller cuts before a round that could overflow
+        if (pos < BM25_WIDE_CAP) sm.keys[pos] = key;
+    }
+}
+
+// part_k != null: the block's n best keys -> part_k[blocks, nq, n]; null (one block per query): the final (score, id) lists -> out_s / out_i
+template <bool FILTERED>
+__global__ __launch_bounds__(BM25_NT) void bm25_wide_kernel(const long long* __restrict__ term_ptr, const uint32_t* __restrict__ post_row,
+                                                            const float* __restrict__ post_w, int vocab, long long n_rows,
+                                                            const unsigned long long* __restrict__ allow, int n_filters,
+                                                            const int32_t* __restrict__ filter_of, const int32_t* __restrict__ q_terms,
+                                                            const int32_t* __restrict__ q_nterms, int n, int tile_rows,
+                                                            unsigned long long* __restrict__ part_k, float* __restrict__ out_s,
+                                                            long long* __restrict__ out_i, long long idx_base) {
+    extern __shared__ __attribute__((aligned(16))) float acc[];               // [tile_rows] f32, then Bm25WideSmem [, Bm25FilterSmem]
+    Bm25WideSmem& sm = *reinterpret_cast<Bm25WideSmem*>(acc + tile_rows);
+    const int tid = threadIdx.x, q = blockIdx.y, nq = gridDim.y;
+    const int32_t* terms = q_terms + (long long)q * BM25_MAXT;
+    int nt = min(max(q_nterms[q], 0), BM25_MAXT);
+    [[maybe_unused]] Bm25FilterSmem* fs = nullptr;
+    [[maybe_unused]] const unsigned long long* bitmap = nullptr;
+    [[maybe_unused]] const long long n_words = (n_rows + 63) >> 6;
+    if constexpr (FILTERED) {
+        fs = reinterpret_cast<Bm25FilterSmem*>(&sm + 1);
+        const int f = filter_of ? filter_of[q] : 0;
+        if (f >= 0 && f < n_filters) bitmap = allow + (long long)f * n_words;
+        else nt = 0;                                         // no such filter: the query sees no row and nothing is read
+    }
+    for (int i = tid; i < tile_rows; i += BM25_NT) acc[i] = 0.f;
+    if (tid == 0) { sm.cnt = 0; sm.thr = 0ull; }
+    __syncthreads();
+    const long long n_tiles = (n_rows + tile_rows - 1) / tile_rows;
+    for (long long t = blockIdx.x; t < n_tiles && nt > 0; t += gridDim.x) {
+        const long long lo = t * tile_rows;
+        const long long hi = min(lo + (long long)tile_rows, n_rows);
+        if constexpr (FILTERED) {
+            // the tile's bitmap words -> LDS (the previous tile's scan ended with a barrier); lo is a multiple of 1024
+            unsigned long long w = 0ull;
+            if (tid < (tile_rows >> 6)) {                    // tile_rows <= BM25_TILE_MAX: inside fs->bits
+                const long long wi = (lo >> 6) + tid;
+                if (wi < n_words) {
+                    w = bitmap[wi];
+                    const long long left = n_rows - (wi << 6);
+                    if (left < 64) w &= ~0ull >> (64 - (int)left);
+                }
+                fs->bits[tid] = w;
+            }
+            if (!__syncthreads_or(w != 0ull)) continue;     // no allowed row: no binary searches, no posting reads; acc is still zero
+        }
+        bm25_accumulate_tile(term_ptr, post_row, post_w, vocab, terms, nt, (uint32_t)lo, (uint32_t)hi, tile_rows, acc, sm);
+        const int rows = (int)(hi - lo);
+        for (int c0 = 0; c0 < rows; c0 += BM25_CHUNK) {
+            const int c = sm.cnt;
+            __syncthreads();                                 // everyone has read cnt before anyone appends
+            if (c + BM25_CHUNK > BM25_WIDE_CAP) bm25_wide_cut(sm, c < BM25_WIDE_CAP ? c : BM25_WIDE_CAP, n);
+            const unsigned long long thr = sm.thr;
+            const int i = c0 + 2 * tid;                      // tile_rows is even and acc is zero beyond `rows`
+            if (i < tile_rows) {
+                const float2 v = *reinterpret_cast<const float2*>(acc + i);
+                *reinterpret_cast<float2*>(acc + i) = make_float2(0.f, 0.f);
+                const float s[2] = {v.x, v.y};
+                [[maybe_unused]] unsigned int ok = 3u;      // the two rows' bits: i is even, so both lie in one bitmap word
+                if constexpr (FILTERED) ok = (unsigned int)(fs->bits[i >> 6] >> (i & 63)) & 3u;
+#pragma unroll
+                for (int e = 0; e < 2; ++e) {
+                    if (s[e] > 0.f && (!FILTERED || ((ok >> e) & 1u)))
+                        bm25_wide_append(sm, ((unsigned long long)__float_as_uint(s[e]) << 32) |
+                                                 (unsigned long long)(0xffffffffu - (uint32_t)(lo + i + e)), thr);
+                }
+            }
+            __syncthreads();
+        }
+    }
+    const int c = sm.cnt < BM25_WIDE_CAP ? sm.cnt : BM25_WIDE_CAP;
+    bm25_wide_sort_desc(sm.keys, c);
+    for (int r = tid; r < n; r += BM25_NT) {
+        const unsigned long long key = r < c ? sm.keys[r] : 0ull;
+        if (part_k) {
+            part_k[((long long)blockIdx.x * nq + q) * n + r] = key;
+        } else {
+            out_s[(long long)q * n + r] = key ? __uint_as_float((uint32_t)(key >> 32)) : -INFINITY;
+            out_i[(long long)q * n + r] = key ? (long long)(0xffffffffu - (uint32_t)key) + idx_base : -1ll;
+        }
+    }
+}
+
+// one block per query: the parts * n keys of the query's partial lists -> its n largest, as (score, id)
+__global__ __launch_bounds__(BM25_NT) void bm25_wide_merge_kernel(const unsigned long long* __restrict__ part_k, int parts, int nq, int n,
+                                                                  float* __restrict__ out_s, long long* __restrict__ out_i, long long idx_base) {
+    __shared__ Bm25WideSmem sm;
+    const int tid = threadIdx.x, q = blockIdx.x;
+    if (tid == 0) { sm.cnt = 0; sm.thr = 0ull; }
+    __syncthreads();
+    const int total = parts * n;                             // <= BM25_WIDE_PART_KEYS
+    for (int e0 = 0; e0 < total; e0 += BM25_CHUNK) {         // block-uniform
+        const int c = sm.cnt;
+        __syncthreads();                                     // everyone has read cnt before anyone appends
+        if (c + BM25_CHUNK > BM25_WIDE_CAP) bm25_wide_cut(sm, c < BM25_WIDE_CAP ? c : BM25_WIDE_CAP, n);
+        const unsigned long long thr = sm.thr;
+#pragma unroll
+        for (int u = 0; u < BM25_CHUNK / BM25_NT; ++u) {
+            const int e = e0 + u * BM25_NT + tid;
+            if (e < total) {
+                const int p = e / n, r = e - p * n;
+                bm25_wide_append(sm, part_k[((long long)p * nq + q) * n + r], thr);      // (thr >= 0: an empty slot is never appended)
+            }
+        }
+        __syncthreads();
+    }
+    const int c = sm.cnt < BM25_WIDE_CAP ? sm.cnt : BM25_WIDE_CAP;
+    bm25_wide_sort_desc(sm.keys, c);
+    for (int r = tid; r < n; r += BM25_NT) {
+        const unsigned long long key = r < c ? sm.keys[r] : 0ull;
+        out_s[(long long)q * n + r] = key ? __uint_as_float((uint32_t)(key >> 32)) : -INFINITY;
+        out_i[(long long)q * n + r] = key ? (long long)(0xffffffffu - (uint32_t)key) + idx_base : -1ll;
+    }
+}
+
+int bm25_wide_default_tile(int64_t n_rows) {
+    const int64_t need = round_up64(n_rows, BM25_CHUNK);
+    return (int)(need < BM25_WIDE_TILE ? need : BM25_WIDE_TILE);
+}
+
+int bm25_wide_blocks(int64_t n_rows, int tile_rows, int n, int max_blocks) {
+    const int64_t tiles = (n_rows + tile_rows - 1) / tile_rows;
+    int64_t b = BM25_WIDE_PART_KEYS / n;                     // >= 64
+    if (b > 512) b = 512;
+    if (max_blocks > 0 && b > max_blocks) b = max_blocks;
+    return (int)(tiles < b ? tiles : b);
+}
+
+}  // namespace
+
+extern "C" int64_t arx_bm25_wide_workspace_bytes(int64_t n_rows, int32_t n_queries, int32_t n) {
+    if (n_rows <= 0 || n_queries <= 0 || n < 1 || n > BM25_WIDE_KMAX) return -1;
+    // sized for the smallest tile a tuned call may ask for, so that one workspace serves every tile size / block count
+    return round_up64((int64_t)bm25_wide_blocks(n_rows, BM25_CHUNK, n, 0) * n_queries * n * 8, 256);
+}
+
+extern "C" int32_t arx_bm25_search_wide(const int64_t* term_ptr, const uint32_t* post_row, const float* post_w, int32_t vocab, int64_t n_rows,
+                                        const uint64_t* allow, int32_t n_filters, const int32_t* filter_of, const int32_t* q_terms,
+                                        const int32_t* q_nterms, int32_t n_queries, int32_t n, float* out_scores, int64_t* out_ids,
+                                        int64_t idx_base, void* ws, int64_t ws_bytes, int32_t tile_rows, int32_t max_blocks, void* stream) {
+    ARX_REQUIRE(term_ptr && post_row && post_w && q_terms && q_nterms && out_scores && out_ids, "null pointer argument");
+    if (allow) ARX_REQUIRE(n_filters >= 1, "n_filters=%d must be at least 1", n_filters);
+    else ARX_REQUIRE(!filter_of, "filter_of needs allow (allow == NULL is the unfiltered search)");
+    ARX_REQUIRE(vocab > 0, "vocab=%d must be positive", vocab);
+    ARX_REQUIRE(n_rows > 0 && n_rows < (1ll << 31), "n_rows=%lld must be in [1, 2^31)", (long long)n_rows);
+    ARX_REQUIRE(n_queries > 0 && n_queries <= 65535, "n_queries=%d must be in [1, 65535]", n_queries);
+    ARX_REQUIRE(n >= 1 && n <= BM25_WIDE_KMAX, "n=%d must be in [1, %d]", n, BM25_WIDE_KMAX);
+    ARX_REQUIRE(idx_base >= 0, "idx_base must be >= 0");
+    ARX_REQUIRE(max_blocks >= 0, "max_blocks must be >= 0 (0 = default)");
+    if (tile_rows == 0) tile_rows = bm25_wide_default_tile(n_rows);
+    ARX_REQUIRE(tile_rows >= BM25_CHUNK && tile_rows <= BM25_TILE_MAX && tile_rows % BM25_CHUNK == 0,
+                "tile_rows=%d must be a multiple of %d in [%d, %d] (0 = default)", tile_rows, BM25_CHUNK, BM25_CHUNK, BM25_TILE_MAX);
+    const int blocks = bm25_wide_blocks(n_rows, tile_rows, n, max_blocks);
+    const int64_t need = arx_bm25_wide_workspace_bytes(n_rows, n_queries, n);
+    ARX_REQUIRE(blocks == 1 || (ws && ws_bytes >= need), "workspace too small: %lld < %lld bytes", (long long)ws_bytes, (long long)need);
+    hipStream_t st = (hipStream_t)stream;
+    const int smem = tile_rows * 4 + (int)sizeof(Bm25WideSmem) + (allow ? (int)sizeof(Bm25FilterSmem) : 0);
+    ARX_HIP_CHECK(arx_func_smem(allow ? (const void*)bm25_wide_kernel<true> : (const void*)bm25_wide_kernel<false>, smem));
+    unsigned long long* part_k = blocks > 1 ? (unsigned long long*)ws : nullptr;
+    if (allow)
+        bm25_wide_kernel<true><<<dim3(blocks, n_queries), BM25_NT, smem, st>>>(
+            (const long long*)term_ptr, post_row, post_w, vocab, n_rows, (const unsigned long long*)allow, n_filters, filter_of, q_terms, q_nterms,
+            n, tile_rows, part_k, out_scores, (long long*)out_ids, idx_base);
+    else
+        bm25_wide_kernel<false><<<dim3(blocks, n_queries), BM25_NT, smem, st>>>(
+            (const long long*)term_ptr, post_row, post_w, vocab, n_rows, nullptr, 0, nullptr, q_terms, q_nterms, n, tile_rows, part_k, out_scores,
+            (long long*)out_ids, idx_base);
+    ARX_HIP_CHECK(hipGetLastError());
+    if (blocks > 1) {
+        bm25_wide_merge_kernel<<<n_queries, BM25_NT, 0, st>>>(part_k, blocks, n_queries, n, out_scores, (long long*)out_ids, idx_base);
+        ARX_HIP_CHECK(hipGetLastError());
+    }
     return ARX_OK;
 }

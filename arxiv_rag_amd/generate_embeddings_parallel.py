@@ -666,12 +666,18 @@ def check_chunk_count(n_rows: int, chunks, *, where=None, keep_mask=None, where_
             raise ValueError(f"{mode}: {len(per_row)} {'chunks' if per_row is chunks else 'entries'} for the shard's {n_rows} rows")
 
 
+def n_cand_of(reranker, rerank_top_k: int, mmr_lambda, mmr_fetch_k: int) -> int:
+    """Candidates per query where something picks among them afterwards: the reranker, MMR, or the fusion (each side's list)."""
+    return rerank_top_k if reranker is not None else (mmr_fetch_k if mmr_lambda is not None else HYBRID_CANDIDATES)
+
+
 def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[str], top_k: int = 10,
                    output_dir: str = "./embeddings_saved", chunk_base: int = 0, reranker=None, rerank_top_k: int = 32,
                    hybrid_alpha: Optional[float] = None, where=None,
                    where_document: Optional[Dict] = None, *, mmr_lambda: Optional[float] = None, mmr_fetch_k: int = 32,
                    keep_mask: Optional[np.ndarray] = None, group_by_paper: bool = False, chunks_per_paper: int = 1,
-                   where_on_device: bool = False, min_score: Optional[float] = None, hybrid_filters: bool = False) -> List[Dict]:
+                   where_on_device: bool = False, min_score: Optional[float] = None, hybrid_filters: bool = False,
+                   hybrid_on_device: bool = False) -> List[Dict]:
     """Brute-force cosine top-k (config.yaml:63-64 `top_k: 10`) over the rank's fp16 rows in HBM; with
     torchrun each rank holds the contiguous row shard it encoded and the partial top-k lists are
     all-gathered over RCCL and merged.  `shard` is the `ShardSink` the encode step filled: rows [lo, hi) are already where they
@@ -721,8 +727,18 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
     `hybrid_filters` (False = nothing changes, every refusal above stays): `hybrid_alpha` then composes with `where` (a dict or a per-query
     list), `where_document`, `keep_mask` and `where_on_device`: the bitmaps the cosine search uses go to the keyword search unchanged
     (`KeywordIndex.search(allow=...)`, `arx_bm25_search_filtered`), so both candidate lists hold allowed rows only and the fusion is what it
-    was.  The BM25 statistics stay those of the whole corpus (INTEGRATION.md "Hybrid search with filters")."""
-    from .retrieval import RowFilters, check_shared_query, retrieve
+    was.  The BM25 statistics stay those of the whole corpus (INTEGRATION.md "Hybrid search with filters").
+    `hybrid_on_device` (False = nothing changes; needs `hybrid_alpha`): the two candidate lists are fused on the device
+    (`keyword.fuse_device`) and, with a reranker, `rerank_top_k` may be up to 1024: the cosine side then comes from
+    `ShardIndex.search_range(-inf)`, the keyword side from `KeywordIndex.search_wide`, and the cross-encoder scores the fused
+    `rerank_top_k` 32 pairs at a time.  Beyond 32 not with a per-query `where` list or more than one rank.  With `rerank_top_k <= 32`
+    the same hits as without it (INTEGRATION.md "Hybrid search on the device")."""
+    from .retrieval import RowFilters, check_hybrid_on_device, check_shared_query, retrieve
+    if hybrid_on_device:
+        if hybrid_alpha is None:
+            raise ValueError("hybrid_on_device needs hybrid_alpha: it chooses where the two candidate lists are fused")
+        check_hybrid_on_device(rerank_top_k if reranker is not None else HYBRID_CANDIDATES, per_query_filters=isinstance(where, (list, tuple)),
+                               world=int(os.environ.get("WORLD_SIZE", "1")))
     if min_score is not None:
         from .ranging import check_range_query
         if reranker is not None:
@@ -754,7 +770,8 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
         compile_where_document(where_document)
     # int8 pre-filter (same exact answers; +50 % shard memory, one quantisation pass): 1.5-1.7x the queries per second on small batches;
     # a filtered, a grouped and a range search run on the fp16 rows
-    masked = where is not None or keep_mask is not None or where_document is not None or group_by_paper or min_score is not None
+    masked = (where is not None or keep_mask is not None or where_document is not None or group_by_paper or min_score is not None
+              or (hybrid_on_device and n_cand_of(reranker, rerank_top_k, mmr_lambda, mmr_fetch_k) > HYBRID_CANDIDATES))
     index = ShardIndex(shard.rows, idx_base=shard.lo, prefilter="int8" if (dim % 128 == 0 and dim <= 1024 and n_rows > 0 and not masked) else None,
                        adaptive=True)
     if min_score is not None and world > 1:
@@ -765,8 +782,7 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
             raise ValueError("group_by_paper needs a single GPU rank: a paper may straddle two ranks, and a cross-rank fold is out of scope")
         group_of, paper_ids = runs_from_keys([(c.get("metadata") or {}).get("paper_id") for c in chunks], base=chunk_base)
         index.set_groups(group_of)
-    # candidates per query where something picks among them afterwards: the reranker, MMR, or the fusion (each side's list)
-    n_cand = rerank_top_k if reranker is not None else (mmr_fetch_k if mmr_lambda is not None else HYBRID_CANDIDATES)
+    n_cand = n_cand_of(reranker, rerank_top_k, mmr_lambda, mmr_fetch_k)
 
     def keyword_index():                                     # (built per call, after the cosine search)
         from .keyword import KeywordIndex
@@ -779,12 +795,14 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
                          texts=lambda: [c["text"] for c in chunks], where_on_device=where_on_device, count_both=False)
     hit = retrieve(index, qd, filters, top_k, n_candidates=n_cand, reranked=reranker is not None, where=where, where_document=where_document,
                    min_score=None if min_score is None else float(min_score), grouped=group_by_paper, chunks_per_group=chunks_per_paper, mmr_lambda=mmr_lambda,
-                   hybrid_alpha=hybrid_alpha, keyword=keyword_index, query_texts=queries)
+                   hybrid_alpha=hybrid_alpha, keyword=keyword_index, query_texts=queries, hybrid_on_device=hybrid_on_device, world=world)
     s, i, grp, truncated, mmr_val, hyb, kws = hit.scores, hit.ids, hit.groups, hit.truncated, hit.mmr, hit.hybrid, hit.keyword
     if reranker is not None:
+        from .ranging import RERANK_BATCH
         from .rerank import rerank_candidates, reorder_by_rerank
         texts = {int(j): chunks[int(j) - chunk_base]["text"] for j in np.unique(i) if chunk_base <= j < chunk_base + len(chunks)}
-        scores = rerank_candidates(lambda pairs: reranker.predict(pairs, batch_size=rerank_top_k, convert_to_numpy=True),
+        scores = rerank_candidates(lambda pairs: reranker.predict(pairs, batch_size=min(rerank_top_k, RERANK_BATCH) if hybrid_on_device else rerank_top_k,
+                                                                   convert_to_numpy=True),
                                    queries, i, texts, dist=dist if world > 1 else None, group=host_group() if world > 1 else None)
         picked = reorder_by_rerank(i, scores, top_k)
     names = {int(j): chunks[int(j) - chunk_base].get("chunk_id", f"chunk_{int(j)}")
@@ -863,6 +881,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--hybrid-filters", action="store_true",
                    help="Let --hybrid-alpha compose with --where, --where-file, --where-document and --dedup-threshold: the BM25 keyword "
                         "search reads the same row bitmaps as the cosine search (default: off, those combinations are refused)")
+    p.add_argument("--hybrid-on-device", action="store_true",
+                   help=f"Fuse the two candidate lists of --hybrid-alpha on the GPU; --rerank-top-k may then be up to {HYBRID_DEVICE_MAX_K} "
+                        "(beyond 32: one GPU rank only, not with --where-file).  config.yaml's recipe: --hybrid-alpha 0.7 --rerank-model ... "
+                        "--rerank-top-k 50 --top-k 10 --hybrid-on-device (default: off, the lists are fused on the host)")
     p.add_argument("--where", type=str, default=None,
                    help="Chroma metadata filter for --queries as JSON, e.g. '{\"section\": \"abstract\"}' or "
                         "'{\"quality_score\": {\"$gte\": 0.95}}': only matching chunks are searched (with --hybrid-alpha only next to --hybrid-filters)")
@@ -901,13 +923,17 @@ def build_parser() -> argparse.ArgumentParser:
 
 
 RERANK_MAX_K = 32          # the exact top-k search returns k <= 32 per query (search.hip KMAX)
+HYBRID_DEVICE_MAX_K = 1024  # ... and with --hybrid-on-device the fused list may be this long (retrieval.HYBRID_DEVICE_CANDIDATES)
 
 
 def check_rerank_args(args) -> Optional[str]:
     """-> an error message for an unusable --rerank-top-k, else None."""
     if not args.rerank_model:
         return None
-    if args.rerank_top_k > RERANK_MAX_K:
+    on_device = getattr(args, "hybrid_on_device", False) and getattr(args, "hybrid_alpha", None) is not None
+    if on_device and args.rerank_top_k > HYBRID_DEVICE_MAX_K:
+        return f"--rerank-top-k {args.rerank_top_k}: --hybrid-on-device fuses at most {HYBRID_DEVICE_MAX_K} candidates per side"
+    if not on_device and args.rerank_top_k > RERANK_MAX_K:
         return f"--rerank-top-k {args.rerank_top_k}: the search returns at most k <= {RERANK_MAX_K} candidates per query"
     if args.rerank_top_k < args.top_k:
         return f"--rerank-top-k {args.rerank_top_k} is below --top-k {args.top_k}: the reranker must see at least the results it keeps"
@@ -925,6 +951,22 @@ def check_hybrid_args(args) -> Optional[str]:
         return f"--hybrid-alpha {args.hybrid_alpha}: the weight of the cosine side must be in [0, 1]"
     if args.top_k > HYBRID_CANDIDATES:
         return f"--top-k {args.top_k}: hybrid search fuses {HYBRID_CANDIDATES} candidates per side and returns at most that many"
+    return None
+
+
+def check_hybrid_device_args(args) -> Optional[str]:
+    """-> an error message for an unusable --hybrid-on-device, else None.  (The other flags are read with getattr: absent = off.)"""
+    if not getattr(args, "hybrid_on_device", False):
+        return None
+    if getattr(args, "hybrid_alpha", None) is None:
+        return "--hybrid-on-device needs --hybrid-alpha: it chooses where the two candidate lists are fused"
+    if getattr(args, "rerank_model", None) and getattr(args, "rerank_top_k", 32) > RERANK_MAX_K:
+        if getattr(args, "where_file", None):
+            return (f"--hybrid-on-device with --rerank-top-k above {RERANK_MAX_K} cannot be combined with --where-file: the range search "
+                    "that fetches the long dense list takes one bitmap per call")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            return (f"--hybrid-on-device with --rerank-top-k above {RERANK_MAX_K} needs a single GPU rank: a cross-rank merge of long "
+                    "candidate lists is out of scope")
     return None
 
 
@@ -1143,7 +1185,7 @@ def check_where_document_args(args) -> Optional[str]:
 def main(argv: Optional[Sequence[str]] = None, model_factory: Optional[Callable] = None) -> int:
     global _model, _model_name
     args = build_parser().parse_args(argv)
-    err = (check_rerank_args(args) or check_hybrid_args(args) or check_hybrid_filters_args(args) or check_where_args(args) or check_where_file_args(args) or check_where_device_args(args)
+    err = (check_rerank_args(args) or check_hybrid_args(args) or check_hybrid_filters_args(args) or check_hybrid_device_args(args) or check_where_args(args) or check_where_file_args(args) or check_where_device_args(args)
            or check_where_document_args(args)
            or check_mmr_args(args) or check_dedup_args(args) or check_group_args(args) or check_range_args(args))
     if err:
@@ -1245,7 +1287,8 @@ def main(argv: Optional[Sequence[str]] = None, model_factory: Optional[Callable]
                                **({"group_by_paper": True, "chunks_per_paper": args.chunks_per_paper} if args.group_by_paper else {}),
                                **({"where_on_device": True} if args.where_on_device else {}),
                                **({"min_score": args.min_score} if args.min_score is not None else {}),
-                               **({"hybrid_filters": True} if args.hybrid_filters else {}))
+                               **({"hybrid_filters": True} if args.hybrid_filters else {}),
+                               **({"hybrid_on_device": True} if args.hybrid_on_device else {}))
         store_time = 0.0
         if rank == 0 and not args.skip_chroma:
             try:

@@ -9,7 +9,9 @@ The reference configures hybrid search and has no code for it, so the definition
 * a query is its first 64 distinct word pieces, sorted by id; `bm25(q, d)` = the f32 sum of its terms' impacts in ascending id order;
 * `arx_bm25_search` (csrc/bm25.hip) returns per query the n <= 32 rows with the largest `(score desc, row asc)`;
 * `arx_bm25_search_filtered` does so among the rows a bitmap allows (one bitmap per query); scores, idf and avgdl are unchanged;
-* `fuse` is relative-score fusion of the (global) dense and keyword lists: `alpha * normD + (1 - alpha) * normK`.
+* `fuse` is relative-score fusion of the (global) dense and keyword lists: `alpha * normD + (1 - alpha) * normK`;
+* `KeywordIndex.search_wide` (`arx_bm25_search_wide`) is the same top-n for n <= 1024 and `fuse_device` (`arx_hybrid_fuse`) is `fuse` on
+  the device, bit for bit: hybrid search with long candidate lists (opt-in, `hybrid_on_device`).
 
 `KeywordStats`, `build_postings`, `impacts_f64` and `fuse` are numpy only; `KeywordIndex` needs the GPU.
 """
@@ -23,6 +25,7 @@ BM25_K1 = 1.2
 BM25_B = 0.75
 MAX_QUERY_TERMS = 64
 MAX_N = 32                     # candidates per query (the merge kernel's list length limit, as for the cosine search)
+MAX_N_WIDE = 1024              # ... of `KeywordIndex.search_wide` and `fuse_device` (hybrid search on the device)
 
 
 class KeywordStats:
@@ -187,6 +190,37 @@ def fuse(dense_scores, dense_ids, kw_scores, kw_ids, alpha: float, k: int):
     return out_f, out_i, out_d, out_k
 
 
+def fuse_device(dense_scores, dense_ids, kw_scores, kw_ids, alpha: float, k: int):
+    """`fuse` on the device (`arx_hybrid_fuse`), bit for bit: device tensors in ([nq, n_dense] / [nq, n_kw], f32 scores and int64 ids,
+    each list at most 1024 long with distinct ids), device tensors out (fused f64, ids int64, dense f32, keyword f32, each [nq, k],
+    k <= 1024).  Nothing crosses to the host."""
+    import torch
+    from . import _lib
+    if not (0.0 <= float(alpha) <= 1.0):
+        raise ValueError(f"alpha={alpha} must be in [0, 1]")
+    for name, t, dt in (("dense_scores", dense_scores, torch.float32), ("dense_ids", dense_ids, torch.int64),
+                        ("kw_scores", kw_scores, torch.float32), ("kw_ids", kw_ids, torch.int64)):
+        if not torch.is_tensor(t) or t.dtype != dt or t.dim() != 2 or t.device != dense_scores.device:
+            raise ValueError(f"{name} must be a 2-d {dt} tensor on the device of dense_scores")
+    nq = dense_scores.shape[0]
+    if kw_scores.shape[0] != nq or dense_scores.shape != dense_ids.shape or kw_scores.shape != kw_ids.shape:
+        raise ValueError("list shapes disagree")
+    n_dense, n_kw = int(dense_scores.shape[1]), int(kw_scores.shape[1])
+    if not (1 <= n_dense <= MAX_N_WIDE and 1 <= n_kw <= MAX_N_WIDE and 1 <= int(k) <= MAX_N_WIDE):
+        raise ValueError(f"list lengths {n_dense}, {n_kw} and k={k} must each be in [1, {MAX_N_WIDE}]")
+    dev = dense_scores.device
+    out_f = torch.empty((nq, k), dtype=torch.float64, device=dev); out_i = torch.empty((nq, k), dtype=torch.int64, device=dev)
+    out_d = torch.empty((nq, k), dtype=torch.float32, device=dev); out_k = torch.empty((nq, k), dtype=torch.float32, device=dev)
+    if nq == 0:
+        return out_f, out_i, out_d, out_k
+    ds, di, ks, ki = dense_scores.contiguous(), dense_ids.contiguous(), kw_scores.contiguous(), kw_ids.contiguous()
+    rc = _lib.load().arx_hybrid_fuse(ds.data_ptr(), di.data_ptr(), n_dense, ks.data_ptr(), ki.data_ptr(), n_kw, nq, float(alpha), int(k),
+                                     out_f.data_ptr(), out_i.data_ptr(), out_d.data_ptr(), out_k.data_ptr(),
+                                     torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(rc, "arx_hybrid_fuse")
+    return out_f, out_i, out_d, out_k
+
+
 class KeywordIndex:
     """This rank's BM25 impact index in HBM (CSR by term) and its top-n search through `arx_bm25_search`."""
 
@@ -320,6 +354,43 @@ class KeywordIndex:
                     b - a, n, out_s[a:b].data_ptr(), out_i[a:b].data_ptr(), self.idx_base, self._ws.data_ptr(), self._ws.numel(),
                     int(tile_rows), int(max_blocks), st)
                 _lib.check(rc, "arx_bm25_search_filtered")
+        return out_s, out_i
+
+    WIDE_QUERY_STEP = 256          # queries per wide call: bounds the partial lists (at most 512 KiB per query) to 128 MiB
+
+    def search_wide(self, queries, n: int, allow=None, filter_of=None, tile_rows: int = 0, max_blocks: int = 0):
+        """`search` with `n` up to MAX_N_WIDE = 1024 (`arx_bm25_search_wide`): the same queries, scores, order, padding and filter
+        arguments; for n <= 32 the same bits, and the first m entries of an n-list are the m-list.  This shard only: a cross-rank merge
+        of long lists is out of scope."""
+        import torch
+        from . import _lib
+        if not (1 <= n <= MAX_N_WIDE):
+            raise ValueError(f"n={n} must be in [1, {MAX_N_WIDE}]")
+        if allow is None and filter_of is not None:
+            raise ValueError("filter_of needs allow")
+        qt, qn = pack_query_terms(self._term_lists(queries), self.vocab_size)
+        nq = len(qn)
+        if allow is not None:
+            allow, filter_of = self._check_filters(allow, filter_of, nq)
+        out_s = torch.full((nq, n), float("-inf"), dtype=torch.float32, device=self.device)
+        out_i = torch.full((nq, n), -1, dtype=torch.int64, device=self.device)
+        if nq == 0 or self.n_rows == 0:
+            return out_s, out_i
+        qt_d, qn_d = torch.from_numpy(qt).to(self.device), torch.from_numpy(qn).to(self.device)
+        step = self.WIDE_QUERY_STEP
+        need = self.lib.arx_bm25_wide_workspace_bytes(self.n_rows, min(nq, step), n)
+        if getattr(self, "_ws_wide", None) is None or self._ws_wide.numel() < need:
+            self._ws_wide = torch.empty(need, dtype=torch.uint8, device=self.device)
+        st = torch.cuda.current_stream(self.device).cuda_stream
+        for a in range(0, nq, step):
+            b = min(nq, a + step)
+            rc = self.lib.arx_bm25_search_wide(
+                self.term_ptr.data_ptr(), self.post_row.data_ptr(), self.post_w.data_ptr(), self.vocab_size, self.n_rows,
+                None if allow is None else allow.data_ptr(), 0 if allow is None else int(allow.shape[0]),
+                None if filter_of is None else filter_of[a:b].data_ptr(), qt_d[a:b].data_ptr(), qn_d[a:b].data_ptr(), b - a, n,
+                out_s[a:b].data_ptr(), out_i[a:b].data_ptr(), self.idx_base, self._ws_wide.data_ptr(), self._ws_wide.numel(),
+                int(tile_rows), int(max_blocks), st)
+            _lib.check(rc, "arx_bm25_search_wide")
         return out_s, out_i
 
     def search_distributed(self, queries, n: int = MAX_N, group=None, allow=None, filter_of=None):

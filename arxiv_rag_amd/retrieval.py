@@ -38,6 +38,23 @@ def check_shared_query(n_results: int, *, hybrid_alpha, hybrid_filters: bool, re
     refuse_filters(filters)
 
 
+HYBRID_HOST_CANDIDATES = 32        # the candidate lists' length limit without `hybrid_on_device`
+HYBRID_DEVICE_CANDIDATES = 1024    # ... and with it (`arx_bm25_search_wide`, `arx_range_search`, `arx_hybrid_fuse`)
+
+
+def check_hybrid_on_device(n_candidates: int, *, per_query_filters: bool = False, world: int = 1) -> None:
+    """The refusals of a hybrid search with `hybrid_on_device`, each a ValueError with its reason."""
+    if n_candidates > HYBRID_DEVICE_CANDIDATES:
+        raise ValueError(f"n_candidates={n_candidates} must be at most {HYBRID_DEVICE_CANDIDATES} with hybrid_on_device (the candidate "
+                         f"lists' length limit on the device)")
+    if n_candidates > HYBRID_HOST_CANDIDATES and per_query_filters:
+        raise ValueError(f"n_candidates={n_candidates} > {HYBRID_HOST_CANDIDATES} cannot be combined with per-query filter lists: the range "
+                         f"search that fetches the long dense list takes one bitmap per call")
+    if n_candidates > HYBRID_HOST_CANDIDATES and world > 1:
+        raise ValueError(f"n_candidates={n_candidates} > {HYBRID_HOST_CANDIDATES} needs a single GPU rank: a cross-rank merge of long "
+                         f"candidate lists is out of scope")
+
+
 class RowFilters:
     """The row bitmaps of one shard: `where` (evaluated on the host, or on the device with `where_on_device`), `where_document` and the
     keep-mask, and-ed.  A bitmap is a device int64 tensor of ceil(n_rows / 64) words in the convention of `where.pack_bitmap`; whichever
@@ -182,20 +199,31 @@ class Retrieved:
 
 def retrieve(index, q, filters: RowFilters, n_results: int, *, n_candidates: int = 32, reranked: bool = False, where=None, where_document=None,
              min_score=None, grouped: bool = False, chunks_per_group: int = 1, mmr_lambda: Optional[float] = None,
-             hybrid_alpha: Optional[float] = None, keyword=None, query_texts: Optional[Sequence[str]] = None) -> Retrieved:
+             hybrid_alpha: Optional[float] = None, keyword=None, query_texts: Optional[Sequence[str]] = None,
+             hybrid_on_device: bool = False, world: int = 1) -> Retrieved:
     """One search of the fp16 device queries `q` over `index` (a `ShardIndex`), in the mode the arguments name, every refusal behind it.
     The width: a range search (`min_score`) returns up to `n_candidates` rows with `reranked` and `n_results` without, a grouped search
     `n_results` groups, every other search `n_candidates` rows when something picks among them afterwards (`reranked`, `mmr_lambda`,
     `hybrid_alpha`) and `n_results` otherwise.  `where` / `where_document`: a dict each, or a list with one entry per query.
     `mmr_lambda`: `mmr.mmr_select` picks `n_results` of the candidates, which come back in pick order.  `hybrid_alpha`: `keyword` (a
     `keyword.KeywordIndex`, or a callable that builds one) fetches `n_candidates` rows for `query_texts`, restricted by the bitmaps the
-    cosine search was given, and `keyword.fuse` keeps the best `n_candidates` (`reranked`) or `n_results`."""
+    cosine search was given, and `keyword.fuse` keeps the best `n_candidates` (`reranked`) or `n_results`.
+    `hybrid_on_device` (False = nothing changes; read only with `hybrid_alpha`): the fusion runs on the device and `n_candidates` may
+    be up to 1024.  The dense list is the search above for `n_candidates <= 32` and `index.search_range(q, -inf, n_candidates)` beyond
+    (the same score bits, by that kernel's contract), the keyword list is `KeywordIndex.search_wide`'s under the same bitmaps, the
+    fusion is `keyword.fuse_device`, and the four result arrays cross to the host once.  For `n_candidates <= 32` the result is the
+    default path's, bit for bit.  ValueError: `n_candidates > 1024`; `n_candidates > 32` with per-query filter lists (the range
+    search takes one bitmap per call) or with `world > 1` ranks (a cross-rank merge of long lists is out of scope)."""
     import torch
     from .filter_sets import is_per_query
     nq = q.shape[0]
     k = n_candidates if (reranked or hybrid_alpha is not None or mmr_lambda is not None) else n_results
     out = Retrieved(None, None)
     kw_filter_of = None
+    on_device = hybrid_alpha is not None and bool(hybrid_on_device)
+    if on_device:
+        check_hybrid_on_device(n_candidates, per_query_filters=is_per_query(where) or is_per_query(where_document), world=world)
+    long_lists = on_device and n_candidates > HYBRID_HOST_CANDIDATES
     if is_per_query(where) or is_per_query(where_document):
         from .index import search_filtered_grouped
         bitmaps, filter_of, counts = filters.per_query(nq, where, where_document)
@@ -210,6 +238,9 @@ def retrieve(index, q, filters: RowFilters, n_results: int, *, n_candidates: int
             s, i, counts = index.search_range(q, thresholds(min_score, nq), n_candidates if reranked else n_results, allow=allow,
                                               n_allowed=n_allowed)
             out.truncated = (counts > s.shape[1]).cpu().tolist()
+        elif long_lists:                                         # every visible row qualifies: the exact top n_candidates
+            from .ranging import thresholds
+            s, i, _ = index.search_range(q, thresholds(float("-inf"), nq), n_candidates, allow=allow, n_allowed=n_allowed)
         elif grouped:
             s, i, grp = index.search_grouped(q, n_results, chunks_per_group, allow=allow, n_allowed=n_allowed)
             out.groups = grp.cpu().numpy()
@@ -223,6 +254,16 @@ def retrieve(index, q, filters: RowFilters, n_results: int, *, n_candidates: int
         s = torch.where(order >= 0, s.gather(1, pos), torch.full_like(mmr_val, float("-inf")))
         i = torch.where(order >= 0, i.gather(1, pos), torch.full_like(pos, -1))
         out.mmr = mmr_val.cpu().numpy()
+    if on_device:
+        from .keyword import fuse_device
+        kw = keyword() if callable(keyword) else keyword
+        if world > 1:                                            # (n_candidates <= 32: the cross-rank merge of the short lists)
+            ks, ki = kw.search_distributed(list(query_texts), n_candidates, allow=allow, filter_of=kw_filter_of)
+        else:
+            ks, ki = kw.search_wide(list(query_texts), n_candidates, allow=allow, filter_of=kw_filter_of)
+        fused = fuse_device(s.float(), i, ks, ki, float(hybrid_alpha), n_candidates if reranked else n_results)
+        out.hybrid, out.ids, out.scores, out.keyword = (t.cpu().numpy() for t in fused)
+        return out
     out.scores, out.ids = s.cpu().numpy(), i.cpu().numpy()
     if grouped:
         out.group_sizes = (out.ids.reshape(nq, n_results, chunks_per_group) >= 0).sum(axis=2)

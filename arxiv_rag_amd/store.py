@@ -76,7 +76,7 @@ class HipCollection:
     def __init__(self, embeddings: np.ndarray, metadata: Sequence[Dict], device="cuda:0", encoder=None,
                  rank: int = 0, world: int = 1, chunk_rows: int = 1 << 18, keyword: bool = False, tokenizer=None,
                  documents: bool = False, dedup_threshold: Optional[float] = None, group_key: Optional[str] = None,
-                 where_on_device: bool = False, hybrid_filters: bool = False):
+                 where_on_device: bool = False, hybrid_filters: bool = False, hybrid_on_device: bool = False):
         """`keyword=True`: also build a BM25 `keyword.KeywordIndex` over this shard's `metadata[i]["text"]` (word pieces of `tokenizer`,
         default the encoder's; corpus statistics summed over all ranks when `world > 1`), which `query(hybrid_alpha=...)` needs.
         `documents=True`: also keep this shard's texts as a UTF-8 blob in HBM (`where_document.DocumentStore`), which
@@ -99,12 +99,19 @@ class HipCollection:
         `where_document`, per-query lists of either, the dedup keep-bitmap and `where_on_device` instead of raising: the bitmaps the
         cosine search is given go to the keyword search unchanged (`KeywordIndex.search(allow=...)`, `arx_bm25_search_filtered`), so
         both candidate lists hold allowed rows only.  The BM25 statistics stay those of the whole corpus (INTEGRATION.md "Hybrid search
-        with filters")."""
+        with filters").
+        `hybrid_on_device` (False = nothing changes; needs `keyword=True`): `query(hybrid_alpha=...)` fuses the two candidate lists on
+        the device (`keyword.fuse_device`, `arx_hybrid_fuse`) and accepts `n_candidates` up to 1024, with or without `reranker`: the
+        dense list then comes from `ShardIndex.search_range(-inf)` and the keyword list from `KeywordIndex.search_wide`.  With
+        `n_candidates <= 32` the result is the default path's, bit for bit (INTEGRATION.md "Hybrid search on the device")."""
         import torch
         from .index import ShardIndex, shard_bounds
         if hybrid_filters and not keyword:
             raise ValueError("hybrid_filters=True needs keyword=True: it passes the row filters to the BM25 keyword search")
+        if hybrid_on_device and not keyword:
+            raise ValueError("hybrid_on_device=True needs keyword=True: it chooses where the BM25 keyword list and the cosine list are fused")
         self.hybrid_filters = bool(hybrid_filters)
+        self.hybrid_on_device = bool(hybrid_on_device)
         if dedup_threshold is not None:
             from .dedup import check_threshold
             dedup_threshold = check_threshold(dedup_threshold)
@@ -237,13 +244,17 @@ class HipCollection:
         On a collection built with `hybrid_filters=True` every "raises ValueError with `hybrid_alpha`" above that is about a row filter
         (`where`, `where_document`, per-query lists, `dedup_threshold`) is lifted: the keyword search is restricted by the very bitmaps
         of the cosine search, query by query, `fuse` and `reranker` work as without a filter, and idf / avgdl stay corpus-wide.
-        `mmr_lambda`, `group_by` and `min_score` stay refused with `hybrid_alpha`."""
+        `mmr_lambda`, `group_by` and `min_score` stay refused with `hybrid_alpha`.
+        On a collection built with `hybrid_on_device=True`, `hybrid_alpha` takes `n_candidates` up to 1024 (each side's list and the
+        fused list a `reranker` receives, whose pairs are then scored 32 at a time) and the fusion runs on the device; beyond 32
+        candidates it raises ValueError with per-query filter lists and with `world > 1`.  Everything else stays as above."""
         import torch
         from .filter_sets import is_per_query
         from .grouping import check_grouped_query
         from .ranging import RERANK_BATCH, check_range_query
-        from .retrieval import check_shared_query, retrieve
+        from .retrieval import check_hybrid_on_device, check_shared_query, retrieve
         per_query = is_per_query(where) or is_per_query(where_document)
+        on_device = hybrid_alpha is not None and getattr(self, "hybrid_on_device", False)
         check_range_query(n_results, ranged=min_score is not None, reranker=reranker, n_candidates=n_candidates, hybrid_alpha=hybrid_alpha,
                           mmr_lambda=mmr_lambda, group_by=group_by, per_query_filters=per_query, world=getattr(self, "world", 1))
         check_grouped_query(n_results, chunks_per_group, grouped=bool(group_by), has_group_key=getattr(self, "group_key", None) is not None,
@@ -266,12 +277,14 @@ class HipCollection:
                 raise ValueError(f"hybrid_alpha={hybrid_alpha} must be in [0, 1]")
             if query_texts is None or self.keyword is None:
                 raise ValueError("hybrid search needs query_texts and a collection built with keyword=True")
-            if not (n_results <= n_candidates <= 32):
-                raise ValueError(f"n_candidates={n_candidates} must be in [n_results, 32] (the candidate lists' length limit)")
+            if on_device:
+                check_hybrid_on_device(n_candidates, per_query_filters=per_query, world=getattr(self, "world", 1))
+            if not (n_results <= n_candidates <= (1024 if on_device else 32)):
+                raise ValueError(f"n_candidates={n_candidates} must be in [n_results, {1024 if on_device else 32}] (the candidate lists' length limit)")
         if reranker is not None:
             if query_texts is None:
                 raise ValueError("reranking needs query_texts")
-            if min_score is None and not (n_results <= n_candidates <= 32):
+            if min_score is None and not on_device and not (n_results <= n_candidates <= 32):
                 raise ValueError(f"n_candidates={n_candidates} must be in [n_results, 32] (the search's k limit)")
         if query_embeddings is None:
             if query_texts is None or self.encoder is None:
@@ -282,12 +295,13 @@ class HipCollection:
             q = q[None]
         hit = retrieve(self.index, q, self._row_filters(), n_results, n_candidates=n_candidates, reranked=reranker is not None, where=where,
                        where_document=where_document, min_score=min_score, grouped=bool(group_by), chunks_per_group=chunks_per_group,
-                       mmr_lambda=mmr_lambda, hybrid_alpha=hybrid_alpha, keyword=self.keyword, query_texts=query_texts)
+                       mmr_lambda=mmr_lambda, hybrid_alpha=hybrid_alpha, keyword=self.keyword, query_texts=query_texts,
+                       hybrid_on_device=on_device, world=getattr(self, "world", 1))
         s, i, hyb, kws = hit.scores, hit.ids, hit.hybrid, hit.keyword
         if reranker is not None:
             from .rerank import rerank_candidates, reorder_by_rerank
             texts = {int(j): self.metadata[int(j)].get("text") or "" for j in np.unique(i) if j >= 0}
-            sc = rerank_candidates(lambda pairs: reranker.predict(pairs, batch_size=n_candidates if min_score is None else min(n_candidates, RERANK_BATCH),
+            sc = rerank_candidates(lambda pairs: reranker.predict(pairs, batch_size=n_candidates if min_score is None and not on_device else min(n_candidates, RERANK_BATCH),
                                                                 convert_to_numpy=True),
                                    list(query_texts), i, texts)
             picked = reorder_by_rerank(i, sc, n_results)

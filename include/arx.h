@@ -577,6 +577,47 @@ int32_t arx_bm25_search_filtered_tuned(const int64_t* term_ptr, const uint32_t* 
                                        const int32_t* q_terms, const int32_t* q_nterms, int32_t n_queries, int32_t n,
                                        float* out_scores, int64_t* out_ids, int64_t idx_base, void* ws, int64_t ws_bytes,
                                        int32_t tile_rows, int32_t max_blocks, void* stream);
+/* Wide BM25 top-n: n in [1, 1024], with an optional row filter (hybrid search with candidate lists longer than 32; opt-in:
+ * `hybrid_on_device=True`, --hybrid-on-device).  Index, queries, scores and filter are those of arx_bm25_search and
+ * arx_bm25_search_filtered:
+ *   allow == NULL   the unfiltered search (n_filters is ignored and filter_of must be NULL);
+ *   allow != NULL   device uint64 [n_filters][ceil(n_rows / 64)] with filter_of device int32 [n_queries] or NULL (= bitmap 0), in the
+ *                   convention of arx_bm25_search_filtered: an index outside [0, n_filters) gives that query no row and reads nothing,
+ *                   bits at or beyond n_rows are ignored, a tile without an allowed row is skipped before its binary searches.
+ * Scores: the impacts of the query's terms added in ascending term order in f32, no float atomics: a row's score has the bits
+ * arx_bm25_search and arx_bm25_scores give it, whatever tile_rows, max_blocks and the other queries of the call are.
+ * Output, per query: the n rows with the largest (score desc, row asc) among the (allowed) rows holding a query term, as (f32 score,
+ * int64 idx_base + row); unused slots are (-inf, -1).  For n <= 32 the output equals arx_bm25_search / arx_bm25_search_filtered bit
+ * for bit, and for m < n the first m entries of the n-list are the m-list.
+ * The per-block lists are merged by a kernel of this call's own (one block per query, the partial lists streamed through an LDS
+ * list with sort-and-cut), not by arx_topk_merge: blocks = min(tiles, 512, 65536 / n[, max_blocks]), 64 blocks at n = 1024.
+ * tile_rows: accumulator rows per LDS tile, a multiple of 1024 in [1024, 12288]; 0 = default (min(round_up(n_rows, 1024), 10240): two
+ * blocks per CU).  max_blocks: cap on the blocks per query (0 = default).
+ * ws: device scratch of arx_bm25_wide_workspace_bytes(n_rows, n_queries, n) bytes
+ *   = round_up(min(ceil(n_rows / 1024), 512, 65536 / n) * n_queries * n * 8, 256)   (the per-block lists as 64-bit keys);
+ * may be NULL when the call runs one block per query.  The function returns -1 for n_rows <= 0, n_queries <= 0, n < 1 or n > 1024.
+ * ARX_ERR_ARG before any launch: a null pointer, filter_of without allow, n_filters < 1 with allow, vocab <= 0, n_rows outside
+ * [1, 2^31), n_queries outside [1, 65535], n outside [1, 1024], idx_base < 0, max_blocks < 0, a tile_rows that is not as above, a
+ * workspace that is too small. */
+int64_t arx_bm25_wide_workspace_bytes(int64_t n_rows, int32_t n_queries, int32_t n);
+int32_t arx_bm25_search_wide(const int64_t* term_ptr, const uint32_t* post_row, const float* post_w, int32_t vocab, int64_t n_rows,
+                             const uint64_t* allow, int32_t n_filters, const int32_t* filter_of, const int32_t* q_terms,
+                             const int32_t* q_nterms, int32_t n_queries, int32_t n, float* out_scores, int64_t* out_ids,
+                             int64_t idx_base, void* ws, int64_t ws_bytes, int32_t tile_rows, int32_t max_blocks, void* stream);
+/* Relative-score fusion of a dense and a keyword candidate list per query, on the device: arxiv_rag_amd/keyword.py `fuse`, bit for bit.
+ *   dense_scores f32 / dense_ids int64 [n_queries, n_dense], kw_scores f32 / kw_ids int64 [n_queries, n_kw] (device); a slot with
+ *   id < 0 is unused.  n_dense, n_kw and k each in [1, 1024]; alpha in [0, 1]; no workspace.
+ *   PRECONDITION: the ids >= 0 of one list of one query are distinct (every search of this library returns such lists), and below
+ *   2^63 - 1.  Ids are compared as int64: they may exceed 2^32.
+ * Per list, in float64, norm = (s - min) / (max - min) over its used slots, 1.0 for every one of them when max == min; a row absent
+ * from a list gets 0.0 from that side; fused = alpha * normD + (1.0 - alpha) * normK as two separately rounded products and one sum
+ * (no FMA contraction).  Output, per query: the best k rows of the union by (fused desc, id asc) as out_fused f64, out_ids int64,
+ * out_dense f32, out_kw f32 [n_queries, k]; out_dense / out_kw are NaN where the row was not in that list; unused slots are
+ * (-inf, -1, NaN, NaN).  Every output element is written.  One block per query, no atomics: a query's output depends on its own two
+ * lists, alpha and k alone. */
+int32_t arx_hybrid_fuse(const float* dense_scores, const int64_t* dense_ids, int32_t n_dense, const float* kw_scores,
+                        const int64_t* kw_ids, int32_t n_kw, int32_t n_queries, double alpha, int32_t k, double* out_fused,
+                        int64_t* out_ids, float* out_dense, float* out_kw, void* stream);
 /* Debug tap: out (device f32 [row_hi - row_lo]) = the score of ONE query (q_terms device int32 [n_terms], ascending) for every row of
  * [row_lo, row_hi), 0 where the row holds none of its terms; the accumulation is the search's own. */
 int32_t arx_bm25_scores(const int64_t* term_ptr, const uint32_t* post_row, const float* post_w, int32_t vocab, int64_t n_rows,

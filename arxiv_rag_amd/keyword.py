@@ -24,7 +24,7 @@ import numpy as np
 BM25_K1 = 1.2
 BM25_B = 0.75
 MAX_QUERY_TERMS = 64
-MAX_N = 32                     # candidates per query (the merge kernel's list length limit, as for the cosine search)
+MAX_N = 32                     # candidates per query (the list length limit of the cross-rank merge, as for the cosine search)
 MAX_N_WIDE = 1024              # ... of `KeywordIndex.search_wide` and `fuse_device` (hybrid search on the device)
 
 
@@ -311,6 +311,42 @@ class KeywordIndex:
         return allow.contiguous(), filter_of
 
     QUERY_STEP = 4096              # queries per kernel call (the grid's y extent is limited to 65535)
+    WIDE_QUERY_STEP = 256          # queries per wide call: bounds the partial lists (at most 512 KiB per query) to 128 MiB
+
+    def _search(self, export: str, n: int, n_max: int, step: int, queries, allow, filter_of, tile_rows: int, max_blocks: int):
+        """`search` and `search_wide`: `export` is the library's call (and names its workspace function), `n_max` its limit on n,
+        `step` the queries per call."""
+        import torch
+        from . import _lib
+        if not (1 <= n <= n_max):
+            raise ValueError(f"n={n} must be in [1, {n_max}]")
+        if allow is None and filter_of is not None:
+            raise ValueError("filter_of needs allow")
+        qt, qn = pack_query_terms(self._term_lists(queries), self.vocab_size)
+        nq = len(qn)
+        if allow is not None:
+            allow, filter_of = self._check_filters(allow, filter_of, nq)
+        out_s = torch.full((nq, n), float("-inf"), dtype=torch.float32, device=self.device)
+        out_i = torch.full((nq, n), -1, dtype=torch.int64, device=self.device)
+        if nq == 0 or self.n_rows == 0:
+            return out_s, out_i
+        qt_d, qn_d = torch.from_numpy(qt).to(self.device), torch.from_numpy(qn).to(self.device)
+        wide = export == "arx_bm25_search_wide"
+        need = (self.lib.arx_bm25_wide_workspace_bytes if wide else self.lib.arx_bm25_workspace_bytes)(self.n_rows, min(nq, step), n)
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        st = torch.cuda.current_stream(self.device).cuda_stream
+        for a in range(0, nq, step):
+            b = min(nq, a + step)
+            filters = () if export == "arx_bm25_search_tuned" else (                      # (the one export without the filter arguments)
+                None if allow is None else allow.data_ptr(), 0 if allow is None else int(allow.shape[0]),
+                None if filter_of is None else filter_of[a:b].data_ptr())
+            rc = getattr(self.lib, export)(
+                self.term_ptr.data_ptr(), self.post_row.data_ptr(), self.post_w.data_ptr(), self.vocab_size, self.n_rows, *filters,
+                qt_d[a:b].data_ptr(), qn_d[a:b].data_ptr(), b - a, n, out_s[a:b].data_ptr(), out_i[a:b].data_ptr(), self.idx_base,
+                self._ws.data_ptr(), self._ws.numel(), int(tile_rows), int(max_blocks), st)
+            _lib.check(rc, export.replace("_tuned", ""))
+        return out_s, out_i
 
     def search(self, queries, n: int = MAX_N, tile_rows: int = 0, max_blocks: int = 0, allow=None, filter_of=None):
         """`queries`: texts, or term-id lists (strictly ascending).  -> (scores f32 [nq, n], ids int64 [nq, n]) on the device; unused
@@ -319,79 +355,14 @@ class KeywordIndex:
         W = ceil(n_rows / 64), in `ShardIndex.search(allow=...)`'s convention; only allowed rows are returned, with the scores they have
         without a filter (`arx_bm25_search_filtered`).  `filter_of`: int32 device tensor [nq], the bitmap of each query (None = bitmap 0
         for all; an index outside [0, F) leaves that query without rows)."""
-        import torch
-        from . import _lib
-        if not (1 <= n <= MAX_N):
-            raise ValueError(f"n={n} must be in [1, {MAX_N}]")
-        if allow is None and filter_of is not None:
-            raise ValueError("filter_of needs allow")
-        qt, qn = pack_query_terms(self._term_lists(queries), self.vocab_size)
-        nq = len(qn)
-        if allow is not None:
-            allow, filter_of = self._check_filters(allow, filter_of, nq)
-        out_s = torch.full((nq, n), float("-inf"), dtype=torch.float32, device=self.device)
-        out_i = torch.full((nq, n), -1, dtype=torch.int64, device=self.device)
-        if nq == 0 or self.n_rows == 0:
-            return out_s, out_i
-        qt_d, qn_d = torch.from_numpy(qt).to(self.device), torch.from_numpy(qn).to(self.device)
-        step = self.QUERY_STEP
-        need = self.lib.arx_bm25_workspace_bytes(self.n_rows, min(nq, step), n)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        st = torch.cuda.current_stream(self.device).cuda_stream
-        for a in range(0, nq, step):
-            b = min(nq, a + step)
-            if allow is None:
-                rc = self.lib.arx_bm25_search_tuned(self.term_ptr.data_ptr(), self.post_row.data_ptr(), self.post_w.data_ptr(), self.vocab_size,
-                                                    self.n_rows, qt_d[a:b].data_ptr(), qn_d[a:b].data_ptr(), b - a, n, out_s[a:b].data_ptr(),
-                                                    out_i[a:b].data_ptr(), self.idx_base, self._ws.data_ptr(), self._ws.numel(),
-                                                    int(tile_rows), int(max_blocks), st)
-                _lib.check(rc, "arx_bm25_search")
-            else:
-                rc = self.lib.arx_bm25_search_filtered_tuned(
-                    self.term_ptr.data_ptr(), self.post_row.data_ptr(), self.post_w.data_ptr(), self.vocab_size, self.n_rows, allow.data_ptr(),
-                    int(allow.shape[0]), None if filter_of is None else filter_of[a:b].data_ptr(), qt_d[a:b].data_ptr(), qn_d[a:b].data_ptr(),
-                    b - a, n, out_s[a:b].data_ptr(), out_i[a:b].data_ptr(), self.idx_base, self._ws.data_ptr(), self._ws.numel(),
-                    int(tile_rows), int(max_blocks), st)
-                _lib.check(rc, "arx_bm25_search_filtered")
-        return out_s, out_i
-
-    WIDE_QUERY_STEP = 256          # queries per wide call: bounds the partial lists (at most 512 KiB per query) to 128 MiB
+        export = "arx_bm25_search_tuned" if allow is None else "arx_bm25_search_filtered_tuned"
+        return self._search(export, n, MAX_N, self.QUERY_STEP, queries, allow, filter_of, tile_rows, max_blocks)
 
     def search_wide(self, queries, n: int, allow=None, filter_of=None, tile_rows: int = 0, max_blocks: int = 0):
-        """`search` with `n` up to MAX_N_WIDE = 1024 (`arx_bm25_search_wide`): the same queries, scores, order, padding and filter
-        arguments; for n <= 32 the same bits, and the first m entries of an n-list are the m-list.  This shard only: a cross-rank merge
-        of long lists is out of scope."""
-        import torch
-        from . import _lib
-        if not (1 <= n <= MAX_N_WIDE):
-            raise ValueError(f"n={n} must be in [1, {MAX_N_WIDE}]")
-        if allow is None and filter_of is not None:
-            raise ValueError("filter_of needs allow")
-        qt, qn = pack_query_terms(self._term_lists(queries), self.vocab_size)
-        nq = len(qn)
-        if allow is not None:
-            allow, filter_of = self._check_filters(allow, filter_of, nq)
-        out_s = torch.full((nq, n), float("-inf"), dtype=torch.float32, device=self.device)
-        out_i = torch.full((nq, n), -1, dtype=torch.int64, device=self.device)
-        if nq == 0 or self.n_rows == 0:
-            return out_s, out_i
-        qt_d, qn_d = torch.from_numpy(qt).to(self.device), torch.from_numpy(qn).to(self.device)
-        step = self.WIDE_QUERY_STEP
-        need = self.lib.arx_bm25_wide_workspace_bytes(self.n_rows, min(nq, step), n)
-        if getattr(self, "_ws_wide", None) is None or self._ws_wide.numel() < need:
-            self._ws_wide = torch.empty(need, dtype=torch.uint8, device=self.device)
-        st = torch.cuda.current_stream(self.device).cuda_stream
-        for a in range(0, nq, step):
-            b = min(nq, a + step)
-            rc = self.lib.arx_bm25_search_wide(
-                self.term_ptr.data_ptr(), self.post_row.data_ptr(), self.post_w.data_ptr(), self.vocab_size, self.n_rows,
-                None if allow is None else allow.data_ptr(), 0 if allow is None else int(allow.shape[0]),
-                None if filter_of is None else filter_of[a:b].data_ptr(), qt_d[a:b].data_ptr(), qn_d[a:b].data_ptr(), b - a, n,
-                out_s[a:b].data_ptr(), out_i[a:b].data_ptr(), self.idx_base, self._ws_wide.data_ptr(), self._ws_wide.numel(),
-                int(tile_rows), int(max_blocks), st)
-            _lib.check(rc, "arx_bm25_search_wide")
-        return out_s, out_i
+        """`search` with `n` up to MAX_N_WIDE = 1024 (`arx_bm25_search_wide`): the same kernel, queries, scores, order, padding and filter
+        arguments, so for n <= 32 the same bits, and the first m entries of an n-list are the m-list.  This shard only: a cross-rank
+        merge of long lists is out of scope."""
+        return self._search("arx_bm25_search_wide", n, MAX_N_WIDE, self.WIDE_QUERY_STEP, queries, allow, filter_of, tile_rows, max_blocks)
 
     def search_distributed(self, queries, n: int = MAX_N, group=None, allow=None, filter_of=None):
         """Every rank passes the SAME queries; returns the global keyword top-n on every rank (local top-n -> all-gather -> merge kernel,

@@ -541,7 +541,15 @@ int32_t arx_mmr_select(const void* q, const void* cand, const int64_t* ids, int3
  * score depends on the index and the query's terms only, never on the tile size, the block count or the other queries of the call.
  * Output, per query: the n <= 32 rows with the largest (score desc, row asc) among rows holding at least one query term, as
  * (f32 score, int64 idx_base + row); unused slots are (-inf, -1), the convention of arx_topk_search, so per-shard lists merge
- * through arx_topk_merge.  ws: device scratch of arx_bm25_workspace_bytes(n_rows, n_queries, n) bytes (the per-block partial lists). */
+ * through arx_topk_merge.
+ * One kernel serves this call, the filtered calls and arx_bm25_search_wide below (csrc/bm25.hip): a block walks row tiles, keeps its
+ * candidates as 64-bit keys (score bits, then the inverted row) in a 4096-key LDS list that one cut function brings back to its n
+ * largest (rounds of a block-wide maximum for n <= 32, a block-wide sort beyond), and with more than one block per query (blocks = min(tiles, 512, 4096 / n[, max_blocks])) the blocks' sorted lists are
+ * merged by one kernel of the call's own, one block per query.  The keys are distinct, so the answer is one set in one order.
+ * ws: device scratch of arx_bm25_workspace_bytes(n_rows, n_queries, n) bytes
+ *   = round_up(min(ceil(n_rows / 1024), 512, 4096 / n) * n_queries * n * 8, 256)   (the per-block lists as 64-bit keys, sized for the
+ * smallest tile); may be NULL when the call runs one block per query.  The function returns -1 for n_rows <= 0, n_queries <= 0,
+ * n < 1 or n > 32. */
 int64_t arx_bm25_workspace_bytes(int64_t n_rows, int32_t n_queries, int32_t n);
 int32_t arx_bm25_search(const int64_t* term_ptr, const uint32_t* post_row, const float* post_w, int32_t vocab, int64_t n_rows,
                         const int32_t* q_terms, const int32_t* q_nterms, int32_t n_queries, int32_t n, float* out_scores,
@@ -563,8 +571,9 @@ int32_t arx_bm25_search_tuned(const int64_t* term_ptr, const uint32_t* post_row,
  * allowed by allow[filter_of[q]].  A row's score has exactly the bits arx_bm25_search / arx_bm25_scores give it: the impacts are
  * untouched, so idf and avgdl stay statistics of the WHOLE corpus, as a Lucene filter clause leaves them.  A query's output depends
  * on the query, its own bitmap and the index only: not on the other queries, their filters, n_filters, tile_rows or max_blocks.
- * Padding, merge and workspace (arx_bm25_workspace_bytes) are those of arx_bm25_search.  ARX_ERR_ARG before any launch: a null
- * allow, n_filters < 1, and every argument error of arx_bm25_search.
+ * Kernel, cut, merge, padding and workspace (arx_bm25_workspace_bytes) are those of arx_bm25_search; the bitmap words of a tile are
+ * staged in LDS and a key is appended only when its row's bit is set.  ARX_ERR_ARG before any launch: a null allow, n_filters < 1,
+ * and every argument error of arx_bm25_search.
  * Cost: a tile (<= 12288 rows) without an allowed row is skipped, with its binary searches and posting reads; a tile with one is
  * streamed whole.  So a contiguous filter saves bandwidth and a scattered one does not, however selective: a doc-at-a-time path for
  * those is out of scope. */
@@ -578,8 +587,8 @@ int32_t arx_bm25_search_filtered_tuned(const int64_t* term_ptr, const uint32_t* 
                                        float* out_scores, int64_t* out_ids, int64_t idx_base, void* ws, int64_t ws_bytes,
                                        int32_t tile_rows, int32_t max_blocks, void* stream);
 /* Wide BM25 top-n: n in [1, 1024], with an optional row filter (hybrid search with candidate lists longer than 32; opt-in:
- * `hybrid_on_device=True`, --hybrid-on-device).  Index, queries, scores and filter are those of arx_bm25_search and
- * arx_bm25_search_filtered:
+ * `hybrid_on_device=True`, --hybrid-on-device).  The kernel, cut and merge of arx_bm25_search and arx_bm25_search_filtered with two
+ * other limits: n <= 1024, and blocks * n <= 65536 instead of 4096.  Index, queries, scores and filter are theirs:
  *   allow == NULL   the unfiltered search (n_filters is ignored and filter_of must be NULL);
  *   allow != NULL   device uint64 [n_filters][ceil(n_rows / 64)] with filter_of device int32 [n_queries] or NULL (= bitmap 0), in the
  *                   convention of arx_bm25_search_filtered: an index outside [0, n_filters) gives that query no row and reads nothing,
@@ -589,10 +598,9 @@ int32_t arx_bm25_search_filtered_tuned(const int64_t* term_ptr, const uint32_t* 
  * Output, per query: the n rows with the largest (score desc, row asc) among the (allowed) rows holding a query term, as (f32 score,
  * int64 idx_base + row); unused slots are (-inf, -1).  For n <= 32 the output equals arx_bm25_search / arx_bm25_search_filtered bit
  * for bit, and for m < n the first m entries of the n-list are the m-list.
- * The per-block lists are merged by a kernel of this call's own (one block per query, the partial lists streamed through an LDS
- * list with sort-and-cut), not by arx_topk_merge: blocks = min(tiles, 512, 65536 / n[, max_blocks]), 64 blocks at n = 1024.
+ * blocks = min(tiles, 512, 65536 / n[, max_blocks]), 64 blocks at n = 1024.
  * tile_rows: accumulator rows per LDS tile, a multiple of 1024 in [1024, 12288]; 0 = default (min(round_up(n_rows, 1024), 10240): two
- * blocks per CU).  max_blocks: cap on the blocks per query (0 = default).
+ * blocks per CU; the default of every BM25 call).  max_blocks: cap on the blocks per query (0 = default).
  * ws: device scratch of arx_bm25_wide_workspace_bytes(n_rows, n_queries, n) bytes
  *   = round_up(min(ceil(n_rows / 1024), 512, 65536 / n) * n_queries * n * 8, 256)   (the per-block lists as 64-bit keys);
  * may be NULL when the call runs one block per query.  The function returns -1 for n_rows <= 0, n_queries <= 0, n < 1 or n > 1024.

@@ -255,8 +255,48 @@ def test_keyword_index_slices_filter_of_with_the_queries_and_refuses_wrong_tenso
             idx.search(queries, 10, **kw)
 
 
+@pytest.mark.parametrize("n", (1, 32))
+def test_the_stated_workspace_is_enough_and_one_byte_less_is_refused(hip, n):
+    """arx_bm25_search_tuned and arx_bm25_search_filtered_tuned called directly with exactly arx_bm25_workspace_bytes(...) bytes of an
+    0xA5-filled buffer: 4097 rows in 1024-row tiles are five blocks per query and a merge.  The 256 bytes behind the stated need stay
+    untouched and the answer is the definition's, bit for bit; with one byte less the call is refused and nothing is launched."""
+    from arxiv_rag_amd import _lib
+    lib = _lib.load()
+    n_rows, tile, nq = 4097, 1024, 3
+    idx = make_index(docs_of(n_rows), idx_base=BASE)
+    qs = [query_sets(idx)[j] for j in (1, 2, 4)]                             # 2 and 17 terms, and the term in every row
+    rows = np.arange(n_rows)
+    masks = [np.random.RandomState(7).rand(n_rows) < 0.5, rows % 3 == 0]
+    f_of = [0, 1, 0]
+    ref = Reference(idx, qs)
+    from arxiv_rag_amd.keyword import pack_query_terms
+    qt, qn = pack_query_terms(qs, idx.vocab_size)
+    qt_d, qn_d = torch.from_numpy(qt).cuda(), torch.from_numpy(qn).cuda()
+    allow, fo = on_device(pack(masks, garbage_seed=1)), torch.tensor(f_of, dtype=torch.int32, device="cuda")
+    need = lib.arx_bm25_workspace_bytes(n_rows, nq, n)
+    assert need == -(-5 * nq * n * 8 // 256) * 256                          # five blocks of 8-byte keys
+    head = (idx.term_ptr.data_ptr(), idx.post_row.data_ptr(), idx.post_w.data_ptr(), idx.vocab_size, n_rows)
+    st = torch.cuda.current_stream().cuda_stream
+    cases = (("arx_bm25_search_tuned", (), [(q, np.ones(n_rows, bool), "ones") for q in range(nq)]),
+             ("arx_bm25_search_filtered_tuned", (allow.data_ptr(), len(masks), fo.data_ptr()), [(q, masks[f_of[q]], f_of[q]) for q in range(nq)]))
+    for name, filters, pairs in cases:
+        def call(ws, ws_bytes, out_s, out_i):
+            rc = getattr(lib, name)(*head, *filters, qt_d.data_ptr(), qn_d.data_ptr(), nq, n, out_s.data_ptr(), out_i.data_ptr(), BASE,
+                                    ws.data_ptr(), ws_bytes, tile, 0, st)
+            torch.cuda.synchronize()
+            return rc
+        ws = torch.full((need + 256,), 0xA5, dtype=torch.uint8, device="cuda")
+        out_s = torch.zeros((nq, n), dtype=torch.float32, device="cuda"); out_i = torch.zeros((nq, n), dtype=torch.int64, device="cuda")
+        assert call(ws, need, out_s, out_i) == 0, lib.arx_last_error().decode()
+        assert (ws[need:] == 0xA5).all() and not (ws[:need] == 0xA5).all(), name
+        assert_bits((out_s, out_i), ref.expect(pairs, n), (name, n))
+        ws.fill_(0xA5); out_s.fill_(7.0); out_i.fill_(7)
+        assert call(ws, need - 1, out_s, out_i) == -1 and "workspace too small" in lib.arx_last_error().decode(), name
+        assert (ws == 0xA5).all() and (out_s == 7.0).all() and (out_i == 7).all(), name       # nothing was launched
+
+
 # 4 ---------------------------------------------------------------------------------------------------------------------------------
-SECTIONS = ("abstract", "Introduction", "Methods", "Results")
+SECTIONS =("abstract", "Introduction", "Methods", "Results")
 
 
 def _collections():

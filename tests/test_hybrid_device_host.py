@@ -202,8 +202,8 @@ def test_new_kernels_do_not_spill_and_keep_two_blocks_per_cu():
     ks = {}
     for f in ("bm25.resources.txt", "fuse.resources.txt"):
         ks.update({m.group(1): (int(m.group(4)), int(m.group(7)), int(m.group(5))) for m in PAT.finditer((BUILD / f).read_text())})
-    wide = {k: v for k, v in ks.items() if "bm25_wide_kernel" in k}
+    wide = {k: v for k, v in ks.items() if "bm25_search_kernel" in k}          # the one top-n kernel: arx_bm25_search_wide runs it too
     assert len(wide) == 2 and any("ILb1E" in k for k in wide) and any("ILb0E" in k for k in wide), list(ks)
-    new = {**wide, **{k: v for k, v in ks.items() if "bm25_wide_merge_kernel" in k or "hybrid_fuse_kernel" in k}}
+    new = {**wide, **{k: v for k, v in ks.items() if "bm25_merge_kernel" in k or "hybrid_fuse_kernel" in k}}
     assert len(new) == 4 and all(v[0] == 0 and v[1] == 0 for v in new.values()), new
     assert all(v[2] >= 4 for v in wide.values()), wide        # two 8-wave blocks per CU (the LDS budget of the 10240-row tile)

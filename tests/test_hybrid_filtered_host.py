@@ -222,7 +222,7 @@ def test_filtered_kernel_does_not_spill_or_use_scratch():
     search = {k: v for k, v in ks.items() if "bm25_search_kernel" in k}
     assert len(search) == 2 and any("ILb1E" in k for k in search) and any("ILb0E" in k for k in search), list(ks)   # <true> and <false>
     assert all(v[0] == 0 and v[1] == 0 for v in search.values()), search
-    # two 8-wave blocks per CU (the LDS budget of the 12288-row tile) need 4 waves per SIMD
+    # two 8-wave blocks per CU (the LDS budget of the default 10240-row tile) need 4 waves per SIMD
     assert all(v[2] >= 4 for v in search.values()), search
 
 

@@ -677,7 +677,7 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
                    where_document: Optional[Dict] = None, *, mmr_lambda: Optional[float] = None, mmr_fetch_k: int = 32,
                    keep_mask: Optional[np.ndarray] = None, group_by_paper: bool = False, chunks_per_paper: int = 1,
                    where_on_device: bool = False, min_score: Optional[float] = None, hybrid_filters: bool = False,
-                   hybrid_on_device: bool = False) -> List[Dict]:
+                   hybrid_on_device: bool = False, keyword_build_on_device: bool = False) -> List[Dict]:
     """Brute-force cosine top-k (config.yaml:63-64 `top_k: 10`) over the rank's fp16 rows in HBM; with
     torchrun each rank holds the contiguous row shard it encoded and the partial top-k lists are
     all-gathered over RCCL and merged.  `shard` is the `ShardSink` the encode step filled: rows [lo, hi) are already where they
@@ -732,8 +732,13 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
     (`keyword.fuse_device`) and, with a reranker, `rerank_top_k` may be up to 1024: the cosine side then comes from
     `ShardIndex.search_range(-inf)`, the keyword side from `KeywordIndex.search_wide`, and the cross-encoder scores the fused
     `rerank_top_k` 32 pairs at a time.  Beyond 32 not with a per-query `where` list or more than one rank.  With `rerank_top_k <= 32`
-    the same hits as without it (INTEGRATION.md "Hybrid search on the device")."""
+    the same hits as without it (INTEGRATION.md "Hybrid search on the device").
+    `keyword_build_on_device` (False = nothing changes; needs `hybrid_alpha`): the BM25 index is built on the device
+    (`KeywordIndex(build_on_device=True)`); it is the default build's, bit for bit, so the hits are the same (INTEGRATION.md "Building the
+    keyword index on the device")."""
     from .retrieval import RowFilters, check_hybrid_on_device, check_shared_query, retrieve
+    if keyword_build_on_device and hybrid_alpha is None:
+        raise ValueError("keyword_build_on_device needs hybrid_alpha: it chooses where the BM25 keyword index is built")
     if hybrid_on_device:
         if hybrid_alpha is None:
             raise ValueError("hybrid_on_device needs hybrid_alpha: it chooses where the two candidate lists are fused")
@@ -789,7 +794,7 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
         if top_k > n_cand:
             raise ValueError(f"hybrid search keeps at most {n_cand} results per query (top_k={top_k})")
         return KeywordIndex(texts=[c["text"] for c in chunks], tokenizer=model.tokenizer, stats="global" if world > 1 else None,
-                            idx_base=chunk_base, device=dev)
+                            idx_base=chunk_base, device=dev, **({"build_on_device": True} if keyword_build_on_device else {}))
     # (a count the device would have to be waited for is left unknown for per-query lists: it merely steers the search's path)
     filters = RowFilters([c.get("metadata") or {} for c in chunks] if where is not None else (), dev, 0, n_rows, keep_mask=keep_mask,
                          texts=lambda: [c["text"] for c in chunks], where_on_device=where_on_device, count_both=False)
@@ -885,6 +890,9 @@ def build_parser() -> argparse.ArgumentParser:
                    help=f"Fuse the two candidate lists of --hybrid-alpha on the GPU; --rerank-top-k may then be up to {HYBRID_DEVICE_MAX_K} "
                         "(beyond 32: one GPU rank only, not with --where-file).  config.yaml's recipe: --hybrid-alpha 0.7 --rerank-model ... "
                         "--rerank-top-k 50 --top-k 10 --hybrid-on-device (default: off, the lists are fused on the host)")
+    p.add_argument("--keyword-build-on-device", action="store_true",
+                   help="Build the BM25 keyword index of --hybrid-alpha on the GPU (a radix sort of the word pieces) instead of with numpy "
+                        "on the host; the index and the results are the same (default: off)")
     p.add_argument("--where", type=str, default=None,
                    help="Chroma metadata filter for --queries as JSON, e.g. '{\"section\": \"abstract\"}' or "
                         "'{\"quality_score\": {\"$gte\": 0.95}}': only matching chunks are searched (with --hybrid-alpha only next to --hybrid-filters)")
@@ -967,6 +975,13 @@ def check_hybrid_device_args(args) -> Optional[str]:
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
             return (f"--hybrid-on-device with --rerank-top-k above {RERANK_MAX_K} needs a single GPU rank: a cross-rank merge of long "
                     "candidate lists is out of scope")
+    return None
+
+
+def check_keyword_build_args(args) -> Optional[str]:
+    """-> an error message for an unusable --keyword-build-on-device, else None."""
+    if getattr(args, "keyword_build_on_device", False) and getattr(args, "hybrid_alpha", None) is None:
+        return "--keyword-build-on-device needs --hybrid-alpha: it chooses where the BM25 keyword index is built"
     return None
 
 
@@ -1185,7 +1200,7 @@ def check_where_document_args(args) -> Optional[str]:
 def main(argv: Optional[Sequence[str]] = None, model_factory: Optional[Callable] = None) -> int:
     global _model, _model_name
     args = build_parser().parse_args(argv)
-    err = (check_rerank_args(args) or check_hybrid_args(args) or check_hybrid_filters_args(args) or check_hybrid_device_args(args) or check_where_args(args) or check_where_file_args(args) or check_where_device_args(args)
+    err = (check_rerank_args(args) or check_hybrid_args(args) or check_hybrid_filters_args(args) or check_hybrid_device_args(args) or check_keyword_build_args(args) or check_where_args(args) or check_where_file_args(args) or check_where_device_args(args)
            or check_where_document_args(args)
            or check_mmr_args(args) or check_dedup_args(args) or check_group_args(args) or check_range_args(args))
     if err:
@@ -1288,7 +1303,8 @@ def main(argv: Optional[Sequence[str]] = None, model_factory: Optional[Callable]
                                **({"where_on_device": True} if args.where_on_device else {}),
                                **({"min_score": args.min_score} if args.min_score is not None else {}),
                                **({"hybrid_filters": True} if args.hybrid_filters else {}),
-                               **({"hybrid_on_device": True} if args.hybrid_on_device else {}))
+                               **({"hybrid_on_device": True} if args.hybrid_on_device else {}),
+                               **({"keyword_build_on_device": True} if args.keyword_build_on_device else {}))
         store_time = 0.0
         if rank == 0 and not args.skip_chroma:
             try:

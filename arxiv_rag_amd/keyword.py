@@ -11,9 +11,13 @@ The reference configures hybrid search and has no code for it, so the definition
 * `arx_bm25_search_filtered` does so among the rows a bitmap allows (one bitmap per query); scores, idf and avgdl are unchanged;
 * `fuse` is relative-score fusion of the (global) dense and keyword lists: `alpha * normD + (1 - alpha) * normK`;
 * `KeywordIndex.search_wide` (`arx_bm25_search_wide`) is the same top-n for n <= 1024 and `fuse_device` (`arx_hybrid_fuse`) is `fuse` on
-  the device, bit for bit: hybrid search with long candidate lists (opt-in, `hybrid_on_device`).
+  the device, bit for bit: hybrid search with long candidate lists (opt-in, `hybrid_on_device`);
+* `build_postings_device` + `build_impacts_device` (`arx_bm25_build_postings`, `arx_bm25_build_impacts`, csrc/bm25_build.hip) are
+  `build_postings` and `impacts_f64(...).astype(float32)` on the device, bit for bit: the index built in HBM from the flat word pieces
+  (opt-in, `KeywordIndex(build_on_device=True)`; the host build stays the default).
 
-`KeywordStats`, `build_postings`, `impacts_f64` and `fuse` are numpy only; `KeywordIndex` needs the GPU.
+`KeywordStats`, `build_postings`, `impacts_f64`, `flatten_pieces` and `fuse` are numpy only; `KeywordIndex` and the `*_device` functions
+need the GPU.
 """
 from __future__ import annotations
 
@@ -105,6 +109,98 @@ def impacts_f64(term_ptr: np.ndarray, rows: np.ndarray, tf: np.ndarray, dl: np.n
     avgdl = stats.avgdl
     norm = BM25_K1 * (1.0 - BM25_B + BM25_B * dl[rows.astype(np.int64)].astype(np.float64) / avgdl) if len(rows) else np.zeros(0)
     return idf * tff * (BM25_K1 + 1.0) / (tff + norm)
+
+
+def flatten_pieces(piece_lists: Sequence[Sequence[int]]) -> Tuple[np.ndarray, np.ndarray]:
+    """-> (pieces int32 [T], doc_ptr int64 [n + 1]): the lists concatenated in order, `build_postings_device`'s input."""
+    import itertools
+    n = len(piece_lists)
+    doc_ptr = np.zeros(n + 1, np.int64)
+    if n:
+        np.cumsum(np.fromiter(map(len, piece_lists), np.int64, n), out=doc_ptr[1:])
+    flat = np.fromiter(itertools.chain.from_iterable(piece_lists), np.int64, int(doc_ptr[-1]))
+    if len(flat) and (flat.min() < np.iinfo(np.int32).min or flat.max() > np.iinfo(np.int32).max):
+        raise ValueError("term id outside the int32 range")
+    return flat.astype(np.int32), doc_ptr
+
+
+BUILD_TILE_TOKENS = 2048       # default tile of `arx_bm25_build_postings`: a block's chunk of tokens is a whole number of tiles
+BUILD_ROUND_TOKENS = 256       # ... and a block walks its chunk this many tokens at a time (the smallest tile)
+
+
+class DevicePostings:
+    """What `build_postings_device` returns: `build_postings`' arrays in HBM (`term_ptr` int64 [V + 1], `post_row` uint32 as int32 bits
+    and `post_tf` int32, each [max(P, 1)]), `doc_ptr` int64 [n + 1] in HBM for `build_impacts_device`, `n_postings` = P, and the host
+    copies `KeywordIndex` keeps: `term_ptr_host` and `dl`."""
+
+    def __init__(self, term_ptr, post_row, post_tf, doc_ptr, n_postings, term_ptr_host, dl):
+        self.term_ptr, self.post_row, self.post_tf, self.doc_ptr = term_ptr, post_row, post_tf, doc_ptr
+        self.n_postings, self.term_ptr_host, self.dl = int(n_postings), term_ptr_host, dl
+
+
+def build_postings_raw(pieces_d, doc_ptr_d, n_tokens: int, n_docs: int, vocab_size: int, term_ptr, post_row, post_tf, n_post, bad,
+                       tile_tokens: int = 0, max_blocks: int = 0) -> None:
+    """`arx_bm25_build_postings_tuned` on device tensors the caller allocated (outputs with room for `n_tokens` postings); the
+    workspace is this call's own."""
+    import torch
+    from . import _lib
+    lib = _lib.load()
+    need = lib.arx_bm25_build_workspace_bytes(int(n_tokens), int(n_docs), int(vocab_size))
+    if need < 0:
+        raise ValueError(f"n_tokens={n_tokens} must be below 2^31, n_docs={n_docs} below 2^32 and vocab_size={vocab_size} in [1, 2^24]")
+    ws = torch.empty(need, dtype=torch.uint8, device=pieces_d.device)
+    rc = lib.arx_bm25_build_postings_tuned(pieces_d.data_ptr(), int(n_tokens), doc_ptr_d.data_ptr(), int(n_docs), int(vocab_size),
+                                           term_ptr.data_ptr(), post_row.data_ptr(), post_tf.data_ptr(), n_post.data_ptr(), bad.data_ptr(),
+                                           ws.data_ptr(), ws.numel(), int(tile_tokens), int(max_blocks),
+                                           torch.cuda.current_stream(pieces_d.device).cuda_stream)
+    _lib.check(rc, "arx_bm25_build_postings")
+
+
+def build_postings_device(pieces_flat, doc_ptr, vocab_size: int, device="cuda:0", tile_tokens: int = 0, max_blocks: int = 0) -> DevicePostings:
+    """`build_postings` on the device, bit for bit (`arx_bm25_build_postings`).  `pieces_flat` int32 [T] and `doc_ptr` int64 [n + 1]
+    (host arrays, `flatten_pieces`' layout).  `tile_tokens` / `max_blocks` choose the launch shape (tests, tuning): the answer's bits do
+    not depend on it.  An id outside [0, V) raises `build_postings`' ValueError."""
+    import torch
+    pieces_flat, doc_ptr = np.ascontiguousarray(pieces_flat, np.int32), np.ascontiguousarray(doc_ptr, np.int64)
+    n_tokens, n_docs, V = len(pieces_flat), len(doc_ptr) - 1, int(vocab_size)
+    if pieces_flat.ndim != 1 or doc_ptr.ndim != 1 or n_docs < 0 or doc_ptr[0] != 0 or doc_ptr[-1] != n_tokens or np.any(np.diff(doc_ptr) < 0):
+        raise ValueError("doc_ptr must be non-decreasing from 0 to len(pieces_flat)")
+    dev = torch.device(device)
+    # (never zero-sized device buffers: the C ABI wants non-null pointers even for a shard without tokens)
+    pieces_d = torch.from_numpy(pieces_flat if n_tokens else np.zeros(1, np.int32)).to(dev)
+    doc_ptr_d = torch.from_numpy(doc_ptr).to(dev)
+    term_ptr = torch.empty(V + 1, dtype=torch.int64, device=dev)
+    post_row = torch.empty(max(n_tokens, 1), dtype=torch.int32, device=dev)
+    post_tf = torch.empty(max(n_tokens, 1), dtype=torch.int32, device=dev)
+    n_post = torch.zeros(1, dtype=torch.int64, device=dev)
+    bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    build_postings_raw(pieces_d, doc_ptr_d, n_tokens, n_docs, V, term_ptr, post_row, post_tf, n_post, bad, tile_tokens, max_blocks)
+    if int(bad.item()):
+        raise ValueError(f"term id outside [0, {V})")
+    P = int(n_post.item())
+    if P == 0:
+        post_row, post_tf = torch.zeros(1, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int32, device=dev)
+    elif P < post_row.numel():                               # (the capacity was n_tokens: give the rest back)
+        post_row, post_tf = post_row[:P].clone(), post_tf[:P].clone()
+    return DevicePostings(term_ptr, post_row, post_tf, doc_ptr_d, P, term_ptr.cpu().numpy(), np.diff(doc_ptr))
+
+
+def build_impacts_device(built: DevicePostings, stats: KeywordStats):
+    """`impacts_f64(...).astype(float32)` on the device, bit for bit (`arx_bm25_build_impacts`), with the (global) statistics `stats`:
+    -> post_w f32 [max(P, 1)] in HBM.  The idf table is `idf_f64(stats)` from the host (V doubles)."""
+    import torch
+    from . import _lib
+    dev = built.term_ptr.device
+    V = int(built.term_ptr.numel()) - 1
+    if stats.df.shape[0] != V:
+        raise ValueError("statistics are for another vocabulary size")
+    post_w = torch.zeros(max(built.n_postings, 1), dtype=torch.float32, device=dev)
+    idf = torch.from_numpy(idf_f64(stats)).to(dev)
+    rc = _lib.load().arx_bm25_build_impacts(built.term_ptr.data_ptr(), built.post_row.data_ptr(), built.post_tf.data_ptr(), built.n_postings,
+                                            built.doc_ptr.data_ptr(), len(built.dl), idf.data_ptr(), V, float(stats.avgdl), post_w.data_ptr(),
+                                            torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(rc, "arx_bm25_build_impacts")
+    return post_w
 
 
 def distinct_terms(pieces: Sequence[int], exclude=()) -> List[int]:
@@ -225,18 +321,28 @@ class KeywordIndex:
     """This rank's BM25 impact index in HBM (CSR by term) and its top-n search through `arx_bm25_search`."""
 
     def __init__(self, pieces: Optional[Sequence[Sequence[int]]] = None, texts: Optional[Sequence[str]] = None, tokenizer=None,
-                 vocab_size: Optional[int] = None, stats: Optional[KeywordStats] = None, idx_base: int = 0, device="cuda:0"):
+                 vocab_size: Optional[int] = None, stats: Optional[KeywordStats] = None, idx_base: int = 0, device="cuda:0",
+                 build_on_device: bool = False):
         """`pieces` (word-piece id lists) or `texts` + `tokenizer`.  `stats`: the GLOBAL statistics when this index is one shard of a
         larger corpus (None = this shard's own; "global" = this shard's own summed over all ranks of the host group).  Row r of the
-        index is global row `idx_base + r`."""
+        index is global row `idx_base + r`.
+        `build_on_device` (False = nothing changes): the postings and their impacts are computed on the device
+        (`build_postings_device`, `build_impacts_device`) and stay there; the index is the default build's, bit for bit.  `pieces` may
+        then also be a `(pieces int32 [T], doc_ptr int64 [n + 1])` pair of numpy arrays, and `texts` go through
+        `tokenizer.full_pieces_flat`, which yields such a pair without a Python list per chunk."""
         if pieces is None:
             if texts is None or tokenizer is None:
                 raise ValueError("pass pieces, or texts with a tokenizer")
-            pieces = tokenizer._full_pieces(list(texts))
+            pieces = tokenizer.full_pieces_flat(list(texts)) if build_on_device else tokenizer._full_pieces(list(texts))
         if vocab_size is None:
             if tokenizer is None:
                 raise ValueError("vocab_size is needed when no tokenizer is given")
             vocab_size = int(tokenizer.cfg.vocab_size)
+        if build_on_device:
+            flat, doc_ptr = pieces if (isinstance(pieces, tuple) and len(pieces) == 2 and isinstance(pieces[0], np.ndarray)) else flatten_pieces(pieces)
+            built = build_postings_device(flat, doc_ptr, int(vocab_size), device)
+            self._setup(built.term_ptr_host, None, None, built.dl, int(vocab_size), stats, idx_base, device, tokenizer, built=built)
+            return
         term_ptr, rows, tf, dl = build_postings(pieces, int(vocab_size))
         self._setup(term_ptr, rows, tf, dl, int(vocab_size), stats, idx_base, device, tokenizer)
 
@@ -249,7 +355,8 @@ class KeywordIndex:
                     len(term_ptr) - 1, stats, idx_base, device, tokenizer)
         return self
 
-    def _setup(self, term_ptr, rows, tf, dl, vocab_size, stats, idx_base, device, tokenizer):
+    def _setup(self, term_ptr, rows, tf, dl, vocab_size, stats, idx_base, device, tokenizer, built: Optional[DevicePostings] = None):
+        """`built`: the postings are in HBM already (`build_on_device`); `rows` and `tf` are then None and nothing is uploaded."""
         import torch
         from . import _lib
         self.lib = _lib.load()
@@ -262,15 +369,19 @@ class KeywordIndex:
         self.stats = stats if stats is not None else self.local_stats
         if self.stats.df.shape[0] != self.vocab_size:
             raise ValueError("statistics are for another vocabulary size")
-        w64 = impacts_f64(term_ptr, rows, tf, dl, self.stats)
-        self.n_rows, self.n_postings = len(dl), len(rows)
         self.device = torch.device(device)
         self.term_ptr_host = term_ptr
+        self._ws = None
+        if built is not None:
+            self.n_rows, self.n_postings = len(dl), built.n_postings
+            self.term_ptr, self.post_row, self.post_w = built.term_ptr, built.post_row, build_impacts_device(built, self.stats)
+            return
+        w64 = impacts_f64(term_ptr, rows, tf, dl, self.stats)
+        self.n_rows, self.n_postings = len(dl), len(rows)
         self.term_ptr = torch.from_numpy(term_ptr).to(self.device)
         # (never zero-sized device buffers: the C ABI wants non-null pointers even for a shard without postings)
         self.post_row = torch.from_numpy(np.ascontiguousarray(rows if len(rows) else np.zeros(1, np.uint32)).view(np.int32)).to(self.device)
         self.post_w = torch.from_numpy(np.ascontiguousarray(w64.astype(np.float32) if len(rows) else np.zeros(1, np.float32))).to(self.device)
-        self._ws = None
 
     # ---- queries ------------------------------------------------------------------------------------------------------------
     def query_terms(self, texts: Sequence[str]) -> List[List[int]]:

@@ -76,7 +76,8 @@ class HipCollection:
     def __init__(self, embeddings: np.ndarray, metadata: Sequence[Dict], device="cuda:0", encoder=None,
                  rank: int = 0, world: int = 1, chunk_rows: int = 1 << 18, keyword: bool = False, tokenizer=None,
                  documents: bool = False, dedup_threshold: Optional[float] = None, group_key: Optional[str] = None,
-                 where_on_device: bool = False, hybrid_filters: bool = False, hybrid_on_device: bool = False):
+                 where_on_device: bool = False, hybrid_filters: bool = False, hybrid_on_device: bool = False,
+                 keyword_build_on_device: bool = False):
         """`keyword=True`: also build a BM25 `keyword.KeywordIndex` over this shard's `metadata[i]["text"]` (word pieces of `tokenizer`,
         default the encoder's; corpus statistics summed over all ranks when `world > 1`), which `query(hybrid_alpha=...)` needs.
         `documents=True`: also keep this shard's texts as a UTF-8 blob in HBM (`where_document.DocumentStore`), which
@@ -103,13 +104,19 @@ class HipCollection:
         `hybrid_on_device` (False = nothing changes; needs `keyword=True`): `query(hybrid_alpha=...)` fuses the two candidate lists on
         the device (`keyword.fuse_device`, `arx_hybrid_fuse`) and accepts `n_candidates` up to 1024, with or without `reranker`: the
         dense list then comes from `ShardIndex.search_range(-inf)` and the keyword list from `KeywordIndex.search_wide`.  With
-        `n_candidates <= 32` the result is the default path's, bit for bit (INTEGRATION.md "Hybrid search on the device")."""
+        `n_candidates <= 32` the result is the default path's, bit for bit (INTEGRATION.md "Hybrid search on the device").
+        `keyword_build_on_device` (False = nothing changes; needs `keyword=True`): the BM25 index is built on the device
+        (`KeywordIndex(build_on_device=True)`: `arx_bm25_build_postings`, `arx_bm25_build_impacts`) from the flat word pieces of
+        `tokenizer.full_pieces_flat`.  The index is the default build's, bit for bit, so every query answers the same (INTEGRATION.md
+        "Building the keyword index on the device")."""
         import torch
         from .index import ShardIndex, shard_bounds
         if hybrid_filters and not keyword:
             raise ValueError("hybrid_filters=True needs keyword=True: it passes the row filters to the BM25 keyword search")
         if hybrid_on_device and not keyword:
             raise ValueError("hybrid_on_device=True needs keyword=True: it chooses where the BM25 keyword list and the cosine list are fused")
+        if keyword_build_on_device and not keyword:
+            raise ValueError("keyword_build_on_device=True needs keyword=True: it chooses where the BM25 keyword index is built")
         self.hybrid_filters = bool(hybrid_filters)
         self.hybrid_on_device = bool(hybrid_on_device)
         if dedup_threshold is not None:
@@ -145,7 +152,8 @@ class HipCollection:
             if tokenizer is None:
                 raise ValueError("keyword=True needs a tokenizer (or an encoder that has one)")
             self.keyword = KeywordIndex(texts=[metadata[r].get("text") or "" for r in range(lo, hi)], tokenizer=tokenizer,
-                                        stats="global" if world > 1 else None, idx_base=lo, device=device)
+                                        stats="global" if world > 1 else None, idx_base=lo, device=device,
+                                        **({"build_on_device": True} if keyword_build_on_device else {}))
         self.documents = None
         if documents:
             from .where_document import DocumentStore

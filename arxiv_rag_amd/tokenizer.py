@@ -224,6 +224,53 @@ class WordPieceTokenizer:
         self._tok.no_truncation()
         return [e.ids for e in self._tok.encode_batch(list(texts), add_special_tokens=False)]
 
+    FLAT_PIECE_CAP = 512           # pieces per text the native feeder's id matrix has room for in `full_pieces_flat`
+
+    def full_pieces_flat(self, texts: Sequence[str], batch: int = 8192, piece_cap: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """-> (pieces int32 [T], doc_ptr int64 [n + 1]): the ids of `_full_pieces(texts)` concatenated (no specials, no truncation),
+        text r being pieces[doc_ptr[r]:doc_ptr[r + 1]]: `keyword.build_postings_device`'s input, without a Python list per text.
+        `batch` texts at a time go through the native feeder where there is one (its two specials stripped, as in `_pieces`); the rows
+        it flags, and the rows that reach `piece_cap` pieces (the width of its id matrix; they may have been cut there), go through HF
+        `tokenizers`.  Without a native feeder every batch does."""
+        import itertools
+        texts = list(texts)
+        cap = int(self.FLAT_PIECE_CAP if piece_cap is None else piece_cap)
+        if batch < 1 or cap < 1:
+            raise ValueError(f"batch={batch} and piece_cap={cap} must be positive")
+        n = len(texts)
+        lens = np.zeros(n, np.int64)
+        parts: List[np.ndarray] = []
+        for a in range(0, n, batch):
+            chunk = texts[a:a + batch]
+            if self._native is None:
+                full = self._full_pieces(chunk)
+                lens[a:a + len(chunk)] = np.fromiter(map(len, full), np.int64, len(full))
+                parts.append(np.fromiter(itertools.chain.from_iterable(full), np.int32, int(lens[a:a + len(chunk)].sum())))
+                continue
+            ids, ln, fb = self._native.encode(chunk, cap + 2, resolve=self._segment_pieces)
+            np_ = np.maximum(ln.astype(np.int64) - 2, 0)                     # pieces between the two specials
+            rest = np.flatnonzero((fb != 0) | (np_ >= cap))
+            np_[rest] = 0
+            keep = np.arange(cap + 2)[None, :] - 1                           # piece j of a row sits in column j + 1
+            flat = ids[(keep >= 0) & (keep < np_[:, None])]                  # row-major: the rows in order, each row's pieces in order
+            if rest.size:                                                    # splice the HF rows in at their places
+                full = self._full_pieces([chunk[i] for i in rest])
+                off = np.zeros(len(chunk) + 1, np.int64)
+                np.cumsum(np_, out=off[1:])
+                pieces, at = [], 0
+                for i, p in zip(rest, full):
+                    pieces.append(flat[at:off[i]])
+                    pieces.append(np.asarray(p, np.int32))
+                    at = off[i]
+                    np_[i] = len(p)
+                pieces.append(flat[at:])
+                flat = np.concatenate(pieces)
+            lens[a:a + len(chunk)] = np_
+            parts.append(flat.astype(np.int32, copy=False))
+        doc_ptr = np.zeros(n + 1, np.int64)
+        np.cumsum(lens, out=doc_ptr[1:])
+        return (np.concatenate(parts) if parts else np.zeros(0, np.int32)), doc_ptr
+
     def _pieces(self, texts: Sequence[str], cap: int):
         """-> (word-piece lists cut to `cap`, exact lengths or -1 where a native row reached `cap` and was cut there)."""
         texts = list(texts)

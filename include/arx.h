@@ -631,6 +631,44 @@ int32_t arx_hybrid_fuse(const float* dense_scores, const int64_t* dense_ids, int
 int32_t arx_bm25_scores(const int64_t* term_ptr, const uint32_t* post_row, const float* post_w, int32_t vocab, int64_t n_rows,
                         const int32_t* q_terms, int32_t n_terms, int64_t row_lo, int64_t row_hi, int32_t tile_rows, float* out,
                         void* stream);
+/* The BM25 index built on the device (opt-in: `KeywordIndex(build_on_device=True)`, `keyword_build_on_device=True`,
+ * --keyword-build-on-device; csrc/bm25_build.hip).  arx_bm25_build_postings computes keyword.py `build_postings`, bit for bit:
+ *   pieces   device int32 [n_tokens]: the word-piece ids of every document, concatenated in row order
+ *   doc_ptr  device int64 [n_docs + 1], non-decreasing, doc_ptr[0] = 0, doc_ptr[n_docs] = n_tokens: document r is pieces[doc_ptr[r] ..
+ *            doc_ptr[r + 1]) (the caller's contract)
+ *   term_ptr device int64 [vocab + 1], post_row device uint32 and post_tf device int32, each with room for n_tokens entries: the
+ *            layout above, rows strictly ascending within a term, post_tf = occurrences of the term in the row; the first *n_postings
+ *            entries are written and nothing beyond them
+ *   n_postings device int64: P, the number of postings;  bad_id device int32: non-zero when any id lies outside [0, vocab).  Such an
+ *            id is sorted as term 0, so nothing is read or written out of range; the other outputs then mean nothing.
+ * A stable LSD radix sort by term id (8-bit digits, the row as payload; tokens arrive in row order), then the heads of equal
+ * (term, row) runs are numbered.  Integer LDS atomics in the digit histograms only; no global and no float atomics; bad_id is a plain
+ * store.  The output is one defined array set: it does not depend on tile_tokens or max_blocks.
+ * n_tokens == 0 or n_docs == 0: term_ptr is all zero, P is 0, and no kernel is launched.
+ * ws: device scratch of arx_bm25_build_workspace_bytes(n_tokens, n_docs, vocab) bytes
+ *   = 4 * round_up(4 * n_tokens, 256) + 4 * 256 * 2048   (two (key, row) pairs the passes alternate between, and the digit counts of up
+ * to 2048 blocks); the function returns -1 outside the limits below.
+ * ARX_ERR_ARG before any launch: a null pointer, n_tokens outside [0, 2^31), n_docs outside [0, 2^32), vocab outside [1, 2^24], a
+ * workspace that is too small.
+ * _tuned: the launch shape is the caller's (tests, tuning).  tile_tokens: a block's chunk of tokens is a whole number of tiles of this
+ * size, a multiple of 256 in [256, 65536] (0 = default, 2048); max_blocks: cap on the blocks, at most 2048 (0 = default, 2048). */
+int64_t arx_bm25_build_workspace_bytes(int64_t n_tokens, int64_t n_docs, int32_t vocab);
+int32_t arx_bm25_build_postings(const int32_t* pieces, int64_t n_tokens, const int64_t* doc_ptr, int64_t n_docs, int32_t vocab,
+                                int64_t* term_ptr, uint32_t* post_row, int32_t* post_tf, int64_t* n_postings, int32_t* bad_id,
+                                void* ws, int64_t ws_bytes, void* stream);
+int32_t arx_bm25_build_postings_tuned(const int32_t* pieces, int64_t n_tokens, const int64_t* doc_ptr, int64_t n_docs, int32_t vocab,
+                                      int64_t* term_ptr, uint32_t* post_row, int32_t* post_tf, int64_t* n_postings, int32_t* bad_id,
+                                      void* ws, int64_t ws_bytes, int32_t tile_tokens, int32_t max_blocks, void* stream);
+/* post_w f32 [n_postings] = keyword.py `impacts_f64(...).astype(float32)`, bit for bit, from the arrays above (n_postings as the host
+ * read it), idf device f64 [vocab] (`keyword.idf_f64` of the statistics in force, computed on the host: with global statistics their
+ * all-reduce sits between the two calls) and avgdl.  Per posting s of term t (the last t with term_ptr[t] <= s) and row r, in float64
+ * and in numpy's operation order, without FMA contraction, rounded once to f32 (k1 = 1.2, b = 0.75):
+ *   dl = doc_ptr[r + 1] - doc_ptr[r];  norm = k1 * ((1.0 - b) + (b * dl) / avgdl);  w = ((idf[t] * tf) * (k1 + 1.0)) / (tf + norm)
+ * ARX_ERR_ARG before any launch: a null pointer, n_postings outside [0, 2^31), n_docs outside [0, 2^32), vocab outside [1, 2^24], a
+ * negative or NaN avgdl.  n_postings == 0 launches nothing. */
+int32_t arx_bm25_build_impacts(const int64_t* term_ptr, const uint32_t* post_row, const int32_t* post_tf, int64_t n_postings,
+                               const int64_t* doc_ptr, int64_t n_docs, const double* idf, int32_t vocab, double avgdl, float* post_w,
+                               void* stream);
 
 /* Raw linear layer of the path: C[M,N] (bf16) = epi(A[M,K] (bf16) x W[N,K]^T (bf16) + bias[N] (f32)),
  * mode 0 = bias, 1 = bias + erf-GELU, 2 = bias + resid[M,N] (bf16).  K % 64 == 0, N % 8 == 0.

@@ -14,6 +14,18 @@
 // a mask; for len <= 4 that is the whole answer, longer patterns compare the rest out of LDS at the (rare) surviving positions.
 // A start position counts only if the whole match lies in [row_off[r], row_off[r + 1]): the blob has no separators, the bound is
 // arithmetic.  A (row, pattern) that has matched is not tested again and the row ends when every pattern has.
+//
+// arx_text_regex: which rows contain a match of which regular expression (`$regex` / `$not_regex`), same output contract.  The host
+// compiles a regex to a byte-level DFA (arxiv_rag_amd/regex_dfa.py); the kernel only walks tables.  The regex is blockIdx.y: a block
+// stages ONE table in LDS (up to 256 x 256 transitions + 512 bytes of classes and flags = 66 048 B, so two blocks share a CU's 160 KiB;
+// the eight worst-case tables of a call would not fit at once) and every wave of the block owns one 64-row group, hence one output
+// word, which it ballots and writes once.  A DFA run is sequential in a row's bytes, so a lane owns a row and carries its state from
+// start to end.  Unlike the substring scan, the text does not go through LDS: a lane reads its own row 16 bytes at a time (aligned on
+// the address, the next chunk in flight while it walks this one) and steps through them in registers, two dependent LDS reads per
+// byte (class, then transition).  A chunk staged for the whole group would cover few rows at a time at arXiv chunk lengths (~1 KB a
+// row, 64 KB a group) and leave most lanes idle in a loop whose cost is the table walk, not the load; a 128-byte line is read by one
+// lane in eight consecutive steps and stays in L1 / L2 meanwhile, so HBM is still read once.  A lane stops at a MATCHED or DEAD
+// state (both absorbing, so looking at the flags once per chunk changes no bit) or at its row's end; the wave stops when all have.
 #include "arx_common.h"
 
 namespace {
@@ -155,6 +167,80 @@ __global__ __launch_bounds__(TS_NT) void text_contains_kernel(const uint8_t* __r
     }
 }
 
+constexpr int TR_MAXRE = 8, TR_MAXS = 256, TR_MAXC = 256;
+constexpr int TR_HEAD = 4;                                    // uint16 n_states, uint16 n_classes, little-endian
+constexpr uint32_t TR_MATCHED = 1, TR_ACCEPT_AT_END = 2, TR_DEAD = 4;
+
+template <int WAVES>
+__global__ __launch_bounds__(WAVES * 64) void text_regex_kernel(const uint8_t* __restrict__ blob, const int64_t* __restrict__ row_off, int64_t n_rows,
+                                                                const uint8_t* __restrict__ tables, const int32_t* __restrict__ table_off,
+                                                                int64_t n_words, unsigned long long* __restrict__ out_bits) {
+    __shared__ __attribute__((aligned(16))) uint8_t s_trans[TR_MAXS * TR_MAXC];
+    __shared__ uint8_t s_cls[256], s_flags[TR_MAXS];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int p = blockIdx.y;
+    // the header and the table's size are device data: anything outside the contract makes this regex match no row, and every staged
+    // class and transition is forced into range, so no index below can leave s_cls / s_flags / s_trans whatever the table holds
+    const int64_t t0 = table_off[p], t_bytes = (int64_t)table_off[p + 1] - t0;
+    const uint8_t* tab = tables + t0;
+    int ns = 0, nc = 0;
+    if (t0 >= 0 && t_bytes >= TR_HEAD) {
+        ns = (int)tab[0] | ((int)tab[1] << 8);
+        nc = (int)tab[2] | ((int)tab[3] << 8);
+    }
+    const bool ok = ns >= 1 && ns <= TR_MAXS && nc >= 1 && nc <= TR_MAXC && t_bytes >= TR_HEAD + 256 + ns + ns * nc;     // (block-uniform)
+    if (ok) {
+        for (int i = tid; i < 256; i += WAVES * 64) {
+            const uint8_t c = tab[TR_HEAD + i];
+            s_cls[i] = c < nc ? c : 0;
+        }
+        for (int i = tid; i < ns; i += WAVES * 64) s_flags[i] = tab[TR_HEAD + 256 + i];
+        const uint8_t* tr = tab + TR_HEAD + 256 + ns;
+        for (int i = tid; i < ns * nc; i += WAVES * 64) {
+            const uint8_t t = tr[i];
+            s_trans[i] = t < ns ? t : 0;
+        }
+    }
+    __syncthreads();
+    const int64_t g = (int64_t)blockIdx.x * WAVES + wave;     // this wave's 64-row group
+    if (g >= n_words) return;
+    const int64_t total = row_off[n_rows];
+    const int64_t shift = (int64_t)((uintptr_t)blob & 15);    // chunk grid laid over the address, as in text_contains_kernel
+    const int64_t r = g * 64 + lane;
+    int64_t a = 0, b = 0;
+    if (r < n_rows) {
+        a = row_off[r], b = row_off[r + 1];
+        a = a < 0 ? 0 : (a > total ? total : a);
+        b = b < a ? a : (b > total ? total : b);
+    }
+    uint32_t state = 0;
+    bool run = ok && a < b && (s_flags[0] & (TR_MATCHED | TR_DEAD)) == 0;
+    int64_t base = ((a + shift) & ~(int64_t)15) - shift;      // blob position of this lane's chunk; the address is 16-B aligned
+    u32x4 cur = {0, 0, 0, 0};
+    if (run) cur = ts_load_chunk(blob, base, total);
+    while (__any(run ? 1 : 0)) {
+        const bool more = run && base + 16 < b;
+        u32x4 nxt = {0, 0, 0, 0};
+        if (more) nxt = ts_load_chunk(blob, base + 16, total);
+        if (run) {
+            const int64_t lo64 = a - base, hi64 = b - base;   // bytes [lo, hi) of the chunk are the row's
+            const int lo = lo64 <= 0 ? 0 : (int)lo64, hi = hi64 >= 16 ? 16 : (int)hi64;
+            const uint32_t w[4] = {cur.x, cur.y, cur.z, cur.w};
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                const uint32_t byte = (w[j >> 2] >> (8 * (j & 3))) & 0xffu;
+                if (j >= lo && j < hi) state = s_trans[state * (uint32_t)nc + s_cls[byte]];
+            }
+            run = more && (s_flags[state] & (TR_MATCHED | TR_DEAD)) == 0;
+        }
+        cur = nxt;
+        base += 16;
+    }
+    const bool hit = ok && r < n_rows && (s_flags[state] & (TR_MATCHED | TR_ACCEPT_AT_END)) != 0;
+    const unsigned long long word = __ballot(hit ? 1 : 0);
+    if (lane == 0) out_bits[(int64_t)p * n_words + g] = word;
+}
+
 // one block: the count is a plain store of one block's sum (nothing to zero, nothing to order)
 __global__ __launch_bounds__(1024) void bitmap_count_kernel(const unsigned long long* __restrict__ bits, int64_t n_rows, long long* __restrict__ out) {
     __shared__ long long s_part[16];
@@ -189,6 +275,34 @@ extern "C" int32_t arx_text_contains(const uint8_t* blob, const int64_t* row_off
                                                                               (unsigned long long*)out_bits);
     ARX_HIP_CHECK(hipGetLastError());
     return ARX_OK;
+}
+
+extern "C" int32_t arx_text_regex_tuned(const uint8_t* blob, const int64_t* row_off, int64_t n_rows, const uint8_t* tables, const int32_t* table_off,
+                                        int32_t n_re, uint64_t* out_bits, int32_t waves_per_block, void* stream) {
+    ARX_REQUIRE(n_rows > 0 && n_rows < ((int64_t)1 << 36), "n_rows=%lld must be in 1..2^36-1", (long long)n_rows);
+    ARX_REQUIRE(n_re >= 1 && n_re <= TR_MAXRE, "n_re=%d out of range 1..%d", n_re, TR_MAXRE);
+    ARX_REQUIRE(blob && row_off && tables && table_off && out_bits, "null pointer argument");
+    const int64_t n_words = (n_rows + 63) >> 6;
+    const int waves = waves_per_block == 0 ? 8 : waves_per_block;         // 8: two blocks a CU (LDS) = 16 waves walking
+    hipStream_t st = (hipStream_t)stream;
+    unsigned long long* out = (unsigned long long*)out_bits;
+#define TR_LAUNCH(W)                                                                                                                  \
+    case W:                                                                                                                           \
+        text_regex_kernel<W><<<dim3((unsigned)((n_words + W - 1) / W), (unsigned)n_re), W * 64, 0, st>>>(blob, row_off, n_rows, tables, \
+                                                                                                          table_off, n_words, out);  \
+        break;
+    switch (waves) {
+        TR_LAUNCH(1) TR_LAUNCH(2) TR_LAUNCH(4) TR_LAUNCH(8) TR_LAUNCH(16)
+        default: ARX_REQUIRE(false, "waves_per_block=%d must be 0 (default), 1, 2, 4, 8 or 16", waves_per_block);
+    }
+#undef TR_LAUNCH
+    ARX_HIP_CHECK(hipGetLastError());
+    return ARX_OK;
+}
+
+extern "C" int32_t arx_text_regex(const uint8_t* blob, const int64_t* row_off, int64_t n_rows, const uint8_t* tables, const int32_t* table_off,
+                                  int32_t n_re, uint64_t* out_bits, void* stream) {
+    return arx_text_regex_tuned(blob, row_off, n_rows, tables, table_off, n_re, out_bits, 0, stream);
 }
 
 extern "C" int32_t arx_bitmap_count(const uint64_t* bits, int64_t n_rows, int64_t* out_count, void* stream) {

@@ -677,7 +677,7 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
                    where_document: Optional[Dict] = None, *, mmr_lambda: Optional[float] = None, mmr_fetch_k: int = 32,
                    keep_mask: Optional[np.ndarray] = None, group_by_paper: bool = False, chunks_per_paper: int = 1,
                    where_on_device: bool = False, min_score: Optional[float] = None, hybrid_filters: bool = False,
-                   hybrid_on_device: bool = False, keyword_build_on_device: bool = False) -> List[Dict]:
+                   hybrid_on_device: bool = False, keyword_build_on_device: bool = False, document_regex: bool = False) -> List[Dict]:
     """Brute-force cosine top-k (config.yaml:63-64 `top_k: 10`) over the rank's fp16 rows in HBM; with
     torchrun each rank holds the contiguous row shard it encoded and the partial top-k lists are
     all-gathered over RCCL and merged.  `shard` is the `ShardSink` the encode step filled: rows [lo, hi) are already where they
@@ -735,7 +735,10 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
     the same hits as without it (INTEGRATION.md "Hybrid search on the device").
     `keyword_build_on_device` (False = nothing changes; needs `hybrid_alpha`): the BM25 index is built on the device
     (`KeywordIndex(build_on_device=True)`); it is the default build's, bit for bit, so the hits are the same (INTEGRATION.md "Building the
-    keyword index on the device")."""
+    keyword index on the device").
+    `document_regex` (False = nothing changes): `where_document` also takes `$regex` / `$not_regex` leaves (`--where-document-regex`),
+    compiled on the host to byte-level DFAs (`regex_dfa.compile_regex`: the dialect and its limits) and scanned on the device
+    (`arx_text_regex`); the bitmap goes where the `$contains` one goes (INTEGRATION.md "Document filters")."""
     from .retrieval import RowFilters, check_hybrid_on_device, check_shared_query, retrieve
     if keyword_build_on_device and hybrid_alpha is None:
         raise ValueError("keyword_build_on_device needs hybrid_alpha: it chooses where the BM25 keyword index is built")
@@ -772,7 +775,7 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
     check_chunk_count(n_rows, chunks, where=where, keep_mask=keep_mask, where_document=where_document, group_by_paper=group_by_paper)
     if where_document is not None:                           # (one dict for the call: a list is refused, as anything else that is no filter)
         from .where_document import compile_where_document
-        compile_where_document(where_document)
+        compile_where_document(where_document, regex=document_regex)
     # int8 pre-filter (same exact answers; +50 % shard memory, one quantisation pass): 1.5-1.7x the queries per second on small batches;
     # a filtered, a grouped and a range search run on the fp16 rows
     masked = (where is not None or keep_mask is not None or where_document is not None or group_by_paper or min_score is not None
@@ -797,7 +800,8 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
                             idx_base=chunk_base, device=dev, **({"build_on_device": True} if keyword_build_on_device else {}))
     # (a count the device would have to be waited for is left unknown for per-query lists: it merely steers the search's path)
     filters = RowFilters([c.get("metadata") or {} for c in chunks] if where is not None else (), dev, 0, n_rows, keep_mask=keep_mask,
-                         texts=lambda: [c["text"] for c in chunks], where_on_device=where_on_device, count_both=False)
+                         texts=lambda: [c["text"] for c in chunks], where_on_device=where_on_device, count_both=False,
+                         document_regex=document_regex)
     hit = retrieve(index, qd, filters, top_k, n_candidates=n_cand, reranked=reranker is not None, where=where, where_document=where_document,
                    min_score=None if min_score is None else float(min_score), grouped=group_by_paper, chunks_per_group=chunks_per_paper, mmr_lambda=mmr_lambda,
                    hybrid_alpha=hybrid_alpha, keyword=keyword_index, query_texts=queries, hybrid_on_device=hybrid_on_device, world=world)
@@ -907,6 +911,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help="Chroma document filter for --queries as JSON, e.g. '{\"$contains\": \"Lipschitz\"}' or "
                         "'{\"$and\": [{\"$contains\": \"graph\"}, {\"$not_contains\": \"lemma\"}]}': only chunks whose text "
                         "satisfies it are searched (case-sensitive substrings, scanned on the GPU; with --hybrid-alpha only next to --hybrid-filters)")
+    p.add_argument("--where-document-regex", action="store_true",
+                   help="Let the --where-document filter use '{\"$regex\": \"...\"}' and '{\"$not_regex\": \"...\"}' as well, e.g. "
+                        "'{\"$regex\": \"(?i)transformer\"}': the pattern is compiled to a DFA and the texts are scanned on the GPU "
+                        "(ASCII \\d \\w \\s, ASCII-only (?i); no backreferences, look-around or \\b; needs --where-document)")
     p.add_argument("--mmr-lambda", type=float, default=None,
                    help="Diversify the --queries results by maximal marginal relevance: weight of the relevance term in [0, 1], the "
                         "penalty on similarity to the rows already picked gets the rest (default: off; not with --rerank-model or "
@@ -1181,6 +1189,8 @@ def check_where_document_args(args) -> Optional[str]:
     (None without --where-document)."""
     args.where_document_filter = None
     if args.where_document is None:
+        if getattr(args, "where_document_regex", False):
+            return "--where-document-regex needs --where-document: the filter still arrives through it"
         return None
     if args.hybrid_alpha is not None and not getattr(args, "hybrid_filters", False):
         return "--where-document cannot be combined with --hybrid-alpha: the BM25 keyword search has no row filter"
@@ -1190,7 +1200,7 @@ def check_where_document_args(args) -> Optional[str]:
         return f"--where-document is not valid JSON: {e}"
     from .where_document import compile_where_document
     try:
-        compile_where_document(parsed)
+        compile_where_document(parsed, regex=getattr(args, "where_document_regex", False))
     except ValueError as e:
         return f"--where-document: {e}"
     args.where_document_filter = parsed
@@ -1304,7 +1314,8 @@ def main(argv: Optional[Sequence[str]] = None, model_factory: Optional[Callable]
                                **({"min_score": args.min_score} if args.min_score is not None else {}),
                                **({"hybrid_filters": True} if args.hybrid_filters else {}),
                                **({"hybrid_on_device": True} if args.hybrid_on_device else {}),
-                               **({"keyword_build_on_device": True} if args.keyword_build_on_device else {}))
+                               **({"keyword_build_on_device": True} if args.keyword_build_on_device else {}),
+                               **({"document_regex": True} if args.where_document_regex else {}))
         store_time = 0.0
         if rank == 0 and not args.skip_chroma:
             try:

@@ -65,11 +65,12 @@ class RowFilters:
     shard's `where_document.DocumentStore` / `where_device.MetadataColumns`, for a front end that keeps its own (one without texts
     raises its refusal there); without them the store is built from `texts()` and the columns from `metadata` when a filter first
     needs them.  `cache`: the dict `where.evaluate` keeps its columns in.  `count_both`: False leaves the count of a per-query bitmap
-    that and-s a `where` with a `where_document` unknown (None) instead of waiting for the device to count it."""
+    that and-s a `where` with a `where_document` unknown (None) instead of waiting for the device to count it.  `document_regex`
+    (False = nothing changes): `where_document` also takes `$regex` / `$not_regex` (`compile_where_document(f, regex=True)`)."""
 
     def __init__(self, metadata: Sequence[Dict], device, lo: int = 0, hi: Optional[int] = None, *, keep_mask=None, keep_words=None,
                  documents: Optional[Callable] = None, texts: Optional[Callable] = None, columns: Optional[Callable] = None,
-                 where_on_device: bool = False, cache: Optional[Dict] = None, count_both: bool = True):
+                 where_on_device: bool = False, cache: Optional[Dict] = None, count_both: bool = True, document_regex: bool = False):
         self.metadata, self.device, self.lo, self.hi = metadata, device, lo, len(metadata) if hi is None else hi
         self.n_rows = self.hi - self.lo
         self.keep_mask = None if keep_mask is None else np.asarray(keep_mask, dtype=bool)
@@ -77,6 +78,7 @@ class RowFilters:
         self._documents, self._texts, self._columns, self.where_on_device = documents, texts, columns, bool(where_on_device)
         self.cache = {} if cache is None else cache
         self.count_both = count_both
+        self.document_regex = bool(document_regex)
 
     def documents(self):
         if self._documents is None:
@@ -141,7 +143,7 @@ class RowFilters:
         from .where import compile_where
         from .where_document import compile_where_document
         tree = compile_where(where) if where is not None else None
-        return self._allow(tree, compile_where_document(where_document) if where_document is not None else None, {})
+        return self._allow(tree, compile_where_document(where_document, regex=self.document_regex) if where_document is not None else None, {})
 
     def per_query(self, nq: int, where, where_document=None):
         """`where` / `where_document` with one entry per query (a list or tuple of `nq` dicts or Nones; a dict or None is repeated) ->
@@ -157,7 +159,7 @@ class RowFilters:
             self.documents()
         trees = []
         for w, d in pairs:                                       # (a pair's where_document first: the same refusal comes first as ever)
-            doc_tree = compile_where_document(d) if d is not None else None
+            doc_tree = compile_where_document(d, regex=self.document_regex) if d is not None else None
             trees.append((compile_where(w) if w is not None else None, doc_tree))
         folds, evaluated = {}, {}
         mine = [j for j, (tree, _) in enumerate(trees) if tree is not None]

@@ -77,7 +77,7 @@ class HipCollection:
                  rank: int = 0, world: int = 1, chunk_rows: int = 1 << 18, keyword: bool = False, tokenizer=None,
                  documents: bool = False, dedup_threshold: Optional[float] = None, group_key: Optional[str] = None,
                  where_on_device: bool = False, hybrid_filters: bool = False, hybrid_on_device: bool = False,
-                 keyword_build_on_device: bool = False):
+                 keyword_build_on_device: bool = False, document_regex: bool = False):
         """`keyword=True`: also build a BM25 `keyword.KeywordIndex` over this shard's `metadata[i]["text"]` (word pieces of `tokenizer`,
         default the encoder's; corpus statistics summed over all ranks when `world > 1`), which `query(hybrid_alpha=...)` needs.
         `documents=True`: also keep this shard's texts as a UTF-8 blob in HBM (`where_document.DocumentStore`), which
@@ -108,7 +108,12 @@ class HipCollection:
         `keyword_build_on_device` (False = nothing changes; needs `keyword=True`): the BM25 index is built on the device
         (`KeywordIndex(build_on_device=True)`: `arx_bm25_build_postings`, `arx_bm25_build_impacts`) from the flat word pieces of
         `tokenizer.full_pieces_flat`.  The index is the default build's, bit for bit, so every query answers the same (INTEGRATION.md
-        "Building the keyword index on the device")."""
+        "Building the keyword index on the device").
+        `document_regex` (False = nothing changes; needs `documents=True`): `query(where_document=...)` also takes `{"$regex": p}` and
+        `{"$not_regex": p}` leaves.  A pattern is compiled on the host to a byte-level DFA (`regex_dfa.compile_regex`: the dialect, its
+        ASCII \\d \\w \\s and ASCII-only `(?i)`, at most 256 states and 8 distinct regexes per filter; a refused pattern is a ValueError
+        before anything is launched) and `arx_text_regex` scans the texts in HBM; the bitmap goes where the `$contains` one goes, so
+        everything that composes with `where_document` composes unchanged (INTEGRATION.md "Document filters")."""
         import torch
         from .index import ShardIndex, shard_bounds
         if hybrid_filters and not keyword:
@@ -117,7 +122,10 @@ class HipCollection:
             raise ValueError("hybrid_on_device=True needs keyword=True: it chooses where the BM25 keyword list and the cosine list are fused")
         if keyword_build_on_device and not keyword:
             raise ValueError("keyword_build_on_device=True needs keyword=True: it chooses where the BM25 keyword index is built")
+        if document_regex and not documents:
+            raise ValueError("document_regex=True needs documents=True: it scans the chunk texts the collection keeps in HBM")
         self.hybrid_filters = bool(hybrid_filters)
+        self.document_regex = bool(document_regex)
         self.hybrid_on_device = bool(hybrid_on_device)
         if dedup_threshold is not None:
             from .dedup import check_threshold
@@ -191,7 +199,7 @@ class HipCollection:
         from .retrieval import RowFilters
         return RowFilters(self.metadata, self.index.corpus.device, self.lo, self.hi, keep_mask=self._keep_mask, keep_words=self._keep,
                           documents=self._documents, columns=self._columns, where_on_device=getattr(self, "where_on_device", False),
-                          cache=self._where_columns)
+                          cache=self._where_columns, document_regex=getattr(self, "document_regex", False))
 
     def query(self, query_embeddings=None, query_texts: Optional[Sequence[str]] = None, n_results: int = 10, reranker=None,
               n_candidates: int = 32, hybrid_alpha: Optional[float] = None, where=None, where_document=None,
@@ -279,7 +287,7 @@ class HipCollection:
         if where_document is not None and not per_query:         # (refused here, before the queries are encoded)
             from .where_document import compile_where_document
             self._documents()
-            compile_where_document(where_document)
+            compile_where_document(where_document, regex=getattr(self, "document_regex", False))
         if hybrid_alpha is not None:
             if not (0.0 <= float(hybrid_alpha) <= 1.0):
                 raise ValueError(f"hybrid_alpha={hybrid_alpha} must be in [0, 1]")

@@ -10,6 +10,12 @@ Operators: `{"$contains": s}` (the text contains `s` as a contiguous substring, 
 sides are UTF-8 bytes (`errors="surrogatepass"`, so a lone surrogate neither raises nor changes the answer); a byte substring of well-formed
 UTF-8 is a code-point substring because UTF-8 is self-synchronising.  Limits (ValueError before anything is launched; there is no host
 path): a pattern of more than 256 bytes once encoded, more than 32 distinct patterns in one filter.
+
+Opt-in (`compile_where_document(f, regex=True)`; without it they stay refused as unknown operators): `{"$regex": p}` (the text contains
+a match of `p`: unanchored, `bool(re.search(...))`) and `{"$not_regex": p}` (its negation).  The dialect, its two deviations from the
+Rust `regex` crate (ASCII \\d \\w \\s, ASCII-only `(?i)`) and its limits are `regex_dfa.compile_regex`'s; a pattern it refuses is a
+ValueError here, before anything is launched.  At most 8 distinct regexes in one filter, counted apart from the 32 substrings; one
+`arx_text_regex` launch scans them all.
 """
 from __future__ import annotations
 
@@ -19,7 +25,11 @@ import numpy as np
 
 MAX_PATTERN_BYTES = 256
 MAX_PATTERNS = 32
+MAX_REGEXES = 8
 _LEAF = ("$contains", "$not_contains")
+_REGEX_LEAF = ("$regex", "$not_regex")
+_DFA_CACHE_SIZE = 256
+_dfa_cache: Dict[str, object] = {}
 _NODE = ("$and", "$or")
 
 
@@ -27,7 +37,19 @@ def encode_text(s: str) -> bytes:
     return s.encode("utf-8", "surrogatepass")
 
 
-def _compile(f) -> Tuple:
+def compiled_regex(pattern: str):
+    """`regex_dfa.compile_regex(pattern)`, kept per pattern string in a bounded dict (the oldest entry leaves first)."""
+    dfa = _dfa_cache.get(pattern)
+    if dfa is None:
+        from .regex_dfa import compile_regex
+        dfa = compile_regex(pattern)
+        if len(_dfa_cache) >= _DFA_CACHE_SIZE:
+            del _dfa_cache[next(iter(_dfa_cache))]
+        _dfa_cache[pattern] = dfa
+    return dfa
+
+
+def _compile(f, regex: bool = False) -> Tuple:
     if not isinstance(f, dict) or not f:
         raise ValueError(f"where_document: expected a non-empty dict, got {f!r}")
     if len(f) != 1:
@@ -42,39 +64,62 @@ def _compile(f) -> Tuple:
         if nbytes > MAX_PATTERN_BYTES:
             raise ValueError(f"where_document: operand of {op} is {nbytes} bytes as UTF-8, at most {MAX_PATTERN_BYTES} are scanned: {val[:24]!r}...")
         return (op[1:], val)
+    if regex and op in _REGEX_LEAF:
+        if not isinstance(val, str):
+            raise ValueError(f"where_document: operand of {op} must be a string, got {val!r}")
+        try:
+            compiled_regex(val)                              # compiled at once: a bad pattern fails before any GPU work
+        except ValueError as e:
+            raise ValueError(f"where_document: operand of {op}: {e}") from None
+        return (op[1:], val)
     if op in _NODE:
         if not isinstance(val, (list, tuple)) or not val:
             raise ValueError(f"where_document: {op} needs a non-empty list of filters, got {val!r}")
-        return (op[1:], tuple(_compile(v) for v in val))
+        return (op[1:], tuple(_compile(v, regex) for v in val))
     raise ValueError(f"where_document: unknown operator {op!r}")
 
 
-def patterns_of(tree: Tuple) -> List[str]:
-    """The distinct strings of the tree's leaves, in first-seen order."""
+def _leaves_of(tree: Tuple, kinds: Tuple[str, str]) -> List[str]:
     out: Dict[str, None] = {}
 
     def walk(node):
         if node[0] in ("and", "or"):
             for c in node[1]:
                 walk(c)
-        else:
+        elif node[0] in kinds:
             out.setdefault(node[1])
     walk(tree)
     return list(out)
 
 
-def compile_where_document(f: Dict) -> Tuple:
+def patterns_of(tree: Tuple) -> List[str]:
+    """The distinct strings of the tree's `contains` / `not_contains` leaves, in first-seen order."""
+    return _leaves_of(tree, ("contains", "not_contains"))
+
+
+def regexes_of(tree: Tuple) -> List[str]:
+    """The distinct patterns of the tree's `regex` / `not_regex` leaves, in first-seen order."""
+    return _leaves_of(tree, ("regex", "not_regex"))
+
+
+def compile_where_document(f: Dict, regex: bool = False) -> Tuple:
     """Validate a Chroma `where_document` filter and return its tree: ("and" | "or", children), ("contains" | "not_contains", str).
-    ValueError names the offending part."""
-    tree = _compile(f)
+    ValueError names the offending part.
+    `regex=True` also accepts `$regex` / `$not_regex` leaves, as ("regex" | "not_regex", pattern), each pattern compiled here
+    (`regex_dfa.compile_regex`: its dialect, deviations and limits); without it they are unknown operators, as ever."""
+    tree = _compile(f, regex)
     n = len(patterns_of(tree))
     if n > MAX_PATTERNS:
         raise ValueError(f"where_document: {n} distinct patterns in one filter, at most {MAX_PATTERNS} are scanned per call")
+    n = len(regexes_of(tree))
+    if n > MAX_REGEXES:
+        raise ValueError(f"where_document: {n} distinct regexes in one filter, at most {MAX_REGEXES} are scanned per call")
     return tree
 
 
 def evaluate_host(tree: Tuple, texts: Sequence[str]) -> np.ndarray:
-    """bool [n]: the pure-Python definition (`s in text` on the strs).  For tests and documentation; the product path never calls it."""
+    """bool [n]: the pure-Python definition (`s in text` on the strs; `regex_dfa.match_host` on the text's bytes for a regex leaf).  For
+    tests and documentation; the product path never calls it."""
     kind = tree[0]
     if kind in ("and", "or"):
         out = evaluate_host(tree[1][0], texts)
@@ -83,6 +128,11 @@ def evaluate_host(tree: Tuple, texts: Sequence[str]) -> np.ndarray:
             out = (out & m) if kind == "and" else (out | m)
         return out
     s = tree[1]
+    if kind in ("regex", "not_regex"):
+        from .regex_dfa import match_host
+        dfa = compiled_regex(s)
+        hit = np.fromiter((match_host(dfa, encode_text(t)) for t in texts), dtype=bool, count=len(texts))
+        return hit if kind == "regex" else ~hit
     hit = np.fromiter((s in t for t in texts), dtype=bool, count=len(texts))
     return hit if kind == "contains" else ~hit
 
@@ -163,6 +213,26 @@ class DocumentStore:
         _lib.check(rc, "arx_text_contains")
         return out
 
+    def regex(self, patterns: Sequence[str], out=None, waves_per_block: int = 0):
+        """int64 [P, ceil(n / 64)] on the device: bit r & 63 of word [p, r >> 6] = `texts[r]` contains a match of the regular expression
+        `patterns[p]` (`regex_dfa.compile_regex`; 1..8 of them); bits at or beyond n are 0.  One `arx_text_regex` launch for all of
+        them, on the current stream, no synchronisation.  `waves_per_block`: the launch shape (`arx_text_regex_tuned`), same bits."""
+        import torch
+        from . import _lib
+        from .regex_dfa import pack_tables
+        tb, to = pack_tables([compiled_regex(p) for p in patterns])
+        if out is None:
+            out = torch.empty((len(patterns), self.n_words), dtype=torch.int64, device=self.device)
+        assert out.shape == (len(patterns), self.n_words) and out.dtype == torch.int64 and out.is_contiguous() and out.device == self.blob.device
+        if self.n_rows == 0:
+            return out
+        with torch.cuda.device(self.device):
+            tbd, tod = torch.from_numpy(tb).to(self.device), torch.from_numpy(to).to(self.device)
+            rc = self.lib.arx_text_regex_tuned(self.blob.data_ptr(), self.row_off.data_ptr(), self.n_rows, tbd.data_ptr(), tod.data_ptr(),
+                                               len(patterns), out.data_ptr(), waves_per_block, self._stream())
+        _lib.check(rc, "arx_text_regex")
+        return out
+
     def count(self, words) -> int:
         """Set bits of `words` (int64 [ceil(n / 64)], device) that name rows below n (`arx_bitmap_count`).  Waits for the result."""
         import torch
@@ -176,10 +246,16 @@ class DocumentStore:
 
     def fold(self, tree: Tuple):
         """int64 [ceil(n / 64)] on the device: the tree folded over the pattern bitmaps with bitwise ops.  `$not_contains` is `~`, which also
-        sets the last word's bits beyond n: the search ignores them and `count` does not count them."""
-        pats = patterns_of(tree)
-        bits = self.contains(pats)
-        row = {s: bits[i] for i, s in enumerate(pats)}
+        sets the last word's bits beyond n: the search ignores them and `count` does not count them.  One `arx_text_contains` launch for
+        the tree's substrings and one `arx_text_regex` launch for its regexes (`$not_regex` is `~` likewise)."""
+        pats, regs = patterns_of(tree), regexes_of(tree)
+        row = {}
+        if pats:
+            bits = self.contains(pats)
+            row.update((("contains", s), bits[i]) for i, s in enumerate(pats))
+        if regs:
+            bits = self.regex(regs)
+            row.update((("regex", s), bits[i]) for i, s in enumerate(regs))
 
         def go(node):
             if node[0] in ("and", "or"):
@@ -187,7 +263,9 @@ class DocumentStore:
                 for c in node[1][1:]:
                     acc = (acc & go(c)) if node[0] == "and" else (acc | go(c))
                 return acc
-            return row[node[1]] if node[0] == "contains" else ~row[node[1]]
+            if node[0] in ("contains", "regex"):
+                return row[node]
+            return ~row[(node[0][4:], node[1])]
         return go(tree).contiguous()
 
     def allow(self, tree: Tuple):

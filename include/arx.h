@@ -464,6 +464,28 @@ int32_t arx_range_stats(const void* ws, int64_t* overflowed_queries, int64_t* ca
 int32_t arx_text_contains(const uint8_t* blob, const int64_t* row_off, int64_t n_rows,
                           const uint8_t* pat_blob, const int32_t* pat_off, int32_t n_pat,
                           uint64_t* out_bits, void* stream);
+/* Regular-expression scan over the same texts (`$regex` / `$not_regex`; csrc/textscan.hip).  The output contract is that of
+ * arx_text_contains: out_bits[p][w] bit (r & 63) of word w = r >> 6  <=>  regex p matches somewhere inside [row_off[r], row_off[r+1])
+ * (`^` / `$` are that row's start and end); bits at or beyond n_rows are 0; every word is written with a plain store.
+ * The host compiles each regex to a byte-level DFA (arxiv_rag_amd/regex_dfa.py: compile_regex, pack_tables); the kernel walks tables.
+ *   tables    device uint8, table_off device int32 [n_re + 1]; 1 <= n_re <= 8.  Table p = tables[table_off[p], table_off[p+1]):
+ *             uint16 n_states, uint16 n_classes (little-endian, each 1..256), class_of[256], flags[n_states],
+ *             trans[n_states][n_classes].  The start state is 0; after byte b in state s the state is trans[s][class_of[b]].
+ *             flags: 1 = matched (absorbing: the row matches whatever follows), 2 = the row matches if it ends in this state,
+ *             4 = dead (absorbing, no accepting state reachable).  A row matches when the state at its end has flag 1 or 2.
+ *   out_bits  device uint64 [n_re, ceil(n_rows / 64)]
+ * The tables are device data and the caller's contract.  A header outside 1..256, or a table shorter than its header says, makes that
+ * regex match no row; a class or transition outside its range is read as 0: a malformed table gives wrong bits, never an access
+ * outside the kernel's LDS copy of it.  One launch on `stream` (a block holds one regex's table in LDS; the regex is the grid's y),
+ * no atomics, no workspace. */
+int32_t arx_text_regex(const uint8_t* blob, const int64_t* row_off, int64_t n_rows,
+                       const uint8_t* tables, const int32_t* table_off, int32_t n_re,
+                       uint64_t* out_bits, void* stream);
+/* The same with the launch shape chosen: waves_per_block = 64-row groups (output words) a block of that many waves covers with one
+ * staged table; 0 = default (8), else 1, 2, 4, 8 or 16.  Same bits for every choice. */
+int32_t arx_text_regex_tuned(const uint8_t* blob, const int64_t* row_off, int64_t n_rows,
+                             const uint8_t* tables, const int32_t* table_off, int32_t n_re,
+                             uint64_t* out_bits, int32_t waves_per_block, void* stream);
 /* *out_count (ONE device int64) = set bits of bits[0 .. ceil(n_rows/64)) that name rows below n_rows. */
 int32_t arx_bitmap_count(const uint64_t* bits, int64_t n_rows, int64_t* out_count, void* stream);
 

@@ -8,7 +8,7 @@
 //
 // A wave streams its row in tiles of 1024 bytes, 16 B per lane, coalesced and 16-B aligned on the ADDRESS (the tile grid is laid over
 // the blob's address, not over the row, so every full chunk is one global_load_dwordx4; the chunks that hang over either end of the
-// blob are assembled from guarded byte loads).  The tile goes to LDS with a halo of max_len - 1 (+3) bytes behind it, so a lane can
+// blob are assembled from guarded byte loads).  The tile goes to LDS with a halo of max(max_len - 1, 3) bytes behind it, so a lane can
 // finish a comparison that runs into its neighbours' bytes.  Each lane tests the 16 start positions of its own chunk: the 4-byte
 // window at every position is built once per tile from five registers and compared with the pattern's first min(len, 4) bytes under
 // a mask; for len <= 4 that is the whole answer, longer patterns compare the rest out of LDS at the (rare) surviving positions.
@@ -32,7 +32,7 @@ namespace {
 constexpr int TS_NT = 256, TS_WAVES = TS_NT / 64;
 constexpr int TS_TILE = 1024;                                 // bytes of start positions per wave step: 64 lanes x 16 B
 constexpr int TS_MAXP = 32, TS_MAXLEN = 256;
-constexpr int TS_HALO = 272;                                  // 255 bytes of a match starting at the tile's last byte + 3 of its window, in 16-B chunks
+constexpr int TS_HALO = 256;                                  // the 255 bytes a match starting at the tile's last byte runs on (its window's 3 are the first of them), in 16-B chunks
 constexpr int TS_BUF = TS_TILE + TS_HALO;
 
 // 16 bytes at blob[pos, pos + 16) (the address is 16-B aligned by construction); bytes outside [0, total) read as 0 and are never part of a match
@@ -98,7 +98,8 @@ __global__ __launch_bounds__(TS_NT) void text_contains_kernel(const uint8_t* __r
     uint32_t live = 0;                                        // patterns that can match at all
     for (int p = 0; p < n_pat; ++p) live |= (s_len[p] > 0 ? 1u : 0u) << p;
     live = __builtin_amdgcn_readfirstlane(live);              // a scalar: the loops below that depend on it branch uniformly
-    const int halo_chunks = (s_maxlen + 2 + 15) >> 4;         // max_len - 1 bytes of a match + 3 of the last lane's window; 1..17
+    // the max_len - 1 bytes that a match starting at the tile's last byte runs on, and at least the 3 of the last lane's window; 1..16
+    const int halo_chunks = ((s_maxlen > 4 ? s_maxlen - 1 : 3) + 15) >> 4;
     const int64_t total = row_off[n_rows];
     const int64_t shift = (int64_t)((uintptr_t)blob & 15);    // tile grid in v = pos + shift: v % 16 == 0 <=> the address is 16-B aligned
     const int64_t rows_left = n_rows - g * 64;

@@ -32,6 +32,32 @@ def runs_from_keys(keys: Sequence, base: int = 0) -> Tuple[np.ndarray, List]:
     return group_of, run_keys
 
 
+def continue_runs(group_of: np.ndarray, run_keys: Sequence, keys: Sequence, base: int = 0) -> Tuple[np.ndarray, List]:
+    """`runs_from_keys` continued over rows appended to a shard (`HipCollection.add`): `group_of` int32 [n] and `run_keys` (the key of
+    every `group_of` value; values need not be dense, a value no row holds any more is a run that was deleted) describe the rows there
+    are, `keys` are the new rows' -> (`group_of` of the new rows, the extended `run_keys`; the arguments are not changed).  A first new
+    row with the key of the last row continues that run; a key whose run already ended is `runs_from_keys`' ValueError, naming the
+    key, the run's last row and the new row (`base` + position among all rows); a new run takes the next unused value."""
+    group_of = np.asarray(group_of, dtype=np.int32)
+    n = len(group_of)
+    out = np.empty(len(keys), dtype=np.int32)
+    run_keys = list(run_keys)
+    live = np.unique(group_of)
+    last_row: Dict = {run_keys[int(g)]: int(np.searchsorted(group_of, g, side="right")) - 1 for g in live}
+    cur = int(group_of[-1]) if n else -1
+    prev = run_keys[cur] if n else object()
+    for j, key in enumerate(keys):
+        if cur < 0 or key != prev:
+            if key in last_row:
+                raise ValueError(f"group key {key!r} appears at row {base + last_row[key]} and again at row {base + n + j} after its run "
+                                 f"ended: a group must be consecutive rows")
+            run_keys.append(key)
+            cur, prev = len(run_keys) - 1, key
+        last_row[key] = n + j
+        out[j] = cur
+    return out, run_keys
+
+
 def groups_touched(max_run_rows: int) -> int:
     """S: the 64-row groups a run of at most `max_run_rows` rows can touch, whatever its offset."""
     return (int(max_run_rows) + 62) // 64 + 1

@@ -77,7 +77,7 @@ class HipCollection:
                  rank: int = 0, world: int = 1, chunk_rows: int = 1 << 18, keyword: bool = False, tokenizer=None,
                  documents: bool = False, dedup_threshold: Optional[float] = None, group_key: Optional[str] = None,
                  where_on_device: bool = False, hybrid_filters: bool = False, hybrid_on_device: bool = False,
-                 keyword_build_on_device: bool = False, document_regex: bool = False):
+                 keyword_build_on_device: bool = False, document_regex: bool = False, capacity: Optional[int] = None):
         """`keyword=True`: also build a BM25 `keyword.KeywordIndex` over this shard's `metadata[i]["text"]` (word pieces of `tokenizer`,
         default the encoder's; corpus statistics summed over all ranks when `world > 1`), which `query(hybrid_alpha=...)` needs.
         `documents=True`: also keep this shard's texts as a UTF-8 blob in HBM (`where_document.DocumentStore`), which
@@ -113,9 +113,25 @@ class HipCollection:
         `{"$not_regex": p}` leaves.  A pattern is compiled on the host to a byte-level DFA (`regex_dfa.compile_regex`: the dialect, its
         ASCII \\d \\w \\s and ASCII-only `(?i)`, at most 256 states and 8 distinct regexes per filter; a refused pattern is a ValueError
         before anything is launched) and `arx_text_regex` scans the texts in HBM; the bitmap goes where the `$contains` one goes, so
-        everything that composes with `where_document` composes unchanged (INTEGRATION.md "Document filters")."""
+        everything that composes with `where_document` composes unchanged (INTEGRATION.md "Document filters").
+        `capacity` (None = nothing changes: the collection is immutable and `add`, `delete`, `compact` raise ValueError): the shard is
+        allocated with room for that many rows (>= len(embeddings); `world` must be 1) and the collection can grow and shrink
+        (INTEGRATION.md "Adding and deleting rows"): `add` appends rows, `delete` tombstones rows in the keep-bitmap every query and-s
+        in, `compact` removes the tombstoned rows from HBM on the device (`arx_compact_plan`, `arx_compact_rows`, `arx_compact_text`),
+        `get` reads rows by id.  `metadata` is then copied into a list the collection owns, and the ids
+        (`metadata[i].get("chunk_id", f"chunk_{i}")`) must be distinct: a duplicate is a ValueError naming it."""
         import torch
-        from .index import ShardIndex, shard_bounds
+        from .index import shard_bounds
+        if capacity is not None:
+            capacity = int(capacity)
+            if world > 1:
+                raise ValueError("capacity needs world == 1: the shard bounds of a multi-rank collection are static")
+            if capacity < len(embeddings):
+                raise ValueError(f"capacity={capacity} is below the {len(embeddings)} rows given")
+            from .mutation import build_id_map
+            metadata = list(metadata)
+            self._ids = build_id_map(metadata)
+        self.capacity, self._deleted, self._n_deleted = capacity, None, 0
         if hybrid_filters and not keyword:
             raise ValueError("hybrid_filters=True needs keyword=True: it passes the row filters to the BM25 keyword search")
         if hybrid_on_device and not keyword:
@@ -144,24 +160,35 @@ class HipCollection:
         self._where_columns: Dict = {}                          # `query(where=...)`: one numpy column per referenced metadata key
         self.where_on_device, self._device_columns = bool(where_on_device), None
         self.encoder = encoder
-        shard = torch.empty((hi - lo, d), dtype=torch.float16, device=device)
+        self._buf = torch.empty((hi - lo if capacity is None else capacity, d), dtype=torch.float16, device=device)
+        self._buf_spare = self._group_buf = None                # (mutable collections: `compact`'s second buffer, `group_of` at capacity)
+        shard = self._buf[:hi - lo]
         for s0 in range(lo, hi, chunk_rows):                   # stream: never a second full copy in host RAM
             s1 = min(hi, s0 + chunk_rows)
             shard[s0 - lo:s1 - lo] = torch.from_numpy(np.ascontiguousarray(embeddings[s0:s1], dtype=np.float16)).to(device)
-        dim = int(shard.shape[1]) if shard.dim() == 2 else 0
-        self.index = ShardIndex(shard, idx_base=lo, prefilter="int8" if (dim % 128 == 0 and 0 < dim <= 1024 and shard.shape[0] > 0) else None,
-                                adaptive=True)
-        if group_key is not None and hi > lo:
+        self._group_host = None
+        if group_key is not None and capacity is not None:
+            self._group_host = group_of
+            self._group_buf = torch.zeros(capacity, dtype=torch.int32, device=device)
+            self._group_buf[:hi - lo] = torch.from_numpy(group_of).to(device)
+        self._make_index()
+        if group_key is not None and hi > lo and capacity is None:
             self.index.set_groups(group_of)
         self.keyword = None
+        self._kw_stale, self._kw_pieces, self._kw_on_device = False, None, bool(keyword_build_on_device)
         if keyword:
             from .keyword import KeywordIndex
             tokenizer = tokenizer if tokenizer is not None else getattr(encoder, "tokenizer", None)
             if tokenizer is None:
                 raise ValueError("keyword=True needs a tokenizer (or an encoder that has one)")
-            self.keyword = KeywordIndex(texts=[metadata[r].get("text") or "" for r in range(lo, hi)], tokenizer=tokenizer,
-                                        stats="global" if world > 1 else None, idx_base=lo, device=device,
-                                        **({"build_on_device": True} if keyword_build_on_device else {}))
+            if capacity is None:
+                self.keyword = KeywordIndex(texts=[metadata[r].get("text") or "" for r in range(lo, hi)], tokenizer=tokenizer,
+                                            stats="global" if world > 1 else None, idx_base=lo, device=device,
+                                            **({"build_on_device": True} if keyword_build_on_device else {}))
+            else:                                               # the collection keeps its rows' flat word pieces: the index is rebuilt from them
+                self._kw_tokenizer = tokenizer
+                self._kw_pieces = self._pieces_of([m.get("text") or "" for m in metadata])
+                self._rebuild_keyword()
         self.documents = None
         if documents:
             from .where_document import DocumentStore
@@ -181,7 +208,193 @@ class HipCollection:
         return cls(emb, meta, **kw)
 
     def count(self) -> int:
-        return self.n_total
+        return self.n_total - getattr(self, "_n_deleted", 0)
+
+    # ---- adding and deleting rows (`capacity=...`; INTEGRATION.md "Adding and deleting rows") -----------------------------------
+    def _make_index(self):
+        """The `ShardIndex` over the rows there are now: the prefix [0, hi - lo) of the capacity buffer.  A new index, so the int8
+        copy, the norm bound, the cached workspaces and the groups all describe these rows and no others."""
+        from .index import ShardIndex
+        shard = self._buf[:self.hi - self.lo]
+        dim = int(shard.shape[1])
+        self.index = ShardIndex(shard, idx_base=self.lo, prefilter="int8" if (dim % 128 == 0 and 0 < dim <= 1024 and shard.shape[0] > 0) else None,
+                                adaptive=True)
+        if self._group_buf is not None and self.hi > self.lo:
+            self.index.set_groups(self._group_buf[:self.hi - self.lo])
+
+    def _pieces_of(self, texts):
+        """(pieces int32 [T], doc_ptr int64 [n + 1]) of `texts`, through the tokenizer call the collection's build path uses."""
+        from .keyword import flatten_pieces
+        if self._kw_on_device:
+            return self._kw_tokenizer.full_pieces_flat(list(texts))
+        return flatten_pieces(self._kw_tokenizer._full_pieces(list(texts)))
+
+    def _rebuild_keyword(self):
+        """The keyword index of the rows there are now, by the build path the collection was created with: the one a fresh collection
+        over these rows builds."""
+        from .keyword import KeywordIndex
+        from .mutation import piece_lists
+        flat, doc_ptr = self._kw_pieces
+        dev = self._buf.device
+        if self._kw_on_device:
+            self.keyword = KeywordIndex(pieces=(flat, doc_ptr), tokenizer=self._kw_tokenizer, idx_base=0, device=dev, build_on_device=True)
+        else:
+            self.keyword = KeywordIndex(pieces=piece_lists(flat, doc_ptr), tokenizer=self._kw_tokenizer, idx_base=0, device=dev)
+        self._kw_stale = False
+
+    def _require_mutable(self, what: str):
+        if getattr(self, "capacity", None) is None:
+            raise ValueError(f"{what} needs a collection built with capacity=...: without it the collection is immutable")
+
+    def _drop_columns(self):
+        """The metadata columns (`where`'s host cache and the device columns) are dropped whenever the rows change, and rebuilt on
+        first use."""
+        self._where_columns, self._device_columns = {}, None
+
+    def _set_keep(self, mask):
+        import torch
+        from .where import pack_bitmap
+        self._keep_mask = mask
+        self._keep = None if mask is None else torch.from_numpy(pack_bitmap(mask).view(np.int64)).to(self._buf.device)
+
+    def add(self, embeddings, metadatas: Sequence[Dict]) -> None:
+        """Append rows (`embeddings` [m, dim], converted to fp16 as the constructor converts them; one metadata dict each).  Everything
+        derived is extended: texts, word pieces (the keyword index is rebuilt on its next use), the runs of `group_key`
+        (`grouping.continue_runs`: the first new row may continue the last run; a key whose run ended is a ValueError) and, with
+        `dedup_threshold`, `duplicates` and the keep-bitmap, from a self-join over the new rows only
+        (`ShardIndex.nearest_earlier(row_lo=old_n)`).  ValueError, with nothing added: more rows than `capacity` has room for, a
+        duplicate id, another dim, a different number of dicts."""
+        import torch
+        from .mutation import append_pieces, build_id_map, chunk_id_of
+        self._require_mutable("add")
+        emb = np.asarray(embeddings) if not isinstance(embeddings, np.ndarray) else embeddings
+        metadatas = list(metadatas)
+        if emb.ndim != 2 or emb.shape[1] != self.dim or emb.shape[0] != len(metadatas):
+            raise ValueError(f"add: embeddings of shape {tuple(emb.shape)} and {len(metadatas)} metadata dicts; rows of dim {self.dim} and "
+                             f"one dict each are needed")
+        n, m = self.n_total, len(metadatas)
+        if n + m > self.capacity:
+            raise ValueError(f"add: {n} rows + {m} new rows exceed capacity={self.capacity}")
+        if m == 0:
+            return
+        ids = build_id_map(metadatas, base=n, into=self._ids)
+        if self.group_key is not None:
+            from .grouping import continue_runs
+            group_new, group_keys = continue_runs(self._group_host, self.group_keys, [md.get(self.group_key) for md in metadatas])
+        texts = [md.get("text") or "" for md in metadatas]
+        pieces = self._pieces_of(texts) if self._kw_pieces is not None else None
+        # nothing above changed the collection; from here on nothing can be refused
+        dev = self._buf.device
+        self._buf[n:n + m] = torch.from_numpy(np.ascontiguousarray(emb, dtype=np.float16)).to(dev)
+        self.metadata.extend(metadatas)
+        self._ids = ids
+        self.n_total = self.hi = n + m
+        if self.group_key is not None:
+            self._group_host, self.group_keys = np.concatenate([self._group_host, group_new]), group_keys
+            self._group_buf[n:n + m] = torch.from_numpy(group_new).to(dev)
+        if pieces is not None:
+            self._kw_pieces, self._kw_stale = append_pieces(*self._kw_pieces, *pieces), True
+        if self.documents is not None:
+            self.documents.append(texts)
+        self._drop_columns()
+        self._make_index()
+        if self._deleted is not None:
+            self._deleted = np.concatenate([self._deleted, np.zeros(m, bool)])
+        if self.dedup_threshold is not None:
+            from .dedup import duplicate_entries, duplicates_from_nearest
+            s, i = self.index.nearest_earlier(n, n + m, 1)
+            s, i = s.cpu().numpy()[:, 0], i.cpu().numpy()[:, 0]
+            dup_new = duplicates_from_nearest(s, i, self.dedup_threshold)
+            dup_of = np.concatenate([np.full(n, -1, np.int64), dup_new])
+            scores = np.concatenate([np.zeros(n, s.dtype), s])
+            self.duplicates = self.duplicates + [e for e in duplicate_entries(dup_of, scores, [chunk_id_of(md, r) for r, md in enumerate(self.metadata)])]
+            old = self._keep_mask if self._keep_mask is not None else np.ones(n, bool)
+            self._set_keep(np.concatenate([old, dup_new < 0]))
+        elif self._keep_mask is not None:
+            self._set_keep(np.concatenate([self._keep_mask, np.ones(m, bool)]))
+
+    def delete(self, ids: Optional[Sequence] = None, where=None, where_document=None) -> int:
+        """Tombstone rows: those of the `chunk_id`s in `ids` (an unknown one is a ValueError naming it) and / or those a `where` /
+        `where_document` filter selects, evaluated by the path a query's filters take; with several arguments a row must satisfy all of
+        them, as in Chroma.  At least one is needed.  The rows' bits are cleared in the keep-bitmap every query and-s in, so no query
+        returns them from this moment (with `hybrid_alpha` that needs `hybrid_filters=True`, as for every keep-bitmap); they stay in HBM,
+        and in the BM25 statistics, until `compact()`.  Their ids are forgotten at once.  -> the number of rows deleted.  With
+        `dedup_threshold` it raises ValueError: a deleted original may un-hide its duplicates, and re-joining them is out of scope."""
+        from .mutation import chunk_id_of, rows_of_ids, unpack_rows
+        self._require_mutable("delete")
+        if self.dedup_threshold is not None:
+            raise ValueError("delete cannot be used on a collection built with dedup_threshold: a deleted original may un-hide its duplicates")
+        if ids is None and where is None and where_document is None:
+            raise ValueError("delete needs ids, where or where_document")
+        n = self.n_total
+        hit = np.ones(n, bool)
+        if ids is not None:
+            by_id = np.zeros(n, bool)
+            by_id[rows_of_ids(self._ids, list(ids))] = True
+            hit &= by_id
+        if where is not None or where_document is not None:
+            words, _ = self._row_filters().allow_of(where, where_document)
+            hit &= unpack_rows(words.cpu().numpy(), n)
+        if self._deleted is not None:
+            hit &= ~self._deleted
+        rows = np.nonzero(hit)[0].tolist()
+        if not rows:
+            return 0
+        for r in rows:
+            del self._ids[chunk_id_of(self.metadata[r], r)]
+        self._deleted = hit if self._deleted is None else (self._deleted | hit)
+        self._n_deleted = int(self._deleted.sum())
+        self._set_keep(~self._deleted)
+        return len(rows)
+
+    def compact(self) -> np.ndarray:
+        """Remove the tombstoned rows for good, on the device: one `arx_compact_plan`, `arx_compact_rows` for the shard (into a second
+        capacity-sized buffer the collection keeps from then on; the two swap) and for `group_of`, `arx_compact_text` for the texts.
+        The host lists are compacted, the id map is rebuilt (a row without a `chunk_id` is `chunk_<its new row>`), the keyword index is
+        rebuilt on its next use, so its statistics become the survivors', and the tombstones are cleared.  -> int64 [rows before]: every
+        old row's new row, -1 for a removed one.  Afterwards the collection answers as one built from the survivors in order."""
+        import torch
+        from . import _lib
+        from .mutation import build_id_map, compact_pieces, compact_rows_device, old_to_new, plan_device
+        self._require_mutable("compact")
+        n = self.n_total
+        if self._deleted is None or not self._deleted.any():
+            return np.arange(n, dtype=np.int64)
+        keep = ~self._deleted
+        word_rank, count = plan_device(self._keep, n)
+        if count != int(keep.sum()):
+            raise _lib.ArxError(f"arx_compact_plan counted {count} rows, the host's tombstones leave {int(keep.sum())}")
+        if self._buf_spare is None:
+            self._buf_spare = torch.empty_like(self._buf)
+        compact_rows_device(self._buf, self._buf_spare, n, self._keep, word_rank)
+        self._buf, self._buf_spare = self._buf_spare, self._buf
+        if self._group_buf is not None:
+            moved = torch.zeros_like(self._group_buf)
+            compact_rows_device(self._group_buf, moved, n, self._keep, word_rank)
+            self._group_buf, self._group_host = moved, self._group_host[keep]
+        if self.documents is not None:
+            self.documents.compact(self._keep, word_rank, count)
+        self.metadata = [md for md, k in zip(self.metadata, keep.tolist()) if k]
+        self._ids = build_id_map(self.metadata)
+        if self._kw_pieces is not None:
+            self._kw_pieces, self._kw_stale = compact_pieces(*self._kw_pieces, keep), True
+        self.n_total = self.hi = count
+        self._deleted, self._n_deleted = None, 0
+        self._set_keep(None)
+        self._drop_columns()
+        self._make_index()
+        return old_to_new(keep)
+
+    def get(self, ids: Sequence) -> Dict:
+        """-> {ids, metadatas, documents} of the rows with these `chunk_id`s, in the order asked, from the host lists (the shape of one
+        query's lists in `query`'s result).  An unknown or deleted id is a ValueError naming it."""
+        from .mutation import build_id_map, rows_of_ids
+        id_map = getattr(self, "_ids", None)
+        if id_map is None:                                       # (an immutable collection: the map is built when first asked for)
+            id_map = self._ids = build_id_map([self.metadata[r] for r in range(self.lo, self.hi)], base=self.lo)
+        ms = [self.metadata[r] for r in rows_of_ids(id_map, list(ids))]
+        return {"ids": list(ids), "documents": [m.get("text") for m in ms],
+                "metadatas": [{k: m.get(k) for k in ("paper_id", "section", "quality_score")} for m in ms]}
 
     def _columns(self):
         if self._device_columns is None:
@@ -281,7 +494,8 @@ class HipCollection:
             mmr_lambda=mmr_lambda, n_fetch=n_candidates,
             fetch_refusal=f"n_candidates={n_candidates} must be in [n_results, 32] (the search's k limit) and n_results at least 1",
             filters_first=(("where cannot be combined", per_query),           # (a per-query list of either argument is refused as `where`)
-                           ("a collection built with dedup_threshold cannot be queried", self._keep is not None)),
+                           ("a collection built with dedup_threshold cannot be queried" if getattr(self, "_deleted", None) is None
+                            else "a collection with deleted rows cannot be queried", self._keep is not None)),
             filters=(("where_document cannot be combined", where_document is not None and not per_query),
                      ("where cannot be combined", where is not None and not per_query)))
         if where_document is not None and not per_query:         # (refused here, before the queries are encoded)
@@ -293,6 +507,8 @@ class HipCollection:
                 raise ValueError(f"hybrid_alpha={hybrid_alpha} must be in [0, 1]")
             if query_texts is None or self.keyword is None:
                 raise ValueError("hybrid search needs query_texts and a collection built with keyword=True")
+            if getattr(self, "_kw_stale", False):                # rows were added or compacted away since the index was built
+                self._rebuild_keyword()
             if on_device:
                 check_hybrid_on_device(n_candidates, per_query_filters=per_query, world=getattr(self, "world", 1))
             if not (n_results <= n_candidates <= (1024 if on_device else 32)):

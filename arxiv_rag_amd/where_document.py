@@ -167,7 +167,9 @@ def pack_patterns(patterns: Sequence[str]) -> Tuple[np.ndarray, np.ndarray]:
 class DocumentStore:
     """The texts of one shard as a UTF-8 blob in HBM, with the substring scan over it."""
 
-    def __init__(self, texts: Sequence[str], device="cuda:0", slab_rows: int = 1 << 16):
+    def __init__(self, texts: Sequence[str], device="cuda:0", slab_rows: int = 1 << 16, capacity_bytes: int = 0):
+        """`capacity_bytes` (0 = nothing changes): the blob is allocated with room for that many bytes, so that `append` need not
+        reallocate it until they are used up."""
         import torch
         from . import _lib
         self.lib = _lib.load()
@@ -182,7 +184,7 @@ class DocumentStore:
             off[s0 + 1:s1 + 1] = off[s0] + o[1:]
             pieces.append(torch.from_numpy(blob.copy()).to(self.device))
         self.n_bytes = int(off[n])
-        self.blob = torch.zeros(max(16, self.n_bytes), dtype=torch.uint8, device=self.device)    # (a valid pointer for an all-empty shard too)
+        self.blob = torch.zeros(max(16, self.n_bytes, int(capacity_bytes)), dtype=torch.uint8, device=self.device)    # (a valid pointer for an all-empty shard too)
         at = 0
         for i in range(len(pieces)):
             p, pieces[i] = pieces[i], None
@@ -194,6 +196,41 @@ class DocumentStore:
     def _stream(self) -> int:
         import torch
         return torch.cuda.current_stream(self.device).cuda_stream
+
+    def append(self, texts: Sequence[str]) -> None:
+        """More rows at the end.  The blob grows by reallocation (to at least twice its size) once its capacity is used up: nothing
+        else holds it.  The scans read `row_off[n_rows]` bytes of it, whatever its size."""
+        import torch
+        if not len(texts):
+            return
+        blob, o = pack_documents(list(texts))
+        need = self.n_bytes + int(o[-1])
+        if need > self.blob.numel():
+            grown = torch.zeros(max(need, 2 * self.blob.numel()), dtype=torch.uint8, device=self.device)
+            grown[:self.n_bytes] = self.blob[:self.n_bytes]
+            self.blob = grown
+        if len(blob):
+            self.blob[self.n_bytes:need] = torch.from_numpy(blob.copy()).to(self.device)
+        more = torch.from_numpy(self.n_bytes + o[1:].astype(np.int64)).to(self.device)
+        self.row_off = torch.cat([self.row_off, more])
+        self.n_rows, self.n_bytes = self.n_rows + len(texts), need
+        self.n_words = (self.n_rows + 63) // 64
+
+    def compact(self, keep, word_rank, count: int) -> None:
+        """Drop the rows whose bit of `keep` (device int64 / uint64 [ceil(n / 64)]) is clear, on the device (`arx_compact_text`).
+        `word_rank`, `count`: the plan of `keep` (`arx_compact_plan`).  The blob keeps its capacity."""
+        import torch
+        from . import _lib
+        assert keep.is_cuda and keep.is_contiguous() and keep.shape == (self.n_words,) and word_rank.shape == (self.n_words + 1,)
+        new_blob = torch.zeros_like(self.blob)
+        new_off = torch.empty(int(count) + 1, dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = self.lib.arx_compact_text(self.blob.data_ptr(), self.row_off.data_ptr(), self.n_rows, keep.data_ptr(), word_rank.data_ptr(),
+                                           new_blob.data_ptr(), new_off.data_ptr(), self._stream())
+        _lib.check(rc, "arx_compact_text")
+        self.blob, self.row_off = new_blob, new_off
+        self.n_rows, self.n_bytes = int(count), int(new_off[-1].item())
+        self.n_words = (self.n_rows + 63) // 64
 
     def contains(self, patterns: Sequence[str], out=None):
         """int64 [P, ceil(n / 64)] on the device: bit r & 63 of word [p, r >> 6] = `patterns[p] in texts[r]`; bits at or beyond n are 0.

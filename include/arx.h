@@ -489,6 +489,36 @@ int32_t arx_text_regex_tuned(const uint8_t* blob, const int64_t* row_off, int64_
 /* *out_count (ONE device int64) = set bits of bits[0 .. ceil(n_rows/64)) that name rows below n_rows. */
 int32_t arx_bitmap_count(const uint64_t* bits, int64_t n_rows, int64_t* out_count, void* stream);
 
+/* ---- Stable compaction under a row bitmap (csrc/compact.hip; `HipCollection.compact()`) ---------------------------------------------
+ * Dropping rows from what a shard keeps in HBM without a round trip through the host.  `keep` is a row bitmap in the convention of
+ * arx_topk_search_filtered: device uint64 [ceil(n_rows / 64)], bit (r & 63) of word r >> 6 set = row r stays; bits at or beyond n_rows
+ * are ignored and may be garbage.  The three calls are stream-ordered on `stream`, work on caller-owned memory only (no workspace), use
+ * no atomics and no float arithmetic, and return ARX_ERR_ARG, naming the argument, before any launch on a null pointer, an n_rows
+ * outside [0, 2^36) or a row_bytes outside [1, 16384].
+ *
+ * The plan:  word_rank device int64 [ceil(n_rows / 64) + 1] receives the exclusive prefix sum of the words' popcounts, the total in
+ * its last entry and in *out_count (ONE device int64).  The new position of a kept row r is
+ *     word_rank[r >> 6] + popcount(keep[r >> 6] & ((1 << (r & 63)) - 1)).
+ * Every entry is written; n_rows == 0 writes word_rank[0] = 0 and a count of 0 (keep may then be null).  Three launches (per-block
+ * sums, one scan of the block totals, one pass that adds them): no block waits for another. */
+int32_t arx_compact_plan(const uint64_t* keep, int64_t n_rows, int64_t* word_rank, int64_t* out_count, void* stream);
+/* Fixed-size rows, out of place: kept row r of src [n_rows, row_bytes] goes to row new(r) of dst.  `word_rank` is the plan of the same
+ * `keep`.  dst must not overlap src (the caller's contract).  Rows [0, count) of dst are written and nothing else: a byte beyond
+ * count * row_bytes keeps what it held.  Only kept rows are read; a 64-row word of `keep` that is zero costs its one load.  Rows move
+ * in 16-byte units when row_bytes and both pointers are multiples of 16, byte by byte otherwise, with the same result.  A plan that
+ * is not this bitmap's (a word's rows would land beyond the plan's own total) moves nothing for that word.  One launch. */
+int32_t arx_compact_rows(const void* src, void* dst, int64_t row_bytes, int64_t n_rows, const uint64_t* keep, const int64_t* word_rank,
+                         void* stream);
+/* The same for variable-length rows: blob / row_off as for arx_text_contains.  new_row_off device int64 [count + 1] receives the
+ * exclusive prefix sum of the kept rows' lengths, starting at 0 (scanned in three launches like the plan); new_blob receives their
+ * bytes, back to back.  new_blob must hold the kept bytes (row_off[n_rows] always suffices) and must not overlap blob; nothing is
+ * written beyond new_row_off[count].  Empty rows, an empty blob and count == 0 are legal; n_rows == 0 writes new_row_off[0] = 0.
+ * Offsets are device data and the caller's contract: a row is clamped into [0, row_off[n_rows]] as the text scans clamp it, and a row
+ * whose bytes would end beyond row_off[n_rows] in new_blob is skipped, so offsets outside the contract give wrong bytes, never an
+ * access out of range.  Four launches. */
+int32_t arx_compact_text(const uint8_t* blob, const int64_t* row_off, int64_t n_rows, const uint64_t* keep, const int64_t* word_rank,
+                         uint8_t* new_blob, int64_t* new_row_off, void* stream);
+
 /* ---- Chroma `where` filters over metadata columns in HBM (csrc/where_eval.hip; the lowering is arxiv_rag_amd/where_device.py) ----
  * A column is one metadata key over the shard's rows: kind uint8 [n_rows] (0 = absent or another type, 1 = number, 2 = string,
  * 3 = bool) and val f64 [n_rows] (the number; a string's rank in the sorted distinct strings of the key; 0.0 / 1.0 for a bool; 0.0

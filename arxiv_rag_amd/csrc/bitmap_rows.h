@@ -1,11 +1,54 @@
-// What the row-bitmap mask policies share (filter.hip: one bitmap per call; filter_multi.hip: a set of them): which bits of a word name rows
-// of the shard, and the exclusive scan of the words' popcounts that turns a bitmap into positions of a row list.
+// What the row-bitmap mask policies share (filter.hip, range.hip, grouped.hip: one bitmap per call; filter_multi.hip: a set of them): which
+// bits of a word name rows of the shard, pass A's policy for one bitmap per call, the all-ones bitmap of a call without one, and the
+// exclusive scan of the words' popcounts that turns a bitmap into positions of a row list.
 // Included inside the including file's anonymous namespace after masked_topk.h; not a stand-alone header.
 #pragma once
 
 __device__ __forceinline__ uint64_t valid_bits(int64_t n_rows, int64_t g) {      // the bits of word g that name rows of the shard
     const int64_t rem = n_rows - g * GROUP_ROWS;
     return rem >= GROUP_ROWS ? ~0ull : ((1ull << rem) - 1ull);
+}
+
+// ---- pass A with one bitmap for every query of the call: the pass-A part of a mask policy (masked_topk.h).  range.hip and grouped.hip,
+// whose tails are their own, use it as it stands; filter.hip's BitmapMask adds the tail's and the exhaustive path's parts ---------------------
+struct BitmapRows {
+    const uint64_t* allow;      // bit r & 63 of word r >> 6 = row r is visible
+    struct LaneRows {           // the bits of the lane's 16 rows, taken once: they do not depend on the query
+        bool on[GROUP_ROWS / 16][4];
+        __device__ __forceinline__ const LaneRows& of_query(int, int) const { return *this; }
+        __device__ __forceinline__ bool operator()(int j, int r) const { return on[j][r]; }
+    };
+    struct Tile {
+        bool empty; uint64_t mine;
+        __device__ __forceinline__ LaneRows lane_rows(int64_t, int lane) const {
+            const uint32_t lrow = (uint32_t)(lane >> 4) * 4u;
+            LaneRows s;
+#pragma unroll
+            for (int j = 0; j < GROUP_ROWS / 16; ++j)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) s.on[j][r] = (mine >> ((uint32_t)(j * 16 + r) + lrow)) & 1ull;
+            return s;
+        }
+    };
+    template <int BM>
+    __device__ __forceinline__ Tile tile(int64_t n0, int wn, int, int, int64_t n_rows) const {
+        const int64_t n_groups = (n_rows + GROUP_ROWS - 1) / GROUP_ROWS;
+        uint64_t any = 0, mine = 0;                            // the tile's four words (block-uniform) and this wave's own
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int64_t gj = (n0 >> 6) + j;
+            const uint64_t w = gj < n_groups ? (allow[gj] & valid_bits(n_rows, gj)) : 0ull;
+            any |= w;
+            mine = j == wn ? w : mine;
+        }
+        return {any == 0ull, mine};
+    }
+};
+
+// every row visible: the bitmap a call without one makes in its workspace
+__global__ __launch_bounds__(256) void bitmap_ones_kernel(uint64_t* __restrict__ words, int64_t n_words) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n_words) words[i] = ~0ull;
 }
 
 // ---- the row list of the exhaustive path --------------------------------------------------------------------------------------------------

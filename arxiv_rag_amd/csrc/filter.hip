@@ -42,44 +42,12 @@ __global__ __launch_bounds__(256) void filter_scatter_kernel(const uint64_t* __r
 }
 
 // ---- the mask policy (masked_topk.h) -------------------------------------------------------------------------------------------------------
-struct BitmapMask {
-    const uint64_t* allow;      // the caller's bitmap
+struct BitmapMask : BitmapRows {      // pass A and `allow`, the caller's bitmap: bitmap_rows.h
     int64_t n_allowed;          // the caller's count of its set bits, -1 = unknown (host only)
     int64_t* off;               // workspace: [n_groups + 1] offsets of the words' rows in `rows`
     int64_t* rows;              // workspace: the allowed rows in ascending order
     const int64_t* n_list;      // = off + n_groups: the number of allowed rows
 
-    // pass A
-    struct LaneRows {           // the bits of the lane's 16 rows, taken once: they do not depend on the query
-        bool on[GROUP_ROWS / 16][4];
-        __device__ __forceinline__ const LaneRows& of_query(int, int) const { return *this; }
-        __device__ __forceinline__ bool operator()(int j, int r) const { return on[j][r]; }
-    };
-    struct Tile {
-        bool empty; uint64_t mine;
-        __device__ __forceinline__ LaneRows lane_rows(int64_t, int lane) const {
-            const uint32_t lrow = (uint32_t)(lane >> 4) * 4u;
-            LaneRows s;
-#pragma unroll
-            for (int j = 0; j < GROUP_ROWS / 16; ++j)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) s.on[j][r] = (mine >> ((uint32_t)(j * 16 + r) + lrow)) & 1ull;
-            return s;
-        }
-    };
-    template <int BM>
-    __device__ __forceinline__ Tile tile(int64_t n0, int wn, int, int, int64_t n_rows) const {
-        const int64_t n_groups = (n_rows + GROUP_ROWS - 1) / GROUP_ROWS;
-        uint64_t any = 0, mine = 0;                            // the tile's four words (block-uniform) and this wave's own
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int64_t gj = (n0 >> 6) + j;
-            const uint64_t w = gj < n_groups ? (allow[gj] & valid_bits(n_rows, gj)) : 0ull;
-            any |= w;
-            mine = j == wn ? w : mine;
-        }
-        return {any == 0ull, mine};
-    }
     // the tail
     struct Query {
         const uint64_t* allow; int64_t n_rows, n_groups;
@@ -125,7 +93,7 @@ extern "C" int32_t arx_topk_search_filtered_tuned(const void* corpus, int64_t n_
                                                   int32_t n_queries, int32_t dim, int32_t k, float* out_scores, int64_t* out_ids,
                                                   int64_t idx_base, float max_row_norm, void* ws, int64_t ws_bytes, int32_t path,
                                                   int32_t cand_cap, void* stream) {
-    return masked_search_impl(BitmapMask{allow, n_allowed, nullptr, nullptr, nullptr}, corpus, n_rows, queries, n_queries, dim, k, out_scores, out_ids,
+    return masked_search_impl(BitmapMask{{allow}, n_allowed, nullptr, nullptr, nullptr}, corpus, n_rows, queries, n_queries, dim, k, out_scores, out_ids,
                               idx_base, max_row_norm, ws, ws_bytes, path, cand_cap, stream);
 }
 

@@ -5,12 +5,13 @@
 //   paper score    the maximum of score(q, r) over the paper's visible rows; a paper without a visible row does not exist for the query
 //   answer         the P best papers by (paper score desc, row of the best chunk asc), and of each the m best visible chunks by (score desc,
 //                  row asc); (-inf, -1) / -1 padding
-// Pass A is masked_topk.h's masked_groupmax_kernel with a bitmap policy (allow == NULL: an all-ones bitmap in the workspace), unchanged.
-// The tail (grouped_tail_kernel, one block per query) is new.  With R = max_run_rows an upper bound on the rows of any run, a run touches
+// Pass A is masked_topk.h's masked_groupmax_kernel with bitmap_rows.h's BitmapRows policy (allow == NULL: an all-ones bitmap in the
+// workspace), unchanged.  The tail (grouped_tail_kernel, one block per query) finds its candidate groups by masked_topk.h's stage
+// (tail_kth_key, tail_candidates) and folds their rows by paper.  With R = max_run_rows an upper bound on the rows of any run, a run touches
 // at most S = floor((R + 62) / 64) + 1 of the 64-row groups; K = P S.
 // Why the tail is exact: let t be the K-th largest group maximum of the query.  The K groups at or above t each hold a visible row whose
 // pass-A score is >= t; a paper touches at most S of them, so at least P distinct papers have a visible row whose pass-A score is >= t,
-// hence whose exact score is >= t - tau (pass A and exact_row_score differ by at most tau = tau_scale |q|, the masked tail's own bound).
+// hence whose exact score is >= t - tau (pass A and exact_row_score differ by at most tau = tau_scale |q|: masked_tau_scale, masked_topk.h).
 // So the P-th best paper score is >= t - tau, and every paper of the true top-P - ties at the P-th score included - has its best row at
 // an exact score >= t - tau, a pass-A score >= t - 2 tau: that row lies in a group with gmax >= t - 2 tau.  Candidates = every non-empty
 // group with gmax >= t - 2 tau; their visible rows are rescored exactly and folded by group_of (maximum per paper, ties to the lower row).
@@ -39,46 +40,6 @@ namespace {      // the headers also define non-template kernels: internal linka
 
 #define GRP_KSEL_MAX 512             // largest K = P S the scan path selects for; beyond: the exhaustive path
 #define GRP_CHUNKS_MAX 8             // largest m
-
-// ---- pass A's mask policy: the bitmap of the call, as filter.hip's ------------------------------------------------------------------------
-struct GroupedBitmap {
-    const uint64_t* allow;
-    struct LaneRows {
-        bool on[GROUP_ROWS / 16][4];
-        __device__ __forceinline__ const LaneRows& of_query(int, int) const { return *this; }
-        __device__ __forceinline__ bool operator()(int j, int r) const { return on[j][r]; }
-    };
-    struct Tile {
-        bool empty; uint64_t mine;
-        __device__ __forceinline__ LaneRows lane_rows(int64_t, int lane) const {
-            const uint32_t lrow = (uint32_t)(lane >> 4) * 4u;
-            LaneRows s;
-#pragma unroll
-            for (int j = 0; j < GROUP_ROWS / 16; ++j)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) s.on[j][r] = (mine >> ((uint32_t)(j * 16 + r) + lrow)) & 1ull;
-            return s;
-        }
-    };
-    template <int BM>
-    __device__ __forceinline__ Tile tile(int64_t n0, int wn, int, int, int64_t n_rows) const {
-        const int64_t n_groups = (n_rows + GROUP_ROWS - 1) / GROUP_ROWS;
-        uint64_t any = 0, mine = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int64_t gj = (n0 >> 6) + j;
-            const uint64_t w = gj < n_groups ? (allow[gj] & valid_bits(n_rows, gj)) : 0ull;
-            any |= w;
-            mine = j == wn ? w : mine;
-        }
-        return {any == 0ull, mine};
-    }
-};
-
-__global__ __launch_bounds__(256) void grouped_ones_kernel(uint64_t* __restrict__ words, int64_t n_words) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n_words) words[i] = ~0ull;
-}
 
 // ---- runs of group_of ---------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ int64_t run_lower(const int32_t* __restrict__ g, int64_t n, int32_t v) {      // first row with g[row] >= v
@@ -171,20 +132,6 @@ __device__ __forceinline__ void block_merge_papers(const float (*w_s)[KMAX], con
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 }
 
-// one wave: the exact scores of the rows of group g that `word` names -> sc[0..64) (entries of other rows are not written)
-__device__ __forceinline__ void score_word_rows(const f16_t* __restrict__ C, int64_t g, uint64_t word, const f16_t* qs, int D, int lane,
-                                                float* sc) {
-    const int nch = D >> 3, l8 = lane & 7, rsub = lane >> 3;
-    for (int r8 = 0; r8 < GROUP_ROWS; r8 += 8) {
-        if (((word >> r8) & 0xffull) == 0ull) continue;          // wave-uniform
-        const int rr = r8 + rsub;
-        const bool ok = (word >> rr) & 1ull;
-        const float a = exact_row_score(C + (g * GROUP_ROWS + rr) * D, qs, nch, l8, ok);
-        if (l8 == 0) sc[rr] = a;
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-}
-
 // ---- the chunk step: wave w of NW takes papers w, w + NW, ... of the query's P selected ones (fin_i: the row of the best chunk, < 0 = no
 // such paper; fin_g: its group_of value): the run's ends, every visible row of the run scored, the m best kept ---------------------------
 __device__ __forceinline__ void paper_chunks(int w, int NW, int lane, const int64_t* fin_i, const int32_t* fin_g, int P, int m,
@@ -233,74 +180,19 @@ __global__ __launch_bounds__(FILT_TAIL_NT) void grouped_tail_kernel(const float*
     __shared__ float fin_s[KMAX];
     __shared__ int64_t fin_i[KMAX];
     __shared__ int32_t fin_g[KMAX];
-    __shared__ int red[NW];
-    __shared__ int n_c;
-    __shared__ float sh_qn;
+    __shared__ TailStage st;
     const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     f16_t* qs = reinterpret_cast<f16_t*>(smem);                                                  // [D] query row
     float* sc_all = reinterpret_cast<float*>(smem + (((size_t)D * 2 + 15) & ~(size_t)15));      // [NW][64] row scores of the group a wave is at
     int32_t* list = reinterpret_cast<int32_t*>(sc_all + NW * GROUP_ROWS);                        // [cand_cap] candidate groups
-    for (int i = tid; i < (D >> 3); i += NT)
-        reinterpret_cast<u32x4*>(qs)[i] = reinterpret_cast<const u32x4*>(Q + (int64_t)q * D)[i];
-    if (tid == 0) n_c = 0;
-    // this query's column of group maxima, as ordered keys: the first FILT_REG_GROUPS per thread stay in registers
-    const float* col = gmax + q;
+    load_query_row<NT>(qs, Q, q, D);
+    if (tid == 0) st.n_c = 0;
+    const float* col = gmax + q;                                                                 // this query's column of group maxima
     uint32_t kv[FILT_REG_GROUPS];
-#pragma unroll
-    for (int j = 0; j < FILT_REG_GROUPS; ++j) {
-        const int64_t g = (int64_t)j * NT + tid;
-        kv[j] = g < n_groups ? order_key(col[g * ldg]) : 0u;
-    }
-    __syncthreads();
-    if (w == 0) {
-        float qq = 0.f;
-        for (int i = lane; i < D; i += 64) { const float v = (float)qs[i]; qq = fmaf(v, v, qq); }
-        qq = wave_sum(qq);
-        if (lane == 0) sh_qn = sqrtf(qq);
-    }
-    // T = the largest key that at least ksel groups reach = the ksel-th largest group maximum: a radix select, one bit per step
-    uint32_t T = 0u;
-    for (int bit = 31; bit >= 0; --bit) {
-        const uint32_t cand = T | (1u << bit);
-        int c = 0;
-#pragma unroll
-        for (int j = 0; j < FILT_REG_GROUPS; ++j) c += __popcll(__ballot(kv[j] >= cand));
-        for (int64_t g0 = (int64_t)FILT_REG_GROUPS * NT + w * 64; g0 < n_groups; g0 += NT) {          // (wave-uniform bounds)
-            const int64_t g = g0 + lane;
-            c += __popcll(__ballot(g < n_groups && order_key(col[(g < n_groups ? g : 0) * ldg]) >= cand));
-        }
-        if (lane == 0) red[w] = c;
-        __syncthreads();
-        int tot = 0;
-#pragma unroll
-        for (int ww = 0; ww < NW; ++ww) tot += red[ww];
-        __syncthreads();
-        T = tot >= ksel ? cand : T;
-    }
-    const float thr = key_value(T) - 2.0f * tau_scale * sh_qn;      // -inf when fewer than ksel groups hold a visible row
-    auto consider = [&](int64_t g, float v) {
-        if (v >= thr && v > -INFINITY) {
-            const int sl = atomicAdd(&n_c, 1);
-            if (sl < cand_cap) list[sl] = (int32_t)g;
-        }
-    };
-#pragma unroll
-    for (int j = 0; j < FILT_REG_GROUPS; ++j) {
-        const int64_t g = (int64_t)j * NT + tid;
-        if (g < n_groups) consider(g, key_value(kv[j]));
-    }
-    for (int64_t g = (int64_t)FILT_REG_GROUPS * NT + tid; g < n_groups; g += NT) consider(g, col[g * ldg]);
-    __syncthreads();
-    const int nc = n_c;
-    if (nc > cand_cap) {                                       // block-uniform: never an answer from a truncated list
-        if (tid == 0) {
-            redo[q] = 1;
-            atomicAdd(&stats[0], 1ull);
-            reinterpret_cast<int*>(stats + 2)[0] = 1;
-        }
-        return;
-    }
-    if (tid == 0) { redo[q] = 0; if (nc) atomicAdd(&stats[1], (unsigned long long)nc); }
+    const uint32_t T = tail_kth_key(st, kv, col, ldg, n_groups, qs, D, ksel);      // the ksel-th largest group maximum
+    const float thr = key_value(T) - 2.0f * tau_scale * st.qn;      // -inf when fewer than ksel groups hold a visible row
+    const int nc = tail_candidates(st, kv, col, ldg, n_groups, thr, list, cand_cap, q, redo, stats);
+    if (nc < 0) return;                                        // block-uniform: flagged for the exhaustive path
     // the visible rows of the candidate groups, exactly, folded by paper: a group per wave at a time
     float* sc = sc_all + w * GROUP_ROWS;
     float cs = -INFINITY; int64_t ci = -1; int32_t cp = -1;
@@ -348,8 +240,7 @@ __global__ __launch_bounds__(256) void grouped_exhaustive_kernel(const uint64_t*
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     f16_t* qs = reinterpret_cast<f16_t*>(smem);
     float* sc = reinterpret_cast<float*>(smem + (((size_t)D * 2 + 15) & ~(size_t)15)) + w * GROUP_ROWS;
-    for (int i = tid; i < (D >> 3); i += 256)
-        reinterpret_cast<u32x4*>(qs)[i] = reinterpret_cast<const u32x4*>(Q + (int64_t)q * D)[i];
+    load_query_row<256>(qs, Q, q, D);
     __syncthreads();
     const int64_t per = ((n_rows + parts - 1) / parts + 63) / 64 * 64;
     const int64_t a = part_cut(group_of, n_rows, per, p), b = p + 1 < parts ? part_cut(group_of, n_rows, per, p + 1) : n_rows;
@@ -395,8 +286,7 @@ __global__ __launch_bounds__(FILT_TAIL_NT) void grouped_chunks_kernel(const int6
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     f16_t* qs = reinterpret_cast<f16_t*>(smem);
     float* sc = reinterpret_cast<float*>(smem + (((size_t)D * 2 + 15) & ~(size_t)15)) + w * GROUP_ROWS;
-    for (int i = tid; i < (D >> 3); i += NT)
-        reinterpret_cast<u32x4*>(qs)[i] = reinterpret_cast<const u32x4*>(Q + (int64_t)q * D)[i];
+    load_query_row<NT>(qs, Q, q, D);
     if (tid < P) {
         const int64_t row = sel_i[(int64_t)q * P + tid];
         fin_i[tid] = row;
@@ -486,15 +376,15 @@ extern "C" int32_t arx_topk_search_grouped_tuned(const void* corpus, int64_t n_r
     int64_t* sel_i = (int64_t*)(wsb + L.sel_i);
     float* part_s = (float*)(wsb + L.part_s);
     int64_t* part_i = (int64_t*)(wsb + L.part_i);
-    const float tau_scale = (0.3125f * (float)dim + 4.0f) * 5.9604645e-8f * (max_row_norm > 0.0f ? max_row_norm : 1.0f + 1.0f / 512.0f);
+    const float tau_scale = masked_tau_scale(dim, max_row_norm);
     ARX_HIP_CHECK(hipMemsetAsync(stats, 0, 64, st));
     if (!allow) {                                               // every row: an all-ones bitmap of the call's own
         uint64_t* ones = (uint64_t*)(wsb + L.ones);
-        grouped_ones_kernel<<<cdiv(L.n_groups, 256), 256, 0, st>>>(ones, L.n_groups);
+        bitmap_ones_kernel<<<cdiv(L.n_groups, 256), 256, 0, st>>>(ones, L.n_groups);
         ARX_HIP_CHECK(hipGetLastError());
         allow = ones;
     }
-    const GroupedBitmap mask{allow};
+    const BitmapRows mask{allow};
     const size_t smem_q = ((size_t)dim * 2 + 15) & ~(size_t)15;
     for (int q0 = 0; q0 < n_queries; q0 += QBATCH_MAX) {
         const int nq = (n_queries - q0) < QBATCH_MAX ? (n_queries - q0) : QBATCH_MAX;
@@ -503,13 +393,7 @@ extern "C" int32_t arx_topk_search_grouped_tuned(const void* corpus, int64_t n_r
         int64_t* oi = out_ids + (int64_t)q0 * P * m;
         int32_t* og = out_groups + (int64_t)q0 * P;
         if (path == 1) {
-            {
-                ProfScope ps(ARX_K_SEARCH_GROUPMAX, st);
-                const int rc = nq <= 64 ? launch_masked_groupmax<64>(Q, nq, C, n_rows, dim, mask, gmax, L.ldg, st)
-                             : nq <= 128 ? launch_masked_groupmax<128>(Q, nq, C, n_rows, dim, mask, gmax, L.ldg, st)
-                                         : launch_masked_groupmax<256>(Q, nq, C, n_rows, dim, mask, gmax, L.ldg, st);
-                if (rc != ARX_OK) return rc;
-            }
+            if (const int rc = launch_masked_pass_a(Q, nq, C, n_rows, dim, mask, gmax, L.ldg, st); rc != ARX_OK) return rc;
             ProfScope ps(ARX_K_SEARCH_RESCORE, st);
             const size_t smem = smem_q + (size_t)(FILT_TAIL_NT / 64) * GROUP_ROWS * 4 + (size_t)cand_cap * 4;
             if (smem > 48 * 1024) ARX_HIP_CHECK(arx_func_smem((const void*)grouped_tail_kernel, (int)smem));

@@ -70,6 +70,25 @@ __device__ __forceinline__ void block_merge_lists(const float (*w_s)[KMAX], cons
     wave_topk<R4>(s, id, k, lane, fin_s, fin_i);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 }
+// the block's NT threads: row q of Q -> qs in LDS (readable after the caller's next barrier)
+template <int NT>
+__device__ __forceinline__ void load_query_row(f16_t* qs, const f16_t* __restrict__ Q, int q, int D) {
+    for (int i = threadIdx.x; i < (D >> 3); i += NT)
+        reinterpret_cast<u32x4*>(qs)[i] = reinterpret_cast<const u32x4*>(Q + (int64_t)q * D)[i];
+}
+// one wave: the exact scores of the rows of group g that `word` names -> sc[0..64) (entries of other rows are not written): 8 lanes per row
+__device__ __forceinline__ void score_word_rows(const f16_t* __restrict__ C, int64_t g, uint64_t word, const f16_t* qs, int D, int lane,
+                                                float* sc) {
+    const int nch = D >> 3, l8 = lane & 7, rsub = lane >> 3;
+    for (int r8 = 0; r8 < GROUP_ROWS; r8 += 8) {
+        if (((word >> r8) & 0xffull) == 0ull) continue;          // wave-uniform
+        const int rr = r8 + rsub;
+        const bool ok = (word >> rr) & 1ull;
+        const float a = exact_row_score(C + (g * GROUP_ROWS + rr) * D, qs, nch, l8, ok);
+        if (l8 == 0) sc[rr] = a;
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+}
 
 // ---- masked pass A: search_groupmax_kernel with the mask in front of the group maximum ---------------------------------------------------
 template <int BM, class Mask>
@@ -122,6 +141,86 @@ __global__ __launch_bounds__(512) void masked_groupmax_kernel(const f16_t* __res
     store_query_row<ML::MI, float>(gmax + g * ldg, gm, m0 + wm * ML::TM, nq, lane);
 }
 
+// ---- the candidate-group stage of a tail block: masked_tail_kernel below, range.hip's and grouped.hip's tails (FILT_TAIL_NT threads, one
+// query).  A kernel copies its query row to LDS, zeroes st.n_c, calls tail_kth_key, computes ITS threshold from the key and st.qn, and
+// calls tail_candidates.  The exactness of every masked scan rests on these two functions and the kernel's threshold between them.
+// (masked_tail_kernel carries tail_kth_key's text inline, for the speed of the self-join: see there.)
+struct TailStage { int red[FILT_TAIL_NT / 64]; int n_c; float qn; };
+
+// kv = this thread's first FILT_REG_GROUPS group maxima of column `col` (the query's) as ordered keys, kept in registers for
+// tail_candidates; st.qn = |q| of the query row qs, by wave 0; returns T = the largest key that at least ksel groups reach = the ksel-th
+// largest group maximum, by a block-wide radix select, one bit per step.  Its first barrier also publishes qs and st.n_c.
+__device__ __forceinline__ uint32_t tail_kth_key(TailStage& st, uint32_t (&kv)[FILT_REG_GROUPS], const float* __restrict__ col, int64_t ldg,
+                                                 int64_t n_groups, const f16_t* qs, int D, int ksel) {
+    constexpr int NT = FILT_TAIL_NT, NW = NT / 64;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+#pragma unroll
+    for (int j = 0; j < FILT_REG_GROUPS; ++j) {
+        const int64_t g = (int64_t)j * NT + tid;
+        kv[j] = g < n_groups ? order_key(col[g * ldg]) : 0u;
+    }
+    __syncthreads();
+    if (w == 0) {
+        float qq = 0.f;
+        for (int i = lane; i < D; i += 64) { const float v = (float)qs[i]; qq = fmaf(v, v, qq); }
+        qq = wave_sum(qq);
+        if (lane == 0) st.qn = sqrtf(qq);
+    }
+    uint32_t T = 0u;
+    for (int bit = 31; bit >= 0; --bit) {
+        const uint32_t cand = T | (1u << bit);
+        int c = 0;
+#pragma unroll
+        for (int j = 0; j < FILT_REG_GROUPS; ++j) c += __popcll(__ballot(kv[j] >= cand));
+        for (int64_t g0 = (int64_t)FILT_REG_GROUPS * NT + w * 64; g0 < n_groups; g0 += NT) {          // (wave-uniform bounds)
+            const int64_t g = g0 + lane;
+            c += __popcll(__ballot(g < n_groups && order_key(col[(g < n_groups ? g : 0) * ldg]) >= cand));
+        }
+        if (lane == 0) st.red[w] = c;
+        __syncthreads();
+        int tot = 0;
+#pragma unroll
+        for (int ww = 0; ww < NW; ++ww) tot += st.red[ww];
+        __syncthreads();
+        T = tot >= ksel ? cand : T;
+    }
+    return T;
+}
+
+// candidates = every non-empty group at or above thr -> list[0 .. cand_cap), in any order (an integer LDS atomic hands out the slots).
+// Returns their number (block-uniform) after recording redo[q] = 0 and stats[1]; or, when the list cannot hold them, -1 after flagging
+// the query for the exhaustive path (redo[q] = 1, stats[0], the gate word): never an answer from a truncated list.
+__device__ __forceinline__ int tail_candidates(TailStage& st, const uint32_t (&kv)[FILT_REG_GROUPS], const float* __restrict__ col, int64_t ldg,
+                                               int64_t n_groups, float thr, int32_t* list, int cand_cap, int q, int32_t* __restrict__ redo,
+                                               unsigned long long* __restrict__ stats) {
+    constexpr int NT = FILT_TAIL_NT;
+    const int tid = threadIdx.x;
+    auto consider = [&](int64_t g, float v) {
+        if (v >= thr && v > -INFINITY) {
+            const int sl = atomicAdd(&st.n_c, 1);
+            if (sl < cand_cap) list[sl] = (int32_t)g;
+        }
+    };
+#pragma unroll
+    for (int j = 0; j < FILT_REG_GROUPS; ++j) {
+        const int64_t g = (int64_t)j * NT + tid;
+        if (g < n_groups) consider(g, key_value(kv[j]));
+    }
+    for (int64_t g = (int64_t)FILT_REG_GROUPS * NT + tid; g < n_groups; g += NT) consider(g, col[g * ldg]);
+    __syncthreads();
+    const int nc = st.n_c;
+    if (nc > cand_cap) {                                       // block-uniform
+        if (tid == 0) {
+            redo[q] = 1;
+            atomicAdd(&stats[0], 1ull);
+            reinterpret_cast<int*>(stats + 2)[0] = 1;
+        }
+        return -1;
+    }
+    if (tid == 0) { redo[q] = 0; if (nc) atomicAdd(&stats[1], (unsigned long long)nc); }
+    return nc;
+}
+
 // ---- masked scan, the tail: one block per query ------------------------------------------------------------------------------------------
 // t = the k-th largest group maximum, candidates = every group with gmax >= t - 2 tau that is not -inf, their visible rows rescored by
 // exact_row_score, top-k by (score desc, row asc).
@@ -143,19 +242,18 @@ __global__ __launch_bounds__(FILT_TAIL_NT) void masked_tail_kernel(const float* 
     __shared__ int64_t w_i[NW][KMAX];
     __shared__ float fin_s[KMAX];
     __shared__ int64_t fin_i[KMAX];
-    __shared__ int red[NW];
-    __shared__ int n_c;
-    __shared__ float sh_qn;
+    __shared__ TailStage st;
     const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const auto qm = mask.query(q, n_rows, n_groups_all);
     const int64_t n_groups = qm.n_groups;                                                        // groups that may hold a visible row
     f16_t* qs = reinterpret_cast<f16_t*>(smem);                                                  // [D] query row
     float* sc_all = reinterpret_cast<float*>(smem + (((size_t)D * 2 + 15) & ~(size_t)15));      // [NW][64] row scores of the group a wave is at
     int32_t* list = reinterpret_cast<int32_t*>(sc_all + NW * GROUP_ROWS);                        // [cand_cap] candidate groups
-    for (int i = tid; i < (D >> 3); i += NT)
-        reinterpret_cast<u32x4*>(qs)[i] = reinterpret_cast<const u32x4*>(Q + (int64_t)q * D)[i];
-    if (tid == 0) n_c = 0;
-    // this query's column of group maxima, as ordered keys: the first FILT_REG_GROUPS per thread stay in registers
+    load_query_row<NT>(qs, Q, q, D);
+    if (tid == 0) st.n_c = 0;
+    // tail_kth_key(st, kv, col, ldg, n_groups, qs, D, k), written out: through the function the compiler schedules the select loop's
+    // second barrier after the compare and select, and the 200 000 blocks of the prefix self-join took 1.4 % longer
+    // (profiles/tail_stages_refactor.md).  Keep the two texts the same.
     const float* col = gmax + q;
     uint32_t kv[FILT_REG_GROUPS];
 #pragma unroll
@@ -168,10 +266,9 @@ __global__ __launch_bounds__(FILT_TAIL_NT) void masked_tail_kernel(const float* 
         float qq = 0.f;
         for (int i = lane; i < D; i += 64) { const float v = (float)qs[i]; qq = fmaf(v, v, qq); }
         qq = wave_sum(qq);
-        if (lane == 0) sh_qn = sqrtf(qq);
+        if (lane == 0) st.qn = sqrtf(qq);
     }
-    // T = the largest key that at least k groups reach = the k-th largest group maximum, bit by bit
-    uint32_t T = 0u;
+    uint32_t T = 0u;                                           // -> the k-th largest group maximum
     for (int bit = 31; bit >= 0; --bit) {
         const uint32_t cand = T | (1u << bit);
         int c = 0;
@@ -181,54 +278,24 @@ __global__ __launch_bounds__(FILT_TAIL_NT) void masked_tail_kernel(const float* 
             const int64_t g = g0 + lane;
             c += __popcll(__ballot(g < n_groups && order_key(col[(g < n_groups ? g : 0) * ldg]) >= cand));
         }
-        if (lane == 0) red[w] = c;
+        if (lane == 0) st.red[w] = c;
         __syncthreads();
         int tot = 0;
 #pragma unroll
-        for (int ww = 0; ww < NW; ++ww) tot += red[ww];
+        for (int ww = 0; ww < NW; ++ww) tot += st.red[ww];
         __syncthreads();
         T = tot >= k ? cand : T;
     }
-    const float thr = key_value(T) - 2.0f * tau_scale * sh_qn;      // -inf when fewer than k groups hold a visible row
-    // candidates: every non-empty group at or above the threshold
-    auto consider = [&](int64_t g, float v) {
-        if (v >= thr && v > -INFINITY) {
-            const int sl = atomicAdd(&n_c, 1);
-            if (sl < cand_cap) list[sl] = (int32_t)g;
-        }
-    };
-#pragma unroll
-    for (int j = 0; j < FILT_REG_GROUPS; ++j) {
-        const int64_t g = (int64_t)j * NT + tid;
-        if (g < n_groups) consider(g, key_value(kv[j]));
-    }
-    for (int64_t g = (int64_t)FILT_REG_GROUPS * NT + tid; g < n_groups; g += NT) consider(g, col[g * ldg]);
-    __syncthreads();
-    const int nc = n_c;
-    if (nc > cand_cap) {                                       // block-uniform: never an answer from a truncated list
-        if (tid == 0) {
-            redo[q] = 1;
-            atomicAdd(&stats[0], 1ull);
-            reinterpret_cast<int*>(stats + 2)[0] = 1;
-        }
-        return;
-    }
-    if (tid == 0) { redo[q] = 0; if (nc) atomicAdd(&stats[1], (unsigned long long)nc); }
-    // the visible rows of the candidate groups, exactly: 8 lanes per row, a group per wave at a time
-    const int nch = D >> 3, l8 = lane & 7, rsub = lane >> 3;
+    const float thr = key_value(T) - 2.0f * tau_scale * st.qn;     // -inf when fewer than k groups hold a visible row
+    const int nc = tail_candidates(st, kv, col, ldg, n_groups, thr, list, cand_cap, q, redo, stats);
+    if (nc < 0) return;                                        // block-uniform: flagged for the exhaustive path
+    // the visible rows of the candidate groups, exactly: a group per wave at a time
     float* sc = sc_all + w * GROUP_ROWS;
     float cs = -INFINITY; int64_t ci = -1;
     for (int p = w; p < nc; p += NW) {
         const int64_t gsel = list[p];
         const uint64_t word = qm.word(gsel);
-        for (int r8 = 0; r8 < GROUP_ROWS; r8 += 8) {
-            if (((word >> r8) & 0xffull) == 0ull) continue;      // wave-uniform
-            const int rr = r8 + rsub;
-            const bool ok = (word >> rr) & 1ull;
-            const float a = exact_row_score(C + (gsel * GROUP_ROWS + rr) * D, qs, nch, l8, ok);
-            if (l8 == 0) sc[rr] = a;
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        score_word_rows(C, gsel, word, qs, D, lane, sc);
         const bool mine = (word >> lane) & 1ull;
         wave_merge64(cs, ci, mine ? sc[lane] : -INFINITY, mine ? gsel * GROUP_ROWS + lane : -1, k, lane, w_s[w], w_i[w]);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -264,8 +331,7 @@ __global__ __launch_bounds__(256) void masked_exhaustive_kernel(const Mask mask,
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     f16_t* qs = reinterpret_cast<f16_t*>(smem);
     float* sc = reinterpret_cast<float*>(smem + (((size_t)D * 2 + 15) & ~(size_t)15)) + w * GROUP_ROWS;
-    for (int i = tid; i < (D >> 3); i += 256)
-        reinterpret_cast<u32x4*>(qs)[i] = reinterpret_cast<const u32x4*>(Q + (int64_t)q * D)[i];
+    load_query_row<256>(qs, Q, q, D);
     __syncthreads();
     const int64_t total = mask.list_total(q);
     const int64_t per = ((total + P - 1) / P + 63) / 64 * 64;
@@ -372,6 +438,20 @@ int launch_masked_groupmax(const f16_t* Q, int nq, const f16_t* C, int64_t n_row
     ARX_HIP_CHECK(hipGetLastError());
     return ARX_OK;
 }
+// pass A of a batch of nq queries: the query tile by the batch's size
+template <class Mask>
+int launch_masked_pass_a(const f16_t* Q, int nq, const f16_t* C, int64_t n_rows, int D, const Mask& mask, float* gmax, int64_t ldg,
+                         hipStream_t st) {
+    ProfScope ps(ARX_K_SEARCH_GROUPMAX, st);
+    return nq <= 64 ? launch_masked_groupmax<64>(Q, nq, C, n_rows, D, mask, gmax, ldg, st)
+         : nq <= 128 ? launch_masked_groupmax<128>(Q, nq, C, n_rows, D, mask, gmax, ldg, st)
+                     : launch_masked_groupmax<256>(Q, nq, C, n_rows, D, mask, gmax, ldg, st);
+}
+// tau = masked_tau_scale |q| bounds the difference between a row's pass-A score and its exact_row_score (rescore_kernel step 5);
+// max_row_norm = 0: unit rows, with search.hip's default norm bound of 1 + 1/512
+float masked_tau_scale(int dim, float max_row_norm) {
+    return (0.3125f * (float)dim + 4.0f) * 5.9604645e-8f * (max_row_norm > 0.0f ? max_row_norm : 1.0f + 1.0f / 512.0f);
+}
 
 // `mask` arrives with the caller's arguments set; its workspace pointers are bound here.  path / cand_cap = 0: the library's choice.
 template <class Mask>
@@ -401,7 +481,7 @@ int masked_search_impl(Mask mask, const void* corpus, int64_t n_rows, const void
     int32_t* redo = (int32_t*)(wsb + L.redo);
     float* part_s = (float*)(wsb + L.part_s);
     int64_t* part_i = (int64_t*)(wsb + L.part_i);
-    const float tau_scale = (0.3125f * (float)dim + 4.0f) * 5.9604645e-8f * (max_row_norm > 0.0f ? max_row_norm : 1.0f + 1.0f / 512.0f);
+    const float tau_scale = masked_tau_scale(dim, max_row_norm);
     ARX_HIP_CHECK(hipMemsetAsync(stats, 0, 64, st));
     const size_t smem_q = ((size_t)dim * 2 + 15) & ~(size_t)15;
     for (int q0 = 0; q0 < n_queries; q0 += QBATCH_MAX) {
@@ -411,13 +491,7 @@ int masked_search_impl(Mask mask, const void* corpus, int64_t n_rows, const void
         int64_t* oi = out_ids + (int64_t)q0 * k;
         if (const int rc = mask.prepare_batch(q0, nq, n_rows, st); rc != ARX_OK) return rc;
         if (path == 1) {
-            {
-                ProfScope ps(ARX_K_SEARCH_GROUPMAX, st);
-                const int rc = nq <= 64 ? launch_masked_groupmax<64>(Q, nq, C, n_rows, dim, mask, gmax, L.ldg, st)
-                             : nq <= 128 ? launch_masked_groupmax<128>(Q, nq, C, n_rows, dim, mask, gmax, L.ldg, st)
-                                         : launch_masked_groupmax<256>(Q, nq, C, n_rows, dim, mask, gmax, L.ldg, st);
-                if (rc != ARX_OK) return rc;
-            }
+            if (const int rc = launch_masked_pass_a(Q, nq, C, n_rows, dim, mask, gmax, L.ldg, st); rc != ARX_OK) return rc;
             ProfScope ps(ARX_K_SEARCH_RESCORE, st);
             const size_t smem = smem_q + (size_t)(FILT_TAIL_NT / 64) * GROUP_ROWS * 4 + (size_t)cand_cap * 4;
             if (smem > 48 * 1024) ARX_HIP_CHECK(arx_func_smem((const void*)masked_tail_kernel<Mask>, (int)smem));

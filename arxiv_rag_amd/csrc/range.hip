@@ -5,9 +5,10 @@
 //   qualifies      a visible row with score(q, r) >= min_score[q], compared in f32 (-inf: every visible row; +inf or NaN: none)
 //   answer         the best min(count, M) qualifying rows by (score desc, row asc), M = max_results <= 1024, (-inf, -1) padding, and
 //                  out_counts[q] = the number of qualifying rows when that is <= M, M + 1 when more qualify (the list is truncated)
-// Pass A is masked_topk.h's masked_groupmax_kernel with a bitmap policy (allow == NULL: an all-ones bitmap in the workspace), unchanged.
-// The tail (range_tail_kernel, one block per query) is new: it keeps a variable, long, ordered list instead of a k <= 32 wave list.
-// Why the tail is exact: pass A and exact_row_score differ by at most tau = tau_scale |q| (the masked tail's own bound), so a qualifying
+// Pass A is masked_topk.h's masked_groupmax_kernel with bitmap_rows.h's BitmapRows policy (allow == NULL: an all-ones bitmap in the
+// workspace), unchanged.  The tail (range_tail_kernel, one block per query) finds its candidate groups by masked_topk.h's stage
+// (tail_kth_key, tail_candidates) with a threshold of its own; then it keeps a variable, long, ordered list instead of a k <= 32 wave list.
+// Why the tail is exact: pass A and exact_row_score differ by at most tau = tau_scale |q| (masked_tau_scale, masked_topk.h), so a qualifying
 // row has a pass-A score >= min_score - tau and its group's maximum is at least that.  Let t be the (M + 1)-th largest group maximum of
 // the query (-inf when fewer than M + 1 groups hold a visible row).  A qualifying row in a group with gmax < t - 2 tau has an exact score
 // below t - tau, while M + 1 distinct groups each hold a visible row whose pass-A score is >= t, hence whose exact score is >= t - tau:
@@ -15,8 +16,8 @@
 // group with gmax >= max(min_score - tau, t - 2 tau): they hold every row of the answer, and whenever more than M rows qualify they
 // alone hold M + 1 qualifying rows.  So "qualifying rows among the candidates <= M" means the list and the count are complete, and
 // ">= M + 1" means truncated: the count is reported as M + 1 and nothing more is known (an exact total would make a loose threshold
-// cost a full exact scan).  The (M + 1)-th largest of up to n_rows / 64 values is the block-wide radix select over order_key of the
-// masked and grouped tails.
+// cost a full exact scan).  The (M + 1)-th largest of up to n_rows / 64 values is the block-wide radix select over order_key that
+// the masked and grouped tails use (tail_kth_key).
 // The list: a qualifying row is the 64-bit key (order_key(score) << 32) | (0xffffffff - row), whose unsigned order is (score desc, row
 // asc); 0 = none (n_rows < 2^32).  The waves append keys to RANGE_CAP = 2048 slots in LDS (an INTEGER LDS atomic hands out the slots:
 // the list's order varies, its content does not); every qualifying row is counted apart.  Before a round of 16 groups that could
@@ -45,46 +46,6 @@ namespace {      // the headers also define non-template kernels: internal linka
 #define RANGE_CAP 2048               // key slots of a block's list (16 KB of LDS): M kept keys + one round of 16 groups x 64 rows
 #define RANGE_NT FILT_TAIL_NT        // threads of every block that keeps a list
 #define RANGE_PART_KEYS 4096         // T M <= this: bounds the exhaustive path's per-part lists (and the workspace)
-
-// ---- pass A's mask policy: the bitmap of the call, as filter.hip's ------------------------------------------------------------------------
-struct RangeBitmap {
-    const uint64_t* allow;
-    struct LaneRows {
-        bool on[GROUP_ROWS / 16][4];
-        __device__ __forceinline__ const LaneRows& of_query(int, int) const { return *this; }
-        __device__ __forceinline__ bool operator()(int j, int r) const { return on[j][r]; }
-    };
-    struct Tile {
-        bool empty; uint64_t mine;
-        __device__ __forceinline__ LaneRows lane_rows(int64_t, int lane) const {
-            const uint32_t lrow = (uint32_t)(lane >> 4) * 4u;
-            LaneRows s;
-#pragma unroll
-            for (int j = 0; j < GROUP_ROWS / 16; ++j)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) s.on[j][r] = (mine >> ((uint32_t)(j * 16 + r) + lrow)) & 1ull;
-            return s;
-        }
-    };
-    template <int BM>
-    __device__ __forceinline__ Tile tile(int64_t n0, int wn, int, int, int64_t n_rows) const {
-        const int64_t n_groups = (n_rows + GROUP_ROWS - 1) / GROUP_ROWS;
-        uint64_t any = 0, mine = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int64_t gj = (n0 >> 6) + j;
-            const uint64_t w = gj < n_groups ? (allow[gj] & valid_bits(n_rows, gj)) : 0ull;
-            any |= w;
-            mine = j == wn ? w : mine;
-        }
-        return {any == 0ull, mine};
-    }
-};
-
-__global__ __launch_bounds__(256) void range_ones_kernel(uint64_t* __restrict__ words, int64_t n_words) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n_words) words[i] = ~0ull;
-}
 
 // ---- the list of a block ------------------------------------------------------------------------------------------------------------------
 struct RangeList {
@@ -125,20 +86,6 @@ __device__ __forceinline__ void range_cut(RangeList& L, int c, int M) {
         L.thr = c >= M ? L.keys[M - 1] : 0ull;
     }
     __syncthreads();
-}
-
-// one wave: the exact scores of the rows of group g that `word` names -> sc[0..64) (entries of other rows are not written)
-__device__ __forceinline__ void score_word_rows(const f16_t* __restrict__ C, int64_t g, uint64_t word, const f16_t* qs, int D, int lane,
-                                                float* sc) {
-    const int nch = D >> 3, l8 = lane & 7, rsub = lane >> 3;
-    for (int r8 = 0; r8 < GROUP_ROWS; r8 += 8) {
-        if (((word >> r8) & 0xffull) == 0ull) continue;          // wave-uniform
-        const int rr = r8 + rsub;
-        const bool ok = (word >> rr) & 1ull;
-        const float a = exact_row_score(C + (g * GROUP_ROWS + rr) * D, qs, nch, l8, ok);
-        if (l8 == 0) sc[rr] = a;
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 }
 
 // one wave: the visible rows `word` of group g scored; those at or above ms counted, and appended where their key is above thr
@@ -209,13 +156,11 @@ __global__ __launch_bounds__(RANGE_NT) void range_tail_kernel(const float* __res
     constexpr int NT = RANGE_NT, NW = NT / 64;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ RangeList L;
-    __shared__ int red[NW];
-    __shared__ int n_c;
-    __shared__ float sh_qn;
-    const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    __shared__ TailStage st;
+    const int q = blockIdx.x, tid = threadIdx.x, w = tid >> 6;
     const float ms = min_score[q];
     out_s += (int64_t)q * M; out_i += (int64_t)q * M; out_c += q;
-    if (tid == 0) { n_c = 0; L.cnt = 0; L.n_qual = 0; L.thr = 0ull; }
+    if (tid == 0) { st.n_c = 0; L.cnt = 0; L.n_qual = 0; L.thr = 0ull; }
     if (!(ms < INFINITY)) {                                     // block-uniform: +inf or NaN, no row qualifies
         __syncthreads();
         range_store(L, 0, 0, M, idx_base, out_s, out_i, out_c);
@@ -225,68 +170,14 @@ __global__ __launch_bounds__(RANGE_NT) void range_tail_kernel(const float* __res
     f16_t* qs = reinterpret_cast<f16_t*>(smem);                                                  // [D] query row
     float* sc_all = reinterpret_cast<float*>(smem + (((size_t)D * 2 + 15) & ~(size_t)15));      // [NW][64] row scores of the group a wave is at
     int32_t* list = reinterpret_cast<int32_t*>(sc_all + NW * GROUP_ROWS);                        // [cand_cap] candidate groups
-    for (int i = tid; i < (D >> 3); i += NT)
-        reinterpret_cast<u32x4*>(qs)[i] = reinterpret_cast<const u32x4*>(Q + (int64_t)q * D)[i];
-    // this query's column of group maxima, as ordered keys: the first FILT_REG_GROUPS per thread stay in registers
-    const float* col = gmax + q;
+    load_query_row<NT>(qs, Q, q, D);
+    const float* col = gmax + q;                                                                 // this query's column of group maxima
     uint32_t kv[FILT_REG_GROUPS];
-#pragma unroll
-    for (int j = 0; j < FILT_REG_GROUPS; ++j) {
-        const int64_t g = (int64_t)j * NT + tid;
-        kv[j] = g < n_groups ? order_key(col[g * ldg]) : 0u;
-    }
-    __syncthreads();
-    if (w == 0) {
-        float qq = 0.f;
-        for (int i = lane; i < D; i += 64) { const float v = (float)qs[i]; qq = fmaf(v, v, qq); }
-        qq = wave_sum(qq);
-        if (lane == 0) sh_qn = sqrtf(qq);
-    }
-    // T = the largest key that at least M + 1 groups reach = the (M + 1)-th largest group maximum: a radix select, one bit per step
-    const int ksel = M + 1;
-    uint32_t T = 0u;
-    for (int bit = 31; bit >= 0; --bit) {
-        const uint32_t cand = T | (1u << bit);
-        int c = 0;
-#pragma unroll
-        for (int j = 0; j < FILT_REG_GROUPS; ++j) c += __popcll(__ballot(kv[j] >= cand));
-        for (int64_t g0 = (int64_t)FILT_REG_GROUPS * NT + w * 64; g0 < n_groups; g0 += NT) {          // (wave-uniform bounds)
-            const int64_t g = g0 + lane;
-            c += __popcll(__ballot(g < n_groups && order_key(col[(g < n_groups ? g : 0) * ldg]) >= cand));
-        }
-        if (lane == 0) red[w] = c;
-        __syncthreads();
-        int tot = 0;
-#pragma unroll
-        for (int ww = 0; ww < NW; ++ww) tot += red[ww];
-        __syncthreads();
-        T = tot >= ksel ? cand : T;
-    }
-    const float tau = tau_scale * sh_qn;
+    const uint32_t T = tail_kth_key(st, kv, col, ldg, n_groups, qs, D, M + 1);      // the (M + 1)-th largest group maximum
+    const float tau = tau_scale * st.qn;
     const float thr = fmaxf(ms - tau, key_value(T) - 2.0f * tau);      // key_value(T) = -inf when fewer than M + 1 groups hold a visible row
-    auto consider = [&](int64_t g, float v) {
-        if (v >= thr && v > -INFINITY) {
-            const int sl = atomicAdd(&n_c, 1);
-            if (sl < cand_cap) list[sl] = (int32_t)g;
-        }
-    };
-#pragma unroll
-    for (int j = 0; j < FILT_REG_GROUPS; ++j) {
-        const int64_t g = (int64_t)j * NT + tid;
-        if (g < n_groups) consider(g, key_value(kv[j]));
-    }
-    for (int64_t g = (int64_t)FILT_REG_GROUPS * NT + tid; g < n_groups; g += NT) consider(g, col[g * ldg]);
-    __syncthreads();
-    const int nc = n_c;
-    if (nc > cand_cap) {                                       // block-uniform: never an answer from a truncated list
-        if (tid == 0) {
-            redo[q] = 1;
-            atomicAdd(&stats[0], 1ull);
-            reinterpret_cast<int*>(stats + 2)[0] = 1;
-        }
-        return;
-    }
-    if (tid == 0) { redo[q] = 0; if (nc) atomicAdd(&stats[1], (unsigned long long)nc); }
+    const int nc = tail_candidates(st, kv, col, ldg, n_groups, thr, list, cand_cap, q, redo, stats);
+    if (nc < 0) return;                                        // block-uniform: flagged for the exhaustive path
     // the visible rows of the candidate groups, exactly: a group per wave at a time
     range_rounds(L, nc, [&](int64_t item) { return (int64_t)list[item]; },
                  [&](int64_t g) { return allow[g] & valid_bits(n_rows, g); }, C, qs, D, sc_all + w * GROUP_ROWS, ms, M);
@@ -311,8 +202,7 @@ __global__ __launch_bounds__(RANGE_NT) void range_exhaustive_kernel(const uint64
     const int tid = threadIdx.x, w = tid >> 6;
     f16_t* qs = reinterpret_cast<f16_t*>(smem);
     float* sc = reinterpret_cast<float*>(smem + (((size_t)D * 2 + 15) & ~(size_t)15)) + w * GROUP_ROWS;
-    for (int i = tid; i < (D >> 3); i += NT)
-        reinterpret_cast<u32x4*>(qs)[i] = reinterpret_cast<const u32x4*>(Q + (int64_t)q * D)[i];
+    load_query_row<NT>(qs, Q, q, D);
     if (tid == 0) { L.cnt = 0; L.n_qual = 0; L.thr = 0ull; }
     __syncthreads();
     const float ms = min_score[q];
@@ -417,15 +307,15 @@ extern "C" int32_t arx_range_search_tuned(const void* corpus, int64_t n_rows, co
     int32_t* redo = (int32_t*)(wsb + L.redo);
     unsigned long long* part_k = (unsigned long long*)(wsb + L.part_k);
     int32_t* part_c = (int32_t*)(wsb + L.part_c);
-    const float tau_scale = (0.3125f * (float)dim + 4.0f) * 5.9604645e-8f * (max_row_norm > 0.0f ? max_row_norm : 1.0f + 1.0f / 512.0f);
+    const float tau_scale = masked_tau_scale(dim, max_row_norm);
     ARX_HIP_CHECK(hipMemsetAsync(stats, 0, 64, st));
     if (!allow) {                                               // every row: an all-ones bitmap of the call's own
         uint64_t* ones = (uint64_t*)(wsb + L.ones);
-        range_ones_kernel<<<cdiv(L.n_groups, 256), 256, 0, st>>>(ones, L.n_groups);
+        bitmap_ones_kernel<<<cdiv(L.n_groups, 256), 256, 0, st>>>(ones, L.n_groups);
         ARX_HIP_CHECK(hipGetLastError());
         allow = ones;
     }
-    const RangeBitmap mask{allow};
+    const BitmapRows mask{allow};
     const size_t smem_q = ((size_t)dim * 2 + 15) & ~(size_t)15;
     for (int q0 = 0; q0 < n_queries; q0 += QBATCH_MAX) {
         const int nq = (n_queries - q0) < QBATCH_MAX ? (n_queries - q0) : QBATCH_MAX;
@@ -435,13 +325,7 @@ extern "C" int32_t arx_range_search_tuned(const void* corpus, int64_t n_rows, co
         int64_t* oi = out_ids + (int64_t)q0 * M;
         int32_t* oc = out_counts + q0;
         if (path == 1) {
-            {
-                ProfScope ps(ARX_K_SEARCH_GROUPMAX, st);
-                const int rc = nq <= 64 ? launch_masked_groupmax<64>(Q, nq, C, n_rows, dim, mask, gmax, L.ldg, st)
-                             : nq <= 128 ? launch_masked_groupmax<128>(Q, nq, C, n_rows, dim, mask, gmax, L.ldg, st)
-                                         : launch_masked_groupmax<256>(Q, nq, C, n_rows, dim, mask, gmax, L.ldg, st);
-                if (rc != ARX_OK) return rc;
-            }
+            if (const int rc = launch_masked_pass_a(Q, nq, C, n_rows, dim, mask, gmax, L.ldg, st); rc != ARX_OK) return rc;
             ProfScope ps(ARX_K_SEARCH_RESCORE, st);
             const size_t smem = smem_q + (size_t)(RANGE_NT / 64) * GROUP_ROWS * 4 + (size_t)cand_cap * 4;
             if (smem > 32 * 1024) ARX_HIP_CHECK(arx_func_smem((const void*)range_tail_kernel, (int)smem));

@@ -189,7 +189,7 @@ def test_range_kernels_do_not_spill_or_use_scratch():
     if not f.exists():
         pytest.skip("no _build/range.resources.txt (library not built by csrc/build.sh in this tree)")
     ks = {m.group(1): (int(m.group(4)), int(m.group(7))) for m in PAT.finditer(f.read_text())}
-    for name in ("masked_groupmax_kernel", "range_tail_kernel", "range_exhaustive_kernel", "range_merge_kernel", "range_ones_kernel"):
+    for name in ("masked_groupmax_kernel", "range_tail_kernel", "range_exhaustive_kernel", "range_merge_kernel", "bitmap_ones_kernel"):
         assert any(name in k for k in ks), name
     assert sum("masked_groupmax_kernel" in k for k in ks) == 3        # 64-, 128- and 256-query tiles
     bad = {k: v for k, v in ks.items() if v[0] or v[1]}

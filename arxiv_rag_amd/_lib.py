@@ -72,6 +72,13 @@ class GemmEpilogueC(C.Structure):
         self.struct_bytes = C.sizeof(GemmEpilogueC)
 
 
+class FacetKeyC(C.Structure):
+    """arx_facet_key (include/arx.h): one key of an arx_facet_count call; 48 bytes, device pointers."""
+    _fields_ = [("kind", C.c_void_p), ("val", C.c_void_p), ("cuts", C.c_void_p), ("mode", C.c_int32), ("want_kind", C.c_int32),
+                ("n_bins", C.c_int32), ("reserved", C.c_int32), ("out_off", C.c_int64)]
+
+
+FACET_CODE, FACET_EXACT, FACET_INTERVAL = 0, 1, 2                                                                     # ARX_FACET_*
 TOPK_NO_PERSISTENT, TOPK_SCAN_ONLY, TOPK_TAIL_ONLY, TOPK_NO_SINGLE_ROW_TAIL, TOPK_I8_CENTRE_QUERY = 1, 2, 4, 8, 16
 GEMM_DEFAULT, GEMM_PER_TILE, GEMM_PERSISTENT, GEMM_2STAGE, GEMM_SPLIT_K, GEMM_TILE_128 = 89, 8, 9, 13, 70, 71          # ARX_GEMM_*
 ATTN_TRANSPOSED, ATTN_RING, ATTN_RING16, ATTN_STAGED = 1, 2, 4, 8                                                     # ARX_ATTN_*
@@ -168,6 +175,10 @@ EXPORTS = {
     "arx_compact_text": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "arx_where_eval": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
                                    C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "arx_facet_count": (C.c_int32, [C.POINTER(FacetKeyC), C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64,
+                                    C.c_void_p]),
+    "arx_facet_count_tuned": (C.c_int32, [C.POINTER(FacetKeyC), C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64,
+                                          C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "arx_gather_rows": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "arx_mmr_select": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p,
                                    C.c_void_p, C.c_void_p]),

@@ -935,6 +935,11 @@ def build_parser() -> argparse.ArgumentParser:
                         "only; not with --rerank-model, --hybrid-alpha, --mmr-lambda, --group-by-paper or --where-file)")
     p.add_argument("--chunks-per-paper", type=int, default=1,
                    help="Chunks returned for each paper of --group-by-paper (default: 1; at most 8)")
+    p.add_argument("--facets", type=str, default=None,
+                   help="Facet counts beside the --queries results: metadata keys separated by commas, e.g. section,paper_id; for each "
+                        "key facets.json lists its values with the most chunks among those --where / --where-document (or each line of "
+                        "--where-file) allow, counted on the GPU (default: off; needs --queries; one GPU rank only)")
+    p.add_argument("--facets-top", type=int, default=10, help="Values listed per key of --facets (default: 10)")
     return p
 
 
@@ -1054,7 +1059,56 @@ def find_shard_duplicates(shard: "ShardSink", chunks: List[Dict], threshold: flo
     return dup_of < 0
 
 
-GROUP_MAX_PAPERS, GROUP_MAX_CHUNKS = 32, 8      # arx_topk_search_grouped: papers per query (the search's k limit), chunks per paper
+def check_facets_args(args) -> Optional[str]:
+    """-> an error message for an unusable --facets / --facets-top, else None.  On success `args.facet_keys` holds the keys (None
+    without --facets).  (The other flags are read with getattr: absent = off.)"""
+    args.facet_keys = None
+    if getattr(args, "facets", None) is None:
+        if getattr(args, "facets_top", 10) != 10:
+            return f"--facets-top {args.facets_top} needs --facets: it counts the values listed per key"
+        return None
+    keys = [k.strip() for k in args.facets.split(",")]
+    if not all(keys):
+        return f"--facets {args.facets!r}: metadata keys separated by commas, e.g. section,paper_id"
+    if not getattr(args, "queries", None):
+        return "--facets needs --queries: it counts under the filters of the search step"
+    if getattr(args, "facets_top", 10) < 1:
+        return f"--facets-top {args.facets_top}: at least one value per key"
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        return "--facets needs a single GPU rank: ranks number their strings separately, and a per-rank top list cannot be merged exactly"
+    args.facet_keys = keys
+    return None
+
+
+def facet_counts(chunks: List[Dict], device, keys: Sequence[str], top: int = 10, where=None, where_document: Optional[Dict] = None, *,
+                 keep_mask: Optional[np.ndarray] = None, where_on_device: bool = False, document_regex: bool = False,
+                 output_dir: str = "./embeddings_saved"):
+    """`--facets`: the facet counts of `keys` (`facets.count`, INTEGRATION.md "Facet counts") over the metadata of `chunks`, under the
+    row filters the search step uses (`retrieval.RowFilters`: `where`, `where_document`, `keep_mask`), written to `facets.json` beside
+    the other output files: `{"keys", "top", "facets"}`, `facets` being one list of per-key results (`{key, values, counts, distinct,
+    missing, unbinned, total}`), or with a per-query `where` list one such list per entry.  -> what was written under `facets`."""
+    from . import facets as F
+    from .retrieval import RowFilters
+    from .where_device import MetadataColumns
+    metadata = [c.get("metadata") or {} for c in chunks]
+    n = len(chunks)
+    filters = RowFilters(metadata, device, 0, n, keep_mask=keep_mask, texts=lambda: [c["text"] for c in chunks],
+                         where_on_device=where_on_device, document_regex=document_regex)
+    cols = filters.columns() if where_on_device else MetadataColumns(metadata, 0, n, device)
+    if isinstance(where, (list, tuple)):
+        bitmaps, filter_of, _ = filters.per_query(len(where), where, where_document)
+        per_filter = F.count(cols, list(keys), bitmaps, top)
+        result = [per_filter[f] for f in filter_of]
+    else:
+        allow, _ = filters.allow_of(where, where_document)
+        result = F.count(cols, list(keys), allow, top)[0]
+    with open(Path(output_dir) / "facets.json", "w", encoding="utf-8") as fh:
+        json.dump({"keys": list(keys), "top": top, "facets": result}, fh, indent=2, ensure_ascii=False)
+    print(f"✅ Facet counts of {', '.join(keys)} written to {Path(output_dir) / 'facets.json'}")
+    return result
+
+
+GROUP_MAX_PAPERS, GROUP_MAX_CHUNKS = 32, 8    # arx_topk_search_grouped: papers per query (the search's k limit), chunks per paper
 
 
 def check_group_args(args) -> Optional[str]:
@@ -1212,7 +1266,7 @@ def main(argv: Optional[Sequence[str]] = None, model_factory: Optional[Callable]
     args = build_parser().parse_args(argv)
     err = (check_rerank_args(args) or check_hybrid_args(args) or check_hybrid_filters_args(args) or check_hybrid_device_args(args) or check_keyword_build_args(args) or check_where_args(args) or check_where_file_args(args) or check_where_device_args(args)
            or check_where_document_args(args)
-           or check_mmr_args(args) or check_dedup_args(args) or check_group_args(args) or check_range_args(args))
+           or check_mmr_args(args) or check_dedup_args(args) or check_group_args(args) or check_range_args(args) or check_facets_args(args))
     if err:
         print(f"Error: {err}")
         return 2
@@ -1316,6 +1370,11 @@ def main(argv: Optional[Sequence[str]] = None, model_factory: Optional[Callable]
                                **({"hybrid_on_device": True} if args.hybrid_on_device else {}),
                                **({"keyword_build_on_device": True} if args.keyword_build_on_device else {}),
                                **({"document_regex": True} if args.where_document_regex else {}))
+                if args.facet_keys is not None:
+                    facet_counts(chunks, _model.encoder.device, args.facet_keys, args.facets_top,
+                                 where=args.where_filters if args.where_filters is not None else args.where_filter,
+                                 where_document=args.where_document_filter, keep_mask=keep_mask, where_on_device=args.where_on_device,
+                                 document_regex=args.where_document_regex)
         store_time = 0.0
         if rank == 0 and not args.skip_chroma:
             try:

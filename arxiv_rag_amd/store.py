@@ -414,6 +414,40 @@ class HipCollection:
                           documents=self._documents, columns=self._columns, where_on_device=getattr(self, "where_on_device", False),
                           cache=self._where_columns, document_regex=getattr(self, "document_regex", False))
 
+    def facets(self, keys, where=None, where_document=None, top: Optional[int] = 10):
+        """Facet counts (INTEGRATION.md "Facet counts"): for every key of `keys`, how many of the rows a query with these filters could
+        return hold each of its values.  `keys`: a list of specs (one spec alone is a list of one): a metadata key name (faceted over
+        its strings if any row has a string there, else its numbers, else its bools), `{"key": k, "kind": "string" | "number" | "bool"}`
+        or `{"key": k, "edges": [e0, e1, ...]}` (numbers counted per interval [e_i, e_i+1), the last one closed).  -> one dict per key,
+        `{key, values, counts, distinct, missing, unbinned, total}`: the `top` values with the most rows (count descending, then value
+        ascending; `top=None`: every value with a row; for `edges` every `(lo, hi)` interval in order, empty ones included), `distinct`
+        the values with at least one row, `missing` the allowed rows without a value of the kind, `unbinned` those with a NaN or a number
+        outside the edges, `total` the allowed rows.  Numbers come back as floats.
+        `where` / `where_document` are what `query` takes, evaluated by the same `retrieval.RowFilters` (on the host, or on the device
+        with `where_on_device`; the dedup and tombstone keep-bitmap and-ed in); a list of either gives a list of results, one per entry,
+        the distinct (where, where_document) pairs evaluated once.  The counting runs on the device (`facets.count`,
+        `arx_facet_count`) from the metadata columns `where_on_device` uses, built on first use whether or not the collection has that
+        flag.  ValueError, before anything is launched: a malformed spec or `top`; `world > 1` (ranks number their strings separately
+        and a per-rank top list cannot be merged exactly); more than 2^20 distinct values under one key."""
+        from . import facets as F
+        from .filter_sets import is_per_query
+        if getattr(self, "world", 1) > 1:
+            raise ValueError("facets needs world == 1: ranks number their strings separately, and a per-rank top list cannot be merged exactly")
+        specs = [keys] if isinstance(keys, (str, dict)) else list(keys)
+        for s in specs:
+            F.parse_spec(s)
+        F._check_top(top)
+        rf = self._row_filters()
+        if is_per_query(where) or is_per_query(where_document):
+            nq = len(where) if is_per_query(where) else len(where_document)
+            bitmaps, filter_of, _ = rf.per_query(nq, where, where_document)
+            per_filter = F.count(self._columns(), specs, bitmaps, top) if nq else []
+            return [per_filter[f] for f in filter_of]
+        if where_document is not None:
+            self._documents()
+        allow, _ = rf.allow_of(where, where_document)
+        return F.count(self._columns(), specs, allow, top)[0]
+
     def query(self, query_embeddings=None, query_texts: Optional[Sequence[str]] = None, n_results: int = 10, reranker=None,
               n_candidates: int = 32, hybrid_alpha: Optional[float] = None, where=None, where_document=None,
               mmr_lambda: Optional[float] = None, group_by=None, chunks_per_group: int = 1, min_score=None) -> Dict:

@@ -266,6 +266,9 @@ class MetadataColumns:
         self.n_words = (self.n_rows + 63) // 64
         self.device = device
         self._strings: Dict[str, List[str]] = {}
+        self._numbers: Dict[str, np.ndarray] = {}
+        self._kinds: Dict[str, frozenset] = {}
+        self._facets: Dict = {}                                 # `facets.resolve`'s results, by spec
         self._host: Dict[str, Tuple[np.ndarray, np.ndarray]] = {}
         self._dev: Dict[str, Tuple] = {}
         self._host_cache: Dict = {}                             # `where.evaluate`'s columns, for the filters past the limits
@@ -287,6 +290,7 @@ class MetadataColumns:
             elif k == _BOOL:
                 val[r] = 1.0 if v else 0.0
         self._strings[key] = strings
+        self._kinds[key] = frozenset(np.unique(kind).tolist())
         return kind, val
 
     def strings(self, key: str) -> List[str]:
@@ -297,6 +301,26 @@ class MetadataColumns:
             else:
                 self.device_column(key)
         return self._strings[key]
+
+    def numbers(self, key: str) -> np.ndarray:
+        """The sorted distinct non-NaN numbers of `key` in [lo, hi), float64, -0.0 folded into 0.0: the `cuts` of an exact facet
+        (`facets.resolve`).  Computed on first use and cached next to `strings(key)`."""
+        if key not in self._numbers:
+            kind, val = self.host_column(key)
+            v = val[(kind == _NUM) & ~np.isnan(val)]
+            self._numbers[key] = np.unique(np.where(v == 0.0, 0.0, v))
+        return self._numbers[key]
+
+    def kinds(self, key: str) -> frozenset:
+        """The kinds (0 absent or another type, 1 number, 2 string, 3 bool) the rows [lo, hi) hold under `key`."""
+        self.strings(key)
+        return self._kinds[key]
+
+    def drop(self) -> None:
+        """Forget every column and what was derived from it (the string and number lists, the host evaluator's cache): the metadata
+        changed, everything is rebuilt on its next use."""
+        self._strings, self._numbers, self._kinds, self._facets = {}, {}, {}, {}
+        self._host, self._dev, self._host_cache = {}, {}, {}
 
     def host_column(self, key: str) -> Tuple[np.ndarray, np.ndarray]:
         """(kind uint8 [n], val float64 [n]) as numpy."""

@@ -563,6 +563,58 @@ int32_t arx_where_eval(const int64_t* col_table, int32_t n_cols, int64_t n_rows,
                        const uint64_t* and_with, int64_t and_stride,
                        uint64_t* out_bits, int64_t* out_counts, void* stream);
 
+/* ---- Facet counts of metadata keys under row bitmaps (csrc/facet.hip; the host layer is arxiv_rag_amd/facets.py) ---------------------
+ * "How many allowed rows per value of this key": the columns are those of arx_where_eval (kind uint8 + val f64 per row), the bitmaps
+ * those every filter here produces (bit (r & 63) of word r >> 6 = row r is allowed).  A key describes one column and how a row's value
+ * becomes a bin.  The bin applies only to a row whose bit is set and whose kind[r] == want_kind:
+ *   mode 0 ARX_FACET_CODE      the bin is val[r], if it is an integer in [0, n_bins) (strings by their code, bools as 0 / 1)
+ *   mode 1 ARX_FACET_EXACT     the bin is i with cuts[i] == val[r]; cuts holds n_bins values, ascends strictly and holds no NaN; the
+ *                              lookup is a binary search with the IEEE compare, so -0.0 finds 0.0
+ *   mode 2 ARX_FACET_INTERVAL  the bin is i with cuts[i] <= val[r] < cuts[i + 1]; cuts holds n_bins + 1 ascending edges and
+ *                              val[r] == cuts[n_bins] falls into the last bin (numpy.histogram's convention)
+ * Comparisons are in f64; no arithmetic touches the values.  The layout of a key, 48 bytes, no padding; the array of keys is a HOST
+ * array whose pointers are DEVICE pointers: */
+#define ARX_FACET_CODE     0
+#define ARX_FACET_EXACT    1
+#define ARX_FACET_INTERVAL 2
+typedef struct arx_facet_key {
+    const uint8_t* kind;  /* offset  0: device uint8 [n_rows] */
+    const double*  val;   /* offset  8: device f64 [n_rows] */
+    const double*  cuts;  /* offset 16: device f64; mode 1: n_bins values, mode 2: n_bins + 1 edges, mode 0: unused, may be NULL */
+    int32_t mode;         /* offset 24 */
+    int32_t want_kind;    /* offset 28: 1 number, 2 string, 3 bool */
+    int32_t n_bins;       /* offset 32: 1 .. 2^20 */
+    int32_t reserved;     /* offset 36: 0 */
+    int64_t out_off;      /* offset 40: where this key's n_bins + 2 counters start within a filter's slice of out */
+} arx_facet_key;
+/*   allow   NULL (every row), or device uint64 bitmaps of ceil(n_rows / 64) words: filter f reads the words at allow + f * allow_stride
+ *           (allow_stride in words; 0 = one bitmap for all filters).  Bits of the last word at or beyond n_rows are not trusted and
+ *           not counted.
+ *   out     device int32 [n_filters][out_stride].  Filter f and key j own out[f * out_stride + out_off_j + b]:  b < n_bins the bins,
+ *           b == n_bins "missing" (an allowed row whose kind is not want_kind), b == n_bins + 1 "unbinned" (the right kind, no bin: a
+ *           NaN, a value outside the edges or not among the cuts, a code out of range or not integral).  Every key's counters sum to
+ *           the allowed rows below n_rows.
+ * The call zeroes all n_filters * out_stride counters on `stream` and launches once: grid (row chunks, filters, keys); a zero bitmap
+ * word costs its one load.  A key with n_bins + 2 <= 8192 is counted in an LDS histogram per block and flushed with one integer atomic
+ * per non-zero counter, a larger one adds to `out` directly; a wave whose rows agree on the bin issues one add of their number.  Only
+ * integer atomic adds are used, so the counts do not depend on the launch shape or on the order of arrival.  No workspace, no host
+ * synchronisation.
+ * ARX_ERR_ARG before anything is launched or zeroed, the message naming the field: a null keys, out, kind, val or (modes 1, 2) cuts;
+ * n_keys outside 1..16; n_filters outside 1..64; n_bins outside 1..2^20; n_rows outside [0, 2^31); a mode or want_kind not among its
+ * values; a negative allow_stride; a key's counters outside out_stride or overlapping another key's; n_filters * out_stride > 2^27.
+ * What the columns and cuts hold is device data: values outside the contract (a wild code, unsorted cuts) may give wrong counts, never
+ * a read or write outside the arrays passed. */
+int32_t arx_facet_count(const arx_facet_key* keys, int32_t n_keys, int64_t n_rows,
+                        const uint64_t* allow, int64_t allow_stride, int32_t n_filters,
+                        int32_t* out, int64_t out_stride, void* stream);
+/* The same with the launch shape chosen: block_threads a multiple of 64 in 64..1024 (default 256), blocks_x >= 1 row-chunk blocks
+ * (blocks without a word exit), lds_bins in 0..32768 counters an LDS histogram may hold (default 8192 = 32 KiB; 0 forces the direct
+ * path).  Same counts for every choice. */
+int32_t arx_facet_count_tuned(const arx_facet_key* keys, int32_t n_keys, int64_t n_rows,
+                              const uint64_t* allow, int64_t allow_stride, int32_t n_filters,
+                              int32_t* out, int64_t out_stride,
+                              int32_t block_threads, int32_t blocks_x, int32_t lds_bins, void* stream);
+
 /* ---- MMR diversified re-ordering of a query's search candidates (csrc/mmr.hip; the definition is INTEGRATION.md "MMR") -----------
  * arx_gather_rows: out[s] (device fp16 [count, dim]) = shard row ids[s] - idx_base where that row lies in [0, n_rows), all zeros
  * otherwise (id -1, a row another rank owns: the ranks' buffers then add up to the rows, arxiv_rag_amd/mmr.py).  shard device fp16

@@ -172,7 +172,7 @@ class HipCollection:
             self._group_buf = torch.zeros(capacity, dtype=torch.int32, device=device)
             self._group_buf[:hi - lo] = torch.from_numpy(group_of).to(device)
         self._make_index()
-        if group_key is not None and hi > lo and capacity is None:
+        if group_key is not None and capacity is None:
             self.index.set_groups(group_of)
         self.keyword = None
         self._kw_stale, self._kw_pieces, self._kw_on_device = False, None, bool(keyword_build_on_device)
@@ -219,7 +219,7 @@ class HipCollection:
         dim = int(shard.shape[1])
         self.index = ShardIndex(shard, idx_base=self.lo, prefilter="int8" if (dim % 128 == 0 and 0 < dim <= 1024 and shard.shape[0] > 0) else None,
                                 adaptive=True)
-        if self._group_buf is not None and self.hi > self.lo:
+        if self._group_buf is not None:                         # (zero rows too: a grouped query of an empty collection returns empty lists)
             self.index.set_groups(self._group_buf[:self.hi - self.lo])
 
     def _pieces_of(self, texts):

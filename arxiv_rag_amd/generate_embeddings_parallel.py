@@ -940,6 +940,12 @@ def build_parser() -> argparse.ArgumentParser:
                         "key facets.json lists its values with the most chunks among those --where / --where-document (or each line of "
                         "--where-file) allow, counted on the GPU (default: off; needs --queries; one GPU rank only)")
     p.add_argument("--facets-top", type=int, default=10, help="Values listed per key of --facets (default: 10)")
+    p.add_argument("--topics", type=int, default=None,
+                   help="Topic clustering beside the --queries results: spherical k-means with this many topics over the embeddings of the "
+                        "chunks --where / --where-document allow, on the GPU; topics.json lists the sizes, the objective and each topic's "
+                        "nearest chunks (default: off; needs --queries; one GPU rank only; not with --where-file)")
+    p.add_argument("--topics-iters", type=int, default=20, help="Iterations of --topics at most (default: 20)")
+    p.add_argument("--topics-seed", type=int, default=0, help="Seed of the initial centroids of --topics (default: 0)")
     return p
 
 
@@ -1078,6 +1084,47 @@ def check_facets_args(args) -> Optional[str]:
         return "--facets needs a single GPU rank: ranks number their strings separately, and a per-rank top list cannot be merged exactly"
     args.facet_keys = keys
     return None
+
+
+def check_topics_args(args) -> Optional[str]:
+    """-> an error message for an unusable --topics / --topics-iters, else None.  (The other flags are read with getattr: absent = off.)"""
+    if getattr(args, "topics", None) is None:
+        return None
+    if not (1 <= args.topics <= 4096):
+        return f"--topics {args.topics} must be in [1, 4096]"
+    if getattr(args, "topics_iters", 20) < 1:
+        return f"--topics-iters {args.topics_iters}: at least one iteration"
+    if not getattr(args, "queries", None):
+        return "--topics needs --queries: it clusters under the filters of the search step"
+    if getattr(args, "where_filters", None) is not None:
+        return "--topics cannot be combined with --where-file: it clusters one set of chunks"
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        return "--topics needs a single GPU rank: a rank sees only its own rows"
+    return None
+
+
+def topic_clusters(chunks: List[Dict], shard: "ShardSink", n_topics: int, iters: int = 20, seed: int = 0, where=None,
+                   where_document: Optional[Dict] = None, *, keep_mask: Optional[np.ndarray] = None, where_on_device: bool = False,
+                   document_regex: bool = False, representatives: int = 3, output_dir: str = "./embeddings_saved"):
+    """`--topics`: spherical k-means (`topics.fit_shard`, INTEGRATION.md "Topics") over the fp16 rows the encode step left in HBM, under
+    the row filters the search step uses (`retrieval.RowFilters`: `where`, `where_document`, `keep_mask`), written to `topics.json`
+    beside the other output files: `{n_topics, iters, seed, sizes, objective, iterations, representatives}`, the representatives being
+    each topic's nearest allowed chunks as chunk ids.  -> what was written."""
+    from . import topics as T
+    from .index import ShardIndex
+    from .retrieval import RowFilters
+    metadata = [c.get("metadata") or {} for c in chunks]
+    filters = RowFilters(metadata, shard.rows.device, keep_mask=keep_mask, texts=lambda: [c.get("text") or "" for c in chunks],
+                         where_on_device=where_on_device, document_regex=document_regex)
+    allow, _ = filters.allow_of(where, where_document)
+    res = T.fit_shard(ShardIndex(shard.rows, idx_base=0), allow, n_topics, iters=iters, seed=seed, representatives=representatives)
+    out = {"n_topics": int(n_topics), "iters": int(iters), "seed": int(seed), "sizes": res["sizes"].tolist(), "objective": res["objective"],
+           "iterations": res["iterations"],
+           "representatives": [[chunks[int(r)].get("chunk_id", f"chunk_{shard.lo + int(r)}") for r in rows if r >= 0] for rows in res["rep_rows"]]}
+    with open(Path(output_dir) / "topics.json", "w", encoding="utf-8") as fh:
+        json.dump(out, fh, indent=2, ensure_ascii=False)
+    print(f"✅ {n_topics} topics over {int(res['sizes'].sum())} chunks written to {Path(output_dir) / 'topics.json'}")
+    return out
 
 
 def facet_counts(chunks: List[Dict], device, keys: Sequence[str], top: int = 10, where=None, where_document: Optional[Dict] = None, *,
@@ -1266,7 +1313,7 @@ def main(argv: Optional[Sequence[str]] = None, model_factory: Optional[Callable]
     args = build_parser().parse_args(argv)
     err = (check_rerank_args(args) or check_hybrid_args(args) or check_hybrid_filters_args(args) or check_hybrid_device_args(args) or check_keyword_build_args(args) or check_where_args(args) or check_where_file_args(args) or check_where_device_args(args)
            or check_where_document_args(args)
-           or check_mmr_args(args) or check_dedup_args(args) or check_group_args(args) or check_range_args(args) or check_facets_args(args))
+           or check_mmr_args(args) or check_dedup_args(args) or check_group_args(args) or check_range_args(args) or check_facets_args(args) or check_topics_args(args))
     if err:
         print(f"Error: {err}")
         return 2
@@ -1375,6 +1422,10 @@ def main(argv: Optional[Sequence[str]] = None, model_factory: Optional[Callable]
                                  where=args.where_filters if args.where_filters is not None else args.where_filter,
                                  where_document=args.where_document_filter, keep_mask=keep_mask, where_on_device=args.where_on_device,
                                  document_regex=args.where_document_regex)
+                if args.topics is not None:
+                    topic_clusters(chunks, sink, args.topics, args.topics_iters, args.topics_seed, where=args.where_filter,
+                                   where_document=args.where_document_filter, keep_mask=keep_mask, where_on_device=args.where_on_device,
+                                   document_regex=args.where_document_regex)
         store_time = 0.0
         if rank == 0 and not args.skip_chroma:
             try:

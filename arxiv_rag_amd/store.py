@@ -448,6 +448,48 @@ class HipCollection:
         allow, _ = rf.allow_of(where, where_document)
         return F.count(self._columns(), specs, allow, top)[0]
 
+    def topics(self, n_topics: int, where=None, where_document=None, iters: int = 20, seed: int = 0, representatives: int = 3,
+               store_as: Optional[str] = None) -> Dict:
+        """Topic clustering (INTEGRATION.md "Topics"): spherical k-means (`topics.kmeans`) of the rows a query with these filters could
+        return, by their embeddings, on the device.  `where` / `where_document` are what `query` takes (single dicts), evaluated by the
+        same `retrieval.RowFilters`, the dedup and tombstone keep-bitmap and-ed in; with any of them the allowed rows are gathered once
+        (`arx_gather_rows`) into a buffer of their own and clustered as a collection built from them alone would be, bit for bit.
+        -> {labels, sizes, centroids, objective, iterations, representatives}: `labels` numpy int32 [rows of this collection], -1 for a
+        row that was not clustered; `sizes` [n_topics]; `centroids` f32 [n_topics, dim]; `objective` the mean cosine of a row to its
+        centroid; `iterations` the assigns run (at most `iters`; fewer once an assign changes no label); `representatives` per topic
+        the `representatives` (0..32) allowed rows nearest its centroid, from one exact `index.search(centroids_f16, k, allow=...)`
+        with its ordering rule, as `{ids, indices, scores, documents, labels}`: a representative is usually a member of its topic but
+        need not be, so its own label is given.  The default initial centroids are `n_topics` of the clustered rows chosen by
+        `numpy.random.default_rng(seed)`; of two identical rows among them the higher-numbered topic is empty in the first assign and
+        keeps its value (empty topics are not relocated).
+        `store_as` (a metadata key, e.g. "topic"): writes `metadata[r][store_as] = int(label)` for every clustered row, leaves the
+        others untouched and drops the metadata columns, so `facets(store_as)` and `query(where={store_as: 3})` see the topics.
+        Nothing else is kept.  ValueError before anything is launched: `world > 1` (a rank sees only its own rows); `representatives`
+        outside [0, 32]; `n_topics` outside [1, min(clustered rows, 4096)]; `iters < 1`; a dim that is not a multiple of 64."""
+        from . import topics as T
+        if getattr(self, "world", 1) > 1:
+            raise ValueError("topics needs world == 1: a rank sees only its own rows, and a multi-rank fit is out of scope")
+        T.check_representatives(representatives)
+        if store_as is not None and not isinstance(store_as, str):
+            raise ValueError(f"store_as={store_as!r} must be a metadata key name or None")
+        T.check_args(max(self.hi - self.lo, 1), self.dim, 1, iters)  # (dim and iters, before a filter is evaluated)
+        if where_document is not None:
+            self._documents()
+        allow, _ = self._row_filters().allow_of(where, where_document)
+        res = T.fit_shard(self.index, allow, n_topics, iters=iters, seed=seed, representatives=representatives)
+        labels, reps = res["labels"], []
+        for s, i in zip(res["rep_scores"], res["rep_rows"]):
+            found = [int(r) for r in i if r >= 0]
+            ms = [self.metadata[r] for r in found]
+            reps.append({"ids": [m.get("chunk_id", f"chunk_{r}") for m, r in zip(ms, found)], "indices": found, "scores": s[i >= 0].tolist(),
+                         "documents": [m.get("text") for m in ms], "labels": [int(labels[r - self.lo]) for r in found]})
+        if store_as is not None:
+            for r in np.nonzero(labels >= 0)[0].tolist():
+                self.metadata[self.lo + r][store_as] = int(labels[r])
+            self._drop_columns()
+        return {"labels": labels, "sizes": res["sizes"], "centroids": res["centroids"], "objective": res["objective"],
+                "iterations": res["iterations"], "representatives": reps}
+
     def query(self, query_embeddings=None, query_texts: Optional[Sequence[str]] = None, n_results: int = 10, reranker=None,
               n_candidates: int = 32, hybrid_alpha: Optional[float] = None, where=None, where_document=None,
               mmr_lambda: Optional[float] = None, group_by=None, chunks_per_group: int = 1, min_score=None) -> Dict:

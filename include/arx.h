@@ -615,6 +615,42 @@ int32_t arx_facet_count_tuned(const arx_facet_key* keys, int32_t n_keys, int64_t
                               int32_t* out, int64_t out_stride,
                               int32_t block_threads, int32_t blocks_x, int32_t lds_bins, void* stream);
 
+/* ---- Spherical k-means update over fp16 rows (csrc/cluster.hip; the host layer is arxiv_rag_amd/topics.py; INTEGRATION.md "Topics") ----
+ * The assign half of a Lloyd iteration is arx_topk_search with the centroids as the shard; these calls are the other half.
+ *   rows    device fp16 [n_rows, dim], 16-byte aligned
+ *   order   device int32 [n_members]: row numbers sorted by (cluster, row)
+ *   start   device int64 [C + 1]: cluster c owns order[start[c], start[c + 1])
+ *   sums    device f32 [C, dim]: S_c[d]; every element is written
+ * A cluster's members are cut into runs of 256 consecutive entries of `order`.  A run's partial starts at 0.0f and adds float(row[d])
+ * entry by entry in ascending position; S_c[d] starts at 0.0f and adds the cluster's partials in ascending run order; every add is a
+ * plain f32 add made by one thread.  The bits therefore depend on rows, order and start alone, never on the launch shape, and equal
+ * topics.sums_host (numpy.cumsum in f32 per run, then over the partials).  Two launches on `stream` (partials, then sums), no atomics,
+ * no host synchronisation, no workspace beyond the partials:
+ *   partials  device scratch of arx_cluster_sums_workspace_bytes(n_members, C, dim) = (ceil(n_members / 256) + C) * dim * 4 bytes,
+ *             16-byte aligned (-1 for arguments outside the contract below).
+ * ARX_ERR_ARG before anything is launched, the message naming the field: dim not a multiple of 64 in [64, 8192]; C outside
+ * [1, 4096]; n_rows or n_members outside [0, 2^31); a null or misaligned pointer; ws_bytes below the figure above.  n_members == 0 or
+ * n_rows == 0 zeroes `sums`.
+ * order and start are device data: an order entry outside [0, n_rows) keeps its place in its run and adds nothing; start values are
+ * clamped into [0, n_members] and made non-decreasing (a running maximum) before use.  Wrong data gives wrong sums, never a read or
+ * write outside the arrays passed. */
+int64_t arx_cluster_sums_workspace_bytes(int64_t n_members, int32_t C, int32_t dim);
+int32_t arx_cluster_sums(const void* rows, int64_t n_rows, int32_t dim, const int32_t* order, int64_t n_members, const int64_t* start,
+                         int32_t C, void* partials, int64_t ws_bytes, float* sums, void* stream);
+/* The same with the launch shape of the partials chosen: block_threads a multiple of 64 in 64..1024 (default 256), runs_per_block in
+ * 1..64 runs a block carries side by side (0 = default: the fewest that fill whole waves, doubled while they fit the block).  Same
+ * bits for every choice. */
+int32_t arx_cluster_sums_tuned(const void* rows, int64_t n_rows, int32_t dim, const int32_t* order, int64_t n_members, const int64_t* start,
+                               int32_t C, void* partials, int64_t ws_bytes, float* sums, int32_t block_threads, int32_t runs_per_block,
+                               void* stream);
+/* The new centroids from the sums: out_f32[c] = S_c / sqrtf(sum_d S_c[d]^2), out_f16 = that rounded to nearest even (device fp16
+ * [C, dim]).  The sum of squares has one fixed order: lane l of 64 adds S[d] * S[d] over d = l, l + 64, ... ascending (product rounded,
+ * then added), then v_l = v_l + v_(l ^ o) for o = 32, 16, 8, 4, 2, 1; sqrtf and the division are IEEE.  A cluster that is empty
+ * (start, clamped below at 0 and made non-decreasing, gives it no entry) or whose norm is 0 or not finite keeps prev[c] (device f32
+ * [C, dim]) bit for bit.  One launch, one wave per cluster.  Same contract for dim and C; a null pointer is ARX_ERR_ARG. */
+int32_t arx_cluster_finish(const float* sums, const int64_t* start, const float* prev, int32_t C, int32_t dim, float* out_f32,
+                           void* out_f16, void* stream);
+
 /* ---- MMR diversified re-ordering of a query's search candidates (csrc/mmr.hip; the definition is INTEGRATION.md "MMR") -----------
  * arx_gather_rows: out[s] (device fp16 [count, dim]) = shard row ids[s] - idx_base where that row lies in [0, n_rows), all zeros
  * otherwise (id -1, a row another rank owns: the ranks' buffers then add up to the rows, arxiv_rag_amd/mmr.py).  shard device fp16

@@ -161,10 +161,8 @@ __device__ __forceinline__ uint32_t tail_kth_key(TailStage& st, uint32_t (&kv)[F
     }
     __syncthreads();
     if (w == 0) {
-        float qq = 0.f;
-        for (int i = lane; i < D; i += 64) { const float v = (float)qs[i]; qq = fmaf(v, v, qq); }
-        qq = wave_sum(qq);
-        if (lane == 0) st.qn = sqrtf(qq);
+        const float qn = wave_query_norm(qs, D, lane);
+        if (lane == 0) st.qn = qn;
     }
     uint32_t T = 0u;
     for (int bit = 31; bit >= 0; --bit) {
@@ -263,10 +261,8 @@ __global__ __launch_bounds__(FILT_TAIL_NT) void masked_tail_kernel(const float* 
     }
     __syncthreads();
     if (w == 0) {
-        float qq = 0.f;
-        for (int i = lane; i < D; i += 64) { const float v = (float)qs[i]; qq = fmaf(v, v, qq); }
-        qq = wave_sum(qq);
-        if (lane == 0) st.qn = sqrtf(qq);
+        const float qn = wave_query_norm(qs, D, lane);
+        if (lane == 0) st.qn = qn;
     }
     uint32_t T = 0u;                                           // -> the k-th largest group maximum
     for (int bit = 31; bit >= 0; --bit) {

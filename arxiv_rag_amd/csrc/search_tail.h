@@ -1,5 +1,9 @@
 // What follows pass A in arx_topk_* (search.hip): group selection, exact fp32 rescoring with the exactness certificate, the single-kernel
 // tails (fp16 aux words / int8 pipeline on small shards), the int8 candidate pipeline of large shards, the merge of per-shard partials.
+// The stages rescore_kernel and tail_single_kernel share are functions above them, each written once: wave_partial_lists,
+// wave0_best_groups, wave_query_norm, wave_group_rows_topk, wave0_merge_topk, certificate_threshold / certificate_open, write_topk_list,
+// write_collect_state, certificate_fallback (tail_single_kernel keeps the fallback's text written out beside the call-free form, for its
+// speed); the int8 candidate steps share append_survivor, group_survivors, survivors_topk.
 // Included by search.hip after search_pass_a.h; not a stand-alone header.
 #pragma once
 
@@ -174,6 +178,240 @@ __device__ __forceinline__ float exact_row_score(const f16_t* __restrict__ crow,
     return a;
 }
 
+// ---- the stages that rescore_kernel, tail_single_kernel and the int8 candidate kernels share, each written once -------------------------
+// Plain inlined functions: every kernel keeps its own body, LDS layout and barrier sequence and calls them.  A function that holds a
+// fence (s_waitcnt lgkmcnt(0)) or a __syncthreads() says so in its contract.  w_s / w_i are the kernels' per-wave lists [NW][KK].
+
+// Stage (1) from the select kernel's lists: wave w's contiguous share of the nslices * K partial super-groups (R per lane) -> its
+// top-(K+1) in ws / wi, and in *vbw the largest K-th kept value of its slices (whatever a slice dropped scores <= that).  No fence.
+template <int K, int R>
+__device__ __forceinline__ void wave_partial_lists(const float* __restrict__ part_s, const int32_t* __restrict__ part_g, int nslices, int64_t ldg,
+                                                   int q, int w, int lane, float* ws, int64_t* wi, float* vbw) {
+    const int ncand = nslices * K;
+    float s[R]; int64_t id[R];
+    float vb = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+        const int i = (w * R + j) * 64 + lane;             // wave w owns a contiguous range
+        s[j] = -INFINITY; id[j] = -1;
+        if (i < ncand) {
+            const int sl = i / K, p = i - sl * K;
+            const int64_t o = ((int64_t)sl * ldg + q) * K + p;
+            s[j] = part_s[o]; id[j] = part_g[o];
+            if (p == K - 1 && id[j] >= 0) vb = fmaxf(vb, s[j]);
+        }
+    }
+    wave_topk<R>(s, id, K + 1, lane, ws, wi);
+    vb = wave_max(vb);
+    if (lane == 0) *vbw = vb;
+}
+
+// Wave 0, end of stage (1) and stage (2): the waves' NW * (K+1) super-groups -> the K best + the best one left out (in gs / gi_[0..K],
+// scratch here); those expanded to K * SUPER groups (their gmax) -> the K best groups in w_s / w_i[0][0..K), the best one left out in
+// [K].  Returns U so far: the best super-group and group left out and the slices' bounds w_vb.  RESET: gs / gi_[0..K] are "empty" again
+// before the lists of wave 0 are written.  Holds fences; the last one follows the write of w_s / w_i[0].
+template <int K, bool RESET, int NW, int KK>
+__device__ __forceinline__ float wave0_best_groups(float (&w_s)[NW][KK], int64_t (&w_i)[NW][KK], const float (&w_vb)[NW], float* gs, int64_t* gi_,
+                                                   const float* __restrict__ gmax, int64_t ldg, int64_t n_groups, int q, int lane) {
+    constexpr int K1 = K + 1;
+    constexpr int R2 = (NW * K1 + 63) / 64;
+    float s[R2]; int64_t id[R2];
+#pragma unroll
+    for (int j = 0; j < R2; ++j) {
+        const int i = j * 64 + lane;
+        s[j] = i < NW * K1 ? w_s[i / K1][i % K1] : -INFINITY;
+        id[j] = i < NW * K1 ? w_i[i / K1][i % K1] : -1;
+    }
+    wave_topk<R2>(s, id, K1, lane, gs, gi_);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    float u = gi_[K] >= 0 ? gs[K] : -INFINITY;
+#pragma unroll
+    for (int ww = 0; ww < NW; ++ww) u = fmaxf(u, w_vb[ww]);
+    constexpr int R3 = (K * SUPER + 63) / 64;
+    float s3[R3]; int64_t id3[R3];
+#pragma unroll
+    for (int j = 0; j < R3; ++j) {
+        const int i = j * 64 + lane;
+        s3[j] = -INFINITY; id3[j] = -1;
+        if (i < K * SUPER) {
+            const int64_t sg = gi_[i / SUPER];
+            const int64_t g = sg * SUPER + (i % SUPER);
+            if (sg >= 0 && g < n_groups) { s3[j] = gmax[g * ldg + q]; id3[j] = g; }
+        }
+    }
+    if constexpr (RESET) {
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        if (lane <= K) { gs[lane] = -INFINITY; gi_[lane] = -1; }
+    }
+    wave_topk<R3>(s3, id3, K1, lane, w_s[0], w_i[0]);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    if (w_i[0][K] >= 0) u = fmaxf(u, w_s[0][K]);
+    return u;
+}
+
+// |q|_2 of the query row staged in LDS, for the certificate's tolerance: called by one whole wave, every lane gets the value.
+__device__ __forceinline__ float wave_query_norm(const f16_t* qs, int D, int lane) {
+    float qq = 0.f;
+    for (int i = lane; i < D; i += 64) { const float v = (float)qs[i]; qq = fmaf(v, v, qq); }
+    return sqrtf(wave_sum(qq));
+}
+
+// Stage (3), second half: wave w's top-k of the rows of its groups w, w + NW, ... (gs / gi_: K x 64 row scores / ids, one row per lane)
+// into ws / wi.  No fence.
+template <int K, int NW>
+__device__ __forceinline__ void wave_group_rows_topk(const float* gs, const int64_t* gi_, int k, int w, int lane, float* ws, int64_t* wi) {
+    constexpr int GPW = (K + NW - 1) / NW;
+    float s[GPW]; int64_t id[GPW];
+#pragma unroll
+    for (int gq = 0; gq < GPW; ++gq) {
+        const int gidx = w + gq * NW;
+        s[gq] = gidx < K ? gs[gidx * GROUP_ROWS + lane] : -INFINITY;
+        id[gq] = gidx < K ? gi_[gidx * GROUP_ROWS + lane] : -1;
+    }
+    wave_topk<GPW>(s, id, k, lane, ws, wi);
+}
+
+// Stage (4), wave 0: the waves' NW * k rows -> the k best, sorted, in gs / gi_[0..k).  Ends with the fence that makes them readable.
+template <int NW, int KK>
+__device__ __forceinline__ void wave0_merge_topk(const float (&w_s)[NW][KK], const int64_t (&w_i)[NW][KK], int k, int lane, float* gs, int64_t* gi_) {
+    constexpr int R4 = (NW * KMAX + 63) / 64;
+    float s[R4]; int64_t id[R4];
+#pragma unroll
+    for (int j = 0; j < R4; ++j) {
+        const int i = j * 64 + lane;
+        const int iw = i / k, ip = i - iw * k;
+        s[j] = i < NW * k ? w_s[iw][ip] : -INFINITY;
+        id[j] = i < NW * k ? w_i[iw][ip] : -1;
+    }
+    wave_topk<R4>(s, id, k, lane, gs, gi_);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+}
+
+// Stage (5): the certificate's threshold s_k - tau of a sorted list (-inf while it holds fewer than k rows), and its test: does U, the
+// bound of every row not scored, reach the threshold (then something unscored might belong to the top-k)?
+__device__ __forceinline__ float certificate_threshold(const float* s, const int64_t* id, int k, float tau_scale, float qn) {
+    return id[k - 1] >= 0 ? s[k - 1] - tau_scale * qn : -INFINITY;
+}
+__device__ __forceinline__ bool certificate_open(float u, float thr) { return u > -INFINITY && u >= thr; }
+
+// A final sorted list (shard-local ids, -1 = empty) -> query q's row of the output: ids + idx_base, empty slots stay -1.
+__device__ __forceinline__ void write_topk_list(float* __restrict__ out_s, int64_t* __restrict__ out_i, int q, int k, int lane,
+                                                const float* s, const int64_t* id, int64_t idx_base) {
+    if (lane < k) {
+        out_s[(int64_t)q * k + lane] = s[lane];
+        out_i[(int64_t)q * k + lane] = id[lane] >= 0 ? id[lane] + idx_base : -1;
+    }
+}
+
+// COLLECT, wave 0: query q's state for collect_pairs / pair_rescore / merge_survivors (no separate memset launch): its threshold, its
+// candidate counters at zero (query 0: the two global ones as well), the K selected groups.
+template <int K>
+__device__ __forceinline__ void write_collect_state(float* __restrict__ thr_out, int32_t* __restrict__ selg_out, int* __restrict__ cand_counters,
+                                                    int* __restrict__ cand_nsurv, int q, int lane, float thr, const int32_t (&sel_g)[K]) {
+    if (lane == 0) {
+        thr_out[q] = thr;
+        cand_counters[CNT_QCOUNT + q] = 0; cand_counters[CNT_QOVER + q] = 0; cand_nsurv[q] = 0;
+        if (q == 0) { cand_counters[0] = 0; cand_counters[1] = 0; }
+    }
+    if (lane < K) selg_out[q * K + lane] = sel_g[lane];
+}
+
+// CERTIFICATE FALLBACK, the whole block: every group whose pass-A maximum reaches thr and that is not one of the K selected groups is
+// rescored in full (a wave per group, 8 lanes per row), each wave keeps a running top-k that starts, in wave 0, from the sorted list in
+// gs / gi_[0..k); wave 0 merges and writes the answer; stats[0] += 1, stats[1] += groups rescored.  gs is scratch afterwards (one
+// 64-float row per wave: 3 K >= NW).  Holds two __syncthreads() (every thread of the block must call it) and fences.
+template <int K, int NW, int KK>
+__device__ __forceinline__ void certificate_fallback(float (&w_s)[NW][KK], int64_t (&w_i)[NW][KK], const int32_t (&sel_g)[K], float* gs, int64_t* gi_,
+                                                     float thr, const float* __restrict__ gmax, int64_t ldg, int64_t n_groups, int q,
+                                                     const f16_t* qs, const f16_t* __restrict__ C, int64_t n_rows, int D, int k,
+                                                     float* __restrict__ out_s, int64_t* __restrict__ out_i, int64_t idx_base,
+                                                     unsigned long long* __restrict__ stats, int w, int lane) {
+    const int nch = D >> 3, l8 = lane & 7, rsub = lane >> 3;
+    float cs = -INFINITY; int64_t ci = -1;                      // this wave's running top-k: entry `lane` (lanes >= k empty)
+    if (w == 0 && lane < k) { cs = gs[lane]; ci = gi_[lane]; }
+    __syncthreads();                                            // gs is scratch from here: one 64-float row per wave
+    float* sc = gs + w * GROUP_ROWS;
+    unsigned long long extra = 0;
+    for (int64_t g0 = (int64_t)w * 64; g0 < n_groups; g0 += (int64_t)NW * 64) {
+        const int64_t g = g0 + lane;
+        bool sus = g < n_groups && gmax[(g < n_groups ? g : 0) * ldg + q] >= thr;
+#pragma unroll 4
+        for (int j = 0; j < K; ++j) sus = sus && (sel_g[j] != (int32_t)g);
+        unsigned long long mask = __ballot(sus);
+        while (mask) {
+            const int b = __ffsll((long long)mask) - 1;
+            mask &= mask - 1;
+            const int64_t gsel = g0 + b;
+            ++extra;
+            for (int r8 = 0; r8 < GROUP_ROWS; r8 += 8) {
+                const int rr = r8 + rsub;
+                const int64_t row = gsel * GROUP_ROWS + rr;
+                const bool ok = row < n_rows;
+                const float a = exact_row_score(C + row * D, qs, nch, l8, ok);
+                if (l8 == 0) sc[rr] = ok ? a : -INFINITY;
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            const int64_t row = gsel * GROUP_ROWS + lane;
+            float s2[2] = {cs, sc[lane]};
+            int64_t i2[2] = {ci, row < n_rows ? row : -1};
+            wave_topk<2>(s2, i2, k, lane, w_s[w], w_i[w]);
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            cs = lane < k ? w_s[w][lane] : -INFINITY;
+            ci = lane < k ? w_i[w][lane] : -1;
+        }
+    }
+    if (lane < k) { w_s[w][lane] = cs; w_i[w][lane] = ci; }
+    __syncthreads();
+    if (w == 0) {
+        wave0_merge_topk(w_s, w_i, k, lane, gs, gi_);
+        write_topk_list(out_s, out_i, q, k, lane, gs, gi_, idx_base);
+    }
+    if (stats && lane == 0) {
+        if (w == 0) atomicAdd(&stats[0], 1ull);
+        if (extra) atomicAdd(&stats[1], extra);
+    }
+}
+
+// int8 candidates: one more survivor (exact score, row) of a list of SURV_CAP slots counted by *n (LDS or global); false = list full,
+// nothing written.
+__device__ __forceinline__ bool append_survivor(int* n, float* sv_s, int64_t* sv_i, float a, int64_t row) {
+    const int sl = atomicAdd(n, 1);
+    if (sl < SURV_CAP) { sv_s[sl] = a; sv_i[sl] = row; }
+    return sl < SURV_CAP;
+}
+
+// int8 candidates, one wave: the 64 rows of group g, 8 lanes per row and 8 rows per step; rows whose exact score is at or above thr join
+// the survivor list (append_survivor).  False if the list overflowed (in some lane: the caller decides what that means).
+__device__ __forceinline__ bool group_survivors(const f16_t* __restrict__ C, const f16_t* qrow, int64_t n_rows, int D, int64_t g, float thr,
+                                                int* n, float* sv_s, int64_t* sv_i) {
+    const int lane = threadIdx.x & 63, l8 = lane & 7, rsub = lane >> 3, nch = D >> 3;
+    bool fits = true;
+    for (int r8 = 0; r8 < GROUP_ROWS; r8 += 8) {
+        const int64_t row = g * GROUP_ROWS + r8 + rsub;
+        const bool ok = row < n_rows;
+        const float a = exact_row_score(C + (ok ? row : 0) * D, qrow, nch, l8, ok);
+        if (l8 == 0 && ok && a >= thr) fits = append_survivor(n, sv_s, sv_i, a, row) && fits;
+    }
+    return fits;
+}
+
+// int8 candidates, one wave: a query's n survivors and its provisional top-k (one candidate per lane: ps / pi, lanes >= k empty) ->
+// the final top-k, sorted, in os / oi (LDS).  Ends with the fence that makes them readable.
+__device__ __forceinline__ void survivors_topk(const float* sv_s, const int64_t* sv_i, int n, float ps, int64_t pi, int k, int lane,
+                                               float* os, int64_t* oi) {
+    constexpr int R = SURV_CAP / 64 + 1;
+    float s[R]; int64_t id[R];
+#pragma unroll
+    for (int j = 0; j < R - 1; ++j) {
+        const int i = j * 64 + lane;
+        s[j] = i < n ? sv_s[i] : -INFINITY;
+        id[j] = i < n ? sv_i[i] : -1;
+    }
+    s[R - 1] = ps; id[R - 1] = pi;
+    wave_topk<R>(s, id, k, lane, os, oi);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+}
+
 // pass B1 stage 2 + pass B2 + exactness certificate: one block of NT/64 waves per query.
 //   (1) each wave reduces its slice of the nslices*K partial super-groups to K+1, wave 0 reduces those to K+1: K selected
 //       super-groups + the best one left out
@@ -224,70 +462,21 @@ __global__ __launch_bounds__(NT) void rescore_kernel(const float* __restrict__ p
     for (int i = tid; i < (D >> 3); i += NT)
         reinterpret_cast<u32x4*>(qs)[i] = reinterpret_cast<const u32x4*>(Q + (int64_t)q * D)[i];
     // (1) partial super-groups -> K best (+ the best one left out)
-    {
-        const int ncand = nslices * K;
-        float s[R1]; int64_t id[R1];
-        float vb = -INFINITY;
-#pragma unroll
-        for (int j = 0; j < R1; ++j) {
-            const int i = (w * R1 + j) * 64 + lane;            // wave w owns a contiguous range
-            s[j] = -INFINITY; id[j] = -1;
-            if (i < ncand) {
-                const int sl = i / K, p = i - sl * K;
-                const int64_t o = ((int64_t)sl * ldg + q) * K + p;
-                s[j] = part_s[o]; id[j] = part_g[o];
-                if (p == K - 1 && id[j] >= 0) vb = fmaxf(vb, s[j]);     // whatever this slice dropped scores <= its K-th kept value
-            }
-        }
-        wave_topk<R1>(s, id, K1, lane, w_s[w], w_i[w]);
-        vb = wave_max(vb);
-        if (lane == 0) w_vb[w] = vb;
-    }
+    wave_partial_lists<K, R1>(part_s, part_g, nslices, ldg, q, w, lane, w_s[w], w_i[w], &w_vb[w]);
     __syncthreads();
     if (w == 0) {
-        constexpr int R2 = (NW * K1 + 63) / 64;
-        float s[R2]; int64_t id[R2];
-#pragma unroll
-        for (int j = 0; j < R2; ++j) {
-            const int i = j * 64 + lane;
-            s[j] = i < NW * K1 ? w_s[i / K1][i % K1] : -INFINITY;
-            id[j] = i < NW * K1 ? w_i[i / K1][i % K1] : -1;
-        }
-        wave_topk<R2>(s, id, K1, lane, gs, gi_);               // K best super-groups -> gs/gi_[0..K), best left out -> [K]
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        float u = gi_[K] >= 0 ? gs[K] : -INFINITY;
-#pragma unroll
-        for (int ww = 0; ww < NW; ++ww) u = fmaxf(u, w_vb[ww]);
         // (2) expand to K*SUPER groups, reduce to the K best groups (+ the best one left out)
-        constexpr int R3 = (K * SUPER + 63) / 64;
-        float s3[R3]; int64_t id3[R3];
-#pragma unroll
-        for (int j = 0; j < R3; ++j) {
-            const int i = j * 64 + lane;
-            s3[j] = -INFINITY; id3[j] = -1;
-            if (i < K * SUPER) {
-                const int64_t sg = gi_[i / SUPER];
-                const int64_t g = sg * SUPER + (i % SUPER);
-                if (sg >= 0 && g < n_groups) { s3[j] = gmax[g * ldg + q]; id3[j] = g; }
-            }
-        }
-        wave_topk<R3>(s3, id3, K1, lane, w_s[0], w_i[0]);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if (w_i[0][K] >= 0) u = fmaxf(u, w_s[0][K]);
+        float u = wave0_best_groups<K, false>(w_s, w_i, w_vb, gs, gi_, gmax, ldg, n_groups, q, lane);
         // test hook (ARX_TOPK_DEBUG_DROP): forget the best group, as if selection had missed it; the certificate must recover it
         if (debug_drop && w_i[0][0] >= 0) u = fmaxf(u, w_s[0][0]);
         if (lane < K) sel_g[lane] = !debug_drop ? (int32_t)w_i[0][lane] : (lane + 1 < K ? (int32_t)w_i[0][lane + 1] : -1);
-        // |q|_2 for the certificate's tolerance
-        float qq = 0.f;
-        for (int i = lane; i < D; i += 64) { const float v = (float)qs[i]; qq = fmaf(v, v, qq); }
-        qq = wave_sum(qq);
-        if (lane == 0) { sh_u = u; sh_qn = sqrtf(qq); }
+        const float qn = wave_query_norm(qs, D, lane);          // |q|_2 for the certificate's tolerance
+        if (lane == 0) { sh_u = u; sh_qn = qn; }
     }
     __syncthreads();
     // (3) exact scores: 8 lanes per corpus row, 8 rows per wave and step; the K x 64 rows are dealt to ALL the block's waves (a 16-wave
     // block scores its 768 rows in 6 steps; one group per wave left four waves idle for 8)
     const int nch = D >> 3, l8 = lane & 7, rsub = lane >> 3;
-    constexpr int GPW = (K + NW - 1) / NW;                    // groups per wave in the per-wave top-k below
     for (int t0 = w * 8; t0 < K * GROUP_ROWS; t0 += NW * 8) {
         const int t = t0 + rsub, gidx = t >> 6, rr = t & 63;
         const int gsel = sel_g[gidx];
@@ -298,108 +487,22 @@ __global__ __launch_bounds__(NT) void rescore_kernel(const float* __restrict__ p
     }
     __syncthreads();
     // each wave: top-k of the rows of its groups (read back one row per lane)
-    {
-        float s[GPW]; int64_t id[GPW];
-#pragma unroll
-        for (int gq = 0; gq < GPW; ++gq) {
-            const int gidx = w + gq * NW;
-            s[gq] = gidx < K ? gs[gidx * GROUP_ROWS + lane] : -INFINITY;
-            id[gq] = gidx < K ? gi_[gidx * GROUP_ROWS + lane] : -1;
-        }
-        wave_topk<GPW>(s, id, k, lane, w_s[w], w_i[w]);
-    }
+    wave_group_rows_topk<K, NW>(gs, gi_, k, w, lane, w_s[w], w_i[w]);
     __syncthreads();
     // (4) NW*k -> k, (5) certificate
     if (w == 0) {
-        constexpr int R4 = (NW * KMAX + 63) / 64;
-        float s[R4]; int64_t id[R4];
-#pragma unroll
-        for (int j = 0; j < R4; ++j) {
-            const int i = j * 64 + lane;
-            s[j] = i < NW * k ? w_s[i / k][i % k] : -INFINITY;
-            id[j] = i < NW * k ? w_i[i / k][i % k] : -1;
-        }
-        wave_topk<R4>(s, id, k, lane, gs, gi_);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        const bool full = gi_[k - 1] >= 0;                    // k rows found
-        const float thr = full ? gs[k - 1] - tau_scale * sh_qn : -INFINITY;
+        wave0_merge_topk(w_s, w_i, k, lane, gs, gi_);
+        const float thr = certificate_threshold(gs, gi_, k, tau_scale, sh_qn);
         const bool collect = thr_out != nullptr;
-        const bool flag = !collect && sh_u > -INFINITY && sh_u >= thr;     // something unscored might belong to the top-k
+        const bool flag = !collect && certificate_open(sh_u, thr);          // something unscored might belong to the top-k
         if (lane == 0) { sh_flag = flag ? 1 : 0; sh_thr = thr; }
-        if (!flag && lane < k) {
-            out_s[(int64_t)q * k + lane] = gs[lane];
-            out_i[(int64_t)q * k + lane] = gi_[lane] >= 0 ? gi_[lane] + idx_base : -1;
-        }
-        if (collect) {
-            if (lane == 0) {
-                thr_out[q] = thr;
-                // this query's candidate state for the steps that follow (no separate memset launch)
-                cand_counters[CNT_QCOUNT + q] = 0; cand_counters[CNT_QOVER + q] = 0; cand_nsurv[q] = 0;
-                if (q == 0) { cand_counters[0] = 0; cand_counters[1] = 0; }
-            }
-            if (lane < K) selg_out[q * K + lane] = sel_g[lane];
-        }
+        if (!flag) write_topk_list(out_s, out_i, q, k, lane, gs, gi_, idx_base);
+        if (collect) write_collect_state<K>(thr_out, selg_out, cand_counters, cand_nsurv, q, lane, thr, sel_g);
     }
     __syncthreads();
     if (!sh_flag) return;                                       // block-uniform
-
-    // ---- certificate fallback: rescoring every unscored group whose pass-A maximum reaches the threshold -----------------
-    float cs = -INFINITY; int64_t ci = -1;                      // this wave's running top-k: entry `lane` (lanes >= k empty)
-    if (w == 0 && lane < k) { cs = gs[lane]; ci = gi_[lane]; }
-    __syncthreads();                                            // gs is scratch from here: one 64-float row per wave
-    float* sc = gs + w * GROUP_ROWS;
-    const float thr = sh_thr;
-    unsigned long long extra = 0;
-    for (int64_t g0 = (int64_t)w * 64; g0 < n_groups; g0 += (int64_t)NW * 64) {
-        const int64_t g = g0 + lane;
-        bool sus = g < n_groups && gmax[(g < n_groups ? g : 0) * ldg + q] >= thr;
-#pragma unroll 4
-        for (int j = 0; j < K; ++j) sus = sus && (sel_g[j] != (int32_t)g);
-        unsigned long long mask = __ballot(sus);
-        while (mask) {
-            const int b = __ffsll((long long)mask) - 1;
-            mask &= mask - 1;
-            const int64_t gsel = g0 + b;
-            ++extra;
-            for (int r8 = 0; r8 < GROUP_ROWS; r8 += 8) {
-                const int rr = r8 + rsub;
-                const int64_t row = gsel * GROUP_ROWS + rr;
-                const bool ok = row < n_rows;
-                const float a = exact_row_score(C + row * D, qs, nch, l8, ok);
-                if (l8 == 0) sc[rr] = ok ? a : -INFINITY;
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            const int64_t row = gsel * GROUP_ROWS + lane;
-            float s2[2] = {cs, sc[lane]};
-            int64_t i2[2] = {ci, row < n_rows ? row : -1};
-            wave_topk<2>(s2, i2, k, lane, w_s[w], w_i[w]);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            cs = lane < k ? w_s[w][lane] : -INFINITY;
-            ci = lane < k ? w_i[w][lane] : -1;
-        }
-    }
-    if (lane < k) { w_s[w][lane] = cs; w_i[w][lane] = ci; }
-    __syncthreads();
-    if (w == 0) {
-        constexpr int R4 = (NW * KMAX + 63) / 64;
-        float s[R4]; int64_t id[R4];
-#pragma unroll
-        for (int j = 0; j < R4; ++j) {
-            const int i = j * 64 + lane;
-            s[j] = i < NW * k ? w_s[i / k][i % k] : -INFINITY;
-            id[j] = i < NW * k ? w_i[i / k][i % k] : -1;
-        }
-        wave_topk<R4>(s, id, k, lane, gs, gi_);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if (lane < k) {
-            out_s[(int64_t)q * k + lane] = gs[lane];
-            out_i[(int64_t)q * k + lane] = gi_[lane] >= 0 ? gi_[lane] + idx_base : -1;
-        }
-    }
-    if (stats && lane == 0) {
-        if (w == 0) atomicAdd(&stats[0], 1ull);
-        if (extra) atomicAdd(&stats[1], extra);
-    }
+    // every unscored group whose pass-A maximum reaches the threshold is rescored
+    certificate_fallback<K>(w_s, w_i, sel_g, gs, gi_, sh_thr, gmax, ldg, n_groups, q, qs, C, n_rows, D, k, out_s, out_i, idx_base, stats, w, lane);
 }
 
 // ---- the tail of a SMALL query batch on the fp16 pass (<= 128 queries; pass A wrote the aux words): ONE kernel, one block per query ------
@@ -486,23 +589,7 @@ __global__ __launch_bounds__(NT) void tail_single_kernel(const float* __restrict
         wave_argbest(bs, bg);
         if (lane == 0) { w_s[w][0] = bs; w_i[w][0] = bg == INT64_MAX ? -1 : bg; w_vb[w] = -INFINITY; }
     } else if constexpr (!INBLOCK) {
-        const int ncand = nslices * K;
-        float s[RS]; int64_t id[RS];
-        float vb = -INFINITY;
-#pragma unroll
-        for (int j = 0; j < RS; ++j) {
-            const int i = (w * RS + j) * 64 + lane;
-            s[j] = -INFINITY; id[j] = -1;
-            if (i < ncand) {
-                const int sl = i / K, pp = i - sl * K;
-                const int64_t o = ((int64_t)sl * ldg + q) * K + pp;
-                s[j] = part_s[o]; id[j] = part_g[o];
-                if (pp == K - 1 && id[j] >= 0) vb = fmaxf(vb, s[j]);       // whatever this slice dropped scores <= its K-th kept value
-            }
-        }
-        wave_topk<RS>(s, id, K1, lane, w_s[w], w_i[w]);
-        vb = wave_max(vb);
-        if (lane == 0) w_vb[w] = vb;
+        wave_partial_lists<K, RS>(part_s, part_g, nslices, ldg, q, w, lane, w_s[w], w_i[w], &w_vb[w]);
     } else {
         if (lane == 0) w_vb[w] = -INFINITY;
         const int64_t n_super = (n_groups + SUPER - 1) / SUPER;
@@ -550,38 +637,8 @@ __global__ __launch_bounds__(NT) void tail_single_kernel(const float* __restrict
         if (mg >= 0 && better < K1) { w_s[0][better] = my; w_i[0][better] = mg; }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       } else {
-        constexpr int R2 = (NW * K1 + 63) / 64;
-        float s[R2]; int64_t id[R2];
-#pragma unroll
-        for (int j = 0; j < R2; ++j) {
-            const int i = j * 64 + lane;
-            s[j] = i < NW * K1 ? w_s[i / K1][i % K1] : -INFINITY;
-            id[j] = i < NW * K1 ? w_i[i / K1][i % K1] : -1;
-        }
-        wave_topk<R2>(s, id, K1, lane, gs, gi_);               // K best super-groups -> gs/gi_[0..K), best left out -> [K]
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        u = gi_[K] >= 0 ? gs[K] : -INFINITY;
-#pragma unroll
-        for (int ww = 0; ww < NW; ++ww) u = fmaxf(u, w_vb[ww]);
-        // (2) expand to K*SUPER groups, reduce to the K best groups (+ the best one left out)
-        constexpr int R3 = (K * SUPER + 63) / 64;
-        float s3[R3]; int64_t id3[R3];
-#pragma unroll
-        for (int j = 0; j < R3; ++j) {
-            const int i = j * 64 + lane;
-            s3[j] = -INFINITY; id3[j] = -1;
-            if (i < K * SUPER) {
-                const int64_t sg = gi_[i / SUPER];
-                const int64_t g = sg * SUPER + (i % SUPER);
-                if (sg >= 0 && g < n_groups) { s3[j] = gmax[g * ldg + q]; id3[j] = g; }
-            }
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        // gs / gi_[0..K] were scratch for the super-group list: back to "empty" before the candidates go in
-        if (lane <= K) { gs[lane] = -INFINITY; gi_[lane] = -1; }
-        wave_topk<R3>(s3, id3, K1, lane, w_s[0], w_i[0]);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if (w_i[0][K] >= 0) u = fmaxf(u, w_s[0][K]);
+        // (2) as rescore_kernel; gs / gi_[0..K], scratch for the super-group list, are back to "empty" before the candidates go in
+        u = wave0_best_groups<K, true>(w_s, w_i, w_vb, gs, gi_, gmax, ldg, n_groups, q, lane);
       }
         if (debug_drop && w_i[0][0] >= 0) u = fmaxf(u, w_s[0][0]);
         if (lane < K) {
@@ -599,10 +656,8 @@ __global__ __launch_bounds__(NT) void tail_single_kernel(const float* __restrict
             }
             sel_row[lane] = row; sel_ub2[lane] = ub2;
         }
-        float qq = 0.f;
-        for (int i = lane; i < D; i += 64) { const float v = (float)qs[i]; qq = fmaf(v, v, qq); }
-        qq = wave_sum(qq);
-        if (lane == 0) { sh_u = u; sh_qn = sqrtf(qq); }
+        const float qn = wave_query_norm(qs, D, lane);
+        if (lane == 0) { sh_u = u; sh_qn = qn; }
     }
     __syncthreads();
     // (3a) the K candidate blocks (CW rows each), exactly
@@ -645,16 +700,9 @@ __global__ __launch_bounds__(NT) void tail_single_kernel(const float* __restrict
                 out_i[(int64_t)q * k + better] = mi + idx_base;
             }
             if (lane >= nvalid && lane < k) { out_s[(int64_t)q * k + lane] = -INFINITY; out_i[(int64_t)q * k + lane] = -1; }
-            const bool flag = !COLLECT && !I8D && sh_u > -INFINITY && sh_u >= thr0;
+            const bool flag = !COLLECT && !I8D && certificate_open(sh_u, thr0);
             if (lane == 0) { sh_flag = flag ? 1 : 0; sh_thr = thr0; }
-            if constexpr (COLLECT) {
-                if (lane == 0) {
-                    thr_out[q] = thr0;
-                    cand_counters[CNT_QCOUNT + q] = 0; cand_counters[CNT_QOVER + q] = 0; cand_nsurv[q] = 0;
-                    if (q == 0) { cand_counters[0] = 0; cand_counters[1] = 0; }
-                }
-                if (lane < K) selg_out[q * K + lane] = sel_g[lane];
-            }
+            if constexpr (COLLECT) write_collect_state<K>(thr_out, selg_out, cand_counters, cand_nsurv, q, lane, thr0, sel_g);
             if (flag || I8D) {                                   // the fallback / the candidate pass start from the sorted list in gs / gi_[0..k)
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 if (lane < NC) { gs[cg * GROUP_ROWS + lane % CW] = -INFINITY; gi_[cg * GROUP_ROWS + lane % CW] = -1; }
@@ -675,45 +723,15 @@ __global__ __launch_bounds__(NT) void tail_single_kernel(const float* __restrict
             if (l8 == 0) { gs[gidx * GROUP_ROWS + rr] = ok ? a : -INFINITY; gi_[gidx * GROUP_ROWS + rr] = ok ? row : -1; }
         }
         __syncthreads();
-        constexpr int GPW = (K + NW - 1) / NW;
-        {
-            float s[GPW]; int64_t id[GPW];
-#pragma unroll
-            for (int gq = 0; gq < GPW; ++gq) {
-                const int gidx = w + gq * NW;
-                s[gq] = gidx < K ? gs[gidx * GROUP_ROWS + lane] : -INFINITY;
-                id[gq] = gidx < K ? gi_[gidx * GROUP_ROWS + lane] : -1;
-            }
-            wave_topk<GPW>(s, id, k, lane, w_s[w], w_i[w]);
-        }
+        wave_group_rows_topk<K, NW>(gs, gi_, k, w, lane, w_s[w], w_i[w]);
         __syncthreads();
         if (w == 0) {
-            constexpr int R4 = (NW * KMAX + 63) / 64;
-            float s[R4]; int64_t id[R4];
-#pragma unroll
-            for (int j = 0; j < R4; ++j) {
-                const int i = j * 64 + lane;
-                s[j] = i < NW * k ? w_s[i / k][i % k] : -INFINITY;
-                id[j] = i < NW * k ? w_i[i / k][i % k] : -1;
-            }
-            wave_topk<R4>(s, id, k, lane, gs, gi_);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            const bool full = gi_[k - 1] >= 0;
-            const float thr = full ? gs[k - 1] - tau_scale * sh_qn : -INFINITY;
-            const bool flag = !COLLECT && !I8D && sh_u > -INFINITY && sh_u >= thr;
+            wave0_merge_topk(w_s, w_i, k, lane, gs, gi_);
+            const float thr = certificate_threshold(gs, gi_, k, tau_scale, sh_qn);
+            const bool flag = !COLLECT && !I8D && certificate_open(sh_u, thr);
             if (lane == 0) { sh_flag = flag ? 1 : 0; sh_thr = thr; }
-            if (!flag && lane < k) {
-                out_s[(int64_t)q * k + lane] = gs[lane];
-                out_i[(int64_t)q * k + lane] = gi_[lane] >= 0 ? gi_[lane] + idx_base : -1;
-            }
-            if constexpr (COLLECT) {
-                if (lane == 0) {
-                    thr_out[q] = thr;
-                    cand_counters[CNT_QCOUNT + q] = 0; cand_counters[CNT_QOVER + q] = 0; cand_nsurv[q] = 0;
-                    if (q == 0) { cand_counters[0] = 0; cand_counters[1] = 0; }
-                }
-                if (lane < K) selg_out[q * K + lane] = sel_g[lane];
-            }
+            if (!flag) write_topk_list(out_s, out_i, q, k, lane, gs, gi_, idx_base);
+            if constexpr (COLLECT) write_collect_state<K>(thr_out, selg_out, cand_counters, cand_nsurv, q, lane, thr, sel_g);
         }
         __syncthreads();
     }
@@ -759,43 +777,15 @@ __global__ __launch_bounds__(NT) void tail_single_kernel(const float* __restrict
                 const bool ok = p0 < nr;
                 const int64_t row = (int64_t)lrow[ok ? p0 : 0];
                 const float a = exact_row_score(C + row * D, qs, nch, l8, ok);
-                if (l8 == 0 && ok && a >= thr) {
-                    const int sl = atomicAdd(&n_s, 1);
-                    if (sl < SURV_CAP) { sv_s[sl] = a; sv_i[sl] = row; } else ovf = 1;
-                }
+                if (l8 == 0 && ok && a >= thr && !append_survivor(&n_s, sv_s, sv_i, a, row)) ovf = 1;
             }
-            for (int p0 = w; p0 < ng; p0 += NW) {
-                const int64_t gg = (int64_t)lgrp[p0];
-                for (int r8 = 0; r8 < GROUP_ROWS; r8 += 8) {
-                    const int64_t row = gg * GROUP_ROWS + r8 + rsub;
-                    const bool ok = row < n_rows;
-                    const float a = exact_row_score(C + (ok ? row : 0) * D, qs, nch, l8, ok);
-                    if (l8 == 0 && ok && a >= thr) {
-                        const int sl = atomicAdd(&n_s, 1);
-                        if (sl < SURV_CAP) { sv_s[sl] = a; sv_i[sl] = row; } else ovf = 1;
-                    }
-                }
-            }
+            for (int p0 = w; p0 < ng; p0 += NW)
+                if (!group_survivors(C, qs, n_rows, D, (int64_t)lgrp[p0], thr, &n_s, sv_s, sv_i)) ovf = 1;
             __syncthreads();
             if (!ovf) {                                           // block-uniform
                 if (w == 0) {
-                    const int ns = n_s;
-                    constexpr int R = SURV_CAP / 64 + 1;
-                    float s[R]; int64_t id[R];
-#pragma unroll
-                    for (int j = 0; j < R - 1; ++j) {
-                        const int i = j * 64 + lane;
-                        s[j] = i < ns ? sv_s[i] : -INFINITY;
-                        id[j] = i < ns ? sv_i[i] : -1;
-                    }
-                    s[R - 1] = lane < k ? gs[lane] : -INFINITY;
-                    id[R - 1] = lane < k ? gi_[lane] : -1;
-                    wave_topk<R>(s, id, k, lane, w_s[0], w_i[0]);
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                    if (lane < k) {
-                        out_s[(int64_t)q * k + lane] = w_s[0][lane];
-                        out_i[(int64_t)q * k + lane] = w_i[0][lane] >= 0 ? w_i[0][lane] + idx_base : -1;
-                    }
+                    survivors_topk(sv_s, sv_i, n_s, lane < k ? gs[lane] : -INFINITY, lane < k ? gi_[lane] : -1, k, lane, w_s[0], w_i[0]);
+                    write_topk_list(out_s, out_i, q, k, lane, w_s[0], w_i[0], idx_base);
                     if (stats && lane == 0) atomicAdd(&stats[1], (unsigned long long)(nr + ng));
                 }
                 return;
@@ -805,9 +795,11 @@ __global__ __launch_bounds__(NT) void tail_single_kernel(const float* __restrict
     }
     if (COLLECT || (!I8D && !sh_flag)) return;                  // block-uniform
 
-    // ---- certificate fallback (as rescore_kernel's): every group whose pass-A maximum reaches the threshold and that is not among the K
-    // selected ones is rescored in full.  A selected group that was NOT expanded is skipped with them: its rows other than the arg-max
-    // row score below ub2 < thr' <= thr.  One that is needed after all (thr dropped? it cannot: s_k only grows) never arises.
+    // ---- certificate fallback: every group whose pass-A maximum reaches the threshold and that is not among the K selected ones is rescored
+    // in full.  A selected group that was NOT expanded is skipped with them: its rows other than the arg-max row score below
+    // ub2 < thr' <= thr.  One that is needed after all (thr dropped? it cannot: s_k only grows) never arises.
+    // The text of certificate_fallback, written out: called as the function, this kernel's common path ran 1 - 2 % slower
+    // (profiles/search_tail_refactor.md).  Keep the two texts the same.
     float cs = -INFINITY; int64_t ci = -1;
     if (w == 0 && lane < k) { cs = gs[lane]; ci = gi_[lane]; }
     __syncthreads();
@@ -954,10 +946,7 @@ __device__ __forceinline__ void row_candidates(const unsigned long long* __restr
         const int64_t row = (int64_t)(uint32_t)pr;
         const bool go = ok && !counters[CNT_QOVER + q];
         const float a = exact_row_score(C + row * D, Q + (int64_t)q * D, nch, l8, go);
-        if (l8 == 0 && go && a >= thr[q]) {
-            const int sidx = atomicAdd(&nsurv[q], 1);
-            if (sidx < SURV_CAP) { surv_s[q * SURV_CAP + sidx] = a; surv_i[q * SURV_CAP + sidx] = row; }
-        }
+        if (l8 == 0 && go && a >= thr[q]) append_survivor(&nsurv[q], surv_s + q * SURV_CAP, surv_i + q * SURV_CAP, a, row);
     }
 }
 
@@ -970,24 +959,13 @@ __global__ __launch_bounds__(256) void pair_rescore_kernel(const unsigned long l
                                                             const float* __restrict__ thr, float* __restrict__ surv_s,
                                                             int64_t* __restrict__ surv_i, int* __restrict__ nsurv) {
     row_candidates(rpairs, counters, Q, C, D, thr, surv_s, surv_i, nsurv);
-    const int lane = threadIdx.x & 63, l8 = lane & 7, rsub = lane >> 3, nch = D >> 3;
     const int np = counters[0];
     for (int p = blockIdx.x * 4 + (threadIdx.x >> 6); p < np; p += gridDim.x * 4) {
         const unsigned long long pr = pairs[p];
         const int q = (int)(pr >> 32);
         if (counters[CNT_QOVER + q]) continue;                    // this query goes to the exhaustive kernel anyway (wave-uniform)
         const int64_t g = (int64_t)(uint32_t)pr;
-        const float t = thr[q];
-        const f16_t* qrow = Q + (int64_t)q * D;
-        for (int r8 = 0; r8 < GROUP_ROWS; r8 += 8) {
-            const int64_t row = g * GROUP_ROWS + r8 + rsub;
-            const bool ok = row < n_rows;
-            const float a = exact_row_score(C + (ok ? row : 0) * D, qrow, nch, l8, ok);
-            if (l8 == 0 && ok && a >= t) {
-                const int sidx = atomicAdd(&nsurv[q], 1);
-                if (sidx < SURV_CAP) { surv_s[q * SURV_CAP + sidx] = a; surv_i[q * SURV_CAP + sidx] = row; }
-            }
-        }
+        group_survivors(C, Q + (int64_t)q * D, n_rows, D, g, thr[q], &nsurv[q], surv_s + q * SURV_CAP, surv_i + q * SURV_CAP);
     }
 }
 
@@ -1008,22 +986,10 @@ __global__ __launch_bounds__(256) void merge_survivors_kernel(float* __restrict_
         if (stats) { if (over) atomicAdd(&stats[0], 1ull); if (q == 0) atomicAdd(&stats[1], (unsigned long long)(counters[0] + counters[1])); }
     }
     if (over) return;
-    constexpr int R = SURV_CAP / 64 + 1;
-    float s[R]; int64_t id[R];
-#pragma unroll
-    for (int j = 0; j < R - 1; ++j) {
-        const int i = j * 64 + lane;
-        s[j] = i < n ? surv_s[q * SURV_CAP + i] : -INFINITY;
-        id[j] = i < n ? surv_i[q * SURV_CAP + i] : -1;
-    }
-    s[R - 1] = lane < k ? out_s[(int64_t)q * k + lane] : -INFINITY;
-    id[R - 1] = (lane < k && out_i[(int64_t)q * k + lane] >= 0) ? out_i[(int64_t)q * k + lane] - idx_base : -1;
-    wave_topk<R>(s, id, k, lane, ms[w], mi[w]);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if (lane < k) {
-        out_s[(int64_t)q * k + lane] = ms[w][lane];
-        out_i[(int64_t)q * k + lane] = mi[w][lane] >= 0 ? mi[w][lane] + idx_base : -1;
-    }
+    const float ps = lane < k ? out_s[(int64_t)q * k + lane] : -INFINITY;
+    const int64_t pi = (lane < k && out_i[(int64_t)q * k + lane] >= 0) ? out_i[(int64_t)q * k + lane] - idx_base : -1;
+    survivors_topk(surv_s + q * SURV_CAP, surv_i + q * SURV_CAP, n, ps, pi, k, lane, ms[w], mi[w]);
+    write_topk_list(out_s, out_i, q, k, lane, ms[w], mi[w], idx_base);
 }
 
 // merge P partial lists: one wave per query (n_parts*k candidates, k <= 32)

@@ -230,6 +230,12 @@ CASES = [
     dict(id="i8-above-crossover-k10", d=896, n=256 * 9 + 1, nq=100, k=10, pre="int8", i8max=64, rows="mixed", sel=0),
     dict(id="i8-kbig-1025q", d=1024, n=64 * 60 + 1, nq=1025, k=11, pre="int8", centre=True, rows="unit", sel=2),
     dict(id="i8-kbig-2049q", d=128, n=64 * 100 + 1, nq=2049, k=32, pre="int8", centre=False, base=1 << 33, rows="mixed", sel=3),
+    # int8 overflow exits: one unit row repeated, so every group's first and second bound is >= the true score = s_k > thr whatever the
+    # quantisation: more group candidates than I8D_CAP_GROUPS = 512 (the single tail's exhaustive exit), than PAIR_CAP_PER_QUERY = 4096
+    # (flagged by merge_survivors_kernel, re-run through tail_single_kernel<only_if> / rescore_kernel<only_if>)
+    dict(id="i8-single-dup-overflow", d=128, n=64 * 600, nq=3, k=10, pre="int8", centre=False, rows="dup", sel=0),
+    dict(id="i8-kbig-dup-redo", d=128, n=64 * 4200, nq=3, k=11, pre="int8", centre=False, rows="dup", sel=1),
+    dict(id="i8-pair-dup-redo", d=128, n=64 * 4200, nq=3, k=2, pre="int8", centre=False, flags=NO_ST, rows="dup", sel=1),
 ]
 
 
@@ -240,6 +246,8 @@ def _case_data(c):
         C_, q = _near_tied(d, n, g)
         q = torch.cat([q, _unit(nq - q.shape[0], d, g).half()]) if nq > q.shape[0] else q[:nq]
         return C_.contiguous(), q.contiguous()
+    if c["rows"] == "dup":
+        return _unit(1, d, g).half().repeat(n, 1).contiguous(), _queries(nq, d, g)
     if c["rows"] == "unit":
         C_ = _unit(n, d, g)
     elif c["rows"] == "tiny":
@@ -277,6 +285,9 @@ def test_search_dispatch_matrix_fp64_and_bitwise_equal_to_the_exhaustive_scan(hi
     fp16_pass = not c.get("pre") or c["nq"] > c.get("i8max", 1024)
     if fp16_pass and (C_.shape[0] + 63) // 64 > (12 if k <= 10 else 36):       # (a shard of no more groups than the selection keeps leaves none out)
         assert flagged >= 1, (c["id"], "the zero query took the fast path")
+    if c["rows"] == "dup":                                                          # every non-zero query overflowed its candidate lists
+        assert flagged >= c["nq"] - 1, (c["id"], "slow-path queries", flagged)
+        assert torch.equal(i, (base + torch.arange(k, device="cuda")).repeat(c["nq"], 1)), (c["id"], "identical rows: ids 0..k-1 in order")
     s1, i1 = idx.search(Q_, k, flags=flags, tau_mult=1e9)
     assert torch.equal(i1, i) and torch.equal(s1.view(torch.int32), s.view(torch.int32)), (c["id"], "certified != exhaustive")
 

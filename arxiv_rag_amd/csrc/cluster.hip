@@ -1,6 +1,6 @@
 // arx_cluster_sums / arx_cluster_finish: the update half of a spherical k-means (Lloyd) iteration over fp16 rows (gfx950; C ABI in
 // include/arx.h; the host layer is arxiv_rag_amd/topics.py; the definitions are INTEGRATION.md "Topics").  The assign half is
-// arx_topk_search with the centroids as the shard.
+// arx_cluster_assign (cluster_assign.hip).
 //
 // Sums.  `order` lists the member rows sorted by (cluster, row), `start[c]` is where cluster c begins in it.  s = start clamped into
 // [0, n_members] and made non-decreasing (a running maximum), so cluster c owns order[s[c], s[c + 1]).  Its members are cut into RUNS

@@ -6,6 +6,7 @@
 // speed); the int8 candidate steps share append_survivor, group_survivors, survivors_topk.
 // Included by search.hip after search_pass_a.h; not a stand-alone header.
 #pragma once
+#include "exact_score.h"
 
 // ---------------------------------------------------------------------------------------------------
 // sorted insert into a register-resident top-K list (score desc, id asc on ties; new element has the
@@ -139,44 +140,7 @@ __device__ __forceinline__ void wave_topk(float (&s)[R], int64_t (&id)[R], int k
     }
 }
 
-// exact score of corpus row `row` against the query row staged in LDS: 8 lanes per row (l8 = lane & 7), two FMA chains per
-// lane over its 16-B chunks, then a 3-step butterfly -> every lane of the octet holds the sum.  The ONE definition of a score
-// in this file: pass B2 and the certificate's fallback both rank by it.
-__device__ __forceinline__ float exact_row_score(const f16_t* __restrict__ crow, const f16_t* qs, int nch, int l8, bool ok) {
-    float a0 = 0.f, a1 = 0.f;
-    // chunks l8, l8 + 8, ... in ascending order, whatever the batching below: the sum's order (hence its bits) is fixed; the batches
-    // only decide how many of the row's 16-B loads are in flight at once (six: a 768-d row is two dependent round trips instead of three)
-    auto fma8 = [&](const f16x8& cv, const f16x8& qq) {
-#pragma unroll
-        for (int e = 0; e < 8; e += 2) {
-            a0 = fmaf((float)cv[e], (float)qq[e], a0);
-            a1 = fmaf((float)cv[e + 1], (float)qq[e + 1], a1);
-        }
-    };
-    if (ok) {
-        int ch = l8;
-#pragma unroll 1
-        for (; ch + 40 < nch; ch += 48) {
-            f16x8 cv[6];
-#pragma unroll
-            for (int u = 0; u < 6; ++u) cv[u] = *reinterpret_cast<const f16x8*>(crow + (ch + 8 * u) * 8);
-#pragma unroll
-            for (int u = 0; u < 6; ++u) fma8(cv[u], *reinterpret_cast<const f16x8*>(qs + (ch + 8 * u) * 8));
-        }
-#pragma unroll 1
-        for (; ch + 8 < nch; ch += 16) {
-            f16x8 cv[2];
-#pragma unroll
-            for (int u = 0; u < 2; ++u) cv[u] = *reinterpret_cast<const f16x8*>(crow + (ch + 8 * u) * 8);
-#pragma unroll
-            for (int u = 0; u < 2; ++u) fma8(cv[u], *reinterpret_cast<const f16x8*>(qs + (ch + 8 * u) * 8));
-        }
-        for (; ch < nch; ch += 8) fma8(*reinterpret_cast<const f16x8*>(crow + ch * 8), *reinterpret_cast<const f16x8*>(qs + ch * 8));
-    }
-    float a = a0 + a1;
-    a += __shfl_xor(a, 4); a += __shfl_xor(a, 2); a += __shfl_xor(a, 1);
-    return a;
-}
+// exact_row_score (exact_score.h): the ONE definition of a score in this file: pass B2 and the certificate's fallback both rank by it.
 
 // ---- the stages that rescore_kernel, tail_single_kernel and the int8 candidate kernels share, each written once -------------------------
 // Plain inlined functions: every kernel keeps its own body, LDS layout and barrier sequence and calls them.  A function that holds a

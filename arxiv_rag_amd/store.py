@@ -490,6 +490,35 @@ class HipCollection:
         return {"labels": labels, "sizes": res["sizes"], "centroids": res["centroids"], "objective": res["objective"],
                 "iterations": res["iterations"], "representatives": reps}
 
+    def assign_topics(self, centroids, where=None, where_document=None, store_as: Optional[str] = None) -> Dict:
+        """Label rows against given topic centroids (INTEGRATION.md "Topics"; `topics.predict`, `arx_cluster_assign`) without a new
+        fit: after `res = topics(...)` and `add(...)`, `assign_topics(res["centroids"], store_as="topic")` brings the stored labels up
+        to date.  `centroids`: f32 or fp16 [C, dim] (numpy or torch), f32 rounded to fp16 as the fit rounds its own, so on the rows of
+        the fit `assign_topics(res["centroids"])` reproduces `res["labels"]`.  The rows labelled are those a query with these filters
+        could return: `where` / `where_document` go through the same `retrieval.RowFilters` as in `topics`, the dedup and tombstone
+        keep-bitmap and-ed in, and the allowed rows are gathered as there.
+        -> {labels, scores, sizes}: `labels` numpy int32 [rows of this collection], -1 for an excluded row, else the lowest centroid
+        that maximises the exact score of the row; `scores` f32, that score, nan for an excluded row; `sizes` int64 [C].
+        `store_as` writes `metadata[r][store_as] = int(label)` for every labelled row and drops the metadata columns, as in `topics`.
+        ValueError before anything is launched: `world > 1`; a `store_as` that is not a string; centroids of the wrong shape or
+        dtype, with a value that is not finite, or more than 4096 of them; a dim that is not a multiple of 64."""
+        from . import topics as T
+        if getattr(self, "world", 1) > 1:
+            raise ValueError("assign_topics needs world == 1: a rank sees only its own rows")
+        if store_as is not None and not isinstance(store_as, str):
+            raise ValueError(f"store_as={store_as!r} must be a metadata key name or None")
+        T.check_centroids(centroids, self.dim)
+        if where_document is not None:
+            self._documents()
+        allow, _ = self._row_filters().allow_of(where, where_document)
+        res = T.label_shard(self.index, allow, centroids)
+        if store_as is not None:
+            labels = res["labels"]
+            for r in np.nonzero(labels >= 0)[0].tolist():
+                self.metadata[self.lo + r][store_as] = int(labels[r])
+            self._drop_columns()
+        return res
+
     def query(self, query_embeddings=None, query_texts: Optional[Sequence[str]] = None, n_results: int = 10, reranker=None,
               n_candidates: int = 32, hybrid_alpha: Optional[float] = None, where=None, where_document=None,
               mmr_lambda: Optional[float] = None, group_by=None, chunks_per_group: int = 1, min_score=None) -> Dict:

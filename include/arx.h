@@ -616,7 +616,7 @@ int32_t arx_facet_count_tuned(const arx_facet_key* keys, int32_t n_keys, int64_t
                               int32_t block_threads, int32_t blocks_x, int32_t lds_bins, void* stream);
 
 /* ---- Spherical k-means update over fp16 rows (csrc/cluster.hip; the host layer is arxiv_rag_amd/topics.py; INTEGRATION.md "Topics") ----
- * The assign half of a Lloyd iteration is arx_topk_search with the centroids as the shard; these calls are the other half.
+ * The assign half of a Lloyd iteration is arx_cluster_assign below; these calls are the other half.
  *   rows    device fp16 [n_rows, dim], 16-byte aligned
  *   order   device int32 [n_members]: row numbers sorted by (cluster, row)
  *   start   device int64 [C + 1]: cluster c owns order[start[c], start[c + 1])
@@ -650,6 +650,43 @@ int32_t arx_cluster_sums_tuned(const void* rows, int64_t n_rows, int32_t dim, co
  * [C, dim]) bit for bit.  One launch, one wave per cluster.  Same contract for dim and C; a null pointer is ARX_ERR_ARG. */
 int32_t arx_cluster_finish(const float* sums, const int64_t* start, const float* prev, int32_t C, int32_t dim, float* out_f32,
                            void* out_f16, void* stream);
+
+/* ---- Nearest centroid of every row (csrc/cluster_assign.hip; the host layer is arxiv_rag_amd/topics.py; INTEGRATION.md "Topics") ----
+ * The assign half of a Lloyd iteration, and "label rows against given centroids":
+ *   out_labels[i] = the lowest c that maximises score(centroid c, row i)        out_scores[i] = that f32 value
+ * where score is exact_row_score (csrc/exact_score.h), the score of arx_topk_search: 8 lanes per pair, lane l taking the 16-byte
+ * chunks l, l + 8, ... in ascending order, two fmaf chains per lane over even and odd elements, a0 + a1, then the butterfly xor 4, 2,
+ * 1.  For finite inputs and a valid norm bound the result equals arx_topk_search(k = 1) over the centroids bit for bit, labels and
+ * scores (and topics.assign_exact_host).
+ *   rows               device fp16 [n_rows, dim], 16-byte aligned
+ *   centroids_f16      device fp16 [C, dim], 16-byte aligned
+ *   max_centroid_norm  a bound on the centroids' 2-norms, positive and finite (0 = 1 + 2^-9, as max_row_norm)
+ *   out_labels         device int32 [n_rows];  out_scores device f32 [n_rows]; 16-byte aligned, every element written once by a plain store
+ *   stats              device int64 [2] or NULL: {rows flagged, exact scores computed on the slow path}, set by the call
+ *   ws                 device scratch of arx_cluster_assign_workspace_bytes(n_rows, C, dim) = 16 + 4 n_rows (rounded up to 16) bytes,
+ *                      16-byte aligned (-1 for arguments outside the contract below)
+ * Fast pass: an fp16 MFMA GEMM of row tiles against centroid tiles with f32 accumulation whose epilogue keeps, per row, the best
+ * approximate score with its centroid (ties to the lower one) and the second best.  Certificate: with
+ *   tau_i = tau_mult * (1.0625 * dim + 4) * 2^-24 * |x_i|_2 * max_centroid_norm
+ * (dim * 2^-24 for the MFMA sum in any order, (dim / 16 + 4) * 2^-24 for the exact score; |x_i|_2 computed in the kernel and rounded
+ * up) a row with a_best - a_second > 2 tau_i has a unique exact winner, and one exact score of that pair is its score.  Every other row
+ * (near ties, NaN or inf rows; none when C == 1) is FLAGGED: listed behind an integer counter and scored against every centroid by
+ * the second launch, which reads the count on the device.  Two identical centroids flag every row: n_rows * C * dim FMAs, what the
+ * search pays.  Two launches and one 16-byte memset on `stream`, no host synchronisation, no float atomics; the results do not depend
+ * on the launch shape.
+ * ARX_ERR_ARG before anything is launched, the message naming the field: dim not a multiple of 64 in [64, 8192]; C outside [1, 4096];
+ * n_rows outside [0, 2^31); a null or misaligned pointer; ws_bytes below the figure above; max_centroid_norm negative or not finite.
+ * n_rows == 0 launches nothing (stats are zeroed).  Rows and centroids are device data: values that are not finite lie outside the
+ * equality above and give some label in [0, C), never a read or write outside the arrays passed. */
+int64_t arx_cluster_assign_workspace_bytes(int64_t n_rows, int32_t C, int32_t dim);
+int32_t arx_cluster_assign(const void* rows, int64_t n_rows, int32_t dim, const void* centroids_f16, int32_t C, float max_centroid_norm,
+                           int32_t* out_labels, float* out_scores, int64_t* stats, void* ws, int64_t ws_bytes, void* stream);
+/* The same with the certificate's margin and the launch shape chosen: tau_mult 0 (= 1) or a finite value >= 1 (values in (0, 1) are
+ * refused; 1e9 sends every row of a C >= 2 call down the slow path); rows_per_block 0 (default), 32 or 64 rows a block stages.  Same
+ * bits for every choice. */
+int32_t arx_cluster_assign_tuned(const void* rows, int64_t n_rows, int32_t dim, const void* centroids_f16, int32_t C,
+                                 float max_centroid_norm, int32_t* out_labels, float* out_scores, int64_t* stats, void* ws,
+                                 int64_t ws_bytes, float tau_mult, int32_t rows_per_block, void* stream);
 
 /* ---- MMR diversified re-ordering of a query's search candidates (csrc/mmr.hip; the definition is INTEGRATION.md "MMR") -----------
  * arx_gather_rows: out[s] (device fp16 [count, dim]) = shard row ids[s] - idx_base where that row lies in [0, n_rows), all zeros

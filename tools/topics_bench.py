@@ -4,7 +4,11 @@
 One process, the arms in turn: `--rows` x `--dim` clustered fp16 rows (`fill_clustered_rows`) at C = 64, 256 and 1024, then two
 filtered sets at C = 256 (a random 10 % and a contiguous 12.5 % of the rows, gathered once with `arx_gather_rows`).  Per arm the
 stages of an iteration are timed apart, each between two events on the stream, median of `--repeats`:
-  assign   `topics.assign`: the exact k = 1 search of every row over the centroids, in batches of 65 536
+  assign_kernel   `topics.assign(how="kernel")`: `arx_cluster_assign`, with its `stats` (rows flagged, slow-path scores) and beside its
+                  floor: the larger of the bytes of X at the copy rate and 2 n C dim flop at the fp16 dense-MFMA rate (2.5 PF/s, the
+                  specification figure, not a measurement of this repository)
+  assign_search   `topics.assign(how="search")`: the exact k = 1 search of every row over the centroids, in batches of 65 536 (what
+                  the assign was before the kernel), timed in the same process right after it
   sort     `topics.members`: the stable sort of the labels, `bincount` and the cumulative sum
   sums     `arx_cluster_sums`, beside its floor: the bytes of X at the 6.29 TB/s copy rate the other tools use
   finish   `arx_cluster_finish`
@@ -26,6 +30,7 @@ from arxiv_rag_amd import topics as T      # noqa: E402
 from arxiv_rag_amd.index import ShardIndex, fill_clustered_rows      # noqa: E402
 
 COPY_RATE = 6.29e12
+MFMA_F16_RATE = 2.5e15          # fp16 dense MFMA, flop/s: the MI355X specification figure
 DEV = "cuda:0"
 
 
@@ -47,7 +52,11 @@ def arm(name, X, C, repeats, out):
     rows = torch.from_numpy(T.default_init_rows(n, C, 0)).to(DEV)
     c32 = X.index_select(0, rows).float()
     c16 = c32.half()
-    labels, _ = T.assign(X, c16)                                 # the state after a first assign: what every later iteration looks like
+    assign_ws = T.assign_workspace(n, C, dim, DEV)
+    stats = torch.zeros(2, dtype=torch.int64, device=DEV)
+    labels, scores = T.cluster_assign(X, c16, stats=stats, ws=assign_ws)     # the state after a first assign: what every later iteration looks like
+    sl, ss = T.assign(X, c16, how="search")
+    same_bits = bool(torch.equal(labels, sl) and torch.equal(scores.view(torch.int32), ss.contiguous().view(torch.int32)))
     order, start, sizes = T.members(labels, C)
     ws = torch.empty(((n + T.RUN - 1) // T.RUN + C) * dim, dtype=torch.float32, device=DEV)
     sums = torch.empty((C, dim), dtype=torch.float32, device=DEV)
@@ -61,16 +70,24 @@ def arm(name, X, C, repeats, out):
     floor_ms = x_bytes / COPY_RATE * 1e3
     row = {"arm": name, "rows": n, "dim": dim, "clusters": C, "largest_cluster": int(sizes.max().item()),
            "empty_clusters": int((sizes == 0).sum().item()),
-           "assign": timed(lambda: T.assign(X, c16), repeats),
+           "assign_kernel": timed(lambda: T.assign(X, c16, how="kernel", ws=assign_ws), repeats),
+           "assign_search": timed(lambda: T.assign(X, c16, how="search"), repeats),
            "sort": timed(lambda: T.members(labels, C), repeats),
            "sums": timed(lambda: T.cluster_sums(X, order, start, C, out=sums, ws=ws), repeats),
            "finish": timed(lambda: T.cluster_finish(sums, start, c32), repeats),
            "torch_index_add_f32": timed(torch_update, repeats)}
     row["sums"].update(bytes_of_X=x_bytes, floor_ms=floor_ms, times_floor=row["sums"]["ms_median"] / floor_ms,
                        achieved_TBps=x_bytes / (row["sums"]["ms_median"] * 1e-3) / 1e12)
-    total = sum(row[k]["ms_median"] for k in ("assign", "sort", "sums", "finish"))
+    flagged, slow_scores = (int(v) for v in stats.cpu().tolist())
+    assign_floor_ms = max(floor_ms, 2.0 * n * C * dim / MFMA_F16_RATE * 1e3)
+    row["assign_kernel"].update(rows_flagged=flagged, slow_path_scores=slow_scores, same_bits_as_search=same_bits, floor_ms=assign_floor_ms,
+                                floor_is="X bytes" if assign_floor_ms == floor_ms else "MFMA flop",
+                                times_floor=row["assign_kernel"]["ms_median"] / assign_floor_ms)
+    row["assign_search_over_kernel"] = row["assign_search"]["ms_median"] / row["assign_kernel"]["ms_median"]
+    stages = ("assign_kernel", "sort", "sums", "finish")
+    total = sum(row[k]["ms_median"] for k in stages)
     row["iteration_ms"] = total
-    row["share_of_iteration"] = {k: row[k]["ms_median"] / total for k in ("assign", "sort", "sums", "finish")}
+    row["share_of_iteration"] = {k: row[k]["ms_median"] / total for k in stages}
     out["arms"].append(row)
     print(json.dumps(row), flush=True)
 
@@ -82,7 +99,8 @@ def main():
     ap.add_argument("--repeats", type=int, default=20)
     ap.add_argument("--out", type=str, default=str(ROOT / "profiles" / "topics_bench.json"))
     args = ap.parse_args()
-    out = {"device": torch.cuda.get_device_name(0), "copy_rate_TBps": COPY_RATE / 1e12, "arms": []}
+    out = {"device": torch.cuda.get_device_name(0), "copy_rate_TBps": COPY_RATE / 1e12, "mfma_f16_rate_PFps": MFMA_F16_RATE / 1e15,
+           "mfma_f16_rate_source": "MI355X specification (dense fp16 MFMA), not measured here", "arms": []}
     X = fill_clustered_rows(args.rows, args.dim, 1, 256, device=DEV)
     Path(args.out).parent.mkdir(parents=True, exist_ok=True)
     for C in (64, 256, 1024):

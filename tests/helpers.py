@@ -115,8 +115,17 @@ def scores_fp64(q, c):
     below 2^28 elements: torch's matmul on this stack has written zeros past element 2^29 of a larger result (tools/search_soak.py)."""
     import torch
     q64 = q.double()
-    step = max(1, (1 << 28) // max(1, q.shape[0]))
+    step = min(ROW_CHUNK, max(1, (1 << 28) // max(1, q.shape[0])))               # (and never the float64 copy of a whole multi-GB shard)
     return torch.cat([q64 @ c[a:a + step].double().T for a in range(0, c.shape[0], step)], dim=1)
+
+
+ROW_CHUNK = 1 << 18
+
+
+def row_norms_fp64(c):
+    """[n] float64 L2 norms of the fp16 rows `c`, converted ROW_CHUNK rows at a time"""
+    import torch
+    return torch.cat([c[a:a + ROW_CHUNK].double().norm(dim=1) for a in range(0, max(1, c.shape[0]), ROW_CHUNK)])
 
 
 def check_topk_fp64(c, q, s, i, k, idx_base=0, e=None, sample_rows=4, what=None):
@@ -141,7 +150,7 @@ def check_topk_fp64(c, q, s, i, k, idx_base=0, e=None, sample_rows=4, what=None)
         assert np.abs(got - ref).max() <= 1e-13 * max(1e-30, float(np.abs(ref).max())), (what, "float64 matmul")
     B = pass_b_budget(D)
     qn = q.double().norm(dim=1)                                                  # [nq]
-    cn = c.double().norm(dim=1)                                                  # [n]
+    cn = row_norms_fp64(c)                                                       # [n]
     kk = min(k, n)
     assert s.shape == (nq, k) and i.shape == (nq, k), what
     if k > n:

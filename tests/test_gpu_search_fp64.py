@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 
 from tests.helpers import U24, check_topk_fp64, pass_a_budget, scores_fp64
+from tests.search_cases import (_adversarial, _gen, _layout, _queries, _tiny, _unit, check_pass_a_workspace,  # noqa: F401
+                                pass_a_reference)
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -22,22 +24,6 @@ def hip():
     return _lib
 
 
-def _gen(seed):
-    g = torch.Generator(device="cuda"); g.manual_seed(seed)
-    return g
-
-
-def _unit(n, d, g):
-    return F.normalize(torch.randn((n, d), generator=g, device="cuda"), dim=1)
-
-
-def _adversarial(n, d, g):
-    """(b) every component positive and of nearly equal size (1/sqrt(d) with a few f16 ulps of jitter): the partial sums of an
-    accumulation chain grow linearly, its worst case."""
-    j = torch.randint(-4, 5, (n, d), generator=g, device="cuda").float()
-    return (1.0 + j * 2.0 ** -10) / d ** 0.5
-
-
 def _cancelling(n, d, g):
     """(c) +-halves (half of the components +1/sqrt(d), half -1/sqrt(d), in random positions) plus a small signal: against a positive
     query the partial sums climb to ~|q||c|/2 and cancel to nearly nothing."""
@@ -50,11 +36,6 @@ def _norms(n, d, g):
     return _unit(n, d, g) * torch.exp(torch.empty((n, 1), device="cuda").uniform_(np.log(0.01), np.log(8.0), generator=g))
 
 
-def _tiny(n, d, g):
-    """(e) norm 1e-3: at d >= 768 most components are fp16 subnormals (< 2^-14)."""
-    return _unit(n, d, g) * 1e-3
-
-
 def _mixed_corpus(d, n_groups, g, ragged=29):
     """Whole 64-row groups of each family (so that a group's budget, relative to its largest row, is tight), tiny rows also mixed into
     unit groups at d >= 768, and a ragged last group."""
@@ -64,32 +45,6 @@ def _mixed_corpus(d, n_groups, g, ragged=29):
         mix = _unit(64, d, g); mix[::2] = _tiny(32, d, g); parts.append(mix)
     parts.append(_unit(ragged, d, g))
     return torch.cat(parts).half().contiguous()
-
-
-def _queries(nq, d, g):
-    """query 0 all zero (f), 1..40 rounding-adversarial (positive), 41..50 tiny (subnormal components), the rest unit, every 7th of
-    those scaled to norm 8."""
-    q = _unit(nq, d, g)
-    m = min(40, nq - 1)
-    if m > 0:
-        q[1:1 + m] = _adversarial(m, d, g)
-    m = min(10, nq - 41)
-    if m > 0:
-        q[41:41 + m] = _tiny(m, d, g)
-    q[51::7] *= 8.0
-    q[0] = 0.0
-    return q.half().contiguous()
-
-
-def _layout(n, nq):
-    """Offsets of the fp16 pass's workspace (csrc/search.hip topk_layout): 256 bytes of counters, gmax [groups][ldg] f32, two selection
-    arrays of nsplit x ldg x 36 words, then the aux words in gmax's shape; every region 256-byte aligned."""
-    r256 = lambda b: (b + 255) // 256 * 256
-    n_groups = (n + 63) // 64
-    ldg = (min(nq, 1024) + 63) // 64 * 64
-    n_super = (n_groups + 15) // 16
-    nsplit = max(1, min(256, (n_super + 7) // 8))
-    return n_groups, ldg, 256, 256 + r256(n_groups * ldg * 4) + 2 * r256(nsplit * ldg * 36 * 4)
 
 
 def test_pass_a_group_maxima_within_budget_every_dim_and_kernel_form(hip):
@@ -109,13 +64,8 @@ def test_pass_a_group_maxima_within_budget_every_dim_and_kernel_form(hip):
         A = pass_a_budget(d)
         idx = ShardIndex(C_)
         e_all = scores_fp64(Qall, C_)                                              # [300, n]
-        G, _, _, _ = _layout(n, 1)
-        pad = torch.full((300, G * 64 - n), float("-inf"), dtype=torch.float64, device="cuda")
-        e_g = torch.cat([e_all, pad], dim=1).view(300, G, 64)
-        cn = torch.cat([C_.double().norm(dim=1), torch.zeros(G * 64 - n, dtype=torch.float64, device="cuda")]).view(G, 64)
+        e_g, cn, emax, cmax = pass_a_reference(e_all, C_, n)                      # [300, G, 64], [G, 64], [300, G], [G]
         qn = Qall.double().norm(dim=1)
-        emax = e_g.max(dim=2).values                                               # [300, G]
-        cmax = cn.max(dim=1).values                                                # [G]
         forms = [(40, 10, 0), (40, 32, 0), (100, 10, 0), (100, 32, 0), (200, 10, 0), (200, 32, 0), (300, 10, 0)]
         if d % 128 == 0:
             forms += [(200, 10, NOP), (200, 32, NOP)]                               # the per-tile 256-query kernel where the persistent one applies
@@ -127,36 +77,7 @@ def test_pass_a_group_maxima_within_budget_every_dim_and_kernel_form(hip):
             ws.fill_(0xFF)                                                          # (NaN patterns: a value the pass did not write cannot pass)
             idx.search(Q_, k, ws=ws, flags=SCAN | fl)
             torch.cuda.synchronize()
-            G, ldg, off_g, off_aux = _layout(n, nq)
-            gm = ws[off_g:off_g + G * ldg * 4].view(torch.float32).view(G, ldg)[:, :nq].T.double()      # [nq, G]
-            bud = A * qn[:nq, None] * cmax[None, :]
-            em = emax[:nq]
-            full = slice(0, G - 1)
-            err = (gm[:, full] - em[:, full]).abs()
-            assert torch.isfinite(gm).all(), what
-            assert (err <= bud[:, full]).all(), (what, "pass A outside A(D)", ((err - bud[:, full]).max().item()))
-            # the ragged last group: rows past the shard may enter the maximum as zeros (a conservative bound), never as anything else
-            assert (gm[:, -1] >= em[:, -1] - bud[:, -1]).all() and (gm[:, -1] <= em[:, -1].clamp_min(0) + bud[:, -1]).all(), what
-            assert (gm[0] == 0).all(), (what, "zero query")
-            scale = U24 * qn[:nq, None] * cmax[None, :]
-            ok = scale[:, full] > 0
-            worst = max(worst, (err[ok] / scale[:, full][ok]).max().item())
-            if k <= 10 and nq <= 256:
-                aux = ws[off_aux:off_aux + G * ldg * 4].view(torch.int32).view(G, ldg)[:, :nq].T         # [nq, G]
-                ub2 = (aux & -65536).view(torch.float32).double()
-                arg = (aux & 63).long()
-                assert (arg % 4 == 0).all(), what
-                lowered = e_g[:nq] - A * qn[:nq, None, None] * cn[None]             # [nq, G, 64]: a lower bound of each pass-A score
-                raised = e_g[:nq] + A * qn[:nq, None, None] * cn[None]
-                blk = arg[:, :, None] + torch.arange(4, device="cuda")[None, None, :]
-                others = lowered.clone(); others.scatter_(2, blk, float("-inf"))
-                o2 = others.max(dim=2).values
-                fin = torch.isfinite(o2)
-                assert (ub2[fin] >= o2[fin]).all(), (what, "aux bound below a row outside the arg-max block", (o2 - ub2)[fin].max().item())
-                # the block is the arg-max of keys whose low 6 bits carry the position: it holds the maximum to within 63 ulp
-                inblk = raised[:, full].gather(2, blk[:, full]).max(dim=2).values
-                assert (inblk >= gm[:, full] - gm[:, full].abs() * 2.0 ** -17).all(), (what, "the arg-max block does not hold the group maximum")
-                assert (ub2 - gm - gm.abs() * 0.008 <= 1e-9).all(), (what, "aux above the group maximum")
+            worst = max(worst, check_pass_a_workspace(ws, n, nq, A, qn, e_g, cn, emax, cmax, what, aux=k <= 10 and nq <= 256))
         print(f"pass A, D = {d}: largest |gmax - max e| / (u |q| max|c|) = {worst:.2f}   (budget 0.25 D = {0.25 * d:g})")
 
 

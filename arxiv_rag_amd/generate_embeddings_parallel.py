@@ -677,7 +677,8 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
                    where_document: Optional[Dict] = None, *, mmr_lambda: Optional[float] = None, mmr_fetch_k: int = 32,
                    keep_mask: Optional[np.ndarray] = None, group_by_paper: bool = False, chunks_per_paper: int = 1,
                    where_on_device: bool = False, min_score: Optional[float] = None, hybrid_filters: bool = False,
-                   hybrid_on_device: bool = False, keyword_build_on_device: bool = False, document_regex: bool = False) -> List[Dict]:
+                   hybrid_on_device: bool = False, keyword_build_on_device: bool = False, document_regex: bool = False,
+                   nprobe: Optional[int] = None, ivf_lists: Optional[int] = None, ivf_iters: int = 10, ivf_seed: int = 0) -> List[Dict]:
     """Brute-force cosine top-k (config.yaml:63-64 `top_k: 10`) over the rank's fp16 rows in HBM; with
     torchrun each rank holds the contiguous row shard it encoded and the partial top-k lists are
     all-gathered over RCCL and merged.  `shard` is the `ShardSink` the encode step filled: rows [lo, hi) are already where they
@@ -738,7 +739,12 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
     keyword index on the device").
     `document_regex` (False = nothing changes): `where_document` also takes `$regex` / `$not_regex` leaves (`--where-document-regex`),
     compiled on the host to byte-level DFAs (`regex_dfa.compile_regex`: the dialect and its limits) and scanned on the device
-    (`arx_text_regex`); the bitmap goes where the `$contains` one goes (INTEGRATION.md "Document filters")."""
+    (`arx_text_regex`); the bitmap goes where the `$contains` one goes (INTEGRATION.md "Document filters").
+    `nprobe` with `ivf_lists` (None = nothing changes): the IVF probe search (INTEGRATION.md "IVF probe search").  An `ivf.IvfIndex` with
+    `ivf_lists` lists is built over the shard (`ivf_iters`, `ivf_seed`) and every query is scored against the rows of its `nprobe` nearest
+    lists only, filters applied as without it; every entry of the results then carries `ivf_scanned`, the rows scored.  Composes with
+    `where` (one dict), `where_document`, `keep_mask`, `reranker` and `mmr_lambda`.  Not together with `hybrid_alpha`, `group_by_paper`,
+    `min_score`, a per-query `where` list or more than one rank."""
     from .retrieval import RowFilters, check_hybrid_on_device, check_shared_query, retrieve
     if keyword_build_on_device and hybrid_alpha is None:
         raise ValueError("keyword_build_on_device needs hybrid_alpha: it chooses where the BM25 keyword index is built")
@@ -753,6 +759,14 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
             raise ValueError("min_score cannot be combined with reranker here: reranking a long range list is out of scope for search_queries")
         check_range_query(top_k, ranged=True, hybrid_alpha=hybrid_alpha, mmr_lambda=mmr_lambda, group_by=group_by_paper,
                           per_query_filters=isinstance(where, (list, tuple)), world=int(os.environ.get("WORLD_SIZE", "1")))
+    if nprobe is not None or ivf_lists is not None:
+        from .ivf import check_build_args, check_query_with_nprobe
+        if nprobe is None or ivf_lists is None:
+            raise ValueError("nprobe and ivf_lists go together: the lists to build and how many of them a query probes")
+        check_query_with_nprobe(nprobe, has_index=True, n_lists=int(ivf_lists), per_query_filters=isinstance(where, (list, tuple)),
+                                hybrid_alpha=hybrid_alpha, group_by=group_by_paper, min_score=min_score,
+                                world=int(os.environ.get("WORLD_SIZE", "1")))
+        check_build_args(int(shard.rows.shape[0]), int(shard.rows.shape[1]), ivf_lists, ivf_iters, None)
     if where_on_device and where is None:
         raise ValueError("where_on_device needs where: it chooses where the where filters are evaluated")
     if group_by_paper:
@@ -778,7 +792,7 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
         compile_where_document(where_document, regex=document_regex)
     # int8 pre-filter (same exact answers; +50 % shard memory, one quantisation pass): 1.5-1.7x the queries per second on small batches;
     # a filtered, a grouped and a range search run on the fp16 rows
-    masked = (where is not None or keep_mask is not None or where_document is not None or group_by_paper or min_score is not None
+    masked = (where is not None or keep_mask is not None or where_document is not None or group_by_paper or min_score is not None or nprobe is not None
               or (hybrid_on_device and n_cand_of(reranker, rerank_top_k, mmr_lambda, mmr_fetch_k) > HYBRID_CANDIDATES))
     index = ShardIndex(shard.rows, idx_base=shard.lo, prefilter="int8" if (dim % 128 == 0 and dim <= 1024 and n_rows > 0 and not masked) else None,
                        adaptive=True)
@@ -804,7 +818,8 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
                          document_regex=document_regex)
     hit = retrieve(index, qd, filters, top_k, n_candidates=n_cand, reranked=reranker is not None, where=where, where_document=where_document,
                    min_score=None if min_score is None else float(min_score), grouped=group_by_paper, chunks_per_group=chunks_per_paper, mmr_lambda=mmr_lambda,
-                   hybrid_alpha=hybrid_alpha, keyword=keyword_index, query_texts=queries, hybrid_on_device=hybrid_on_device, world=world)
+                   hybrid_alpha=hybrid_alpha, keyword=keyword_index, query_texts=queries, hybrid_on_device=hybrid_on_device, world=world,
+                   **({} if nprobe is None else {"nprobe": int(nprobe), "ivf": build_ivf_index(index, ivf_lists, ivf_iters, ivf_seed)}))
     s, i, grp, truncated, mmr_val, hyb, kws = hit.scores, hit.ids, hit.groups, hit.truncated, hit.mmr, hit.hybrid, hit.keyword
     if reranker is not None:
         from .ranging import RERANK_BATCH
@@ -821,6 +836,7 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
         dist.all_gather_object(parts, names, group=host_group())
         names = {k: v for part in parts for k, v in part.items()}
     results = []
+    scanned_of = (lambda qi: {}) if hit.ivf_scanned is None else (lambda qi: {"ivf_scanned": int(hit.ivf_scanned[qi])})
 
     def hybrid_fields(qi, p):                                # (null, not NaN, in the JSON file)
         if hyb is None:
@@ -834,7 +850,7 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
             for r, (p, j, rs_) in enumerate(picked[qi]):
                 hits.append({"rank": r + 1, "score": float(s[qi, p]), "rerank_score": float(rs_), "index": j,
                              "chunk_id": names.get(j, f"chunk_{j}"), **hybrid_fields(qi, p)})
-            results.append({"query": text, "results": hits})
+            results.append({"query": text, "results": hits, **scanned_of(qi)})
             continue
         if grp is not None:                                   # paper by paper; the padding of short papers is skipped
             for r in range(i.shape[1]):
@@ -850,12 +866,22 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
                 continue
             hits.append({"rank": r + 1, "score": float(s[qi, r]), "index": j, "chunk_id": names.get(j, f"chunk_{j}"),
                          **hybrid_fields(qi, r), **({} if mmr_val is None else {"mmr_score": float(mmr_val[qi, r])})})
-        results.append({"query": text, "results": hits, **({} if truncated is None else {"truncated": bool(truncated[qi])})})
+        results.append({"query": text, "results": hits, **({} if truncated is None else {"truncated": bool(truncated[qi])}), **scanned_of(qi)})
     if rank == 0:
         with open(Path(output_dir) / "search_results.json", "w", encoding="utf-8") as fh:
             json.dump(results, fh, indent=2, ensure_ascii=False)
         print(f"✅ Saved top-{top_k} {'papers' if group_by_paper else 'results'} for {len(queries)} queries to {Path(output_dir) / 'search_results.json'}")
     return results
+
+
+def build_ivf_index(index, n_lists: int, iters: int = 10, seed: int = 0):
+    """`--ivf-lists`: the `ivf.IvfIndex` of the search step's shard, with its summary printed."""
+    from .ivf import IvfIndex
+    ivf = IvfIndex.build(index, int(n_lists), iters=int(iters), seed=int(seed))
+    info = ivf.summary()
+    print(f"IVF index: {info['n_lists']} lists of {info['list_rows_min']} / {info['list_rows_median']:.0f} / {info['list_rows_max']} rows "
+          f"(min / median / max), {info['iterations']} iterations on {info['train_rows']} rows, {info['seconds']:.2f} s")
+    return ivf
 
 
 # --------------------------------------------------------------------------------------------- main
@@ -946,6 +972,14 @@ def build_parser() -> argparse.ArgumentParser:
                         "nearest chunks (default: off; needs --queries; one GPU rank only; not with --where-file)")
     p.add_argument("--topics-iters", type=int, default=20, help="Iterations of --topics at most (default: 20)")
     p.add_argument("--topics-seed", type=int, default=0, help="Seed of the initial centroids of --topics (default: 0)")
+    p.add_argument("--ivf-lists", type=int, default=None,
+                   help="IVF probe search: cluster the chunks into this many lists (1..4096, spherical k-means on the GPU) before the "
+                        "--queries search (default: off; needs --nprobe and --queries; one GPU rank only)")
+    p.add_argument("--ivf-iters", type=int, default=10, help="Iterations of the --ivf-lists k-means at most (default: 10)")
+    p.add_argument("--ivf-seed", type=int, default=0, help="Seed of the --ivf-lists sample and initial centroids (default: 0)")
+    p.add_argument("--nprobe", type=int, default=None,
+                   help="IVF probe search: score every query against the chunks of its this many nearest lists only (1..min(128, "
+                        "--ivf-lists); exact among those; not with --hybrid-alpha, --group-by-paper, --min-score or --where-file)")
     return p
 
 
@@ -1083,6 +1117,35 @@ def check_facets_args(args) -> Optional[str]:
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         return "--facets needs a single GPU rank: ranks number their strings separately, and a per-rank top list cannot be merged exactly"
     args.facet_keys = keys
+    return None
+
+
+def check_ivf_args(args) -> Optional[str]:
+    """-> an error message for an unusable --ivf-lists / --ivf-iters / --nprobe, else None.  (The other flags are read with getattr:
+    absent = off.)"""
+    lists, nprobe = getattr(args, "ivf_lists", None), getattr(args, "nprobe", None)
+    if lists is None and nprobe is None:
+        return None
+    if lists is None or nprobe is None:
+        return "--ivf-lists and --nprobe go together: the lists to build and how many of them a query probes"
+    if not (1 <= lists <= 4096):
+        return f"--ivf-lists {lists} must be in [1, 4096]"
+    if not (1 <= nprobe <= min(128, lists)):
+        return f"--nprobe {nprobe} must be in [1, min(128, --ivf-lists)] = [1, {min(128, lists)}]"
+    if getattr(args, "ivf_iters", 10) < 1:
+        return f"--ivf-iters {args.ivf_iters}: at least one iteration"
+    if not getattr(args, "queries", None):
+        return "--nprobe needs --queries: it is a mode of the search step"
+    if getattr(args, "hybrid_alpha", None) is not None:
+        return "--nprobe cannot be combined with --hybrid-alpha: the BM25 keyword search has no inverted lists of topics"
+    if getattr(args, "group_by_paper", False):
+        return "--nprobe cannot be combined with --group-by-paper: the grouped search reads every row"
+    if getattr(args, "min_score", None) is not None:
+        return "--nprobe cannot be combined with --min-score: the range search reads every row"
+    if getattr(args, "where_filters", None) is not None:
+        return "--nprobe cannot be combined with --where-file: the IVF search takes one bitmap per call"
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        return "--nprobe needs a single GPU rank: more than one rank is out of scope"
     return None
 
 
@@ -1313,7 +1376,7 @@ def main(argv: Optional[Sequence[str]] = None, model_factory: Optional[Callable]
     args = build_parser().parse_args(argv)
     err = (check_rerank_args(args) or check_hybrid_args(args) or check_hybrid_filters_args(args) or check_hybrid_device_args(args) or check_keyword_build_args(args) or check_where_args(args) or check_where_file_args(args) or check_where_device_args(args)
            or check_where_document_args(args)
-           or check_mmr_args(args) or check_dedup_args(args) or check_group_args(args) or check_range_args(args) or check_facets_args(args) or check_topics_args(args))
+           or check_mmr_args(args) or check_dedup_args(args) or check_group_args(args) or check_range_args(args) or check_facets_args(args) or check_topics_args(args) or check_ivf_args(args))
     if err:
         print(f"Error: {err}")
         return 2
@@ -1416,7 +1479,9 @@ def main(argv: Optional[Sequence[str]] = None, model_factory: Optional[Callable]
                                **({"hybrid_filters": True} if args.hybrid_filters else {}),
                                **({"hybrid_on_device": True} if args.hybrid_on_device else {}),
                                **({"keyword_build_on_device": True} if args.keyword_build_on_device else {}),
-                               **({"document_regex": True} if args.where_document_regex else {}))
+                               **({"document_regex": True} if args.where_document_regex else {}),
+                               **({"nprobe": args.nprobe, "ivf_lists": args.ivf_lists, "ivf_iters": args.ivf_iters, "ivf_seed": args.ivf_seed}
+                                  if args.nprobe is not None else {}))
                 if args.facet_keys is not None:
                     facet_counts(chunks, _model.encoder.device, args.facet_keys, args.facets_top,
                                  where=args.where_filters if args.where_filters is not None else args.where_filter,

@@ -197,12 +197,13 @@ class Retrieved:
     mmr: Optional[np.ndarray] = None             # mmr_lambda: the objective at each pick
     hybrid: Optional[np.ndarray] = None          # hybrid_alpha: the fused scores ...
     keyword: Optional[np.ndarray] = None         # ... and the BM25 ones (nan where the row was not in the keyword list)
+    ivf_scanned: Optional[np.ndarray] = None     # nprobe: int64 [Q], the rows scored for every query
 
 
 def retrieve(index, q, filters: RowFilters, n_results: int, *, n_candidates: int = 32, reranked: bool = False, where=None, where_document=None,
              min_score=None, grouped: bool = False, chunks_per_group: int = 1, mmr_lambda: Optional[float] = None,
              hybrid_alpha: Optional[float] = None, keyword=None, query_texts: Optional[Sequence[str]] = None,
-             hybrid_on_device: bool = False, world: int = 1) -> Retrieved:
+             hybrid_on_device: bool = False, world: int = 1, nprobe: Optional[int] = None, ivf=None) -> Retrieved:
     """One search of the fp16 device queries `q` over `index` (a `ShardIndex`), in the mode the arguments name, every refusal behind it.
     The width: a range search (`min_score`) returns up to `n_candidates` rows with `reranked` and `n_results` without, a grouped search
     `n_results` groups, every other search `n_candidates` rows when something picks among them afterwards (`reranked`, `mmr_lambda`,
@@ -215,11 +216,20 @@ def retrieve(index, q, filters: RowFilters, n_results: int, *, n_candidates: int
     (the same score bits, by that kernel's contract), the keyword list is `KeywordIndex.search_wide`'s under the same bitmaps, the
     fusion is `keyword.fuse_device`, and the four result arrays cross to the host once.  For `n_candidates <= 32` the result is the
     default path's, bit for bit.  ValueError: `n_candidates > 1024`; `n_candidates > 32` with per-query filter lists (the range
-    search takes one bitmap per call) or with `world > 1` ranks (a cross-rank merge of long lists is out of scope)."""
+    search takes one bitmap per call) or with `world > 1` ranks (a cross-rank merge of long lists is out of scope).
+    `nprobe` (None = nothing changes) with `ivf` (an `ivf.IvfIndex` over `index`): the IVF probe search (INTEGRATION.md "IVF probe
+    search"): the exact top-k of the rows of every query's `nprobe` nearest lists, under the one bitmap of `where`, `where_document`
+    and the keep-mask; `ivf_scanned` holds the rows scored.  MMR and a reranker consume its candidate list as any other.  ValueError
+    (`ivf.check_query_with_nprobe`): per-query filter lists, `hybrid_alpha`, `grouped`, `min_score`, `world > 1`, no `ivf`."""
     import torch
     from .filter_sets import is_per_query
     nq = q.shape[0]
     k = n_candidates if (reranked or hybrid_alpha is not None or mmr_lambda is not None) else n_results
+    if nprobe is not None:
+        from .ivf import check_query_with_nprobe
+        check_query_with_nprobe(nprobe, has_index=ivf is not None, n_lists=getattr(ivf, "n_lists", 0),
+                                per_query_filters=is_per_query(where) or is_per_query(where_document), hybrid_alpha=hybrid_alpha,
+                                group_by=grouped, min_score=min_score, world=world, n_width=k)
     out = Retrieved(None, None)
     kw_filter_of = None
     on_device = hybrid_alpha is not None and bool(hybrid_on_device)
@@ -235,7 +245,10 @@ def retrieve(index, q, filters: RowFilters, n_results: int, *, n_candidates: int
             kw_filter_of = torch.tensor(list(filter_of), dtype=torch.int32, device=q.device)
     else:
         allow, n_allowed = filters.allow_of(where, where_document)
-        if min_score is not None:
+        if nprobe is not None:
+            s, i, scanned = ivf.search(q, k, int(nprobe), allow=allow)
+            out.ivf_scanned = scanned.cpu().numpy()
+        elif min_score is not None:
             from .ranging import thresholds
             s, i, counts = index.search_range(q, thresholds(min_score, nq), n_candidates if reranked else n_results, allow=allow,
                                               n_allowed=n_allowed)

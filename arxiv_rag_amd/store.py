@@ -298,6 +298,10 @@ class HipCollection:
             self.documents.append(texts)
         self._drop_columns()
         self._make_index()
+        if getattr(self, "ivf", None) is not None:               # the new rows labelled against the kept centroids; the lists rebuilt
+            from .ivf import label_rows
+            self.ivf.index = self.index
+            self.ivf.set_labels(torch.cat([self.ivf.labels, label_rows(self._buf[n:n + m], self.ivf.centroids_f16)]))
         if self._deleted is not None:
             self._deleted = np.concatenate([self._deleted, np.zeros(m, bool)])
         if self.dedup_threshold is not None:
@@ -374,6 +378,10 @@ class HipCollection:
             self._group_buf, self._group_host = moved, self._group_host[keep]
         if self.documents is not None:
             self.documents.compact(self._keep, word_rank, count)
+        ivf_labels = None
+        if getattr(self, "ivf", None) is not None:               # the labels move as `group_of` moves: 4-byte rows
+            ivf_labels = torch.zeros_like(self.ivf.labels)
+            compact_rows_device(self.ivf.labels.contiguous(), ivf_labels, n, self._keep, word_rank)
         self.metadata = [md for md, k in zip(self.metadata, keep.tolist()) if k]
         self._ids = build_id_map(self.metadata)
         if self._kw_pieces is not None:
@@ -383,7 +391,23 @@ class HipCollection:
         self._set_keep(None)
         self._drop_columns()
         self._make_index()
+        if ivf_labels is not None:
+            self.ivf.index = self.index
+            self.ivf.set_labels(ivf_labels[:count].contiguous())
         return old_to_new(keep)
+
+    def build_ivf(self, n_lists: int, iters: int = 10, seed: int = 0, train_rows: Optional[int] = None) -> Dict:
+        """Build the inverted lists `query(nprobe=...)` needs (INTEGRATION.md "IVF probe search"; `ivf.IvfIndex.build`): k-means with
+        `n_lists` centroids on a sample of this collection's rows (tombstoned ones included: the keep-bitmap hides them at query
+        time), every row labelled, the rows sorted by list.  Again replaces the index; nothing re-fits the centroids otherwise: `add`
+        labels the new rows against them, `compact` moves the labels.  -> {n_lists, list_rows_min / median / max, iterations,
+        train_rows, seconds}.  ValueError before any launch: `world > 1`, an empty collection, the refusals of `IvfIndex.build`."""
+        from .ivf import IvfIndex, check_build_args
+        if getattr(self, "world", 1) > 1:
+            raise ValueError("build_ivf needs world == 1: more than one rank is out of scope")
+        check_build_args(self.hi - self.lo, self.dim, n_lists, iters, train_rows)
+        self.ivf = IvfIndex.build(self.index, n_lists, iters=iters, seed=seed, train_rows=train_rows)
+        return self.ivf.summary()
 
     def get(self, ids: Sequence) -> Dict:
         """-> {ids, metadatas, documents} of the rows with these `chunk_id`s, in the order asked, from the host lists (the shape of one
@@ -521,7 +545,8 @@ class HipCollection:
 
     def query(self, query_embeddings=None, query_texts: Optional[Sequence[str]] = None, n_results: int = 10, reranker=None,
               n_candidates: int = 32, hybrid_alpha: Optional[float] = None, where=None, where_document=None,
-              mmr_lambda: Optional[float] = None, group_by=None, chunks_per_group: int = 1, min_score=None) -> Dict:
+              mmr_lambda: Optional[float] = None, group_by=None, chunks_per_group: int = 1, min_score=None,
+              nprobe: Optional[int] = None) -> Dict:
         """Between the encoded queries and the rerank step this is the pipeline `search_queries` runs too: `retrieval.RowFilters` builds
         the row bitmaps, `retrieval.retrieve` searches, picks by MMR and fuses.
         `reranker` (a `rerank.HipCrossEncoder`; needs `query_texts`): the search fetches `n_candidates` (<= 32) rows per query,
@@ -581,13 +606,25 @@ class HipCollection:
         `mmr_lambda`, `group_by` and `min_score` stay refused with `hybrid_alpha`.
         On a collection built with `hybrid_on_device=True`, `hybrid_alpha` takes `n_candidates` up to 1024 (each side's list and the
         fused list a `reranker` receives, whose pairs are then scored 32 at a time) and the fusion runs on the device; beyond 32
-        candidates it raises ValueError with per-query filter lists and with `world > 1`.  Everything else stays as above."""
+        candidates it raises ValueError with per-query filter lists and with `world > 1`.  Everything else stays as above.
+        `nprobe` (an integer in [1, min(128, n_lists)]; None = nothing changes; needs `build_ivf` first): the IVF probe search
+        (INTEGRATION.md "IVF probe search").  Every query is scored against the rows of its `nprobe` nearest lists only
+        (`ivf.IvfIndex.search`, `arx_ivf_search`): the exact top rows among those, with the score bits and the order of the exact
+        search, and an added `ivf_scanned` list holds the rows scored per query.  `nprobe = n_lists` is the exact search.  Composes
+        with a single `where`, `where_document` and the dedup and tombstone keep-bitmap (one bitmap per call), and with `reranker` and
+        `mmr_lambda`, which consume the candidate list (`n_candidates <= 32`).  ValueError, naming the part: per-query filter lists,
+        `hybrid_alpha`, `group_by`, `min_score`, `world > 1`, or a collection without `build_ivf`."""
         import torch
         from .filter_sets import is_per_query
         from .grouping import check_grouped_query
         from .ranging import RERANK_BATCH, check_range_query
         from .retrieval import check_hybrid_on_device, check_shared_query, retrieve
         per_query = is_per_query(where) or is_per_query(where_document)
+        if nprobe is not None:
+            from .ivf import check_query_with_nprobe
+            ivf = getattr(self, "ivf", None)
+            check_query_with_nprobe(nprobe, has_index=ivf is not None, n_lists=getattr(ivf, "n_lists", 0), per_query_filters=per_query,
+                                    hybrid_alpha=hybrid_alpha, group_by=group_by, min_score=min_score, world=getattr(self, "world", 1))
         on_device = hybrid_alpha is not None and getattr(self, "hybrid_on_device", False)
         check_range_query(n_results, ranged=min_score is not None, reranker=reranker, n_candidates=n_candidates, hybrid_alpha=hybrid_alpha,
                           mmr_lambda=mmr_lambda, group_by=group_by, per_query_filters=per_query, world=getattr(self, "world", 1))
@@ -633,7 +670,8 @@ class HipCollection:
         hit = retrieve(self.index, q, self._row_filters(), n_results, n_candidates=n_candidates, reranked=reranker is not None, where=where,
                        where_document=where_document, min_score=min_score, grouped=bool(group_by), chunks_per_group=chunks_per_group,
                        mmr_lambda=mmr_lambda, hybrid_alpha=hybrid_alpha, keyword=self.keyword, query_texts=query_texts,
-                       hybrid_on_device=on_device, world=getattr(self, "world", 1))
+                       hybrid_on_device=on_device, world=getattr(self, "world", 1),
+                       **({} if nprobe is None else {"nprobe": nprobe, "ivf": self.ivf}))
         s, i, hyb, kws = hit.scores, hit.ids, hit.hybrid, hit.keyword
         if reranker is not None:
             from .rerank import rerank_candidates, reorder_by_rerank
@@ -668,6 +706,8 @@ class HipCollection:
             out["group_sizes"] = [[int(n) for n, v in zip(hit.group_sizes[qi], hit.groups[qi]) if v >= 0] for qi in range(q.shape[0])]
         if hit.truncated is not None:
             out["truncated"] = hit.truncated
+        if hit.ivf_scanned is not None:
+            out["ivf_scanned"] = [int(v) for v in hit.ivf_scanned]
         if hit.mmr is not None:
             out["mmr_scores"] = [hit.mmr[qi][i[qi] >= 0].tolist() for qi in range(q.shape[0])]
         if reranker is not None:

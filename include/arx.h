@@ -688,6 +688,48 @@ int32_t arx_cluster_assign_tuned(const void* rows, int64_t n_rows, int32_t dim, 
                                  float max_centroid_norm, int32_t* out_labels, float* out_scores, int64_t* stats, void* ws,
                                  int64_t ws_bytes, float tau_mult, int32_t rows_per_block, void* stream);
 
+/* ---- IVF probe search: exact top-k over the rows of the lists a query probes (csrc/ivf.hip; the host layer is arxiv_rag_amd/ivf.py;
+ * the definition is INTEGRATION.md "IVF probe search") ------------------------------------------------------------------------------
+ * The lists are the member lists of a clustering (topics.members): order[start[c] .. start[c + 1]) are the rows of list c.  The rows
+ * query q SEES are order[j] for j in [start[c], start[c + 1]) over the distinct c in probes[q] that lie in [0, n_lists), restricted to
+ * [0, n_rows) and, when `allow` is given, to rows whose bit is set.  Per query the call returns the best k visible rows by
+ * (exact_row_score desc, row asc), padded with (-inf, -1); ids are row + idx_base; out_scanned[q] is the number of visible rows, each
+ * scored once.  A (query, row) score is exact_row_score (csrc/exact_score.h), the bits of arx_topk_search; the answer equals
+ * arx_topk_search_filtered over the bitmap of the visible rows bit for bit.  Which lists to probe is the caller's choice (the nearest
+ * centroids: ivf.IvfIndex.probe) and the only approximation.
+ *   corpus        device fp16 [n_rows, dim], 16-byte aligned; queries device fp16 [n_queries, dim], 16-byte aligned
+ *   order         device int32 [n_members] (NULL only when n_members == 0); start device int64 [n_lists + 1]
+ *   max_list_rows a bound on the lists' lengths the HOST knows (it sizes the grid: no host read inside the call); a list is read up to
+ *                 its first max_list_rows entries
+ *   probes        device int32 [n_queries, n_probe]
+ *   allow         device uint64 [ceil(n_rows / 64)] or NULL: arx_topk_search_filtered's convention (bit r & 63 of word r >> 6)
+ *   out_scores    device f32 [n_queries, k]; out_ids device int64 [n_queries, k]; out_scanned device int64 [n_queries] or NULL
+ *   ws            device scratch of arx_ivf_workspace_bytes(n_members, n_lists, n_queries, n_probe, dim, k) bytes, 16-byte aligned
+ *                 (-1 for arguments outside the limits below); at most about 50 MB
+ * Three launches per 1024 queries on `stream` (prepare: dedupe the probes, cumulative list lengths; scan: blocks of rows_per_block list
+ * positions x query, 8 lanes per row; merge: any number of partial lists per query), no host synchronisation, no float atomics.  A
+ * query's answer depends on its row of queries, its row of probes, the lists, `allow` and the corpus; not on the batch, its order or
+ * the launch shape.
+ * ARX_ERR_ARG before anything is launched, the message naming the field: k outside 1..32; n_probe outside 1..128; dim not a multiple of
+ * 64 or above 8192; n_lists outside 1..4096; n_rows outside 1..2^31-1; n_members outside 0..2^31-1; max_list_rows outside
+ * 0..n_members; n_queries < 1; a null or misaligned pointer; ws_bytes below the figure above.
+ * order, start and probes are device data.  Bad values give a defined answer and never an access out of range: a probe outside
+ * [0, n_lists) is ignored; a repeated probe counts once; start is read clamped into [0, n_members] and made non-decreasing
+ * (topics.clamp_starts); an order entry outside [0, n_rows) keeps its place and is skipped.  order should name a row at most once; if
+ * it does not, a row may come back twice. */
+int64_t arx_ivf_workspace_bytes(int64_t n_members, int32_t n_lists, int32_t n_queries, int32_t n_probe, int32_t dim, int32_t k);
+int32_t arx_ivf_search(const void* corpus, int64_t n_rows, int32_t dim, const int32_t* order, int64_t n_members, const int64_t* start,
+                       int32_t n_lists, int64_t max_list_rows, const void* queries, int32_t n_queries, const int32_t* probes,
+                       int32_t n_probe, const uint64_t* allow, int32_t k, float* out_scores, int64_t* out_ids, int64_t* out_scanned,
+                       int64_t idx_base, void* ws, int64_t ws_bytes, void* stream);
+/* The same with the scan's launch shape chosen: rows_per_block list positions per block, 0 (default: 128, growing to 1024 while the
+ * grid holds more than 2048 blocks) or a multiple of 64 in 64..2^20; raised where the workspace could not hold the partial lists.  Same
+ * bits for every choice. */
+int32_t arx_ivf_search_tuned(const void* corpus, int64_t n_rows, int32_t dim, const int32_t* order, int64_t n_members, const int64_t* start,
+                             int32_t n_lists, int64_t max_list_rows, const void* queries, int32_t n_queries, const int32_t* probes,
+                             int32_t n_probe, const uint64_t* allow, int32_t k, float* out_scores, int64_t* out_ids,
+                             int64_t* out_scanned, int64_t idx_base, void* ws, int64_t ws_bytes, int32_t rows_per_block, void* stream);
+
 /* ---- MMR diversified re-ordering of a query's search candidates (csrc/mmr.hip; the definition is INTEGRATION.md "MMR") -----------
  * arx_gather_rows: out[s] (device fp16 [count, dim]) = shard row ids[s] - idx_base where that row lies in [0, n_rows), all zeros
  * otherwise (id -1, a row another rank owns: the ranks' buffers then add up to the rows, arxiv_rag_amd/mmr.py).  shard device fp16

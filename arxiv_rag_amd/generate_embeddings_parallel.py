@@ -743,8 +743,10 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
     `nprobe` with `ivf_lists` (None = nothing changes): the IVF probe search (INTEGRATION.md "IVF probe search").  An `ivf.IvfIndex` with
     `ivf_lists` lists is built over the shard (`ivf_iters`, `ivf_seed`) and every query is scored against the rows of its `nprobe` nearest
     lists only, filters applied as without it; every entry of the results then carries `ivf_scanned`, the rows scored.  Composes with
-    `where` (one dict), `where_document`, `keep_mask`, `reranker` and `mmr_lambda`.  Not together with `hybrid_alpha`, `group_by_paper`,
-    `min_score`, a per-query `where` list or more than one rank."""
+    `where` (one dict, or a list with one filter per query: one IVF call per batch whatever the number of distinct filters),
+    `where_document`, `keep_mask`, `reranker`, `mmr_lambda` and `min_score` (`top_k` then at most 32).  With a `where` list or `min_score`
+    the entries also carry `ivf_hits`, the exact number of visible chunks at or above the threshold (without one: the rows scored), and
+    with `min_score` `truncated` (`ivf_hits > top_k`).  Not together with `hybrid_alpha`, `group_by_paper` or more than one rank."""
     from .retrieval import RowFilters, check_hybrid_on_device, check_shared_query, retrieve
     if keyword_build_on_device and hybrid_alpha is None:
         raise ValueError("keyword_build_on_device needs hybrid_alpha: it chooses where the BM25 keyword index is built")
@@ -757,15 +759,16 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
         from .ranging import check_range_query
         if reranker is not None:
             raise ValueError("min_score cannot be combined with reranker here: reranking a long range list is out of scope for search_queries")
-        check_range_query(top_k, ranged=True, hybrid_alpha=hybrid_alpha, mmr_lambda=mmr_lambda, group_by=group_by_paper,
-                          per_query_filters=isinstance(where, (list, tuple)), world=int(os.environ.get("WORLD_SIZE", "1")))
+        check_range_query(top_k, ranged=True, hybrid_alpha=hybrid_alpha, mmr_lambda=mmr_lambda, group_by=group_by_paper,    # (IVF: a bitmap per query)
+                          per_query_filters=isinstance(where, (list, tuple)) and nprobe is None, world=int(os.environ.get("WORLD_SIZE", "1")))
     if nprobe is not None or ivf_lists is not None:
         from .ivf import check_build_args, check_query_with_nprobe
         if nprobe is None or ivf_lists is None:
             raise ValueError("nprobe and ivf_lists go together: the lists to build and how many of them a query probes")
         check_query_with_nprobe(nprobe, has_index=True, n_lists=int(ivf_lists), per_query_filters=isinstance(where, (list, tuple)),
                                 hybrid_alpha=hybrid_alpha, group_by=group_by_paper, min_score=min_score,
-                                world=int(os.environ.get("WORLD_SIZE", "1")))
+                                world=int(os.environ.get("WORLD_SIZE", "1")), n_width=top_k if min_score is not None else 1,
+                                allow_per_query_filters=True, allow_min_score=True)
         check_build_args(int(shard.rows.shape[0]), int(shard.rows.shape[1]), ivf_lists, ivf_iters, None)
     if where_on_device and where is None:
         raise ValueError("where_on_device needs where: it chooses where the where filters are evaluated")
@@ -836,7 +839,8 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
         dist.all_gather_object(parts, names, group=host_group())
         names = {k: v for part in parts for k, v in part.items()}
     results = []
-    scanned_of = (lambda qi: {}) if hit.ivf_scanned is None else (lambda qi: {"ivf_scanned": int(hit.ivf_scanned[qi])})
+    scanned_of = (lambda qi: {}) if hit.ivf_scanned is None else (lambda qi: {"ivf_scanned": int(hit.ivf_scanned[qi]),
+                                                                              **({} if hit.ivf_hits is None else {"ivf_hits": int(hit.ivf_hits[qi])})})
 
     def hybrid_fields(qi, p):                                # (null, not NaN, in the JSON file)
         if hyb is None:

@@ -10,8 +10,11 @@ the rows of those lists: which rows a query may see is the approximation, everyt
 every other search here (`exact_row_score`, score desc, row asc), so the answer equals `ShardIndex.search(allow=...)` over the
 bitmap of the probed lists' rows, bit for bit.  `nprobe = n_lists` is the exact search.
 
-`check_probe_args`, `probe_bitmaps_host` and `search_host` restate the refusals and the definition with numpy (for the tests; the
-product path never calls the last two).
+`search_many` is `search` with a row filter per query and a score threshold per query (`arx_ivf_search_multi`): one call per batch
+whatever the number of distinct filters, and `hits`, the exact number of rows at or above the threshold, as a fourth result.
+
+`check_probe_args`, `probe_bitmaps_host`, `search_host` and `search_many_host` restate the refusals and the definitions with numpy (for
+the tests; the product path never calls the last three).
 """
 from __future__ import annotations
 
@@ -53,15 +56,19 @@ def check_build_args(n_rows: int, dim: int, n_lists, iters, train_rows) -> int:
 
 
 def check_query_with_nprobe(nprobe, *, has_index: bool, n_lists: int = 0, per_query_filters: bool = False, hybrid_alpha=None, group_by=None,
-                            min_score=None, world: int = 1, n_width: int = 1) -> None:
-    """The refusals of `query(nprobe=...)`, `retrieve` and `search_queries`, each a ValueError naming the part, before any launch."""
-    if per_query_filters:
+                            min_score=None, world: int = 1, n_width: int = 1, allow_per_query_filters: bool = False,
+                            allow_min_score: bool = False) -> None:
+    """The refusals of `query(nprobe=...)`, `retrieve` and `search_queries`, each a ValueError naming the part, before any launch.
+    `allow_per_query_filters` / `allow_min_score` (default off): `retrieve` and `search_queries`, which route such a batch through
+    `IvfIndex.search_many`, pass them, and per-query filter lists / `min_score` are then let through; everything else is refused as
+    without them (`HipCollection.query` does not pass them)."""
+    if per_query_filters and not allow_per_query_filters:
         raise ValueError("nprobe cannot be combined with per-query filter lists: the IVF search takes one bitmap per call")
     if hybrid_alpha is not None:
         raise ValueError("nprobe cannot be combined with hybrid_alpha: the BM25 keyword search has no inverted lists of topics")
     if group_by:
         raise ValueError("nprobe cannot be combined with group_by: the grouped search reads every row")
-    if min_score is not None:
+    if min_score is not None and not allow_min_score:
         raise ValueError("nprobe cannot be combined with min_score: the range search reads every row")
     if world > 1:
         raise ValueError("nprobe needs world == 1: more than one rank is out of scope")
@@ -126,6 +133,57 @@ def search_host(X, order, start, probes, Q, k: int, allow=None):
     return scores, ids, scanned
 
 
+def _thresholds(min_score, nq: int) -> np.ndarray:
+    """f32 [nq] from a float or one value per query."""
+    ms = np.asarray(min_score, dtype=np.float32)
+    if ms.ndim == 0:
+        ms = np.full(nq, ms, np.float32)
+    if ms.shape != (nq,):
+        raise ValueError(f"min_score has shape {tuple(ms.shape)}: a float or one entry per query ({nq},)")
+    return np.ascontiguousarray(ms)
+
+
+def search_many_host(X, order, start, probes, Q, k: int, allows=None, filter_of=None, min_score=None):
+    """(scores f32 [nq, k], ids int64 [nq, k], scanned int64 [nq], hits int64 [nq]): what `arx_ivf_search_multi` returns with
+    idx_base = 0, bit for bit.  `allows`: None (no filter; `filter_of` is ignored), bool masks [F, n_rows] or bitmap words (int64 /
+    uint64 [F, ceil(n_rows / 64)]); `filter_of` int [nq]: query q sees the rows of `search_host` under `allows[filter_of[q]]`, and no
+    row when `filter_of[q]` lies outside [0, F).  `scanned` counts the visible rows.  `min_score`: None, a float or one per query; a
+    visible row qualifies when its f32 score `>=` the query's f32 threshold (a NaN on either side: not), and with None every visible
+    row qualifies.  `hits` counts the qualifying rows (with None: `hits == scanned`); the list is their best k by (score desc, row
+    asc), `lexsort`ed from `topics.exact_scores_host`."""
+    from .mutation import unpack_rows
+    from .topics import exact_scores_host
+    X, Q, probes = np.asarray(X), np.asarray(Q), np.asarray(probes)
+    n_rows, nq = X.shape[0], Q.shape[0]
+    masks = None
+    if allows is not None:
+        allows = np.asarray(allows)
+        assert allows.ndim == 2 and filter_of is not None
+        masks = allows if allows.dtype == bool else np.stack([unpack_rows(a, n_rows) for a in allows]) if allows.shape[0] else np.zeros((0, n_rows), bool)
+        filter_of = np.asarray(filter_of, dtype=np.int64)
+        assert filter_of.shape == (nq,)
+    thr = None if min_score is None else _thresholds(min_score, nq)
+    scores = np.full((nq, k), -np.inf, np.float32)
+    ids = np.full((nq, k), -1, np.int64)
+    scanned, hits = np.zeros(nq, np.int64), np.zeros(nq, np.int64)
+    for q in range(nq):
+        rows = _visible_rows(order, start, probes[q], n_rows)
+        if masks is not None:
+            f = int(filter_of[q])
+            rows = rows[masks[f][rows]] if 0 <= f < masks.shape[0] else rows[:0]
+        scanned[q] = hits[q] = rows.shape[0]
+        if rows.shape[0] == 0:
+            continue
+        sc = exact_scores_host(X[rows], Q[q:q + 1])[:, 0].astype(np.float32, copy=False)
+        if thr is not None:
+            ok = sc >= thr[q]                                    # the f32 compare: False where either side is NaN
+            rows, sc = rows[ok], sc[ok]
+            hits[q] = rows.shape[0]
+        best = np.lexsort((rows, -sc))[:k]                       # score desc, row asc
+        scores[q, :best.shape[0]], ids[q, :best.shape[0]] = sc[best], rows[best]
+    return scores, ids, scanned, hits
+
+
 # ---- the device path ---------------------------------------------------------------------------------------------------------------
 def ivf_search(corpus, order, start, max_list_rows: int, q, probes, k: int, allow=None, idx_base: int = 0, rows_per_block: Optional[int] = None,
                ws=None, n_rows: Optional[int] = None):
@@ -167,6 +225,61 @@ def ivf_search(corpus, order, start, max_list_rows: int, q, probes, k: int, allo
         else:
             _lib.check(lib.arx_ivf_search_tuned(*head, int(rows_per_block), stream), "arx_ivf_search_tuned")
     return scores, ids, scanned
+
+
+def ivf_search_multi(corpus, order, start, max_list_rows: int, q, probes, k: int, allows=None, filter_of=None, min_score=None, idx_base: int = 0,
+                     rows_per_block: Optional[int] = None, ws=None, n_rows: Optional[int] = None, _n_filters: Optional[int] = None):
+    """`arx_ivf_search_multi` (or, with `rows_per_block` given, `arx_ivf_search_multi_tuned`) on the current stream: `ivf_search` with
+    a bitmap per query and a threshold per query.  `allows` int64 / uint64 device [n_filters, ceil(n_rows / 64)] or None, `filter_of`
+    int32 device [nq] (query q is restricted by `allows[filter_of[q]]`; outside [0, n_filters): the query sees no row), `min_score`
+    float32 device [nq] or None -> (scores f32 [nq, k], ids int64 [nq, k], scanned int64 [nq], hits int64 [nq]) on the device; `hits`
+    is the exact number of visible rows with score >= the query's threshold (without `min_score`: `scanned`), the lists hold the best k
+    of those.  The library checks the contract; a refusal is an `ArxError` naming the field (`_n_filters`: a test hook, the n_filters
+    the library is told instead of `allows.shape[0]`)."""
+    import torch
+    from . import _lib
+    lib = _lib.load()
+    n_rows = int(corpus.shape[0]) if n_rows is None else int(n_rows)
+    dim, nq, n_probe = int(corpus.shape[1]), int(q.shape[0]), int(probes.shape[1])
+    n_members, n_lists = int(order.shape[0]), int(start.shape[0]) - 1
+    assert corpus.is_cuda and corpus.dtype == torch.float16 and corpus.is_contiguous()
+    assert q.is_cuda and q.dtype == torch.float16 and q.dim() == 2 and q.shape[1] == dim and q.is_contiguous()
+    assert order.is_cuda and order.dtype == torch.int32 and order.dim() == 1 and order.is_contiguous()
+    assert start.is_cuda and start.dtype == torch.int64 and start.dim() == 1 and start.is_contiguous()
+    assert probes.is_cuda and probes.dtype == torch.int32 and probes.shape == (nq, n_probe) and probes.is_contiguous()
+    n_filters = 0
+    if allows is not None:
+        assert allows.is_cuda and allows.dtype in (torch.int64, torch.uint64) and allows.is_contiguous()
+        assert allows.dim() == 2 and allows.shape[1] == (n_rows + 63) // 64
+        n_filters = int(allows.shape[0])
+    if _n_filters is not None:
+        n_filters = int(_n_filters)
+    if filter_of is not None:
+        assert filter_of.is_cuda and filter_of.dtype == torch.int32 and filter_of.shape == (nq,) and filter_of.is_contiguous()
+    if min_score is not None:
+        assert min_score.is_cuda and min_score.dtype == torch.float32 and min_score.shape == (nq,) and min_score.is_contiguous()
+    scores = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+    ids = torch.empty((nq, k), dtype=torch.int64, device=q.device)
+    scanned = torch.empty((nq,), dtype=torch.int64, device=q.device)
+    hits = torch.empty((nq,), dtype=torch.int64, device=q.device)
+    if nq == 0:
+        return scores, ids, scanned, hits
+    need = lib.arx_ivf_multi_workspace_bytes(n_members, n_lists, nq, n_probe, dim, k)
+    if need < 0:
+        raise _lib.ArxError(f"arx_ivf_search_multi: unsupported shape n_members={n_members} n_lists={n_lists} nq={nq} n_probe={n_probe} dim={dim} k={k}")
+    if ws is None or ws.numel() * ws.element_size() < need:
+        ws = torch.empty(need, dtype=torch.uint8, device=q.device)
+    with torch.cuda.device(q.device):
+        stream = torch.cuda.current_stream(q.device).cuda_stream
+        head = (corpus.data_ptr(), n_rows, dim, order.data_ptr() if n_members else None, n_members, start.data_ptr(), n_lists, int(max_list_rows),
+                q.data_ptr(), nq, probes.data_ptr(), n_probe, None if allows is None else allows.data_ptr(), n_filters,
+                None if filter_of is None else filter_of.data_ptr(), None if min_score is None else min_score.data_ptr(), int(k),
+                scores.data_ptr(), ids.data_ptr(), scanned.data_ptr(), hits.data_ptr(), int(idx_base), ws.data_ptr(), ws.numel() * ws.element_size())
+        if rows_per_block is None:
+            _lib.check(lib.arx_ivf_search_multi(*head, stream), "arx_ivf_search_multi")
+        else:
+            _lib.check(lib.arx_ivf_search_multi_tuned(*head, int(rows_per_block), stream), "arx_ivf_search_multi_tuned")
+    return scores, ids, scanned, hits
 
 
 class IvfIndex:
@@ -249,6 +362,40 @@ class IvfIndex:
             self._ws = torch.empty(need, dtype=torch.uint8, device=q.device)
         return ivf_search(self.index.corpus, self.order, self.start, self.max_list_rows, q, probes, int(k), allow=allow, idx_base=self.index.idx_base,
                           rows_per_block=rows_per_block, ws=self._ws, n_rows=self.index.n_rows)
+
+    def search_many(self, q, k: int, nprobe: int, allows=None, filter_of=None, min_score=None, probes=None, rows_per_block: Optional[int] = None):
+        """(scores f32 [nq, k], ids int64 [nq, k], scanned int64 [nq], hits int64 [nq]) on the device: `search` with a bitmap per
+        query and a threshold per query, in one call whatever the number of distinct filters (`arx_ivf_search_multi`).  `allows`:
+        int64 / uint64 device [n_filters, ceil(n_rows / 64)] with `filter_of` int32 device [nq] (a value outside [0, n_filters): that
+        query sees no row), or None.  `min_score`: None, a float, or a sequence or tensor of one per query; a visible row qualifies
+        when its f32 score is >= the threshold (NaN on either side: not).  `hits` is the exact number of qualifying rows (without
+        `min_score`: `scanned`), the lists their best k.  Reuses the index's cached workspace."""
+        import torch
+        check_probe_args(k, nprobe, self.n_lists)
+        nq = int(q.shape[0])
+        if probes is None:
+            probes = self.probe(q, nprobe)
+        if allows is not None:
+            if not (torch.is_tensor(allows) and allows.dim() == 2 and allows.shape[0] >= 1):
+                raise ValueError("allows must be a 2-d device tensor [n_filters >= 1, ceil(n_rows / 64)]")
+            if filter_of is None:
+                raise ValueError("allows needs filter_of: one filter index per query")
+        if min_score is not None:
+            if torch.is_tensor(min_score):
+                ms = min_score.to(device=q.device, dtype=torch.float32)
+                if ms.dim() == 0:
+                    ms = ms.expand(nq)
+                if ms.shape != (nq,):
+                    raise ValueError(f"min_score has shape {tuple(ms.shape)}: a float or one entry per query ({nq},)")
+            else:
+                ms = torch.from_numpy(_thresholds(min_score, nq)).to(q.device)
+            min_score = ms.contiguous()
+        need = self.index.lib.arx_ivf_multi_workspace_bytes(int(self.order.shape[0]), self.n_lists, max(nq, 1), int(nprobe), self.index.dim, int(k))
+        if need > 0 and (self._ws is None or self._ws.numel() < need):
+            self._ws = torch.empty(need, dtype=torch.uint8, device=q.device)
+        return ivf_search_multi(self.index.corpus, self.order, self.start, self.max_list_rows, q, probes, int(k), allows=allows, filter_of=filter_of,
+                                min_score=min_score, idx_base=self.index.idx_base, rows_per_block=rows_per_block, ws=self._ws,
+                                n_rows=self.index.n_rows)
 
 
 def label_rows(X, centroids_f16):

@@ -198,6 +198,7 @@ class Retrieved:
     hybrid: Optional[np.ndarray] = None          # hybrid_alpha: the fused scores ...
     keyword: Optional[np.ndarray] = None         # ... and the BM25 ones (nan where the row was not in the keyword list)
     ivf_scanned: Optional[np.ndarray] = None     # nprobe: int64 [Q], the rows scored for every query
+    ivf_hits: Optional[np.ndarray] = None        # nprobe with per-query filters or min_score: int64 [Q], the rows at or above the threshold
 
 
 def retrieve(index, q, filters: RowFilters, n_results: int, *, n_candidates: int = 32, reranked: bool = False, where=None, where_document=None,
@@ -219,8 +220,13 @@ def retrieve(index, q, filters: RowFilters, n_results: int, *, n_candidates: int
     search takes one bitmap per call) or with `world > 1` ranks (a cross-rank merge of long lists is out of scope).
     `nprobe` (None = nothing changes) with `ivf` (an `ivf.IvfIndex` over `index`): the IVF probe search (INTEGRATION.md "IVF probe
     search"): the exact top-k of the rows of every query's `nprobe` nearest lists, under the one bitmap of `where`, `where_document`
-    and the keep-mask; `ivf_scanned` holds the rows scored.  MMR and a reranker consume its candidate list as any other.  ValueError
-    (`ivf.check_query_with_nprobe`): per-query filter lists, `hybrid_alpha`, `grouped`, `min_score`, `world > 1`, no `ivf`."""
+    and the keep-mask; `ivf_scanned` holds the rows scored.  MMR and a reranker consume its candidate list as any other.  With
+    per-query `where` / `where_document` lists (the bitmaps of `filters.per_query`, the keep-mask and-ed into each) or with `min_score`
+    (a float or one per query; the width is the top-k search's, at most 32) the batch is one
+    `IvfIndex.search_many` call whatever the number of distinct filters: only rows at or above the threshold come back, `ivf_hits`
+    holds their exact number per query (without `min_score`: the rows scored) and, with `min_score`, `truncated` is
+    `ivf_hits > width`.  ValueError (`ivf.check_query_with_nprobe`): `hybrid_alpha`, `grouped`, `world > 1`, no `ivf`, a width above
+    32."""
     import torch
     from .filter_sets import is_per_query
     nq = q.shape[0]
@@ -229,14 +235,31 @@ def retrieve(index, q, filters: RowFilters, n_results: int, *, n_candidates: int
         from .ivf import check_query_with_nprobe
         check_query_with_nprobe(nprobe, has_index=ivf is not None, n_lists=getattr(ivf, "n_lists", 0),
                                 per_query_filters=is_per_query(where) or is_per_query(where_document), hybrid_alpha=hybrid_alpha,
-                                group_by=grouped, min_score=min_score, world=world, n_width=k)
+                                group_by=grouped, min_score=min_score, world=world, n_width=k, allow_per_query_filters=True,
+                                allow_min_score=True)
     out = Retrieved(None, None)
     kw_filter_of = None
     on_device = hybrid_alpha is not None and bool(hybrid_on_device)
     if on_device:
         check_hybrid_on_device(n_candidates, per_query_filters=is_per_query(where) or is_per_query(where_document), world=world)
     long_lists = on_device and n_candidates > HYBRID_HOST_CANDIDATES
-    if is_per_query(where) or is_per_query(where_document):
+    if nprobe is not None and (min_score is not None or is_per_query(where) or is_per_query(where_document)):
+        if is_per_query(where) or is_per_query(where_document):  # one IVF call per batch, whatever the number of distinct filters
+            bitmaps, filter_of, _ = filters.per_query(nq, where, where_document)
+            allows = bitmaps if torch.is_tensor(bitmaps) else torch.stack(list(bitmaps)).contiguous()
+            fo = torch.tensor(list(filter_of), dtype=torch.int32, device=q.device)
+        else:
+            allow, _ = filters.allow_of(where, where_document)
+            allows = None if allow is None else allow[None].contiguous()
+            fo = None if allow is None else torch.zeros(nq, dtype=torch.int32, device=q.device)
+        if min_score is not None:
+            from .ranging import thresholds
+            min_score = thresholds(min_score, nq)
+        s, i, scanned, hits = ivf.search_many(q, k, int(nprobe), allows=allows, filter_of=fo, min_score=min_score)
+        out.ivf_scanned, out.ivf_hits = scanned.cpu().numpy(), hits.cpu().numpy()
+        if min_score is not None:
+            out.truncated = (out.ivf_hits > k).tolist()
+    elif is_per_query(where) or is_per_query(where_document):
         from .index import search_filtered_grouped
         bitmaps, filter_of, counts = filters.per_query(nq, where, where_document)
         s, i = search_filtered_grouped(index, q, k, bitmaps, filter_of, counts)

@@ -729,6 +729,44 @@ int32_t arx_ivf_search_tuned(const void* corpus, int64_t n_rows, int32_t dim, co
                              int32_t n_lists, int64_t max_list_rows, const void* queries, int32_t n_queries, const int32_t* probes,
                              int32_t n_probe, const uint64_t* allow, int32_t k, float* out_scores, int64_t* out_ids,
                              int64_t* out_scanned, int64_t idx_base, void* ws, int64_t ws_bytes, int32_t rows_per_block, void* stream);
+/* arx_ivf_search_multi: arx_ivf_search with a row filter per query and a score threshold per query, in the same three launches (a scan
+ * block serves one query, so both are values the block loads once).  The arguments of arx_ivf_search, with after `allow`:
+ *   allow         device uint64 [n_filters][ceil(n_rows / 64)] or NULL; n_filters >= 1 (any number: there is no limit of 64)
+ *   filter_of     device int32 [n_queries]: the bitmap of query q is allow + filter_of[q] * ceil(n_rows / 64)
+ *   min_score     device f32 [n_queries] or NULL (4-byte aligned)
+ * and after out_scanned:
+ *   out_hits      device int64 [n_queries] or NULL
+ * Visible rows: query q sees the rows arx_ivf_search sees with `allow` replaced by its own bitmap.  filter_of is device data: a value
+ * outside [0, n_filters) means the query sees no row (all (-inf, -1), scanned = 0, hits = 0) and nothing is read through it, the
+ * convention of arx_topk_search_filtered_multi and arx_bm25_search_filtered.  allow == NULL means no filter: filter_of is ignored and
+ * may be NULL.  out_scanned[q] is the number of visible rows, each scored once.
+ * With min_score a visible row QUALIFIES when score >= min_score[q], a plain f32 compare on the exact_row_score bits: a NaN score never
+ * qualifies, a NaN threshold qualifies nothing, -inf qualifies every visible row whose score is not NaN.  With min_score == NULL every
+ * visible row qualifies and is ranked as arx_ivf_search ranks it.  (There a NaN score, which needs inf or NaN in the rows or the query,
+ * never starts a merge of the running top-k, and inside one it wins or loses by comparisons that are all false: the rank of such a row
+ * is not defined.  It is whatever arx_ivf_search gives: the code is the same.)
+ * Result: the best k qualifying rows by (score desc, row asc), padded with (-inf, -1), ids + idx_base.  out_hits[q] is the exact number
+ * of qualifying rows, an int64 sum of integer per-block counts with no cap; with min_score == NULL out_hits[q] = out_scanned[q].
+ * With n_filters = 1, filter_of all zero and min_score = NULL the outputs equal arx_ivf_search's with that bitmap bit for bit, for every
+ * rows_per_block.  Query by query the outputs equal those of a call with that query alone: the batch, its order, the other queries'
+ * filters and thresholds and the launch shape do not matter.  No float atomics.
+ *   ws            device scratch of arx_ivf_multi_workspace_bytes(...) bytes, 16-byte aligned: arx_ivf_workspace_bytes of the same
+ *                 arguments + 4 bytes per (partial list, query) slot, rounded up to 256 (the blocks' counts of qualifying rows), where
+ *                 slots = clamp(ceil(n_members / 64) * min(n_queries, 1024), min(n_queries, 1024), 2^17); -1 outside the limits
+ * ARX_ERR_ARG, the message naming the field: everything arx_ivf_search_tuned refuses; with allow given, n_filters < 1 or a null
+ * filter_of; a filter_of or min_score that is not 4-byte aligned; ws_bytes below the figure above. */
+int64_t arx_ivf_multi_workspace_bytes(int64_t n_members, int32_t n_lists, int32_t n_queries, int32_t n_probe, int32_t dim, int32_t k);
+int32_t arx_ivf_search_multi(const void* corpus, int64_t n_rows, int32_t dim, const int32_t* order, int64_t n_members, const int64_t* start,
+                             int32_t n_lists, int64_t max_list_rows, const void* queries, int32_t n_queries, const int32_t* probes,
+                             int32_t n_probe, const uint64_t* allow, int32_t n_filters, const int32_t* filter_of, const float* min_score,
+                             int32_t k, float* out_scores, int64_t* out_ids, int64_t* out_scanned, int64_t* out_hits, int64_t idx_base,
+                             void* ws, int64_t ws_bytes, void* stream);
+int32_t arx_ivf_search_multi_tuned(const void* corpus, int64_t n_rows, int32_t dim, const int32_t* order, int64_t n_members,
+                                   const int64_t* start, int32_t n_lists, int64_t max_list_rows, const void* queries, int32_t n_queries,
+                                   const int32_t* probes, int32_t n_probe, const uint64_t* allow, int32_t n_filters,
+                                   const int32_t* filter_of, const float* min_score, int32_t k, float* out_scores, int64_t* out_ids,
+                                   int64_t* out_scanned, int64_t* out_hits, int64_t idx_base, void* ws, int64_t ws_bytes,
+                                   int32_t rows_per_block, void* stream);
 
 /* ---- MMR diversified re-ordering of a query's search candidates (csrc/mmr.hip; the definition is INTEGRATION.md "MMR") -----------
  * arx_gather_rows: out[s] (device fp16 [count, dim]) = shard row ids[s] - idx_base where that row lies in [0, n_rows), all zeros

@@ -14,8 +14,8 @@
 // next cluster's first slot (ceil(m / 256) <= floor((s + m) / 256) - floor(s / 256) + 1), so the slots are distinct, lie below
 // ceil(n_members / 256) + C (the workspace) and need no prefix sum: the first launch covers every slot, a block finds the cluster of a
 // slot by binary search over s and leaves alone a slot no run owns (the second pass never reads it).  The host writes no run table.
-// s itself is a running maximum over C + 1 values: every block of the first launch scans them into LDS (4 (C + 1) bytes, beside the
-// 256 x dim x 2 bytes a run reads), a block of the second reduces the two values it needs.
+// s itself is a running maximum over C + 1 values (list_starts.h, shared with ivf.hip): every block of the first launch scans them into
+// LDS (scan_starts: 4 (C + 1) bytes, beside the 256 x dim x 2 bytes a run reads), a block of the second reduces the two values it needs.
 // Launch shape of the partials: a thread owns 8 consecutive dims of one run (one 16-byte load per row), dim / 8 threads make a run, a
 // block carries `runs_per_block` runs side by side so that small dims still fill its waves (dim 64: 8 lanes a run, 32 runs in a
 // 256-thread block); with fewer threads than that, a thread takes several (run, 8 dims) units one after the other.  The loads of 8
@@ -29,42 +29,13 @@
 // A cluster that is empty (s[c + 1] == s[c], start clamped below at 0) or whose norm is 0 or not finite keeps prev[c] bit for bit.
 // out_f16 = the f32 centroid rounded to nearest even.
 #include "arx_common.h"
+#include "list_starts.h"
 
 namespace {
 
 constexpr int CL_RUN = 256;                                   // members of a run
 constexpr int CL_DEPTH = 8;                                   // rows whose loads are in flight ahead of the ordered adds
 constexpr int CL_DIM_MAX = 8192, CL_C_MAX = 4096;
-
-__device__ __forceinline__ int clamp_start(long long v, int n_members) {
-    return v < 0 ? 0 : (v > n_members ? n_members : (int)v);
-}
-
-// s_start[0 .. C] = running maximum of the clamped start values (one block; bt a multiple of 64, at most 1024)
-__device__ __forceinline__ void scan_starts(const int64_t* __restrict__ start, int C, int n_members, int* s_start, int* s_wave) {
-    const int tid = threadIdx.x, bt = blockDim.x, lane = tid & 63, wave = tid >> 6, n = C + 1;
-    const int seg = (n + bt - 1) / bt;
-    const int a = tid * seg < n ? tid * seg : n, b = a + seg < n ? a + seg : n;
-    int mine = 0;
-    for (int i = a; i < b; ++i) {
-        const int v = clamp_start(start[i], n_members);
-        mine = v > mine ? v : mine;
-        s_start[i] = mine;                                    // (the segment's own running maximum; what came before is folded in below)
-    }
-    int inc = mine;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int up = __shfl_up(inc, o);
-        if (lane >= o) inc = up > inc ? up : inc;
-    }
-    if (lane == 63) s_wave[wave] = inc;
-    __syncthreads();
-    int before = __shfl_up(inc, 1);                           // the maximum of the lanes below, then of the waves below
-    if (lane == 0) before = 0;
-    for (int w = 0; w < wave; ++w) before = s_wave[w] > before ? s_wave[w] : before;
-    for (int i = a; i < b; ++i) s_start[i] = s_start[i] > before ? s_start[i] : before;
-    __syncthreads();
-}
 
 __global__ __launch_bounds__(1024) void cluster_partials_kernel(const f16_t* __restrict__ rows, int64_t n_rows, int dim, const int* __restrict__ order, int n_members,
                                         const int64_t* __restrict__ start, int C, float* __restrict__ partials, int n_slots,

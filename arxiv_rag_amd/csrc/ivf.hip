@@ -6,8 +6,8 @@
 // to rows whose bit is set.  Which lists a query probes is the caller's approximation; everything here is exact: a (query, row) score is
 // exact_row_score (exact_score.h), the order is (score desc, row asc), and the answer is what arx_topk_search_filtered gives for the
 // bitmap of those rows, bit for bit.
-//   prepare   one block per query.  `start` clamped into [0, n_members] and made non-decreasing (a block-wide prefix maximum in LDS), the
-//             probes deduped (an entry equal to an earlier one, or outside [0, n_lists), gets length 0), every list cut at max_list_rows
+//   prepare   one block per query.  `start` clamped into [0, n_members] and made non-decreasing (list_starts.h's scan_starts, the block-
+//             wide prefix maximum in LDS that cluster.hip reads the same lists with), the probes deduped (an entry equal to an earlier one, or outside [0, n_lists), gets length 0), every list cut at max_list_rows
 //             entries -> cum[q][0 .. n_probe] the cumulative lengths, beg[q][i] the first `order` position of probe i's list.  A position
 //             of the query's concatenated list maps to (probe, offset) by a binary search over cum.  The clamped lists are disjoint
 //             stretches of `order`, so a query's total is at most n_members.
@@ -36,13 +36,15 @@
 //   hits[q]       the exact number of qualifying rows: an int64 sum of the blocks' integer counts, no cap.  With min_score == NULL
 //                 hits[q] = scanned[q] (every visible row qualifies, whatever its score).
 // With n_filters = 1, filter_of all zero and min_score = NULL the outputs equal arx_ivf_search's with that bitmap bit for bit, for every
-// rows_per_block; query by query the outputs equal those of a call with that query alone.  The scan is one template: <false, false> is
-// the kernel arx_ivf_search runs, <true, THR> adds the per-query bitmap and, with THR, the threshold and the count of qualifying rows.
+// rows_per_block; query by query the outputs equal those of a call with that query alone.  Both entry points run the same kernels:
+// arx_ivf_search is the call with filter_of = NULL (one bitmap or none, a block-uniform test in the scan), no threshold and no hits.  The
+// scan is one template on THR: <true>, launched when min_score is given, adds the threshold and the count of qualifying rows.
 #include <math.h>
 
 #include "arx_common.h"
 #include "gemm.h"
 #include "gemm8.h"
+#include "list_starts.h"
 #include "search_consts.h"
 
 namespace {      // the headers also define non-template kernels: internal linkage keeps this object's copies apart from search.hip's
@@ -52,7 +54,6 @@ namespace {      // the headers also define non-template kernels: internal linka
 
 constexpr int IVF_PROBE_MAX = 128, IVF_LISTS_MAX = 4096;
 constexpr int IVF_PREP_NT = 1024;
-constexpr int IVF_PREP_PER = (IVF_LISTS_MAX + 1 + IVF_PREP_NT - 1) / IVF_PREP_NT;      // `start` entries a prepare thread owns (5)
 constexpr int IVF_SCAN_NW = 4, IVF_MERGE_NW = 8;
 constexpr int64_t IVF_SLOTS_MAX = 1ll << 17;      // (part, query) lists the workspace holds at most: 50 MB at k = 32
 constexpr int IVF_RPB_DEFAULT = 128;              // 1 query x 32 probes x 2 400 rows = 600 blocks: two per CU and more
@@ -63,33 +64,12 @@ constexpr int IVF_RPB_LIMIT = 1 << 20;
 __global__ __launch_bounds__(IVF_PREP_NT) void ivf_prepare_kernel(const int64_t* __restrict__ start, int n_lists, int64_t n_members,
                                                                    int64_t max_list_rows, const int32_t* __restrict__ probes, int n_probe,
                                                                    int32_t* __restrict__ cum, int32_t* __restrict__ beg) {
-    __shared__ int32_t cs[IVF_LISTS_MAX + 1];      // start, clamped and non-decreasing
-    __shared__ int32_t wmax[IVF_PREP_NT / 64];
+    __shared__ int cs[IVF_LISTS_MAX + 1];          // start, clamped and non-decreasing
+    __shared__ int wmax[IVF_PREP_NT / 64];
     __shared__ int32_t pr[IVF_PROBE_MAX], len[IVF_PROBE_MAX];
-    const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int n = n_lists + 1;
-    const int a = tid * IVF_PREP_PER, b = a + IVF_PREP_PER < n ? a + IVF_PREP_PER : n;
-    int32_t run = 0;
-    for (int i = a; i < b; ++i) {
-        const int64_t v = start[i];
-        const int32_t c = (int32_t)(v < 0 ? 0 : (v > n_members ? n_members : v));
-        run = run > c ? run : c;
-        cs[i] = run;
-    }
-    int32_t inc = run;                                         // inclusive prefix maximum inside the wave, then over the waves
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int32_t t = __shfl_up(inc, o);
-        if (lane >= o) inc = inc > t ? inc : t;
-    }
-    if (lane == 63) wmax[w] = inc;
+    const int q = blockIdx.x, tid = threadIdx.x;
     if (tid < n_probe) pr[tid] = probes[(int64_t)q * n_probe + tid];
-    __syncthreads();
-    int32_t before = __shfl_up(inc, 1);
-    if (lane == 0) before = 0;
-    for (int ww = 0; ww < w; ++ww) before = before > wmax[ww] ? before : wmax[ww];
-    for (int i = a; i < b; ++i) cs[i] = cs[i] > before ? cs[i] : before;
-    __syncthreads();
+    scan_starts(start, n_lists, (int)n_members, cs, wmax);    // (n_members < 2^31: ivf_run; ends in a barrier, which covers pr too)
     if (tid < n_probe) {
         const int32_t c = pr[tid];
         bool use = c >= 0 && c < n_lists;
@@ -107,9 +87,10 @@ __global__ __launch_bounds__(IVF_PREP_NT) void ivf_prepare_kernel(const int64_t*
     }
 }
 
-// MULTI: the block's bitmap is allow + filter_of[q] * words (a filter_of outside [0, n_filters): the block scores nothing and writes an
-// empty list).  THR (with MULTI): a row qualifies when its score >= min_score[q]; part_m holds the block's count of those.
-template <bool MULTI, bool THR>
+// filter_of (NULL: one bitmap for every query, or none): the block's bitmap is allow + filter_of[q] * words (a filter_of outside
+// [0, n_filters): the block scores nothing and writes an empty list).  THR: a row qualifies when its score >= min_score[q]; part_m holds
+// the block's count of those.
+template <bool THR>
 __global__ __launch_bounds__(IVF_SCAN_NW * 64) void ivf_scan_kernel(const f16_t* __restrict__ C, int64_t n_rows, int D,
                                                                      const int32_t* __restrict__ order, const f16_t* __restrict__ Q, int nq,
                                                                      const int32_t* __restrict__ cum, const int32_t* __restrict__ beg, int n_probe,
@@ -117,7 +98,6 @@ __global__ __launch_bounds__(IVF_SCAN_NW * 64) void ivf_scan_kernel(const f16_t*
                                                                      const int32_t* __restrict__ filter_of, const float* __restrict__ min_score,
                                                                      int k, int rpb, float* __restrict__ part_s, int64_t* __restrict__ part_i,
                                                                      int32_t* __restrict__ part_n, int32_t* __restrict__ part_m) {
-    static_assert(MULTI || !THR, "a threshold comes with the per-query arguments");
     constexpr int NW = IVF_SCAN_NW;
     const int q = blockIdx.y, p = blockIdx.x;
     const int64_t total = cum[(int64_t)q * (n_probe + 1) + n_probe];
@@ -125,14 +105,12 @@ __global__ __launch_bounds__(IVF_SCAN_NW * 64) void ivf_scan_kernel(const f16_t*
     if (lo >= total) return;                                   // block-uniform, before any barrier
     int64_t hi = lo + rpb < total ? lo + rpb : total;
     float thr = 0.f;
-    if constexpr (MULTI) {                                     // the query's own bitmap and threshold: block-uniform, loaded once
-        if (allow) {
-            const int32_t f = filter_of[q];
-            if (f >= 0 && f < n_filters) allow += (int64_t)f * ((n_rows + 63) >> 6);
-            else hi = lo;                                      // no row: the loop below does not run, the list stays (-inf, -1), 0 rows
-        }
-        if constexpr (THR) thr = min_score[q];
+    if (allow && filter_of) {                                  // the query's own bitmap and threshold: block-uniform, loaded once
+        const int32_t f = filter_of[q];
+        if (f >= 0 && f < n_filters) allow += (int64_t)f * ((n_rows + 63) >> 6);
+        else hi = lo;                                          // no row: the loop below does not run, the list stays (-inf, -1), 0 rows
     }
+    if constexpr (THR) thr = min_score[q];
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ float w_s[NW][KMAX];
     __shared__ int64_t w_i[NW][KMAX];
@@ -284,13 +262,13 @@ IvfWs ivf_layout(int64_t n_members, int n_queries, int n_probe, int k, bool mult
     return w;
 }
 
-// The per-query arguments of arx_ivf_search_multi; `on` = false is arx_ivf_search (one bitmap, no threshold, no hits).
-struct IvfMulti { bool on; int32_t n_filters; const int32_t* filter_of; const float* min_score; int64_t* out_hits; };
-
-int32_t ivf_run(const void* corpus, int64_t n_rows, int32_t dim, const int32_t* order, int64_t n_members, const int64_t* start, int32_t n_lists,
-                int64_t max_list_rows, const void* queries, int32_t n_queries, const int32_t* probes, int32_t n_probe, const uint64_t* allow,
-                const IvfMulti& M, int32_t k, float* out_scores, int64_t* out_ids, int64_t* out_scanned, int64_t idx_base, void* ws,
-                int64_t ws_bytes, int32_t rows_per_block, void* stream) {
+// multi: arx_ivf_search_multi's workspace layout and its checks of the per-query arguments.  arx_ivf_search is multi = false with
+// n_filters = 1, filter_of = min_score = out_hits = NULL (one bitmap, no threshold, no hits).
+int32_t ivf_run(bool multi, const void* corpus, int64_t n_rows, int32_t dim, const int32_t* order, int64_t n_members, const int64_t* start,
+                int32_t n_lists, int64_t max_list_rows, const void* queries, int32_t n_queries, const int32_t* probes, int32_t n_probe,
+                const uint64_t* allow, int32_t n_filters, const int32_t* filter_of, const float* min_score, int32_t k, float* out_scores,
+                int64_t* out_ids, int64_t* out_scanned, int64_t* out_hits, int64_t idx_base, void* ws, int64_t ws_bytes, int32_t rows_per_block,
+                void* stream) {
     ARX_REQUIRE(k >= 1 && k <= KMAX, "k=%d out of range 1..%d", k, KMAX);
     ARX_REQUIRE(n_probe >= 1 && n_probe <= IVF_PROBE_MAX, "n_probe=%d out of range 1..%d", n_probe, IVF_PROBE_MAX);
     ARX_REQUIRE(dim > 0 && dim % 64 == 0 && dim <= 8192, "dim=%d must be a multiple of 64, at most 8192", dim);
@@ -303,16 +281,17 @@ int32_t ivf_run(const void* corpus, int64_t n_rows, int32_t dim, const int32_t* 
                 "rows_per_block=%d: 0 (default) or a multiple of 64 in 64..%d", rows_per_block, IVF_RPB_LIMIT);
     ARX_REQUIRE(corpus && start && queries && probes && out_scores && out_ids && ws && (order || n_members == 0), "null pointer argument");
     ARX_REQUIRE(((uintptr_t)corpus | (uintptr_t)queries | (uintptr_t)ws) % 16 == 0, "corpus, queries and ws must be 16-byte aligned");
-    if (M.on && allow) {
-        ARX_REQUIRE(M.n_filters >= 1, "n_filters=%d: at least one bitmap when allow is given", M.n_filters);
-        ARX_REQUIRE(M.filter_of != nullptr, "filter_of is null: allow needs one filter index per query");
-        ARX_REQUIRE((int64_t)M.n_filters <= INT64_MAX / ((n_rows + 63) >> 6), "n_filters=%d: n_filters * ceil(n_rows / 64) overflows int64", M.n_filters);
-        ARX_REQUIRE((uintptr_t)M.filter_of % 4 == 0, "filter_of must be 4-byte aligned");
+    if (multi && allow) {
+        ARX_REQUIRE(n_filters >= 1, "n_filters=%d: at least one bitmap when allow is given", n_filters);
+        ARX_REQUIRE(filter_of != nullptr, "filter_of is null: allow needs one filter index per query");
+        ARX_REQUIRE((int64_t)n_filters <= INT64_MAX / ((n_rows + 63) >> 6), "n_filters=%d: n_filters * ceil(n_rows / 64) overflows int64", n_filters);
+        ARX_REQUIRE((uintptr_t)filter_of % 4 == 0, "filter_of must be 4-byte aligned");
     }
-    if (M.on && M.min_score) ARX_REQUIRE((uintptr_t)M.min_score % 4 == 0, "min_score must be 4-byte aligned");
-    const IvfWs L = ivf_layout(n_members, n_queries, n_probe, k, M.on);
+    if (min_score) ARX_REQUIRE((uintptr_t)min_score % 4 == 0, "min_score must be 4-byte aligned");
+    if (!allow) filter_of = nullptr;                           // no filter: filter_of is ignored
+    const IvfWs L = ivf_layout(n_members, n_queries, n_probe, k, multi);
     ARX_REQUIRE(ws_bytes >= L.total, "workspace too small: %lld < %lld (%s)", (long long)ws_bytes, (long long)L.total,
-                M.on ? "arx_ivf_multi_workspace_bytes" : "arx_ivf_workspace_bytes");
+                multi ? "arx_ivf_multi_workspace_bytes" : "arx_ivf_workspace_bytes");
     hipStream_t st = (hipStream_t)stream;
     char* wsb = (char*)ws;
     int32_t* cum = (int32_t*)(wsb + L.cum);
@@ -320,9 +299,8 @@ int32_t ivf_run(const void* corpus, int64_t n_rows, int32_t dim, const int32_t* 
     float* part_s = (float*)(wsb + L.part_s);
     int64_t* part_i = (int64_t*)(wsb + L.part_i);
     int32_t* part_n = (int32_t*)(wsb + L.part_n);
-    const bool thr = M.on && M.min_score;
+    const bool thr = multi && min_score;                       // (part_m exists in the multi layout alone)
     int32_t* part_m = thr ? (int32_t*)(wsb + L.part_m) : nullptr;
-    const int32_t* filter_of = M.on && allow ? M.filter_of : nullptr;
     // positions a query's lists can hold: n_probe lists of at most max_list_rows entries, disjoint stretches of `order`
     const int64_t P = (int64_t)n_probe * max_list_rows < n_members ? (int64_t)n_probe * max_list_rows : n_members;
     const size_t smem = (((size_t)dim * 2 + 15) & ~(size_t)15) + IVF_SCAN_NW * GROUP_ROWS * 4;
@@ -340,19 +318,17 @@ int32_t ivf_run(const void* corpus, int64_t n_rows, int32_t dim, const int32_t* 
         ARX_HIP_CHECK(hipGetLastError());
         const dim3 grid((unsigned)nbx, (unsigned)nq);
         const int32_t* fo = filter_of ? filter_of + q0 : nullptr;
-#define IVF_SCAN(MULTI, THR)                                                                                                                 \
-        ivf_scan_kernel<MULTI, THR><<<grid, IVF_SCAN_NW * 64, smem, st>>>((const f16_t*)corpus, n_rows, dim, order, Q, nq, cum, beg, n_probe, \
-                                                                          allow, M.n_filters, fo, thr ? M.min_score + q0 : nullptr, k,         \
-                                                                          (int)rpb, part_s, part_i, part_n, part_m)
-        if (!M.on) IVF_SCAN(false, false);
-        else if (!thr) IVF_SCAN(true, false);
-        else IVF_SCAN(true, true);
-#undef IVF_SCAN
+        if (thr)
+            ivf_scan_kernel<true><<<grid, IVF_SCAN_NW * 64, smem, st>>>((const f16_t*)corpus, n_rows, dim, order, Q, nq, cum, beg, n_probe, allow,
+                                                                        n_filters, fo, min_score + q0, k, (int)rpb, part_s, part_i, part_n, part_m);
+        else
+            ivf_scan_kernel<false><<<grid, IVF_SCAN_NW * 64, smem, st>>>((const f16_t*)corpus, n_rows, dim, order, Q, nq, cum, beg, n_probe, allow,
+                                                                         n_filters, fo, nullptr, k, (int)rpb, part_s, part_i, part_n, nullptr);
         ARX_HIP_CHECK(hipGetLastError());
         ivf_merge_kernel<<<nq, IVF_MERGE_NW * 64, 0, st>>>(part_s, part_i, part_n, part_m, cum, n_probe, (int)rpb, nq, k, idx_base,
                                                            out_scores + (int64_t)q0 * k, out_ids + (int64_t)q0 * k,
                                                            out_scanned ? out_scanned + q0 : nullptr,
-                                                           M.on && M.out_hits ? M.out_hits + q0 : nullptr);
+                                                           out_hits ? out_hits + q0 : nullptr);
         ARX_HIP_CHECK(hipGetLastError());
     }
     return ARX_OK;
@@ -374,8 +350,8 @@ extern "C" int32_t arx_ivf_search_tuned(const void* corpus, int64_t n_rows, int3
                                         const int32_t* probes, int32_t n_probe, const uint64_t* allow, int32_t k, float* out_scores,
                                         int64_t* out_ids, int64_t* out_scanned, int64_t idx_base, void* ws, int64_t ws_bytes,
                                         int32_t rows_per_block, void* stream) {
-    return ivf_run(corpus, n_rows, dim, order, n_members, start, n_lists, max_list_rows, queries, n_queries, probes, n_probe, allow,
-                   IvfMulti{false, 1, nullptr, nullptr, nullptr}, k, out_scores, out_ids, out_scanned, idx_base, ws, ws_bytes, rows_per_block, stream);
+    return ivf_run(false, corpus, n_rows, dim, order, n_members, start, n_lists, max_list_rows, queries, n_queries, probes, n_probe, allow, 1,
+                   nullptr, nullptr, k, out_scores, out_ids, out_scanned, nullptr, idx_base, ws, ws_bytes, rows_per_block, stream);
 }
 
 extern "C" int32_t arx_ivf_search(const void* corpus, int64_t n_rows, int32_t dim, const int32_t* order, int64_t n_members, const int64_t* start,
@@ -392,9 +368,8 @@ extern "C" int32_t arx_ivf_search_multi_tuned(const void* corpus, int64_t n_rows
                                               int32_t n_filters, const int32_t* filter_of, const float* min_score, int32_t k,
                                               float* out_scores, int64_t* out_ids, int64_t* out_scanned, int64_t* out_hits, int64_t idx_base,
                                               void* ws, int64_t ws_bytes, int32_t rows_per_block, void* stream) {
-    return ivf_run(corpus, n_rows, dim, order, n_members, start, n_lists, max_list_rows, queries, n_queries, probes, n_probe, allow,
-                   IvfMulti{true, n_filters, filter_of, min_score, out_hits}, k, out_scores, out_ids, out_scanned, idx_base, ws, ws_bytes,
-                   rows_per_block, stream);
+    return ivf_run(true, corpus, n_rows, dim, order, n_members, start, n_lists, max_list_rows, queries, n_queries, probes, n_probe, allow,
+                   n_filters, filter_of, min_score, k, out_scores, out_ids, out_scanned, out_hits, idx_base, ws, ws_bytes, rows_per_block, stream);
 }
 
 extern "C" int32_t arx_ivf_search_multi(const void* corpus, int64_t n_rows, int32_t dim, const int32_t* order, int64_t n_members,

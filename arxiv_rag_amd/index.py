@@ -13,6 +13,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
+from .ranging import device_thresholds
 
 
 class ShardIndex:
@@ -425,16 +426,7 @@ class ShardIndex:
         q, M = queries_f16, int(max_results)
         assert q.is_cuda and q.dtype == torch.float16 and q.dim() == 2 and q.shape[1] == self.dim and q.is_contiguous()
         nq = q.shape[0]
-        if torch.is_tensor(min_score):
-            ms = min_score.to(device=q.device, dtype=torch.float32)
-        else:
-            import numpy as np
-            ms = torch.from_numpy(np.asarray(min_score, dtype=np.float32)).to(q.device)
-        if ms.dim() == 0:
-            ms = ms.expand(nq)
-        if ms.shape != (nq,):
-            raise ValueError(f"min_score has shape {tuple(ms.shape)}: a float or one entry per query ({nq},)")
-        ms = ms.contiguous()
+        ms = device_thresholds(min_score, nq, q.device)
         if allow is not None:
             self._check_allow(allow)
         need = self.lib.arx_range_workspace_bytes(max(self.n_rows, 1), max(nq, 1), self.dim, M)

@@ -11,10 +11,12 @@ every other search here (`exact_row_score`, score desc, row asc), so the answer 
 bitmap of the probed lists' rows, bit for bit.  `nprobe = n_lists` is the exact search.
 
 `search_many` is `search` with a row filter per query and a score threshold per query (`arx_ivf_search_multi`): one call per batch
-whatever the number of distinct filters, and `hits`, the exact number of rows at or above the threshold, as a fourth result.
+whatever the number of distinct filters, and `hits`, the exact number of rows at or above the threshold, as a fourth result.  Both
+reach the library through `_launch`, the one place that calls it (`ivf_search` and `ivf_search_multi` name the entry point).
 
 `check_probe_args`, `probe_bitmaps_host`, `search_host` and `search_many_host` restate the refusals and the definitions with numpy (for
-the tests; the product path never calls the last three).
+the tests; the product path never calls the last three).  The rows are ranked in one loop, `search_many_host`'s: `search_host` is that
+function with one filter for every query and no threshold.
 """
 from __future__ import annotations
 
@@ -108,39 +110,16 @@ def probe_bitmaps_host(order, start, probes, n_rows: int) -> np.ndarray:
 def search_host(X, order, start, probes, Q, k: int, allow=None):
     """(scores f32 [nq, k], ids int64 [nq, k], scanned int64 [nq]): what `arx_ivf_search` returns with idx_base = 0, bit for bit, from
     `topics.exact_scores_host`.  `X` fp16 [n_rows, dim], `Q` fp16 [nq, dim], `probes` int [nq, nprobe]; `allow`: None, a bool mask
-    [n_rows] or bitmap words (int64 / uint64 [ceil(n_rows / 64)])."""
-    from .mutation import unpack_rows
-    from .topics import exact_scores_host
-    X, Q, probes = np.asarray(X), np.asarray(Q), np.asarray(probes)
-    n_rows, nq = X.shape[0], Q.shape[0]
-    mask = None
-    if allow is not None:
-        allow = np.asarray(allow)
-        mask = allow if allow.dtype == bool else unpack_rows(allow, n_rows)
-    scores = np.full((nq, k), -np.inf, np.float32)
-    ids = np.full((nq, k), -1, np.int64)
-    scanned = np.zeros(nq, np.int64)
-    for q in range(nq):
-        rows = _visible_rows(order, start, probes[q], n_rows)
-        if mask is not None:
-            rows = rows[mask[rows]]
-        scanned[q] = rows.shape[0]
-        if rows.shape[0] == 0:
-            continue
-        sc = exact_scores_host(X[rows], Q[q:q + 1])[:, 0]
-        best = np.lexsort((rows, -sc))[:k]                       # score desc, row asc (-0.0 and +0.0 tie, as the kernel compares them)
-        scores[q, :best.shape[0]], ids[q, :best.shape[0]] = sc[best], rows[best]
-    return scores, ids, scanned
+    [n_rows] or bitmap words (int64 / uint64 [ceil(n_rows / 64)]).  `search_many_host` with that one filter for every query."""
+    nq = np.asarray(Q).shape[0]
+    allows = None if allow is None else np.asarray(allow)[None]
+    return search_many_host(X, order, start, probes, Q, k, allows=allows, filter_of=np.zeros(nq, np.int64))[:3]
 
 
 def _thresholds(min_score, nq: int) -> np.ndarray:
     """f32 [nq] from a float or one value per query."""
-    ms = np.asarray(min_score, dtype=np.float32)
-    if ms.ndim == 0:
-        ms = np.full(nq, ms, np.float32)
-    if ms.shape != (nq,):
-        raise ValueError(f"min_score has shape {tuple(ms.shape)}: a float or one entry per query ({nq},)")
-    return np.ascontiguousarray(ms)
+    from .ranging import thresholds
+    return thresholds(min_score, nq, each="entry")
 
 
 def search_many_host(X, order, start, probes, Q, k: int, allows=None, filter_of=None, min_score=None):
@@ -179,22 +158,20 @@ def search_many_host(X, order, start, probes, Q, k: int, allows=None, filter_of=
             ok = sc >= thr[q]                                    # the f32 compare: False where either side is NaN
             rows, sc = rows[ok], sc[ok]
             hits[q] = rows.shape[0]
-        best = np.lexsort((rows, -sc))[:k]                       # score desc, row asc
+        best = np.lexsort((rows, -sc))[:k]                       # score desc, row asc (-0.0 and +0.0 tie, as the kernel compares them)
         scores[q, :best.shape[0]], ids[q, :best.shape[0]] = sc[best], rows[best]
     return scores, ids, scanned, hits
 
 
 # ---- the device path ---------------------------------------------------------------------------------------------------------------
-def ivf_search(corpus, order, start, max_list_rows: int, q, probes, k: int, allow=None, idx_base: int = 0, rows_per_block: Optional[int] = None,
-               ws=None, n_rows: Optional[int] = None):
-    """`arx_ivf_search` (or, with `rows_per_block` given, `arx_ivf_search_tuned`) on the current stream.  `corpus` fp16 device
-    [n_rows, dim], `order` int32 device [n_members], `start` int64 device [n_lists + 1], `q` fp16 device [nq, dim], `probes` int32 device
-    [nq, nprobe], `allow` int64 / uint64 device words or None -> (scores f32 [nq, k], ids int64 [nq, k], scanned int64 [nq]) on the
-    device.  `ws`: a device uint8 tensor to use as the workspace if it is large enough.  The library checks the contract; a refusal
-    is an `ArxError` naming the field."""
+def _launch(corpus, order, start, max_list_rows, q, probes, k, allow, per_query, idx_base, rows_per_block, ws, n_rows):
+    """The one call into the library.  `per_query` None: `arx_ivf_search[_tuned]`, `allow` one bitmap or None -> (scores, ids, scanned).
+    `per_query` (n_filters, filter_of, min_score): `arx_ivf_search_multi[_tuned]`, `allow` [n_filters, words] or None -> (scores, ids,
+    scanned, hits).  Checks the tensors, allocates the outputs, uses `ws` if it holds the entry's workspace and a new one if not."""
     import torch
     from . import _lib
     lib = _lib.load()
+    name, ws_bytes = ("arx_ivf_search", lib.arx_ivf_workspace_bytes) if per_query is None else ("arx_ivf_search_multi", lib.arx_ivf_multi_workspace_bytes)
     n_rows = int(corpus.shape[0]) if n_rows is None else int(n_rows)
     dim, nq, n_probe = int(corpus.shape[1]), int(q.shape[0]), int(probes.shape[1])
     n_members, n_lists = int(order.shape[0]), int(start.shape[0]) - 1
@@ -204,27 +181,45 @@ def ivf_search(corpus, order, start, max_list_rows: int, q, probes, k: int, allo
     assert start.is_cuda and start.dtype == torch.int64 and start.dim() == 1 and start.is_contiguous()
     assert probes.is_cuda and probes.dtype == torch.int32 and probes.shape == (nq, n_probe) and probes.is_contiguous()
     if allow is not None:
-        assert allow.is_cuda and allow.dtype in (torch.int64, torch.uint64) and allow.is_contiguous() and allow.shape == ((n_rows + 63) // 64,)
-    scores = torch.empty((nq, k), dtype=torch.float32, device=q.device)
-    ids = torch.empty((nq, k), dtype=torch.int64, device=q.device)
-    scanned = torch.empty((nq,), dtype=torch.int64, device=q.device)
+        assert allow.is_cuda and allow.dtype in (torch.int64, torch.uint64) and allow.is_contiguous()
+        assert allow.dim() == (1 if per_query is None else 2) and allow.shape[-1] == (n_rows + 63) // 64
+    n_filters, filter_of, min_score = per_query or (None, None, None)
+    if filter_of is not None:
+        assert filter_of.is_cuda and filter_of.dtype == torch.int32 and filter_of.shape == (nq,) and filter_of.is_contiguous()
+    if min_score is not None:
+        assert min_score.is_cuda and min_score.dtype == torch.float32 and min_score.shape == (nq,) and min_score.is_contiguous()
+    out =[torch.empty((nq, k), dtype=torch.float32, device=q.device), torch.empty((nq, k), dtype=torch.int64, device=q.device)]
+    out += [torch.empty((nq,), dtype=torch.int64, device=q.device) for _ in range(1 if per_query is None else 2)]      # scanned[, hits]
     if nq == 0:
-        return scores, ids, scanned
-    need = lib.arx_ivf_workspace_bytes(n_members, n_lists, nq, n_probe, dim, k)
+        return tuple(out)
+    need = ws_bytes(n_members, n_lists, nq, n_probe, dim, k)
     if need < 0:
-        raise _lib.ArxError(f"arx_ivf_search: unsupported shape n_members={n_members} n_lists={n_lists} nq={nq} n_probe={n_probe} dim={dim} k={k}")
+        raise _lib.ArxError(f"{name}: unsupported shape n_members={n_members} n_lists={n_lists} nq={nq} n_probe={n_probe} dim={dim} k={k}")
     if ws is None or ws.numel() * ws.element_size() < need:
         ws = torch.empty(need, dtype=torch.uint8, device=q.device)
+
+    def ptr(t):
+        return None if t is None else t.data_ptr()
+    args = [corpus.data_ptr(), n_rows, dim, order.data_ptr() if n_members else None, n_members, start.data_ptr(), n_lists, int(max_list_rows),
+            q.data_ptr(), nq, probes.data_ptr(), n_probe, ptr(allow)]
+    if per_query is not None:
+        args += [n_filters, ptr(filter_of), ptr(min_score)]
+    args += [int(k)] + [t.data_ptr() for t in out] + [int(idx_base), ws.data_ptr(), ws.numel() * ws.element_size()]
+    if rows_per_block is not None:
+        name, args = name + "_tuned", args + [int(rows_per_block)]
     with torch.cuda.device(q.device):
-        stream = torch.cuda.current_stream(q.device).cuda_stream
-        head = (corpus.data_ptr(), n_rows, dim, order.data_ptr() if n_members else None, n_members, start.data_ptr(), n_lists, int(max_list_rows),
-                q.data_ptr(), nq, probes.data_ptr(), n_probe, None if allow is None else allow.data_ptr(), int(k), scores.data_ptr(),
-                ids.data_ptr(), scanned.data_ptr(), int(idx_base), ws.data_ptr(), ws.numel() * ws.element_size())
-        if rows_per_block is None:
-            _lib.check(lib.arx_ivf_search(*head, stream), "arx_ivf_search")
-        else:
-            _lib.check(lib.arx_ivf_search_tuned(*head, int(rows_per_block), stream), "arx_ivf_search_tuned")
-    return scores, ids, scanned
+        _lib.check(getattr(lib, name)(*args, torch.cuda.current_stream(q.device).cuda_stream), name)
+    return tuple(out)
+
+
+def ivf_search(corpus, order, start, max_list_rows: int, q, probes, k: int, allow=None, idx_base: int = 0, rows_per_block: Optional[int] = None,
+               ws=None, n_rows: Optional[int] = None):
+    """`arx_ivf_search` (or, with `rows_per_block` given, `arx_ivf_search_tuned`) on the current stream.  `corpus` fp16 device
+    [n_rows, dim], `order` int32 device [n_members], `start` int64 device [n_lists + 1], `q` fp16 device [nq, dim], `probes` int32 device
+    [nq, nprobe], `allow` int64 / uint64 device words or None -> (scores f32 [nq, k], ids int64 [nq, k], scanned int64 [nq]) on the
+    device.  `ws`: a device uint8 tensor to use as the workspace if it is large enough.  The library checks the contract; a refusal
+    is an `ArxError` naming the field."""
+    return _launch(corpus, order, start, max_list_rows, q, probes, k, allow, None, idx_base, rows_per_block, ws, n_rows)
 
 
 def ivf_search_multi(corpus, order, start, max_list_rows: int, q, probes, k: int, allows=None, filter_of=None, min_score=None, idx_base: int = 0,
@@ -236,50 +231,8 @@ def ivf_search_multi(corpus, order, start, max_list_rows: int, q, probes, k: int
     is the exact number of visible rows with score >= the query's threshold (without `min_score`: `scanned`), the lists hold the best k
     of those.  The library checks the contract; a refusal is an `ArxError` naming the field (`_n_filters`: a test hook, the n_filters
     the library is told instead of `allows.shape[0]`)."""
-    import torch
-    from . import _lib
-    lib = _lib.load()
-    n_rows = int(corpus.shape[0]) if n_rows is None else int(n_rows)
-    dim, nq, n_probe = int(corpus.shape[1]), int(q.shape[0]), int(probes.shape[1])
-    n_members, n_lists = int(order.shape[0]), int(start.shape[0]) - 1
-    assert corpus.is_cuda and corpus.dtype == torch.float16 and corpus.is_contiguous()
-    assert q.is_cuda and q.dtype == torch.float16 and q.dim() == 2 and q.shape[1] == dim and q.is_contiguous()
-    assert order.is_cuda and order.dtype == torch.int32 and order.dim() == 1 and order.is_contiguous()
-    assert start.is_cuda and start.dtype == torch.int64 and start.dim() == 1 and start.is_contiguous()
-    assert probes.is_cuda and probes.dtype == torch.int32 and probes.shape == (nq, n_probe) and probes.is_contiguous()
-    n_filters = 0
-    if allows is not None:
-        assert allows.is_cuda and allows.dtype in (torch.int64, torch.uint64) and allows.is_contiguous()
-        assert allows.dim() == 2 and allows.shape[1] == (n_rows + 63) // 64
-        n_filters = int(allows.shape[0])
-    if _n_filters is not None:
-        n_filters = int(_n_filters)
-    if filter_of is not None:
-        assert filter_of.is_cuda and filter_of.dtype == torch.int32 and filter_of.shape == (nq,) and filter_of.is_contiguous()
-    if min_score is not None:
-        assert min_score.is_cuda and min_score.dtype == torch.float32 and min_score.shape == (nq,) and min_score.is_contiguous()
-    scores = torch.empty((nq, k), dtype=torch.float32, device=q.device)
-    ids = torch.empty((nq, k), dtype=torch.int64, device=q.device)
-    scanned = torch.empty((nq,), dtype=torch.int64, device=q.device)
-    hits = torch.empty((nq,), dtype=torch.int64, device=q.device)
-    if nq == 0:
-        return scores, ids, scanned, hits
-    need = lib.arx_ivf_multi_workspace_bytes(n_members, n_lists, nq, n_probe, dim, k)
-    if need < 0:
-        raise _lib.ArxError(f"arx_ivf_search_multi: unsupported shape n_members={n_members} n_lists={n_lists} nq={nq} n_probe={n_probe} dim={dim} k={k}")
-    if ws is None or ws.numel() * ws.element_size() < need:
-        ws = torch.empty(need, dtype=torch.uint8, device=q.device)
-    with torch.cuda.device(q.device):
-        stream = torch.cuda.current_stream(q.device).cuda_stream
-        head = (corpus.data_ptr(), n_rows, dim, order.data_ptr() if n_members else None, n_members, start.data_ptr(), n_lists, int(max_list_rows),
-                q.data_ptr(), nq, probes.data_ptr(), n_probe, None if allows is None else allows.data_ptr(), n_filters,
-                None if filter_of is None else filter_of.data_ptr(), None if min_score is None else min_score.data_ptr(), int(k),
-                scores.data_ptr(), ids.data_ptr(), scanned.data_ptr(), hits.data_ptr(), int(idx_base), ws.data_ptr(), ws.numel() * ws.element_size())
-        if rows_per_block is None:
-            _lib.check(lib.arx_ivf_search_multi(*head, stream), "arx_ivf_search_multi")
-        else:
-            _lib.check(lib.arx_ivf_search_multi_tuned(*head, int(rows_per_block), stream), "arx_ivf_search_multi_tuned")
-    return scores, ids, scanned, hits
+    n_filters = (0 if allows is None else int(allows.shape[0])) if _n_filters is None else int(_n_filters)
+    return _launch(corpus, order, start, max_list_rows, q, probes, k, allows, (n_filters, filter_of, min_score), idx_base, rows_per_block, ws, n_rows)
 
 
 class IvfIndex:
@@ -347,19 +300,25 @@ class IvfIndex:
             _, ids, _ = self.centroids.search_range(q, float("-inf"), int(nprobe))
         return ids.to(torch.int32).contiguous()
 
+    def _prepare(self, q, k: int, nprobe: int, probes, workspace_bytes):
+        """What `search` and `search_many` do first -> the probes: the refusals about k and nprobe, `probe(q, nprobe)` unless `probes`
+        is given, and `_ws` (a uint8 device tensor that only grows) made to hold `workspace_bytes` (the entry point's own) of the call."""
+        check_probe_args(k, nprobe, self.n_lists)
+        if probes is None:
+            probes = self.probe(q, nprobe)
+        need = workspace_bytes(int(self.order.shape[0]), self.n_lists, max(int(q.shape[0]), 1), int(nprobe), self.index.dim, int(k))
+        if need > 0 and (self._ws is None or self._ws.numel() < need):
+            import torch
+            self._ws = torch.empty(need, dtype=torch.uint8, device=q.device)
+        return probes
+
     def search(self, q, k: int, nprobe: int, allow=None, probes=None, rows_per_block: Optional[int] = None):
         """(scores f32 [nq, k], ids int64 [nq, k], scanned int64 [nq]) on the device: the exact top-k of the rows of every query's
         `nprobe` nearest lists (`probes`: int32 device [nq, nprobe] to use instead of `probe(q, nprobe)`), restricted by the bitmap
         `allow` as `ShardIndex.search(allow=...)` restricts; ids = local row + the index's idx_base; `scanned` the rows scored."""
-        check_probe_args(k, nprobe, self.n_lists)
-        if probes is None:
-            probes = self.probe(q, nprobe)
+        probes = self._prepare(q, k, nprobe, probes, self.index.lib.arx_ivf_workspace_bytes)
         if allow is not None:
             self.index._check_allow(allow)
-        need = self.index.lib.arx_ivf_workspace_bytes(int(self.order.shape[0]), self.n_lists, max(int(q.shape[0]), 1), int(nprobe), self.index.dim, int(k))
-        if need > 0 and (self._ws is None or self._ws.numel() < need):
-            import torch
-            self._ws = torch.empty(need, dtype=torch.uint8, device=q.device)
         return ivf_search(self.index.corpus, self.order, self.start, self.max_list_rows, q, probes, int(k), allow=allow, idx_base=self.index.idx_base,
                           rows_per_block=rows_per_block, ws=self._ws, n_rows=self.index.n_rows)
 
@@ -371,28 +330,15 @@ class IvfIndex:
         when its f32 score is >= the threshold (NaN on either side: not).  `hits` is the exact number of qualifying rows (without
         `min_score`: `scanned`), the lists their best k.  Reuses the index's cached workspace."""
         import torch
-        check_probe_args(k, nprobe, self.n_lists)
-        nq = int(q.shape[0])
-        if probes is None:
-            probes = self.probe(q, nprobe)
+        from .ranging import device_thresholds
+        probes = self._prepare(q, k, nprobe, probes, self.index.lib.arx_ivf_multi_workspace_bytes)
         if allows is not None:
             if not (torch.is_tensor(allows) and allows.dim() == 2 and allows.shape[0] >= 1):
                 raise ValueError("allows must be a 2-d device tensor [n_filters >= 1, ceil(n_rows / 64)]")
             if filter_of is None:
                 raise ValueError("allows needs filter_of: one filter index per query")
         if min_score is not None:
-            if torch.is_tensor(min_score):
-                ms = min_score.to(device=q.device, dtype=torch.float32)
-                if ms.dim() == 0:
-                    ms = ms.expand(nq)
-                if ms.shape != (nq,):
-                    raise ValueError(f"min_score has shape {tuple(ms.shape)}: a float or one entry per query ({nq},)")
-            else:
-                ms = torch.from_numpy(_thresholds(min_score, nq)).to(q.device)
-            min_score = ms.contiguous()
-        need = self.index.lib.arx_ivf_multi_workspace_bytes(int(self.order.shape[0]), self.n_lists, max(nq, 1), int(nprobe), self.index.dim, int(k))
-        if need > 0 and (self._ws is None or self._ws.numel() < need):
-            self._ws = torch.empty(need, dtype=torch.uint8, device=q.device)
+            min_score = device_thresholds(min_score, int(q.shape[0]), q.device)
         return ivf_search_multi(self.index.corpus, self.order, self.start, self.max_list_rows, q, probes, int(k), allows=allows, filter_of=filter_of,
                                 min_score=min_score, idx_base=self.index.idx_base, rows_per_block=rows_per_block, ws=self._ws,
                                 n_rows=self.index.n_rows)

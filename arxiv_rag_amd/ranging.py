@@ -10,14 +10,29 @@ RANGE_MAX_RESULTS = 1024      # arx_range_search: rows per query
 RERANK_BATCH = 32             # pairs the cross-encoder scores per batch, whatever the length of the range list
 
 
-def thresholds(min_score, n_queries: int) -> np.ndarray:
-    """`min_score` (a float or one float per query) -> float32 [n_queries]."""
+def thresholds(min_score, n_queries: int, each: str = "float") -> np.ndarray:
+    """`min_score` (a float or one float per query) -> float32 [n_queries].  `each`: the noun of the refusal ("one float per query"
+    from the front ends, "one entry per query" from the searches themselves)."""
     ms = np.asarray(min_score, dtype=np.float32)
     if ms.ndim == 0:
         return np.full(n_queries, ms, np.float32)
     if ms.shape != (n_queries,):
-        raise ValueError(f"min_score has shape {tuple(ms.shape)}: a float or one float per query ({n_queries},)")
+        raise ValueError(f"min_score has shape {tuple(ms.shape)}: a float or one {each} per query ({n_queries},)")
     return np.ascontiguousarray(ms)
+
+
+def device_thresholds(min_score, n_queries: int, device):
+    """`min_score` (a float, anything numpy converts, or a tensor on the host or the device; one value or one per query) ->
+    contiguous float32 device [n_queries], as `ShardIndex.search_range` and `IvfIndex.search_many` hand it to the library."""
+    import torch
+    if not torch.is_tensor(min_score):
+        return torch.from_numpy(thresholds(min_score, n_queries, each="entry")).to(device)
+    ms = min_score.to(device=device, dtype=torch.float32)
+    if ms.dim() == 0:
+        ms = ms.expand(n_queries)
+    if ms.shape != (n_queries,):
+        raise ValueError(f"min_score has shape {tuple(ms.shape)}: a float or one entry per query ({n_queries},)")
+    return ms.contiguous()
 
 
 def check_range_query(n_results: int, *, ranged: bool, reranker=None, n_candidates: int = 32, hybrid_alpha: Optional[float] = None,

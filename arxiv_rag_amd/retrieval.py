@@ -201,6 +201,33 @@ class Retrieved:
     ivf_hits: Optional[np.ndarray] = None        # nprobe with per-query filters or min_score: int64 [Q], the rows at or above the threshold
 
 
+def _retrieve_ivf(ivf, q, k: int, nprobe: int, filters: RowFilters, where, where_document, per_query: bool, min_score, out: Retrieved):
+    """The `nprobe` case of `retrieve` -> (scores, ids) on the device, `out.ivf_scanned` / `ivf_hits` / `truncated` filled: one dict and
+    no `min_score` is `IvfIndex.search`, per-query filter lists or a `min_score` one `IvfIndex.search_many` call."""
+    import torch
+    nq = q.shape[0]
+    if not per_query and min_score is None:
+        s, i, scanned = ivf.search(q, k, nprobe, allow=filters.allow_of(where, where_document)[0])
+        out.ivf_scanned = scanned.cpu().numpy()
+        return s, i
+    if per_query:                                                # one IVF call per batch, whatever the number of distinct filters
+        bitmaps, filter_of, _ = filters.per_query(nq, where, where_document)
+        allows = bitmaps if torch.is_tensor(bitmaps) else torch.stack(list(bitmaps)).contiguous()
+        fo = torch.tensor(list(filter_of), dtype=torch.int32, device=q.device)
+    else:
+        allow, _ = filters.allow_of(where, where_document)
+        allows = None if allow is None else allow[None].contiguous()
+        fo = None if allow is None else torch.zeros(nq, dtype=torch.int32, device=q.device)
+    if min_score is not None:
+        from .ranging import thresholds
+        min_score = thresholds(min_score, nq)
+    s, i, scanned, hits = ivf.search_many(q, k, nprobe, allows=allows, filter_of=fo, min_score=min_score)
+    out.ivf_scanned, out.ivf_hits = scanned.cpu().numpy(), hits.cpu().numpy()
+    if min_score is not None:
+        out.truncated = (out.ivf_hits > k).tolist()
+    return s, i
+
+
 def retrieve(index, q, filters: RowFilters, n_results: int, *, n_candidates: int = 32, reranked: bool = False, where=None, where_document=None,
              min_score=None, grouped: bool = False, chunks_per_group: int = 1, mmr_lambda: Optional[float] = None,
              hybrid_alpha: Optional[float] = None, keyword=None, query_texts: Optional[Sequence[str]] = None,
@@ -231,35 +258,21 @@ def retrieve(index, q, filters: RowFilters, n_results: int, *, n_candidates: int
     from .filter_sets import is_per_query
     nq = q.shape[0]
     k = n_candidates if (reranked or hybrid_alpha is not None or mmr_lambda is not None) else n_results
+    per_query = is_per_query(where) or is_per_query(where_document)
     if nprobe is not None:
         from .ivf import check_query_with_nprobe
-        check_query_with_nprobe(nprobe, has_index=ivf is not None, n_lists=getattr(ivf, "n_lists", 0),
-                                per_query_filters=is_per_query(where) or is_per_query(where_document), hybrid_alpha=hybrid_alpha,
-                                group_by=grouped, min_score=min_score, world=world, n_width=k, allow_per_query_filters=True,
-                                allow_min_score=True)
+        check_query_with_nprobe(nprobe, has_index=ivf is not None, n_lists=getattr(ivf, "n_lists", 0), per_query_filters=per_query,
+                                hybrid_alpha=hybrid_alpha, group_by=grouped, min_score=min_score, world=world, n_width=k,
+                                allow_per_query_filters=True, allow_min_score=True)
     out = Retrieved(None, None)
     kw_filter_of = None
     on_device = hybrid_alpha is not None and bool(hybrid_on_device)
     if on_device:
-        check_hybrid_on_device(n_candidates, per_query_filters=is_per_query(where) or is_per_query(where_document), world=world)
+        check_hybrid_on_device(n_candidates, per_query_filters=per_query, world=world)
     long_lists = on_device and n_candidates > HYBRID_HOST_CANDIDATES
-    if nprobe is not None and (min_score is not None or is_per_query(where) or is_per_query(where_document)):
-        if is_per_query(where) or is_per_query(where_document):  # one IVF call per batch, whatever the number of distinct filters
-            bitmaps, filter_of, _ = filters.per_query(nq, where, where_document)
-            allows = bitmaps if torch.is_tensor(bitmaps) else torch.stack(list(bitmaps)).contiguous()
-            fo = torch.tensor(list(filter_of), dtype=torch.int32, device=q.device)
-        else:
-            allow, _ = filters.allow_of(where, where_document)
-            allows = None if allow is None else allow[None].contiguous()
-            fo = None if allow is None else torch.zeros(nq, dtype=torch.int32, device=q.device)
-        if min_score is not None:
-            from .ranging import thresholds
-            min_score = thresholds(min_score, nq)
-        s, i, scanned, hits = ivf.search_many(q, k, int(nprobe), allows=allows, filter_of=fo, min_score=min_score)
-        out.ivf_scanned, out.ivf_hits = scanned.cpu().numpy(), hits.cpu().numpy()
-        if min_score is not None:
-            out.truncated = (out.ivf_hits > k).tolist()
-    elif is_per_query(where) or is_per_query(where_document):
+    if nprobe is not None:
+        s, i = _retrieve_ivf(ivf, q, k, int(nprobe), filters, where, where_document, per_query, min_score, out)
+    elif per_query:
         from .index import search_filtered_grouped
         bitmaps, filter_of, counts = filters.per_query(nq, where, where_document)
         s, i = search_filtered_grouped(index, q, k, bitmaps, filter_of, counts)
@@ -268,10 +281,7 @@ def retrieve(index, q, filters: RowFilters, n_results: int, *, n_candidates: int
             kw_filter_of = torch.tensor(list(filter_of), dtype=torch.int32, device=q.device)
     else:
         allow, n_allowed = filters.allow_of(where, where_document)
-        if nprobe is not None:
-            s, i, scanned = ivf.search(q, k, int(nprobe), allow=allow)
-            out.ivf_scanned = scanned.cpu().numpy()
-        elif min_score is not None:
+        if min_score is not None:
             from .ranging import thresholds
             s, i, counts = index.search_range(q, thresholds(min_score, nq), n_candidates if reranked else n_results, allow=allow,
                                               n_allowed=n_allowed)

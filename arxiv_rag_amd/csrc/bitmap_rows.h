@@ -1,6 +1,6 @@
 // What the row-bitmap mask policies share (filter.hip, range.hip, grouped.hip: one bitmap per call; filter_multi.hip: a set of them): which
-// bits of a word name rows of the shard, pass A's policy for one bitmap per call, the all-ones bitmap of a call without one, and the
-// exclusive scan of the words' popcounts that turns a bitmap into positions of a row list.
+// bits of a word name rows of the shard, pass A's policy for one bitmap per call, the mask of a call that may come without a bitmap
+// (an all-ones one in its workspace), and the exclusive scan of the words' popcounts that turns a bitmap into positions of a row list.
 // Included inside the including file's anonymous namespace after masked_topk.h; not a stand-alone header.
 #pragma once
 
@@ -10,7 +10,8 @@ __device__ __forceinline__ uint64_t valid_bits(int64_t n_rows, int64_t g) {     
 }
 
 // ---- pass A with one bitmap for every query of the call: the pass-A part of a mask policy (masked_topk.h).  range.hip and grouped.hip,
-// whose tails are their own, use it as it stands; filter.hip's BitmapMask adds the tail's and the exhaustive path's parts ---------------------
+// whose tails are their own, hand it to the kernels as it stands (AllowRows below); filter.hip's BitmapMask adds the tail's and the
+// exhaustive path's parts ---------------------------------------------------------------------------------------------------------------------
 struct BitmapRows {
     const uint64_t* allow;      // bit r & 63 of word r >> 6 = row r is visible
     struct LaneRows {           // the bits of the lane's 16 rows, taken once: they do not depend on the query
@@ -50,6 +51,28 @@ __global__ __launch_bounds__(256) void bitmap_ones_kernel(uint64_t* __restrict__
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i < n_words) words[i] = ~0ull;
 }
+
+// ---- the mask of range.hip and grouped.hip: BitmapRows for pass A and, for the scan driver (masked_topk.h), the host part of a mask
+// policy.  allow == NULL means every row: the call makes an all-ones bitmap in its workspace, ahead of its first slice ------------------------
+struct AllowRows : BitmapRows {
+    int64_t n_allowed;          // the caller's count of the set bits, -1 = unknown: checked, not used
+    uint64_t* ones;             // workspace: the all-ones bitmap `allow` points at when the caller gave none, else null (set by bind)
+
+    bool given() const { return true; }
+    int check(int64_t n_rows) const { ARX_REQUIRE(n_allowed >= -1 && n_allowed <= n_rows, "n_allowed=%lld", (long long)n_allowed); return ARX_OK; }
+    static void own_bytes(const MaskedWs& L, int64_t, int64_t b[2]) { b[0] = L.n_groups * 8; b[1] = 0; }
+    void bind(char* ws, const MaskedWs& L) { ones = allow ? nullptr : (uint64_t*)(ws + L.own[0]); allow = allow ? allow : ones; }
+    int prepare_batch(int q0, int, int64_t n_rows, hipStream_t st) const {
+        const int64_t n_words = (n_rows + GROUP_ROWS - 1) / GROUP_ROWS;
+        if (ones && q0 == 0) {
+            bitmap_ones_kernel<<<cdiv(n_words, 256), 256, 0, st>>>(ones, n_words);
+            ARX_HIP_CHECK(hipGetLastError());
+        }
+        return ARX_OK;
+    }
+    int prepare_lists(int, int, int64_t, int64_t, const int*, hipStream_t) const { return ARX_OK; }
+};
+inline const BitmapRows& pass_a_mask(const AllowRows& mask) { return mask; }      // the kernels take the bitmap alone
 
 // ---- the row list of the exhaustive path --------------------------------------------------------------------------------------------------
 // offsets of the words' rows in the compacted list (exclusive scan of the popcounts; off[n_words] = the number of allowed rows).  One

@@ -5,8 +5,9 @@
 //   paper score    the maximum of score(q, r) over the paper's visible rows; a paper without a visible row does not exist for the query
 //   answer         the P best papers by (paper score desc, row of the best chunk asc), and of each the m best visible chunks by (score desc,
 //                  row asc); (-inf, -1) / -1 padding
-// Pass A is masked_topk.h's masked_groupmax_kernel with bitmap_rows.h's BitmapRows policy (allow == NULL: an all-ones bitmap in the
-// workspace), unchanged.  The tail (grouped_tail_kernel, one block per query) finds its candidate groups by masked_topk.h's stage
+// The host side is masked_topk.h's scan driver (masked_scan) with GroupedSearch below as its search policy and bitmap_rows.h's AllowRows as
+// its mask (allow == NULL: an all-ones bitmap in the workspace).  Pass A is masked_topk.h's masked_groupmax_kernel with bitmap_rows.h's
+// BitmapRows policy, unchanged.  The tail (grouped_tail_kernel, one block per query) finds its candidate groups by masked_topk.h's stage
 // (tail_kth_key, tail_candidates) and folds their rows by paper.  With R = max_run_rows an upper bound on the rows of any run, a run touches
 // at most S = floor((R + 62) / 64) + 1 of the 64-row groups; K = P S.
 // Why the tail is exact: let t be the K-th largest group maximum of the query.  The K groups at or above t each hold a visible row whose
@@ -297,35 +298,68 @@ __global__ __launch_bounds__(FILT_TAIL_NT) void grouped_chunks_kernel(const int6
                  out_s + (int64_t)q * P * m, out_i + (int64_t)q * P * m, out_g + (int64_t)q * P);
 }
 
-// ---- host ---------------------------------------------------------------------------------------------------------------------------------
-struct GroupedWs { int64_t stats, gmax, ones, redo, sel_s, sel_i, part_s, part_i, total, ldg, n_groups; int parts; };
-GroupedWs grouped_layout(int64_t n_rows, int nq, int P) {
-    GroupedWs w;
-    const int qb = nq < QBATCH_MAX ? nq : QBATCH_MAX;
-    w.ldg = round_up64(qb, 64);
-    w.n_groups = (n_rows + GROUP_ROWS - 1) / GROUP_ROWS;
-    const int64_t want = (n_rows + 255) / 256;
-    w.parts = (int)(want < FILT_PARTS_MAX ? want : FILT_PARTS_MAX);
-    int64_t o = 0;
-    auto take = [&](int64_t b) { int64_t r = o; o += round_up64(b, 256); return r; };
-    w.stats = take(64);                                         // at the allocation's start: masked_stats reads it
-    w.gmax = take(w.n_groups * w.ldg * 4);
-    w.ones = take(w.n_groups * 8);
-    w.redo = take((int64_t)qb * 4);
-    w.sel_s = take((int64_t)qb * P * 4);
-    w.sel_i = take((int64_t)qb * P * 8);
-    w.part_s = take((int64_t)w.parts * qb * P * 4);
-    w.part_i = take((int64_t)w.parts * qb * P * 8);
-    w.total = o;
-    return w;
-}
+// ---- the search policy (masked_topk.h: the scan driver) -----------------------------------------------------------------------------------
+struct GroupedSearch {
+    int P, m; const int32_t* group_of; int64_t max_run_rows; float* out_s; int64_t* out_i; int32_t* out_g; int64_t idx_base;
+    float* sel_s; int64_t* sel_i;        // workspace: the merged paper lists [nq][P] of the queries the exhaustive path answers
+    float* part_s; int64_t* part_i;      // workspace: the exhaustive path's per-part paper lists [parts][nq][P]
+    static constexpr const char* workspace_fn = "arx_topk_grouped_workspace_bytes";
+    static constexpr size_t kSmemRaise = 48 * 1024;      // more dynamic LDS than this is asked for before the launch
+
+    bool given() const { return group_of && out_s && out_i && out_g; }
+    int check(int64_t) const {
+        ARX_REQUIRE(P >= 1 && P <= KMAX, "n_groups=%d out of range 1..%d", P, KMAX);
+        ARX_REQUIRE(m >= 1 && m <= GRP_CHUNKS_MAX, "chunks_per_group=%d out of range 1..%d", m, GRP_CHUNKS_MAX);
+        ARX_REQUIRE(max_run_rows >= 1, "max_run_rows=%lld must be at least 1", (long long)max_run_rows);
+        return ARX_OK;
+    }
+    void take_buffers(MaskedWs& w) {
+        sel_s = w.take<float>((int64_t)w.qb * P * 4);
+        sel_i = w.take<int64_t>((int64_t)w.qb * P * 8);
+        part_s = w.take<float>((int64_t)w.parts * w.qb * P * 4);
+        part_i = w.take<int64_t>((int64_t)w.parts * w.qb * P * 8);
+    }
+    // S = the 64-row groups a run of at most max_run_rows rows can touch, K = P S (the clamp only keeps the arithmetic in range)
+    int64_t ksel() const {
+        const int64_t R = max_run_rows < (1ll << 40) ? max_run_rows : (1ll << 40);
+        return (int64_t)P * ((R + 62) / 64 + 1);
+    }
+    int resolve_path(const AllowRows&, int path, int) const { return ksel() > GRP_KSEL_MAX ? 2 : (path ? path : 1); }      // K too large: the whole call
+    int default_cand_cap() const { return FILT_CAND_CAP_DEFAULT; }
+    int launch_tail(const ScanSlice& s, const AllowRows& mask) const {
+        const size_t smem = s.smem_q + (size_t)(FILT_TAIL_NT / 64) * GROUP_ROWS * 4 + (size_t)s.cand_cap * 4;
+        if (smem > kSmemRaise) ARX_HIP_CHECK(arx_func_smem((const void*)grouped_tail_kernel, (int)smem));
+        grouped_tail_kernel<<<s.nq, FILT_TAIL_NT, smem, s.st>>>(s.L.gmax, s.L.ldg, s.L.n_groups, mask.allow, group_of, s.Q, s.C, s.n_rows, s.dim, P, m,
+                                                                (int)ksel(), out_s + (int64_t)s.q0 * P * m, out_i + (int64_t)s.q0 * P * m,
+                                                                out_g + (int64_t)s.q0 * P, idx_base, s.tau_scale, s.cand_cap, s.L.redo, s.L.stats);
+        ARX_HIP_CHECK(hipGetLastError());
+        return ARX_OK;
+    }
+    int launch_exhaustive(const ScanSlice& s, const AllowRows& mask) const {
+        const size_t smem_x = s.smem_q + 4 * GROUP_ROWS * 4;
+        if (smem_x > kSmemRaise) ARX_HIP_CHECK(arx_func_smem((const void*)grouped_exhaustive_kernel, (int)smem_x));
+        grouped_exhaustive_kernel<<<dim3(s.L.parts, s.nq), 256, smem_x, s.st>>>(mask.allow, group_of, s.Q, s.C, s.n_rows, s.dim, s.nq, P, part_s, part_i,
+                                                                                s.only_if, s.gate);
+        ARX_HIP_CHECK(hipGetLastError());
+        filter_merge_kernel<<<cdiv(s.nq, 4), 256, 0, s.st>>>(part_s, part_i, s.L.parts, s.nq, P, sel_s, sel_i, s.only_if, s.gate);
+        ARX_HIP_CHECK(hipGetLastError());
+        const size_t smem_c = s.smem_q + (size_t)(FILT_TAIL_NT / 64) * GROUP_ROWS * 4;
+        if (smem_c > kSmemRaise) ARX_HIP_CHECK(arx_func_smem((const void*)grouped_chunks_kernel, (int)smem_c));
+        grouped_chunks_kernel<<<s.nq, FILT_TAIL_NT, smem_c, s.st>>>(sel_i, mask.allow, group_of, s.Q, s.C, s.n_rows, s.dim, P, m,
+                                                                    out_s + (int64_t)s.q0 * P * m, out_i + (int64_t)s.q0 * P * m,
+                                                                    out_g + (int64_t)s.q0 * P, idx_base, s.only_if, s.gate);
+        ARX_HIP_CHECK(hipGetLastError());
+        return ARX_OK;
+    }
+};
 }      // namespace
 
 extern "C" int64_t arx_topk_grouped_workspace_bytes(int64_t n_rows, int32_t n_queries, int32_t dim, int32_t n_groups, int32_t chunks_per_group) {
     if (n_rows <= 0 || n_rows >= (1ll << 36) || n_queries <= 0 || dim <= 0 || dim % 64 != 0 || dim > 8192 || n_groups <= 0 || n_groups > KMAX ||
         chunks_per_group <= 0 || chunks_per_group > GRP_CHUNKS_MAX)
         return -1;
-    return grouped_layout(n_rows, n_queries, n_groups).total;
+    GroupedSearch search{n_groups};
+    return scan_layout<AllowRows>(search, n_rows, n_queries, nullptr).total;
 }
 
 extern "C" int32_t arx_group_runs_info(const int32_t* group_of, int64_t n_rows, int64_t* out, void* stream) {
@@ -345,76 +379,9 @@ extern "C" int32_t arx_topk_search_grouped_tuned(const void* corpus, int64_t n_r
                                                  int32_t n_groups, int32_t chunks_per_group, float* out_scores, int64_t* out_ids,
                                                  int32_t* out_groups, int64_t idx_base, float max_row_norm, void* ws, int64_t ws_bytes,
                                                  int32_t path, int32_t cand_cap, void* stream) {
-    const int P = n_groups, m = chunks_per_group;
-    ARX_REQUIRE(corpus && group_of && queries && out_scores && out_ids && out_groups && ws, "null pointer argument");
-    ARX_REQUIRE(n_rows > 0 && n_queries > 0, "empty corpus or query set");
-    ARX_REQUIRE(n_rows < (1ll << 36), "n_rows=%lld: group numbers are 32-bit", (long long)n_rows);
-    ARX_REQUIRE(dim > 0 && dim % 64 == 0 && dim <= 8192, "dim=%d must be a multiple of 64", dim);
-    ARX_REQUIRE(P >= 1 && P <= KMAX, "n_groups=%d out of range 1..%d", P, KMAX);
-    ARX_REQUIRE(m >= 1 && m <= GRP_CHUNKS_MAX, "chunks_per_group=%d out of range 1..%d", m, GRP_CHUNKS_MAX);
-    ARX_REQUIRE(max_run_rows >= 1, "max_run_rows=%lld must be at least 1", (long long)max_run_rows);
-    ARX_REQUIRE(n_allowed >= -1 && n_allowed <= n_rows, "n_allowed=%lld", (long long)n_allowed);
-    ARX_REQUIRE(path >= 0 && path <= 2, "path=%d: 0 (library's choice), 1 (scan) or 2 (exhaustive)", path);
-    ARX_REQUIRE(cand_cap >= 0 && cand_cap <= FILT_CAND_CAP_MAX, "cand_cap=%d out of range 0..%d", cand_cap, FILT_CAND_CAP_MAX);
-    ARX_REQUIRE(max_row_norm >= 0.0f && max_row_norm < INFINITY, "max_row_norm=%g: must be a finite bound (0 = unit rows)", (double)max_row_norm);
-    const GroupedWs L = grouped_layout(n_rows, n_queries, P);
-    ARX_REQUIRE(ws_bytes >= L.total, "workspace too small: %lld < %lld (arx_topk_grouped_workspace_bytes)", (long long)ws_bytes, (long long)L.total);
-    hipStream_t st = (hipStream_t)stream;
-    // S = the 64-row groups a run of at most max_run_rows rows can touch, K = P S (the clamp only keeps the arithmetic in range)
-    const int64_t R = max_run_rows < (1ll << 40) ? max_run_rows : (1ll << 40);
-    const int64_t ksel = (int64_t)P * ((R + 62) / 64 + 1);
-    if (path == 0) path = 1;
-    if (ksel > GRP_KSEL_MAX) path = 2;                          // the whole call
-    if (cand_cap == 0) cand_cap = FILT_CAND_CAP_DEFAULT;
-    const f16_t* C = (const f16_t*)corpus;
-    char* wsb = (char*)ws;
-    unsigned long long* stats = (unsigned long long*)(wsb + L.stats);
-    const int* gate = path == 1 ? (const int*)(stats + 2) : nullptr;      // scan: the exhaustive kernels run only after an overflow
-    float* gmax = (float*)(wsb + L.gmax);
-    int32_t* redo = (int32_t*)(wsb + L.redo);
-    float* sel_s = (float*)(wsb + L.sel_s);
-    int64_t* sel_i = (int64_t*)(wsb + L.sel_i);
-    float* part_s = (float*)(wsb + L.part_s);
-    int64_t* part_i = (int64_t*)(wsb + L.part_i);
-    const float tau_scale = masked_tau_scale(dim, max_row_norm);
-    ARX_HIP_CHECK(hipMemsetAsync(stats, 0, 64, st));
-    if (!allow) {                                               // every row: an all-ones bitmap of the call's own
-        uint64_t* ones = (uint64_t*)(wsb + L.ones);
-        bitmap_ones_kernel<<<cdiv(L.n_groups, 256), 256, 0, st>>>(ones, L.n_groups);
-        ARX_HIP_CHECK(hipGetLastError());
-        allow = ones;
-    }
-    const BitmapRows mask{allow};
-    const size_t smem_q = ((size_t)dim * 2 + 15) & ~(size_t)15;
-    for (int q0 = 0; q0 < n_queries; q0 += QBATCH_MAX) {
-        const int nq = (n_queries - q0) < QBATCH_MAX ? (n_queries - q0) : QBATCH_MAX;
-        const f16_t* Q = (const f16_t*)queries + (int64_t)q0 * dim;
-        float* os = out_scores + (int64_t)q0 * P * m;
-        int64_t* oi = out_ids + (int64_t)q0 * P * m;
-        int32_t* og = out_groups + (int64_t)q0 * P;
-        if (path == 1) {
-            if (const int rc = launch_masked_pass_a(Q, nq, C, n_rows, dim, mask, gmax, L.ldg, st); rc != ARX_OK) return rc;
-            ProfScope ps(ARX_K_SEARCH_RESCORE, st);
-            const size_t smem = smem_q + (size_t)(FILT_TAIL_NT / 64) * GROUP_ROWS * 4 + (size_t)cand_cap * 4;
-            if (smem > 48 * 1024) ARX_HIP_CHECK(arx_func_smem((const void*)grouped_tail_kernel, (int)smem));
-            grouped_tail_kernel<<<nq, FILT_TAIL_NT, smem, st>>>(gmax, L.ldg, L.n_groups, allow, group_of, Q, C, n_rows, dim, P, m, (int)ksel, os, oi,
-                                                                og, idx_base, tau_scale, cand_cap, redo, stats);
-            ARX_HIP_CHECK(hipGetLastError());
-        }
-        // exhaustive over the visible rows: every query (path 2) or the queries the tail flagged (the kernels return at once if none)
-        const int32_t* only_if = path == 1 ? redo : nullptr;
-        const size_t smem_x = smem_q + 4 * GROUP_ROWS * 4;
-        if (smem_x > 48 * 1024) ARX_HIP_CHECK(arx_func_smem((const void*)grouped_exhaustive_kernel, (int)smem_x));
-        grouped_exhaustive_kernel<<<dim3(L.parts, nq), 256, smem_x, st>>>(allow, group_of, Q, C, n_rows, dim, nq, P, part_s, part_i, only_if, gate);
-        ARX_HIP_CHECK(hipGetLastError());
-        filter_merge_kernel<<<cdiv(nq, 4), 256, 0, st>>>(part_s, part_i, L.parts, nq, P, sel_s, sel_i, only_if, gate);
-        ARX_HIP_CHECK(hipGetLastError());
-        const size_t smem_c = smem_q + (size_t)(FILT_TAIL_NT / 64) * GROUP_ROWS * 4;
-        if (smem_c > 48 * 1024) ARX_HIP_CHECK(arx_func_smem((const void*)grouped_chunks_kernel, (int)smem_c));
-        grouped_chunks_kernel<<<nq, FILT_TAIL_NT, smem_c, st>>>(sel_i, allow, group_of, Q, C, n_rows, dim, P, m, os, oi, og, idx_base, only_if, gate);
-        ARX_HIP_CHECK(hipGetLastError());
-    }
-    return ARX_OK;
+    return masked_scan(AllowRows{{allow}, n_allowed},
+                       GroupedSearch{n_groups, chunks_per_group, group_of, max_run_rows, out_scores, out_ids, out_groups, idx_base}, corpus, n_rows,
+                       queries, n_queries, dim, max_row_norm, ws, ws_bytes, path, cand_cap, stream);
 }
 
 extern "C" int32_t arx_topk_search_grouped(const void* corpus, int64_t n_rows, const int32_t* group_of, int64_t max_run_rows,

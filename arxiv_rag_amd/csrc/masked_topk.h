@@ -21,10 +21,19 @@
 //                                      list_row is a load
 // and on the host
 //   given(), check(n_rows)             its own arguments: non-null, in range
-//   choose_path(n_queries)             what path = 0 means
+//   choose_path(n_queries)             what path = 0 means for a top-k search
 //   own_bytes(L, n_rows, b)            its two workspace buffers (between gmax and redo), bind(ws, L) points the mask at them
 //   prepare_batch / prepare_lists      kernels of its own before pass A of a batch / before the exhaustive kernel
 //   kWorkspaceFn                       the name of its arx_topk_*_workspace_bytes, for the error text
+//
+// The host side is ONE scan driver (masked_scan) for every search that reads a row mask: these three, range.hip and grouped.hip.  It owns
+// the protocol their exactness rests on: the common argument checks, the workspace prefix (stats at offset 0, gmax, the mask's buffers,
+// redo) and its reset, gate / only_if, tau_scale, and the loop over slices of QBATCH_MAX queries with pass A, the tail and the gated
+// exhaustive kernels in that order.  What differs comes from a search policy `Search`, a plain host struct passed by value like the mask
+// (TopkSearch for these three): given(), check(n_rows) for its own arguments and limits; take_buffers(L) for its workspace buffers after
+// redo; resolve_path(mask, path, nq) and default_cand_cap() for what path = 0 and cand_cap = 0 mean; launch_tail(slice, mask) and
+// launch_exhaustive(slice, mask) for its kernels of one slice, the merge included; workspace_fn, and kSmemRaise, the dynamic LDS above
+// which its launches ask for more.
 // Included inside the including file's anonymous namespace after search_pass_a.h and search_tail.h; not a stand-alone header.
 #pragma once
 
@@ -392,32 +401,33 @@ __global__ __launch_bounds__(256) void filter_merge_kernel(const float* __restri
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------------
-struct MaskedWs { int64_t stats, gmax, own[2], redo, part_s, part_i, total, ldg, n_groups; int parts; };
-template <class Mask>
-MaskedWs masked_layout(int64_t n_rows, int nq, int k) {
+// The workspace of a scan: the common prefix (stats, gmax, the mask's two buffers, redo), then the search's own buffers in the order it
+// takes them, each rounded up to 256 bytes.  qb = the queries of a slice, parts = the blocks per query of the exhaustive path.
+struct MaskedWs {
+    char* base;                                                 // the allocation; null = sizes only
+    int64_t total, own[2], ldg, n_groups; int qb, parts;
+    unsigned long long* stats; float* gmax; int32_t* redo;
+    template <class T>
+    T* take(int64_t bytes) { const int64_t o = total; total += round_up64(bytes, 256); return base ? (T*)(base + o) : nullptr; }
+};
+// `search.take_buffers(w)` takes the search's buffers (it may lower w.parts first).  With ws = null only the sizes mean anything.
+template <class Mask, class Search>
+MaskedWs scan_layout(Search& search, int64_t n_rows, int nq, char* ws) {
     MaskedWs w;
-    const int qb = nq < QBATCH_MAX ? nq : QBATCH_MAX;
-    w.ldg = round_up64(qb, 64);
+    w.base = ws; w.total = 0;
+    w.qb = nq < QBATCH_MAX ? nq : QBATCH_MAX;
+    w.ldg = round_up64(w.qb, 64);
     w.n_groups = (n_rows + GROUP_ROWS - 1) / GROUP_ROWS;
     const int64_t want = (n_rows + 255) / 256;
     w.parts = (int)(want < FILT_PARTS_MAX ? want : FILT_PARTS_MAX);
-    int64_t o = 0, own[2];
-    auto take = [&](int64_t b) { int64_t r = o; o += round_up64(b, 256); return r; };
-    w.stats = take(64);                                         // at the allocation's start: masked_stats reads it
-    w.gmax = take(w.n_groups * w.ldg * 4);
+    w.stats = w.take<unsigned long long>(64);                   // at the allocation's start: masked_stats reads it
+    w.gmax = w.take<float>(w.n_groups * w.ldg * 4);
+    int64_t own[2];
     Mask::own_bytes(w, n_rows, own);
-    w.own[0] = take(own[0]);
-    w.own[1] = take(own[1]);
-    w.redo = take((int64_t)qb * 4);
-    w.part_s = take((int64_t)w.parts * qb * k * 4);
-    w.part_i = take((int64_t)w.parts * qb * k * 8);
-    w.total = o;
+    for (int i = 0; i < 2; ++i) { w.own[i] = w.total; w.take<char>(own[i]); }
+    w.redo = w.take<int32_t>((int64_t)w.qb * 4);
+    search.take_buffers(w);
     return w;
-}
-template <class Mask>
-int64_t masked_workspace_bytes(int64_t n_rows, int32_t n_queries, int32_t dim, int32_t k) {
-    if (n_rows <= 0 || n_queries <= 0 || dim <= 0 || dim % 64 != 0 || k <= 0 || k > KMAX) return -1;
-    return masked_layout<Mask>(n_rows, n_queries, k).total;
 }
 
 template <int BM, class Mask>
@@ -449,63 +459,111 @@ float masked_tau_scale(int dim, float max_row_norm) {
     return (0.3125f * (float)dim + 4.0f) * 5.9604645e-8f * (max_row_norm > 0.0f ? max_row_norm : 1.0f + 1.0f / 512.0f);
 }
 
-// `mask` arrives with the caller's arguments set; its workspace pointers are bound here.  path / cand_cap = 0: the library's choice.
+// what pass A's kernel takes of a mask: the mask itself, unless a mask with host-only members says otherwise (bitmap_rows.h: AllowRows)
 template <class Mask>
-int masked_search_impl(Mask mask, const void* corpus, int64_t n_rows, const void* queries, int32_t n_queries, int32_t dim, int32_t k,
-                       float* out_scores, int64_t* out_ids, int64_t idx_base, float max_row_norm, void* ws, int64_t ws_bytes, int32_t path,
-                       int32_t cand_cap, void* stream) {
-    ARX_REQUIRE(corpus && mask.given() && queries && out_scores && out_ids && ws, "null pointer argument");
+const Mask& pass_a_mask(const Mask& mask) { return mask; }
+
+// ---- the scan driver: see the header comment -------------------------------------------------------------------------------------------------
+// What a search's launches are given: a slice of at most QBATCH_MAX queries (q0 = its first query in the call: the search advances its
+// own per-query pointers by it; Q = its rows) and what the driver bound for the whole call
+struct ScanSlice {
+    int q0, nq; const f16_t* Q;
+    const MaskedWs& L; const f16_t* C; int64_t n_rows; int dim; float tau_scale; int cand_cap;
+    const int32_t* only_if; const int* gate;      // the exhaustive kernels' restriction: the scan's redo[] and overflow word; null on path 2
+    size_t smem_q;                                // a query row in LDS, rounded up to 16 bytes
+    hipStream_t st;
+};
+// `mask` and `search` arrive with the caller's arguments set; their workspace pointers are bound here.  path / cand_cap = 0: the search's
+// choice.  The tail answers a query or flags it in redo[] and sets the gate word: never an answer from a truncated list.
+template <class Mask, class Search>
+int masked_scan(Mask mask, Search search, const void* corpus, int64_t n_rows, const void* queries, int32_t n_queries, int32_t dim,
+                float max_row_norm, void* ws, int64_t ws_bytes, int32_t path, int32_t cand_cap, void* stream) {
+    ARX_REQUIRE(corpus && mask.given() && queries && search.given() && ws, "null pointer argument");
     ARX_REQUIRE(n_rows > 0 && n_queries > 0, "empty corpus or query set");
+    if (const int rc = search.check(n_rows); rc != ARX_OK) return rc;
     ARX_REQUIRE(n_rows < (1ll << 36), "n_rows=%lld: group numbers are 32-bit", (long long)n_rows);
     ARX_REQUIRE(dim > 0 && dim % 64 == 0 && dim <= 8192, "dim=%d must be a multiple of 64", dim);
-    ARX_REQUIRE(k > 0 && k <= KMAX, "k=%d out of range 1..%d", k, KMAX);
     ARX_REQUIRE(path >= 0 && path <= 2, "path=%d: 0 (library's choice), 1 (masked scan) or 2 (exhaustive)", path);
     ARX_REQUIRE(cand_cap >= 0 && cand_cap <= FILT_CAND_CAP_MAX, "cand_cap=%d out of range 0..%d", cand_cap, FILT_CAND_CAP_MAX);
     if (const int rc = mask.check(n_rows); rc != ARX_OK) return rc;
     ARX_REQUIRE(max_row_norm >= 0.0f && max_row_norm < INFINITY, "max_row_norm=%g: must be a finite bound (0 = unit rows)", (double)max_row_norm);
-    const MaskedWs L = masked_layout<Mask>(n_rows, n_queries, k);
-    ARX_REQUIRE(ws_bytes >= L.total, "workspace too small: %lld < %lld (%s)", (long long)ws_bytes, (long long)L.total, Mask::kWorkspaceFn);
+    const MaskedWs L = scan_layout<Mask>(search, n_rows, n_queries, (char*)ws);
+    ARX_REQUIRE(ws_bytes >= L.total, "workspace too small: %lld < %lld (%s)", (long long)ws_bytes, (long long)L.total, search.workspace_fn);
     hipStream_t st = (hipStream_t)stream;
-    if (path == 0) path = mask.choose_path(n_queries);
-    if (cand_cap == 0) cand_cap = FILT_CAND_CAP_DEFAULT;
-    const f16_t* C = (const f16_t*)corpus;
-    char* wsb = (char*)ws;
-    unsigned long long* stats = (unsigned long long*)(wsb + L.stats);
-    const int* gate = path == 1 ? (const int*)(stats + 2) : nullptr;      // masked scan: the exhaustive kernels run only after an overflow
-    float* gmax = (float*)(wsb + L.gmax);
-    mask.bind(wsb, L);
-    int32_t* redo = (int32_t*)(wsb + L.redo);
-    float* part_s = (float*)(wsb + L.part_s);
-    int64_t* part_i = (int64_t*)(wsb + L.part_i);
-    const float tau_scale = masked_tau_scale(dim, max_row_norm);
-    ARX_HIP_CHECK(hipMemsetAsync(stats, 0, 64, st));
-    const size_t smem_q = ((size_t)dim * 2 + 15) & ~(size_t)15;
-    for (int q0 = 0; q0 < n_queries; q0 += QBATCH_MAX) {
-        const int nq = (n_queries - q0) < QBATCH_MAX ? (n_queries - q0) : QBATCH_MAX;
-        const f16_t* Q = (const f16_t*)queries + (int64_t)q0 * dim;
-        float* os = out_scores + (int64_t)q0 * k;
-        int64_t* oi = out_ids + (int64_t)q0 * k;
-        if (const int rc = mask.prepare_batch(q0, nq, n_rows, st); rc != ARX_OK) return rc;
+    path = search.resolve_path(mask, path, n_queries);
+    if (cand_cap == 0) cand_cap = search.default_cand_cap();
+    mask.bind(L.base, L);
+    const int* gate = path == 1 ? (const int*)(L.stats + 2) : nullptr;      // masked scan: the exhaustive kernels run only after an overflow
+    ScanSlice s{0, 0, nullptr, L, (const f16_t*)corpus, n_rows, dim, masked_tau_scale(dim, max_row_norm), cand_cap,
+                path == 1 ? L.redo : nullptr, gate, ((size_t)dim * 2 + 15) & ~(size_t)15, st};
+    ARX_HIP_CHECK(hipMemsetAsync(L.stats, 0, 64, st));
+    for (s.q0 = 0; s.q0 < n_queries; s.q0 += QBATCH_MAX) {
+        s.nq = (n_queries - s.q0) < QBATCH_MAX ? (n_queries - s.q0) : QBATCH_MAX;
+        s.Q = (const f16_t*)queries + (int64_t)s.q0 * dim;
+        if (const int rc = mask.prepare_batch(s.q0, s.nq, n_rows, st); rc != ARX_OK) return rc;
         if (path == 1) {
-            if (const int rc = launch_masked_pass_a(Q, nq, C, n_rows, dim, mask, gmax, L.ldg, st); rc != ARX_OK) return rc;
+            if (const int rc = launch_masked_pass_a(s.Q, s.nq, s.C, n_rows, dim, pass_a_mask(mask), L.gmax, L.ldg, st); rc != ARX_OK) return rc;
             ProfScope ps(ARX_K_SEARCH_RESCORE, st);
-            const size_t smem = smem_q + (size_t)(FILT_TAIL_NT / 64) * GROUP_ROWS * 4 + (size_t)cand_cap * 4;
-            if (smem > 48 * 1024) ARX_HIP_CHECK(arx_func_smem((const void*)masked_tail_kernel<Mask>, (int)smem));
-            masked_tail_kernel<Mask><<<nq, FILT_TAIL_NT, smem, st>>>(gmax, L.ldg, L.n_groups, mask, Q, C, n_rows, dim, k, os, oi, idx_base, tau_scale,
-                                                                     cand_cap, redo, stats);
-            ARX_HIP_CHECK(hipGetLastError());
+            if (const int rc = search.launch_tail(s, mask); rc != ARX_OK) return rc;
         }
         // exhaustive over the visible rows: every query (path 2) or the queries the tail flagged (the kernels return at once if none)
-        if (const int rc = mask.prepare_lists(q0, path, n_rows, L.n_groups, gate, st); rc != ARX_OK) return rc;
-        const int32_t* only_if = path == 1 ? redo : nullptr;
-        const size_t smem_x = smem_q + 4 * GROUP_ROWS * 4;
-        if (smem_x > 48 * 1024) ARX_HIP_CHECK(arx_func_smem((const void*)masked_exhaustive_kernel<Mask>, (int)smem_x));
-        masked_exhaustive_kernel<Mask><<<dim3(L.parts, nq), 256, smem_x, st>>>(mask, Q, C, dim, nq, k, idx_base, part_s, part_i, only_if, gate);
-        ARX_HIP_CHECK(hipGetLastError());
-        filter_merge_kernel<<<cdiv(nq, 4), 256, 0, st>>>(part_s, part_i, L.parts, nq, k, os, oi, only_if, gate);
-        ARX_HIP_CHECK(hipGetLastError());
+        if (const int rc = mask.prepare_lists(s.q0, path, n_rows, L.n_groups, gate, st); rc != ARX_OK) return rc;
+        if (const int rc = search.launch_exhaustive(s, mask); rc != ARX_OK) return rc;
     }
     return ARX_OK;
+}
+
+// ---- the top-k search policy: masked_tail_kernel, masked_exhaustive_kernel and filter_merge_kernel ---------------------------------------
+struct TopkSearch {
+    int k; float* out_s; int64_t* out_i; int64_t idx_base;
+    const char* workspace_fn;   // the name of the entry point's arx_topk_*_workspace_bytes, for the error text
+    float* part_s; int64_t* part_i;      // workspace: the exhaustive path's per-part lists [parts][nq][k]
+    static constexpr size_t kSmemRaise = 48 * 1024;      // more dynamic LDS than this is asked for before the launch
+
+    bool given() const { return out_s && out_i; }
+    int check(int64_t) const { ARX_REQUIRE(k > 0 && k <= KMAX, "k=%d out of range 1..%d", k, KMAX); return ARX_OK; }
+    void take_buffers(MaskedWs& w) {
+        part_s = w.take<float>((int64_t)w.parts * w.qb * k * 4);
+        part_i = w.take<int64_t>((int64_t)w.parts * w.qb * k * 8);
+    }
+    template <class Mask>
+    int resolve_path(const Mask& mask, int path, int n_queries) const { return path ? path : mask.choose_path(n_queries); }
+    int default_cand_cap() const { return FILT_CAND_CAP_DEFAULT; }
+    template <class Mask>
+    int launch_tail(const ScanSlice& s, const Mask& mask) const {
+        const size_t smem = s.smem_q + (size_t)(FILT_TAIL_NT / 64) * GROUP_ROWS * 4 + (size_t)s.cand_cap * 4;
+        if (smem > kSmemRaise) ARX_HIP_CHECK(arx_func_smem((const void*)masked_tail_kernel<Mask>, (int)smem));
+        masked_tail_kernel<Mask><<<s.nq, FILT_TAIL_NT, smem, s.st>>>(s.L.gmax, s.L.ldg, s.L.n_groups, mask, s.Q, s.C, s.n_rows, s.dim, k,
+                                                                     out_s + (int64_t)s.q0 * k, out_i + (int64_t)s.q0 * k, idx_base, s.tau_scale,
+                                                                     s.cand_cap, s.L.redo, s.L.stats);
+        ARX_HIP_CHECK(hipGetLastError());
+        return ARX_OK;
+    }
+    template <class Mask>
+    int launch_exhaustive(const ScanSlice& s, const Mask& mask) const {
+        const size_t smem_x = s.smem_q + 4 * GROUP_ROWS * 4;
+        if (smem_x > kSmemRaise) ARX_HIP_CHECK(arx_func_smem((const void*)masked_exhaustive_kernel<Mask>, (int)smem_x));
+        masked_exhaustive_kernel<Mask><<<dim3(s.L.parts, s.nq), 256, smem_x, s.st>>>(mask, s.Q, s.C, s.dim, s.nq, k, idx_base, part_s, part_i,
+                                                                                     s.only_if, s.gate);
+        ARX_HIP_CHECK(hipGetLastError());
+        filter_merge_kernel<<<cdiv(s.nq, 4), 256, 0, s.st>>>(part_s, part_i, s.L.parts, s.nq, k, out_s + (int64_t)s.q0 * k,
+                                                             out_i + (int64_t)s.q0 * k, s.only_if, s.gate);
+        ARX_HIP_CHECK(hipGetLastError());
+        return ARX_OK;
+    }
+};
+template <class Mask>
+int64_t masked_workspace_bytes(int64_t n_rows, int32_t n_queries, int32_t dim, int32_t k) {
+    if (n_rows <= 0 || n_queries <= 0 || dim <= 0 || dim % 64 != 0 || k <= 0 || k > KMAX) return -1;
+    TopkSearch search{k};
+    return scan_layout<Mask>(search, n_rows, n_queries, nullptr).total;
+}
+template <class Mask>
+int masked_search_impl(Mask mask, const void* corpus, int64_t n_rows, const void* queries, int32_t n_queries, int32_t dim, int32_t k,
+                       float* out_scores, int64_t* out_ids, int64_t idx_base, float max_row_norm, void* ws, int64_t ws_bytes, int32_t path,
+                       int32_t cand_cap, void* stream) {
+    return masked_scan(mask, TopkSearch{k, out_scores, out_ids, idx_base, Mask::kWorkspaceFn}, corpus, n_rows, queries, n_queries, dim,
+                       max_row_norm, ws, ws_bytes, path, cand_cap, stream);
 }
 
 // the counters of the last search that used workspace `ws`

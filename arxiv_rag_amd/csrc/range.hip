@@ -5,8 +5,9 @@
 //   qualifies      a visible row with score(q, r) >= min_score[q], compared in f32 (-inf: every visible row; +inf or NaN: none)
 //   answer         the best min(count, M) qualifying rows by (score desc, row asc), M = max_results <= 1024, (-inf, -1) padding, and
 //                  out_counts[q] = the number of qualifying rows when that is <= M, M + 1 when more qualify (the list is truncated)
-// Pass A is masked_topk.h's masked_groupmax_kernel with bitmap_rows.h's BitmapRows policy (allow == NULL: an all-ones bitmap in the
-// workspace), unchanged.  The tail (range_tail_kernel, one block per query) finds its candidate groups by masked_topk.h's stage
+// The host side is masked_topk.h's scan driver (masked_scan) with RangeSearch below as its search policy and bitmap_rows.h's AllowRows as
+// its mask (allow == NULL: an all-ones bitmap in the workspace).  Pass A is masked_topk.h's masked_groupmax_kernel with bitmap_rows.h's
+// BitmapRows policy, unchanged.  The tail (range_tail_kernel, one block per query) finds its candidate groups by masked_topk.h's stage
 // (tail_kth_key, tail_candidates) with a threshold of its own; then it keeps a variable, long, ordered list instead of a k <= 32 wave list.
 // Why the tail is exact: pass A and exact_row_score differ by at most tau = tau_scale |q| (masked_tau_scale, masked_topk.h), so a qualifying
 // row has a pass-A score >= min_score - tau and its group's maximum is at least that.  Let t be the (M + 1)-th largest group maximum of
@@ -250,100 +251,63 @@ __global__ __launch_bounds__(RANGE_NT) void range_merge_kernel(const unsigned lo
     range_store(L, c, (int)(total < M + 1 ? total : M + 1), M, idx_base, out_s + (int64_t)q * M, out_i + (int64_t)q * M, out_c + q);
 }
 
-// ---- host ---------------------------------------------------------------------------------------------------------------------------------
-struct RangeWs { int64_t stats, gmax, ones, redo, part_k, part_c, total, ldg, n_groups; int parts; };
-RangeWs range_layout(int64_t n_rows, int nq, int M) {
-    RangeWs w;
-    const int qb = nq < QBATCH_MAX ? nq : QBATCH_MAX;
-    w.ldg = round_up64(qb, 64);
-    w.n_groups = (n_rows + GROUP_ROWS - 1) / GROUP_ROWS;
-    int64_t want = (n_rows + 255) / 256;
-    want = want < FILT_PARTS_MAX ? want : FILT_PARTS_MAX;
-    w.parts = (int)(want < RANGE_PART_KEYS / M ? want : RANGE_PART_KEYS / M);
-    int64_t o = 0;
-    auto take = [&](int64_t b) { int64_t r = o; o += round_up64(b, 256); return r; };
-    w.stats = take(64);                                         // at the allocation's start: masked_stats reads it
-    w.gmax = take(w.n_groups * w.ldg * 4);
-    w.ones = take(w.n_groups * 8);
-    w.redo = take((int64_t)qb * 4);
-    w.part_k = take((int64_t)w.parts * qb * M * 8);
-    w.part_c = take((int64_t)w.parts * qb * 4);
-    w.total = o;
-    return w;
-}
+// ---- the search policy (masked_topk.h: the scan driver) -----------------------------------------------------------------------------------
+struct RangeSearch {
+    int M; const float* min_score; float* out_s; int64_t* out_i; int32_t* out_c; int64_t idx_base;
+    unsigned long long* part_k; int32_t* part_c;      // workspace: the exhaustive path's keys [parts][nq][M] and counts [parts][nq]
+    static constexpr const char* workspace_fn = "arx_range_workspace_bytes";
+    static constexpr size_t kSmemRaise = 32 * 1024;      // more dynamic LDS than this is asked for before the launch
+
+    bool given() const { return min_score && out_s && out_i && out_c; }
+    int check(int64_t n_rows) const {
+        ARX_REQUIRE(n_rows < (1ll << 32), "n_rows=%lld: a row is 32 bits of a sort key (at most 2^32 - 1 rows per shard)", (long long)n_rows);
+        ARX_REQUIRE(M >= 1 && M <= RANGE_MAX_RESULTS, "max_results=%d out of range 1..%d", M, RANGE_MAX_RESULTS);
+        return ARX_OK;
+    }
+    void take_buffers(MaskedWs& w) {
+        if (w.parts > RANGE_PART_KEYS / M) w.parts = RANGE_PART_KEYS / M;
+        part_k = w.take<unsigned long long>((int64_t)w.parts * w.qb * M * 8);
+        part_c = w.take<int32_t>((int64_t)w.parts * w.qb * 4);
+    }
+    int resolve_path(const AllowRows&, int path, int) const { return path ? path : 1; }
+    int default_cand_cap() const { return 2 * (M + 1) + FILT_CAND_CAP_DEFAULT; }      // M + 1 groups reach t by definition: twice that and the masked tail's slack
+    int launch_tail(const ScanSlice& s, const AllowRows& mask) const {
+        const size_t smem = s.smem_q + (size_t)(RANGE_NT / 64) * GROUP_ROWS * 4 + (size_t)s.cand_cap * 4;
+        if (smem > kSmemRaise) ARX_HIP_CHECK(arx_func_smem((const void*)range_tail_kernel, (int)smem));
+        range_tail_kernel<<<s.nq, RANGE_NT, smem, s.st>>>(s.L.gmax, s.L.ldg, s.L.n_groups, mask.allow, s.Q, min_score + s.q0, s.C, s.n_rows, s.dim, M,
+                                                          out_s + (int64_t)s.q0 * M, out_i + (int64_t)s.q0 * M, out_c + s.q0, idx_base,
+                                                          s.tau_scale, s.cand_cap, s.L.redo, s.L.stats);
+        ARX_HIP_CHECK(hipGetLastError());
+        return ARX_OK;
+    }
+    int launch_exhaustive(const ScanSlice& s, const AllowRows& mask) const {
+        const size_t smem_x = s.smem_q + (size_t)(RANGE_NT / 64) * GROUP_ROWS * 4;
+        if (smem_x > kSmemRaise) ARX_HIP_CHECK(arx_func_smem((const void*)range_exhaustive_kernel, (int)smem_x));
+        range_exhaustive_kernel<<<dim3(s.L.parts, s.nq), RANGE_NT, smem_x, s.st>>>(mask.allow, s.Q, min_score + s.q0, s.C, s.n_rows, s.L.n_groups,
+                                                                                   s.dim, s.nq, M, part_k, part_c, s.only_if, s.gate);
+        ARX_HIP_CHECK(hipGetLastError());
+        range_merge_kernel<<<s.nq, RANGE_NT, 0, s.st>>>(part_k, part_c, s.L.parts, s.nq, M, out_s + (int64_t)s.q0 * M, out_i + (int64_t)s.q0 * M,
+                                                        out_c + s.q0, idx_base, s.only_if, s.gate);
+        ARX_HIP_CHECK(hipGetLastError());
+        return ARX_OK;
+    }
+};
 }      // namespace
 
 extern "C" int64_t arx_range_workspace_bytes(int64_t n_rows, int32_t n_queries, int32_t dim, int32_t max_results) {
     if (n_rows <= 0 || n_rows >= (1ll << 32) || n_queries <= 0 || dim <= 0 || dim % 64 != 0 || dim > 8192 || max_results <= 0 ||
         max_results > RANGE_MAX_RESULTS)
         return -1;
-    return range_layout(n_rows, n_queries, max_results).total;
+    RangeSearch search{max_results};
+    return scan_layout<AllowRows>(search, n_rows, n_queries, nullptr).total;
 }
 
 extern "C" int32_t arx_range_search_tuned(const void* corpus, int64_t n_rows, const uint64_t* allow, int64_t n_allowed, const void* queries,
                                           const float* min_score, int32_t n_queries, int32_t dim, int32_t max_results, float* out_scores,
                                           int64_t* out_ids, int32_t* out_counts, int64_t idx_base, float max_row_norm, void* ws,
                                           int64_t ws_bytes, int32_t path, int32_t cand_cap, void* stream) {
-    const int M = max_results;
-    ARX_REQUIRE(corpus && queries && min_score && out_scores && out_ids && out_counts && ws, "null pointer argument");
-    ARX_REQUIRE(n_rows > 0 && n_queries > 0, "empty corpus or query set");
-    ARX_REQUIRE(n_rows < (1ll << 32), "n_rows=%lld: a row is 32 bits of a sort key (at most 2^32 - 1 rows per shard)", (long long)n_rows);
-    ARX_REQUIRE(dim > 0 && dim % 64 == 0 && dim <= 8192, "dim=%d must be a multiple of 64", dim);
-    ARX_REQUIRE(M >= 1 && M <= RANGE_MAX_RESULTS, "max_results=%d out of range 1..%d", M, RANGE_MAX_RESULTS);
-    ARX_REQUIRE(n_allowed >= -1 && n_allowed <= n_rows, "n_allowed=%lld", (long long)n_allowed);
-    ARX_REQUIRE(path >= 0 && path <= 2, "path=%d: 0 (library's choice), 1 (scan) or 2 (exhaustive)", path);
-    ARX_REQUIRE(cand_cap >= 0 && cand_cap <= FILT_CAND_CAP_MAX, "cand_cap=%d out of range 0..%d", cand_cap, FILT_CAND_CAP_MAX);
-    ARX_REQUIRE(max_row_norm >= 0.0f && max_row_norm < INFINITY, "max_row_norm=%g: must be a finite bound (0 = unit rows)", (double)max_row_norm);
-    const RangeWs L = range_layout(n_rows, n_queries, M);
-    ARX_REQUIRE(ws_bytes >= L.total, "workspace too small: %lld < %lld (arx_range_workspace_bytes)", (long long)ws_bytes, (long long)L.total);
-    hipStream_t st = (hipStream_t)stream;
-    if (path == 0) path = 1;
-    if (cand_cap == 0) cand_cap = 2 * (M + 1) + FILT_CAND_CAP_DEFAULT;      // M + 1 groups reach t by definition: twice that and the masked tail's slack
-    const f16_t* C = (const f16_t*)corpus;
-    char* wsb = (char*)ws;
-    unsigned long long* stats = (unsigned long long*)(wsb + L.stats);
-    const int* gate = path == 1 ? (const int*)(stats + 2) : nullptr;      // scan: the exhaustive kernels run only after an overflow
-    float* gmax = (float*)(wsb + L.gmax);
-    int32_t* redo = (int32_t*)(wsb + L.redo);
-    unsigned long long* part_k = (unsigned long long*)(wsb + L.part_k);
-    int32_t* part_c = (int32_t*)(wsb + L.part_c);
-    const float tau_scale = masked_tau_scale(dim, max_row_norm);
-    ARX_HIP_CHECK(hipMemsetAsync(stats, 0, 64, st));
-    if (!allow) {                                               // every row: an all-ones bitmap of the call's own
-        uint64_t* ones = (uint64_t*)(wsb + L.ones);
-        bitmap_ones_kernel<<<cdiv(L.n_groups, 256), 256, 0, st>>>(ones, L.n_groups);
-        ARX_HIP_CHECK(hipGetLastError());
-        allow = ones;
-    }
-    const BitmapRows mask{allow};
-    const size_t smem_q = ((size_t)dim * 2 + 15) & ~(size_t)15;
-    for (int q0 = 0; q0 < n_queries; q0 += QBATCH_MAX) {
-        const int nq = (n_queries - q0) < QBATCH_MAX ? (n_queries - q0) : QBATCH_MAX;
-        const f16_t* Q = (const f16_t*)queries + (int64_t)q0 * dim;
-        const float* ms = min_score + q0;
-        float* os = out_scores + (int64_t)q0 * M;
-        int64_t* oi = out_ids + (int64_t)q0 * M;
-        int32_t* oc = out_counts + q0;
-        if (path == 1) {
-            if (const int rc = launch_masked_pass_a(Q, nq, C, n_rows, dim, mask, gmax, L.ldg, st); rc != ARX_OK) return rc;
-            ProfScope ps(ARX_K_SEARCH_RESCORE, st);
-            const size_t smem = smem_q + (size_t)(RANGE_NT / 64) * GROUP_ROWS * 4 + (size_t)cand_cap * 4;
-            if (smem > 32 * 1024) ARX_HIP_CHECK(arx_func_smem((const void*)range_tail_kernel, (int)smem));
-            range_tail_kernel<<<nq, RANGE_NT, smem, st>>>(gmax, L.ldg, L.n_groups, allow, Q, ms, C, n_rows, dim, M, os, oi, oc, idx_base, tau_scale,
-                                                          cand_cap, redo, stats);
-            ARX_HIP_CHECK(hipGetLastError());
-        }
-        // exhaustive over the visible rows: every query (path 2) or the queries the tail flagged (the kernels return at once if none)
-        const int32_t* only_if = path == 1 ? redo : nullptr;
-        const size_t smem_x = smem_q + (size_t)(RANGE_NT / 64) * GROUP_ROWS * 4;
-        if (smem_x > 32 * 1024) ARX_HIP_CHECK(arx_func_smem((const void*)range_exhaustive_kernel, (int)smem_x));
-        range_exhaustive_kernel<<<dim3(L.parts, nq), RANGE_NT, smem_x, st>>>(allow, Q, ms, C, n_rows, L.n_groups, dim, nq, M, part_k, part_c, only_if,
-                                                                             gate);
-        ARX_HIP_CHECK(hipGetLastError());
-        range_merge_kernel<<<nq, RANGE_NT, 0, st>>>(part_k, part_c, L.parts, nq, M, os, oi, oc, idx_base, only_if, gate);
-        ARX_HIP_CHECK(hipGetLastError());
-    }
-    return ARX_OK;
+    return masked_scan(AllowRows{{allow}, n_allowed}, RangeSearch{max_results, min_score, out_scores, out_ids, out_counts, idx_base}, corpus, n_rows,
+                       queries, n_queries, dim, max_row_norm, ws, ws_bytes, path, cand_cap, stream);
 }
 
 extern "C" int32_t arx_range_search(const void* corpus, int64_t n_rows, const uint64_t* allow, int64_t n_allowed, const void* queries,

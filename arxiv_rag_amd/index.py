@@ -215,38 +215,50 @@ class ShardIndex:
         self._i8_searches += 1 if ran_i8 else 0
         return scores, ids
 
-    def _search_masked(self, kind, who, workspace_bytes, q, k, ws, out, _stream, debug, check_mask, call):
-        """What the masked searches share (csrc/masked_topk.h).  `kind`: "filtered" / "prefix" / "filtered_multi", the key of the cached workspace and the
-        word in messages; `who`: the public spelling; `workspace_bytes`: the library's arx_topk_<kind>_workspace_bytes; `check_mask(nq)`
-        asserts the mask's tensors, `call(...)` is arx_topk_search_<kind>_tuned with its leading (corpus, mask, queries) arguments bound."""
-        unknown = set(debug) - {"path", "cand_cap"}
-        if unknown:
-            raise TypeError(f"ShardIndex.{who} got unexpected keyword argument(s): {', '.join(sorted(unknown))}")
+    def _scan_search(self, kind, entry, q, dims, outs, workspace_bytes, call, check_mask=None, path=0, cand_cap=0, ws=None, out=None,
+                     _stream=None, refuse_empty=False):
+        """What the searches of the scan driver share (csrc/masked_topk.h).  `kind`: the key of the cached workspace and the word in
+        messages; `entry`: the C function behind `call`, for error texts; `dims`: the search's own sizes by name, in the order the C
+        functions take them (k / max_results / n_groups, chunks_per_group); `outs`: per output tensor (its shape after [Q], dtype, pad);
+        `workspace_bytes`: the library's arx_*_workspace_bytes; `check_mask(nq)` asserts the mask's tensors; `call(...)`: the library's
+        *_tuned function with its leading arguments, up to the queries, bound.  `refuse_empty`: a shape the library does not support is an
+        ArxError for an empty shard or query set too."""
         assert q.is_cuda and q.dtype == torch.float16 and q.dim() == 2 and q.shape[1] == self.dim and q.is_contiguous()
         nq = q.shape[0]
-        check_mask(nq)
+        if check_mask is not None:
+            check_mask(nq)
         if out is None:
-            scores = torch.empty((nq, k), dtype=torch.float32, device=q.device)
-            ids = torch.empty((nq, k), dtype=torch.int64, device=q.device)
+            out = tuple(torch.empty((nq, *shape), dtype=dtype, device=q.device) for shape, dtype, _ in outs)
         else:
-            scores, ids = out
-            assert scores.shape == (nq, k) and ids.shape == (nq, k) and scores.is_contiguous() and ids.is_contiguous()
-        if nq == 0:
-            return scores, ids
-        if self.n_rows == 0:
-            scores.fill_(float("-inf")); ids.fill_(-1)
-            return scores, ids
-        need = workspace_bytes(self.n_rows, nq, self.dim, k)
-        if need < 0:
-            raise _lib.ArxError(f"unsupported {kind} search shape n_rows={self.n_rows} nq={nq} dim={self.dim} k={k}")
+            out = tuple(out)
+            assert len(out) == len(outs) and all(t.shape == (nq, *shape) and t.is_contiguous() for t, (shape, _, _) in zip(out, outs))
+        empty = nq == 0 or self.n_rows == 0
+        if refuse_empty or not empty:
+            need = workspace_bytes(max(self.n_rows, 1), max(nq, 1), self.dim, *dims.values())
+            if need < 0:
+                raise _lib.ArxError(f"unsupported {kind} search shape n_rows={self.n_rows} nq={nq} dim={self.dim} "
+                                    + " ".join(f"{name}={v}" for name, v in dims.items()))
+        if empty:
+            for t, (_, _, pad) in zip(out, outs):
+                t.fill_(pad)
+            return out
         if ws is None:
             ws = self._masked_workspace(kind, need)
         st = torch.cuda.current_stream().cuda_stream if _stream is None else _stream
-        rc = call(nq, self.dim, k, scores.data_ptr(), ids.data_ptr(), self.idx_base, self._norm_bound(), ws.data_ptr(), ws.numel(),
-                  int(debug.get("path", 0)), int(debug.get("cand_cap", 0)), st)
-        _lib.check(rc, f"arx_topk_search_{kind}")
+        rc = call(nq, self.dim, *dims.values(), *(t.data_ptr() for t in out), self.idx_base, self._norm_bound(), ws.data_ptr(), ws.numel(),
+                  int(path), int(cand_cap), st)
+        _lib.check(rc, entry)
         self._last_ws_masked[kind] = ws
-        return scores, ids
+        return out
+
+    def _search_masked(self, kind, who, workspace_bytes, q, k, ws, out, _stream, debug, check_mask, call):
+        """The three masked top-k searches.  `kind`: "filtered" / "prefix" / "filtered_multi"; `who`: the public spelling; the test hooks
+        `path` and `cand_cap` arrive in `debug`, any other keyword is a TypeError."""
+        unknown = set(debug) - {"path", "cand_cap"}
+        if unknown:
+            raise TypeError(f"ShardIndex.{who} got unexpected keyword argument(s): {', '.join(sorted(unknown))}")
+        return self._scan_search(kind, f"arx_topk_search_{kind}", q, {"k": k}, (((k,), torch.float32, float("-inf")), ((k,), torch.int64, -1)),
+                                 workspace_bytes, call, check_mask, ws=ws, out=out, _stream=_stream, **debug)
 
     def _masked_stats(self, kind, stats, ws):
         """`stats`: the library's arx_topk_<kind>_stats."""
@@ -382,30 +394,16 @@ class ShardIndex:
         if getattr(self, "group_of", None) is None:
             raise ValueError("search_grouped needs set_groups(group_of) first")
         q, P, m = queries_f16, int(n_groups), int(chunks_per_group)
-        assert q.is_cuda and q.dtype == torch.float16 and q.dim() == 2 and q.shape[1] == self.dim and q.is_contiguous()
-        nq = q.shape[0]
-        if allow is not None:
-            self._check_allow(allow)
-        need = self.lib.arx_topk_grouped_workspace_bytes(max(self.n_rows, 1), max(nq, 1), self.dim, P, m)
-        if need < 0:
-            raise _lib.ArxError(f"unsupported grouped search shape n_rows={self.n_rows} nq={nq} dim={self.dim} n_groups={P} "
-                                f"chunks_per_group={m}")
-        scores = torch.full((nq, P, m), float("-inf"), dtype=torch.float32, device=q.device)
-        ids = torch.full((nq, P, m), -1, dtype=torch.int64, device=q.device)
-        groups = torch.full((nq, P), -1, dtype=torch.int32, device=q.device)
-        if nq == 0 or self.n_rows == 0:
-            return scores, ids, groups
-        if ws is None:
-            ws = self._masked_workspace("grouped", need)
-        rc = self.lib.arx_topk_search_grouped_tuned(self.corpus.data_ptr(), self.n_rows, self.group_of.data_ptr(),
-                                                    int(self.max_run_rows if max_run_rows is None else max_run_rows),
-                                                    None if allow is None else allow.data_ptr(), -1 if n_allowed is None else int(n_allowed),
-                                                    q.data_ptr(), nq, self.dim, P, m, scores.data_ptr(), ids.data_ptr(), groups.data_ptr(),
-                                                    self.idx_base, self._norm_bound(), ws.data_ptr(), ws.numel(), int(path), int(cand_cap),
-                                                    torch.cuda.current_stream().cuda_stream)
-        _lib.check(rc, "arx_topk_search_grouped")
-        self._last_ws_masked["grouped"] = ws
-        return scores, ids, groups
+
+        def call(*rest):
+            return self.lib.arx_topk_search_grouped_tuned(self.corpus.data_ptr(), self.n_rows, self.group_of.data_ptr(),
+                                                          int(self.max_run_rows if max_run_rows is None else max_run_rows),
+                                                          None if allow is None else allow.data_ptr(), -1 if n_allowed is None else int(n_allowed),
+                                                          q.data_ptr(), *rest)
+        outs = (((P, m), torch.float32, float("-inf")), ((P, m), torch.int64, -1), ((P,), torch.int32, -1))
+        return self._scan_search("grouped", "arx_topk_search_grouped", q, {"n_groups": P, "chunks_per_group": m}, outs,
+                                 self.lib.arx_topk_grouped_workspace_bytes, call, lambda nq: allow is None or self._check_allow(allow),
+                                 path, cand_cap, ws, refuse_empty=True)
 
     def grouped_stats(self, ws: Optional[torch.Tensor] = None) -> Tuple[int, int]:
         """(queries whose candidate list overflowed and were answered by the exhaustive path, candidate groups rescored) of the LAST
@@ -424,31 +422,14 @@ class ShardIndex:
         it.  `allow` / `n_allowed` as for `search(allow=...)`, None = every row.  Runs on the fp16 rows: the int8 index plays no part.
         Test hooks: `path` (1 = scan, 2 = exhaustive) and `cand_cap`; `range_stats` reads the counters."""
         q, M = queries_f16, int(max_results)
-        assert q.is_cuda and q.dtype == torch.float16 and q.dim() == 2 and q.shape[1] == self.dim and q.is_contiguous()
-        nq = q.shape[0]
-        ms = device_thresholds(min_score, nq, q.device)
-        if allow is not None:
-            self._check_allow(allow)
-        need = self.lib.arx_range_workspace_bytes(max(self.n_rows, 1), max(nq, 1), self.dim, M)
-        if need < 0:
-            raise _lib.ArxError(f"unsupported range search shape n_rows={self.n_rows} nq={nq} dim={self.dim} max_results={M}")
-        scores = torch.empty((nq, M), dtype=torch.float32, device=q.device)
-        ids = torch.empty((nq, M), dtype=torch.int64, device=q.device)
-        counts = torch.empty((nq,), dtype=torch.int32, device=q.device)
-        if nq == 0:
-            return scores, ids, counts
-        if self.n_rows == 0:
-            scores.fill_(float("-inf")); ids.fill_(-1); counts.zero_()
-            return scores, ids, counts
-        if ws is None:
-            ws = self._masked_workspace("range", need)
-        rc = self.lib.arx_range_search_tuned(self.corpus.data_ptr(), self.n_rows, None if allow is None else allow.data_ptr(),
-                                             -1 if n_allowed is None else int(n_allowed), q.data_ptr(), ms.data_ptr(), nq, self.dim, M,
-                                             scores.data_ptr(), ids.data_ptr(), counts.data_ptr(), self.idx_base, self._norm_bound(), ws.data_ptr(),
-                                             ws.numel(), int(path), int(cand_cap), torch.cuda.current_stream().cuda_stream)
-        _lib.check(rc, "arx_range_search")
-        self._last_ws_masked["range"] = ws
-        return scores, ids, counts
+        ms = device_thresholds(min_score, q.shape[0], q.device)
+
+        def call(*rest):
+            return self.lib.arx_range_search_tuned(self.corpus.data_ptr(), self.n_rows, None if allow is None else allow.data_ptr(),
+                                                   -1 if n_allowed is None else int(n_allowed), q.data_ptr(), ms.data_ptr(), *rest)
+        outs = (((M,), torch.float32, float("-inf")), ((M,), torch.int64, -1), ((), torch.int32, 0))
+        return self._scan_search("range", "arx_range_search", q, {"max_results": M}, outs, self.lib.arx_range_workspace_bytes, call,
+                                 lambda nq: allow is None or self._check_allow(allow), path, cand_cap, ws, refuse_empty=True)
 
     def range_stats(self, ws: Optional[torch.Tensor] = None) -> Tuple[int, int]:
         """(queries whose candidate list overflowed and were answered by the exhaustive path, candidate groups rescored) of the LAST

@@ -678,7 +678,8 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
                    keep_mask: Optional[np.ndarray] = None, group_by_paper: bool = False, chunks_per_paper: int = 1,
                    where_on_device: bool = False, min_score: Optional[float] = None, hybrid_filters: bool = False,
                    hybrid_on_device: bool = False, keyword_build_on_device: bool = False, document_regex: bool = False,
-                   nprobe: Optional[int] = None, ivf_lists: Optional[int] = None, ivf_iters: int = 10, ivf_seed: int = 0) -> List[Dict]:
+                   nprobe: Optional[int] = None, ivf_lists: Optional[int] = None, ivf_iters: int = 10, ivf_seed: int = 0,
+                   binary_candidates: Optional[int] = None, binary_centre: Optional[str] = "mean") -> List[Dict]:
     """Brute-force cosine top-k (config.yaml:63-64 `top_k: 10`) over the rank's fp16 rows in HBM; with
     torchrun each rank holds the contiguous row shard it encoded and the partial top-k lists are
     all-gathered over RCCL and merged.  `shard` is the `ShardSink` the encode step filled: rows [lo, hi) are already where they
@@ -746,7 +747,13 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
     `where` (one dict, or a list with one filter per query: one IVF call per batch whatever the number of distinct filters),
     `where_document`, `keep_mask`, `reranker`, `mmr_lambda` and `min_score` (`top_k` then at most 32).  With a `where` list or `min_score`
     the entries also carry `ivf_hits`, the exact number of visible chunks at or above the threshold (without one: the rows scored), and
-    with `min_score` `truncated` (`ivf_hits > top_k`).  Not together with `hybrid_alpha`, `group_by_paper` or more than one rank."""
+    with `min_score` `truncated` (`ivf_hits > top_k`).  Not together with `hybrid_alpha`, `group_by_paper` or more than one rank.
+    `binary_candidates` (None = nothing changes): the binary-code search (INTEGRATION.md "Binary-code search").  A `binary.BinaryIndex` is
+    packed over the shard (`binary_centre`: "mean", the column mean of the rows, or None / "none", zero) and every query's first
+    `binary_candidates` (at most 256, at least the width the search returns) visible rows by Hamming distance of the sign bits are
+    rescored exactly, `where` (one dict), `where_document` and `keep_mask` applied as without it; every entry of the results then
+    carries `binary_count`, the candidates rescored.  Composes with `reranker` and `mmr_lambda`.  Not together with `nprobe`,
+    `hybrid_alpha`, `group_by_paper`, `min_score`, a per-query `where` list or more than one rank."""
     from .retrieval import RowFilters, check_hybrid_on_device, check_shared_query, retrieve
     if keyword_build_on_device and hybrid_alpha is None:
         raise ValueError("keyword_build_on_device needs hybrid_alpha: it chooses where the BM25 keyword index is built")
@@ -761,6 +768,14 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
             raise ValueError("min_score cannot be combined with reranker here: reranking a long range list is out of scope for search_queries")
         check_range_query(top_k, ranged=True, hybrid_alpha=hybrid_alpha, mmr_lambda=mmr_lambda, group_by=group_by_paper,    # (IVF: a bitmap per query)
                           per_query_filters=isinstance(where, (list, tuple)) and nprobe is None, world=int(os.environ.get("WORLD_SIZE", "1")))
+    if binary_candidates is not None:
+        from .binary import check_query_with_binary
+        if binary_centre not in (None, "none", "mean"):
+            raise ValueError(f"binary_centre={binary_centre!r} must be \"mean\" or \"none\"")
+        check_query_with_binary(binary_candidates, has_index=True, per_query_filters=isinstance(where, (list, tuple)), hybrid_alpha=hybrid_alpha,
+                                group_by=group_by_paper, min_score=min_score, nprobe=nprobe if nprobe is not None else ivf_lists,
+                                world=int(os.environ.get("WORLD_SIZE", "1")),
+                                n_width=n_cand_of(reranker, rerank_top_k, mmr_lambda, mmr_fetch_k) if (reranker is not None or mmr_lambda is not None) else top_k)
     if nprobe is not None or ivf_lists is not None:
         from .ivf import check_build_args, check_query_with_nprobe
         if nprobe is None or ivf_lists is None:
@@ -795,7 +810,7 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
         compile_where_document(where_document, regex=document_regex)
     # int8 pre-filter (same exact answers; +50 % shard memory, one quantisation pass): 1.5-1.7x the queries per second on small batches;
     # a filtered, a grouped and a range search run on the fp16 rows
-    masked = (where is not None or keep_mask is not None or where_document is not None or group_by_paper or min_score is not None or nprobe is not None
+    masked = (where is not None or keep_mask is not None or where_document is not None or group_by_paper or min_score is not None or nprobe is not None or binary_candidates is not None
               or (hybrid_on_device and n_cand_of(reranker, rerank_top_k, mmr_lambda, mmr_fetch_k) > HYBRID_CANDIDATES))
     index = ShardIndex(shard.rows, idx_base=shard.lo, prefilter="int8" if (dim % 128 == 0 and dim <= 1024 and n_rows > 0 and not masked) else None,
                        adaptive=True)
@@ -822,7 +837,8 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
     hit = retrieve(index, qd, filters, top_k, n_candidates=n_cand, reranked=reranker is not None, where=where, where_document=where_document,
                    min_score=None if min_score is None else float(min_score), grouped=group_by_paper, chunks_per_group=chunks_per_paper, mmr_lambda=mmr_lambda,
                    hybrid_alpha=hybrid_alpha, keyword=keyword_index, query_texts=queries, hybrid_on_device=hybrid_on_device, world=world,
-                   **({} if nprobe is None else {"nprobe": int(nprobe), "ivf": build_ivf_index(index, ivf_lists, ivf_iters, ivf_seed)}))
+                   **({} if nprobe is None else {"nprobe": int(nprobe), "ivf": build_ivf_index(index, ivf_lists, ivf_iters, ivf_seed)}),
+                   **({} if binary_candidates is None else {"binary_candidates": int(binary_candidates), "binary": build_binary_index(index, binary_centre)}))
     s, i, grp, truncated, mmr_val, hyb, kws = hit.scores, hit.ids, hit.groups, hit.truncated, hit.mmr, hit.hybrid, hit.keyword
     if reranker is not None:
         from .ranging import RERANK_BATCH
@@ -841,6 +857,8 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
     results = []
     scanned_of = (lambda qi: {}) if hit.ivf_scanned is None else (lambda qi: {"ivf_scanned": int(hit.ivf_scanned[qi]),
                                                                               **({} if hit.ivf_hits is None else {"ivf_hits": int(hit.ivf_hits[qi])})})
+    if hit.binary_count is not None:
+        scanned_of = lambda qi: {"binary_count": int(hit.binary_count[qi])}      # noqa: E731
 
     def hybrid_fields(qi, p):                                # (null, not NaN, in the JSON file)
         if hyb is None:
@@ -886,6 +904,15 @@ def build_ivf_index(index, n_lists: int, iters: int = 10, seed: int = 0):
     print(f"IVF index: {info['n_lists']} lists of {info['list_rows_min']} / {info['list_rows_median']:.0f} / {info['list_rows_max']} rows "
           f"(min / median / max), {info['iterations']} iterations on {info['train_rows']} rows, {info['seconds']:.2f} s")
     return ivf
+
+
+def build_binary_index(index, centre: Optional[str] = "mean"):
+    """`--binary-candidates`: the `binary.BinaryIndex` of the search step's shard, with its size printed."""
+    from .binary import BinaryIndex
+    bi = BinaryIndex.build(index, centre=None if centre in (None, "none") else "mean")
+    n, w = (int(v) for v in bi.codes.shape)
+    print(f"Binary index: {n} rows x {w * 64} sign bits ({n * w * 8} bytes), centre {'none' if bi.centre is None else 'mean'}")
+    return bi
 
 
 # --------------------------------------------------------------------------------------------- main
@@ -984,6 +1011,13 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--nprobe", type=int, default=None,
                    help="IVF probe search: score every query against the chunks of its this many nearest lists only (1..min(128, "
                         "--ivf-lists); exact among those; not with --hybrid-alpha, --group-by-paper, --min-score or --where-file)")
+    p.add_argument("--binary-candidates", type=int, default=None,
+                   help="Binary-code search: rank every chunk by the Hamming distance of its sign bits to the query's and rescore the "
+                        "best this many exactly (1..256, at least the search's width; default: off; needs --queries; one GPU rank "
+                        "only; not with --nprobe, --hybrid-alpha, --group-by-paper, --min-score or --where-file)")
+    p.add_argument("--binary-centre", choices=("mean", "none"), default="mean",
+                   help="What the sign bits of --binary-candidates are taken against: the column mean of the chunks' rows, or zero "
+                        "(default: mean)")
     return p
 
 
@@ -1150,6 +1184,37 @@ def check_ivf_args(args) -> Optional[str]:
         return "--nprobe cannot be combined with --where-file: the IVF search takes one bitmap per call"
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         return "--nprobe needs a single GPU rank: more than one rank is out of scope"
+    return None
+
+
+def check_binary_args(args) -> Optional[str]:
+    """-> an error message for an unusable --binary-candidates, else None.  (The other flags are read with getattr: absent = off.)"""
+    r = getattr(args, "binary_candidates", None)
+    if r is None:
+        return None
+    if not (1 <= r <= 256):
+        return f"--binary-candidates {r} must be in [1, 256]"
+    if not getattr(args, "queries", None):
+        return "--binary-candidates needs --queries: it is a mode of the search step"
+    if getattr(args, "nprobe", None) is not None or getattr(args, "ivf_lists", None) is not None:
+        return "--binary-candidates cannot be combined with --nprobe / --ivf-lists: both choose which rows get scored"
+    if getattr(args, "hybrid_alpha", None) is not None:
+        return "--binary-candidates cannot be combined with --hybrid-alpha: the BM25 keyword search has no binary codes"
+    if getattr(args, "group_by_paper", False):
+        return "--binary-candidates cannot be combined with --group-by-paper: the grouped search reads every row"
+    if getattr(args, "min_score", None) is not None:
+        return "--binary-candidates cannot be combined with --min-score: the range search reads every row"
+    if getattr(args, "where_filters", None) is not None:
+        return "--binary-candidates cannot be combined with --where-file: the Hamming scan takes one bitmap per call"
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        return "--binary-candidates needs a single GPU rank: more than one rank is out of scope"
+    width = getattr(args, "top_k", 10)
+    if getattr(args, "rerank_model", None):
+        width = getattr(args, "rerank_top_k", 32)
+    elif getattr(args, "mmr_lambda", None) is not None:
+        width = getattr(args, "mmr_fetch_k", 32)
+    if r < width:
+        return f"--binary-candidates {r} is below the {width} rows the search returns per query"
     return None
 
 
@@ -1380,7 +1445,8 @@ def main(argv: Optional[Sequence[str]] = None, model_factory: Optional[Callable]
     args = build_parser().parse_args(argv)
     err = (check_rerank_args(args) or check_hybrid_args(args) or check_hybrid_filters_args(args) or check_hybrid_device_args(args) or check_keyword_build_args(args) or check_where_args(args) or check_where_file_args(args) or check_where_device_args(args)
            or check_where_document_args(args)
-           or check_mmr_args(args) or check_dedup_args(args) or check_group_args(args) or check_range_args(args) or check_facets_args(args) or check_topics_args(args) or check_ivf_args(args))
+           or check_mmr_args(args) or check_dedup_args(args) or check_group_args(args) or check_range_args(args) or check_facets_args(args) or check_topics_args(args) or check_ivf_args(args)
+           or check_binary_args(args))
     if err:
         print(f"Error: {err}")
         return 2
@@ -1485,7 +1551,9 @@ def main(argv: Optional[Sequence[str]] = None, model_factory: Optional[Callable]
                                **({"keyword_build_on_device": True} if args.keyword_build_on_device else {}),
                                **({"document_regex": True} if args.where_document_regex else {}),
                                **({"nprobe": args.nprobe, "ivf_lists": args.ivf_lists, "ivf_iters": args.ivf_iters, "ivf_seed": args.ivf_seed}
-                                  if args.nprobe is not None else {}))
+                                  if args.nprobe is not None else {}),
+                               **({"binary_candidates": args.binary_candidates, "binary_centre": args.binary_centre}
+                                  if args.binary_candidates is not None else {}))
                 if args.facet_keys is not None:
                     facet_counts(chunks, _model.encoder.device, args.facet_keys, args.facets_top,
                                  where=args.where_filters if args.where_filters is not None else args.where_filter,

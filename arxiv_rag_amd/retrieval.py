@@ -199,6 +199,7 @@ class Retrieved:
     keyword: Optional[np.ndarray] = None         # ... and the BM25 ones (nan where the row was not in the keyword list)
     ivf_scanned: Optional[np.ndarray] = None     # nprobe: int64 [Q], the rows scored for every query
     ivf_hits: Optional[np.ndarray] = None        # nprobe with per-query filters or min_score: int64 [Q], the rows at or above the threshold
+    binary_count: Optional[np.ndarray] = None    # binary_candidates: int64 [Q], the Hamming candidates rescored for every query
 
 
 def _retrieve_ivf(ivf, q, k: int, nprobe: int, filters: RowFilters, where, where_document, per_query: bool, min_score, out: Retrieved):
@@ -231,7 +232,8 @@ def _retrieve_ivf(ivf, q, k: int, nprobe: int, filters: RowFilters, where, where
 def retrieve(index, q, filters: RowFilters, n_results: int, *, n_candidates: int = 32, reranked: bool = False, where=None, where_document=None,
              min_score=None, grouped: bool = False, chunks_per_group: int = 1, mmr_lambda: Optional[float] = None,
              hybrid_alpha: Optional[float] = None, keyword=None, query_texts: Optional[Sequence[str]] = None,
-             hybrid_on_device: bool = False, world: int = 1, nprobe: Optional[int] = None, ivf=None) -> Retrieved:
+             hybrid_on_device: bool = False, world: int = 1, nprobe: Optional[int] = None, ivf=None,
+             binary_candidates: Optional[int] = None, binary=None) -> Retrieved:
     """One search of the fp16 device queries `q` over `index` (a `ShardIndex`), in the mode the arguments name, every refusal behind it.
     The width: a range search (`min_score`) returns up to `n_candidates` rows with `reranked` and `n_results` without, a grouped search
     `n_results` groups, every other search `n_candidates` rows when something picks among them afterwards (`reranked`, `mmr_lambda`,
@@ -253,12 +255,22 @@ def retrieve(index, q, filters: RowFilters, n_results: int, *, n_candidates: int
     `IvfIndex.search_many` call whatever the number of distinct filters: only rows at or above the threshold come back, `ivf_hits`
     holds their exact number per query (without `min_score`: the rows scored) and, with `min_score`, `truncated` is
     `ivf_hits > width`.  ValueError (`ivf.check_query_with_nprobe`): `hybrid_alpha`, `grouped`, `world > 1`, no `ivf`, a width above
-    32."""
+    32.
+    `binary_candidates` (None = nothing changes) with `binary` (a `binary.BinaryIndex` over `index`): the binary-code search
+    (INTEGRATION.md "Binary-code search"): every query's first `binary_candidates` visible rows by (Hamming distance of the sign bits,
+    row), under the one bitmap of `where`, `where_document` and the keep-mask, rescored exactly; `binary_count` holds the candidates
+    rescored.  MMR and a reranker consume the list as any other.  ValueError (`binary.check_query_with_binary`): `nprobe`,
+    `hybrid_alpha`, `grouped`, `min_score`, per-query filter lists, `world > 1`, no `binary`, `binary_candidates` outside
+    [width, 256], a width above 32."""
     import torch
     from .filter_sets import is_per_query
     nq = q.shape[0]
     k = n_candidates if (reranked or hybrid_alpha is not None or mmr_lambda is not None) else n_results
     per_query = is_per_query(where) or is_per_query(where_document)
+    if binary_candidates is not None:
+        from .binary import check_query_with_binary
+        check_query_with_binary(binary_candidates, has_index=binary is not None, per_query_filters=per_query, hybrid_alpha=hybrid_alpha,
+                                group_by=grouped, min_score=min_score, nprobe=nprobe, world=world, n_width=k)
     if nprobe is not None:
         from .ivf import check_query_with_nprobe
         check_query_with_nprobe(nprobe, has_index=ivf is not None, n_lists=getattr(ivf, "n_lists", 0), per_query_filters=per_query,
@@ -272,6 +284,9 @@ def retrieve(index, q, filters: RowFilters, n_results: int, *, n_candidates: int
     long_lists = on_device and n_candidates > HYBRID_HOST_CANDIDATES
     if nprobe is not None:
         s, i = _retrieve_ivf(ivf, q, k, int(nprobe), filters, where, where_document, per_query, min_score, out)
+    elif binary_candidates is not None:
+        s, i, count = binary.search(q, k, int(binary_candidates), allow=filters.allow_of(where, where_document)[0])
+        out.binary_count = count.cpu().numpy()
     elif per_query:
         from .index import search_filtered_grouped
         bitmaps, filter_of, counts = filters.per_query(nq, where, where_document)

@@ -302,6 +302,8 @@ class HipCollection:
             from .ivf import label_rows
             self.ivf.index = self.index
             self.ivf.set_labels(torch.cat([self.ivf.labels, label_rows(self._buf[n:n + m], self.ivf.centroids_f16)]))
+        if getattr(self, "binary", None) is not None:            # the new rows packed with the kept centre
+            self.binary.append(self._buf[n:n + m], index=self.index)
         if self._deleted is not None:
             self._deleted = np.concatenate([self._deleted, np.zeros(m, bool)])
         if self.dedup_threshold is not None:
@@ -382,6 +384,7 @@ class HipCollection:
         if getattr(self, "ivf", None) is not None:               # the labels move as `group_of` moves: 4-byte rows
             ivf_labels = torch.zeros_like(self.ivf.labels)
             compact_rows_device(self.ivf.labels.contiguous(), ivf_labels, n, self._keep, word_rank)
+        keep_words = self._keep
         self.metadata = [md for md, k in zip(self.metadata, keep.tolist()) if k]
         self._ids = build_id_map(self.metadata)
         if self._kw_pieces is not None:
@@ -394,6 +397,8 @@ class HipCollection:
         if ivf_labels is not None:
             self.ivf.index = self.index
             self.ivf.set_labels(ivf_labels[:count].contiguous())
+        if getattr(self, "binary", None) is not None:            # the codes move as the rows moved: dim / 8-byte rows
+            self.binary.compact(keep_words, word_rank, count, index=self.index)
         return old_to_new(keep)
 
     def build_ivf(self, n_lists: int, iters: int = 10, seed: int = 0, train_rows: Optional[int] = None) -> Dict:
@@ -408,6 +413,22 @@ class HipCollection:
         check_build_args(self.hi - self.lo, self.dim, n_lists, iters, train_rows)
         self.ivf = IvfIndex.build(self.index, n_lists, iters=iters, seed=seed, train_rows=train_rows)
         return self.ivf.summary()
+
+    def build_binary(self, centre="mean") -> Dict:
+        """Pack the sign-bit codes `query(binary_candidates=...)` needs (INTEGRATION.md "Binary-code search";
+        `binary.BinaryIndex.build`): one bit per dimension, `x[j] > centre[j]`, of every row (tombstoned ones included: the keep-bitmap
+        hides them at query time).  `centre`: "mean" (the f32 column mean of the rows there are now, computed once and kept), None (0)
+        or a float array [dim].  Again replaces the codes and the centre; nothing recomputes the centre otherwise: `add` packs the new
+        rows with it, `compact` moves the codes.  -> {rows, words_per_row, code_bytes, centre}.  ValueError before any launch:
+        `world > 1`, a dim that is not a multiple of 64 in [64, 8192], a centre of another shape."""
+        from .binary import BinaryIndex, check_centre, check_dim
+        if getattr(self, "world", 1) > 1:
+            raise ValueError("build_binary needs world == 1: more than one rank is out of scope")
+        check_dim(int(self.dim))
+        kind = check_centre(centre, int(self.dim))
+        self.binary = BinaryIndex.build(self.index, centre=kind)
+        n, w = (int(v) for v in self.binary.codes.shape)
+        return {"rows": n, "words_per_row": w, "code_bytes": n * w * 8, "centre": "mean" if isinstance(kind, str) else ("none" if kind is None else "given")}
 
     def get(self, ids: Sequence) -> Dict:
         """-> {ids, metadatas, documents} of the rows with these `chunk_id`s, in the order asked, from the host lists (the shape of one
@@ -546,7 +567,7 @@ class HipCollection:
     def query(self, query_embeddings=None, query_texts: Optional[Sequence[str]] = None, n_results: int = 10, reranker=None,
               n_candidates: int = 32, hybrid_alpha: Optional[float] = None, where=None, where_document=None,
               mmr_lambda: Optional[float] = None, group_by=None, chunks_per_group: int = 1, min_score=None,
-              nprobe: Optional[int] = None) -> Dict:
+              nprobe: Optional[int] = None, binary_candidates: Optional[int] = None) -> Dict:
         """Between the encoded queries and the rerank step this is the pipeline `search_queries` runs too: `retrieval.RowFilters` builds
         the row bitmaps, `retrieval.retrieve` searches, picks by MMR and fuses.
         `reranker` (a `rerank.HipCrossEncoder`; needs `query_texts`): the search fetches `n_candidates` (<= 32) rows per query,
@@ -613,13 +634,26 @@ class HipCollection:
         search, and an added `ivf_scanned` list holds the rows scored per query.  `nprobe = n_lists` is the exact search.  Composes
         with a single `where`, `where_document` and the dedup and tombstone keep-bitmap (one bitmap per call), and with `reranker` and
         `mmr_lambda`, which consume the candidate list (`n_candidates <= 32`).  ValueError, naming the part: per-query filter lists,
-        `hybrid_alpha`, `group_by`, `min_score`, `world > 1`, or a collection without `build_ivf`."""
+        `hybrid_alpha`, `group_by`, `min_score`, `world > 1`, or a collection without `build_ivf`.
+        `binary_candidates` (an integer R in [width, 256], the width being what the search returns: `n_candidates` with `reranker`
+        or `mmr_lambda`, else `n_results`; None = nothing changes; needs `build_binary` first): the binary-code search
+        (INTEGRATION.md "Binary-code search").  Every row is ranked by the Hamming distance between its sign bits and the query's
+        (`arx_binary_candidates`), and the first R visible rows by (distance, row) are rescored exactly: the exact top rows among
+        those, with the score bits and the order of the exact search, and an added `binary_count` list holds the candidates rescored
+        per query.  Composes with a single `where`, `where_document` and the dedup and tombstone keep-bitmap (one bitmap per call),
+        and with `reranker` and `mmr_lambda`, which consume the list (`n_candidates <= 32`).  ValueError, naming the part: `nprobe`,
+        `hybrid_alpha`, `group_by`, `min_score`, per-query filter lists, `world > 1`, or a collection without `build_binary`."""
         import torch
         from .filter_sets import is_per_query
         from .grouping import check_grouped_query
         from .ranging import RERANK_BATCH, check_range_query
         from .retrieval import check_hybrid_on_device, check_shared_query, retrieve
         per_query = is_per_query(where) or is_per_query(where_document)
+        if binary_candidates is not None:
+            from .binary import check_query_with_binary
+            check_query_with_binary(binary_candidates, has_index=getattr(self, "binary", None) is not None, per_query_filters=per_query,
+                                    hybrid_alpha=hybrid_alpha, group_by=group_by, min_score=min_score, nprobe=nprobe, world=getattr(self, "world", 1),
+                                    n_width=n_candidates if (reranker is not None or mmr_lambda is not None) else n_results)
         if nprobe is not None:
             from .ivf import check_query_with_nprobe
             ivf = getattr(self, "ivf", None)
@@ -671,7 +705,8 @@ class HipCollection:
                        where_document=where_document, min_score=min_score, grouped=bool(group_by), chunks_per_group=chunks_per_group,
                        mmr_lambda=mmr_lambda, hybrid_alpha=hybrid_alpha, keyword=self.keyword, query_texts=query_texts,
                        hybrid_on_device=on_device, world=getattr(self, "world", 1),
-                       **({} if nprobe is None else {"nprobe": nprobe, "ivf": self.ivf}))
+                       **({} if nprobe is None else {"nprobe": nprobe, "ivf": self.ivf}),
+                       **({} if binary_candidates is None else {"binary_candidates": binary_candidates, "binary": self.binary}))
         s, i, hyb, kws = hit.scores, hit.ids, hit.hybrid, hit.keyword
         if reranker is not None:
             from .rerank import rerank_candidates, reorder_by_rerank
@@ -708,6 +743,8 @@ class HipCollection:
             out["truncated"] = hit.truncated
         if hit.ivf_scanned is not None:
             out["ivf_scanned"] = [int(v) for v in hit.ivf_scanned]
+        if hit.binary_count is not None:
+            out["binary_count"] = [int(v) for v in hit.binary_count]
         if hit.mmr is not None:
             out["mmr_scores"] = [hit.mmr[qi][i[qi] >= 0].tolist() for qi in range(q.shape[0])]
         if reranker is not None:

@@ -768,6 +768,50 @@ int32_t arx_ivf_search_multi_tuned(const void* corpus, int64_t n_rows, int32_t d
                                    int64_t* out_scanned, int64_t* out_hits, int64_t idx_base, void* ws, int64_t ws_bytes,
                                    int32_t rows_per_block, void* stream);
 
+/* ---- Binary-code search: sign-bit codes, exact Hamming candidate lists (csrc/binary.hip; the host layer is arxiv_rag_amd/binary.py;
+ * the definition is INTEGRATION.md "Binary-code search") -----------------------------------------------------------------------------
+ * arx_binary_pack: rows device fp16 [n_rows, dim] -> out_codes device uint64 [n_rows, dim / 64].  Bit j & 63 of word j >> 6 is set iff
+ * (float)x[j] > centre[j]: a strict f32 compare, so NaN gives 0, +inf gives 1 (against a finite centre), -0 and a value equal to the
+ * centre give 0.  centre is device f32 [dim] or NULL (NULL: 0).  This is the bit convention of the row bitmaps, on the host
+ * np.packbits(bits, bitorder="little").view(np.uint64).  One launch on `stream`, every word written once with a plain store, no atomics,
+ * no float arithmetic beyond the convert and the compare.  The same call packs the queries.  n_rows = 0 is legal and launches nothing.
+ * ARX_ERR_ARG before the launch, the message naming the field: dim not a multiple of 64 in 64..8192; n_rows outside 0..2^31-1; a null
+ * rows or out_codes with n_rows > 0; rows not 2-byte, centre not 4-byte or out_codes not 8-byte aligned. */
+int32_t arx_binary_pack(const void* rows, int64_t n_rows, int32_t dim, const float* centre, uint64_t* out_codes, void* stream);
+/* arx_binary_candidates: with W = dim / 64, d(q, r) = sum over w of popcount(codes[r][w] ^ qcodes[q][w]), an integer.  The VISIBLE rows
+ * are [0, n_rows), restricted to the rows whose bit of `allow` is set when it is given.  C(q) is the first min(R, visible) visible rows
+ * by (d ascending, row ascending), R = n_candidates: distances are integers, so C(q) is defined exactly, ties to the lower row.
+ *   codes         device uint64 [n_rows, W], 16-byte aligned (NULL only when n_rows == 0); qcodes device uint64 [n_queries, W]
+ *   allow         device uint64 [ceil(n_rows / 64)] or NULL: arx_topk_search_filtered's convention (bit r & 63 of word r >> 6); bits at
+ *                 or beyond n_rows may hold anything
+ *   out_cand      device int32 [n_queries, R]: C(q) in that order, padded with -1.  Rows are local (there is no idx_base)
+ *   out_dist      device int32 [n_queries, R] or NULL: their distances, padded with -1
+ *   out_count     device int64 [n_queries]: |C(q)|
+ *   ws            device scratch of arx_binary_workspace_bytes(n_rows, n_queries, dim, n_candidates) bytes, 16-byte aligned (-1 for
+ *                 arguments outside the limits below); at most 64 MiB
+ * Two launches per 256 queries on `stream` (scan: blocks of rows_per_block rows x tile of 8 queries, so the code array is read once per
+ * query tile, not once per query; a 64-row word of `allow` that is zero costs its one load; merge: one block per query over any number
+ * of partial lists), no host synchronisation, integer work only, no global atomics.  A query's outputs depend on its own row of qcodes,
+ * codes and allow; not on the batch, its order, the tile it lands in or the launch shape.  n_rows = 0 is legal: all -1, counts 0.
+ * ARX_ERR_ARG before anything is launched, the message naming the field: n_candidates outside 1..256; dim not a multiple of 64 in
+ * 64..8192; n_rows outside 0..2^31-1; n_queries < 1; a null or misaligned pointer; ws_bytes below the figure above.
+ * codes, qcodes and allow are device data of which every bit pattern is legal: nothing read from them addresses anything.
+ * THE EXACT RESCORE needs no call of its own.  The candidate lists are lists in arx_ivf_search's layout: order = out_cand flattened
+ * (an entry of -1 keeps its place and is skipped), n_members = n_queries * R, start[q] = q * R (int64 [n_queries + 1]), n_lists =
+ * n_queries, max_list_rows = R, probes[q] = {q}, n_probe = 1, allow = NULL (it has been applied).  arx_ivf_search then returns the best
+ * k <= 32 of C(q) by (exact_row_score desc, row asc), with the score bits of every other search; out_scanned[q] = |C(q)|.  n_lists is at
+ * most 4096 there, so the queries go in slices of at most 4096 (binary.py uses 1024).  Both calls are stream-ordered. */
+int64_t arx_binary_workspace_bytes(int64_t n_rows, int32_t n_queries, int32_t dim, int32_t n_candidates);
+int32_t arx_binary_candidates(const uint64_t* codes, int64_t n_rows, int32_t dim, const uint64_t* qcodes, int32_t n_queries,
+                              const uint64_t* allow, int32_t n_candidates, int32_t* out_cand, int32_t* out_dist, int64_t* out_count,
+                              void* ws, int64_t ws_bytes, void* stream);
+/* The same with the scan's launch shape chosen: rows_per_block rows per block, 0 (default: about 1024 blocks over the shard and the
+ * query tiles, at least 2048 rows each) or a multiple of 64 in 64..2^20; raised where the workspace could not hold the partial lists.
+ * Same bits for every choice. */
+int32_t arx_binary_candidates_tuned(const uint64_t* codes, int64_t n_rows, int32_t dim, const uint64_t* qcodes, int32_t n_queries,
+                                    const uint64_t* allow, int32_t n_candidates, int32_t* out_cand, int32_t* out_dist,
+                                    int64_t* out_count, void* ws, int64_t ws_bytes, int32_t rows_per_block, void* stream);
+
 /* ---- MMR diversified re-ordering of a query's search candidates (csrc/mmr.hip; the definition is INTEGRATION.md "MMR") -----------
  * arx_gather_rows: out[s] (device fp16 [count, dim]) = shard row ids[s] - idx_base where that row lies in [0, n_rows), all zeros
  * otherwise (id -1, a row another rank owns: the ranks' buffers then add up to the rows, arxiv_rag_amd/mmr.py).  shard device fp16

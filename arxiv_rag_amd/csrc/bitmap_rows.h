@@ -106,3 +106,15 @@ __global__ __launch_bounds__(1024) void filter_scan_kernel(const uint64_t* __res
     }
     if (tid == 1023) off[n_words] = base + inc;
 }
+
+// one lane per row: the rows of the bitmap in ascending order, at the offsets filter_scan_kernel wrote (filter.hip, boosted.hip)
+__global__ __launch_bounds__(256) void filter_scatter_kernel(const uint64_t* __restrict__ allow, int64_t n_words, int64_t n_rows,
+                                                              const int64_t* __restrict__ off, int64_t* __restrict__ rows,
+                                                              const int* __restrict__ gate) {
+    if (gate && !*gate) return;
+    const int lane = threadIdx.x & 63;
+    const int64_t wd = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (wd >= n_words) return;
+    const uint64_t word = allow[wd] & valid_bits(n_rows, wd);
+    if ((word >> lane) & 1ull) rows[off[wd] + __popcll(word & ((1ull << lane) - 1ull))] = wd * GROUP_ROWS + lane;
+}

@@ -5,7 +5,7 @@
 //   pass A        a wave's select is a bit of its group's word, the same for every query; a 256-row tile whose four words are zero is
 //                 skipped
 //   the tail      a query reads every group of the shard; a group's visible rows are its word
-//   exhaustive    the bitmap compacted to the list of allowed rows (popcount + scan, scatter: the two kernels below), once per call, or
+//   exhaustive    the bitmap compacted to the list of allowed rows (popcount + scan, scatter: bitmap_rows.h), once per call, or
 //                 after a masked scan's overflow; the list is the same for every query
 //   path 0        the exhaustive path when the caller gave n_allowed and (allowed row, query) pairs are few, else the masked scan
 #include <math.h>
@@ -28,18 +28,6 @@ namespace {      // the headers also define non-template kernels: internal linka
 #define FILT_EXHAUSTIVE_MAX_PAIRS_WIDE (1ll << 20)
 #define FILT_EXHAUSTIVE_MAX_PAIRS (1ll << 18)
 #define FILT_WIDE_NQ 64
-
-// one lane per row: the allowed rows in ascending order
-__global__ __launch_bounds__(256) void filter_scatter_kernel(const uint64_t* __restrict__ allow, int64_t n_words, int64_t n_rows,
-                                                              const int64_t* __restrict__ off, int64_t* __restrict__ rows,
-                                                              const int* __restrict__ gate) {
-    if (gate && !*gate) return;
-    const int lane = threadIdx.x & 63;
-    const int64_t wd = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (wd >= n_words) return;
-    const uint64_t word = allow[wd] & valid_bits(n_rows, wd);
-    if ((word >> lane) & 1ull) rows[off[wd] + __popcll(word & ((1ull << lane) - 1ull))] = wd * GROUP_ROWS + lane;
-}
 
 // ---- the mask policy (masked_topk.h) -------------------------------------------------------------------------------------------------------
 struct BitmapMask : BitmapRows {      // pass A and `allow`, the caller's bitmap: bitmap_rows.h

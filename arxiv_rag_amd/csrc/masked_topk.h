@@ -26,8 +26,8 @@
 //   prepare_batch / prepare_lists      kernels of its own before pass A of a batch / before the exhaustive kernel
 //   kWorkspaceFn                       the name of its arx_topk_*_workspace_bytes, for the error text
 //
-// The host side is ONE scan driver (masked_scan) for every search that reads a row mask: these three, range.hip and grouped.hip.  It owns
-// the protocol their exactness rests on: the common argument checks, the workspace prefix (stats at offset 0, gmax, the mask's buffers,
+// The host side is ONE scan driver (masked_scan) for every search that reads a row mask: these three, range.hip, grouped.hip and
+// boosted.hip (whose mask also carries pass A's prior policy: PriorOf below).  It owns the protocol their exactness rests on: the common argument checks, the workspace prefix (stats at offset 0, gmax, the mask's buffers,
 // redo) and its reset, gate / only_if, tau_scale, and the loop over slices of QBATCH_MAX queries with pass A, the tail and the gated
 // exhaustive kernels in that order.  What differs comes from a search policy `Search`, a plain host struct passed by value like the mask
 // (TopkSearch for these three): given(), check(n_rows) for its own arguments and limits; take_buffers(L) for its workspace buffers after
@@ -99,6 +99,14 @@ __device__ __forceinline__ void score_word_rows(const f16_t* __restrict__ C, int
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 }
 
+// ---- the prior policy of pass A: what a mask adds to a (query, row) value in front of the group maximum.  A mask type that declares a
+// member type `RowPrior` (boosted.hip) supplies `prior_rows(g, lane, n_rows)`, the lane's 16 rows' priors taken once, and its
+// `.of_query(m, nq)`, whose result called with (v, j, r) gives the value that stands for row j*16 + (lane>>4)*4 + r instead of v.  Every
+// other mask has NoPrior, and its pass A is the code it was before the policy existed: the branches below are compile-time.
+struct NoPrior { static constexpr bool kOn = false; };
+template <class Mask, class = void> struct PriorOf { using type = NoPrior; };
+template <class Mask> struct PriorOf<Mask, decltype((void)sizeof(typename Mask::RowPrior))> { using type = typename Mask::RowPrior; };
+
 // ---- masked pass A: search_groupmax_kernel with the mask in front of the group maximum ---------------------------------------------------
 template <int BM, class Mask>
 __global__ __launch_bounds__(512) void masked_groupmax_kernel(const f16_t* __restrict__ Q, int nq, const f16_t* __restrict__ C, int64_t n_rows,
@@ -136,7 +144,25 @@ __global__ __launch_bounds__(512) void masked_groupmax_kernel(const f16_t* __res
         ML::run(Q, D, nq, C + n0 * D, D, rows_here, D, m0, 0, smem, acc, tile_q * 2);
     if (wn * GROUP_ROWS >= rows_here) return;
     // acc[j][i][r] belongs to row j*16 + (lane>>4)*4 + r of the wave's group and to query m0 + wm*TM + i*16 + (lane & 15)
+    using Prior = typename PriorOf<Mask>::type;
     const auto rows = tile.lane_rows(g, lane);
+    if constexpr (Prior::kOn) {
+        // the same epilogue with the prior policy's value in the row's place: 16 priors per lane and one weight per accumulator column,
+        // loaded here, after the k-loop, as the mixed-filter policy loads its words
+        const auto priors = mask.prior_rows(g, lane, n_rows);
+#pragma unroll
+        for (int i = 0; i < ML::MI; ++i) {
+            const int m = m0 + wm * ML::TM + i * 16 + (lane & 15);
+            const auto keep = rows.of_query(m, nq);
+            const auto boost = priors.of_query(m, nq);
+            float mx = -INFINITY;
+#pragma unroll
+            for (int j = 0; j < ML::NI; ++j)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) mx = fmaxf(mx, keep(j, r) ? boost(acc[j][i][r], j, r) : -INFINITY);
+            gm[i] = max_over_rows(mx);
+        }
+    } else {
 #pragma unroll
     for (int i = 0; i < ML::MI; ++i) {
         const auto keep = rows.of_query(m0 + wm * ML::TM + i * 16 + (lane & 15), nq);
@@ -146,6 +172,7 @@ __global__ __launch_bounds__(512) void masked_groupmax_kernel(const f16_t* __res
 #pragma unroll
             for (int r = 0; r < 4; ++r) mx = fmaxf(mx, keep(j, r) ? acc[j][i][r] : -INFINITY);      // a select: the row may hold anything finite
         gm[i] = max_over_rows(mx);
+    }
     }
     store_query_row<ML::MI, float>(gmax + g * ldg, gm, m0 + wm * ML::TM, nq, lane);
 }

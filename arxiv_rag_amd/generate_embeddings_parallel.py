@@ -679,7 +679,8 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
                    where_on_device: bool = False, min_score: Optional[float] = None, hybrid_filters: bool = False,
                    hybrid_on_device: bool = False, keyword_build_on_device: bool = False, document_regex: bool = False,
                    nprobe: Optional[int] = None, ivf_lists: Optional[int] = None, ivf_iters: int = 10, ivf_seed: int = 0,
-                   binary_candidates: Optional[int] = None, binary_centre: Optional[str] = "mean") -> List[Dict]:
+                   binary_candidates: Optional[int] = None, binary_centre: Optional[str] = "mean", boost_spec: Optional[Dict] = None,
+                   boost_weight: Optional[float] = None) -> List[Dict]:
     """Brute-force cosine top-k (config.yaml:63-64 `top_k: 10`) over the rank's fp16 rows in HBM; with
     torchrun each rank holds the contiguous row shard it encoded and the partial top-k lists are
     all-gathered over RCCL and merged.  `shard` is the `ShardSink` the encode step filled: rows [lo, hi) are already where they
@@ -753,7 +754,12 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
     `binary_candidates` (at most 256, at least the width the search returns) visible rows by Hamming distance of the sign bits are
     rescored exactly, `where` (one dict), `where_document` and `keep_mask` applied as without it; every entry of the results then
     carries `binary_count`, the candidates rescored.  Composes with `reranker` and `mmr_lambda`.  Not together with `nprobe`,
-    `hybrid_alpha`, `group_by_paper`, `min_score`, a per-query `where` list or more than one rank."""
+    `hybrid_alpha`, `group_by_paper`, `min_score`, a per-query `where` list or more than one rank.
+    `boost_weight` with `boost_spec` (both or neither; None = nothing changes): the boosted search (INTEGRATION.md "Boosted search").
+    `boost.prior_from_metadata(the chunks' metadata, boost_spec)` gives one prior per chunk, the ranking is by float32(cosine +
+    float32(boost_weight * prior)) under the bitmap of `where`, `where_document` and `keep_mask`, every hit's "score" is the boosted
+    value and an added "base_score" the cosine.  ValueError (`boost.check_query_with_boost`), before anything is launched:
+    `hybrid_alpha`, `group_by_paper`, `min_score`, `nprobe`, `binary_candidates`, a per-query `where` list, more than one rank."""
     from .retrieval import RowFilters, check_hybrid_on_device, check_shared_query, retrieve
     if keyword_build_on_device and hybrid_alpha is None:
         raise ValueError("keyword_build_on_device needs hybrid_alpha: it chooses where the BM25 keyword index is built")
@@ -768,6 +774,16 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
             raise ValueError("min_score cannot be combined with reranker here: reranking a long range list is out of scope for search_queries")
         check_range_query(top_k, ranged=True, hybrid_alpha=hybrid_alpha, mmr_lambda=mmr_lambda, group_by=group_by_paper,    # (IVF: a bitmap per query)
                           per_query_filters=isinstance(where, (list, tuple)) and nprobe is None, world=int(os.environ.get("WORLD_SIZE", "1")))
+    if (boost_weight is None) != (boost_spec is None):
+        raise ValueError("boost_weight and boost_spec go together: the weight and the metadata key the prior comes from")
+    if boost_weight is not None:
+        from .boost import check_query_with_boost, prior_from_metadata
+        check_query_with_boost(boost_weight, has_prior=True, per_query_filters=isinstance(where, (list, tuple)), hybrid_alpha=hybrid_alpha,
+                               group_by=group_by_paper, min_score=min_score, nprobe=nprobe if nprobe is not None else ivf_lists,
+                               binary_candidates=binary_candidates, world=int(os.environ.get("WORLD_SIZE", "1")),
+                               n_width=n_cand_of(reranker, rerank_top_k, mmr_lambda, mmr_fetch_k) if (reranker is not None or mmr_lambda is not None) else top_k,
+                               n_queries=len(queries))
+        prior_host = prior_from_metadata([c.get("metadata") or {} for c in chunks], boost_spec)      # (a bad spec or value: refused here)
     if binary_candidates is not None:
         from .binary import check_query_with_binary
         if binary_centre not in (None, "none", "mean"):
@@ -811,6 +827,7 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
     # int8 pre-filter (same exact answers; +50 % shard memory, one quantisation pass): 1.5-1.7x the queries per second on small batches;
     # a filtered, a grouped and a range search run on the fp16 rows
     masked = (where is not None or keep_mask is not None or where_document is not None or group_by_paper or min_score is not None or nprobe is not None or binary_candidates is not None
+              or boost_weight is not None
               or (hybrid_on_device and n_cand_of(reranker, rerank_top_k, mmr_lambda, mmr_fetch_k) > HYBRID_CANDIDATES))
     index = ShardIndex(shard.rows, idx_base=shard.lo, prefilter="int8" if (dim % 128 == 0 and dim <= 1024 and n_rows > 0 and not masked) else None,
                        adaptive=True)
@@ -838,7 +855,9 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
                    min_score=None if min_score is None else float(min_score), grouped=group_by_paper, chunks_per_group=chunks_per_paper, mmr_lambda=mmr_lambda,
                    hybrid_alpha=hybrid_alpha, keyword=keyword_index, query_texts=queries, hybrid_on_device=hybrid_on_device, world=world,
                    **({} if nprobe is None else {"nprobe": int(nprobe), "ivf": build_ivf_index(index, ivf_lists, ivf_iters, ivf_seed)}),
-                   **({} if binary_candidates is None else {"binary_candidates": int(binary_candidates), "binary": build_binary_index(index, binary_centre)}))
+                   **({} if binary_candidates is None else {"binary_candidates": int(binary_candidates), "binary": build_binary_index(index, binary_centre)}),
+                   **({} if boost_weight is None else {"boost_weight": float(boost_weight), "prior": torch.from_numpy(prior_host).to(dev)}))
+    base_of = (lambda qi, p: {}) if hit.base is None else (lambda qi, p: {"base_score": float(hit.base[qi, p])})
     s, i, grp, truncated, mmr_val, hyb, kws = hit.scores, hit.ids, hit.groups, hit.truncated, hit.mmr, hit.hybrid, hit.keyword
     if reranker is not None:
         from .ranging import RERANK_BATCH
@@ -871,7 +890,7 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
         if reranker is not None:
             for r, (p, j, rs_) in enumerate(picked[qi]):
                 hits.append({"rank": r + 1, "score": float(s[qi, p]), "rerank_score": float(rs_), "index": j,
-                             "chunk_id": names.get(j, f"chunk_{j}"), **hybrid_fields(qi, p)})
+                             "chunk_id": names.get(j, f"chunk_{j}"), **hybrid_fields(qi, p), **base_of(qi, p)})
             results.append({"query": text, "results": hits, **scanned_of(qi)})
             continue
         if grp is not None:                                   # paper by paper; the padding of short papers is skipped
@@ -887,7 +906,7 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
             if j < 0:
                 continue
             hits.append({"rank": r + 1, "score": float(s[qi, r]), "index": j, "chunk_id": names.get(j, f"chunk_{j}"),
-                         **hybrid_fields(qi, r), **({} if mmr_val is None else {"mmr_score": float(mmr_val[qi, r])})})
+                         **hybrid_fields(qi, r), **({} if mmr_val is None else {"mmr_score": float(mmr_val[qi, r])}), **base_of(qi, r)})
         results.append({"query": text, "results": hits, **({} if truncated is None else {"truncated": bool(truncated[qi])}), **scanned_of(qi)})
     if rank == 0:
         with open(Path(output_dir) / "search_results.json", "w", encoding="utf-8") as fh:
@@ -1018,6 +1037,15 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--binary-centre", choices=("mean", "none"), default="mean",
                    help="What the sign bits of --binary-candidates are taken against: the column mean of the chunks' rows, or zero "
                         "(default: mean)")
+    p.add_argument("--boost-key", type=str, default=None,
+                   help="Boosted search: rank by cosine + --boost-weight * prior, the prior being this metadata key's numeric value "
+                        "(missing: 0), or its exponential decay with --boost-decay-origin / --boost-half-life (default: off; needs "
+                        "--queries and --boost-weight; one GPU rank only; not with --hybrid-alpha, --group-by-paper, --min-score, "
+                        "--nprobe, --binary-candidates or --where-file)")
+    p.add_argument("--boost-weight", type=float, default=None, help="The weight of the --boost-key prior (finite; negative penalises)")
+    p.add_argument("--boost-decay-origin", type=float, default=None,
+                   help="With --boost-half-life: the prior is exp(-ln 2 * |value - origin| / half_life) of the --boost-key value")
+    p.add_argument("--boost-half-life", type=float, default=None, help="The half-life of the --boost-decay-origin decay (> 0)")
     return p
 
 
@@ -1215,6 +1243,44 @@ def check_binary_args(args) -> Optional[str]:
         width = getattr(args, "mmr_fetch_k", 32)
     if r < width:
         return f"--binary-candidates {r} is below the {width} rows the search returns per query"
+    return None
+
+
+def boost_spec_of(args) -> Optional[Dict]:
+    """The `boost.prior_from_metadata` spec the --boost-* flags name, None without --boost-key."""
+    if getattr(args, "boost_key", None) is None:
+        return None
+    spec = {"key": args.boost_key, "missing": 0.0}
+    if getattr(args, "boost_decay_origin", None) is not None:
+        spec.update(decay="exp", origin=args.boost_decay_origin, half_life=args.boost_half_life)
+    return spec
+
+
+def check_boost_args(args) -> Optional[str]:
+    """-> an error message for unusable --boost-* flags, else None.  (The other flags are read with getattr: absent = off.)"""
+    key, w = getattr(args, "boost_key", None), getattr(args, "boost_weight", None)
+    origin, half = getattr(args, "boost_decay_origin", None), getattr(args, "boost_half_life", None)
+    if key is None and w is None and origin is None and half is None:
+        return None
+    if key is None or w is None:
+        return "--boost-key and --boost-weight go together (and --boost-decay-origin / --boost-half-life need both)"
+    if (origin is None) != (half is None):
+        return "--boost-decay-origin and --boost-half-life go together"
+    if not np.isfinite(np.float32(w)):
+        return f"--boost-weight {w} must be finite"
+    if half is not None and not (half > 0 and np.isfinite(half) and np.isfinite(origin)):
+        return f"--boost-half-life {half} must be positive and finite, --boost-decay-origin finite"
+    if not getattr(args, "queries", None):
+        return "--boost-key needs --queries: it is a mode of the search step"
+    for flag, on in (("--hybrid-alpha", getattr(args, "hybrid_alpha", None) is not None), ("--group-by-paper", getattr(args, "group_by_paper", False)),
+                     ("--min-score", getattr(args, "min_score", None) is not None),
+                     ("--nprobe / --ivf-lists", getattr(args, "nprobe", None) is not None or getattr(args, "ivf_lists", None) is not None),
+                     ("--binary-candidates", getattr(args, "binary_candidates", None) is not None),
+                     ("--where-file", getattr(args, "where_filters", None) is not None)):
+        if on:
+            return f"--boost-key cannot be combined with {flag}: a boosted variant of that search is out of scope"
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        return "--boost-key needs a single GPU rank: more than one rank is out of scope"
     return None
 
 
@@ -1446,7 +1512,7 @@ def main(argv: Optional[Sequence[str]] = None, model_factory: Optional[Callable]
     err = (check_rerank_args(args) or check_hybrid_args(args) or check_hybrid_filters_args(args) or check_hybrid_device_args(args) or check_keyword_build_args(args) or check_where_args(args) or check_where_file_args(args) or check_where_device_args(args)
            or check_where_document_args(args)
            or check_mmr_args(args) or check_dedup_args(args) or check_group_args(args) or check_range_args(args) or check_facets_args(args) or check_topics_args(args) or check_ivf_args(args)
-           or check_binary_args(args))
+           or check_binary_args(args) or check_boost_args(args))
     if err:
         print(f"Error: {err}")
         return 2
@@ -1553,7 +1619,8 @@ def main(argv: Optional[Sequence[str]] = None, model_factory: Optional[Callable]
                                **({"nprobe": args.nprobe, "ivf_lists": args.ivf_lists, "ivf_iters": args.ivf_iters, "ivf_seed": args.ivf_seed}
                                   if args.nprobe is not None else {}),
                                **({"binary_candidates": args.binary_candidates, "binary_centre": args.binary_centre}
-                                  if args.binary_candidates is not None else {}))
+                                  if args.binary_candidates is not None else {}),
+                               **({"boost_spec": boost_spec_of(args), "boost_weight": args.boost_weight} if args.boost_key is not None else {}))
                 if args.facet_keys is not None:
                     facet_counts(chunks, _model.encoder.device, args.facet_keys, args.facets_top,
                                  where=args.where_filters if args.where_filters is not None else args.where_filter,

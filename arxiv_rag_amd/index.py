@@ -8,6 +8,7 @@ merge kernel (ties -> lower global row id).
 from __future__ import annotations
 
 import ctypes as C
+import struct
 from typing import Optional, Tuple
 
 import torch
@@ -409,6 +410,69 @@ class ShardIndex:
         """(queries whose candidate list overflowed and were answered by the exhaustive path, candidate groups rescored) of the LAST
         `search_grouped` on this index (or on `ws`).  Synchronises on the current stream."""
         return self._masked_stats("grouped", self.lib.arx_topk_grouped_stats, ws)
+
+    # ---- boosted search: cosine plus a weighted row prior ---------------------------------------------------------------------
+    def prior_info(self, prior: torch.Tensor) -> Tuple[float, int]:
+        """(the largest |finite value|, the number of non-finite values) of a device f32 tensor, in one pass (`arx_prior_info`).
+        Synchronises on the current stream."""
+        assert prior.is_cuda and prior.dtype == torch.float32 and prior.dim() == 1 and prior.is_contiguous()
+        info = torch.zeros(2, dtype=torch.int64, device=prior.device)
+        if prior.numel():
+            _lib.check(self.lib.arx_prior_info(prior.data_ptr(), prior.numel(), info.data_ptr(), torch.cuda.current_stream().cuda_stream),
+                       "arx_prior_info")
+        bits, bad = (int(v) for v in info.tolist())
+        return struct.unpack("<f", struct.pack("<I", bits & 0xFFFFFFFF))[0], bad
+
+    def search_boosted(self, queries_f16: torch.Tensor, k: int, prior: torch.Tensor, weight, allow: Optional[torch.Tensor] = None,
+                       n_allowed: Optional[int] = None, ws: Optional[torch.Tensor] = None, max_abs_prior: Optional[float] = None,
+                       **debug) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """queries fp16 [Q, D] (device), `prior` f32 [n_rows] (device), `weight` a number or one per query ->
+        (scores f32 [Q, k], base f32 [Q, k], ids int64 [Q, k]) on the device (`arx_topk_search_boosted`): the k <= 32
+        best visible rows by (boosted desc, row asc), boosted = float32(base + float32(weight[q] * prior[r])), `base` the bits `search`
+        gives the pair; (-inf, -inf, -1) pads.  A row with a NaN or +-inf prior is hidden from every query.  `allow` / `n_allowed` as
+        for `search(allow=...)`, None = every row.  Runs on the fp16 rows.
+        `weight` on the host (a number, a sequence, a numpy array, a host tensor): one that is not finite, or whose product with the
+        largest |prior| is not, is a ValueError (`boost.check_args`), and the checked values are uploaded, which waits for the copy.
+        `weight` as a contiguous device float32 tensor [Q] is taken as it is, with no copy and no wait: the device's rule holds (a
+        non-finite weight gives its query no rows).
+        `max_abs_prior`: the largest |finite prior|.  Given (`HipCollection.set_boost` measures it once), the call is stream-ordered
+        with a device weight.  None: `prior_info` measures it, which synchronises, once per prior tensor and version of it (the result
+        is kept beside the tensor's address; a prior written behind torch's back needs the argument).
+        Test hooks: `path` (1 = scan, 2 = exhaustive) and `cand_cap`; `boosted_stats` reads the counters."""
+        from . import boost as _boost
+        unknown = set(debug) - {"path", "cand_cap"}
+        if unknown:
+            raise TypeError(f"ShardIndex.search_boosted() got unexpected keyword argument(s): {', '.join(sorted(unknown))}")
+        q = queries_f16
+        if not (torch.is_tensor(prior) and prior.is_cuda and prior.dtype == torch.float32 and prior.shape == (self.n_rows,) and prior.is_contiguous()):
+            raise ValueError(f"prior must be a contiguous device float32 tensor of shape ({self.n_rows},)")
+        if max_abs_prior is None:
+            key = (prior.data_ptr(), prior.numel(), prior._version)
+            if getattr(self, "_prior_info_key", None) != key:
+                self._prior_info_key, self._prior_info_max = key, self.prior_info(prior)[0]
+            max_abs_prior = self._prior_info_max
+        nq = int(q.shape[0])
+        if torch.is_tensor(weight) and weight.is_cuda:
+            if not (weight.dtype == torch.float32 and weight.shape == (nq,) and weight.is_contiguous()):
+                raise ValueError(f"a device boost weight must be a contiguous float32 tensor of shape ({nq},)")
+            _boost.check_args(k, 0.0, nq, max_abs_prior, self.dim)
+            wd = weight
+        else:
+            wd = torch.from_numpy(_boost.check_args(k, weight, nq, max_abs_prior, self.dim)).to(q.device)
+
+        def call(*rest):
+            return self.lib.arx_topk_search_boosted(self.corpus.data_ptr(), self.n_rows, prior.data_ptr(), float(max_abs_prior), wd.data_ptr(),
+                                                    None if allow is None else allow.data_ptr(), -1 if n_allowed is None else int(n_allowed),
+                                                    q.data_ptr(), *rest)
+        ninf = float("-inf")
+        outs = (((k,), torch.float32, ninf), ((k,), torch.float32, ninf), ((k,), torch.int64, -1))
+        return self._scan_search("boosted", "arx_topk_search_boosted", q, {"k": k}, outs, self.lib.arx_topk_search_boosted_workspace_bytes, call,
+                                 lambda nq: allow is None or self._check_allow(allow), ws=ws, **debug)
+
+    def boosted_stats(self, ws: Optional[torch.Tensor] = None) -> Tuple[int, int]:
+        """(queries whose candidate list overflowed and were answered by the exhaustive path, candidate groups rescored) of the LAST
+        `search_boosted` on this index (or on `ws`).  Synchronises on the current stream."""
+        return self._masked_stats("boosted", self.lib.arx_topk_boosted_stats, ws)
 
     # ---- score threshold: every row at or above a cosine, up to 1 024 per query ---------------------------------------------
     def search_range(self, queries_f16: torch.Tensor, min_score, max_results: int, allow: Optional[torch.Tensor] = None, n_allowed: int = -1,

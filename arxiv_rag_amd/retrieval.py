@@ -200,6 +200,7 @@ class Retrieved:
     ivf_scanned: Optional[np.ndarray] = None     # nprobe: int64 [Q], the rows scored for every query
     ivf_hits: Optional[np.ndarray] = None        # nprobe with per-query filters or min_score: int64 [Q], the rows at or above the threshold
     binary_count: Optional[np.ndarray] = None    # binary_candidates: int64 [Q], the Hamming candidates rescored for every query
+    base: Optional[np.ndarray] = None            # boost_weight: the cosine of every returned row (`scores` holds the boosted values)
 
 
 def _retrieve_ivf(ivf, q, k: int, nprobe: int, filters: RowFilters, where, where_document, per_query: bool, min_score, out: Retrieved):
@@ -233,7 +234,8 @@ def retrieve(index, q, filters: RowFilters, n_results: int, *, n_candidates: int
              min_score=None, grouped: bool = False, chunks_per_group: int = 1, mmr_lambda: Optional[float] = None,
              hybrid_alpha: Optional[float] = None, keyword=None, query_texts: Optional[Sequence[str]] = None,
              hybrid_on_device: bool = False, world: int = 1, nprobe: Optional[int] = None, ivf=None,
-             binary_candidates: Optional[int] = None, binary=None) -> Retrieved:
+             binary_candidates: Optional[int] = None, binary=None, boost_weight=None, prior=None,
+             max_abs_prior: Optional[float] = None) -> Retrieved:
     """One search of the fp16 device queries `q` over `index` (a `ShardIndex`), in the mode the arguments name, every refusal behind it.
     The width: a range search (`min_score`) returns up to `n_candidates` rows with `reranked` and `n_results` without, a grouped search
     `n_results` groups, every other search `n_candidates` rows when something picks among them afterwards (`reranked`, `mmr_lambda`,
@@ -261,12 +263,24 @@ def retrieve(index, q, filters: RowFilters, n_results: int, *, n_candidates: int
     row), under the one bitmap of `where`, `where_document` and the keep-mask, rescored exactly; `binary_count` holds the candidates
     rescored.  MMR and a reranker consume the list as any other.  ValueError (`binary.check_query_with_binary`): `nprobe`,
     `hybrid_alpha`, `grouped`, `min_score`, per-query filter lists, `world > 1`, no `binary`, `binary_candidates` outside
-    [width, 256], a width above 32."""
+    [width, 256], a width above 32.
+    `boost_weight` (None = nothing changes; a number or one per query) with `prior` (device f32 [rows of `index`]) and
+    `max_abs_prior` (its largest |finite value|, None = measured): the boosted search (INTEGRATION.md "Boosted search"): the exact
+    top rows by cosine + weight * prior under the one bitmap of `where`, `where_document` and the keep-mask
+    (`ShardIndex.search_boosted`); `scores` holds the boosted values and `base` the cosines of the same rows, in the same order
+    (MMR's pick order included).  MMR and a reranker consume the list as any other.  ValueError (`boost.check_query_with_boost`):
+    `hybrid_alpha`, `grouped`, `min_score`, `nprobe`, `binary_candidates`, per-query filter lists, `world > 1`, no `prior`, a weight
+    that is not finite, a width above 32."""
     import torch
     from .filter_sets import is_per_query
     nq = q.shape[0]
     k = n_candidates if (reranked or hybrid_alpha is not None or mmr_lambda is not None) else n_results
     per_query = is_per_query(where) or is_per_query(where_document)
+    if boost_weight is not None:
+        from .boost import check_query_with_boost
+        boost_weight = check_query_with_boost(boost_weight, has_prior=prior is not None, per_query_filters=per_query, hybrid_alpha=hybrid_alpha,
+                                              group_by=grouped, min_score=min_score, nprobe=nprobe, binary_candidates=binary_candidates,
+                                              world=world, n_width=k, n_queries=nq, max_abs_prior=0.0 if max_abs_prior is None else max_abs_prior)
     if binary_candidates is not None:
         from .binary import check_query_with_binary
         check_query_with_binary(binary_candidates, has_index=binary is not None, per_query_filters=per_query, hybrid_alpha=hybrid_alpha,
@@ -287,6 +301,9 @@ def retrieve(index, q, filters: RowFilters, n_results: int, *, n_candidates: int
     elif binary_candidates is not None:
         s, i, count = binary.search(q, k, int(binary_candidates), allow=filters.allow_of(where, where_document)[0])
         out.binary_count = count.cpu().numpy()
+    elif boost_weight is not None:
+        allow, n_allowed = filters.allow_of(where, where_document)
+        s, base, i = index.search_boosted(q, k, prior, boost_weight, allow=allow, n_allowed=n_allowed, max_abs_prior=max_abs_prior)
     elif per_query:
         from .index import search_filtered_grouped
         bitmaps, filter_of, counts = filters.per_query(nq, where, where_document)
@@ -316,6 +333,8 @@ def retrieve(index, q, filters: RowFilters, n_results: int, *, n_candidates: int
         pos = order.clamp(min=0).long()                          # (-1 where fewer than n_results rows were found: masked here)
         s = torch.where(order >= 0, s.gather(1, pos), torch.full_like(mmr_val, float("-inf")))
         i = torch.where(order >= 0, i.gather(1, pos), torch.full_like(pos, -1))
+        if boost_weight is not None:
+            base = torch.where(order >= 0, base.gather(1, pos), torch.full_like(mmr_val, float("-inf")))
         out.mmr = mmr_val.cpu().numpy()
     if on_device:
         from .keyword import fuse_device
@@ -328,6 +347,8 @@ def retrieve(index, q, filters: RowFilters, n_results: int, *, n_candidates: int
         out.hybrid, out.ids, out.scores, out.keyword = (t.cpu().numpy() for t in fused)
         return out
     out.scores, out.ids = s.cpu().numpy(), i.cpu().numpy()
+    if boost_weight is not None:
+        out.base = base.cpu().numpy()
     if grouped:
         out.group_sizes = (out.ids.reshape(nq, n_results, chunks_per_group) >= 0).sum(axis=2)
     if hybrid_alpha is not None:

@@ -195,6 +195,8 @@ class HipCollection:
             self.documents = DocumentStore([metadata[r].get("text") or "" for r in range(lo, hi)], device=device)
         self.dedup_threshold, self.duplicates = dedup_threshold, []
         self._keep_mask = self._keep = None                     # rows that are not duplicates: host bool [n], device bitmap words
+        self._boost_spec = self._boost_buf = None               # `set_boost`: the spec (None for an array) and the prior, f32 in HBM
+        self._boost_max = 0.0                                   # ... and its largest |finite value| (`arx_prior_info`, once per change)
         if dedup_threshold is not None and hi > lo:
             from .dedup import duplicate_entries, find_duplicates, keep_bitmap
             dup_of, scores = find_duplicates(self.index, dedup_threshold)
@@ -257,13 +259,14 @@ class HipCollection:
         self._keep_mask = mask
         self._keep = None if mask is None else torch.from_numpy(pack_bitmap(mask).view(np.int64)).to(self._buf.device)
 
-    def add(self, embeddings, metadatas: Sequence[Dict]) -> None:
+    def add(self, embeddings, metadatas: Sequence[Dict], boost=None) -> None:
         """Append rows (`embeddings` [m, dim], converted to fp16 as the constructor converts them; one metadata dict each).  Everything
         derived is extended: texts, word pieces (the keyword index is rebuilt on its next use), the runs of `group_key`
         (`grouping.continue_runs`: the first new row may continue the last run; a key whose run ended is a ValueError) and, with
         `dedup_threshold`, `duplicates` and the keep-bitmap, from a self-join over the new rows only
         (`ShardIndex.nearest_earlier(row_lo=old_n)`).  ValueError, with nothing added: more rows than `capacity` has room for, a
-        duplicate id, another dim, a different number of dicts."""
+        duplicate id, another dim, a different number of dicts.  With `set_boost` the prior is extended: from the new metadatas for a
+        spec; for an array prior `boost` (floats [m]) is needed, and is refused in every other case."""
         import torch
         from .mutation import append_pieces, build_id_map, chunk_id_of
         self._require_mutable("add")
@@ -277,6 +280,22 @@ class HipCollection:
             raise ValueError(f"add: {n} rows + {m} new rows exceed capacity={self.capacity}")
         if m == 0:
             return
+        prior_new = None
+        if getattr(self, "_boost_buf", None) is not None and self._boost_spec is not None:
+            if boost is not None:
+                raise ValueError("add: boost= cannot be given when set_boost took a spec: the prior of the new rows comes from their metadata")
+            from .boost import prior_from_metadata
+            prior_new = prior_from_metadata(metadatas, self._boost_spec)
+        elif getattr(self, "_boost_buf", None) is not None:
+            if boost is None:
+                raise ValueError("add: set_boost took an array, so the prior of the new rows is needed: pass boost=[m floats]")
+            a = boost.detach().cpu().numpy() if torch.is_tensor(boost) else np.asarray(boost)
+            if a.dtype.kind != "f" or a.shape != (m,):
+                raise ValueError(f"add: boost must hold floats and have shape ({m},), not {a.dtype} {tuple(a.shape)}")
+            with np.errstate(over="ignore"):
+                prior_new = np.ascontiguousarray(a, dtype=np.float32)
+        elif boost is not None:
+            raise ValueError("add: boost= needs set_boost(array) first")
         ids = build_id_map(metadatas, base=n, into=self._ids)
         if self.group_key is not None:
             from .grouping import continue_runs
@@ -298,6 +317,9 @@ class HipCollection:
             self.documents.append(texts)
         self._drop_columns()
         self._make_index()
+        if prior_new is not None:
+            self._boost_buf[n:n + m] = torch.from_numpy(prior_new).to(dev)
+            self._measure_prior((n, n + m))
         if getattr(self, "ivf", None) is not None:               # the new rows labelled against the kept centroids; the lists rebuilt
             from .ivf import label_rows
             self.ivf.index = self.index
@@ -380,6 +402,10 @@ class HipCollection:
             self._group_buf, self._group_host = moved, self._group_host[keep]
         if self.documents is not None:
             self.documents.compact(self._keep, word_rank, count)
+        if getattr(self, "_boost_buf", None) is not None:      # the prior moves as `group_of` moves: 4-byte rows
+            moved = torch.zeros_like(self._boost_buf)
+            compact_rows_device(self._boost_buf, moved, n, self._keep, word_rank)
+            self._boost_buf = moved
         ivf_labels = None
         if getattr(self, "ivf", None) is not None:               # the labels move as `group_of` moves: 4-byte rows
             ivf_labels = torch.zeros_like(self.ivf.labels)
@@ -394,12 +420,57 @@ class HipCollection:
         self._set_keep(None)
         self._drop_columns()
         self._make_index()
+        if getattr(self, "_boost_buf", None) is not None:      # (the survivors' maximum: what a collection built from them measures)
+            self._measure_prior()
         if ivf_labels is not None:
             self.ivf.index = self.index
             self.ivf.set_labels(ivf_labels[:count].contiguous())
         if getattr(self, "binary", None) is not None:            # the codes move as the rows moved: dim / 8-byte rows
             self.binary.compact(keep_words, word_rank, count, index=self.index)
         return old_to_new(keep)
+
+    def _prior(self):
+        """The prior of the rows there are now (a view of the capacity-sized buffer), or None."""
+        return None if getattr(self, "_boost_buf", None) is None else self._boost_buf[:self.hi - self.lo]
+
+    def _measure_prior(self, rows=None) -> None:
+        """`arx_prior_info` over the prior (or its rows [rows[0], rows[1]): the new ones, whose maximum joins the kept one)."""
+        p = self._prior()
+        if rows is None:
+            self._boost_max = self.index.prior_info(p)[0] if p.numel() else 0.0
+        elif rows[1] > rows[0]:
+            self._boost_max = max(self._boost_max, self.index.prior_info(p[rows[0]:rows[1]])[0])
+
+    def set_boost(self, spec_or_array) -> Optional[Dict]:
+        """The per-row prior `query(boost_weight=...)` adds to the cosine (INTEGRATION.md "Boosted search").  A dict is a spec of
+        `boost.prior_from_metadata` ({"key": K, "missing": 0.0}, or with "decay": "exp", "origin", "half_life"), evaluated over this
+        rank's metadata and again over the new rows of every `add`; a float array or tensor [rows] is taken as it is (`add` then needs
+        `boost=`).  The prior is kept in HBM as f32 (at `capacity` on a mutable collection), `arx_prior_info` runs once, and rows with
+        a NaN or +-inf prior are hidden from every boosted query.  `set_boost(None)` clears it.  -> {"rows", "max_abs_prior",
+        "non_finite"} (None after clearing).  ValueError: a bad spec, a non-numeric metadata value, another length."""
+        import torch
+        from .boost import prior_from_metadata
+        if spec_or_array is None:
+            self._boost_spec = self._boost_buf = None
+            self._boost_max = 0.0
+            return None
+        rows = self.hi - self.lo
+        if isinstance(spec_or_array, dict):
+            spec = dict(spec_or_array)
+            prior = prior_from_metadata([self.metadata[r] for r in range(self.lo, self.hi)], spec)
+        else:
+            spec = None
+            a = spec_or_array.detach().cpu().numpy() if torch.is_tensor(spec_or_array) else np.asarray(spec_or_array)
+            if a.dtype.kind != "f" or a.shape != (rows,):
+                raise ValueError(f"set_boost: a prior array must hold floats and have shape ({rows},), not {a.dtype} {tuple(a.shape)}")
+            with np.errstate(over="ignore"):
+                prior = np.ascontiguousarray(a, dtype=np.float32)
+        cap = getattr(self, "capacity", None)
+        buf = torch.zeros(rows if cap is None else cap, dtype=torch.float32, device=self._buf.device)
+        buf[:rows] = torch.from_numpy(prior).to(buf.device)
+        self._boost_spec, self._boost_buf = spec, buf
+        self._measure_prior()
+        return {"rows": rows, "max_abs_prior": self._boost_max, "non_finite": int((~np.isfinite(prior)).sum())}
 
     def build_ivf(self, n_lists: int, iters: int = 10, seed: int = 0, train_rows: Optional[int] = None) -> Dict:
         """Build the inverted lists `query(nprobe=...)` needs (INTEGRATION.md "IVF probe search"; `ivf.IvfIndex.build`): k-means with
@@ -567,7 +638,7 @@ class HipCollection:
     def query(self, query_embeddings=None, query_texts: Optional[Sequence[str]] = None, n_results: int = 10, reranker=None,
               n_candidates: int = 32, hybrid_alpha: Optional[float] = None, where=None, where_document=None,
               mmr_lambda: Optional[float] = None, group_by=None, chunks_per_group: int = 1, min_score=None,
-              nprobe: Optional[int] = None, binary_candidates: Optional[int] = None) -> Dict:
+              nprobe: Optional[int] = None, binary_candidates: Optional[int] = None, boost_weight=None) -> Dict:
         """Between the encoded queries and the rerank step this is the pipeline `search_queries` runs too: `retrieval.RowFilters` builds
         the row bitmaps, `retrieval.retrieve` searches, picks by MMR and fuses.
         `reranker` (a `rerank.HipCrossEncoder`; needs `query_texts`): the search fetches `n_candidates` (<= 32) rows per query,
@@ -642,13 +713,29 @@ class HipCollection:
         those, with the score bits and the order of the exact search, and an added `binary_count` list holds the candidates rescored
         per query.  Composes with a single `where`, `where_document` and the dedup and tombstone keep-bitmap (one bitmap per call),
         and with `reranker` and `mmr_lambda`, which consume the list (`n_candidates <= 32`).  ValueError, naming the part: `nprobe`,
-        `hybrid_alpha`, `group_by`, `min_score`, per-query filter lists, `world > 1`, or a collection without `build_binary`."""
+        `hybrid_alpha`, `group_by`, `min_score`, per-query filter lists, `world > 1`, or a collection without `build_binary`.
+        `boost_weight` (a float, or one per query; None = nothing changes; needs `set_boost` first): the boosted search (INTEGRATION.md
+        "Boosted search"): the exact top rows by float32(cosine + float32(weight * prior)) under the one bitmap of `where`,
+        `where_document` and the keep-bitmap.  `scores` holds the boosted values, `distances` follow them as they follow the cosine
+        otherwise, and an added `base_scores` list holds the cosines of the same rows.  `reranker` and `mmr_lambda` consume the list
+        as any other.  Refused with a ValueError (`boost.check_query_with_boost`) before anything is launched: `hybrid_alpha`,
+        `group_by`, `min_score`, `nprobe`, `binary_candidates`, per-query filter lists, `world > 1`, a weight that is not finite, or a
+        collection without `set_boost`."""
         import torch
         from .filter_sets import is_per_query
         from .grouping import check_grouped_query
         from .ranging import RERANK_BATCH, check_range_query
         from .retrieval import check_hybrid_on_device, check_shared_query, retrieve
         per_query = is_per_query(where) or is_per_query(where_document)
+        if boost_weight is not None:
+            from .boost import check_query_with_boost
+            nq_given = None if query_embeddings is None else (1 if np.ndim(query_embeddings) == 1 else len(query_embeddings))
+            nq_given = nq_given if nq_given is not None else (len(query_texts) if query_texts is not None else 1)
+            check_query_with_boost(boost_weight, has_prior=self._prior() is not None, per_query_filters=per_query,
+                                   hybrid_alpha=hybrid_alpha, group_by=group_by, min_score=min_score, nprobe=nprobe,
+                                   binary_candidates=binary_candidates, world=getattr(self, "world", 1),
+                                   n_width=n_candidates if (reranker is not None or mmr_lambda is not None) else n_results,
+                                   n_queries=nq_given, max_abs_prior=getattr(self, "_boost_max", 0.0))
         if binary_candidates is not None:
             from .binary import check_query_with_binary
             check_query_with_binary(binary_candidates, has_index=getattr(self, "binary", None) is not None, per_query_filters=per_query,
@@ -706,8 +793,9 @@ class HipCollection:
                        mmr_lambda=mmr_lambda, hybrid_alpha=hybrid_alpha, keyword=self.keyword, query_texts=query_texts,
                        hybrid_on_device=on_device, world=getattr(self, "world", 1),
                        **({} if nprobe is None else {"nprobe": nprobe, "ivf": self.ivf}),
-                       **({} if binary_candidates is None else {"binary_candidates": binary_candidates, "binary": self.binary}))
-        s, i, hyb, kws = hit.scores, hit.ids, hit.hybrid, hit.keyword
+                       **({} if binary_candidates is None else {"binary_candidates": binary_candidates, "binary": self.binary}),
+                       **({} if boost_weight is None else {"boost_weight": boost_weight, "prior": self._prior(), "max_abs_prior": self._boost_max}))
+        s, i, hyb, kws, base = hit.scores, hit.ids, hit.hybrid, hit.keyword, hit.base
         if reranker is not None:
             from .rerank import rerank_candidates, reorder_by_rerank
             texts = {int(j): self.metadata[int(j)].get("text") or "" for j in np.unique(i) if j >= 0}
@@ -717,6 +805,8 @@ class HipCollection:
             picked = reorder_by_rerank(i, sc, n_results)
             width = max([len(p) for p in picked] + [1])
             s2 = np.full((len(picked), width), -np.inf, np.float32); i2 = np.full((len(picked), width), -1, np.int64)
+            if base is not None:
+                base = np.array([[base[qi, p[r][0]] if r < len(p) else -np.inf for r in range(width)] for qi, p in enumerate(picked)], np.float32)
             rr = [[h[2] for h in p] for p in picked]
             for qi, p in enumerate(picked):
                 for r, (pos, j, _) in enumerate(p):
@@ -745,6 +835,8 @@ class HipCollection:
             out["ivf_scanned"] = [int(v) for v in hit.ivf_scanned]
         if hit.binary_count is not None:
             out["binary_count"] = [int(v) for v in hit.binary_count]
+        if base is not None:
+            out["base_scores"] = [base[qi][i[qi] >= 0].tolist() for qi in range(q.shape[0])]
         if hit.mmr is not None:
             out["mmr_scores"] = [hit.mmr[qi][i[qi] >= 0].tolist() for qi in range(q.shape[0])]
         if reranker is not None:

@@ -413,6 +413,38 @@ int32_t arx_topk_grouped_stats(const void* ws, int64_t* overflowed_queries, int6
  * max_row_norm wants. */
 int32_t arx_group_runs_info(const int32_t* group_of, int64_t n_rows, int64_t* out, void* stream);
 
+/* ---- Boosted exact search: top-k of cosine plus a weighted row prior (score boosting, a rank profile; csrc/boosted.hip) ---------------
+ * prior: device f32 [n_rows], 16-byte aligned, one value per row.  weight: device f32 [n_queries], one per query.  allow: a row bitmap
+ * in the convention of arx_topk_search_filtered, NULL = every row; n_allowed as there (-1 = unknown).
+ * Row r is visible to query q when its bit is set (or allow is NULL) and p(q, r) = fl32(weight[q] * prior[r]) is finite: a NaN or +-inf
+ * prior hides the row from every query, a non-finite weight gives its query no rows, and no NaN is ever ranked or returned.
+ *   base(q, r)    = the f32 score arx_topk_search and arx_topk_search_filtered give the pair, bit for bit
+ *   boosted(q, r) = fl32(base(q, r) + p(q, r)): two separately rounded f32 operations, no FMA (numpy: base + np.float32(w) * prior)
+ * The answer is the k best visible rows by (boosted desc, row asc):
+ *   out_scores f32 [n_queries, k] = boosted, out_base f32 [n_queries, k] = base of the same rows, out_ids int64 [n_queries, k] =
+ *   idx_base + row; padding (-inf, -inf, -1).  weight[q] == 0: the ids and base bits of arx_topk_search_filtered.
+ * max_abs_prior: an upper bound on |prior[r]| over the finite values, the caller's contract as max_row_norm is (arx_prior_info measures
+ * it): too small voids the exactness proof (csrc/boosted.hip), too large only widens the candidate set.  max_row_norm as for the
+ * filtered search, 0 = unit rows.  1 <= k <= 32, dim % 64 == 0 up to 8192, any n_queries (sliced above 1 024).
+ * path: 0 = library's choice, 1 = the scan, 2 = exhaustive over the visible rows; cand_cap = candidate groups a query may list before it
+ * goes to the exhaustive path (0 = default 1 024, at most 8192): test hooks, same bits for every choice.  A query's output depends on
+ * its row of `queries`, its weight, the prior, the bitmap and the corpus alone - not on the batch, its order, the path or cand_cap.
+ * A null or misaligned pointer, a negative size, k or dim out of range, a max_abs_prior that is negative or not finite, a workspace
+ * that is too small: ARX_ERR_ARG before any launch, the message naming the part.
+ * ws: device workspace of arx_topk_search_boosted_workspace_bytes(...) bytes, caller-owned (-1 for an unsupported shape); the stats
+ * counters sit at its start as the siblings' do. */
+int64_t arx_topk_search_boosted_workspace_bytes(int64_t n_rows, int32_t n_queries, int32_t dim, int32_t k);
+int32_t arx_topk_search_boosted(const void* corpus, int64_t n_rows, const float* prior, float max_abs_prior, const float* weight,
+                                const uint64_t* allow, int64_t n_allowed, const void* queries, int32_t n_queries, int32_t dim, int32_t k,
+                                float* out_scores, float* out_base, int64_t* out_ids, int64_t idx_base, float max_row_norm, void* ws,
+                                int64_t ws_bytes, int32_t path, int32_t cand_cap, void* stream);
+/* {queries sent to the exhaustive path because their candidate list overflowed, candidate groups rescored} of the LAST boosted search
+ * on this workspace.  Copies 16 bytes to the host and waits on `stream`. */
+int32_t arx_topk_boosted_stats(const void* ws, int64_t* overflowed_queries, int64_t* candidate_groups, void* stream);
+/* out (device int64 [2], written by the kernels on `stream`): out[0] = the f32 bits (in the low word) of the largest |finite value| of
+ * prior[0 .. n_rows), 0 when there is none; out[1] = the number of non-finite values (NaN, +-inf).  One pass.  What max_abs_prior wants. */
+int32_t arx_prior_info(const float* prior, int64_t n_rows, int64_t* out, void* stream);
+
 /* ---- Score threshold (`min_score`): every row at or above a cosine, up to 1 024 exact rows per query (csrc/range.hip) ------------------
  * min_score: device f32 [n_queries], one threshold per query.  allow: a row bitmap in the convention of arx_topk_search_filtered, NULL =
  * every row; n_allowed as there (-1 = unknown).  For query q a visible row r QUALIFIES when score(q, r) >= min_score[q], compared in

@@ -62,11 +62,13 @@ def check_centre(centre, dim: int):
 
 
 def check_query_with_binary(binary_candidates, *, has_index: bool, per_query_filters: bool = False, hybrid_alpha=None, group_by=None,
-                            min_score=None, nprobe=None, world: int = 1, n_width: int = 1) -> None:
+                            min_score=None, nprobe=None, world: int = 1, n_width: int = 1, pq_candidates=None) -> None:
     """The refusals of `query(binary_candidates=...)`, `retrieve` and `search_queries`, each a ValueError naming the part, before any
     launch.  `n_width`: the rows the search returns per query (the reranker's or MMR's candidates, else n_results)."""
     if nprobe is not None:
         raise ValueError("binary_candidates cannot be combined with nprobe: both choose which rows get scored")
+    if pq_candidates is not None:
+        raise ValueError("binary_candidates cannot be combined with pq_candidates: both choose which rows get scored")
     if hybrid_alpha is not None:
         raise ValueError("binary_candidates cannot be combined with hybrid_alpha: the BM25 keyword search has no binary codes")
     if group_by:

@@ -67,7 +67,7 @@ def check_args(k, weight, n_queries: int, max_abs_prior: float = 0.0, dim=None) 
 
 def check_query_with_boost(boost_weight, *, has_prior: bool, per_query_filters: bool = False, hybrid_alpha=None, group_by=None,
                            min_score=None, nprobe=None, binary_candidates=None, world: int = 1, n_width: int = 1, n_queries: int = 1,
-                           max_abs_prior: float = 0.0) -> np.ndarray:
+                           max_abs_prior: float = 0.0, pq_candidates=None) -> np.ndarray:
     """The refusals of `query(boost_weight=...)`, `retrieve` and `search_queries`, each a ValueError naming the part, before any launch
     -> the weights as float32 [n_queries].  `n_width`: the rows the search returns per query (the reranker's or MMR's candidates, else
     n_results)."""
@@ -81,6 +81,8 @@ def check_query_with_boost(boost_weight, *, has_prior: bool, per_query_filters: 
         raise ValueError("boost_weight cannot be combined with nprobe: a boosted IVF search is out of scope")
     if binary_candidates is not None:
         raise ValueError("boost_weight cannot be combined with binary_candidates: a boosted binary-code search is out of scope")
+    if pq_candidates is not None:
+        raise ValueError("boost_weight cannot be combined with pq_candidates: a boosted product-quantised search is out of scope")
     if per_query_filters:
         raise ValueError("boost_weight cannot be combined with per-query filter lists: the boosted search takes one bitmap per call")
     if world > 1:

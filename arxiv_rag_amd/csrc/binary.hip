@@ -12,27 +12,22 @@
 //   scan    block (stretch p of rows_per_block rows, tile t of BIN_QT = 8 queries), four waves.  The tile's query words sit in LDS; a
 //           round gives every lane one row (a wave's 64 rows are one contiguous span of the code array and one word of `allow`: a zero
 //           word costs that one load), the lane reads its row's words once and keeps the eight distances in registers, so the code
-//           array is read once per query tile.  Each query keeps a list of BIN_CAP keys in LDS: a lane appends a key above the list's
-//           threshold (0 until the list has been cut once; afterwards its R-th largest key) through an integer LDS slot counter; before
-//           a round that could overflow a list, the lists that could are cut back to their R largest by a block-wide bitonic sort
-//           (bm25.hip's, over all those lists in the same stages).  A key at or below the R-th largest of keys already seen is not
-//           among the R largest of all, so the block's final list is the exact R largest keys of its stretch, sorted, whatever the
+//           array is read once per query tile.  Each query keeps a list of KEY_CAP keys in LDS (key_lists.h, shared with pq.hip): a
+//           lane appends a key above the list's threshold, and the lists are cut back to their R largest by a block-wide sort before a
+//           round that could overflow one, so the block's final list is the exact R largest keys of its stretch, sorted, whatever the
 //           order of the appends.  -> part_k [parts][nq][R] (0 = none).
-//   merge   one block per query over its parts * R keys, any number of them, through the same list and cut -> out_cand / out_dist /
-//           out_count.
+//   merge   key_lists.h's: one block per query over its parts * R keys, any number of them -> out_cand / out_dist / out_count.
 // No float work at all, no global atomics.  A query's outputs are the R largest of a set of distinct integer keys: they depend on its
 // qcodes row, codes and allow alone, not on the batch, the tile or rows_per_block.  codes, qcodes and allow are device data of which
 // every bit pattern is a legal value; bits of allow at or beyond n_rows are masked off before use.
 #include "arx_common.h"
+#include "key_lists.h"
 
 namespace {
-constexpr int BIN_NT = 256, BIN_NW = BIN_NT / 64;
+constexpr int BIN_NT = KEY_NT, BIN_NW = BIN_NT / 64;
 constexpr int BIN_QT = 8;                       // queries of a tile
-constexpr int BIN_CAP = 1024;                   // keys of a query's list (8 lists: 64 KiB of LDS)
-constexpr int BIN_R_MAX = 256;
+constexpr int BIN_R_MAX = KEY_R_MAX;
 constexpr int BIN_W_MAX = 128;                  // dim 8192
-constexpr int BIN_QBATCH = 256;                 // queries per slice of a call
-constexpr int64_t BIN_SLOTS_MAX = 1ll << 15;    // (part, query) lists the workspace holds at most: 64 MiB at R = 256
 constexpr int BIN_BLOCKS_TARGET = 1024;         // the default rows_per_block aims at this many scan blocks
 constexpr int BIN_RPB_MIN_DEFAULT = 2048;
 constexpr int BIN_RPB_LIMIT = 1 << 20;
@@ -53,65 +48,12 @@ __global__ __launch_bounds__(BIN_NT) void binary_pack_kernel(const f16_t* __rest
     if (g0 + lane < n_words) out[g0 + lane] = mine;
 }
 
-template <int NL>                               // NL lists: BIN_QT in the scan, one in the merge
-struct BinLists {
-    unsigned long long keys[NL][BIN_CAP];
-    unsigned long long thr[NL];
-    int cnt[NL];
-};
-
-// Cut the lists of `mask` (list l holds min(cnt[l], BIN_CAP) keys in any order) back to their n largest, sorted descending; updates cnt
-// and thr.  The whole block; mask block-uniform; earlier writes to the lists are behind a barrier already; ends with a barrier.
-template <int NL>
-__device__ __forceinline__ void bin_cut(BinLists<NL>& sm, unsigned mask, int n) {
-    const int tid = threadIdx.x;
-    for (int t = tid; t < NL * BIN_CAP; t += BIN_NT) {
-        const int l = t / BIN_CAP, i = t % BIN_CAP;
-        if (((mask >> l) & 1u) && i >= sm.cnt[l]) sm.keys[l][i] = 0ull;
-    }
-    __syncthreads();
-    for (int k = 2; k <= BIN_CAP; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < NL * (BIN_CAP / 2); t += BIN_NT) {
-                const int l = t / (BIN_CAP / 2), u = t % (BIN_CAP / 2);
-                if (!((mask >> l) & 1u)) continue;
-                const int i = ((u & ~(j - 1)) << 1) | (u & (j - 1)), p = i | j;           // p < BIN_CAP
-                const unsigned long long a = sm.keys[l][i], b = sm.keys[l][p];
-                if (((i & k) == 0) ? a < b : a > b) { sm.keys[l][i] = b; sm.keys[l][p] = a; }
-            }
-            __syncthreads();
-        }
-    if (tid < NL && ((mask >> tid) & 1u)) {
-        const int c = sm.cnt[tid] < BIN_CAP ? sm.cnt[tid] : BIN_CAP;
-        sm.cnt[tid] = c < n ? c : n;
-        sm.thr[tid] = c >= n ? sm.keys[tid][n - 1] : 0ull;
-    }
-    __syncthreads();
-}
-
-// the lists (of the first nl) that the next round of at most BIN_NT appends each could overflow; block-uniform once cnt is stable
-template <int NL>
-__device__ __forceinline__ unsigned bin_full_mask(const BinLists<NL>& sm, int nl) {
-    unsigned m = 0;
-#pragma unroll
-    for (int l = 0; l < NL; ++l) m |= (l < nl && sm.cnt[l] + BIN_NT > BIN_CAP) ? (1u << l) : 0u;
-    return m;
-}
-
-template <int NL>
-__device__ __forceinline__ void bin_append(BinLists<NL>& sm, int l, unsigned long long key) {
-    if (key > sm.thr[l]) {
-        const int pos = atomicAdd(&sm.cnt[l], 1);              // integer slot counter; pos < BIN_CAP: the lists are cut before a round that could overflow
-        if (pos < BIN_CAP) sm.keys[l][pos] = key;
-    }
-}
-
 // V: 64-bit words per load (2: a 16-byte load, W even; 1: any W)
 template <int V>
 __global__ __launch_bounds__(BIN_NT) void binary_scan_kernel(const uint64_t* __restrict__ codes, int64_t n_rows, int W,
                                                              const uint64_t* __restrict__ qcodes, int nq, const uint64_t* __restrict__ allow,
                                                              int R, int64_t rpb, unsigned long long* __restrict__ part_k) {
-    __shared__ BinLists<BIN_QT> sm;
+    __shared__ KeyLists<BIN_QT> sm;
     __shared__ __attribute__((aligned(16))) uint64_t qs[BIN_W_MAX][BIN_QT];              // word-major: a word's eight query words are adjacent
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int q0 = blockIdx.y * BIN_QT;
@@ -125,9 +67,9 @@ __global__ __launch_bounds__(BIN_NT) void binary_scan_kernel(const uint64_t* __r
     const int64_t lo = (int64_t)blockIdx.x * rpb;             // a multiple of 64
     const int64_t hi = lo + rpb < n_rows ? lo + rpb : n_rows;
     for (int64_t base = lo; base < hi; base += BIN_NT) {      // block-uniform
-        const unsigned full = bin_full_mask(sm, nl);
+        const unsigned full = key_full_mask(sm, nl);
         __syncthreads();                                       // everyone has read cnt before anyone appends or cuts
-        if (full) bin_cut(sm, full, R);
+        if (full) key_cut(sm, full, R);
         const int64_t r0 = base + (int64_t)w * 64;             // the wave's 64 rows: one word of allow
         uint64_t vis = 0ull;
         if (r0 < hi) {
@@ -159,61 +101,22 @@ __global__ __launch_bounds__(BIN_NT) void binary_scan_kernel(const uint64_t* __r
                 const unsigned long long low = (unsigned long long)(0xffffffffu - (uint32_t)row);
 #pragma unroll
                 for (int l = 0; l < BIN_QT; ++l)
-                    if (l < nl) bin_append(sm, l, ((unsigned long long)(0x7fffffffu - (uint32_t)d[l]) << 32) | low);
+                    if (l < nl) key_append(sm, l, ((unsigned long long)(0x7fffffffu - (uint32_t)d[l]) << 32) | low);
             }
         }
         __syncthreads();
     }
-    bin_cut(sm, (1u << nl) - 1u, R);
+    key_cut(sm, (1u << nl) - 1u, R);
     for (int t = tid; t < nl * R; t += BIN_NT) {
         const int l = t / R, r = t % R;
         part_k[((int64_t)blockIdx.x * nq + q0 + l) * R + r] = r < sm.cnt[l] ? sm.keys[l][r] : 0ull;
     }
 }
 
-// one block per query: the parts * R keys of its partial lists -> its R largest, as (row, distance), and their number
-__global__ __launch_bounds__(BIN_NT) void binary_merge_kernel(const unsigned long long* __restrict__ part_k, int64_t parts, int nq, int R,
-                                                              int32_t* __restrict__ out_cand, int32_t* __restrict__ out_dist,
-                                                              int64_t* __restrict__ out_count) {
-    __shared__ BinLists<1> sm;
-    const int tid = threadIdx.x, q = blockIdx.x;
-    if (tid == 0) { sm.cnt[0] = 0; sm.thr[0] = 0ull; }
-    __syncthreads();
-    const int64_t total = parts * R;
-    for (int64_t e0 = 0; e0 < total; e0 += BIN_NT) {          // block-uniform
-        const unsigned full = bin_full_mask(sm, 1);
-        __syncthreads();
-        if (full) bin_cut(sm, 1u, R);
-        const int64_t e = e0 + tid;
-        if (e < total) {
-            const int64_t p = e / R;
-            bin_append(sm, 0, part_k[(p * nq + q) * R + (e - p * R)]);                   // (thr >= 0: an empty slot is never appended)
-        }
-        __syncthreads();
-    }
-    bin_cut(sm, 1u, R);
-    for (int r = tid; r < R; r += BIN_NT) {
-        const unsigned long long key = r < sm.cnt[0] ? sm.keys[0][r] : 0ull;
-        out_cand[(int64_t)q * R + r] = key ? (int32_t)(0xffffffffu - (uint32_t)key) : -1;
-        if (out_dist) out_dist[(int64_t)q * R + r] = key ? (int32_t)(0x7fffffffu - (uint32_t)(key >> 32)) : -1;
-    }
-    if (tid == 0) out_count[q] = sm.cnt[0];
-}
-
 // ---- host ---------------------------------------------------------------------------------------------------------------------------------
 bool bin_dim_ok(int32_t dim) { return dim >= 64 && dim % 64 == 0 && dim <= 64 * BIN_W_MAX; }
 bool bin_shape_ok(int64_t n_rows, int32_t n_queries, int32_t dim, int32_t R) {
     return n_rows >= 0 && n_rows < (1ll << 31) && n_queries >= 1 && bin_dim_ok(dim) && R >= 1 && R <= BIN_R_MAX;
-}
-struct BinWs { int64_t slots, total; int qb; };
-BinWs bin_layout(int64_t n_rows, int n_queries, int R) {
-    BinWs w;
-    w.qb = n_queries < BIN_QBATCH ? n_queries : BIN_QBATCH;
-    const int64_t parts = (n_rows + 63) / 64 > 0 ? (n_rows + 63) / 64 : 1;             // at the smallest rows_per_block
-    w.slots = parts * w.qb < BIN_SLOTS_MAX ? parts * w.qb : BIN_SLOTS_MAX;
-    if (w.slots < w.qb) w.slots = w.qb;
-    w.total = round_up64(w.slots * R * 8, 256);
-    return w;
 }
 }      // namespace
 
@@ -234,7 +137,7 @@ extern "C" int32_t arx_binary_pack(const void* rows, int64_t n_rows, int32_t dim
 
 extern "C" int64_t arx_binary_workspace_bytes(int64_t n_rows, int32_t n_queries, int32_t dim, int32_t n_candidates) {
     if (!bin_shape_ok(n_rows, n_queries, dim, n_candidates)) return -1;
-    return bin_layout(n_rows, n_queries, n_candidates).total;
+    return key_layout(n_rows, n_queries, n_candidates).total;
 }
 
 extern "C" int32_t arx_binary_candidates_tuned(const uint64_t* codes, int64_t n_rows, int32_t dim, const uint64_t* qcodes, int32_t n_queries,
@@ -251,13 +154,13 @@ extern "C" int32_t arx_binary_candidates_tuned(const uint64_t* codes, int64_t n_
     ARX_REQUIRE(((uintptr_t)codes | (uintptr_t)ws) % 16 == 0, "codes and ws must be 16-byte aligned");
     ARX_REQUIRE(((uintptr_t)qcodes | (uintptr_t)allow | (uintptr_t)out_count) % 8 == 0, "qcodes, allow and out_count must be 8-byte aligned");
     ARX_REQUIRE(((uintptr_t)out_cand | (uintptr_t)out_dist) % 4 == 0, "out_cand and out_dist must be 4-byte aligned");
-    const BinWs L = bin_layout(n_rows, n_queries, R);
+    const KeyWs L = key_layout(n_rows, n_queries, R);
     ARX_REQUIRE(ws_bytes >= L.total, "workspace too small: %lld < %lld (arx_binary_workspace_bytes)", (long long)ws_bytes, (long long)L.total);
     hipStream_t st = (hipStream_t)stream;
     const int W = dim / 64;
     unsigned long long* part_k = (unsigned long long*)ws;
-    for (int q0 = 0; q0 < n_queries; q0 += BIN_QBATCH) {
-        const int nq = (n_queries - q0) < BIN_QBATCH ? (n_queries - q0) : BIN_QBATCH;
+    for (int q0 = 0; q0 < n_queries; q0 += KEY_QBATCH) {
+        const int nq = (n_queries - q0) < KEY_QBATCH ? (n_queries - q0) : KEY_QBATCH;
         const int tiles = (nq + BIN_QT - 1) / BIN_QT;
         int64_t rpb = rows_per_block;
         if (rpb == 0) {
@@ -274,7 +177,7 @@ extern "C" int32_t arx_binary_candidates_tuned(const uint64_t* codes, int64_t n_
         if (W % 2 == 0) binary_scan_kernel<2><<<grid, BIN_NT, 0, st>>>(codes, n_rows, W, Q, nq, allow, R, rpb, part_k);
         else binary_scan_kernel<1><<<grid, BIN_NT, 0, st>>>(codes, n_rows, W, Q, nq, allow, R, rpb, part_k);
         ARX_HIP_CHECK(hipGetLastError());
-        binary_merge_kernel<<<nq, BIN_NT, 0, st>>>(part_k, parts, nq, R, out_cand + (int64_t)q0 * R,
+        key_merge_kernel<false><<<nq, BIN_NT, 0, st>>>(part_k, parts, nq, R, out_cand + (int64_t)q0 * R,
                                                    out_dist ? out_dist + (int64_t)q0 * R : nullptr, out_count + q0);
         ARX_HIP_CHECK(hipGetLastError());
     }

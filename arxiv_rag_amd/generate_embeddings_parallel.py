@@ -680,7 +680,8 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
                    hybrid_on_device: bool = False, keyword_build_on_device: bool = False, document_regex: bool = False,
                    nprobe: Optional[int] = None, ivf_lists: Optional[int] = None, ivf_iters: int = 10, ivf_seed: int = 0,
                    binary_candidates: Optional[int] = None, binary_centre: Optional[str] = "mean", boost_spec: Optional[Dict] = None,
-                   boost_weight: Optional[float] = None) -> List[Dict]:
+                   boost_weight: Optional[float] = None, pq_candidates: Optional[int] = None, pq_dsub: int = 8,
+                   pq_centre: Optional[str] = "mean") -> List[Dict]:
     """Brute-force cosine top-k (config.yaml:63-64 `top_k: 10`) over the rank's fp16 rows in HBM; with
     torchrun each rank holds the contiguous row shard it encoded and the partial top-k lists are
     all-gathered over RCCL and merged.  `shard` is the `ShardSink` the encode step filled: rows [lo, hi) are already where they
@@ -759,7 +760,13 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
     `boost.prior_from_metadata(the chunks' metadata, boost_spec)` gives one prior per chunk, the ranking is by float32(cosine +
     float32(boost_weight * prior)) under the bitmap of `where`, `where_document` and `keep_mask`, every hit's "score" is the boosted
     value and an added "base_score" the cosine.  ValueError (`boost.check_query_with_boost`), before anything is launched:
-    `hybrid_alpha`, `group_by_paper`, `min_score`, `nprobe`, `binary_candidates`, a per-query `where` list, more than one rank."""
+    `hybrid_alpha`, `group_by_paper`, `min_score`, `nprobe`, `binary_candidates`, a per-query `where` list, more than one rank.
+    `pq_candidates` (None = nothing changes): the product-quantised search (INTEGRATION.md "Product-quantised search").  A `pq.PqIndex`
+    is trained and encoded over the shard (`pq_dsub` dimensions per code byte; `pq_centre`: "mean" or None / "none") and every query's
+    first `pq_candidates` (at most 256, at least the width the search returns) visible rows by the sum of its byte tables over the
+    codes are rescored exactly, `where` (one dict), `where_document` and `keep_mask` applied as without it; every entry of the
+    results then carries `pq_count`, the candidates rescored.  Composes with `reranker` and `mmr_lambda`.  Not together with `nprobe`,
+    `binary_candidates`, `hybrid_alpha`, `group_by_paper`, `min_score`, `boost_weight`, a per-query `where` list or more than one rank."""
     from .retrieval import RowFilters, check_hybrid_on_device, check_shared_query, retrieve
     if keyword_build_on_device and hybrid_alpha is None:
         raise ValueError("keyword_build_on_device needs hybrid_alpha: it chooses where the BM25 keyword index is built")
@@ -782,8 +789,17 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
                                group_by=group_by_paper, min_score=min_score, nprobe=nprobe if nprobe is not None else ivf_lists,
                                binary_candidates=binary_candidates, world=int(os.environ.get("WORLD_SIZE", "1")),
                                n_width=n_cand_of(reranker, rerank_top_k, mmr_lambda, mmr_fetch_k) if (reranker is not None or mmr_lambda is not None) else top_k,
-                               n_queries=len(queries))
+                               n_queries=len(queries), pq_candidates=pq_candidates)
         prior_host = prior_from_metadata([c.get("metadata") or {} for c in chunks], boost_spec)      # (a bad spec or value: refused here)
+    if pq_candidates is not None:
+        from .pq import check_dsub, check_query_with_pq
+        if pq_centre not in (None, "none", "mean"):
+            raise ValueError(f"pq_centre={pq_centre!r} must be \"mean\" or \"none\"")
+        check_query_with_pq(pq_candidates, has_index=True, per_query_filters=isinstance(where, (list, tuple)), hybrid_alpha=hybrid_alpha,
+                            group_by=group_by_paper, min_score=min_score, nprobe=nprobe if nprobe is not None else ivf_lists,
+                            binary_candidates=binary_candidates, boost_weight=boost_weight, world=int(os.environ.get("WORLD_SIZE", "1")),
+                            n_width=n_cand_of(reranker, rerank_top_k, mmr_lambda, mmr_fetch_k) if (reranker is not None or mmr_lambda is not None) else top_k)
+        check_dsub(int(shard.rows.shape[1]), pq_dsub)
     if binary_candidates is not None:
         from .binary import check_query_with_binary
         if binary_centre not in (None, "none", "mean"):
@@ -791,7 +807,8 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
         check_query_with_binary(binary_candidates, has_index=True, per_query_filters=isinstance(where, (list, tuple)), hybrid_alpha=hybrid_alpha,
                                 group_by=group_by_paper, min_score=min_score, nprobe=nprobe if nprobe is not None else ivf_lists,
                                 world=int(os.environ.get("WORLD_SIZE", "1")),
-                                n_width=n_cand_of(reranker, rerank_top_k, mmr_lambda, mmr_fetch_k) if (reranker is not None or mmr_lambda is not None) else top_k)
+                                n_width=n_cand_of(reranker, rerank_top_k, mmr_lambda, mmr_fetch_k) if (reranker is not None or mmr_lambda is not None) else top_k,
+                                pq_candidates=pq_candidates)
     if nprobe is not None or ivf_lists is not None:
         from .ivf import check_build_args, check_query_with_nprobe
         if nprobe is None or ivf_lists is None:
@@ -827,7 +844,7 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
     # int8 pre-filter (same exact answers; +50 % shard memory, one quantisation pass): 1.5-1.7x the queries per second on small batches;
     # a filtered, a grouped and a range search run on the fp16 rows
     masked = (where is not None or keep_mask is not None or where_document is not None or group_by_paper or min_score is not None or nprobe is not None or binary_candidates is not None
-              or boost_weight is not None
+              or boost_weight is not None or pq_candidates is not None
               or (hybrid_on_device and n_cand_of(reranker, rerank_top_k, mmr_lambda, mmr_fetch_k) > HYBRID_CANDIDATES))
     index = ShardIndex(shard.rows, idx_base=shard.lo, prefilter="int8" if (dim % 128 == 0 and dim <= 1024 and n_rows > 0 and not masked) else None,
                        adaptive=True)
@@ -856,6 +873,7 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
                    hybrid_alpha=hybrid_alpha, keyword=keyword_index, query_texts=queries, hybrid_on_device=hybrid_on_device, world=world,
                    **({} if nprobe is None else {"nprobe": int(nprobe), "ivf": build_ivf_index(index, ivf_lists, ivf_iters, ivf_seed)}),
                    **({} if binary_candidates is None else {"binary_candidates": int(binary_candidates), "binary": build_binary_index(index, binary_centre)}),
+                   **({} if pq_candidates is None else {"pq_candidates": int(pq_candidates), "pq": build_pq_index(index, pq_dsub, pq_centre)}),
                    **({} if boost_weight is None else {"boost_weight": float(boost_weight), "prior": torch.from_numpy(prior_host).to(dev)}))
     base_of = (lambda qi, p: {}) if hit.base is None else (lambda qi, p: {"base_score": float(hit.base[qi, p])})
     s, i, grp, truncated, mmr_val, hyb, kws = hit.scores, hit.ids, hit.groups, hit.truncated, hit.mmr, hit.hybrid, hit.keyword
@@ -878,6 +896,8 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
                                                                               **({} if hit.ivf_hits is None else {"ivf_hits": int(hit.ivf_hits[qi])})})
     if hit.binary_count is not None:
         scanned_of = lambda qi: {"binary_count": int(hit.binary_count[qi])}      # noqa: E731
+    if hit.pq_count is not None:
+        scanned_of = lambda qi: {"pq_count": int(hit.pq_count[qi])}              # noqa: E731
 
     def hybrid_fields(qi, p):                                # (null, not NaN, in the JSON file)
         if hyb is None:
@@ -932,6 +952,15 @@ def build_binary_index(index, centre: Optional[str] = "mean"):
     n, w = (int(v) for v in bi.codes.shape)
     print(f"Binary index: {n} rows x {w * 64} sign bits ({n * w * 8} bytes), centre {'none' if bi.centre is None else 'mean'}")
     return bi
+
+
+def build_pq_index(index, dsub: int = 8, centre: Optional[str] = "mean"):
+    """`--pq-candidates`: the `pq.PqIndex` of the search step's shard (codebooks trained here), with its size printed."""
+    from .pq import PqIndex
+    pi = PqIndex.build(index, dsub=int(dsub), centre=None if centre in (None, "none") else "mean")
+    n, m = (int(v) for v in pi.codes.shape)
+    print(f"PQ index: {n} rows x {m} code bytes (dsub {int(dsub)}, {n * m} bytes), centre {'none' if pi.centre is None else 'mean'}")
+    return pi
 
 
 # --------------------------------------------------------------------------------------------- main
@@ -1037,6 +1066,16 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--binary-centre", choices=("mean", "none"), default="mean",
                    help="What the sign bits of --binary-candidates are taken against: the column mean of the chunks' rows, or zero "
                         "(default: mean)")
+    p.add_argument("--pq-candidates", type=int, default=None,
+                   help="Product-quantised search: rank every chunk by the sum of the query's byte look-up tables over its 8-bit PQ "
+                        "code and rescore the best this many exactly (1..256, at least the search's width; default: off; needs "
+                        "--queries; one GPU rank only; not with --nprobe, --binary-candidates, --hybrid-alpha, --group-by-paper, "
+                        "--min-score, --boost-key or --where-file)")
+    p.add_argument("--pq-dsub", type=int, default=8,
+                   help="Dimensions per code byte of --pq-candidates: a power of two in 4..64 (default: 8, dim / 8 bytes per chunk)")
+    p.add_argument("--pq-centre", choices=("mean", "none"), default="mean",
+                   help="What the rows are centred on before --pq-candidates encodes them: the column mean of the chunks' rows, or "
+                        "zero (default: mean)")
     p.add_argument("--boost-key", type=str, default=None,
                    help="Boosted search: rank by cosine + --boost-weight * prior, the prior being this metadata key's numeric value "
                         "(missing: 0), or its exponential decay with --boost-decay-origin / --boost-half-life (default: off; needs "
@@ -1215,35 +1254,54 @@ def check_ivf_args(args) -> Optional[str]:
     return None
 
 
-def check_binary_args(args) -> Optional[str]:
-    """-> an error message for an unusable --binary-candidates, else None.  (The other flags are read with getattr: absent = off.)"""
-    r = getattr(args, "binary_candidates", None)
-    if r is None:
-        return None
+def _check_candidate_scan_args(args, flag: str, r, codes: str, scan: str, also=()) -> Optional[str]:
+    """The refusals the candidate-scan modes of the search step share (--binary-candidates, --pq-candidates): `r` the flag's value,
+    `codes` / `scan` the mode's words for its codes and its scan, `also` further (flag, on, why) refusals placed after --nprobe."""
     if not (1 <= r <= 256):
-        return f"--binary-candidates {r} must be in [1, 256]"
+        return f"{flag} {r} must be in [1, 256]"
     if not getattr(args, "queries", None):
-        return "--binary-candidates needs --queries: it is a mode of the search step"
-    if getattr(args, "nprobe", None) is not None or getattr(args, "ivf_lists", None) is not None:
-        return "--binary-candidates cannot be combined with --nprobe / --ivf-lists: both choose which rows get scored"
-    if getattr(args, "hybrid_alpha", None) is not None:
-        return "--binary-candidates cannot be combined with --hybrid-alpha: the BM25 keyword search has no binary codes"
-    if getattr(args, "group_by_paper", False):
-        return "--binary-candidates cannot be combined with --group-by-paper: the grouped search reads every row"
-    if getattr(args, "min_score", None) is not None:
-        return "--binary-candidates cannot be combined with --min-score: the range search reads every row"
-    if getattr(args, "where_filters", None) is not None:
-        return "--binary-candidates cannot be combined with --where-file: the Hamming scan takes one bitmap per call"
+        return f"{flag} needs --queries: it is a mode of the search step"
+    for other, on, why in (
+            ("--nprobe / --ivf-lists", getattr(args, "nprobe", None) is not None or getattr(args, "ivf_lists", None) is not None,
+             "both choose which rows get scored"),
+            *also,
+            ("--hybrid-alpha", getattr(args, "hybrid_alpha", None) is not None, f"the BM25 keyword search has no {codes}"),
+            ("--group-by-paper", getattr(args, "group_by_paper", False), "the grouped search reads every row"),
+            ("--min-score", getattr(args, "min_score", None) is not None, "the range search reads every row"),
+            ("--where-file", getattr(args, "where_filters", None) is not None, f"{scan} takes one bitmap per call")):
+        if on:
+            return f"{flag} cannot be combined with {other}: {why}"
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        return "--binary-candidates needs a single GPU rank: more than one rank is out of scope"
+        return f"{flag} needs a single GPU rank: more than one rank is out of scope"
     width = getattr(args, "top_k", 10)
     if getattr(args, "rerank_model", None):
         width = getattr(args, "rerank_top_k", 32)
     elif getattr(args, "mmr_lambda", None) is not None:
         width = getattr(args, "mmr_fetch_k", 32)
     if r < width:
-        return f"--binary-candidates {r} is below the {width} rows the search returns per query"
+        return f"{flag} {r} is below the {width} rows the search returns per query"
     return None
+
+
+def check_binary_args(args) -> Optional[str]:
+    """-> an error message for an unusable --binary-candidates, else None.  (The other flags are read with getattr: absent = off.)"""
+    r = getattr(args, "binary_candidates", None)
+    if r is None:
+        return None
+    return _check_candidate_scan_args(args, "--binary-candidates", r, "binary codes", "the Hamming scan")
+
+
+def check_pq_args(args) -> Optional[str]:
+    """-> an error message for an unusable --pq-candidates / --pq-dsub, else None.  (The other flags are read with getattr: absent = off.)"""
+    r = getattr(args, "pq_candidates", None)
+    if r is None:
+        return None
+    if 1 <= r <= 256 and getattr(args, "pq_dsub", 8) not in (4, 8, 16, 32, 64):
+        return f"--pq-dsub {getattr(args, 'pq_dsub', 8)} must be a power of two in [4, 64]"
+    return _check_candidate_scan_args(
+        args, "--pq-candidates", r, "PQ codes", "the code scan",
+        also=(("--binary-candidates", getattr(args, "binary_candidates", None) is not None, "both choose which rows get scored"),
+              ("--boost-key", getattr(args, "boost_key", None) is not None, "the boosted search reads every row")))
 
 
 def boost_spec_of(args) -> Optional[Dict]:
@@ -1512,7 +1570,7 @@ def main(argv: Optional[Sequence[str]] = None, model_factory: Optional[Callable]
     err = (check_rerank_args(args) or check_hybrid_args(args) or check_hybrid_filters_args(args) or check_hybrid_device_args(args) or check_keyword_build_args(args) or check_where_args(args) or check_where_file_args(args) or check_where_device_args(args)
            or check_where_document_args(args)
            or check_mmr_args(args) or check_dedup_args(args) or check_group_args(args) or check_range_args(args) or check_facets_args(args) or check_topics_args(args) or check_ivf_args(args)
-           or check_binary_args(args) or check_boost_args(args))
+           or check_binary_args(args) or check_pq_args(args) or check_boost_args(args))
     if err:
         print(f"Error: {err}")
         return 2
@@ -1620,6 +1678,8 @@ def main(argv: Optional[Sequence[str]] = None, model_factory: Optional[Callable]
                                   if args.nprobe is not None else {}),
                                **({"binary_candidates": args.binary_candidates, "binary_centre": args.binary_centre}
                                   if args.binary_candidates is not None else {}),
+                               **({"pq_candidates": args.pq_candidates, "pq_dsub": args.pq_dsub, "pq_centre": args.pq_centre}
+                                  if args.pq_candidates is not None else {}),
                                **({"boost_spec": boost_spec_of(args), "boost_weight": args.boost_weight} if args.boost_key is not None else {}))
                 if args.facet_keys is not None:
                     facet_counts(chunks, _model.encoder.device, args.facet_keys, args.facets_top,

@@ -200,6 +200,7 @@ class Retrieved:
     ivf_scanned: Optional[np.ndarray] = None     # nprobe: int64 [Q], the rows scored for every query
     ivf_hits: Optional[np.ndarray] = None        # nprobe with per-query filters or min_score: int64 [Q], the rows at or above the threshold
     binary_count: Optional[np.ndarray] = None    # binary_candidates: int64 [Q], the Hamming candidates rescored for every query
+    pq_count: Optional[np.ndarray] = None        # pq_candidates: int64 [Q], the PQ candidates rescored for every query
     base: Optional[np.ndarray] = None            # boost_weight: the cosine of every returned row (`scores` holds the boosted values)
 
 
@@ -235,7 +236,7 @@ def retrieve(index, q, filters: RowFilters, n_results: int, *, n_candidates: int
              hybrid_alpha: Optional[float] = None, keyword=None, query_texts: Optional[Sequence[str]] = None,
              hybrid_on_device: bool = False, world: int = 1, nprobe: Optional[int] = None, ivf=None,
              binary_candidates: Optional[int] = None, binary=None, boost_weight=None, prior=None,
-             max_abs_prior: Optional[float] = None) -> Retrieved:
+             max_abs_prior: Optional[float] = None, pq_candidates: Optional[int] = None, pq=None) -> Retrieved:
     """One search of the fp16 device queries `q` over `index` (a `ShardIndex`), in the mode the arguments name, every refusal behind it.
     The width: a range search (`min_score`) returns up to `n_candidates` rows with `reranked` and `n_results` without, a grouped search
     `n_results` groups, every other search `n_candidates` rows when something picks among them afterwards (`reranked`, `mmr_lambda`,
@@ -270,21 +271,33 @@ def retrieve(index, q, filters: RowFilters, n_results: int, *, n_candidates: int
     (`ShardIndex.search_boosted`); `scores` holds the boosted values and `base` the cosines of the same rows, in the same order
     (MMR's pick order included).  MMR and a reranker consume the list as any other.  ValueError (`boost.check_query_with_boost`):
     `hybrid_alpha`, `grouped`, `min_score`, `nprobe`, `binary_candidates`, per-query filter lists, `world > 1`, no `prior`, a weight
-    that is not finite, a width above 32."""
+    that is not finite, a width above 32.
+    `pq_candidates` (None = nothing changes) with `pq` (a `pq.PqIndex` over `index`): the product-quantised search (INTEGRATION.md
+    "Product-quantised search"): every query's first `pq_candidates` visible rows by (sum of its byte tables over the row's PQ code,
+    row), under the one bitmap of `where`, `where_document` and the keep-mask, rescored exactly; `pq_count` holds the candidates
+    rescored.  MMR and a reranker consume the list as any other.  ValueError (`pq.check_query_with_pq`): `nprobe`,
+    `binary_candidates`, `hybrid_alpha`, `grouped`, `min_score`, `boost_weight`, per-query filter lists, `world > 1`, no `pq`,
+    `pq_candidates` outside [width, 256], a width above 32."""
     import torch
     from .filter_sets import is_per_query
     nq = q.shape[0]
     k = n_candidates if (reranked or hybrid_alpha is not None or mmr_lambda is not None) else n_results
     per_query = is_per_query(where) or is_per_query(where_document)
+    if pq_candidates is not None:
+        from .pq import check_query_with_pq
+        check_query_with_pq(pq_candidates, has_index=pq is not None, per_query_filters=per_query, hybrid_alpha=hybrid_alpha, group_by=grouped,
+                            min_score=min_score, nprobe=nprobe, binary_candidates=binary_candidates, boost_weight=boost_weight, world=world,
+                            n_width=k)
     if boost_weight is not None:
         from .boost import check_query_with_boost
         boost_weight = check_query_with_boost(boost_weight, has_prior=prior is not None, per_query_filters=per_query, hybrid_alpha=hybrid_alpha,
                                               group_by=grouped, min_score=min_score, nprobe=nprobe, binary_candidates=binary_candidates,
-                                              world=world, n_width=k, n_queries=nq, max_abs_prior=0.0 if max_abs_prior is None else max_abs_prior)
+                                              world=world, n_width=k, n_queries=nq, max_abs_prior=0.0 if max_abs_prior is None else max_abs_prior,
+                                              pq_candidates=pq_candidates)
     if binary_candidates is not None:
         from .binary import check_query_with_binary
         check_query_with_binary(binary_candidates, has_index=binary is not None, per_query_filters=per_query, hybrid_alpha=hybrid_alpha,
-                                group_by=grouped, min_score=min_score, nprobe=nprobe, world=world, n_width=k)
+                                group_by=grouped, min_score=min_score, nprobe=nprobe, world=world, n_width=k, pq_candidates=pq_candidates)
     if nprobe is not None:
         from .ivf import check_query_with_nprobe
         check_query_with_nprobe(nprobe, has_index=ivf is not None, n_lists=getattr(ivf, "n_lists", 0), per_query_filters=per_query,
@@ -301,6 +314,9 @@ def retrieve(index, q, filters: RowFilters, n_results: int, *, n_candidates: int
     elif binary_candidates is not None:
         s, i, count = binary.search(q, k, int(binary_candidates), allow=filters.allow_of(where, where_document)[0])
         out.binary_count = count.cpu().numpy()
+    elif pq_candidates is not None:
+        s, i, count = pq.search(q, k, int(pq_candidates), allow=filters.allow_of(where, where_document)[0])
+        out.pq_count = count.cpu().numpy()
     elif boost_weight is not None:
         allow, n_allowed = filters.allow_of(where, where_document)
         s, base, i = index.search_boosted(q, k, prior, boost_weight, allow=allow, n_allowed=n_allowed, max_abs_prior=max_abs_prior)

@@ -326,6 +326,8 @@ class HipCollection:
             self.ivf.set_labels(torch.cat([self.ivf.labels, label_rows(self._buf[n:n + m], self.ivf.centroids_f16)]))
         if getattr(self, "binary", None) is not None:            # the new rows packed with the kept centre
             self.binary.append(self._buf[n:n + m], index=self.index)
+        if getattr(self, "pq", None) is not None:                # the new rows encoded with the kept codebooks and centre
+            self.pq.append(self._buf[n:n + m], index=self.index)
         if self._deleted is not None:
             self._deleted = np.concatenate([self._deleted, np.zeros(m, bool)])
         if self.dedup_threshold is not None:
@@ -427,6 +429,8 @@ class HipCollection:
             self.ivf.set_labels(ivf_labels[:count].contiguous())
         if getattr(self, "binary", None) is not None:            # the codes move as the rows moved: dim / 8-byte rows
             self.binary.compact(keep_words, word_rank, count, index=self.index)
+        if getattr(self, "pq", None) is not None:                # the PQ codes move as the rows moved: dim / dsub-byte rows
+            self.pq.compact(keep_words, word_rank, count, index=self.index)
         return old_to_new(keep)
 
     def _prior(self):
@@ -500,6 +504,28 @@ class HipCollection:
         self.binary = BinaryIndex.build(self.index, centre=kind)
         n, w = (int(v) for v in self.binary.codes.shape)
         return {"rows": n, "words_per_row": w, "code_bytes": n * w * 8, "centre": "mean" if isinstance(kind, str) else ("none" if kind is None else "given")}
+
+    def build_pq(self, dsub: int = 8, centre="mean", train_rows: int = 65536, iters: int = 10, seed: int = 0, codebooks=None) -> Dict:
+        """Train the codebooks and encode the 8-bit PQ codes `query(pq_candidates=...)` needs (INTEGRATION.md "Product-quantised
+        search"; `pq.PqIndex.build`): one byte per `dsub` dimensions of every row (tombstoned ones included: the keep-bitmap hides
+        them at query time), the nearest of 256 sub-centroids to the centred row.  `centre` as `build_binary` takes it; `codebooks`: a
+        float array [dim / dsub, 256, dsub] kept unchanged, or None: Lloyd's algorithm over at most `train_rows` rows, `iters` rounds.
+        Again replaces the codes, the codebooks and the centre; nothing recomputes them otherwise: `add` encodes the new rows with
+        them, `compact` moves the codes.  -> {rows, dsub, bytes_per_row, code_bytes, centre, trained}.  ValueError before any launch:
+        `world > 1`, a dim, dsub or dim / dsub outside the limits, a centre or codebooks of another shape or not finite, an empty
+        collection without `codebooks`."""
+        from .binary import check_centre
+        from .pq import PqIndex, check_codebooks, check_dsub
+        if getattr(self, "world", 1) > 1:
+            raise ValueError("build_pq needs world == 1: more than one rank is out of scope")
+        check_dsub(int(self.dim), dsub)
+        kind = check_centre(centre, int(self.dim))
+        if codebooks is not None:
+            codebooks = check_codebooks(codebooks, int(self.dim), dsub)
+        self.pq = PqIndex.build(self.index, dsub=dsub, centre=kind, codebooks=codebooks, train_rows=train_rows, iters=iters, seed=seed)
+        n, m = (int(v) for v in self.pq.codes.shape)
+        return {"rows": n, "dsub": int(dsub), "bytes_per_row": m, "code_bytes": n * m,
+                "centre": "mean" if isinstance(kind, str) else ("none" if kind is None else "given"), "trained": codebooks is None}
 
     def get(self, ids: Sequence) -> Dict:
         """-> {ids, metadatas, documents} of the rows with these `chunk_id`s, in the order asked, from the host lists (the shape of one
@@ -638,7 +664,8 @@ class HipCollection:
     def query(self, query_embeddings=None, query_texts: Optional[Sequence[str]] = None, n_results: int = 10, reranker=None,
               n_candidates: int = 32, hybrid_alpha: Optional[float] = None, where=None, where_document=None,
               mmr_lambda: Optional[float] = None, group_by=None, chunks_per_group: int = 1, min_score=None,
-              nprobe: Optional[int] = None, binary_candidates: Optional[int] = None, boost_weight=None) -> Dict:
+              nprobe: Optional[int] = None, binary_candidates: Optional[int] = None, boost_weight=None,
+              pq_candidates: Optional[int] = None) -> Dict:
         """Between the encoded queries and the rerank step this is the pipeline `search_queries` runs too: `retrieval.RowFilters` builds
         the row bitmaps, `retrieval.retrieve` searches, picks by MMR and fuses.
         `reranker` (a `rerank.HipCrossEncoder`; needs `query_texts`): the search fetches `n_candidates` (<= 32) rows per query,
@@ -720,13 +747,27 @@ class HipCollection:
         otherwise, and an added `base_scores` list holds the cosines of the same rows.  `reranker` and `mmr_lambda` consume the list
         as any other.  Refused with a ValueError (`boost.check_query_with_boost`) before anything is launched: `hybrid_alpha`,
         `group_by`, `min_score`, `nprobe`, `binary_candidates`, per-query filter lists, `world > 1`, a weight that is not finite, or a
-        collection without `set_boost`."""
+        collection without `set_boost`.
+        `pq_candidates` (an integer R in [width, 256], the width as for `binary_candidates`; None = nothing changes; needs `build_pq`
+        first): the product-quantised search (INTEGRATION.md "Product-quantised search").  Every row is ranked by the sum of the
+        query's byte look-up tables over its PQ code (`arx_pq_candidates`), and the first R visible rows by (sum desc, row) are
+        rescored exactly: the exact top rows among those, with the score bits and the order of the exact search, and an added
+        `pq_count` list holds the candidates rescored per query.  Composes with a single `where`, `where_document` and the dedup and
+        tombstone keep-bitmap (one bitmap per call), and with `reranker` and `mmr_lambda` (`n_candidates <= 32`).  ValueError, naming
+        the part: `nprobe`, `binary_candidates`, `hybrid_alpha`, `group_by`, `min_score`, `boost_weight`, per-query filter lists,
+        `world > 1`, or a collection without `build_pq`."""
         import torch
         from .filter_sets import is_per_query
         from .grouping import check_grouped_query
         from .ranging import RERANK_BATCH, check_range_query
         from .retrieval import check_hybrid_on_device, check_shared_query, retrieve
         per_query = is_per_query(where) or is_per_query(where_document)
+        if pq_candidates is not None:
+            from .pq import check_query_with_pq
+            check_query_with_pq(pq_candidates, has_index=getattr(self, "pq", None) is not None, per_query_filters=per_query,
+                                hybrid_alpha=hybrid_alpha, group_by=group_by, min_score=min_score, nprobe=nprobe,
+                                binary_candidates=binary_candidates, boost_weight=boost_weight, world=getattr(self, "world", 1),
+                                n_width=n_candidates if (reranker is not None or mmr_lambda is not None) else n_results)
         if boost_weight is not None:
             from .boost import check_query_with_boost
             nq_given = None if query_embeddings is None else (1 if np.ndim(query_embeddings) == 1 else len(query_embeddings))
@@ -735,12 +776,13 @@ class HipCollection:
                                    hybrid_alpha=hybrid_alpha, group_by=group_by, min_score=min_score, nprobe=nprobe,
                                    binary_candidates=binary_candidates, world=getattr(self, "world", 1),
                                    n_width=n_candidates if (reranker is not None or mmr_lambda is not None) else n_results,
-                                   n_queries=nq_given, max_abs_prior=getattr(self, "_boost_max", 0.0))
+                                   n_queries=nq_given, max_abs_prior=getattr(self, "_boost_max", 0.0), pq_candidates=pq_candidates)
         if binary_candidates is not None:
             from .binary import check_query_with_binary
             check_query_with_binary(binary_candidates, has_index=getattr(self, "binary", None) is not None, per_query_filters=per_query,
                                     hybrid_alpha=hybrid_alpha, group_by=group_by, min_score=min_score, nprobe=nprobe, world=getattr(self, "world", 1),
-                                    n_width=n_candidates if (reranker is not None or mmr_lambda is not None) else n_results)
+                                    n_width=n_candidates if (reranker is not None or mmr_lambda is not None) else n_results,
+                                    pq_candidates=pq_candidates)
         if nprobe is not None:
             from .ivf import check_query_with_nprobe
             ivf = getattr(self, "ivf", None)
@@ -794,6 +836,7 @@ class HipCollection:
                        hybrid_on_device=on_device, world=getattr(self, "world", 1),
                        **({} if nprobe is None else {"nprobe": nprobe, "ivf": self.ivf}),
                        **({} if binary_candidates is None else {"binary_candidates": binary_candidates, "binary": self.binary}),
+                       **({} if pq_candidates is None else {"pq_candidates": pq_candidates, "pq": self.pq}),
                        **({} if boost_weight is None else {"boost_weight": boost_weight, "prior": self._prior(), "max_abs_prior": self._boost_max}))
         s, i, hyb, kws, base = hit.scores, hit.ids, hit.hybrid, hit.keyword, hit.base
         if reranker is not None:
@@ -835,6 +878,8 @@ class HipCollection:
             out["ivf_scanned"] = [int(v) for v in hit.ivf_scanned]
         if hit.binary_count is not None:
             out["binary_count"] = [int(v) for v in hit.binary_count]
+        if hit.pq_count is not None:
+            out["pq_count"] = [int(v) for v in hit.pq_count]
         if base is not None:
             out["base_scores"] = [base[qi][i[qi] >= 0].tolist() for qi in range(q.shape[0])]
         if hit.mmr is not None:

@@ -844,6 +844,57 @@ int32_t arx_binary_candidates_tuned(const uint64_t* codes, int64_t n_rows, int32
                                     const uint64_t* allow, int32_t n_candidates, int32_t* out_cand, int32_t* out_dist,
                                     int64_t* out_count, void* ws, int64_t ws_bytes, int32_t rows_per_block, void* stream);
 
+/* ---- Product-quantised search: 8-bit PQ codes, byte look-up tables, exact candidate lists by table sum (csrc/pq.hip; the host layer
+ * is arxiv_rag_amd/pq.py; the definition is INTEGRATION.md "Product-quantised search") --------------------------------------------
+ * Shapes: dim a multiple of 64 in 64..8192; dsub a power of two in 4..64; M = dim / dsub in 1..256 (the look-up tables must fit in
+ * LDS).  codebooks: device f32 [M, 256, dsub], 16-byte aligned, every value finite (the host layer checks that; the library reads them
+ * as they are).  centre: device f32 [dim] or NULL.  fl32() below is one rounding to f32; no product is fused with a sum.
+ * arx_pq_encode: rows device fp16 [n_rows, dim] (16-byte aligned) -> out_codes device uint8 [n_rows, M] (16-byte aligned).  For row r
+ * and subspace m: v_t = fl32((float)x[m dsub + t] - centre[m dsub + t]) (the exact widened value without a centre); d_j starts from
+ * acc = 0 and takes, t ascending, e = fl32(v_t - c[m][j][t]), acc = fl32(acc + fl32(e e)); the code starts as (best = d_0, code = 0)
+ * and j = 1..255 wins iff d_j < best (strict): ties go to the lowest j, a NaN distance never wins, a row of NaN gets code 0.  One
+ * launch on `stream`, every byte written once with a plain store, no atomics.  n_rows = 0 is legal and launches nothing.
+ * ARX_ERR_ARG before the launch, the message naming the field: dim, dsub or M outside the shapes above; n_rows outside 0..2^31-1; a
+ * null rows, codebooks or out_codes with n_rows > 0; a misaligned pointer. */
+int32_t arx_pq_encode(const void* rows, int64_t n_rows, int32_t dim, int32_t dsub, const float* centre, const float* codebooks,
+                      uint8_t* out_codes, void* stream);
+/* arx_pq_lut: queries device fp16 [n_queries, dim] -> out_lut device uint8 [n_queries, M, 256].  f[m][j] starts from acc = 0 and takes,
+ * t ascending, acc = fl32(acc + fl32((float)q[m dsub + t] c[m][j][t])): the query is NOT centred (<q, centre> is one constant per
+ * query and does not change the order).  lo_m = min_j f[m][j]; span = max_m fl32(max_j f[m][j] - lo_m).  If any f is not finite, or
+ * span is not a finite value > 0, the query's whole table is 0.  Otherwise inv = fl32(255.f / span) and
+ * u[m][j] = (uint8) min(255, rintf(fl32(fl32(f - lo_m) inv))).  One launch, one block per query; n_queries = 0 launches nothing. */
+int32_t arx_pq_lut(const void* queries, int32_t n_queries, int32_t dim, int32_t dsub, const float* codebooks, uint8_t* out_lut,
+                   void* stream);
+/* arx_pq_candidates: s(q, r) = sum over m of lut[q][m][codes[r][m]], an integer <= 65280.  The VISIBLE rows are [0, n_rows), restricted
+ * to the rows whose bit of `allow` is set when it is given.  C(q) is the first min(R, visible) visible rows by (s descending, row
+ * ascending), R = n_candidates: sums are integers, so C(q) is defined exactly, ties to the lower row.
+ *   codes         device uint8 [n_rows, M], row-major, 16-byte aligned (NULL only when n_rows == 0); lut device uint8 [n_queries, M, 256],
+ *                 16-byte aligned
+ *   allow         device uint64 [ceil(n_rows / 64)] or NULL: arx_topk_search_filtered's convention; bits at or beyond n_rows may hold
+ *                 anything
+ *   out_cand      device int32 [n_queries, R]: C(q) in that order, padded with -1.  Rows are local (there is no idx_base)
+ *   out_sum       device int32 [n_queries, R] or NULL: their sums, padded with -1
+ *   out_count     device int64 [n_queries]: |C(q)|
+ *   ws            device scratch of arx_pq_workspace_bytes(n_rows, n_queries, dim, dsub, n_candidates) bytes, 16-byte aligned (-1 for
+ *                 arguments outside the limits, n_queries < 1 among them); at most 64 MiB
+ * Two launches per 256 queries on `stream` (scan: blocks of rows_per_block rows x tile of 8, 4, 2 or 1 queries, chosen from M so that a
+ * tile's tables and key lists take at most 80 KiB of LDS; merge: one block per query over any number of partial lists), no host
+ * synchronisation, integer work only, no global atomics.  A query's outputs depend on its own table, codes and allow; not on the batch,
+ * its order, the tile it lands in, the launch shape or the workspace.  n_rows = 0 is legal (all -1, counts 0; the scan is not
+ * launched) and so is n_queries = 0 (nothing is launched).
+ * ARX_ERR_ARG before anything is launched, the message naming the field: n_candidates outside 1..256; dim, dsub or M outside the
+ * shapes above; n_rows outside 0..2^31-1; n_queries < 0; a null or misaligned pointer; ws_bytes below the figure above.
+ * codes, lut and allow are device data of which every bit pattern is legal: nothing read from them addresses anything out of range.
+ * THE EXACT RESCORE is arx_ivf_search over the candidate lists, composed exactly as for arx_binary_candidates above. */
+int64_t arx_pq_workspace_bytes(int64_t n_rows, int32_t n_queries, int32_t dim, int32_t dsub, int32_t n_candidates);
+int32_t arx_pq_candidates(const uint8_t* codes, int64_t n_rows, int32_t dim, int32_t dsub, const uint8_t* lut, int32_t n_queries,
+                          const uint64_t* allow, int32_t n_candidates, int32_t* out_cand, int32_t* out_sum, int64_t* out_count, void* ws,
+                          int64_t ws_bytes, void* stream);
+/* The same with the scan's launch shape chosen: rows_per_block as for arx_binary_candidates_tuned.  Same bits for every choice. */
+int32_t arx_pq_candidates_tuned(const uint8_t* codes, int64_t n_rows, int32_t dim, int32_t dsub, const uint8_t* lut, int32_t n_queries,
+                                const uint64_t* allow, int32_t n_candidates, int32_t* out_cand, int32_t* out_sum, int64_t* out_count,
+                                void* ws, int64_t ws_bytes, int32_t rows_per_block, void* stream);
+
 /* ---- MMR diversified re-ordering of a query's search candidates (csrc/mmr.hip; the definition is INTEGRATION.md "MMR") -----------
  * arx_gather_rows: out[s] (device fp16 [count, dim]) = shard row ids[s] - idx_base where that row lies in [0, n_rows), all zeros
  * otherwise (id -1, a row another rank owns: the ranks' buffers then add up to the rows, arxiv_rag_amd/mmr.py).  shard device fp16

@@ -2,9 +2,13 @@
 
 A scan block cuts a query's LDS list back to its R best keys whenever the next round of 256 rows could overflow its 1024 slots, and from
 then on appends only keys above the list's threshold.  That path needs more than 1024 rows per block: here 9000 rows at
-rows_per_block = default (2048), 4096 and 8192, compared exactly against `binary.candidates_host`.  `schedule` restates the block's
-bookkeeping (which lists are cut before which round, how many keys a non-zero threshold turns away) so that the tests can assert that
-the runs really contain cut and uncut lists, tiles whose eight lists are not cut together, and rejections."""
+rows_per_block = default (2048), 4096 and 8192, compared exactly against `binary.candidates_host`.  `schedule` (tests/key_list_cases.py,
+shared with the PQ scan's suite) restates the block's bookkeeping (which lists are cut before which round, how many keys a non-zero
+threshold turns away) so that the tests can assert that the runs really contain cut and uncut lists, tiles whose eight lists are not cut
+together, and rejections.
+
+Further down: the one-word load at odd W above 1 (dims 192 and 8128), W = 128 (dim 8192: the whole of the query words' LDS array), and a
+shard of 2^21 + 197 rows whose planted rows put a query's candidates beyond row 2^20, across it, and in the ragged last wave."""
 import numpy as np
 import pytest
 import torch
@@ -12,11 +16,11 @@ import torch
 from arxiv_rag_amd import binary as B
 from arxiv_rag_amd.index import ShardIndex
 from arxiv_rag_amd.where import pack_bitmap
+from tests.key_list_cases import schedule_distances as schedule      # (distance asc, row asc): the restated bookkeeping of a list
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 N, NQ = 9000, 70
-ROUND, CAP = 256, 1024                                          # rows per round of a block, slots of a list (csrc/binary.hip)
 DEFAULT_RPB = 2048                                              # what the library picks for 9000 rows x 9 query tiles
 
 
@@ -52,26 +56,6 @@ def host(w, R, masked):
     if (R, masked) not in w["host"]:
         w["host"][(R, masked)] = B.candidates_host(w["codes"], w["qcodes"], R, w["half"] if masked else None)
     return w["host"][(R, masked)]
-
-
-def schedule(d, visible, lo, hi, R):
-    """One query's list in the block of rows [lo, hi): -> (rounds before which it was cut, keys turned away by a non-zero threshold).
-    Keys order as (distance asc, row asc); the list is cut to its R best before a round when count + 256 > 1024."""
-    keys = d.astype(np.int64) * (1 << 32) + np.arange(d.shape[0], dtype=np.int64)      # smaller is better
-    held, thr, cuts, turned = np.zeros(0, np.int64), None, [], 0
-    for r, a in enumerate(range(lo, hi, ROUND)):
-        if held.shape[0] + ROUND > CAP:
-            held = np.sort(held)[:R]
-            thr = held[R - 1] if held.shape[0] >= R else None
-            cuts.append(r)
-        rows = np.arange(a, min(a + ROUND, hi))
-        k = keys[rows[visible[rows]]]
-        if thr is not None:
-            turned += int((k >= thr).sum())
-            k = k[k < thr]
-        held = np.concatenate([held, k])
-        assert held.shape[0] <= CAP
-    return cuts, turned
 
 
 @pytest.mark.parametrize("masked", [False, True])
@@ -148,3 +132,100 @@ def test_tensors_of_the_wrong_kind_are_value_errors():
                                (x, torch.zeros(65, device=DEV), "centre")):
         with pytest.raises(ValueError, match=part):
             B.pack_device(rows, centre)
+
+
+# ---- odd W above 1, and W = 128 -----------------------------------------------------------------------------------------------------------
+N_W, LINE = 1000, 1 << 20
+N_BIG = 2 * LINE + 64 * 3 + 5                                    # three blocks at rows_per_block = 2^20; the last wave holds 5 rows
+
+
+@pytest.fixture(scope="module")
+def wide():
+    """dim -> random code words of 1000 rows and 70 queries (the scan reads words, whatever packed them), two identical rows and a query
+    equal to them, a half-random bitmap, and the host lists at R = 256 (a shorter list is their prefix); built once, left unchanged"""
+    built = {}
+
+    def get(dim):
+        if dim not in built:
+            W = dim // 64
+            rs = np.random.RandomState(dim)
+            codes = rs.randint(0, 2 ** 63, (N_W, W), dtype=np.int64).view(np.uint64) * np.uint64(2) + rs.randint(0, 2, (N_W, W)).astype(np.uint64)
+            qcodes = codes[rs.randint(0, N_W, NQ)] ^ (rs.randint(0, 2 ** 62, (NQ, W), dtype=np.int64).view(np.uint64)
+                                                      & rs.randint(0, 2 ** 62, (NQ, W), dtype=np.int64).view(np.uint64))
+            codes[700] = codes[10]
+            qcodes[0] = codes[10]
+            half = rs.rand(N_W) < 0.5
+            built[dim] = dict(codes=codes, qcodes=qcodes, half=half, dcodes=dev(codes.view(np.int64), np.int64),
+                              dqcodes=dev(qcodes.view(np.int64), np.int64), dhalf=dev(pack_bitmap(half).view(np.int64), np.int64),
+                              want=B.candidates_host(codes, qcodes, 256), want_half=B.candidates_host(codes, qcodes, 256, half))
+        return built[dim]
+    yield get
+    built.clear()
+
+
+def prefix(full, R):
+    cand, dist, count = full
+    return cand[:, :R], dist[:, :R], np.minimum(count, R)
+
+
+@pytest.mark.parametrize("dim", [192, 8128, 8192])
+def test_odd_word_counts_above_one_and_the_widest_code(wide, dim):
+    """W = 3 and W = 127 take the one-word load (W odd) with a row stride that is no multiple of 16 bytes; W = 128 fills the query
+    words' LDS array.  1000 rows, 70 queries (a full tile and a ragged one), exactly `candidates_host`."""
+    w = wide(dim)
+    assert w["codes"].shape[1] == dim // 64 and (dim // 64) % 2 == (0 if dim == 8192 else 1)
+    for R in (1, 256):
+        for rpb in (None, 64):
+            assert same(B.candidates_device(w["dcodes"], w["dqcodes"], R, rows_per_block=rpb), prefix(w["want"], R)), (dim, R, rpb)
+        assert same(B.candidates_device(w["dcodes"], w["dqcodes"], R, allow=w["dhalf"]), prefix(w["want_half"], R)), (dim, R, "half")
+    cand, dist, _ = w["want"]
+    assert cand[0, :2].tolist() == [10, 700] and dist[0, :2].tolist() == [0, 0]
+    assert len(set(dist[:, 0].tolist())) > 5 and dist[:, 255].min() > 0      # the queries are not all alike, and no list is all ties
+
+
+# ---- beyond 2^20 rows ---------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def big():
+    """2^21 + 197 rows of one random word, 9 queries.  Planted: query 0's 300 nearest rows (distance 1) all lie beyond 2^20, a thousand
+    rows apart; query 1 has 260 rows at distance 0 across 2^20 - 130 ... 2^20 + 129; query 2's best row is the shard's last.  Random
+    words lie at distance 8 or more from a query (a distance below 8 has probability 4e-11 per row, 2^21 rows)."""
+    rs = np.random.RandomState(77)
+    codes = rs.randint(0, 2 ** 63, (N_BIG, 1), dtype=np.int64).view(np.uint64) * np.uint64(2) + rs.randint(0, 2, (N_BIG, 1)).astype(np.uint64)
+    qcodes = rs.randint(0, 2 ** 63, (9, 1), dtype=np.int64).view(np.uint64) * np.uint64(2) + rs.randint(0, 2, (9, 1)).astype(np.uint64)
+    near = LINE + 1000 * np.arange(1, 301) + 3
+    codes[near, 0] = qcodes[0, 0] ^ (np.uint64(1) << (np.arange(300) % 64).astype(np.uint64))
+    codes[LINE - 130:LINE + 130, 0] = qcodes[1, 0]
+    codes[N_BIG - 1, 0] = qcodes[2, 0]
+    hidden = np.ones(N_BIG, bool)
+    hidden[near[:3]] = False; hidden[[LINE - 1, LINE, N_BIG - 1]] = False
+    words = pack_bitmap(hidden).copy()
+    words[-1] |= np.uint64(0xffffff) << np.uint64(40)            # bits beyond the last row: they name no row
+    half = rs.rand(N_BIG) < 0.5
+    w = dict(codes=codes, qcodes=qcodes, near=near, dcodes=dev(codes.view(np.int64), np.int64), dqcodes=dev(qcodes.view(np.int64), np.int64),
+             masks={"none": (None, None), "hidden": (hidden, dev(words.view(np.int64), np.int64)),
+                    "half": (half, dev(pack_bitmap(half).view(np.int64), np.int64))})
+    w["want"] = {name: B.candidates_host(codes, qcodes, 256, m) for name, (m, _) in w["masks"].items()}
+    yield w
+    w.clear()
+    torch.cuda.empty_cache()
+
+
+@pytest.mark.parametrize("mask", ["none", "hidden", "half"])
+def test_rows_beyond_2_20_enter_the_keys_low_word(big, mask):
+    want = big["want"][mask]
+    for R in (1, 256):
+        for rpb in (None, LINE):
+            got = B.candidates_device(big["dcodes"], big["dqcodes"], R, allow=big["masks"][mask][1], rows_per_block=rpb)
+            assert same(got, prefix(want, R)), (mask, R, rpb)
+    cand, dist, count = want
+    assert (count == 256).all()
+    near = big["near"]
+    if mask == "none":
+        assert cand[0].tolist() == near[:256].tolist() and (dist[0] == 1).all()
+        assert cand[1].tolist() == list(range(LINE - 130, LINE + 126)) and (dist[1] == 0).all()
+        assert cand[2, 0] == N_BIG - 1 and dist[2, 0] == 0 and dist[2, 1] >= 8
+    if mask == "hidden":
+        assert cand[0].tolist() == near[3:259].tolist()
+        assert cand[1].tolist() == [r for r in range(LINE - 130, LINE + 130) if r not in (LINE - 1, LINE)][:256]
+        assert cand[2, 0] != N_BIG - 1 and dist[2, 0] >= 8
+    assert sum(int((cand[q] >= LINE).sum()) > 64 for q in range(9)) >= 3

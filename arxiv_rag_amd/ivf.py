@@ -80,9 +80,10 @@ def check_query_with_nprobe(nprobe, *, has_index: bool, n_lists: int = 0, per_qu
 
 
 # ---- the numpy restatement ---------------------------------------------------------------------------------------------------------
-def _visible_rows(order, start, probe_row, n_rows: int) -> np.ndarray:
+def _visible_rows(order, start, probe_row, n_rows: int, max_list_rows=None) -> np.ndarray:
     """The rows one query sees, in list order: the distinct valid lists of `probe_row` in probe order, `start` as `clamp_starts`
-    reads it, `order` entries outside [0, n_rows) dropped."""
+    reads it, each list cut at its first `max_list_rows` entries (None: whole), `order` entries outside [0, n_rows) dropped (after the
+    cut: such an entry keeps its place inside it)."""
     from .topics import clamp_starts
     order = np.asarray(order, dtype=np.int64)
     s = clamp_starts(start, order.shape[0])
@@ -90,30 +91,32 @@ def _visible_rows(order, start, probe_row, n_rows: int) -> np.ndarray:
     for c in np.asarray(probe_row, dtype=np.int64).tolist():
         if 0 <= c < n_lists and c not in seen:
             seen.add(c)
-            rows.append(order[int(s[c]):int(s[c + 1])])
+            end = int(s[c + 1]) if max_list_rows is None else min(int(s[c + 1]), int(s[c]) + int(max_list_rows))
+            rows.append(order[int(s[c]):end])
     rows = np.concatenate(rows) if rows else np.zeros(0, np.int64)
     return rows[(rows >= 0) & (rows < n_rows)]
 
 
-def probe_bitmaps_host(order, start, probes, n_rows: int) -> np.ndarray:
-    """int64 [nq, ceil(n_rows / 64)]: per query the bitmap (`where.pack_bitmap`'s convention) of the rows it sees."""
+def probe_bitmaps_host(order, start, probes, n_rows: int, max_list_rows=None) -> np.ndarray:
+    """int64 [nq, ceil(n_rows / 64)]: per query the bitmap (`where.pack_bitmap`'s convention) of the rows it sees (`max_list_rows`:
+    as `_visible_rows` cuts the lists)."""
     from .where import pack_bitmap
     probes = np.asarray(probes)
     out = np.zeros((probes.shape[0], (n_rows + 63) // 64), np.int64)
     for q in range(probes.shape[0]):
         mask = np.zeros(n_rows, bool)
-        mask[_visible_rows(order, start, probes[q], n_rows)] = True
+        mask[_visible_rows(order, start, probes[q], n_rows, max_list_rows)] = True
         out[q] = pack_bitmap(mask).view(np.int64)
     return out
 
 
-def search_host(X, order, start, probes, Q, k: int, allow=None):
+def search_host(X, order, start, probes, Q, k: int, allow=None, max_list_rows=None):
     """(scores f32 [nq, k], ids int64 [nq, k], scanned int64 [nq]): what `arx_ivf_search` returns with idx_base = 0, bit for bit, from
     `topics.exact_scores_host`.  `X` fp16 [n_rows, dim], `Q` fp16 [nq, dim], `probes` int [nq, nprobe]; `allow`: None, a bool mask
     [n_rows] or bitmap words (int64 / uint64 [ceil(n_rows / 64)]).  `search_many_host` with that one filter for every query."""
     nq = np.asarray(Q).shape[0]
     allows = None if allow is None else np.asarray(allow)[None]
-    return search_many_host(X, order, start, probes, Q, k, allows=allows, filter_of=np.zeros(nq, np.int64))[:3]
+    return search_many_host(X, order, start, probes, Q, k, allows=allows, filter_of=np.zeros(nq, np.int64), max_list_rows=max_list_rows)[:3]
 
 
 def _thresholds(min_score, nq: int) -> np.ndarray:
@@ -122,14 +125,15 @@ def _thresholds(min_score, nq: int) -> np.ndarray:
     return thresholds(min_score, nq, each="entry")
 
 
-def search_many_host(X, order, start, probes, Q, k: int, allows=None, filter_of=None, min_score=None):
+def search_many_host(X, order, start, probes, Q, k: int, allows=None, filter_of=None, min_score=None, max_list_rows=None):
     """(scores f32 [nq, k], ids int64 [nq, k], scanned int64 [nq], hits int64 [nq]): what `arx_ivf_search_multi` returns with
     idx_base = 0, bit for bit.  `allows`: None (no filter; `filter_of` is ignored), bool masks [F, n_rows] or bitmap words (int64 /
     uint64 [F, ceil(n_rows / 64)]); `filter_of` int [nq]: query q sees the rows of `search_host` under `allows[filter_of[q]]`, and no
     row when `filter_of[q]` lies outside [0, F).  `scanned` counts the visible rows.  `min_score`: None, a float or one per query; a
     visible row qualifies when its f32 score `>=` the query's f32 threshold (a NaN on either side: not), and with None every visible
     row qualifies.  `hits` counts the qualifying rows (with None: `hits == scanned`); the list is their best k by (score desc, row
-    asc), `lexsort`ed from `topics.exact_scores_host`."""
+    asc), `lexsort`ed from `topics.exact_scores_host`.  `max_list_rows`: None, or the entries a list is read up to (the library's
+    argument of that name): `scanned` and `hits` count rows inside the cut alone."""
     from .mutation import unpack_rows
     from .topics import exact_scores_host
     X, Q, probes = np.asarray(X), np.asarray(Q), np.asarray(probes)
@@ -146,7 +150,7 @@ def search_many_host(X, order, start, probes, Q, k: int, allows=None, filter_of=
     ids = np.full((nq, k), -1, np.int64)
     scanned, hits = np.zeros(nq, np.int64), np.zeros(nq, np.int64)
     for q in range(nq):
-        rows = _visible_rows(order, start, probes[q], n_rows)
+        rows = _visible_rows(order, start, probes[q], n_rows, max_list_rows)
         if masks is not None:
             f = int(filter_of[q])
             rows = rows[masks[f][rows]] if 0 <= f < masks.shape[0] else rows[:0]

@@ -84,6 +84,54 @@ def test_probe_bitmaps_host_and_the_clamps():
     assert none[2].tolist() == [0] and (none[1] == -1).all() and np.isneginf(none[0]).all()
 
 
+def test_max_list_rows_cuts_every_list_at_its_first_entries():
+    """`max_list_rows` (the library's argument of that name) in the restatement: the answer is that of the lists rebuilt from the first
+    `cut` entries of each, without the parameter; None and a cut at the longest list change nothing; a cut of 0 leaves nothing; a bad
+    `order` entry keeps its place inside the cut (it is dropped after the cut, and no later entry moves up)."""
+    X, Q, labels, order, start, probes = _world()
+    n, sizes = X.shape[0], np.diff(start)
+    mask = np.random.RandomState(4).rand(n) < 0.6
+    fo = np.arange(Q.shape[0]) % 3 - 1                                    # -1 (no row), 0, 1
+    kw = dict(allows=np.stack([mask, ~mask]), filter_of=fo, min_score=0.0)
+    whole = I.search_many_host(X, order, start, probes, Q, 10, **kw)
+    for cut in (None, int(sizes.max()), n):
+        assert all(np.array_equal(a, b) for a, b in zip(I.search_many_host(X, order, start, probes, Q, 10, max_list_rows=cut, **kw), whole))
+    assert 1 < 7 < sizes.min() and sizes.max() > 40
+    for cut in (1, 7, 40, int(sizes.max()) - 1):
+        kept = np.minimum(sizes, cut)
+        cut_order = np.concatenate([order[start[c]:start[c] + kept[c]] for c in range(9)])
+        cut_start = np.concatenate([[0], np.cumsum(kept)])
+        got = I.search_many_host(X, order, start, probes, Q, 10, max_list_rows=cut, **kw)
+        want = I.search_many_host(X, cut_order, cut_start, probes, Q, 10, **kw)
+        assert all(np.array_equal(a, b) for a, b in zip(got, want)), cut
+        assert (got[3] <= got[2]).all() and (cut > 7 or got[2].sum() < whole[2].sum() // 4) and (got[2][fo < 0] == 0).all()
+        one = I.search_host(X, order, start, probes, Q, 10, allow=mask, max_list_rows=cut)
+        assert all(np.array_equal(a, b) for a, b in zip(one, I.search_host(X, cut_order, cut_start, probes, Q, 10, allow=mask)))
+        maps = I.probe_bitmaps_host(order, start, probes, n, max_list_rows=cut)
+        assert np.array_equal(maps, I.probe_bitmaps_host(cut_order, cut_start, probes, n))
+        plain = I.search_host(X, order, start, probes, Q, 10, max_list_rows=cut)
+        assert plain[2].tolist() == [int(unpack_rows(m, n).sum()) for m in maps]
+    none = I.search_many_host(X, order, start, probes, Q, 10, max_list_rows=0, **kw)
+    assert (none[2] == 0).all() and (none[3] == 0).all() and (none[1] == -1).all() and np.isneginf(none[0]).all()
+    assert not I.probe_bitmaps_host(order, start, probes, n, max_list_rows=0).any()
+    # a bad entry at place 2 of list 4, a cut of 3: places 0 and 1 are seen, the bad entry takes the third, place 3 stays outside
+    bad = order.copy()
+    a = int(start[4])
+    for value in (-5, n + 3):
+        bad[a + 2] = value
+        s, i, scanned = I.search_host(X, bad, start, np.array([[4]]), Q[:1], 10, max_list_rows=3)
+        assert scanned.tolist() == [2] and sorted(i[0][i[0] >= 0].tolist()) == sorted(order[a:a + 2].tolist())
+        assert I._visible_rows(bad, start, [4], n, 3).tolist() == order[a:a + 2].tolist()
+        assert I._visible_rows(bad, start, [4], n, 4).tolist() == order[[a, a + 1, a + 3]].tolist()
+        assert unpack_rows(I.probe_bitmaps_host(bad, start, np.array([[4, 4]]), n, max_list_rows=3)[0], n).sum() == 2
+    # ... and a cut meets clamped starts: the cut counts from the clamped start of the list
+    bad_start = start.copy()
+    bad_start[3], bad_start[5] = -4, 10                                    # lists 2 and 4 become empty, 3 and 5 grow (clamp_starts)
+    s_ = T.clamp_starts(bad_start, order.shape[0])
+    assert s_[3] == s_[2] and s_[5] == s_[4] and s_[4] - s_[3] > sizes[3]
+    assert I._visible_rows(order, bad_start, [3, 2, 5], n, 6).tolist() == np.concatenate([order[s_[3]:s_[3] + 6], order[s_[5]:s_[5] + 6]]).tolist()
+
+
 def test_python_side_refusals():
     for k in (0, 33, 2.0, True):
         with pytest.raises(ValueError, match="k="):

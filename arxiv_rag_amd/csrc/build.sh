@@ -14,7 +14,7 @@ pids=()
 # cluster.hip computes topics.finish_host's sum of squares bit for bit, and is compiled the same way too;
 # boosted.hip computes boost.boosted_host's rounded product and rounded sum bit for bit, and is compiled the same way;
 # pq.hip computes pq.encode_host's and pq.lut_host's sums operation by operation, and is compiled the same way)
-for f in runtime encoder search bm25 filter filter_multi prefix grouped range textscan where_eval mmr fuse bm25_build compact facet cluster cluster_assign boosted binary pq ivf; do
+for f in runtime encoder search bm25 filter filter_multi prefix grouped range textscan where_eval mmr fuse bm25_build compact facet cluster cluster_assign boosted binary pq graph ivf; do
   PER_FILE=""; { [ $f = fuse ] || [ $f = bm25_build ] || [ $f = cluster ] || [ $f = boosted ] || [ $f = pq ]; } && PER_FILE="-ffp-contract=off"
   ( hipcc $FLAGS $PER_FILE -Rpass-analysis=kernel-resource-usage -c $f.hip -o $BLD/$f.o ${ARX_HIPCC_EXTRA} 2> $BLD/$f.resources.txt \
       || { grep -v "kernel-resource-usage" $BLD/$f.resources.txt >&2; exit 1; } ) &
@@ -24,5 +24,5 @@ done
 g++ -O3 -std=c++17 -fPIC -pthread -c wordpiece.cpp -o $BLD/wordpiece.o &
 pids+=($!)
 for p in "${pids[@]}"; do wait $p || exit 1; done
-hipcc --offload-arch=gfx950 -shared -fPIC -pthread -o $OUT $BLD/runtime.o $BLD/encoder.o $BLD/search.o $BLD/bm25.o $BLD/filter.o $BLD/filter_multi.o $BLD/prefix.o $BLD/grouped.o $BLD/range.o $BLD/textscan.o $BLD/where_eval.o $BLD/mmr.o $BLD/fuse.o $BLD/bm25_build.o $BLD/compact.o $BLD/facet.o $BLD/cluster.o $BLD/cluster_assign.o $BLD/ivf.o $BLD/binary.o $BLD/pq.o $BLD/boosted.o $BLD/wordpiece.o
+hipcc --offload-arch=gfx950 -shared -fPIC -pthread -o $OUT $BLD/runtime.o $BLD/encoder.o $BLD/search.o $BLD/bm25.o $BLD/filter.o $BLD/filter_multi.o $BLD/prefix.o $BLD/grouped.o $BLD/range.o $BLD/textscan.o $BLD/where_eval.o $BLD/mmr.o $BLD/fuse.o $BLD/bm25_build.o $BLD/compact.o $BLD/facet.o $BLD/cluster.o $BLD/cluster_assign.o $BLD/ivf.o $BLD/binary.o $BLD/pq.o $BLD/boosted.o $BLD/graph.o $BLD/wordpiece.o
 echo "built $(realpath $OUT)"

@@ -681,7 +681,8 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
                    nprobe: Optional[int] = None, ivf_lists: Optional[int] = None, ivf_iters: int = 10, ivf_seed: int = 0,
                    binary_candidates: Optional[int] = None, binary_centre: Optional[str] = "mean", boost_spec: Optional[Dict] = None,
                    boost_weight: Optional[float] = None, pq_candidates: Optional[int] = None, pq_dsub: int = 8,
-                   pq_centre: Optional[str] = "mean") -> List[Dict]:
+                   pq_centre: Optional[str] = "mean", graph_ef: Optional[int] = None, graph_degree: int = 32,
+                   graph_entries: int = 8) -> List[Dict]:
     """Brute-force cosine top-k (config.yaml:63-64 `top_k: 10`) over the rank's fp16 rows in HBM; with
     torchrun each rank holds the contiguous row shard it encoded and the partial top-k lists are
     all-gathered over RCCL and merged.  `shard` is the `ShardSink` the encode step filled: rows [lo, hi) are already where they
@@ -766,7 +767,14 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
     first `pq_candidates` (at most 256, at least the width the search returns) visible rows by the sum of its byte tables over the
     codes are rescored exactly, `where` (one dict), `where_document` and `keep_mask` applied as without it; every entry of the
     results then carries `pq_count`, the candidates rescored.  Composes with `reranker` and `mmr_lambda`.  Not together with `nprobe`,
-    `binary_candidates`, `hybrid_alpha`, `group_by_paper`, `min_score`, `boost_weight`, a per-query `where` list or more than one rank."""
+    `binary_candidates`, `hybrid_alpha`, `group_by_paper`, `min_score`, `boost_weight`, a per-query `where` list or more than one rank.
+    `graph_ef` (None = nothing changes): the graph search (INTEGRATION.md "Graph search").  A `graph.GraphIndex` of degree
+    `graph_degree` is built over the shard (exact k-NN lists, about sqrt(rows) entry lists) and every query walks it with a beam of
+    `graph_ef` rows (at most 512, at least the width the search returns) from the medoids of its `graph_entries` nearest entry
+    centroids, `where` (one dict), `where_document` and `keep_mask` restricting what comes back as without it; every entry of the
+    results then carries `graph_scored`, the rows scored.  Composes with `reranker` and `mmr_lambda`.  Not together with `nprobe`,
+    `binary_candidates`, `pq_candidates`, `hybrid_alpha`, `group_by_paper`, `min_score`, `boost_weight`, a per-query `where` list or
+    more than one rank."""
     from .retrieval import RowFilters, check_hybrid_on_device, check_shared_query, retrieve
     if keyword_build_on_device and hybrid_alpha is None:
         raise ValueError("keyword_build_on_device needs hybrid_alpha: it chooses where the BM25 keyword index is built")
@@ -791,6 +799,14 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
                                n_width=n_cand_of(reranker, rerank_top_k, mmr_lambda, mmr_fetch_k) if (reranker is not None or mmr_lambda is not None) else top_k,
                                n_queries=len(queries), pq_candidates=pq_candidates)
         prior_host = prior_from_metadata([c.get("metadata") or {} for c in chunks], boost_spec)      # (a bad spec or value: refused here)
+    if graph_ef is not None:
+        from .graph import check_build_args as check_graph_build, check_query_with_graph
+        n_entry_lists = check_graph_build(int(shard.rows.shape[0]), int(shard.rows.shape[1]), graph_degree, None, 10)
+        check_query_with_graph(graph_ef, has_index=True, n_entries=graph_entries, n_entry_lists=n_entry_lists, degree=int(graph_degree),
+                               per_query_filters=isinstance(where, (list, tuple)), hybrid_alpha=hybrid_alpha, group_by=group_by_paper,
+                               min_score=min_score, boost_weight=boost_weight, nprobe=nprobe if nprobe is not None else ivf_lists,
+                               binary_candidates=binary_candidates, pq_candidates=pq_candidates, world=int(os.environ.get("WORLD_SIZE", "1")),
+                               n_width=n_cand_of(reranker, rerank_top_k, mmr_lambda, mmr_fetch_k) if (reranker is not None or mmr_lambda is not None) else top_k)
     if pq_candidates is not None:
         from .pq import check_dsub, check_query_with_pq
         if pq_centre not in (None, "none", "mean"):
@@ -844,7 +860,7 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
     # int8 pre-filter (same exact answers; +50 % shard memory, one quantisation pass): 1.5-1.7x the queries per second on small batches;
     # a filtered, a grouped and a range search run on the fp16 rows
     masked = (where is not None or keep_mask is not None or where_document is not None or group_by_paper or min_score is not None or nprobe is not None or binary_candidates is not None
-              or boost_weight is not None or pq_candidates is not None
+              or boost_weight is not None or pq_candidates is not None or graph_ef is not None
               or (hybrid_on_device and n_cand_of(reranker, rerank_top_k, mmr_lambda, mmr_fetch_k) > HYBRID_CANDIDATES))
     index = ShardIndex(shard.rows, idx_base=shard.lo, prefilter="int8" if (dim % 128 == 0 and dim <= 1024 and n_rows > 0 and not masked) else None,
                        adaptive=True)
@@ -874,6 +890,8 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
                    **({} if nprobe is None else {"nprobe": int(nprobe), "ivf": build_ivf_index(index, ivf_lists, ivf_iters, ivf_seed)}),
                    **({} if binary_candidates is None else {"binary_candidates": int(binary_candidates), "binary": build_binary_index(index, binary_centre)}),
                    **({} if pq_candidates is None else {"pq_candidates": int(pq_candidates), "pq": build_pq_index(index, pq_dsub, pq_centre)}),
+                   **({} if graph_ef is None else {"graph_ef": int(graph_ef), "graph": build_graph_index(index, graph_degree),
+                                                   "graph_entries": int(graph_entries)}),
                    **({} if boost_weight is None else {"boost_weight": float(boost_weight), "prior": torch.from_numpy(prior_host).to(dev)}))
     base_of = (lambda qi, p: {}) if hit.base is None else (lambda qi, p: {"base_score": float(hit.base[qi, p])})
     s, i, grp, truncated, mmr_val, hyb, kws = hit.scores, hit.ids, hit.groups, hit.truncated, hit.mmr, hit.hybrid, hit.keyword
@@ -898,6 +916,8 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
         scanned_of = lambda qi: {"binary_count": int(hit.binary_count[qi])}      # noqa: E731
     if hit.pq_count is not None:
         scanned_of = lambda qi: {"pq_count": int(hit.pq_count[qi])}              # noqa: E731
+    if hit.graph_scored is not None:
+        scanned_of = lambda qi: {"graph_scored": int(hit.graph_scored[qi])}      # noqa: E731
 
     def hybrid_fields(qi, p):                                # (null, not NaN, in the JSON file)
         if hyb is None:
@@ -961,6 +981,16 @@ def build_pq_index(index, dsub: int = 8, centre: Optional[str] = "mean"):
     n, m = (int(v) for v in pi.codes.shape)
     print(f"PQ index: {n} rows x {m} code bytes (dsub {int(dsub)}, {n * m} bytes), centre {'none' if pi.centre is None else 'mean'}")
     return pi
+
+
+def build_graph_index(index, degree: int = 32):
+    """`--graph-ef`: the `graph.GraphIndex` of the search step's shard (exact k-NN lists), with its summary printed."""
+    from .graph import GraphIndex
+    g = GraphIndex.build(index, degree=int(degree))
+    info = g.summary()
+    print(f"Graph index: {info['rows']} rows x degree {info['degree']}, {info['edges']} edges, {info['entry_lists']} entry lists, "
+          f"{info['seconds']:.2f} s")
+    return g
 
 
 # --------------------------------------------------------------------------------------------- main
@@ -1076,6 +1106,15 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--pq-centre", choices=("mean", "none"), default="mean",
                    help="What the rows are centred on before --pq-candidates encodes them: the column mean of the chunks' rows, or "
                         "zero (default: mean)")
+    p.add_argument("--graph-ef", type=int, default=None,
+                   help="Graph search: build a k-NN graph over the chunks and answer every query by a beam search of this width over "
+                        "it, every score exact (at most 512, at least the search's width; default: off; needs --queries; one GPU "
+                        "rank only; not with --nprobe, --binary-candidates, --pq-candidates, --hybrid-alpha, --group-by-paper, "
+                        "--min-score, --boost-key or --where-file)")
+    p.add_argument("--graph-degree", type=int, default=32,
+                   help="Neighbours per chunk of --graph-ef's graph: a multiple of 8 in 8..32 (default: 32)")
+    p.add_argument("--graph-entries", type=int, default=8,
+                   help="Entry points per query of --graph-ef: the medoids of this many nearest entry centroids, 1..32 (default: 8)")
     p.add_argument("--boost-key", type=str, default=None,
                    help="Boosted search: rank by cosine + --boost-weight * prior, the prior being this metadata key's numeric value "
                         "(missing: 0), or its exponential decay with --boost-decay-origin / --boost-half-life (default: off; needs "
@@ -1302,6 +1341,45 @@ def check_pq_args(args) -> Optional[str]:
         args, "--pq-candidates", r, "PQ codes", "the code scan",
         also=(("--binary-candidates", getattr(args, "binary_candidates", None) is not None, "both choose which rows get scored"),
               ("--boost-key", getattr(args, "boost_key", None) is not None, "the boosted search reads every row")))
+
+
+def check_graph_args(args) -> Optional[str]:
+    """-> an error message for an unusable --graph-ef / --graph-degree / --graph-entries, else None.  (The other flags are read with
+    getattr: absent = off.)"""
+    ef = getattr(args, "graph_ef", None)
+    if ef is None:
+        return None
+    if not (1 <= ef <= 512):
+        return f"--graph-ef {ef} must be in [1, 512]"
+    degree, entries = getattr(args, "graph_degree", 32), getattr(args, "graph_entries", 8)
+    if degree not in (8, 16, 24, 32):
+        return f"--graph-degree {degree} must be a multiple of 8 in [8, 32]"
+    if not (1 <= entries <= 32):
+        return f"--graph-entries {entries} must be in [1, 32]"
+    if not getattr(args, "queries", None):
+        return "--graph-ef needs --queries: it is a mode of the search step"
+    for other, on, why in (
+            ("--nprobe / --ivf-lists", getattr(args, "nprobe", None) is not None or getattr(args, "ivf_lists", None) is not None,
+             "both choose which rows get scored"),
+            ("--binary-candidates", getattr(args, "binary_candidates", None) is not None, "both choose which rows get scored"),
+            ("--pq-candidates", getattr(args, "pq_candidates", None) is not None, "both choose which rows get scored"),
+            ("--boost-key", getattr(args, "boost_key", None) is not None, "the boosted search reads every row"),
+            ("--hybrid-alpha", getattr(args, "hybrid_alpha", None) is not None, "the BM25 keyword search has no graph"),
+            ("--group-by-paper", getattr(args, "group_by_paper", False), "the grouped search reads every row"),
+            ("--min-score", getattr(args, "min_score", None) is not None, "the range search reads every row"),
+            ("--where-file", getattr(args, "where_filters", None) is not None, "the graph search takes one bitmap per call")):
+        if on:
+            return f"--graph-ef cannot be combined with {other}: {why}"
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        return "--graph-ef needs a single GPU rank: more than one rank is out of scope"
+    width = getattr(args, "top_k", 10)
+    if getattr(args, "rerank_model", None):
+        width = getattr(args, "rerank_top_k", 32)
+    elif getattr(args, "mmr_lambda", None) is not None:
+        width = getattr(args, "mmr_fetch_k", 32)
+    if ef < width:
+        return f"--graph-ef {ef} is below the {width} rows the search returns per query"
+    return None
 
 
 def boost_spec_of(args) -> Optional[Dict]:
@@ -1570,7 +1648,7 @@ def main(argv: Optional[Sequence[str]] = None, model_factory: Optional[Callable]
     err = (check_rerank_args(args) or check_hybrid_args(args) or check_hybrid_filters_args(args) or check_hybrid_device_args(args) or check_keyword_build_args(args) or check_where_args(args) or check_where_file_args(args) or check_where_device_args(args)
            or check_where_document_args(args)
            or check_mmr_args(args) or check_dedup_args(args) or check_group_args(args) or check_range_args(args) or check_facets_args(args) or check_topics_args(args) or check_ivf_args(args)
-           or check_binary_args(args) or check_pq_args(args) or check_boost_args(args))
+           or check_binary_args(args) or check_pq_args(args) or check_graph_args(args) or check_boost_args(args))
     if err:
         print(f"Error: {err}")
         return 2
@@ -1680,6 +1758,8 @@ def main(argv: Optional[Sequence[str]] = None, model_factory: Optional[Callable]
                                   if args.binary_candidates is not None else {}),
                                **({"pq_candidates": args.pq_candidates, "pq_dsub": args.pq_dsub, "pq_centre": args.pq_centre}
                                   if args.pq_candidates is not None else {}),
+                               **({"graph_ef": args.graph_ef, "graph_degree": args.graph_degree, "graph_entries": args.graph_entries}
+                                  if args.graph_ef is not None else {}),
                                **({"boost_spec": boost_spec_of(args), "boost_weight": args.boost_weight} if args.boost_key is not None else {}))
                 if args.facet_keys is not None:
                     facet_counts(chunks, _model.encoder.device, args.facet_keys, args.facets_top,

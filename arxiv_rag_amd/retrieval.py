@@ -201,6 +201,7 @@ class Retrieved:
     ivf_hits: Optional[np.ndarray] = None        # nprobe with per-query filters or min_score: int64 [Q], the rows at or above the threshold
     binary_count: Optional[np.ndarray] = None    # binary_candidates: int64 [Q], the Hamming candidates rescored for every query
     pq_count: Optional[np.ndarray] = None        # pq_candidates: int64 [Q], the PQ candidates rescored for every query
+    graph_scored: Optional[np.ndarray] = None    # graph_ef: int64 [Q], the rows the graph walk scored for every query
     base: Optional[np.ndarray] = None            # boost_weight: the cosine of every returned row (`scores` holds the boosted values)
 
 
@@ -236,7 +237,8 @@ def retrieve(index, q, filters: RowFilters, n_results: int, *, n_candidates: int
              hybrid_alpha: Optional[float] = None, keyword=None, query_texts: Optional[Sequence[str]] = None,
              hybrid_on_device: bool = False, world: int = 1, nprobe: Optional[int] = None, ivf=None,
              binary_candidates: Optional[int] = None, binary=None, boost_weight=None, prior=None,
-             max_abs_prior: Optional[float] = None, pq_candidates: Optional[int] = None, pq=None) -> Retrieved:
+             max_abs_prior: Optional[float] = None, pq_candidates: Optional[int] = None, pq=None,
+             graph_ef: Optional[int] = None, graph=None, graph_entries: int = 8) -> Retrieved:
     """One search of the fp16 device queries `q` over `index` (a `ShardIndex`), in the mode the arguments name, every refusal behind it.
     The width: a range search (`min_score`) returns up to `n_candidates` rows with `reranked` and `n_results` without, a grouped search
     `n_results` groups, every other search `n_candidates` rows when something picks among them afterwards (`reranked`, `mmr_lambda`,
@@ -277,12 +279,24 @@ def retrieve(index, q, filters: RowFilters, n_results: int, *, n_candidates: int
     row), under the one bitmap of `where`, `where_document` and the keep-mask, rescored exactly; `pq_count` holds the candidates
     rescored.  MMR and a reranker consume the list as any other.  ValueError (`pq.check_query_with_pq`): `nprobe`,
     `binary_candidates`, `hybrid_alpha`, `grouped`, `min_score`, `boost_weight`, per-query filter lists, `world > 1`, no `pq`,
-    `pq_candidates` outside [width, 256], a width above 32."""
+    `pq_candidates` outside [width, 256], a width above 32.
+    `graph_ef` (None = nothing changes) with `graph` (a `graph.GraphIndex` over `index`) and `graph_entries`: the graph search
+    (INTEGRATION.md "Graph search"): a beam search of width `graph_ef` over the k-NN graph from the medoids of every query's
+    `graph_entries` nearest entry centroids; the one bitmap of `where`, `where_document` and the keep-mask restricts what comes back,
+    not where the walk goes; `graph_scored` holds the rows scored.  MMR and a reranker consume the list as any other.  ValueError
+    (`graph.check_query_with_graph`): `nprobe`, `binary_candidates`, `pq_candidates`, `hybrid_alpha`, `grouped`, `min_score`,
+    `boost_weight`, per-query filter lists, `world > 1`, no `graph` or a stale one, `graph_ef` outside [width, 512], a width above 32."""
     import torch
     from .filter_sets import is_per_query
     nq = q.shape[0]
     k = n_candidates if (reranked or hybrid_alpha is not None or mmr_lambda is not None) else n_results
     per_query = is_per_query(where) or is_per_query(where_document)
+    if graph_ef is not None:
+        from .graph import check_query_with_graph
+        check_query_with_graph(graph_ef, has_index=graph is not None, stale=getattr(graph, "stale", False), n_entries=graph_entries,
+                               n_entry_lists=getattr(graph, "n_entry_lists", 0), degree=getattr(graph, "degree", 32), per_query_filters=per_query,
+                               hybrid_alpha=hybrid_alpha, group_by=grouped, min_score=min_score, boost_weight=boost_weight, nprobe=nprobe,
+                               binary_candidates=binary_candidates, pq_candidates=pq_candidates, world=world, n_width=k)
     if pq_candidates is not None:
         from .pq import check_query_with_pq
         check_query_with_pq(pq_candidates, has_index=pq is not None, per_query_filters=per_query, hybrid_alpha=hybrid_alpha, group_by=grouped,
@@ -309,7 +323,10 @@ def retrieve(index, q, filters: RowFilters, n_results: int, *, n_candidates: int
     if on_device:
         check_hybrid_on_device(n_candidates, per_query_filters=per_query, world=world)
     long_lists = on_device and n_candidates > HYBRID_HOST_CANDIDATES
-    if nprobe is not None:
+    if graph_ef is not None:
+        s, i, scored = graph.search(q, k, int(graph_ef), allow=filters.allow_of(where, where_document)[0], n_entries=int(graph_entries))
+        out.graph_scored = scored.cpu().numpy()
+    elif nprobe is not None:
         s, i = _retrieve_ivf(ivf, q, k, int(nprobe), filters, where, where_document, per_query, min_score, out)
     elif binary_candidates is not None:
         s, i, count = binary.search(q, k, int(binary_candidates), allow=filters.allow_of(where, where_document)[0])

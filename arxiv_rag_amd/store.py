@@ -328,6 +328,8 @@ class HipCollection:
             self.binary.append(self._buf[n:n + m], index=self.index)
         if getattr(self, "pq", None) is not None:                # the new rows encoded with the kept codebooks and centre
             self.pq.append(self._buf[n:n + m], index=self.index)
+        if getattr(self, "graph", None) is not None:             # the new rows have no edges: the graph is stale until build_graph runs again
+            self.graph.stale = True
         if self._deleted is not None:
             self._deleted = np.concatenate([self._deleted, np.zeros(m, bool)])
         if self.dedup_threshold is not None:
@@ -431,6 +433,8 @@ class HipCollection:
             self.binary.compact(keep_words, word_rank, count, index=self.index)
         if getattr(self, "pq", None) is not None:                # the PQ codes move as the rows moved: dim / dsub-byte rows
             self.pq.compact(keep_words, word_rank, count, index=self.index)
+        if getattr(self, "graph", None) is not None:             # the rows moved under the edges: stale until build_graph runs again
+            self.graph.stale = True
         return old_to_new(keep)
 
     def _prior(self):
@@ -526,6 +530,25 @@ class HipCollection:
         n, m = (int(v) for v in self.pq.codes.shape)
         return {"rows": n, "dsub": int(dsub), "bytes_per_row": m, "code_bytes": n * m,
                 "centre": "mean" if isinstance(kind, str) else ("none" if kind is None else "given"), "trained": codebooks is None}
+
+    def build_graph(self, degree: int = 32, n_entry_lists: Optional[int] = None, iters: int = 10, seed: int = 0, nprobe: Optional[int] = None) -> Dict:
+        """Build the k-NN graph `query(graph_ef=...)` walks (INTEGRATION.md "Graph search"; `graph.GraphIndex.build`) over this
+        collection's rows (tombstoned ones included: the keep-bitmap hides them at query time and they stay bridges of the walk).
+        `nprobe` (needs `build_ivf` first): the k-NN lists come from the IVF search with that many probes, an approximate build.
+        Again replaces the graph.  `delete` needs nothing; `add` and `compact` make the graph stale, and `query(graph_ef=...)` then
+        raises until `build_graph` has run again (inserting rows into a built graph is out of scope).  -> {rows, degree, edges,
+        entry_lists, approximate, seconds}.  ValueError before any launch: `world > 1`, an empty collection, `nprobe` without
+        `build_ivf`, the refusals of `graph.check_build_args`."""
+        from .graph import GraphIndex, check_build_args
+        if getattr(self, "world", 1) > 1:
+            raise ValueError("build_graph needs world == 1: more than one rank is out of scope")
+        ivf = getattr(self, "ivf", None) if nprobe is not None else None
+        if nprobe is not None and ivf is None:
+            raise ValueError("build_graph(nprobe=...) needs an IVF index: call build_ivf(n_lists) first")
+        check_build_args(self.hi - self.lo, self.dim, degree, ivf.n_lists if ivf is not None and n_entry_lists is None else n_entry_lists, iters,
+                         nprobe=nprobe, has_ivf=ivf is not None)
+        self.graph = GraphIndex.build(self.index, degree=degree, n_entry_lists=n_entry_lists, iters=iters, seed=seed, ivf=ivf, nprobe=nprobe)
+        return self.graph.summary()
 
     def get(self, ids: Sequence) -> Dict:
         """-> {ids, metadatas, documents} of the rows with these `chunk_id`s, in the order asked, from the host lists (the shape of one
@@ -665,7 +688,7 @@ class HipCollection:
               n_candidates: int = 32, hybrid_alpha: Optional[float] = None, where=None, where_document=None,
               mmr_lambda: Optional[float] = None, group_by=None, chunks_per_group: int = 1, min_score=None,
               nprobe: Optional[int] = None, binary_candidates: Optional[int] = None, boost_weight=None,
-              pq_candidates: Optional[int] = None) -> Dict:
+              pq_candidates: Optional[int] = None, graph_ef: Optional[int] = None, graph_entries: int = 8) -> Dict:
         """Between the encoded queries and the rerank step this is the pipeline `search_queries` runs too: `retrieval.RowFilters` builds
         the row bitmaps, `retrieval.retrieve` searches, picks by MMR and fuses.
         `reranker` (a `rerank.HipCrossEncoder`; needs `query_texts`): the search fetches `n_candidates` (<= 32) rows per query,
@@ -755,13 +778,32 @@ class HipCollection:
         `pq_count` list holds the candidates rescored per query.  Composes with a single `where`, `where_document` and the dedup and
         tombstone keep-bitmap (one bitmap per call), and with `reranker` and `mmr_lambda` (`n_candidates <= 32`).  ValueError, naming
         the part: `nprobe`, `binary_candidates`, `hybrid_alpha`, `group_by`, `min_score`, `boost_weight`, per-query filter lists,
-        `world > 1`, or a collection without `build_pq`."""
+        `world > 1`, or a collection without `build_pq`.
+        `graph_ef` (an integer L in [width, 512], the width as for `binary_candidates`; None = nothing changes; needs `build_graph`
+        first) with `graph_entries` (E in [1, 32], at most the graph's entry lists): the graph search (INTEGRATION.md "Graph
+        search").  Every query walks the k-NN graph from the medoids of its E nearest entry centroids with a beam of L rows
+        (`arx_graph_search`), scoring a few thousand rows whatever the collection's size: which rows get visited is the only
+        approximation, the scores and the order are the exact search's, and an added `graph_scored` list holds the rows scored per
+        query.  Composes with a single `where`, `where_document` and the dedup and tombstone keep-bitmap (one bitmap per call; it
+        restricts what comes back, hidden rows stay bridges of the walk), and with `reranker` and `mmr_lambda`
+        (`n_candidates <= 32`).  ValueError, naming the part: `nprobe`, `binary_candidates`, `pq_candidates`, `hybrid_alpha`,
+        `group_by`, `min_score`, `boost_weight`, per-query filter lists, `world > 1`, a collection without `build_graph`, or one
+        whose graph is stale after `add` or `compact`."""
         import torch
         from .filter_sets import is_per_query
         from .grouping import check_grouped_query
         from .ranging import RERANK_BATCH, check_range_query
         from .retrieval import check_hybrid_on_device, check_shared_query, retrieve
         per_query = is_per_query(where) or is_per_query(where_document)
+        if graph_ef is not None:
+            from .graph import check_query_with_graph
+            graph = getattr(self, "graph", None)
+            check_query_with_graph(graph_ef, has_index=graph is not None, stale=getattr(graph, "stale", False), n_entries=graph_entries,
+                                   n_entry_lists=getattr(graph, "n_entry_lists", 0), degree=getattr(graph, "degree", 32),
+                                   per_query_filters=per_query, hybrid_alpha=hybrid_alpha, group_by=group_by, min_score=min_score,
+                                   boost_weight=boost_weight, nprobe=nprobe, binary_candidates=binary_candidates, pq_candidates=pq_candidates,
+                                   world=getattr(self, "world", 1),
+                                   n_width=n_candidates if (reranker is not None or mmr_lambda is not None) else n_results)
         if pq_candidates is not None:
             from .pq import check_query_with_pq
             check_query_with_pq(pq_candidates, has_index=getattr(self, "pq", None) is not None, per_query_filters=per_query,
@@ -837,6 +879,7 @@ class HipCollection:
                        **({} if nprobe is None else {"nprobe": nprobe, "ivf": self.ivf}),
                        **({} if binary_candidates is None else {"binary_candidates": binary_candidates, "binary": self.binary}),
                        **({} if pq_candidates is None else {"pq_candidates": pq_candidates, "pq": self.pq}),
+                       **({} if graph_ef is None else {"graph_ef": graph_ef, "graph": self.graph, "graph_entries": graph_entries}),
                        **({} if boost_weight is None else {"boost_weight": boost_weight, "prior": self._prior(), "max_abs_prior": self._boost_max}))
         s, i, hyb, kws, base = hit.scores, hit.ids, hit.hybrid, hit.keyword, hit.base
         if reranker is not None:
@@ -880,6 +923,8 @@ class HipCollection:
             out["binary_count"] = [int(v) for v in hit.binary_count]
         if hit.pq_count is not None:
             out["pq_count"] = [int(v) for v in hit.pq_count]
+        if hit.graph_scored is not None:
+            out["graph_scored"] = [int(v) for v in hit.graph_scored]
         if base is not None:
             out["base_scores"] = [base[qi][i[qi] >= 0].tolist() for qi in range(q.shape[0])]
         if hit.mmr is not None:

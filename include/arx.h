@@ -895,6 +895,45 @@ int32_t arx_pq_candidates_tuned(const uint8_t* codes, int64_t n_rows, int32_t di
                                 const uint64_t* allow, int32_t n_candidates, int32_t* out_cand, int32_t* out_sum, int64_t* out_count,
                                 void* ws, int64_t ws_bytes, int32_t rows_per_block, void* stream);
 
+/* ---- Graph search: beam search over a fixed-degree k-NN graph, exact scores (csrc/graph.hip; the host layer and the numpy restatement
+ * `search_host` are arxiv_rag_amd/graph.py; the definition is INTEGRATION.md "Graph search") --------------------------------------------
+ *   corpus        device fp16 [n_rows, dim], 16-byte aligned; queries device fp16 [n_queries, dim], 16-byte aligned
+ *   neighbors     device int32 [n_rows, degree], degree a multiple of 8 in 8..64; an entry outside [0, n_rows) is "no edge"
+ *   entries       device int32 [n_queries, n_entries], n_entries in 1..64; an entry outside [0, n_rows) is skipped
+ *   allow         device uint64 [ceil(n_rows / 64)] or NULL: arx_topk_search_filtered's convention (bit r & 63 of word r >> 6)
+ *   k in 1..32, ef in k..512, max_iters in 1..1024
+ *   out_scores    device f32 [n_queries, k]; out_ids device int64 [n_queries, k]; out_scored, out_expanded device int64 [n_queries] or NULL
+ *   ws            device scratch of arx_graph_workspace_bytes(...) bytes (-1 for arguments outside the limits below)
+ * Per query, with a visited set (exact set semantics), a beam of at most ef (score, row) pairs ordered by (score desc, row asc) and an
+ * "expanded" mark per beam row.  A row's score is exact_row_score (csrc/exact_score.h) against the query, the bits of arx_topk_search; a
+ * NaN score ranks below every number (among NaNs: row asc) and comes back as the quiet NaN 0x7fc00000.
+ *   start    the distinct valid entry rows become visited, are scored and merged into the beam, which is cut to its best ef
+ *   iterate  at most max_iters times: the parent is the best beam row not yet expanded (none: stop); it is marked expanded; each of its
+ *            neighbours that is valid and not yet visited becomes visited and is scored; the new pairs are merged into the beam, which
+ *            is cut to ef.  A row that falls off the beam stays visited and is never scored again.
+ *   answer   without allow the first k of the beam; with allow the best k by (score desc, row asc) among ALL rows scored whose bit is
+ *            set (the walk ignores the bitmap: hidden rows stay bridges).  Missing places are (-inf, -1); ids are row + idx_base.
+ *   out_scored[q] the rows scored, out_expanded[q] the iterations run.
+ * One launch on `stream`, one block per query, all state in LDS (the workspace is not written): a query's outputs depend on its row of
+ * queries and entries, the graph, allow and the corpus; not on the batch or the launch shape.  The visited set is an open-addressing
+ * table of 16384 slots filled by integer LDS compare-and-swap, the only atomics; it holds at most 8192 rows, and a call whose
+ * n_entries + max_iters * degree exceeds 8192 is refused: the table never drops a row.
+ * ARX_ERR_ARG before the launch, the message naming the field: any of the ranges above; n_entries + max_iters * degree > 8192; dim not a
+ * multiple of 64 or above 8192; n_rows outside 1..2^31-1; n_queries < 1; a null or misaligned pointer; ws_bytes below the figure above.
+ * neighbors, entries and allow are device data: bad values give the defined answer above and never an access out of range. */
+int64_t arx_graph_workspace_bytes(int64_t n_rows, int32_t n_queries, int32_t dim, int32_t degree, int32_t k, int32_t ef, int32_t max_iters,
+                                  int32_t n_entries);
+int32_t arx_graph_search(const void* corpus, int64_t n_rows, int32_t dim, const int32_t* neighbors, int32_t degree, const void* queries,
+                         int32_t n_queries, const int32_t* entries, int32_t n_entries, const uint64_t* allow, int32_t k, int32_t ef,
+                         int32_t max_iters, float* out_scores, int64_t* out_ids, int64_t* out_scored, int64_t* out_expanded, int64_t idx_base,
+                         void* ws, int64_t ws_bytes, void* stream);
+/* The same with the block size chosen: threads 0 (default: 256, or 128 for degree <= 16), 64, 128 or 256; a block scores threads / 8
+ * rows per pass.  Same bits for every choice. */
+int32_t arx_graph_search_tuned(const void* corpus, int64_t n_rows, int32_t dim, const int32_t* neighbors, int32_t degree, const void* queries,
+                               int32_t n_queries, const int32_t* entries, int32_t n_entries, const uint64_t* allow, int32_t k, int32_t ef,
+                               int32_t max_iters, float* out_scores, int64_t* out_ids, int64_t* out_scored, int64_t* out_expanded,
+                               int64_t idx_base, void* ws, int64_t ws_bytes, int32_t threads, void* stream);
+
 /* ---- MMR diversified re-ordering of a query's search candidates (csrc/mmr.hip; the definition is INTEGRATION.md "MMR") -----------
  * arx_gather_rows: out[s] (device fp16 [count, dim]) = shard row ids[s] - idx_base where that row lies in [0, n_rows), all zeros
  * otherwise (id -1, a row another rank owns: the ranks' buffers then add up to the rows, arxiv_rag_amd/mmr.py).  shard device fp16

@@ -1,5 +1,6 @@
 // arx_graph_search: beam search over a fixed-degree k-NN graph, exact scores (gfx950; C ABI in include/arx.h; the host layer and the
-// numpy restatement are arxiv_rag_amd/graph.py; the definition is INTEGRATION.md "Graph search").
+// numpy restatement are arxiv_rag_amd/graph.py; the definition is INTEGRATION.md "Graph search").  arx_graph_link and arx_graph_remap,
+// which keep a built graph usable across added and compacted rows, are further down with their own notes.
 //
 // One block per query, every bit of state in LDS, so a query's answer cannot depend on its batch:
 //   qs        the fp16 query row.
@@ -206,6 +207,133 @@ __global__ __launch_bounds__(GRAPH_NT_MAX) void graph_search_kernel(const f16_t*
     }
 }
 
+// ---- arx_graph_link: offer rows to the tails of other rows' neighbour lists (include/arx.h; INTEGRATION.md "Graph search") ---------
+// One block per target slot; a slot that passes the checks below is the only writer of its row, so plain stores, no atomics and no
+// workspace.  The row t is the query (staged in LDS); its head, neighbors[t][0:H], is never written.  The candidates are a stream:
+// the H entries of the old tail, then the slot's offers, 64 at a time:
+//   1  wave 0 reads the chunk, drops what is outside [0, n_rows), t itself and the head's rows, compacts the rest.        barrier
+//   2  eight lanes score a row (exact_row_score), blockDim / 8 rows per pass, and write its key.                          barrier
+//   3  wave 0 sorts the keys (the search's bitonic network), drops a key equal to its left neighbour or already in the running
+//      tail (one row always gives one key: that is the whole de-duplication, there is no visited set), and merges the rest by rank
+//      into the other of the two H-wide tail buffers.
+// The tail is the H largest keys of a set, so it depends neither on the chunking nor on the block size.
+struct LinkSm {
+    u64 best[2][GRAPH_DEGREE_MAX / 2];          // the running tail, sorted descending; two buffers as for the beam
+    u64 fresh[64], uniq[64];
+    int32_t head[GRAPH_DEGREE_MAX / 2];
+    int32_t cand[64];
+    int32_t red[GRAPH_NW_MAX];
+    int32_t n_cand;
+};
+
+__global__ __launch_bounds__(GRAPH_NT_MAX) void graph_link_kernel(const f16_t* __restrict__ C, int64_t n_rows, int D, int32_t* nbr, int degree,
+                                                                   const int32_t* __restrict__ targets, const int32_t* __restrict__ offer_start,
+                                                                   const int32_t* __restrict__ offers, int64_t n_offers) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    f16_t* qs = reinterpret_cast<f16_t*>(smem);
+    LinkSm& sm = *reinterpret_cast<LinkSm*>(smem + (size_t)D * 2);
+    const int s = blockIdx.x, tid = threadIdx.x, nt = blockDim.x, lane = tid & 63, w = tid >> 6;
+    const int nch = D >> 3, l8 = lane & 7, oct = tid >> 3, n_oct = nt >> 3, H = degree >> 1;
+    const int64_t t = targets[s];
+    const int64_t o0 = offer_start[s], o1 = offer_start[s + 1];
+    if (t < 0 || t >= n_rows || o0 < 0 || o1 < o0 || o1 > n_offers) return;          // (block-uniform, as every return below)
+    // the largest valid target of the slots before this one: a slot at or below it is skipped, so no two blocks ever write one row
+    int32_t before = -1;
+    for (int i = tid; i < s; i += nt) {
+        const int32_t v = targets[i];
+        if (v < n_rows) before = max(before, v);                 // (a negative one cannot raise it)
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) before = max(before, __shfl_xor(before, o));
+    if (lane == 0) sm.red[w] = before;
+    __syncthreads();
+    for (int i = 0; i < (nt >> 6); ++i) before = max(before, sm.red[i]);
+    if (t <= before) return;
+    for (int i = tid; i < nch; i += nt) reinterpret_cast<u32x4*>(qs)[i] = reinterpret_cast<const u32x4*>(C + t * D)[i];
+    if (tid < H) sm.head[tid] = nbr[t * degree + tid];
+    __syncthreads();
+    const int total = H + (int)(o1 - o0);
+    int cur = 0, n_best = 0;                                     // (wave 0's)
+    for (int c0 = 0; c0 < total; c0 += 64) {
+        // ---- 1: the chunk's candidates (wave 0)
+        if (w == 0) {
+            const int j = c0 + lane;
+            int32_t r = -1;
+            if (j < total) r = j < H ? nbr[t * degree + H + j] : offers[o0 + (j - H)];
+            bool ok = r >= 0 && r < n_rows && r != t;
+            for (int i = 0; i < H; ++i) ok = ok && sm.head[i] != r;
+            const u64 in = __ballot(ok);
+            if (ok) sm.cand[__popcll(in & ((1ull << lane) - 1ull))] = r;
+            if (lane == 0) sm.n_cand = __popcll(in);
+        }
+        __syncthreads();
+        // ---- 2: score them, eight lanes each
+        const int n_cand = sm.n_cand;
+        for (int b0 = 0; b0 < n_cand; b0 += n_oct) {             // wave-uniform bounds: every lane of an octet reaches the shuffles
+            const int c = b0 + oct;
+            const bool ok = c < n_cand;
+            const int64_t row = ok ? sm.cand[c] : 0;
+            const float a = exact_row_score(C + row * D, qs, nch, l8, ok);
+            if (ok && l8 == 0) sm.fresh[c] = ((u64)graph_order_word(a) << 32) | (u64)(0xffffffffu - (uint32_t)row);
+        }
+        if (tid < 64 && tid >= n_cand) sm.fresh[tid] = 0ull;
+        __syncthreads();
+        // ---- 3: sort, drop the repeats, merge by rank (wave 0; the next chunk's step 1 is wave 0's too, so no barrier follows)
+        if (w == 0) {
+            const u64 key = graph_wave_sort(sm.fresh[lane], lane);
+            const u64 left = __shfl_up(key, 1);
+            const u64* ob = sm.best[cur];
+            u64* nb = sm.best[cur ^ 1];
+            bool fresh = key != 0ull && (lane == 0 || key != left);
+            if (fresh) {
+                const int p = graph_above(ob, n_best, key);
+                fresh = !(p < n_best && ob[p] == key);
+            }
+            const u64 in = __ballot(fresh);
+            const int n_new = __popcll(in);
+            if (fresh) sm.uniq[__popcll(in & ((1ull << lane) - 1ull))] = key;
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            if (lane < n_best) {
+                const u64 k0 = ob[lane];
+                const int pos = lane + graph_above(sm.uniq, n_new, k0);
+                if (pos < H) nb[pos] = k0;
+            }
+            if (lane < n_new) {
+                const u64 k1 = sm.uniq[lane];
+                const int pos = lane + graph_above(ob, n_best, k1);
+                if (pos < H) nb[pos] = k1;
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            n_best = n_best + n_new < H ? n_best + n_new : H;
+            cur ^= 1;
+        }
+    }
+    if (w == 0 && lane < H) nbr[t * degree + H + lane] = lane < n_best ? (int32_t)(0xffffffffu - (uint32_t)sm.best[cur][lane]) : -1;
+}
+
+// ---- arx_graph_remap: renumber the moved neighbour rows of a stable compaction.  A wave per row, a lane per entry: every lane has
+// read its entry before the ballot that places the survivors, so the row is rewritten in place with plain stores.
+__global__ __launch_bounds__(GRAPH_NT_MAX) void graph_remap_kernel(int32_t* nbr, int64_t count, int degree, const unsigned long long* __restrict__ keep,
+                                                                    const long long* __restrict__ word_rank, int64_t n_old) {
+    const int lane = threadIdx.x & 63;
+    const int64_t r = (int64_t)blockIdx.x * GRAPH_NW_MAX + (threadIdx.x >> 6);
+    if (r >= count) return;                                      // (wave-uniform)
+    int64_t e = -1;
+    if (lane < degree) e = nbr[r * degree + lane];
+    bool ok = false;
+    if (e >= 0 && e < n_old) {
+        const unsigned long long kw = keep[e >> 6];
+        if ((kw >> (e & 63)) & 1ull) {
+            e = word_rank[e >> 6] + __popcll(kw & ((1ull << (e & 63)) - 1ull));
+            ok = e >= 0 && e < count;                            // (false only for a plan that is not this bitmap's)
+        }
+    }
+    const u64 in = __ballot(ok);
+    const int n_ok = __popcll(in);
+    if (ok) nbr[r * degree + __popcll(in & ((1ull << lane) - 1ull))] = (int32_t)e;
+    if (lane >= n_ok && lane < degree) nbr[r * degree + lane] = -1;
+}
+
 bool graph_shape_ok(int64_t n_rows, int32_t n_queries, int32_t dim, int32_t degree, int32_t k, int32_t ef, int32_t max_iters, int32_t n_entries) {
     return n_rows > 0 && n_rows < (1ll << 31) && n_queries > 0 && dim > 0 && dim % 64 == 0 && dim <= 8192 && degree >= 8 &&
            degree <= GRAPH_DEGREE_MAX && degree % 8 == 0 && k >= 1 && k <= GRAPH_K_MAX && ef >= k && ef <= GRAPH_EF_MAX && max_iters >= 1 &&
@@ -257,4 +385,45 @@ extern "C" int32_t arx_graph_search(const void* corpus, int64_t n_rows, int32_t 
                                     int64_t* out_expanded, int64_t idx_base, void* ws, int64_t ws_bytes, void* stream) {
     return arx_graph_search_tuned(corpus, n_rows, dim, neighbors, degree, queries, n_queries, entries, n_entries, allow, k, ef, max_iters,
                                   out_scores, out_ids, out_scored, out_expanded, idx_base, ws, ws_bytes, 0, stream);
+}
+
+extern "C" int32_t arx_graph_link_tuned(const void* corpus, int64_t n_rows, int32_t dim, int32_t* neighbors, int32_t degree, const int32_t* targets,
+                                        int32_t n_targets, const int32_t* offer_start, const int32_t* offers, int64_t n_offers, int32_t threads,
+                                        void* stream) {
+    ARX_REQUIRE(degree >= 8 && degree <= GRAPH_DEGREE_MAX && degree % 8 == 0, "degree=%d must be a multiple of 8 in 8..%d", degree, GRAPH_DEGREE_MAX);
+    ARX_REQUIRE(dim > 0 && dim % 64 == 0 && dim <= 8192, "dim=%d must be a multiple of 64, at most 8192", dim);
+    ARX_REQUIRE(n_rows > 0 && n_rows < (1ll << 31), "n_rows=%lld out of range 1..2^31-1", (long long)n_rows);
+    ARX_REQUIRE(n_targets >= 0, "n_targets=%d is negative", n_targets);
+    ARX_REQUIRE(n_offers >= 0 && n_offers < (1ll << 31) - GRAPH_DEGREE_MAX, "n_offers=%lld out of range 0..2^31-%d", (long long)n_offers,
+                GRAPH_DEGREE_MAX + 1);
+    ARX_REQUIRE(threads == 0 || threads == 64 || threads == 128 || threads == 256, "threads=%d: 0 (default), 64, 128 or 256", threads);
+    ARX_REQUIRE(corpus && neighbors && offer_start, "null pointer argument");
+    ARX_REQUIRE(targets || n_targets == 0, "targets is a null pointer (n_targets=%d)", n_targets);
+    ARX_REQUIRE(offers || n_offers == 0, "offers is a null pointer (n_offers=%lld)", (long long)n_offers);
+    ARX_REQUIRE((uintptr_t)corpus % 16 == 0, "corpus must be 16-byte aligned");
+    if (n_targets == 0) return ARX_OK;
+    if (threads == 0) threads = degree > 16 ? 256 : 128;          // the search's choice: a first chunk of H + offers rows, 32 or 16 a pass
+    const int smem = dim * 2 + (int)sizeof(LinkSm);
+    graph_link_kernel<<<n_targets, threads, smem, (hipStream_t)stream>>>((const f16_t*)corpus, n_rows, dim, neighbors, degree, targets, offer_start,
+                                                                        offers, n_offers);
+    ARX_HIP_CHECK(hipGetLastError());
+    return ARX_OK;
+}
+
+extern "C" int32_t arx_graph_link(const void* corpus, int64_t n_rows, int32_t dim, int32_t* neighbors, int32_t degree, const int32_t* targets,
+                                  int32_t n_targets, const int32_t* offer_start, const int32_t* offers, int64_t n_offers, void* stream) {
+    return arx_graph_link_tuned(corpus, n_rows, dim, neighbors, degree, targets, n_targets, offer_start, offers, n_offers, 0, stream);
+}
+
+extern "C" int32_t arx_graph_remap(int32_t* neighbors, int64_t count, int32_t degree, const uint64_t* keep, const int64_t* word_rank, int64_t n_old,
+                                   void* stream) {
+    ARX_REQUIRE(degree >= 8 && degree <= GRAPH_DEGREE_MAX && degree % 8 == 0, "degree=%d must be a multiple of 8 in 8..%d", degree, GRAPH_DEGREE_MAX);
+    ARX_REQUIRE(n_old >= 0 && n_old < (1ll << 31), "n_old=%lld out of range 0..2^31-1", (long long)n_old);
+    ARX_REQUIRE(count >= 0 && count <= n_old, "count=%lld out of range 0..n_old=%lld", (long long)count, (long long)n_old);
+    if (count == 0) return ARX_OK;
+    ARX_REQUIRE(neighbors && keep && word_rank, "null pointer argument");
+    graph_remap_kernel<<<(unsigned)((count + GRAPH_NW_MAX - 1) / GRAPH_NW_MAX), GRAPH_NT_MAX, 0, (hipStream_t)stream>>>(
+        neighbors, count, degree, (const unsigned long long*)keep, (const long long*)word_rank, n_old);
+    ARX_HIP_CHECK(hipGetLastError());
+    return ARX_OK;
 }

@@ -11,8 +11,13 @@ thousand rows whatever the shard's size, and its answer does not depend on the b
 
 `graph_search` is the one place that calls the library.  `search_host` and `assemble_host` restate the kernel and the graph assembly
 with numpy (for the tests; the product path never calls them); `check_search_args`, `check_build_args` and `check_query_with_graph` are
-the refusals, each a ValueError before any launch.  A graph is built once over the rows there are: inserting rows into a built graph is
-out of scope, `HipCollection.add` and `compact` mark it stale and `build_graph` has to run again.
+the refusals, each a ValueError before any launch.
+
+A built graph follows the rows only where that is asked for (`HipCollection.build_graph(maintain=True)`): `GraphIndex.insert` links new
+rows in (a graph search and an exact search of the batch for their candidates, then one `arx_graph_link` that offers them to the tails
+of their nearest rows' lists), `GraphIndex.remap` renumbers the graph after a compaction (`arx_graph_remap`).  `graph_link` and
+`graph_remap` are the only callers of those two entry points; `link_host`, `remap_host` and `insert_host` restate them with numpy.
+Without `maintain`, `HipCollection.add` and `compact` mark the graph stale and `build_graph` has to run again.
 """
 from __future__ import annotations
 
@@ -98,7 +103,7 @@ def check_query_with_graph(graph_ef, *, has_index: bool, stale: bool = False, n_
         raise ValueError("graph_ef needs a graph index: call build_graph() first")
     if stale:
         raise ValueError("the graph index is stale: rows were added or compacted since build_graph(); run build_graph() again "
-                         "(inserting rows into a built graph is out of scope)")
+                         "(build_graph(maintain=True) keeps the graph usable across add and compact)")
     if not _is_int(n_entries) or not (1 <= n_entries <= min(MAX_QUERY_ENTRIES, n_entry_lists)):
         raise ValueError(f"graph_entries={n_entries!r} must be an integer in [1, min({MAX_QUERY_ENTRIES}, entry lists = {n_entry_lists})]")
     if not _is_int(n_width) or not (1 <= n_width <= MAX_K):
@@ -213,7 +218,171 @@ def assemble_host(knn, degree: int) -> np.ndarray:
     return out
 
 
+def _keys_of(scores, rows):
+    """The kernel's integer keys of (score, row) pairs: order word << 32 | (0xffffffff - row)."""
+    return [(int(w) << 32) | (0xFFFFFFFF - int(r)) for w, r in zip(order_words(scores), rows)]
+
+
+def link_host(X, neighbors, targets, offer_start, offers, n_rows: Optional[int] = None) -> np.ndarray:
+    """int32 [rows, degree]: `neighbors` after `arx_graph_link`, bit for bit (include/arx.h has the definition).  `X` fp16 [>= n_rows,
+    dim], `neighbors` int [>= n_rows, degree], `targets` int [T], `offer_start` int [T + 1], `offers` int [n_offers]; `n_rows`: the
+    rows there are (None: all of `X`).  Per live slot: the head stays, the pool is the old tail and the offers without the target, the
+    head's rows and repeats, the new tail its H largest keys.  A slot is live when its target lies in [0, n_rows), is above every
+    earlier slot's target inside [0, n_rows) and its `offer_start` pair is ascending inside [0, n_offers]."""
+    from .topics import exact_scores_host
+    X = np.asarray(X)
+    out = np.array(neighbors, dtype=np.int32, copy=True)
+    n = int(X.shape[0]) if n_rows is None else int(n_rows)
+    H = out.shape[1] // 2
+    targets, start, offers = (np.asarray(v).astype(np.int64).tolist() for v in (targets, offer_start, offers))
+    top = -1
+    for s, t in enumerate(targets):
+        before, top = top, (max(top, t) if t < n else top)
+        a, b = start[s], start[s + 1]
+        if not (0 <= t < n) or t <= before or a < 0 or b < a or b > len(offers):
+            continue
+        head = {int(r) for r in out[t, :H] if 0 <= r < n}
+        pool = sorted({int(r) for r in out[t, H:].tolist() + offers[a:b] if 0 <= r < n and r != t and r not in head})
+        keys = sorted(_keys_of(exact_scores_host(X[pool], X[t:t + 1])[:, 0], pool), reverse=True)[:H] if pool else []
+        out[t, H:] = [0xFFFFFFFF - (key & 0xFFFFFFFF) for key in keys] + [-1] * (H - len(keys))
+    return out
+
+
+def remap_host(neighbors, keep, n_old: Optional[int] = None) -> np.ndarray:
+    """int32 [count, degree]: the moved neighbour rows `neighbors` (those of the kept rows, in order) after `arx_graph_remap`.
+    `keep`: bool [n_old] or bitmap words (then `n_old` is needed).  An entry that names a kept row becomes that row's new number
+    (`mutation.old_to_new`), every other entry is dropped; the survivors move to the row's front in order, the rest is -1."""
+    from .mutation import old_to_new, unpack_rows
+    keep = np.asarray(keep)
+    mask = keep if keep.dtype == bool else unpack_rows(keep, int(n_old))
+    new = old_to_new(mask)
+    nb = np.asarray(neighbors)
+    out = np.full(nb.shape, -1, np.int32)
+    for i, row in enumerate(nb.tolist()):
+        v = [int(new[e]) for e in row if 0 <= e < mask.shape[0] and mask[e]]
+        out[i, :len(v)] = v
+    return out
+
+
+def orphans_host(neighbors, lo: int, hi: int) -> int:
+    """The rows of [lo, hi) that no row's list names."""
+    nb = np.asarray(neighbors)[:hi]
+    return int(hi - lo - np.unique(nb[(nb >= lo) & (nb < hi)]).shape[0])
+
+
+def insert_host(X, neighbors, lo: int, hi: int, entries, insert_ef: int = 64, batch: Optional[int] = None, pair_scores=None):
+    """(int32 [hi, degree], {inserted, offers, orphans}): what `GraphIndex.insert(lo, hi, insert_ef)` leaves, edge for edge.  `X` fp16
+    [>= hi, dim], `neighbors` int [lo, degree] (the graph over [0, lo)), `entries` int [hi - lo, E]: the entry rows of every new
+    row's walk (`GraphIndex.entries` of the rows), `batch`: rows per batch (None: `BUILD_BATCH`).  Per batch [a, b): `search_host`
+    over the a rows before it (k = 31), the exact scores of the batch against itself (the 32 best a row, its own id dropped as
+    `knn_lists` drops it), the 31 best of the two by key, the new rows' lists, and one `link_host` of the offers over b rows.
+    `pair_scores`: f32 [hi, hi - lo], `exact_scores_host(X[:hi], X[lo:hi])` computed once by the caller."""
+    from .topics import exact_scores_host
+    X, entries = np.asarray(X), np.asarray(entries)
+    degree = int(np.asarray(neighbors).shape[1])
+    check_insert_args(degree, int(np.asarray(neighbors).shape[0]), lo, hi, int(X.shape[0]), insert_ef)
+    H, batch = degree // 2, BUILD_BATCH if batch is None else int(batch)
+    E = int(entries.shape[1])
+    max_iters = max(1, min(int(insert_ef), max_iters_for(degree, E)))
+    nb = np.full((hi, degree), -1, np.int32)
+    nb[:lo] = np.asarray(neighbors)[:lo]
+    n_offers = 0
+    for a in range(lo, hi, batch):
+        b = min(hi, a + batch)
+        m = b - a
+        P = None if pair_scores is None else pair_scores[:, a - lo:b - lo]
+        so, io, _, _ = search_host(X[:a], nb[:a], X[a:b], entries[a - lo:b - lo], KNN - 1, int(insert_ef), max_iters,
+                                   pair_scores=None if P is None else P[:a])
+        S = exact_scores_host(X[a:b], X[a:b]) if P is None else P[a:b]                      # [row, query]
+        by_target: Dict[int, list] = {}
+        for j in range(m):
+            own = sorted(_keys_of(S[:, j], range(m)), reverse=True)[:KNN]
+            me = next((p for p, key in enumerate(own) if 0xFFFFFFFF - (key & 0xFFFFFFFF) == j), None)
+            if me is not None:
+                del own[me]
+            elif len(own) == KNN:
+                del own[-1]
+            own = [((key >> 32) << 32) | (0xFFFFFFFF - (0xFFFFFFFF - (key & 0xFFFFFFFF) + a)) for key in own]
+            old = _keys_of(so[j][io[j] >= 0], io[j][io[j] >= 0])
+            knn = [0xFFFFFFFF - (key & 0xFFFFFFFF) for key in sorted(old + own, reverse=True)[:KNN - 1]]
+            nb[a + j, :min(degree, len(knn))] = knn[:degree]
+            for t in knn[:H]:
+                by_target.setdefault(t, []).append(a + j)
+        targets = sorted(by_target)
+        start = np.zeros(len(targets) + 1, np.int64)
+        start[1:] = np.cumsum([len(by_target[t]) for t in targets])
+        offers = [r for t in targets for r in by_target[t]]
+        n_offers += len(offers)
+        nb = link_host(X, nb, targets, start, offers, n_rows=b)
+    return nb, {"inserted": hi - lo, "offers": n_offers, "orphans": orphans_host(nb, lo, hi)}
+
+
+def check_insert_args(degree: int, n_rows: int, lo, hi, corpus_rows: int, insert_ef) -> None:
+    """The refusals of `GraphIndex.insert` (and `insert_host`), each a ValueError before anything is launched."""
+    if degree > MAX_BUILD_DEGREE:
+        raise ValueError(f"degree={degree} is above {MAX_BUILD_DEGREE}: an insert has {KNN - 1} candidates a row, as a build has")
+    if not _is_int(lo) or lo != n_rows:
+        raise ValueError(f"lo={lo!r} must be the graph's row count {n_rows}: rows are inserted behind the rows the graph covers")
+    if not _is_int(hi) or hi < lo or hi > corpus_rows:
+        raise ValueError(f"hi={hi!r} must lie in [lo, rows of the corpus] = [{lo}, {corpus_rows}]")
+    if hi >= 1 << 31:
+        raise ValueError(f"hi={hi} must be below 2^31 (the graph holds int32 rows)")
+    if not _is_int(insert_ef) or not (KNN - 1 <= insert_ef <= MAX_EF):
+        raise ValueError(f"insert_ef={insert_ef!r} must be an integer in [{KNN - 1}, {MAX_EF}] (the walk returns {KNN - 1} candidates a row)")
+
+
 # ---- the device path ---------------------------------------------------------------------------------------------------------------
+def graph_link(corpus, neighbors, targets, offer_start, offers, n_rows: Optional[int] = None, threads: Optional[int] = None) -> None:
+    """`arx_graph_link` (with `threads`: `arx_graph_link_tuned`) on the current stream, its one caller: `neighbors` (int32 device
+    [>= n_rows, degree]) is rewritten in place.  `corpus` fp16 device [>= n_rows, dim]; `targets` int32 device [T], `offer_start` int32
+    device [T + 1], `offers` int32 device [n_offers].  The library checks the contract: an `ArxError` naming the field, before any launch."""
+    import torch
+    from . import _lib
+    lib = _lib.load()
+    n_rows = int(corpus.shape[0]) if n_rows is None else int(n_rows)
+    assert corpus.is_cuda and corpus.dtype == torch.float16 and corpus.dim() == 2 and corpus.is_contiguous() and corpus.shape[0] >= n_rows
+    assert neighbors.is_cuda and neighbors.dtype == torch.int32 and neighbors.dim() == 2 and neighbors.shape[0] >= n_rows and neighbors.is_contiguous()
+    for t in (targets, offer_start, offers):
+        assert t.is_cuda and t.dtype == torch.int32 and t.dim() == 1 and t.is_contiguous()
+    assert offer_start.shape[0] == targets.shape[0] + 1
+    name = "arx_graph_link"
+    args = [corpus.data_ptr(), n_rows, int(corpus.shape[1]), neighbors.data_ptr(), int(neighbors.shape[1]), targets.data_ptr(), int(targets.shape[0]),
+            offer_start.data_ptr(), offers.data_ptr(), int(offers.shape[0])]
+    if threads is not None:
+        name, args = name + "_tuned", args + [int(threads)]
+    with torch.cuda.device(corpus.device):
+        _lib.check(getattr(lib, name)(*args, torch.cuda.current_stream(corpus.device).cuda_stream), name)
+
+
+def graph_remap(neighbors, count: int, keep_words, word_rank, n_old: int) -> None:
+    """`arx_graph_remap` on the current stream, its one caller: the first `count` rows of `neighbors` (int32 device, the kept rows
+    already moved) are renumbered in place.  `keep_words`, `word_rank`: the bitmap and `mutation.plan_device`'s plan over `n_old` rows."""
+    import torch
+    from . import _lib
+    assert neighbors.is_cuda and neighbors.dtype == torch.int32 and neighbors.dim() == 2 and neighbors.is_contiguous() and neighbors.shape[0] >= count
+    assert keep_words.is_cuda and keep_words.dtype in (torch.int64, torch.uint64) and keep_words.shape[0] >= (n_old + 63) // 64
+    assert word_rank.is_cuda and word_rank.dtype == torch.int64 and word_rank.shape[0] >= (n_old + 63) // 64 + 1
+    with torch.cuda.device(neighbors.device):
+        _lib.check(_lib.load().arx_graph_remap(neighbors.data_ptr(), int(count), int(neighbors.shape[1]), keep_words.data_ptr(), word_rank.data_ptr(),
+                                               int(n_old), torch.cuda.current_stream(neighbors.device).cuda_stream), "arx_graph_remap")
+
+
+def best_of(scores, ids, width: int):
+    """int64 device [m, width]: per row the ids of the `width` best (score, id) pairs by the kernel's key order (score desc by order
+    word, id asc; an id < 0 is no pair), -1 padded.  `scores` f32 device [m, w], `ids` int64 device [m, w].  Two stable torch sorts."""
+    import torch
+    u = scores.contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    word = torch.where(u >= 0x80000000, u ^ 0xFFFFFFFF, u | 0x80000000)
+    word = torch.where(torch.isnan(scores), torch.zeros_like(word), word)
+    word = torch.where(ids >= 0, word, torch.full_like(word, -1))
+    by_id = torch.sort(torch.where(ids >= 0, ids, torch.full_like(ids, 1 << 40)), dim=1, stable=True).indices
+    by_word = torch.sort(word.gather(1, by_id), dim=1, descending=True, stable=True).indices
+    out = ids.gather(1, by_id).gather(1, by_word)[:, :width]
+    if out.shape[1] < width:
+        out = torch.cat([out, torch.full((out.shape[0], width - out.shape[1]), -1, dtype=torch.int64, device=out.device)], dim=1)
+    return out.contiguous()
+
+
 def graph_search(corpus, neighbors, q, entries, k: int, ef: int, max_iters: int, allow=None, idx_base: int = 0, threads: Optional[int] = None,
                  ws=None, n_rows: Optional[int] = None):
     """`arx_graph_search` (or, with `threads` given, `arx_graph_search_tuned`) on the current stream, the one call into the library.
@@ -329,6 +498,8 @@ class GraphIndex:
         self.info = dict(info or {})
         self.stale = False                                       # set by `HipCollection.add` / `compact`: the rows changed under the graph
         self._ws = None
+        self._buf, self._spare = self.neighbors, None            # `neighbors` is the first n_rows rows of `_buf` (`reserve`)
+        self.inserted = self.orphans = 0                         # totals over every `insert`
 
     @classmethod
     def build(cls, index, degree: int = 32, n_entry_lists: Optional[int] = None, iters: int = 10, seed: int = 0, ivf=None,
@@ -365,9 +536,89 @@ class GraphIndex:
         return self
 
     def summary(self) -> Dict:
-        """{rows, degree, edges, entry_lists, approximate, seconds}: `edges` the neighbour slots filled."""
+        """{rows, degree, edges, entry_lists, inserted, orphans, approximate, seconds}: `edges` the neighbour slots filled, `inserted`
+        and `orphans` the totals of every `insert` (an orphan: an inserted row no list named when its insert ended)."""
         return {"rows": self.n_rows, "degree": self.degree, "edges": int((self.neighbors >= 0).sum().item()),
-                "entry_lists": self.n_entry_lists, **self.info}
+                "entry_lists": self.n_entry_lists, "inserted": self.inserted, "orphans": self.orphans, **self.info}
+
+    def reserve(self, rows: int) -> None:
+        """Make room for `rows` neighbour rows: `neighbors` stays a view of the first `n_rows` rows of the buffer."""
+        import torch
+        if self._buf.shape[0] < rows:
+            buf = torch.full((int(rows), self.degree), -1, dtype=torch.int32, device=self._buf.device)
+            buf[:self.n_rows] = self.neighbors
+            self._buf, self._spare, self.neighbors = buf, None, buf[:self.n_rows]
+
+    def insert(self, lo: int, hi: int, insert_ef: int = 64, n_entries: int = 8) -> Dict:
+        """Link the rows [lo, hi) of `index.corpus` into the graph over [0, lo) (INTEGRATION.md "Keeping the graph"), in batches
+        [a, b) of at most `BUILD_BATCH` rows: the candidates of a new row are the 31 best of its graph search over the a rows before the
+        batch (k = 31, ef = `insert_ef`, from the medoids of its `n_entries` nearest entry centroids) and of the exact search of the
+        batch among itself; its list is their first `degree`; its H = degree / 2 best are offered the row, one `arx_graph_link` over b
+        rows a batch.  Nothing is rebuilt: the old rows' heads, the centroids and the medoids stay.  -> {inserted, offers, orphans,
+        seconds}, `orphans` the inserted rows no row's list names afterwards (the walk cannot reach them; they are reported, not
+        hidden).  ValueError before any launch: `check_insert_args`."""
+        import torch
+        from .index import ShardIndex
+        X = self.index.corpus
+        check_insert_args(self.degree, self.n_rows, lo, hi, int(X.shape[0]), insert_ef)
+        E = min(int(n_entries), self.n_entry_lists) if _is_int(n_entries) else n_entries
+        if not _is_int(E) or not (1 <= E <= MAX_QUERY_ENTRIES):
+            raise ValueError(f"n_entries={n_entries!r} must be an integer in [1, {MAX_QUERY_ENTRIES}]")
+        t0 = time.perf_counter()
+        dev, H = X.device, self.degree // 2
+        self.reserve(hi)
+        nb = self._buf
+        max_iters = max(1, min(int(insert_ef), max_iters_for(self.degree, E)))
+        if self._ws is None:
+            self._ws = torch.empty(256, dtype=torch.uint8, device=dev)
+        n_offers = 0
+        for a in range(lo, hi, BUILD_BATCH):
+            b = min(hi, a + BUILD_BATCH)
+            m, q = b - a, X[a:b]
+            so, io, _, _ = graph_search(X, nb, q, self.entries(q, E), KNN - 1, int(insert_ef), max_iters, ws=self._ws, n_rows=a)
+            sn, i_n = ShardIndex(q).search(q, KNN)
+            own = i_n == torch.arange(m, device=dev)[:, None]                              # dropped as `knn_lists` drops it
+            drop = torch.where(own.any(dim=1), own.to(torch.int32).argmax(dim=1), torch.full((m,), KNN - 1, device=dev))
+            keep = torch.arange(KNN, device=dev)[None, :] != drop[:, None]
+            sn, i_n = sn[keep].reshape(m, KNN - 1), i_n[keep].reshape(m, KNN - 1)
+            knn = best_of(torch.cat([so, sn], dim=1), torch.cat([io, torch.where(i_n >= 0, i_n + a, i_n)], dim=1), KNN - 1)
+            nb[a:b] = -1
+            nb[a:b, :min(self.degree, KNN - 1)] = knn[:, :self.degree].to(torch.int32)
+            # the offers (target = one of the row's H best, row) in the CSR form by target: a stable sort, as `assemble_device` sorts
+            tgt = knn[:, :H]
+            ok = tgt >= 0
+            by_t = torch.sort(tgt[ok], stable=True)
+            offers = torch.arange(a, b, device=dev)[:, None].expand(m, H)[ok][by_t.indices].to(torch.int32).contiguous()
+            targets, counts = torch.unique_consecutive(by_t.values, return_counts=True)
+            start = torch.zeros(targets.shape[0] + 1, dtype=torch.int32, device=dev)
+            start[1:] = torch.cumsum(counts, 0)
+            n_offers += int(offers.shape[0])
+            graph_link(X, nb, targets.to(torch.int32).contiguous(), start, offers, n_rows=b)
+        self.neighbors, self.n_rows = nb[:hi], int(hi)
+        named = torch.zeros(hi + 1, dtype=torch.bool, device=dev)
+        named[torch.where((self.neighbors >= lo) & (self.neighbors < hi), self.neighbors, torch.full_like(self.neighbors, hi)).long().flatten()] = True
+        orphans = int(hi - lo - named[lo:hi].sum().item())
+        self.inserted, self.orphans = self.inserted + (hi - lo), self.orphans + orphans
+        torch.cuda.synchronize(dev)
+        return {"inserted": hi - lo, "offers": n_offers, "orphans": orphans, "seconds": time.perf_counter() - t0}
+
+    def remap(self, keep_words, word_rank, count: int, index=None) -> None:
+        """Follow a stable compaction of the rows (`HipCollection.compact`): the kept rows' lists move (`arx_compact_rows`) and every
+        entry is renumbered (`arx_graph_remap`: an edge to a removed row is dropped, the survivors move to the front).  `index`: the
+        `ShardIndex` over the compacted rows.  The entry centroids are kept; the medoids are searched again, since rows moved."""
+        import torch
+        from .mutation import compact_rows_device
+        n_old = self.n_rows
+        if self._spare is None:
+            self._spare = torch.empty_like(self._buf)
+        compact_rows_device(self._buf, self._spare, n_old, keep_words, word_rank)
+        graph_remap(self._spare, int(count), keep_words, word_rank, n_old)
+        self._buf, self._spare = self._spare, self._buf
+        self.neighbors, self.n_rows = self._buf[:int(count)], int(count)
+        if index is not None:
+            self.index = index
+        medoid = self.index.search(self.centroids_f16, 1)[1][:, 0]
+        self.medoid = torch.where(medoid >= 0, medoid - self.index.idx_base, medoid).to(torch.int32).contiguous()
 
     def entries(self, q, n_entries: int):
         """int32 device [nq, n_entries]: the medoids of every query's `n_entries` nearest entry centroids (an exact search)."""

@@ -328,8 +328,12 @@ class HipCollection:
             self.binary.append(self._buf[n:n + m], index=self.index)
         if getattr(self, "pq", None) is not None:                # the new rows encoded with the kept codebooks and centre
             self.pq.append(self._buf[n:n + m], index=self.index)
-        if getattr(self, "graph", None) is not None:             # the new rows have no edges: the graph is stale until build_graph runs again
-            self.graph.stale = True
+        if getattr(self, "graph", None) is not None:
+            if getattr(self, "_graph_maintain", False):          # the new rows are linked into the graph (`GraphIndex.insert`)
+                self.graph.index = self.index
+                self.graph.insert(n, n + m, insert_ef=self._graph_insert_ef)
+            else:                                                # the new rows have no edges: the graph is stale until build_graph runs again
+                self.graph.stale = True
         if self._deleted is not None:
             self._deleted = np.concatenate([self._deleted, np.zeros(m, bool)])
         if self.dedup_threshold is not None:
@@ -433,8 +437,11 @@ class HipCollection:
             self.binary.compact(keep_words, word_rank, count, index=self.index)
         if getattr(self, "pq", None) is not None:                # the PQ codes move as the rows moved: dim / dsub-byte rows
             self.pq.compact(keep_words, word_rank, count, index=self.index)
-        if getattr(self, "graph", None) is not None:             # the rows moved under the edges: stale until build_graph runs again
-            self.graph.stale = True
+        if getattr(self, "graph", None) is not None:
+            if getattr(self, "_graph_maintain", False):          # the lists move as the rows moved and are renumbered: 4 * degree-byte rows
+                self.graph.remap(keep_words, word_rank, count, index=self.index)
+            else:                                                # the rows moved under the edges: stale until build_graph runs again
+                self.graph.stale = True
         return old_to_new(keep)
 
     def _prior(self):
@@ -531,23 +538,34 @@ class HipCollection:
         return {"rows": n, "dsub": int(dsub), "bytes_per_row": m, "code_bytes": n * m,
                 "centre": "mean" if isinstance(kind, str) else ("none" if kind is None else "given"), "trained": codebooks is None}
 
-    def build_graph(self, degree: int = 32, n_entry_lists: Optional[int] = None, iters: int = 10, seed: int = 0, nprobe: Optional[int] = None) -> Dict:
+    def build_graph(self, degree: int = 32, n_entry_lists: Optional[int] = None, iters: int = 10, seed: int = 0, nprobe: Optional[int] = None,
+                    maintain: bool = False, insert_ef: int = 64) -> Dict:
         """Build the k-NN graph `query(graph_ef=...)` walks (INTEGRATION.md "Graph search"; `graph.GraphIndex.build`) over this
         collection's rows (tombstoned ones included: the keep-bitmap hides them at query time and they stay bridges of the walk).
         `nprobe` (needs `build_ivf` first): the k-NN lists come from the IVF search with that many probes, an approximate build.
         Again replaces the graph.  `delete` needs nothing; `add` and `compact` make the graph stale, and `query(graph_ef=...)` then
-        raises until `build_graph` has run again (inserting rows into a built graph is out of scope).  -> {rows, degree, edges,
-        entry_lists, approximate, seconds}.  ValueError before any launch: `world > 1`, an empty collection, `nprobe` without
-        `build_ivf`, the refusals of `graph.check_build_args`."""
-        from .graph import GraphIndex, check_build_args
+        raises until `build_graph` has run again.  With `maintain=True` (a collection with `capacity=`) the graph follows the rows
+        instead (INTEGRATION.md "Keeping the graph"): `add` links the new rows in (`GraphIndex.insert`, a walk of width `insert_ef`
+        in [31, 512] a row), `compact` moves and renumbers the lists (`GraphIndex.remap`), and the graph never goes stale.
+        -> {rows, degree, edges, entry_lists, inserted, orphans, approximate, seconds}.  ValueError before any launch: `world > 1`,
+        an empty collection, `nprobe` without `build_ivf`, `maintain` without `capacity`, an `insert_ef` outside its range, the
+        refusals of `graph.check_build_args`."""
+        from .graph import KNN, MAX_EF, GraphIndex, _is_int, check_build_args
         if getattr(self, "world", 1) > 1:
             raise ValueError("build_graph needs world == 1: more than one rank is out of scope")
+        if maintain and getattr(self, "capacity", None) is None:
+            raise ValueError("build_graph(maintain=True) needs a collection built with capacity=...: without it the collection is immutable")
+        if maintain and (not _is_int(insert_ef) or not (KNN - 1 <= insert_ef <= MAX_EF)):
+            raise ValueError(f"insert_ef={insert_ef!r} must be an integer in [{KNN - 1}, {MAX_EF}]")
         ivf = getattr(self, "ivf", None) if nprobe is not None else None
         if nprobe is not None and ivf is None:
             raise ValueError("build_graph(nprobe=...) needs an IVF index: call build_ivf(n_lists) first")
         check_build_args(self.hi - self.lo, self.dim, degree, ivf.n_lists if ivf is not None and n_entry_lists is None else n_entry_lists, iters,
                          nprobe=nprobe, has_ivf=ivf is not None)
         self.graph = GraphIndex.build(self.index, degree=degree, n_entry_lists=n_entry_lists, iters=iters, seed=seed, ivf=ivf, nprobe=nprobe)
+        self._graph_maintain, self._graph_insert_ef = bool(maintain), int(insert_ef)
+        if maintain:
+            self.graph.reserve(self.capacity)
         return self.graph.summary()
 
     def get(self, ids: Sequence) -> Dict:

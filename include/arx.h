@@ -934,6 +934,45 @@ int32_t arx_graph_search_tuned(const void* corpus, int64_t n_rows, int32_t dim, 
                                int32_t max_iters, float* out_scores, int64_t* out_ids, int64_t* out_scored, int64_t* out_expanded,
                                int64_t idx_base, void* ws, int64_t ws_bytes, int32_t threads, void* stream);
 
+/* ---- Graph maintenance: link new rows into a built graph, renumber it after a compaction (csrc/graph.hip; the host layer and the numpy
+ * restatements `link_host`, `remap_host`, `insert_host` are arxiv_rag_amd/graph.py; INTEGRATION.md "Graph search", "Keeping the graph") ---
+ * arx_graph_link offers rows to the tails of other rows' neighbour lists.
+ *   corpus        device fp16 [n_rows, dim], 16-byte aligned; dim a multiple of 64, at most 8192
+ *   neighbors     device int32 [n_rows, degree], read and written; degree a multiple of 8 in 8..64
+ *   targets       device int32 [n_targets]; offer_start device int32 [n_targets + 1]; offers device int32 [n_offers], n_offers < 2^31 - 64:
+ *                 slot s offers the rows offers[offer_start[s] .. offer_start[s + 1]) to row targets[s]
+ * With H = degree / 2, an entry being valid when it lies in [0, n_rows), for every slot s with t = targets[s]:
+ *   head     neighbors[t][0 .. H) is left exactly as it is
+ *   pool     the valid entries of neighbors[t][H .. degree) and the valid rows among the slot's offers, without t and without the head's
+ *            valid entries; a row named several times is in the pool once
+ *   key      of pool row c:  order word of exact_row_score(row c, query = row t) << 32 | (0xffffffff - c), the keys of arx_graph_search:
+ *            score desc, row asc, a NaN score below every number
+ *   tail     neighbors[t][H .. degree) becomes the rows of the pool's degree - H largest keys in descending order, padded with -1
+ * A slot is skipped, its row left untouched, when t lies outside [0, n_rows), when t is not strictly greater than every t inside
+ * [0, n_rows) of the slots before it (with ascending targets: the previous slot's; so no two blocks ever write one row), or when its
+ * offer_start pair is negative, decreasing or beyond n_offers.  targets, offer_start, offers and neighbors are device data: bad values give the answer
+ * above and never an access out of range.
+ * One launch on `stream`, one block per slot, plain stores only: no atomics, no workspace.  A target's new tail depends on the corpus,
+ * its own old row and its own offers alone; the offers are taken 64 at a time and merged into the running tail, and because the tail is
+ * the top of a SET the result depends neither on that chunking nor on the launch shape.
+ * ARX_ERR_ARG before the launch, the message naming the field: degree, dim, n_rows outside 1..2^31-1, n_targets < 0 (0: nothing to do),
+ * n_offers outside the range above, a null or misaligned pointer. */
+int32_t arx_graph_link(const void* corpus, int64_t n_rows, int32_t dim, int32_t* neighbors, int32_t degree, const int32_t* targets,
+                       int32_t n_targets, const int32_t* offer_start, const int32_t* offers, int64_t n_offers, void* stream);
+/* The same with the block size chosen: threads as for arx_graph_search_tuned.  Same bits for every choice. */
+int32_t arx_graph_link_tuned(const void* corpus, int64_t n_rows, int32_t dim, int32_t* neighbors, int32_t degree, const int32_t* targets,
+                             int32_t n_targets, const int32_t* offer_start, const int32_t* offers, int64_t n_offers, int32_t threads,
+                             void* stream);
+/* arx_graph_remap renumbers a graph after a stable compaction.  neighbors: device int32 [count, degree], the kept rows already moved by
+ * arx_compact_rows (rows of 4 * degree bytes); keep, word_rank: the bitmap and the plan of arx_compact_plan over the n_old rows there
+ * were (n_old < 2^31, count <= n_old).  Every entry e is rewritten in place: a valid one (in [0, n_old)) whose keep bit is set becomes
+ * word_rank[e >> 6] + popcount(keep[e >> 6] & the bits below e & 63); any other is dropped (as is one whose new number would not lie in
+ * [0, count): a plan that is not this bitmap's).  A row's surviving entries move to its front in their old order, the rest become -1.
+ * One launch on `stream`, a wave per row, plain stores; any bit pattern in the rows is legal.  ARX_ERR_ARG: degree, n_old, count, a null
+ * pointer (count = 0: nothing to do). */
+int32_t arx_graph_remap(int32_t* neighbors, int64_t count, int32_t degree, const uint64_t* keep, const int64_t* word_rank, int64_t n_old,
+                        void* stream);
+
 /* ---- MMR diversified re-ordering of a query's search candidates (csrc/mmr.hip; the definition is INTEGRATION.md "MMR") -----------
  * arx_gather_rows: out[s] (device fp16 [count, dim]) = shard row ids[s] - idx_base where that row lies in [0, n_rows), all zeros
  * otherwise (id -1, a row another rank owns: the ranks' buffers then add up to the rows, arxiv_rag_amd/mmr.py).  shard device fp16

@@ -11,10 +11,11 @@ every returned score has the bits of `ShardIndex.search` and the order is (score
 `ShardIndex.search(allow=bitmap of C(q))`.  Which rows get scored is the only approximation; `n_candidates >= ` the visible rows is
 the exact search.
 
-`_launch` is the one place of this module that launches anything; the workspace sizes (`_workspace_bytes`, and
-`arx_ivf_workspace_bytes` for the rescore) are host arithmetic, and the rescore's launch is `ivf._launch`.  `pack_host`,
-`candidates_host` and `search_host` restate the definitions with numpy (for the tests; the product path never calls them);
-`check_args` and `check_query_with_binary` are the refusals; a tensor of the wrong kind is a ValueError too.
+`codes.launch` is the one place this module launches anything through; the workspace sizes (`_workspace_bytes`, and
+`arx_ivf_workspace_bytes` for the rescore) are host arithmetic.  What the index shares with `pq.PqIndex` is `codes.CodeIndex`: the
+lifecycle of the code array, the cached workspaces, `search` and the rescore (`codes.rescore_candidates`, whose launch is
+`ivf._launch`).  `pack_host`, `candidates_host` and `search_host` restate the definitions with numpy (for the tests; the product path
+never calls them); `check_args` and `check_query_with_binary` are the refusals; a tensor of the wrong kind is a ValueError too.
 """
 from __future__ import annotations
 
@@ -22,13 +23,9 @@ from typing import Optional
 
 import numpy as np
 
-MAX_CANDIDATES, MAX_K, MAX_DIM = 256, 32, 8192
-RESCORE_QUERIES = 1024          # queries per `arx_ivf_search` call of a rescore (one list per query, n_lists <= 4096)
+from .codes import MAX_CANDIDATES, MAX_K, RESCORE_QUERIES, CodeIndex, _is_int, check_candidate_args, check_centre, launch, rescore_host  # noqa: F401
 
-
-# ---- refusals ----------------------------------------------------------------------------------------------------------------------
-def _is_int(v) -> bool:
-    return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+MAX_DIM = 8192
 
 
 def check_dim(dim) -> None:
@@ -38,50 +35,18 @@ def check_dim(dim) -> None:
 
 def check_args(k, n_candidates, dim=None) -> None:
     """The refusals of `BinaryIndex.search` / `candidates` (k = None), each a ValueError before anything is launched."""
-    if not _is_int(n_candidates) or not (1 <= n_candidates <= MAX_CANDIDATES):
-        raise ValueError(f"n_candidates={n_candidates!r} must be an integer in [1, {MAX_CANDIDATES}]")
-    if k is not None:
-        if not _is_int(k) or not (1 <= k <= MAX_K):
-            raise ValueError(f"k={k!r} must be an integer in [1, {MAX_K}] (the search's k limit)")
-        if n_candidates < k:
-            raise ValueError(f"n_candidates={n_candidates} is below k={k}: the rescore picks its k rows among the candidates")
+    check_candidate_args(k, n_candidates)
     if dim is not None:
         check_dim(dim)
-
-
-def check_centre(centre, dim: int):
-    """`centre` as `BinaryIndex.build` takes it -> "mean", None or a float32 array [dim]; anything else is a ValueError."""
-    if centre is None or (isinstance(centre, str) and centre == "mean"):
-        return centre
-    if isinstance(centre, str):
-        raise ValueError(f"centre={centre!r} must be \"mean\", None or a float32 array [dim]")
-    c = np.asarray(centre.detach().cpu().numpy() if hasattr(centre, "detach") else centre)
-    if c.shape != (dim,) or c.dtype.kind != "f":
-        raise ValueError(f"centre must be \"mean\", None or a float array of shape ({dim},), not {c.dtype} {tuple(c.shape)}")
-    return np.ascontiguousarray(c, dtype=np.float32)
 
 
 def check_query_with_binary(binary_candidates, *, has_index: bool, per_query_filters: bool = False, hybrid_alpha=None, group_by=None,
                             min_score=None, nprobe=None, world: int = 1, n_width: int = 1, pq_candidates=None) -> None:
     """The refusals of `query(binary_candidates=...)`, `retrieve` and `search_queries`, each a ValueError naming the part, before any
-    launch.  `n_width`: the rows the search returns per query (the reranker's or MMR's candidates, else n_results)."""
-    if nprobe is not None:
-        raise ValueError("binary_candidates cannot be combined with nprobe: both choose which rows get scored")
-    if pq_candidates is not None:
-        raise ValueError("binary_candidates cannot be combined with pq_candidates: both choose which rows get scored")
-    if hybrid_alpha is not None:
-        raise ValueError("binary_candidates cannot be combined with hybrid_alpha: the BM25 keyword search has no binary codes")
-    if group_by:
-        raise ValueError("binary_candidates cannot be combined with group_by: the grouped search reads every row")
-    if min_score is not None:
-        raise ValueError("binary_candidates cannot be combined with min_score: the range search reads every row")
-    if per_query_filters:
-        raise ValueError("binary_candidates cannot be combined with per-query filter lists: the Hamming scan takes one bitmap per call")
-    if world > 1:
-        raise ValueError("binary_candidates needs world == 1: more than one rank is out of scope")
-    if not has_index:
-        raise ValueError("binary_candidates needs a binary index: call build_binary() first")
-    check_args(n_width, binary_candidates)
+    launch (`modes.check_mode`).  `n_width`: the rows the search returns per query (the reranker's or MMR's candidates, else n_results)."""
+    from .modes import check_mode
+    check_mode("binary_candidates", binary_candidates, has_index=has_index, per_query=per_query_filters, hybrid_alpha=hybrid_alpha,
+               group_by=group_by, min_score=min_score, world=world, n_width=n_width, others={"nprobe": nprobe, "pq_candidates": pq_candidates})
 
 
 # ---- the numpy restatement ---------------------------------------------------------------------------------------------------------
@@ -136,20 +101,9 @@ def candidates_host(codes, qcodes, n_candidates: int, allow=None):
 
 def search_host(X, codes, qcodes, Q, k: int, n_candidates: int, allow=None):
     """(scores f32 [nq, k], ids int64 [nq, k], count int64 [nq]): what `BinaryIndex.search` returns with idx_base = 0, bit for bit:
-    the best k of `candidates_host`'s lists by (`topics.exact_scores_host` desc, row asc), `lexsort`ed."""
-    from .topics import exact_scores_host
-    X, Q = np.asarray(X), np.asarray(Q)
+    `codes.rescore_host` of `candidates_host`'s lists."""
     cand, _, count = candidates_host(codes, qcodes, n_candidates, allow)
-    nq = Q.shape[0]
-    scores, ids = np.full((nq, k), -np.inf, np.float32), np.full((nq, k), -1, np.int64)
-    for q in range(nq):
-        rows = cand[q, :count[q]].astype(np.int64)
-        if rows.shape[0] == 0:
-            continue
-        sc = exact_scores_host(X[rows], Q[q:q + 1])[:, 0].astype(np.float32, copy=False)
-        best = np.lexsort((rows, -sc))[:k]
-        scores[q, :best.shape[0]], ids[q, :best.shape[0]] = sc[best], rows[best]
-    return scores, ids, count
+    return rescore_host(X, Q, cand, count, k)
 
 
 # ---- the device path ---------------------------------------------------------------------------------------------------------------
@@ -171,16 +125,6 @@ def _workspace_bytes(n_rows: int, nq: int, dim: int, R: int) -> int:
     return int(need)
 
 
-def _launch(name: str, device, *args):
-    """The one launch path: entry point `name` with `args` and the current stream of `device` behind them; a refusal is an
-    `ArxError` naming the field."""
-    import torch
-    from . import _lib
-    lib = _lib.load()
-    with torch.cuda.device(device):
-        _lib.check(getattr(lib, name)(*args, torch.cuda.current_stream(device).cuda_stream), name)
-
-
 def pack_device(x16, centre=None):
     """`arx_binary_pack` on the current stream: `x16` fp16 device [n, dim] (dense), `centre` f32 device [dim] or None -> int64 device
     [n, dim / 64] (the words' bits are the uint64 codes')."""
@@ -192,7 +136,7 @@ def pack_device(x16, centre=None):
         _require_tensor(centre, "centre", (torch.float32,), 1, torch.is_tensor(centre) and tuple(centre.shape) == (dim,), f" [{dim}]")
     out = torch.empty((n, dim // 64), dtype=torch.int64, device=x16.device)
     if n:
-        _launch("arx_binary_pack", x16.device, x16.data_ptr(), n, dim, None if centre is None else centre.data_ptr(), out.data_ptr())
+        launch("arx_binary_pack", x16.device, x16.data_ptr(), n, dim, None if centre is None else centre.data_ptr(), out.data_ptr())
     return out
 
 
@@ -221,101 +165,42 @@ def candidates_device(codes, qcodes, n_candidates: int, allow=None, rows_per_blo
     args = [codes.data_ptr() if n_rows else None, n_rows, W * 64, qcodes.data_ptr(), nq, None if allow is None else allow.data_ptr(), R,
             cand.data_ptr(), None if dist is None else dist.data_ptr(), count.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size()]
     if rows_per_block is None:
-        _launch("arx_binary_candidates", dev, *args)
+        launch("arx_binary_candidates", dev, *args)
     else:
-        _launch("arx_binary_candidates_tuned", dev, *args, int(rows_per_block))
+        launch("arx_binary_candidates_tuned", dev, *args, int(rows_per_block))
     return cand, dist, count
 
 
-class BinaryIndex:
+class BinaryIndex(CodeIndex):
     """The sign-bit codes of a `ShardIndex`'s rows: `codes` (int64 device [n_rows, dim / 64]) and `centre` (f32 device [dim] or None),
-    kept as given: nothing recomputes it, so answers do not depend on how a mean was reduced."""
-
-    def __init__(self, index, codes, centre):
-        self.index, self.codes, self.centre = index, codes, centre
-        self._ws = self._ws_ivf = None
+    kept as given."""
 
     @classmethod
     def build(cls, index, centre="mean") -> "BinaryIndex":
         """Pack the rows of `index`.  `centre`: "mean" (the f32 column mean of the rows, computed once here and stored), None (0) or
         an f32 array / tensor [dim].  ValueError before any launch: dim not a multiple of 64 in [64, 8192], n_rows >= 2^31, a centre
         of another shape."""
-        import torch
-        dim, n = int(index.dim), int(index.n_rows)
-        check_dim(dim)
-        if n >= 1 << 31:
-            raise ValueError(f"n_rows={n} must be below 2^31 (the candidate lists hold int32 rows)")
-        centre = check_centre(centre, dim)
-        dev = index.corpus.device
-        if isinstance(centre, str):
-            c = index.corpus[:n].mean(dim=0, dtype=torch.float32) if n else torch.zeros(dim, dtype=torch.float32, device=dev)
-        else:
-            c = None if centre is None else torch.from_numpy(centre).to(dev)
-        c = None if c is None else c.contiguous()
-        return cls(index, pack_device(index.corpus[:n], c), c)
+        check_dim(int(index.dim))
+        c = cls.device_centre(index, cls.check_build(index, centre))
+        return cls(index, pack_device(index.corpus[:int(index.n_rows)], c), c)
 
     def pack(self, x16):
         """The codes of fp16 device rows or queries [n, dim] under the index's centre."""
         return pack_device(x16.contiguous(), self.centre)
 
-    def append(self, rows, index=None) -> None:
-        """Pack `rows` (fp16 device [m, dim], the rows appended to the shard) with the kept centre; `index`: the `ShardIndex` over the
-        grown shard, where the caller made a new one."""
-        import torch
-        self.codes = torch.cat([self.codes, self.pack(rows)])
-        if index is not None:
-            self.index = index
+    encode_rows = pack
 
-    def compact(self, keep_words, word_rank, count: int, index=None) -> None:
-        """Move the kept rows' codes to the front (`arx_compact_rows`, row_bytes = dim / 8), as the shard's rows moved."""
-        import torch
-        from .mutation import compact_rows_device
-        moved = torch.zeros_like(self.codes)
-        compact_rows_device(self.codes, moved, int(self.codes.shape[0]), keep_words, word_rank)
-        self.codes = moved[:count].contiguous()
-        if index is not None:
-            self.index = index
+    def check(self, k, n_candidates) -> None:
+        check_args(k, n_candidates, int(self.index.dim))
 
-    def _workspace(self, nq: int, R: int):
-        import torch
-        need = _workspace_bytes(int(self.codes.shape[0]), nq, int(self.index.dim), int(R))
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.codes.device)
-        return self._ws
+    def _scan_bytes(self, nq: int, R: int) -> int:
+        return _workspace_bytes(int(self.codes.shape[0]), nq, int(self.index.dim), int(R))
 
     def candidates(self, q16, n_candidates: int, allow=None, rows_per_block: Optional[int] = None):
         """(cand int32 [nq, R], dist int32 [nq, R], count int64 [nq]) on the device: per query the first `n_candidates` visible rows by
         (Hamming distance asc, row asc), padded with -1; rows are local.  `allow`: the row bitmap `ShardIndex.search(allow=...)`
         takes, or None."""
-        check_args(None, n_candidates, int(self.index.dim))
-        if int(self.codes.shape[0]) != int(self.index.n_rows):
-            raise ValueError(f"the index holds {int(self.index.n_rows)} rows, the codes {int(self.codes.shape[0])}: append or compact them first")
+        self.check(None, n_candidates)
+        self._require_rows()
         return candidates_device(self.codes, self.pack(q16), int(n_candidates), allow=allow, rows_per_block=rows_per_block,
                                  ws=self._workspace(int(q16.shape[0]), n_candidates))
-
-    def search(self, q16, k: int, n_candidates: int, allow=None, rows_per_block: Optional[int] = None):
-        """(scores f32 [nq, k], ids int64 [nq, k], count int64 [nq]) on the device: the best k of every query's candidate list by
-        (exact score desc, row asc), padded with (-inf, -1); ids = local row + the index's idx_base; `count` the candidates scored.
-        Stream-ordered, no host synchronisation."""
-        import torch
-        from .ivf import _launch as ivf_launch
-        check_args(k, n_candidates, int(self.index.dim))
-        cand, _, count = self.candidates(q16, n_candidates, allow=allow, rows_per_block=rows_per_block)
-        nq, R, dev = int(q16.shape[0]), int(n_candidates), q16.device
-        scores = torch.full((nq, int(k)), float("-inf"), dtype=torch.float32, device=dev)
-        ids = torch.full((nq, int(k)), -1, dtype=torch.int64, device=dev)
-        if nq == 0 or int(self.index.n_rows) == 0:
-            return scores, ids, count
-        q16 = q16.contiguous()
-        for a in range(0, nq, RESCORE_QUERIES):                  # a query's candidates are one list: order = cand, start[q] = q R, probes[q] = {q}
-            b = min(nq, a + RESCORE_QUERIES)
-            m = b - a
-            start = torch.arange(m + 1, dtype=torch.int64, device=dev) * R
-            probes = torch.arange(m, dtype=torch.int32, device=dev)[:, None].contiguous()
-            need = self.index.lib.arx_ivf_workspace_bytes(m * R, m, m, 1, int(self.index.dim), int(k))
-            if self._ws_ivf is None or self._ws_ivf.numel() < need:
-                self._ws_ivf = torch.empty(need, dtype=torch.uint8, device=dev)
-            s, i, _ = ivf_launch(self.index.corpus, cand[a:b].reshape(-1), start, R, q16[a:b], probes, int(k), None, None, self.index.idx_base,
-                                 None, self._ws_ivf, self.index.n_rows)
-            scores[a:b], ids[a:b] = s, i
-        return scores, ids, count

@@ -69,27 +69,12 @@ def check_query_with_boost(boost_weight, *, has_prior: bool, per_query_filters: 
                            min_score=None, nprobe=None, binary_candidates=None, world: int = 1, n_width: int = 1, n_queries: int = 1,
                            max_abs_prior: float = 0.0, pq_candidates=None) -> np.ndarray:
     """The refusals of `query(boost_weight=...)`, `retrieve` and `search_queries`, each a ValueError naming the part, before any launch
-    -> the weights as float32 [n_queries].  `n_width`: the rows the search returns per query (the reranker's or MMR's candidates, else
-    n_results)."""
-    if hybrid_alpha is not None:
-        raise ValueError("boost_weight cannot be combined with hybrid_alpha: the fusion ranks by its own score")
-    if group_by:
-        raise ValueError("boost_weight cannot be combined with group_by: a boosted grouped search is out of scope")
-    if min_score is not None:
-        raise ValueError("boost_weight cannot be combined with min_score: a boosted range search is out of scope")
-    if nprobe is not None:
-        raise ValueError("boost_weight cannot be combined with nprobe: a boosted IVF search is out of scope")
-    if binary_candidates is not None:
-        raise ValueError("boost_weight cannot be combined with binary_candidates: a boosted binary-code search is out of scope")
-    if pq_candidates is not None:
-        raise ValueError("boost_weight cannot be combined with pq_candidates: a boosted product-quantised search is out of scope")
-    if per_query_filters:
-        raise ValueError("boost_weight cannot be combined with per-query filter lists: the boosted search takes one bitmap per call")
-    if world > 1:
-        raise ValueError("boost_weight needs world == 1: more than one rank is out of scope")
-    if not has_prior:
-        raise ValueError("boost_weight needs a prior: call set_boost() first")
-    return check_args(n_width, boost_weight, n_queries, max_abs_prior)
+    (`modes.check_mode`) -> the weights as float32 [n_queries].  `n_width`: the rows the search returns per query (the reranker's or
+    MMR's candidates, else n_results)."""
+    from .modes import check_mode
+    return check_mode("boost_weight", boost_weight, has_index=has_prior, per_query=per_query_filters, hybrid_alpha=hybrid_alpha,
+                      group_by=group_by, min_score=min_score, world=world, n_width=n_width, n_queries=n_queries, max_abs_prior=max_abs_prior,
+                      others={"nprobe": nprobe, "binary_candidates": binary_candidates, "pq_candidates": pq_candidates})
 
 
 # ---- the prior column ----------------------------------------------------------------------------------------------------------------

@@ -755,26 +755,24 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
     packed over the shard (`binary_centre`: "mean", the column mean of the rows, or None / "none", zero) and every query's first
     `binary_candidates` (at most 256, at least the width the search returns) visible rows by Hamming distance of the sign bits are
     rescored exactly, `where` (one dict), `where_document` and `keep_mask` applied as without it; every entry of the results then
-    carries `binary_count`, the candidates rescored.  Composes with `reranker` and `mmr_lambda`.  Not together with `nprobe`,
-    `hybrid_alpha`, `group_by_paper`, `min_score`, a per-query `where` list or more than one rank.
+    carries `binary_count`, the candidates rescored.  Composes with `reranker` and `mmr_lambda`.
     `boost_weight` with `boost_spec` (both or neither; None = nothing changes): the boosted search (INTEGRATION.md "Boosted search").
     `boost.prior_from_metadata(the chunks' metadata, boost_spec)` gives one prior per chunk, the ranking is by float32(cosine +
     float32(boost_weight * prior)) under the bitmap of `where`, `where_document` and `keep_mask`, every hit's "score" is the boosted
-    value and an added "base_score" the cosine.  ValueError (`boost.check_query_with_boost`), before anything is launched:
-    `hybrid_alpha`, `group_by_paper`, `min_score`, `nprobe`, `binary_candidates`, a per-query `where` list, more than one rank.
+    value and an added "base_score" the cosine.
     `pq_candidates` (None = nothing changes): the product-quantised search (INTEGRATION.md "Product-quantised search").  A `pq.PqIndex`
     is trained and encoded over the shard (`pq_dsub` dimensions per code byte; `pq_centre`: "mean" or None / "none") and every query's
     first `pq_candidates` (at most 256, at least the width the search returns) visible rows by the sum of its byte tables over the
     codes are rescored exactly, `where` (one dict), `where_document` and `keep_mask` applied as without it; every entry of the
-    results then carries `pq_count`, the candidates rescored.  Composes with `reranker` and `mmr_lambda`.  Not together with `nprobe`,
-    `binary_candidates`, `hybrid_alpha`, `group_by_paper`, `min_score`, `boost_weight`, a per-query `where` list or more than one rank.
+    results then carries `pq_count`, the candidates rescored.  Composes with `reranker` and `mmr_lambda`.
     `graph_ef` (None = nothing changes): the graph search (INTEGRATION.md "Graph search").  A `graph.GraphIndex` of degree
     `graph_degree` is built over the shard (exact k-NN lists, about sqrt(rows) entry lists) and every query walks it with a beam of
     `graph_ef` rows (at most 512, at least the width the search returns) from the medoids of its `graph_entries` nearest entry
     centroids, `where` (one dict), `where_document` and `keep_mask` restricting what comes back as without it; every entry of the
-    results then carries `graph_scored`, the rows scored.  Composes with `reranker` and `mmr_lambda`.  Not together with `nprobe`,
-    `binary_candidates`, `pq_candidates`, `hybrid_alpha`, `group_by_paper`, `min_score`, `boost_weight`, a per-query `where` list or
-    more than one rank."""
+    results then carries `graph_scored`, the rows scored.  Composes with `reranker` and `mmr_lambda`.
+    None of `binary_candidates`, `boost_weight`, `pq_candidates` and `graph_ef` goes together with another of them, `nprobe`,
+    `hybrid_alpha`, `group_by_paper`, `min_score`, a per-query `where` list or more than one rank: a ValueError from `modes.check_mode`
+    (the table is `modes.MODES`), before anything is launched."""
     from .retrieval import RowFilters, check_hybrid_on_device, check_shared_query, retrieve
     if keyword_build_on_device and hybrid_alpha is None:
         raise ValueError("keyword_build_on_device needs hybrid_alpha: it chooses where the BM25 keyword index is built")
@@ -789,50 +787,39 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
             raise ValueError("min_score cannot be combined with reranker here: reranking a long range list is out of scope for search_queries")
         check_range_query(top_k, ranged=True, hybrid_alpha=hybrid_alpha, mmr_lambda=mmr_lambda, group_by=group_by_paper,    # (IVF: a bitmap per query)
                           per_query_filters=isinstance(where, (list, tuple)) and nprobe is None, world=int(os.environ.get("WORLD_SIZE", "1")))
+    from functools import partial
+    from .modes import check_mode
+    # every mode refuses through `modes.check_mode` with the one context; the boost is asked first here, and what a mode builds is checked with it
+    refuse = partial(check_mode, per_query=isinstance(where, (list, tuple)), hybrid_alpha=hybrid_alpha, group_by=group_by_paper, min_score=min_score,
+                     world=int(os.environ.get("WORLD_SIZE", "1")), has_index=True,
+                     n_width=n_cand_of(reranker, rerank_top_k, mmr_lambda, mmr_fetch_k) if (reranker is not None or mmr_lambda is not None) else top_k,
+                     others={"graph_ef": graph_ef, "pq_candidates": pq_candidates, "boost_weight": boost_weight, "binary_candidates": binary_candidates,
+                             "nprobe": nprobe if nprobe is not None else ivf_lists})
     if (boost_weight is None) != (boost_spec is None):
         raise ValueError("boost_weight and boost_spec go together: the weight and the metadata key the prior comes from")
     if boost_weight is not None:
-        from .boost import check_query_with_boost, prior_from_metadata
-        check_query_with_boost(boost_weight, has_prior=True, per_query_filters=isinstance(where, (list, tuple)), hybrid_alpha=hybrid_alpha,
-                               group_by=group_by_paper, min_score=min_score, nprobe=nprobe if nprobe is not None else ivf_lists,
-                               binary_candidates=binary_candidates, world=int(os.environ.get("WORLD_SIZE", "1")),
-                               n_width=n_cand_of(reranker, rerank_top_k, mmr_lambda, mmr_fetch_k) if (reranker is not None or mmr_lambda is not None) else top_k,
-                               n_queries=len(queries), pq_candidates=pq_candidates)
+        from .boost import prior_from_metadata
+        refuse("boost_weight", boost_weight, n_queries=len(queries))
         prior_host = prior_from_metadata([c.get("metadata") or {} for c in chunks], boost_spec)      # (a bad spec or value: refused here)
     if graph_ef is not None:
-        from .graph import check_build_args as check_graph_build, check_query_with_graph
+        from .graph import check_build_args as check_graph_build
         n_entry_lists = check_graph_build(int(shard.rows.shape[0]), int(shard.rows.shape[1]), graph_degree, None, 10)
-        check_query_with_graph(graph_ef, has_index=True, n_entries=graph_entries, n_entry_lists=n_entry_lists, degree=int(graph_degree),
-                               per_query_filters=isinstance(where, (list, tuple)), hybrid_alpha=hybrid_alpha, group_by=group_by_paper,
-                               min_score=min_score, boost_weight=boost_weight, nprobe=nprobe if nprobe is not None else ivf_lists,
-                               binary_candidates=binary_candidates, pq_candidates=pq_candidates, world=int(os.environ.get("WORLD_SIZE", "1")),
-                               n_width=n_cand_of(reranker, rerank_top_k, mmr_lambda, mmr_fetch_k) if (reranker is not None or mmr_lambda is not None) else top_k)
+        refuse("graph_ef", graph_ef, n_entries=graph_entries, n_entry_lists=n_entry_lists, degree=int(graph_degree))
     if pq_candidates is not None:
-        from .pq import check_dsub, check_query_with_pq
+        from .pq import check_dsub
         if pq_centre not in (None, "none", "mean"):
             raise ValueError(f"pq_centre={pq_centre!r} must be \"mean\" or \"none\"")
-        check_query_with_pq(pq_candidates, has_index=True, per_query_filters=isinstance(where, (list, tuple)), hybrid_alpha=hybrid_alpha,
-                            group_by=group_by_paper, min_score=min_score, nprobe=nprobe if nprobe is not None else ivf_lists,
-                            binary_candidates=binary_candidates, boost_weight=boost_weight, world=int(os.environ.get("WORLD_SIZE", "1")),
-                            n_width=n_cand_of(reranker, rerank_top_k, mmr_lambda, mmr_fetch_k) if (reranker is not None or mmr_lambda is not None) else top_k)
+        refuse("pq_candidates", pq_candidates)
         check_dsub(int(shard.rows.shape[1]), pq_dsub)
     if binary_candidates is not None:
-        from .binary import check_query_with_binary
         if binary_centre not in (None, "none", "mean"):
             raise ValueError(f"binary_centre={binary_centre!r} must be \"mean\" or \"none\"")
-        check_query_with_binary(binary_candidates, has_index=True, per_query_filters=isinstance(where, (list, tuple)), hybrid_alpha=hybrid_alpha,
-                                group_by=group_by_paper, min_score=min_score, nprobe=nprobe if nprobe is not None else ivf_lists,
-                                world=int(os.environ.get("WORLD_SIZE", "1")),
-                                n_width=n_cand_of(reranker, rerank_top_k, mmr_lambda, mmr_fetch_k) if (reranker is not None or mmr_lambda is not None) else top_k,
-                                pq_candidates=pq_candidates)
+        refuse("binary_candidates", binary_candidates)
     if nprobe is not None or ivf_lists is not None:
-        from .ivf import check_build_args, check_query_with_nprobe
+        from .ivf import check_build_args
         if nprobe is None or ivf_lists is None:
             raise ValueError("nprobe and ivf_lists go together: the lists to build and how many of them a query probes")
-        check_query_with_nprobe(nprobe, has_index=True, n_lists=int(ivf_lists), per_query_filters=isinstance(where, (list, tuple)),
-                                hybrid_alpha=hybrid_alpha, group_by=group_by_paper, min_score=min_score,
-                                world=int(os.environ.get("WORLD_SIZE", "1")), n_width=top_k if min_score is not None else 1,
-                                allow_per_query_filters=True, allow_min_score=True)
+        refuse("nprobe", nprobe, n_lists=int(ivf_lists), n_width=top_k if min_score is not None else 1, let_through=("per_query", "min_score"))
         check_build_args(int(shard.rows.shape[0]), int(shard.rows.shape[1]), ivf_lists, ivf_iters, None)
     if where_on_device and where is None:
         raise ValueError("where_on_device needs where: it chooses where the where filters are evaluated")
@@ -910,14 +897,10 @@ def search_queries(model, chunks: List[Dict], shard: "ShardSink", queries: List[
         dist.all_gather_object(parts, names, group=host_group())
         names = {k: v for part in parts for k, v in part.items()}
     results = []
-    scanned_of = (lambda qi: {}) if hit.ivf_scanned is None else (lambda qi: {"ivf_scanned": int(hit.ivf_scanned[qi]),
-                                                                              **({} if hit.ivf_hits is None else {"ivf_hits": int(hit.ivf_hits[qi])})})
-    if hit.binary_count is not None:
-        scanned_of = lambda qi: {"binary_count": int(hit.binary_count[qi])}      # noqa: E731
-    if hit.pq_count is not None:
-        scanned_of = lambda qi: {"pq_count": int(hit.pq_count[qi])}              # noqa: E731
-    if hit.graph_scored is not None:
-        scanned_of = lambda qi: {"graph_scored": int(hit.graph_scored[qi])}      # noqa: E731
+    counters = {c: getattr(hit, c) for c in ("ivf_scanned", "ivf_hits", "binary_count", "pq_count", "graph_scored") if getattr(hit, c) is not None}
+
+    def scanned_of(qi):                                      # the rows the mode that ran scored (with nprobe also the hits, where counted)
+        return {c: int(v[qi]) for c, v in counters.items()}
 
     def hybrid_fields(qi, p):                                # (null, not NaN, in the JSON file)
         if hyb is None:
@@ -1293,11 +1276,12 @@ def check_ivf_args(args) -> Optional[str]:
     return None
 
 
-def _check_candidate_scan_args(args, flag: str, r, codes: str, scan: str, also=()) -> Optional[str]:
-    """The refusals the candidate-scan modes of the search step share (--binary-candidates, --pq-candidates): `r` the flag's value,
-    `codes` / `scan` the mode's words for its codes and its scan, `also` further (flag, on, why) refusals placed after --nprobe."""
-    if not (1 <= r <= 256):
-        return f"{flag} {r} must be in [1, 256]"
+def _check_candidate_scan_args(args, flag: str, r, codes: str, scan: str, also=(), limit: int = 256) -> Optional[str]:
+    """The refusals the row-choosing modes of the search step share (--binary-candidates, --pq-candidates, --graph-ef): `r` the flag's
+    value (at most `limit`), `codes` / `scan` the mode's words for what it keeps and its scan, `also` further (flag, on, why) refusals
+    placed after --nprobe."""
+    if not (1 <= r <= limit):
+        return f"{flag} {r} must be in [1, {limit}]"
     if not getattr(args, "queries", None):
         return f"{flag} needs --queries: it is a mode of the search step"
     for other, on, why in (
@@ -1356,30 +1340,11 @@ def check_graph_args(args) -> Optional[str]:
         return f"--graph-degree {degree} must be a multiple of 8 in [8, 32]"
     if not (1 <= entries <= 32):
         return f"--graph-entries {entries} must be in [1, 32]"
-    if not getattr(args, "queries", None):
-        return "--graph-ef needs --queries: it is a mode of the search step"
-    for other, on, why in (
-            ("--nprobe / --ivf-lists", getattr(args, "nprobe", None) is not None or getattr(args, "ivf_lists", None) is not None,
-             "both choose which rows get scored"),
-            ("--binary-candidates", getattr(args, "binary_candidates", None) is not None, "both choose which rows get scored"),
-            ("--pq-candidates", getattr(args, "pq_candidates", None) is not None, "both choose which rows get scored"),
-            ("--boost-key", getattr(args, "boost_key", None) is not None, "the boosted search reads every row"),
-            ("--hybrid-alpha", getattr(args, "hybrid_alpha", None) is not None, "the BM25 keyword search has no graph"),
-            ("--group-by-paper", getattr(args, "group_by_paper", False), "the grouped search reads every row"),
-            ("--min-score", getattr(args, "min_score", None) is not None, "the range search reads every row"),
-            ("--where-file", getattr(args, "where_filters", None) is not None, "the graph search takes one bitmap per call")):
-        if on:
-            return f"--graph-ef cannot be combined with {other}: {why}"
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        return "--graph-ef needs a single GPU rank: more than one rank is out of scope"
-    width = getattr(args, "top_k", 10)
-    if getattr(args, "rerank_model", None):
-        width = getattr(args, "rerank_top_k", 32)
-    elif getattr(args, "mmr_lambda", None) is not None:
-        width = getattr(args, "mmr_fetch_k", 32)
-    if ef < width:
-        return f"--graph-ef {ef} is below the {width} rows the search returns per query"
-    return None
+    return _check_candidate_scan_args(
+        args, "--graph-ef", ef, "graph", "the graph search", limit=512,
+        also=(("--binary-candidates", getattr(args, "binary_candidates", None) is not None, "both choose which rows get scored"),
+              ("--pq-candidates", getattr(args, "pq_candidates", None) is not None, "both choose which rows get scored"),
+              ("--boost-key", getattr(args, "boost_key", None) is not None, "the boosted search reads every row")))
 
 
 def boost_spec_of(args) -> Optional[Dict]:

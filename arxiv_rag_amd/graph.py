@@ -17,7 +17,8 @@ A built graph follows the rows only where that is asked for (`HipCollection.buil
 rows in (a graph search and an exact search of the batch for their candidates, then one `arx_graph_link` that offers them to the tails
 of their nearest rows' lists), `GraphIndex.remap` renumbers the graph after a compaction (`arx_graph_remap`).  `graph_link` and
 `graph_remap` are the only callers of those two entry points; `link_host`, `remap_host` and `insert_host` restate them with numpy.
-Without `maintain`, `HipCollection.add` and `compact` mark the graph stale and `build_graph` has to run again.
+`rows_added` and `rows_compacted` are what `HipCollection.add` and `compact` call: with `maintain` they insert and remap, without it they
+mark the graph stale and `build_graph` has to run again.
 """
 from __future__ import annotations
 
@@ -80,27 +81,9 @@ def check_build_args(n_rows: int, dim: int, degree, n_entry_lists, iters, nprobe
     return int(n_entry_lists)
 
 
-def check_query_with_graph(graph_ef, *, has_index: bool, stale: bool = False, n_entries=8, n_entry_lists: int = MAX_ENTRY_LISTS, degree: int = 32,
-                           per_query_filters: bool = False, hybrid_alpha=None, group_by=None, min_score=None, boost_weight=None, nprobe=None,
-                           binary_candidates=None, pq_candidates=None, world: int = 1, n_width: int = 1) -> None:
-    """The refusals of `query(graph_ef=...)`, `retrieve` and `search_queries`, each a ValueError naming the part, before any launch."""
-    for name, given in (("nprobe", nprobe is not None), ("binary_candidates", binary_candidates is not None), ("pq_candidates", pq_candidates is not None)):
-        if given:
-            raise ValueError(f"graph_ef cannot be combined with {name}: both choose which rows get scored")
-    if hybrid_alpha is not None:
-        raise ValueError("graph_ef cannot be combined with hybrid_alpha: the BM25 keyword search has no graph")
-    if group_by:
-        raise ValueError("graph_ef cannot be combined with group_by: the grouped search reads every row")
-    if min_score is not None:
-        raise ValueError("graph_ef cannot be combined with min_score: the range search reads every row")
-    if boost_weight is not None:
-        raise ValueError("graph_ef cannot be combined with boost_weight: the boosted search reads every row")
-    if per_query_filters:
-        raise ValueError("graph_ef cannot be combined with per-query filter lists: the graph search takes one bitmap per call")
-    if world > 1:
-        raise ValueError("graph_ef needs world == 1: more than one rank is out of scope")
-    if not has_index:
-        raise ValueError("graph_ef needs a graph index: call build_graph() first")
+def check_query_args(n_width, graph_ef, stale: bool = False, n_entries=8, n_entry_lists: int = MAX_ENTRY_LISTS, degree: int = 32) -> None:
+    """The refusals of a query's `graph_ef` / `graph_entries` against a graph that is there (`modes.MODES`): a stale graph, then
+    the walk's parameters at the width `n_width` the search returns."""
     if stale:
         raise ValueError("the graph index is stale: rows were added or compacted since build_graph(); run build_graph() again "
                          "(build_graph(maintain=True) keeps the graph usable across add and compact)")
@@ -112,6 +95,17 @@ def check_query_with_graph(graph_ef, *, has_index: bool, stale: bool = False, n_
         raise ValueError(f"graph_ef={graph_ef!r} must be an integer in [width, {MAX_EF}] = [{n_width}, {MAX_EF}]: it lies below k={n_width} or "
                          f"above the limit")
     check_search_args(n_width, graph_ef, max(1, min(int(graph_ef), max_iters_for(degree, n_entries))), degree, n_entries)
+
+
+def check_query_with_graph(graph_ef, *, has_index: bool, stale: bool = False, n_entries=8, n_entry_lists: int = MAX_ENTRY_LISTS, degree: int = 32,
+                           per_query_filters: bool = False, hybrid_alpha=None, group_by=None, min_score=None, boost_weight=None, nprobe=None,
+                           binary_candidates=None, pq_candidates=None, world: int = 1, n_width: int = 1) -> None:
+    """The refusals of `query(graph_ef=...)`, `retrieve` and `search_queries`, each a ValueError naming the part, before any launch
+    (`modes.check_mode`)."""
+    from .modes import check_mode
+    check_mode("graph_ef", graph_ef, has_index=has_index, per_query=per_query_filters, hybrid_alpha=hybrid_alpha, group_by=group_by,
+               min_score=min_score, world=world, n_width=n_width, stale=stale, n_entries=n_entries, n_entry_lists=n_entry_lists, degree=degree,
+               others={"boost_weight": boost_weight, "nprobe": nprobe, "binary_candidates": binary_candidates, "pq_candidates": pq_candidates})
 
 
 # ---- the numpy restatement ---------------------------------------------------------------------------------------------------------
@@ -496,7 +490,8 @@ class GraphIndex:
         self.n_entry_lists = int(self.centroids_f16.shape[0])
         self.medoid = medoid.contiguous()
         self.info = dict(info or {})
-        self.stale = False                                       # set by `HipCollection.add` / `compact`: the rows changed under the graph
+        self.stale = False                                       # set by `rows_added` / `rows_compacted`: the rows changed under the graph
+        self.maintain, self.insert_ef = False, 64                # `HipCollection.build_graph(maintain=True, insert_ef=...)`: follow the rows
         self._ws = None
         self._buf, self._spare = self.neighbors, None            # `neighbors` is the first n_rows rows of `_buf` (`reserve`)
         self.inserted = self.orphans = 0                         # totals over every `insert`
@@ -619,6 +614,23 @@ class GraphIndex:
             self.index = index
         medoid = self.index.search(self.centroids_f16, 1)[1][:, 0]
         self.medoid = torch.where(medoid >= 0, medoid - self.index.idx_base, medoid).to(torch.int32).contiguous()
+
+    def rows_added(self, lo: int, hi: int, rows, index=None) -> None:
+        """The shard grew by the rows [lo, hi) (`index`: the `ShardIndex` over it): with `maintain` they are linked in (`insert`, a walk
+        of width `insert_ef`); without, they have no edges and the graph is stale until it is built again."""
+        if not self.maintain:
+            self.stale = True
+            return
+        if index is not None:
+            self.index = index
+        self.insert(lo, hi, insert_ef=self.insert_ef)
+
+    def rows_compacted(self, keep_words, word_rank, count: int, index=None) -> None:
+        """The shard's rows moved: with `maintain` the lists move and are renumbered (`remap`); without, the graph is stale."""
+        if not self.maintain:
+            self.stale = True
+            return
+        self.remap(keep_words, word_rank, count, index=index)
 
     def entries(self, q, n_entries: int):
         """int32 device [nq, n_entries]: the medoids of every query's `n_entries` nearest entry centroids (an exact search)."""

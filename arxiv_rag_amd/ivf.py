@@ -64,19 +64,10 @@ def check_query_with_nprobe(nprobe, *, has_index: bool, n_lists: int = 0, per_qu
     `allow_per_query_filters` / `allow_min_score` (default off): `retrieve` and `search_queries`, which route such a batch through
     `IvfIndex.search_many`, pass them, and per-query filter lists / `min_score` are then let through; everything else is refused as
     without them (`HipCollection.query` does not pass them)."""
-    if per_query_filters and not allow_per_query_filters:
-        raise ValueError("nprobe cannot be combined with per-query filter lists: the IVF search takes one bitmap per call")
-    if hybrid_alpha is not None:
-        raise ValueError("nprobe cannot be combined with hybrid_alpha: the BM25 keyword search has no inverted lists of topics")
-    if group_by:
-        raise ValueError("nprobe cannot be combined with group_by: the grouped search reads every row")
-    if min_score is not None and not allow_min_score:
-        raise ValueError("nprobe cannot be combined with min_score: the range search reads every row")
-    if world > 1:
-        raise ValueError("nprobe needs world == 1: more than one rank is out of scope")
-    if not has_index:
-        raise ValueError("nprobe needs an IVF index: call build_ivf(n_lists) first")
-    check_probe_args(n_width, nprobe, n_lists)
+    from .modes import check_mode
+    check_mode("nprobe", nprobe, has_index=has_index, per_query=per_query_filters, hybrid_alpha=hybrid_alpha, group_by=group_by,
+               min_score=min_score, world=world, n_width=n_width, n_lists=n_lists,
+               let_through=("per_query",) * bool(allow_per_query_filters) + ("min_score",) * bool(allow_min_score))
 
 
 # ---- the numpy restatement ---------------------------------------------------------------------------------------------------------
@@ -260,6 +251,24 @@ class IvfIndex:
         self.labels = labels
         self.order, self.start, self.sizes = members(labels.long(), self.n_lists)
         self.max_list_rows = int(self.sizes.max().item()) if labels.shape[0] else 0
+
+    def rows_added(self, lo: int, hi: int, rows, index=None) -> None:
+        """The shard grew by `rows` (fp16 device [hi - lo, dim]): they are labelled against the kept centroids and the lists rebuilt;
+        `index`: the `ShardIndex` over the grown shard, where the caller made a new one."""
+        import torch
+        if index is not None:
+            self.index = index
+        self.set_labels(torch.cat([self.labels, label_rows(rows, self.centroids_f16)]))
+
+    def rows_compacted(self, keep_words, word_rank, count: int, index=None) -> None:
+        """The labels move as the shard's rows moved (`arx_compact_rows`, 4-byte rows) and the lists are rebuilt."""
+        import torch
+        from .mutation import compact_rows_device
+        moved = torch.zeros_like(self.labels)
+        compact_rows_device(self.labels.contiguous(), moved, int(self.labels.shape[0]), keep_words, word_rank)
+        if index is not None:
+            self.index = index
+        self.set_labels(moved[:count].contiguous())
 
     @classmethod
     def build(cls, index, n_lists: int, iters: int = 10, seed: int = 0, train_rows: Optional[int] = None) -> "IvfIndex":

@@ -11,7 +11,8 @@ row asc): sums are integers, so the list is defined bit for bit.  `search` is th
 desc, row asc); the answer equals `ShardIndex.search(allow=bitmap of C(q))`.  Which rows get scored is the only approximation;
 `n_candidates >= ` the visible rows is the exact search.
 
-`_launch` is the one place of this module that launches a kernel of the library; the rescore's launch is `ivf._launch`.  `encode_host`,
+`codes.launch` is the one place this module launches a kernel of the library through; the lifecycle of the code array, `search` and
+the rescore are `codes.CodeIndex`'s, shared with `binary.BinaryIndex` (the rescore's launch is `ivf._launch`).  `encode_host`,
 `lut_host`, `sums_host`, `candidates_host` and `search_host` restate the definitions with numpy (for the tests; the product path never
 calls them); `check_args`, `check_dsub`, `check_codebooks` and `check_query_with_pq` are the refusals; a tensor of the wrong kind is a
 ValueError too.  `train` is Lloyd's algorithm whose assign step is `arx_pq_encode`: its floats need not be reproducible; the codebooks
@@ -23,7 +24,8 @@ from typing import Optional
 
 import numpy as np
 
-from .binary import MAX_CANDIDATES, MAX_K, RESCORE_QUERIES, _is_int, _require_tensor, _visible, check_centre, check_dim
+from .binary import _require_tensor, _visible, check_dim
+from .codes import MAX_CANDIDATES, MAX_K, RESCORE_QUERIES, CodeIndex, _is_int, check_candidate_args, check_centre, launch, rescore_host  # noqa: F401
 
 N_CODES, MAX_M, DSUBS = 256, 256, (4, 8, 16, 32, 64)
 
@@ -42,13 +44,7 @@ def check_dsub(dim, dsub) -> int:
 
 def check_args(k, n_candidates, dim=None, dsub=None) -> None:
     """The refusals of `PqIndex.search` / `candidates` (k = None), each a ValueError before anything is launched."""
-    if not _is_int(n_candidates) or not (1 <= n_candidates <= MAX_CANDIDATES):
-        raise ValueError(f"n_candidates={n_candidates!r} must be an integer in [1, {MAX_CANDIDATES}]")
-    if k is not None:
-        if not _is_int(k) or not (1 <= k <= MAX_K):
-            raise ValueError(f"k={k!r} must be an integer in [1, {MAX_K}] (the search's k limit)")
-        if n_candidates < k:
-            raise ValueError(f"n_candidates={n_candidates} is below k={k}: the rescore picks its k rows among the candidates")
+    check_candidate_args(k, n_candidates)
     if dim is not None:
         check_dim(dim) if dsub is None else check_dsub(dim, dsub)
 
@@ -68,26 +64,11 @@ def check_codebooks(codebooks, dim: int, dsub: int) -> np.ndarray:
 def check_query_with_pq(pq_candidates, *, has_index: bool, per_query_filters: bool = False, hybrid_alpha=None, group_by=None, min_score=None,
                         nprobe=None, binary_candidates=None, boost_weight=None, world: int = 1, n_width: int = 1) -> None:
     """The refusals of `query(pq_candidates=...)`, `retrieve` and `search_queries`, each a ValueError naming the part, before any
-    launch.  `n_width`: the rows the search returns per query (the reranker's or MMR's candidates, else n_results)."""
-    if nprobe is not None:
-        raise ValueError("pq_candidates cannot be combined with nprobe: both choose which rows get scored")
-    if binary_candidates is not None:
-        raise ValueError("pq_candidates cannot be combined with binary_candidates: both choose which rows get scored")
-    if hybrid_alpha is not None:
-        raise ValueError("pq_candidates cannot be combined with hybrid_alpha: the BM25 keyword search has no PQ codes")
-    if group_by:
-        raise ValueError("pq_candidates cannot be combined with group_by: the grouped search reads every row")
-    if min_score is not None:
-        raise ValueError("pq_candidates cannot be combined with min_score: the range search reads every row")
-    if boost_weight is not None:
-        raise ValueError("pq_candidates cannot be combined with boost_weight: the boosted search reads every row")
-    if per_query_filters:
-        raise ValueError("pq_candidates cannot be combined with per-query filter lists: the code scan takes one bitmap per call")
-    if world > 1:
-        raise ValueError("pq_candidates needs world == 1: more than one rank is out of scope")
-    if not has_index:
-        raise ValueError("pq_candidates needs a PQ index: call build_pq() first")
-    check_args(n_width, pq_candidates)
+    launch (`modes.check_mode`).  `n_width`: the rows the search returns per query (the reranker's or MMR's candidates, else n_results)."""
+    from .modes import check_mode
+    check_mode("pq_candidates", pq_candidates, has_index=has_index, per_query=per_query_filters, hybrid_alpha=hybrid_alpha, group_by=group_by,
+               min_score=min_score, world=world, n_width=n_width,
+               others={"nprobe": nprobe, "binary_candidates": binary_candidates, "boost_weight": boost_weight})
 
 
 # ---- the numpy restatement ---------------------------------------------------------------------------------------------------------
@@ -181,20 +162,9 @@ def candidates_host(codes, lut, n_candidates: int, allow=None):
 
 def search_host(X, codes, lut, Q, k: int, n_candidates: int, allow=None):
     """(scores f32 [nq, k], ids int64 [nq, k], count int64 [nq]): what `PqIndex.search` returns with idx_base = 0, bit for bit: the
-    best k of `candidates_host`'s lists by (`topics.exact_scores_host` desc, row asc), `lexsort`ed."""
-    from .topics import exact_scores_host
-    X, Q = np.asarray(X), np.asarray(Q)
+    `codes.rescore_host` of `candidates_host`'s lists."""
     cand, _, count = candidates_host(codes, lut, n_candidates, allow)
-    nq = Q.shape[0]
-    scores, ids = np.full((nq, k), -np.inf, np.float32), np.full((nq, k), -1, np.int64)
-    for q in range(nq):
-        rows = cand[q, :count[q]].astype(np.int64)
-        if rows.shape[0] == 0:
-            continue
-        sc = exact_scores_host(X[rows], Q[q:q + 1])[:, 0].astype(np.float32, copy=False)
-        best = np.lexsort((rows, -sc))[:k]
-        scores[q, :best.shape[0]], ids[q, :best.shape[0]] = sc[best], rows[best]
-    return scores, ids, count
+    return rescore_host(X, Q, cand, count, k)
 
 
 # ---- the device path ---------------------------------------------------------------------------------------------------------------
@@ -205,16 +175,6 @@ def _workspace_bytes(n_rows: int, nq: int, dim: int, dsub: int, R: int) -> int:
     if need < 0:
         raise _lib.ArxError(f"arx_pq_candidates: unsupported shape n_rows={n_rows} nq={nq} dim={dim} dsub={dsub} n_candidates={R}")
     return int(need)
-
-
-def _launch(name: str, device, *args):
-    """The one launch path: entry point `name` with `args` and the current stream of `device` behind them; a refusal is an
-    `ArxError` naming the field."""
-    import torch
-    from . import _lib
-    lib = _lib.load()
-    with torch.cuda.device(device):
-        _lib.check(getattr(lib, name)(*args, torch.cuda.current_stream(device).cuda_stream), name)
 
 
 def _require_codebooks(codebooks, dim: int, dsub: int) -> int:
@@ -236,7 +196,7 @@ def encode_device(x16, dsub: int, centre, codebooks):
         _require_tensor(centre, "centre", (torch.float32,), 1, torch.is_tensor(centre) and tuple(centre.shape) == (dim,), f" [{dim}]")
     out = torch.empty((n, M), dtype=torch.uint8, device=x16.device)
     if n:
-        _launch("arx_pq_encode", x16.device, x16.data_ptr(), n, dim, int(dsub), None if centre is None else centre.data_ptr(),
+        launch("arx_pq_encode", x16.device, x16.data_ptr(), n, dim, int(dsub), None if centre is None else centre.data_ptr(),
                 codebooks.data_ptr(), out.data_ptr())
     return out
 
@@ -249,7 +209,7 @@ def lut_device(q16, dsub: int, codebooks):
     M = _require_codebooks(codebooks, dim, dsub)
     out = torch.empty((nq, M, N_CODES), dtype=torch.uint8, device=q16.device)
     if nq:
-        _launch("arx_pq_lut", q16.device, q16.data_ptr(), nq, dim, int(dsub), codebooks.data_ptr(), out.data_ptr())
+        launch("arx_pq_lut", q16.device, q16.data_ptr(), nq, dim, int(dsub), codebooks.data_ptr(), out.data_ptr())
     return out
 
 
@@ -281,9 +241,9 @@ def candidates_device(codes, lut, dsub: int, n_candidates: int, allow=None, rows
     args = [codes.data_ptr() if n_rows else None, n_rows, dim, int(dsub), lut.data_ptr(), nq, None if allow is None else allow.data_ptr(), R,
             cand.data_ptr(), None if sums is None else sums.data_ptr(), count.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size()]
     if rows_per_block is None:
-        _launch("arx_pq_candidates", dev, *args)
+        launch("arx_pq_candidates", dev, *args)
     else:
-        _launch("arx_pq_candidates_tuned", dev, *args, int(rows_per_block))
+        launch("arx_pq_candidates_tuned", dev, *args, int(rows_per_block))
     return cand, sums, count
 
 
@@ -322,13 +282,13 @@ def train(X16, dsub: int, centre=None, iters: int = 10, seed: int = 0, n_codes: 
     return cb
 
 
-class PqIndex:
+class PqIndex(CodeIndex):
     """The PQ codes of a `ShardIndex`'s rows: `codes` (uint8 device [n_rows, dim / dsub]), `codebooks` (f32 device [M, 256, dsub]) and
     `centre` (f32 device [dim] or None), all kept as given: nothing recomputes them."""
 
     def __init__(self, index, codes, codebooks, centre, dsub: int):
-        self.index, self.codes, self.codebooks, self.centre, self.dsub = index, codes, codebooks, centre, int(dsub)
-        self._ws = self._ws_ivf = None
+        super().__init__(index, codes, centre)
+        self.codebooks, self.dsub = codebooks, int(dsub)
 
     @classmethod
     def build(cls, index, dsub: int = 8, centre="mean", codebooks=None, train_rows: int = 65536, iters: int = 10, seed: int = 0) -> "PqIndex":
@@ -339,22 +299,15 @@ class PqIndex:
         import torch
         dim, n = int(index.dim), int(index.n_rows)
         check_dsub(dim, dsub)
-        if n >= 1 << 31:
-            raise ValueError(f"n_rows={n} must be below 2^31 (the candidate lists hold int32 rows)")
-        centre = check_centre(centre, dim)
+        centre = cls.check_build(index, centre)
         if codebooks is not None:
             codebooks = check_codebooks(codebooks, dim, dsub)
         elif n == 0:
             raise ValueError("an empty index has no rows to train the codebooks on: pass codebooks")
         elif not _is_int(train_rows) or train_rows < 1:
             raise ValueError(f"train_rows={train_rows!r} must be a positive integer")
-        dev = index.corpus.device
-        if isinstance(centre, str):
-            c = index.corpus[:n].mean(dim=0, dtype=torch.float32) if n else torch.zeros(dim, dtype=torch.float32, device=dev)
-        else:
-            c = None if centre is None else torch.from_numpy(centre).to(dev)
-        c = None if c is None else c.contiguous()
-        rows = index.corpus[:n]
+        c = cls.device_centre(index, centre)
+        dev, rows = index.corpus.device, index.corpus[:n]
         if codebooks is None:
             sample = rows
             if n > train_rows:
@@ -369,68 +322,23 @@ class PqIndex:
         """The codes of fp16 device rows [n, dim] under the index's codebooks and centre."""
         return encode_device(x16.contiguous(), self.dsub, self.centre, self.codebooks)
 
+    encode_rows = encode
+
     def lut(self, q16):
         """The byte tables of fp16 device queries [nq, dim]."""
         return lut_device(q16.contiguous(), self.dsub, self.codebooks)
 
-    def append(self, rows, index=None) -> None:
-        """Encode `rows` (fp16 device [m, dim], the rows appended to the shard) with the kept codebooks and centre; `index`: the
-        `ShardIndex` over the grown shard, where the caller made a new one."""
-        import torch
-        self.codes = torch.cat([self.codes, self.encode(rows)])
-        if index is not None:
-            self.index = index
+    def check(self, k, n_candidates) -> None:
+        check_args(k, n_candidates, int(self.index.dim), self.dsub)
 
-    def compact(self, keep_words, word_rank, count: int, index=None) -> None:
-        """Move the kept rows' codes to the front (`arx_compact_rows`, row_bytes = M), as the shard's rows moved."""
-        import torch
-        from .mutation import compact_rows_device
-        moved = torch.zeros_like(self.codes)
-        compact_rows_device(self.codes, moved, int(self.codes.shape[0]), keep_words, word_rank)
-        self.codes = moved[:count].contiguous()
-        if index is not None:
-            self.index = index
-
-    def _workspace(self, nq: int, R: int):
-        import torch
-        need = _workspace_bytes(int(self.codes.shape[0]), nq, int(self.index.dim), self.dsub, int(R))
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.codes.device)
-        return self._ws
+    def _scan_bytes(self, nq: int, R: int) -> int:
+        return _workspace_bytes(int(self.codes.shape[0]), nq, int(self.index.dim), self.dsub, int(R))
 
     def candidates(self, q16, n_candidates: int, allow=None, rows_per_block: Optional[int] = None):
         """(cand int32 [nq, R], sum int32 [nq, R], count int64 [nq]) on the device: per query the first `n_candidates` visible rows by
         (table sum desc, row asc), padded with -1; rows are local.  `allow`: the row bitmap `ShardIndex.search(allow=...)` takes, or
         None."""
-        check_args(None, n_candidates, int(self.index.dim), self.dsub)
-        if int(self.codes.shape[0]) != int(self.index.n_rows):
-            raise ValueError(f"the index holds {int(self.index.n_rows)} rows, the codes {int(self.codes.shape[0])}: append or compact them first")
+        self.check(None, n_candidates)
+        self._require_rows()
         return candidates_device(self.codes, self.lut(q16), self.dsub, int(n_candidates), allow=allow, rows_per_block=rows_per_block,
                                  ws=self._workspace(int(q16.shape[0]), n_candidates))
-
-    def search(self, q16, k: int, n_candidates: int, allow=None, rows_per_block: Optional[int] = None):
-        """(scores f32 [nq, k], ids int64 [nq, k], count int64 [nq]) on the device: the best k of every query's candidate list by
-        (exact score desc, row asc), padded with (-inf, -1); ids = local row + the index's idx_base; `count` the candidates scored.
-        Stream-ordered, no host synchronisation."""
-        import torch
-        from .ivf import _launch as ivf_launch
-        check_args(k, n_candidates, int(self.index.dim), self.dsub)
-        cand, _, count = self.candidates(q16, n_candidates, allow=allow, rows_per_block=rows_per_block)
-        nq, R, dev = int(q16.shape[0]), int(n_candidates), q16.device
-        scores = torch.full((nq, int(k)), float("-inf"), dtype=torch.float32, device=dev)
-        ids = torch.full((nq, int(k)), -1, dtype=torch.int64, device=dev)
-        if nq == 0 or int(self.index.n_rows) == 0:
-            return scores, ids, count
-        q16 = q16.contiguous()
-        for a in range(0, nq, RESCORE_QUERIES):                  # a query's candidates are one list: order = cand, start[q] = q R, probes[q] = {q}
-            b = min(nq, a + RESCORE_QUERIES)
-            m = b - a
-            start = torch.arange(m + 1, dtype=torch.int64, device=dev) * R
-            probes = torch.arange(m, dtype=torch.int32, device=dev)[:, None].contiguous()
-            need = self.index.lib.arx_ivf_workspace_bytes(m * R, m, m, 1, int(self.index.dim), int(k))
-            if self._ws_ivf is None or self._ws_ivf.numel() < need:
-                self._ws_ivf = torch.empty(need, dtype=torch.uint8, device=dev)
-            s, i, _ = ivf_launch(self.index.corpus, cand[a:b].reshape(-1), start, R, q16[a:b], probes, int(k), None, None, self.index.idx_base,
-                                 None, self._ws_ivf, self.index.n_rows)
-            scores[a:b], ids[a:b] = s, i
-        return scores, ids, count

@@ -259,64 +259,45 @@ def retrieve(index, q, filters: RowFilters, n_results: int, *, n_candidates: int
     (a float or one per query; the width is the top-k search's, at most 32) the batch is one
     `IvfIndex.search_many` call whatever the number of distinct filters: only rows at or above the threshold come back, `ivf_hits`
     holds their exact number per query (without `min_score`: the rows scored) and, with `min_score`, `truncated` is
-    `ivf_hits > width`.  ValueError (`ivf.check_query_with_nprobe`): `hybrid_alpha`, `grouped`, `world > 1`, no `ivf`, a width above
-    32.
+    `ivf_hits > width`.
     `binary_candidates` (None = nothing changes) with `binary` (a `binary.BinaryIndex` over `index`): the binary-code search
     (INTEGRATION.md "Binary-code search"): every query's first `binary_candidates` visible rows by (Hamming distance of the sign bits,
     row), under the one bitmap of `where`, `where_document` and the keep-mask, rescored exactly; `binary_count` holds the candidates
-    rescored.  MMR and a reranker consume the list as any other.  ValueError (`binary.check_query_with_binary`): `nprobe`,
-    `hybrid_alpha`, `grouped`, `min_score`, per-query filter lists, `world > 1`, no `binary`, `binary_candidates` outside
-    [width, 256], a width above 32.
+    rescored.  MMR and a reranker consume the list as any other.  `binary_candidates` lies in [width, 256].
     `boost_weight` (None = nothing changes; a number or one per query) with `prior` (device f32 [rows of `index`]) and
     `max_abs_prior` (its largest |finite value|, None = measured): the boosted search (INTEGRATION.md "Boosted search"): the exact
     top rows by cosine + weight * prior under the one bitmap of `where`, `where_document` and the keep-mask
     (`ShardIndex.search_boosted`); `scores` holds the boosted values and `base` the cosines of the same rows, in the same order
-    (MMR's pick order included).  MMR and a reranker consume the list as any other.  ValueError (`boost.check_query_with_boost`):
-    `hybrid_alpha`, `grouped`, `min_score`, `nprobe`, `binary_candidates`, per-query filter lists, `world > 1`, no `prior`, a weight
-    that is not finite, a width above 32.
+    (MMR's pick order included).  MMR and a reranker consume the list as any other.  The weight must be finite.
     `pq_candidates` (None = nothing changes) with `pq` (a `pq.PqIndex` over `index`): the product-quantised search (INTEGRATION.md
     "Product-quantised search"): every query's first `pq_candidates` visible rows by (sum of its byte tables over the row's PQ code,
     row), under the one bitmap of `where`, `where_document` and the keep-mask, rescored exactly; `pq_count` holds the candidates
-    rescored.  MMR and a reranker consume the list as any other.  ValueError (`pq.check_query_with_pq`): `nprobe`,
-    `binary_candidates`, `hybrid_alpha`, `grouped`, `min_score`, `boost_weight`, per-query filter lists, `world > 1`, no `pq`,
-    `pq_candidates` outside [width, 256], a width above 32.
+    rescored.  MMR and a reranker consume the list as any other.  `pq_candidates` lies in [width, 256].
     `graph_ef` (None = nothing changes) with `graph` (a `graph.GraphIndex` over `index`) and `graph_entries`: the graph search
     (INTEGRATION.md "Graph search"): a beam search of width `graph_ef` over the k-NN graph from the medoids of every query's
     `graph_entries` nearest entry centroids; the one bitmap of `where`, `where_document` and the keep-mask restricts what comes back,
-    not where the walk goes; `graph_scored` holds the rows scored.  MMR and a reranker consume the list as any other.  ValueError
-    (`graph.check_query_with_graph`): `nprobe`, `binary_candidates`, `pq_candidates`, `hybrid_alpha`, `grouped`, `min_score`,
-    `boost_weight`, per-query filter lists, `world > 1`, no `graph` or a stale one, `graph_ef` outside [width, 512], a width above 32."""
+    not where the walk goes; `graph_scored` holds the rows scored.  MMR and a reranker consume the list as any other.  `graph_ef`
+    lies in [width, 512]; a stale graph is refused.
+    ValueError for each of these five modes (`modes.check_modes`, before anything is launched): what `modes.MODES` says it cannot be
+    combined with (each other, `hybrid_alpha`, `grouped`, `min_score` and per-query filter lists, the last two let through for
+    `nprobe`), `world > 1`, its index missing, a width above 32."""
     import torch
     from .filter_sets import is_per_query
+    from .modes import check_modes
     nq = q.shape[0]
     k = n_candidates if (reranked or hybrid_alpha is not None or mmr_lambda is not None) else n_results
     per_query = is_per_query(where) or is_per_query(where_document)
-    if graph_ef is not None:
-        from .graph import check_query_with_graph
-        check_query_with_graph(graph_ef, has_index=graph is not None, stale=getattr(graph, "stale", False), n_entries=graph_entries,
-                               n_entry_lists=getattr(graph, "n_entry_lists", 0), degree=getattr(graph, "degree", 32), per_query_filters=per_query,
-                               hybrid_alpha=hybrid_alpha, group_by=grouped, min_score=min_score, boost_weight=boost_weight, nprobe=nprobe,
-                               binary_candidates=binary_candidates, pq_candidates=pq_candidates, world=world, n_width=k)
-    if pq_candidates is not None:
-        from .pq import check_query_with_pq
-        check_query_with_pq(pq_candidates, has_index=pq is not None, per_query_filters=per_query, hybrid_alpha=hybrid_alpha, group_by=grouped,
-                            min_score=min_score, nprobe=nprobe, binary_candidates=binary_candidates, boost_weight=boost_weight, world=world,
-                            n_width=k)
-    if boost_weight is not None:
-        from .boost import check_query_with_boost
-        boost_weight = check_query_with_boost(boost_weight, has_prior=prior is not None, per_query_filters=per_query, hybrid_alpha=hybrid_alpha,
-                                              group_by=grouped, min_score=min_score, nprobe=nprobe, binary_candidates=binary_candidates,
-                                              world=world, n_width=k, n_queries=nq, max_abs_prior=0.0 if max_abs_prior is None else max_abs_prior,
-                                              pq_candidates=pq_candidates)
-    if binary_candidates is not None:
-        from .binary import check_query_with_binary
-        check_query_with_binary(binary_candidates, has_index=binary is not None, per_query_filters=per_query, hybrid_alpha=hybrid_alpha,
-                                group_by=grouped, min_score=min_score, nprobe=nprobe, world=world, n_width=k, pq_candidates=pq_candidates)
-    if nprobe is not None:
-        from .ivf import check_query_with_nprobe
-        check_query_with_nprobe(nprobe, has_index=ivf is not None, n_lists=getattr(ivf, "n_lists", 0), per_query_filters=per_query,
-                                hybrid_alpha=hybrid_alpha, group_by=grouped, min_score=min_score, world=world, n_width=k,
-                                allow_per_query_filters=True, allow_min_score=True)
+    weights = check_modes(
+        {"graph_ef": graph_ef, "pq_candidates": pq_candidates, "boost_weight": boost_weight, "binary_candidates": binary_candidates,
+         "nprobe": nprobe},
+        {"graph_ef": dict(has_index=graph is not None, stale=getattr(graph, "stale", False), n_entries=graph_entries,
+                          n_entry_lists=getattr(graph, "n_entry_lists", 0), degree=getattr(graph, "degree", 32)),
+         "pq_candidates": dict(has_index=pq is not None),
+         "boost_weight": dict(has_index=prior is not None, n_queries=nq, max_abs_prior=0.0 if max_abs_prior is None else max_abs_prior),
+         "binary_candidates": dict(has_index=binary is not None),
+         "nprobe": dict(has_index=ivf is not None, n_lists=getattr(ivf, "n_lists", 0), let_through=("per_query", "min_score"))},
+        per_query=per_query, hybrid_alpha=hybrid_alpha, group_by=grouped, min_score=min_score, world=world, n_width=k)
+    boost_weight = boost_weight if weights is None else weights
     out = Retrieved(None, None)
     kw_filter_of = None
     on_device = hybrid_alpha is not None and bool(hybrid_on_device)

@@ -320,20 +320,8 @@ class HipCollection:
         if prior_new is not None:
             self._boost_buf[n:n + m] = torch.from_numpy(prior_new).to(dev)
             self._measure_prior((n, n + m))
-        if getattr(self, "ivf", None) is not None:               # the new rows labelled against the kept centroids; the lists rebuilt
-            from .ivf import label_rows
-            self.ivf.index = self.index
-            self.ivf.set_labels(torch.cat([self.ivf.labels, label_rows(self._buf[n:n + m], self.ivf.centroids_f16)]))
-        if getattr(self, "binary", None) is not None:            # the new rows packed with the kept centre
-            self.binary.append(self._buf[n:n + m], index=self.index)
-        if getattr(self, "pq", None) is not None:                # the new rows encoded with the kept codebooks and centre
-            self.pq.append(self._buf[n:n + m], index=self.index)
-        if getattr(self, "graph", None) is not None:
-            if getattr(self, "_graph_maintain", False):          # the new rows are linked into the graph (`GraphIndex.insert`)
-                self.graph.index = self.index
-                self.graph.insert(n, n + m, insert_ef=self._graph_insert_ef)
-            else:                                                # the new rows have no edges: the graph is stale until build_graph runs again
-                self.graph.stale = True
+        for derived in self._derived():                          # labelled, packed, encoded, linked in (or the graph goes stale)
+            derived.rows_added(n, n + m, self._buf[n:n + m], index=self.index)
         if self._deleted is not None:
             self._deleted = np.concatenate([self._deleted, np.zeros(m, bool)])
         if self.dedup_threshold is not None:
@@ -414,10 +402,6 @@ class HipCollection:
             moved = torch.zeros_like(self._boost_buf)
             compact_rows_device(self._boost_buf, moved, n, self._keep, word_rank)
             self._boost_buf = moved
-        ivf_labels = None
-        if getattr(self, "ivf", None) is not None:               # the labels move as `group_of` moves: 4-byte rows
-            ivf_labels = torch.zeros_like(self.ivf.labels)
-            compact_rows_device(self.ivf.labels.contiguous(), ivf_labels, n, self._keep, word_rank)
         keep_words = self._keep
         self.metadata = [md for md, k in zip(self.metadata, keep.tolist()) if k]
         self._ids = build_id_map(self.metadata)
@@ -430,19 +414,14 @@ class HipCollection:
         self._make_index()
         if getattr(self, "_boost_buf", None) is not None:      # (the survivors' maximum: what a collection built from them measures)
             self._measure_prior()
-        if ivf_labels is not None:
-            self.ivf.index = self.index
-            self.ivf.set_labels(ivf_labels[:count].contiguous())
-        if getattr(self, "binary", None) is not None:            # the codes move as the rows moved: dim / 8-byte rows
-            self.binary.compact(keep_words, word_rank, count, index=self.index)
-        if getattr(self, "pq", None) is not None:                # the PQ codes move as the rows moved: dim / dsub-byte rows
-            self.pq.compact(keep_words, word_rank, count, index=self.index)
-        if getattr(self, "graph", None) is not None:
-            if getattr(self, "_graph_maintain", False):          # the lists move as the rows moved and are renumbered: 4 * degree-byte rows
-                self.graph.remap(keep_words, word_rank, count, index=self.index)
-            else:                                                # the rows moved under the edges: stale until build_graph runs again
-                self.graph.stale = True
+        for derived in self._derived():                          # what each keeps per row moves as the rows moved, by the old keep-bitmap
+            derived.rows_compacted(keep_words, word_rank, count, index=self.index)
         return old_to_new(keep)
+
+    def _derived(self):
+        """The indexes built over the rows that follow them through `add` and `compact` (`rows_added`, `rows_compacted`), in the order
+        they are told."""
+        return [ix for ix in (getattr(self, name, None) for name in ("ivf", "binary", "pq", "graph")) if ix is not None]
 
     def _prior(self):
         """The prior of the rows there are now (a view of the capacity-sized buffer), or None."""
@@ -563,7 +542,7 @@ class HipCollection:
         check_build_args(self.hi - self.lo, self.dim, degree, ivf.n_lists if ivf is not None and n_entry_lists is None else n_entry_lists, iters,
                          nprobe=nprobe, has_ivf=ivf is not None)
         self.graph = GraphIndex.build(self.index, degree=degree, n_entry_lists=n_entry_lists, iters=iters, seed=seed, ivf=ivf, nprobe=nprobe)
-        self._graph_maintain, self._graph_insert_ef = bool(maintain), int(insert_ef)
+        self.graph.maintain, self.graph.insert_ef = bool(maintain), int(insert_ef)
         if maintain:
             self.graph.reserve(self.capacity)
         return self.graph.summary()
@@ -772,31 +751,25 @@ class HipCollection:
         (`ivf.IvfIndex.search`, `arx_ivf_search`): the exact top rows among those, with the score bits and the order of the exact
         search, and an added `ivf_scanned` list holds the rows scored per query.  `nprobe = n_lists` is the exact search.  Composes
         with a single `where`, `where_document` and the dedup and tombstone keep-bitmap (one bitmap per call), and with `reranker` and
-        `mmr_lambda`, which consume the candidate list (`n_candidates <= 32`).  ValueError, naming the part: per-query filter lists,
-        `hybrid_alpha`, `group_by`, `min_score`, `world > 1`, or a collection without `build_ivf`.
+        `mmr_lambda`, which consume the candidate list (`n_candidates <= 32`).
         `binary_candidates` (an integer R in [width, 256], the width being what the search returns: `n_candidates` with `reranker`
         or `mmr_lambda`, else `n_results`; None = nothing changes; needs `build_binary` first): the binary-code search
         (INTEGRATION.md "Binary-code search").  Every row is ranked by the Hamming distance between its sign bits and the query's
         (`arx_binary_candidates`), and the first R visible rows by (distance, row) are rescored exactly: the exact top rows among
         those, with the score bits and the order of the exact search, and an added `binary_count` list holds the candidates rescored
         per query.  Composes with a single `where`, `where_document` and the dedup and tombstone keep-bitmap (one bitmap per call),
-        and with `reranker` and `mmr_lambda`, which consume the list (`n_candidates <= 32`).  ValueError, naming the part: `nprobe`,
-        `hybrid_alpha`, `group_by`, `min_score`, per-query filter lists, `world > 1`, or a collection without `build_binary`.
+        and with `reranker` and `mmr_lambda`, which consume the list (`n_candidates <= 32`).
         `boost_weight` (a float, or one per query; None = nothing changes; needs `set_boost` first): the boosted search (INTEGRATION.md
         "Boosted search"): the exact top rows by float32(cosine + float32(weight * prior)) under the one bitmap of `where`,
         `where_document` and the keep-bitmap.  `scores` holds the boosted values, `distances` follow them as they follow the cosine
         otherwise, and an added `base_scores` list holds the cosines of the same rows.  `reranker` and `mmr_lambda` consume the list
-        as any other.  Refused with a ValueError (`boost.check_query_with_boost`) before anything is launched: `hybrid_alpha`,
-        `group_by`, `min_score`, `nprobe`, `binary_candidates`, per-query filter lists, `world > 1`, a weight that is not finite, or a
-        collection without `set_boost`.
+        as any other.  A weight that is not finite is a ValueError.
         `pq_candidates` (an integer R in [width, 256], the width as for `binary_candidates`; None = nothing changes; needs `build_pq`
         first): the product-quantised search (INTEGRATION.md "Product-quantised search").  Every row is ranked by the sum of the
         query's byte look-up tables over its PQ code (`arx_pq_candidates`), and the first R visible rows by (sum desc, row) are
         rescored exactly: the exact top rows among those, with the score bits and the order of the exact search, and an added
         `pq_count` list holds the candidates rescored per query.  Composes with a single `where`, `where_document` and the dedup and
-        tombstone keep-bitmap (one bitmap per call), and with `reranker` and `mmr_lambda` (`n_candidates <= 32`).  ValueError, naming
-        the part: `nprobe`, `binary_candidates`, `hybrid_alpha`, `group_by`, `min_score`, `boost_weight`, per-query filter lists,
-        `world > 1`, or a collection without `build_pq`.
+        tombstone keep-bitmap (one bitmap per call), and with `reranker` and `mmr_lambda` (`n_candidates <= 32`).
         `graph_ef` (an integer L in [width, 512], the width as for `binary_candidates`; None = nothing changes; needs `build_graph`
         first) with `graph_entries` (E in [1, 32], at most the graph's entry lists): the graph search (INTEGRATION.md "Graph
         search").  Every query walks the k-NN graph from the medoids of its E nearest entry centroids with a beam of L rows
@@ -804,50 +777,34 @@ class HipCollection:
         approximation, the scores and the order are the exact search's, and an added `graph_scored` list holds the rows scored per
         query.  Composes with a single `where`, `where_document` and the dedup and tombstone keep-bitmap (one bitmap per call; it
         restricts what comes back, hidden rows stay bridges of the walk), and with `reranker` and `mmr_lambda`
-        (`n_candidates <= 32`).  ValueError, naming the part: `nprobe`, `binary_candidates`, `pq_candidates`, `hybrid_alpha`,
-        `group_by`, `min_score`, `boost_weight`, per-query filter lists, `world > 1`, a collection without `build_graph`, or one
-        whose graph is stale after `add` or `compact`."""
+        (`n_candidates <= 32`).  A graph that is stale after `add` or `compact` is a ValueError.
+        What each of these five modes cannot be combined with (each other, `hybrid_alpha`, `group_by`, `min_score`, per-query filter
+        lists, `world > 1`, a collection without its index) is `modes.MODES`; `modes.check_modes` refuses, with a ValueError naming the
+        part, before the queries are encoded or anything is launched."""
         import torch
         from .filter_sets import is_per_query
         from .grouping import check_grouped_query
+        from .modes import MODES, check_modes
         from .ranging import RERANK_BATCH, check_range_query
         from .retrieval import check_hybrid_on_device, check_shared_query, retrieve
         per_query = is_per_query(where) or is_per_query(where_document)
-        if graph_ef is not None:
-            from .graph import check_query_with_graph
-            graph = getattr(self, "graph", None)
-            check_query_with_graph(graph_ef, has_index=graph is not None, stale=getattr(graph, "stale", False), n_entries=graph_entries,
-                                   n_entry_lists=getattr(graph, "n_entry_lists", 0), degree=getattr(graph, "degree", 32),
-                                   per_query_filters=per_query, hybrid_alpha=hybrid_alpha, group_by=group_by, min_score=min_score,
-                                   boost_weight=boost_weight, nprobe=nprobe, binary_candidates=binary_candidates, pq_candidates=pq_candidates,
-                                   world=getattr(self, "world", 1),
-                                   n_width=n_candidates if (reranker is not None or mmr_lambda is not None) else n_results)
-        if pq_candidates is not None:
-            from .pq import check_query_with_pq
-            check_query_with_pq(pq_candidates, has_index=getattr(self, "pq", None) is not None, per_query_filters=per_query,
-                                hybrid_alpha=hybrid_alpha, group_by=group_by, min_score=min_score, nprobe=nprobe,
-                                binary_candidates=binary_candidates, boost_weight=boost_weight, world=getattr(self, "world", 1),
-                                n_width=n_candidates if (reranker is not None or mmr_lambda is not None) else n_results)
-        if boost_weight is not None:
-            from .boost import check_query_with_boost
-            nq_given = None if query_embeddings is None else (1 if np.ndim(query_embeddings) == 1 else len(query_embeddings))
-            nq_given = nq_given if nq_given is not None else (len(query_texts) if query_texts is not None else 1)
-            check_query_with_boost(boost_weight, has_prior=self._prior() is not None, per_query_filters=per_query,
-                                   hybrid_alpha=hybrid_alpha, group_by=group_by, min_score=min_score, nprobe=nprobe,
-                                   binary_candidates=binary_candidates, world=getattr(self, "world", 1),
-                                   n_width=n_candidates if (reranker is not None or mmr_lambda is not None) else n_results,
-                                   n_queries=nq_given, max_abs_prior=getattr(self, "_boost_max", 0.0), pq_candidates=pq_candidates)
-        if binary_candidates is not None:
-            from .binary import check_query_with_binary
-            check_query_with_binary(binary_candidates, has_index=getattr(self, "binary", None) is not None, per_query_filters=per_query,
-                                    hybrid_alpha=hybrid_alpha, group_by=group_by, min_score=min_score, nprobe=nprobe, world=getattr(self, "world", 1),
-                                    n_width=n_candidates if (reranker is not None or mmr_lambda is not None) else n_results,
-                                    pq_candidates=pq_candidates)
-        if nprobe is not None:
-            from .ivf import check_query_with_nprobe
-            ivf = getattr(self, "ivf", None)
-            check_query_with_nprobe(nprobe, has_index=ivf is not None, n_lists=getattr(ivf, "n_lists", 0), per_query_filters=per_query,
-                                    hybrid_alpha=hybrid_alpha, group_by=group_by, min_score=min_score, world=getattr(self, "world", 1))
+        graph, ivf = getattr(self, "graph", None), getattr(self, "ivf", None)
+        nq_given = 1
+        if boost_weight is not None and query_embeddings is not None:
+            nq_given = 1 if np.ndim(query_embeddings) == 1 else len(query_embeddings)
+        elif boost_weight is not None and query_texts is not None:
+            nq_given = len(query_texts)
+        check_modes(                                             # (nprobe: its width is `retrieve`'s to check, which asks all of this again)
+            {"graph_ef": graph_ef, "pq_candidates": pq_candidates, "boost_weight": boost_weight, "binary_candidates": binary_candidates,
+             "nprobe": nprobe},
+            {"graph_ef": dict(has_index=graph is not None, stale=getattr(graph, "stale", False), n_entries=graph_entries,
+                              n_entry_lists=getattr(graph, "n_entry_lists", 0), degree=getattr(graph, "degree", 32)),
+             "pq_candidates": dict(has_index=getattr(self, "pq", None) is not None),
+             "boost_weight": dict(has_index=self._prior() is not None, n_queries=nq_given, max_abs_prior=getattr(self, "_boost_max", 0.0)),
+             "binary_candidates": dict(has_index=getattr(self, "binary", None) is not None),
+             "nprobe": dict(has_index=ivf is not None, n_lists=getattr(ivf, "n_lists", 0), n_width=1)},
+            per_query=per_query, hybrid_alpha=hybrid_alpha, group_by=group_by, min_score=min_score, world=getattr(self, "world", 1),
+            n_width=n_candidates if (reranker is not None or mmr_lambda is not None) else n_results)
         on_device = hybrid_alpha is not None and getattr(self, "hybrid_on_device", False)
         check_range_query(n_results, ranged=min_score is not None, reranker=reranker, n_candidates=n_candidates, hybrid_alpha=hybrid_alpha,
                           mmr_lambda=mmr_lambda, group_by=group_by, per_query_filters=per_query, world=getattr(self, "world", 1))
@@ -935,14 +892,9 @@ class HipCollection:
             out["group_sizes"] = [[int(n) for n, v in zip(hit.group_sizes[qi], hit.groups[qi]) if v >= 0] for qi in range(q.shape[0])]
         if hit.truncated is not None:
             out["truncated"] = hit.truncated
-        if hit.ivf_scanned is not None:
-            out["ivf_scanned"] = [int(v) for v in hit.ivf_scanned]
-        if hit.binary_count is not None:
-            out["binary_count"] = [int(v) for v in hit.binary_count]
-        if hit.pq_count is not None:
-            out["pq_count"] = [int(v) for v in hit.pq_count]
-        if hit.graph_scored is not None:
-            out["graph_scored"] = [int(v) for v in hit.graph_scored]
+        for counter in (m.counter for m in MODES.values() if m.counter is not None):      # the rows the mode that ran scored, per query
+            if getattr(hit, counter) is not None:
+                out[counter] = [int(v) for v in getattr(hit, counter)]
         if base is not None:
             out["base_scores"] = [base[qi][i[qi] >= 0].tolist() for qi in range(q.shape[0])]
         if hit.mmr is not None:

@@ -1,5 +1,5 @@
-// Exact "R largest 64-bit keys" lists in LDS, written once for the candidate scans (binary.hip: Hamming distances over sign bits;
-// pq.hip: byte-table sums over product-quantiser codes).  A key is  high word << 32 | (0xffffffff - row):  larger is better, distinct
+// Exact "R largest 64-bit keys" lists in LDS and the candidate scan over them, written once for binary.hip (Hamming distances over sign
+// bits) and pq.hip (byte-table sums over product-quantiser codes).  A key is  high word << 32 | (0xffffffff - row):  larger is better, distinct
 // for distinct rows, never 0 (0 = an empty slot; rows are below 2^31).  What the high word means is the caller's business.
 //   KeyLists   NL lists of KEY_CAP keys, each with an integer slot counter and a threshold (0 until the list has been cut once;
 //              afterwards its R-th largest key).
@@ -8,8 +8,12 @@
 //              R largest by a block-wide bitonic sort (bm25.hip's, over all those lists in the same stages).  A key at or below the R-th
 //              largest of keys already seen is not among the R largest of all, so a list cut at the end holds the exact R largest keys
 //              of everything offered to it, sorted, whatever the order of the appends.
+//   key_scan_kernel  block (stretch p of rows_per_block rows, tile t of Code::QT queries), four waves, the tile's query-side data in LDS.
+//              A round gives every lane one row (a wave's 64 rows: one contiguous span of the code array and one word of `allow`), read
+//              once per query tile; its QT high words stay in registers.  The block's final lists -> part_k [parts][nq][R] (0 = none).
 //   key_merge_kernel  one block per query over its parts * R keys of partial lists, any number of them, through the same list and cut
 //              -> out_cand (the rows), out_hi (the high word, or 0x7fffffff - it) and out_count.
+//   key_scan   the host driver of a call: slices of KEY_QBATCH queries, each one scan launch (none over an empty shard) and one merge.
 // Integer work only, no global atomics.  Every kernel that uses these runs KEY_NT threads.
 #pragma once
 #include "arx_common.h"
@@ -106,6 +110,70 @@ __global__ __launch_bounds__(KEY_NT) void key_merge_kernel(const unsigned long l
     if (tid == 0) out_count[q] = sm.cnt[0];
 }
 
+// The scan.  `Code` is what differs between the codes.  The kernel builds it as Code{codes, width, qdata}, so that the pointers stay
+// its own __restrict__ arguments: a Code declares exactly these three members first, in this order, both arrays of one element type.
+//   Word, QT                  that element type; queries of a tile (compile time)
+//   lds()                     the block's LDS as a handle, `.lists` (KeyLists<QT>&) and the Code's query-side storage; it goes on by value
+//                             (by reference its fields are reloaded after every LDS store until inlining, and the loops differ)
+//   stage(lds, q0, nl)        the whole block brings the data of queries q0 .. q0 + nl - 1 into that storage (zeros for l >= nl)
+//   high_words(lds, row, h)   a lane reads the code of `row` and writes the QT high words of its keys (larger is better)
+template <typename Code>
+__global__ __launch_bounds__(KEY_NT) void key_scan_kernel(const typename Code::Word* __restrict__ codes, int64_t n_rows, int width,
+                                                          const typename Code::Word* __restrict__ qdata, int nq, const uint64_t* __restrict__ allow,
+                                                          int R, int64_t rpb, unsigned long long* __restrict__ part_k) {
+    constexpr int QT = Code::QT;
+    const Code code{codes, width, qdata};
+    const auto lds = code.lds();
+    KeyLists<QT>& sm = lds.lists;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int q0 = blockIdx.y * QT;
+    const int nl = nq - q0 < QT ? nq - q0 : QT;               // the tile's queries
+    code.stage(lds, q0, nl);
+    if (tid < QT) { sm.cnt[tid] = 0; sm.thr[tid] = 0ull; }
+    __syncthreads();
+    const int64_t lo = (int64_t)blockIdx.x * rpb;             // a multiple of 64
+    const int64_t hi = lo + rpb < n_rows ? lo + rpb : n_rows;
+    for (int64_t base = lo; base < hi; base += KEY_NT) {      // block-uniform
+        const unsigned full = key_full_mask(sm, nl);
+        __syncthreads();                                       // everyone has read cnt before anyone appends or cuts
+        if (full) key_cut(sm, full, R);
+        const int64_t r0 = base + (int64_t)w * 64;             // the wave's 64 rows: one word of allow
+        uint64_t vis = 0ull;
+        if (r0 < hi) {
+            const int64_t left = hi - r0;
+            vis = left >= 64 ? ~0ull : ((1ull << left) - 1ull);
+            if (allow) vis &= allow[r0 >> 6];
+        }
+        if (vis != 0ull) {                                     // wave-uniform
+            const int64_t row = r0 + lane;
+            const bool on = (vis >> lane) & 1ull;
+            uint32_t h[QT];
+            code.high_words(lds, on ? row : r0, h);            // (a lane without a row reads the wave's first row: inside the array)
+            if (on) {
+                const unsigned long long low = (unsigned long long)(0xffffffffu - (uint32_t)row);
+#pragma unroll
+                for (int l = 0; l < QT; ++l)
+                    if (l < nl) key_append(sm, l, ((unsigned long long)h[l] << 32) | low);
+            }
+        }
+        __syncthreads();
+    }
+    key_cut(sm, (1u << nl) - 1u, R);
+    for (int t = tid; t < nl * R; t += KEY_NT) {
+        const int l = t / R, r = t % R;
+        part_k[((int64_t)blockIdx.x * nq + q0 + l) * R + r] = r < sm.cnt[l] ? sm.keys[l][r] : 0ull;
+    }
+}
+
+struct KeyScanArgs { dim3 grid; hipStream_t st; int64_t n_rows; int nq; const uint64_t* allow; int R; int64_t rpb; unsigned long long* part_k; };
+template <typename Code>
+int32_t key_scan_launch(const KeyScanArgs& a, const typename Code::Word* codes, int width, const typename Code::Word* qdata, int smem) {
+    if (smem > 0) ARX_HIP_CHECK(arx_func_smem((const void*)key_scan_kernel<Code>, smem));   // the Code's dynamic LDS (0: its LDS is static)
+    key_scan_kernel<Code><<<a.grid, KEY_NT, smem, a.st>>>(codes, a.n_rows, width, qdata, a.nq, a.allow, a.R, a.rpb, a.part_k);
+    ARX_HIP_CHECK(hipGetLastError());
+    return ARX_OK;
+}
+
 // the workspace of a candidate scan: (part, query) lists of R keys, at most KEY_SLOTS_MAX of them (64 MiB at R = 256)
 constexpr int KEY_QBATCH = 256;                 // queries per slice of a call
 constexpr int64_t KEY_SLOTS_MAX = 1ll << 15;
@@ -118,5 +186,44 @@ inline KeyWs key_layout(int64_t n_rows, int n_queries, int R) {
     if (w.slots < w.qb) w.slots = w.qb;
     w.total = round_up64(w.slots * R * 8, 256);
     return w;
+}
+
+constexpr int KEY_BLOCKS_TARGET = 1024, KEY_RPB_MIN_DEFAULT = 2048, KEY_RPB_LIMIT = 1 << 20;   // the default rows_per_block aims at that many scan blocks
+#define KEY_REQUIRE_ROWS_PER_BLOCK(rpb)                                                                                      \
+    ARX_REQUIRE((rpb) == 0 || ((rpb) >= 64 && (rpb) % 64 == 0 && (rpb) <= KEY_RPB_LIMIT),                                    \
+                "rows_per_block=%d: 0 (default) or a multiple of 64 in 64..%d", rpb, KEY_RPB_LIMIT)
+
+// The driver of a call, n_queries >= 1, after the caller's own argument checks (KEY_REQUIRE_ROWS_PER_BLOCK among them).  `Scan` is the
+// host side of a code: HI_DIRECT (key_merge_kernel's), WORKSPACE_FN (the name the size refusal gives), tile() (the QT its kernels run) and
+// launch(args, q0), which picks the instantiation and launches it for the slice of queries q0 .. q0 + args.nq - 1.
+template <typename Scan>
+int32_t key_scan(const Scan& scan, int64_t n_rows, int n_queries, const uint64_t* allow, int R, int rows_per_block, void* ws, int64_t ws_bytes,
+                 int32_t* out_cand, int32_t* out_hi, int64_t* out_count, hipStream_t st) {
+    const KeyWs L = key_layout(n_rows, n_queries, R);
+    ARX_REQUIRE(ws_bytes >= L.total, "workspace too small: %lld < %lld (%s)", (long long)ws_bytes, (long long)L.total, Scan::WORKSPACE_FN);
+    unsigned long long* part_k = (unsigned long long*)ws;
+    for (int q0 = 0; q0 < n_queries; q0 += KEY_QBATCH) {
+        const int nq = (n_queries - q0) < KEY_QBATCH ? (n_queries - q0) : KEY_QBATCH;
+        const int tiles = (nq + scan.tile() - 1) / scan.tile();
+        int64_t parts = 0;                                     // an empty shard launches no scan: the merge of no parts writes -1 and 0
+        if (n_rows > 0) {
+            int64_t rpb = rows_per_block;
+            if (rpb == 0) {
+                const int64_t want = KEY_BLOCKS_TARGET / tiles > 0 ? KEY_BLOCKS_TARGET / tiles : 1;
+                rpb = round_up64((n_rows + want - 1) / want, 256);
+                if (rpb < KEY_RPB_MIN_DEFAULT) rpb = KEY_RPB_MIN_DEFAULT;
+            }
+            const int64_t max_parts = L.slots / nq;             // >= 1: the partial lists the workspace holds per query
+            if ((n_rows + rpb - 1) / rpb > max_parts) rpb = round_up64((n_rows + max_parts - 1) / max_parts, 64);
+            parts = (n_rows + rpb - 1) / rpb;
+            ARX_REQUIRE(parts <= max_parts && parts < (1ll << 31), "grid too large");
+            const int32_t rc = scan.launch(KeyScanArgs{dim3((unsigned)parts, (unsigned)tiles), st, n_rows, nq, allow, R, rpb, part_k}, q0);
+            if (rc != ARX_OK) return rc;
+        }
+        key_merge_kernel<Scan::HI_DIRECT><<<nq, KEY_NT, 0, st>>>(part_k, parts, nq, R, out_cand + (int64_t)q0 * R,
+                                                                 out_hi ? out_hi + (int64_t)q0 * R : nullptr, out_count + q0);
+        ARX_HIP_CHECK(hipGetLastError());
+    }
+    return ARX_OK;
 }
 }      // namespace

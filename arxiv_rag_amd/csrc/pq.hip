@@ -20,10 +20,9 @@
 //           and the second read of the codebooks (dim KiB per query block, from L2) could be saved: a second kernel path that has not
 //           been written; tools/pq_bench.py's lut_event_ms is the cost it would halve at most.
 //   keys    s << 32 | (0xffffffff - row): key_lists.h.
-//   scan    block (stretch p of rows_per_block rows, tile t of QT queries), four waves.  The tile's byte tables sit in LDS, M * 256
-//           bytes per query, behind the tile's key lists (8 KiB per query).  A round gives every lane one row (a wave's 64 rows are one
-//           word of `allow`: a zero word costs that one load); the lane reads its M code bytes once, 16 at a time (4 or 1 where M is
-//           no multiple of 16), and for every byte gathers one table byte per query of the tile into an integer sum per query.
+//   scan    key_lists.h's key_scan_kernel (shared with binary.hip) over tiles of QT queries.  The tile's byte tables sit in LDS, M * 256
+//           bytes per query, behind the tile's key lists (8 KiB per query).  A lane reads its row's M code bytes once, 16 at a time (4 or
+//           1 where M is no multiple of 16), and for every byte gathers one table byte per query of the tile into that query's sum.
 //           QT IS CHOSEN FROM M SO THAT TWO BLOCKS FIT A CU: the largest of 8, 4, 2, 1 with QT * (M * 256 + 8 KiB lists) inside 80 KiB
 //           (QT = 8 for M <= 7, 4 for M <= 47, 2 for M <= 127, e.g. dim 768 at dsub 8, and 1 up to M = 256: 72 KiB).  The scan is a
 //           stream of dependent-address LDS byte gathers with a block-wide sort between rounds now and then; with two blocks per CU
@@ -50,9 +49,8 @@ constexpr int PQ_CODES = 256;                   // centroids of a subspace: one 
 constexpr int PQ_M_MAX = 256;
 constexpr int PQ_DIM_MAX = 8192;
 constexpr int PQ_LDS_BLOCK = 80 * 1024;         // a scan block's LDS: two blocks per CU
-constexpr int PQ_BLOCKS_TARGET = 1024;          // the default rows_per_block aims at this many scan blocks
-constexpr int PQ_RPB_MIN_DEFAULT = 2048;
-constexpr int PQ_RPB_LIMIT = 1 << 20;
+constexpr int PQ_BLOCKS_TARGET = 1024, PQ_RPB_MIN_DEFAULT = 2048, PQ_RPB_LIMIT = 1 << 20;   // key_scan's, as tests/test_gpu_pq_long.py reads them
+static_assert(PQ_BLOCKS_TARGET == KEY_BLOCKS_TARGET && PQ_RPB_MIN_DEFAULT == KEY_RPB_MIN_DEFAULT && PQ_RPB_LIMIT == KEY_RPB_LIMIT, "one set");
 
 // ---- encode -------------------------------------------------------------------------------------------------------------------------------
 template <int DS>
@@ -177,78 +175,57 @@ __global__ __launch_bounds__(PQ_NT) void pq_lut_kernel(const f16_t* __restrict__
 template <int QT>
 constexpr int pq_lists_bytes() { return (int)((sizeof(KeyLists<QT>) + 15) / 16 * 16); }
 
-// V: code bytes per load (16: M % 16 == 0; 4: M % 4 == 0; 1: any M)
-template <int QT, int V>
-__global__ __launch_bounds__(PQ_NT) void pq_scan_kernel(const uint8_t* __restrict__ codes, int64_t n_rows, int M, const uint8_t* __restrict__ lut,
-                                                        int nq, const uint64_t* __restrict__ allow, int R, int64_t rpb,
-                                                        unsigned long long* __restrict__ part_k) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    KeyLists<QT>& sm = *reinterpret_cast<KeyLists<QT>*>(smem);
-    const uint8_t* tab = reinterpret_cast<const uint8_t*>(smem + pq_lists_bytes<QT>());    // [QT][M][256]
-    const int TB = M * PQ_CODES;                                                           // a query's table, a multiple of 256 bytes
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int q0 = blockIdx.y * QT;
-    const int nl = nq - q0 < QT ? nq - q0 : QT;               // the tile's queries
-    for (int t = tid; t < QT * (TB / 16); t += PQ_NT) {
-        const int l = t / (TB / 16), o = t % (TB / 16);
-        uint4 val = {0u, 0u, 0u, 0u};
-        if (l < nl) val = reinterpret_cast<const uint4*>(lut + (int64_t)(q0 + l) * TB)[o];
-        reinterpret_cast<uint4*>(smem + pq_lists_bytes<QT>())[t] = val;
+// The PQ code as key_scan_kernel sees it.  V: code bytes per load (16: M % 16 == 0; 4: M % 4 == 0; 1: any M)
+template <int QT_, int V>
+struct PqCode {
+    using Word = uint8_t;
+    static constexpr int QT = QT_;
+    const uint8_t* codes; int M; const uint8_t* lut;            // [n_rows][M]; the slice's [nq][M][256]
+    struct Lds { KeyLists<QT>& lists; uint8_t* tab; };          // tab: [QT][M][256], behind the lists
+    __device__ __forceinline__ Lds lds() const {
+        extern __shared__ __attribute__((aligned(16))) char smem[];
+        return {*reinterpret_cast<KeyLists<QT>*>(smem), reinterpret_cast<uint8_t*>(smem + pq_lists_bytes<QT>())};
     }
-    if (tid < QT) { sm.cnt[tid] = 0; sm.thr[tid] = 0ull; }
-    __syncthreads();
-    const int64_t lo = (int64_t)blockIdx.x * rpb;             // a multiple of 64
-    const int64_t hi = lo + rpb < n_rows ? lo + rpb : n_rows;
-    for (int64_t base = lo; base < hi; base += PQ_NT) {       // block-uniform
-        const unsigned full = key_full_mask(sm, nl);
-        __syncthreads();                                       // everyone has read cnt before anyone appends or cuts
-        if (full) key_cut(sm, full, R);
-        const int64_t r0 = base + (int64_t)w * 64;             // the wave's 64 rows: one word of allow
-        uint64_t vis = 0ull;
-        if (r0 < hi) {
-            const int64_t left = hi - r0;
-            vis = left >= 64 ? ~0ull : ((1ull << left) - 1ull);
-            if (allow) vis &= allow[r0 >> 6];
+    __device__ __forceinline__ void stage(const Lds s, int q0, int nl) const {
+        const int TB = M * PQ_CODES;                            // a query's table, a multiple of 256 bytes
+        for (int t = threadIdx.x; t < QT * (TB / 16); t += PQ_NT) {
+            const int l = t / (TB / 16), o = t % (TB / 16);
+            uint4 val = {0u, 0u, 0u, 0u};
+            if (l < nl) val = reinterpret_cast<const uint4*>(lut + (int64_t)(q0 + l) * TB)[o];
+            reinterpret_cast<uint4*>(s.tab)[t] = val;
         }
-        if (vis != 0ull) {                                     // wave-uniform
-            const int64_t row = r0 + lane;
-            const bool on = (vis >> lane) & 1ull;
-            const uint8_t* c = codes + (on ? row : r0) * M;    // (a lane without a row reads the wave's first row: inside the array)
-            int s[QT];
-#pragma unroll
-            for (int l = 0; l < QT; ++l) s[l] = 0;
-            for (int mm = 0; mm < M; mm += V) {
-                uint32_t xw[V >= 4 ? V / 4 : 1];
-                if constexpr (V == 16) {
-                    const uint4 v = *reinterpret_cast<const uint4*>(c + mm);
-                    xw[0] = v.x; xw[1] = v.y; xw[2] = v.z; xw[3] = v.w;
-                } else if constexpr (V == 4) {
-                    xw[0] = *reinterpret_cast<const uint32_t*>(c + mm);
-                } else {
-                    xw[0] = c[mm];
-                }
-#pragma unroll
-                for (int e = 0; e < V; ++e) {
-                    const uint8_t* t = tab + (mm + e) * PQ_CODES + ((xw[e >> 2] >> (8 * (e & 3))) & 255u);
-#pragma unroll
-                    for (int l = 0; l < QT; ++l) s[l] += t[l * TB];
-                }
-            }
-            if (on) {
-                const unsigned long long low = (unsigned long long)(0xffffffffu - (uint32_t)row);
-#pragma unroll
-                for (int l = 0; l < QT; ++l)
-                    if (l < nl) key_append(sm, l, ((unsigned long long)(uint32_t)s[l] << 32) | low);
-            }
+    }
+    __device__ __forceinline__ void gather(const Lds s, const uint8_t* c, int mm, int (&sum)[QT]) const {
+        const int TB = M * PQ_CODES;                            // (the V code bytes at c[mm]: a table byte per query for each)
+        uint32_t xw[V >= 4 ? V / 4 : 1];
+        if constexpr (V == 16) {
+            const uint4 v = *reinterpret_cast<const uint4*>(c + mm);
+            xw[0] = v.x; xw[1] = v.y; xw[2] = v.z; xw[3] = v.w;
+        } else if constexpr (V == 4) {
+            xw[0] = *reinterpret_cast<const uint32_t*>(c + mm);
+        } else {
+            xw[0] = c[mm];
         }
-        __syncthreads();
+#pragma unroll
+        for (int e = 0; e < V; ++e) {
+            const uint8_t* t = s.tab + (mm + e) * PQ_CODES + ((xw[e >> 2] >> (8 * (e & 3))) & 255u);
+#pragma unroll
+            for (int l = 0; l < QT; ++l) sum[l] += t[l * TB];
+        }
     }
-    key_cut(sm, (1u << nl) - 1u, R);
-    for (int t = tid; t < nl * R; t += PQ_NT) {
-        const int l = t / R, r = t % R;
-        part_k[((int64_t)blockIdx.x * nq + q0 + l) * R + r] = r < sm.cnt[l] ? sm.keys[l][r] : 0ull;
+    __device__ __forceinline__ void high_words(const Lds s, int64_t row, uint32_t (&h)[QT]) const {
+        const uint8_t* c = codes + row * M;
+        int sum[QT] = {};                                                                 // the sums, in registers
+        if constexpr (V == 16) {                               // one 16-byte load a trip: unrolled further, <1, 16> takes 16 more VGPRs
+#pragma unroll 1
+            for (int mm = 0; mm < M; mm += V) gather(s, c, mm, sum);
+        } else {
+            for (int mm = 0; mm < M; mm += V) gather(s, c, mm, sum);
+        }
+#pragma unroll
+        for (int l = 0; l < QT; ++l) h[l] = (uint32_t)sum[l];
     }
-}
+};
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------------
 bool pq_dim_ok(int32_t dim) { return dim >= 64 && dim % 64 == 0 && dim <= PQ_DIM_MAX; }
@@ -269,21 +246,22 @@ static_assert(pq_scan_smem<1>(PQ_M_MAX) <= PQ_LDS_BLOCK, "one query's lists and 
     ARX_REQUIRE(pq_dsub_ok(dsub), "dsub=%d must be a power of two in 4..64", dsub);                                          \
     ARX_REQUIRE(pq_m_ok(dim, dsub), "M=%d (dim / dsub) must be in 1..%d: the look-up tables must fit in LDS", dim / dsub, PQ_M_MAX)
 
-template <int QT, int V>
-int32_t pq_launch_scan(dim3 grid, hipStream_t st, const uint8_t* codes, int64_t n_rows, int M, const uint8_t* lut, int nq, const uint64_t* allow,
-                       int R, int64_t rpb, unsigned long long* part_k) {
-    const int smem = (int)pq_scan_smem<QT>(M);                 // <= PQ_LDS_BLOCK by pq_tile
-    ARX_HIP_CHECK(arx_func_smem((const void*)pq_scan_kernel<QT, V>, smem));
-    pq_scan_kernel<QT, V><<<grid, PQ_NT, smem, st>>>(codes, n_rows, M, lut, nq, allow, R, rpb, part_k);
-    ARX_HIP_CHECK(hipGetLastError());
-    return ARX_OK;
-}
-template <int QT, typename... A>
-int32_t pq_launch_scan_v(int M, A... a) {
-    if (M % 16 == 0) return pq_launch_scan<QT, 16>(a...);
-    if (M % 4 == 0) return pq_launch_scan<QT, 4>(a...);
-    return pq_launch_scan<QT, 1>(a...);
-}
+struct PqScan {                                                // the host side of the code, for key_scan
+    static constexpr bool HI_DIRECT = true;                    // out_sum is the high word
+    static constexpr const char* WORKSPACE_FN = "arx_pq_workspace_bytes";
+    const uint8_t *codes, *lut; int M;
+    int tile() const { return pq_tile(M); }
+    int32_t launch(const KeyScanArgs& a, int q0) const {
+        const uint8_t* T = lut + (int64_t)q0 * M * PQ_CODES;
+        const int QT = tile(), V = M % 16 == 0 ? 16 : M % 4 == 0 ? 4 : 1;
+#define PQ_SCAN(QT_, V_) /* smem <= PQ_LDS_BLOCK by pq_tile */ \
+    if (QT == QT_ && V == V_) return key_scan_launch<PqCode<QT_, V_>>(a, codes, M, T, (int)pq_scan_smem<QT_>(M))
+        PQ_SCAN(8, 16); PQ_SCAN(8, 4); PQ_SCAN(8, 1); PQ_SCAN(4, 16); PQ_SCAN(4, 4); PQ_SCAN(4, 1);
+        PQ_SCAN(2, 16); PQ_SCAN(2, 4); PQ_SCAN(2, 1); PQ_SCAN(1, 16); PQ_SCAN(1, 4);
+#undef PQ_SCAN
+        return key_scan_launch<PqCode<1, 1>>(a, codes, M, T, (int)pq_scan_smem<1>(M));
+    }
+};
 }      // namespace
 
 extern "C" int32_t arx_pq_encode(const void* rows, int64_t n_rows, int32_t dim, int32_t dsub, const float* centre, const float* codebooks,
@@ -342,49 +320,14 @@ extern "C" int32_t arx_pq_candidates_tuned(const uint8_t* codes, int64_t n_rows,
     PQ_REQUIRE_SHAPE(dim, dsub);
     ARX_REQUIRE(n_rows >= 0 && n_rows < (1ll << 31), "n_rows=%lld out of range 0..2^31-1", (long long)n_rows);
     ARX_REQUIRE(n_queries >= 0, "n_queries=%d is negative", n_queries);
-    ARX_REQUIRE(rows_per_block == 0 || (rows_per_block >= 64 && rows_per_block % 64 == 0 && rows_per_block <= PQ_RPB_LIMIT),
-                "rows_per_block=%d: 0 (default) or a multiple of 64 in 64..%d", rows_per_block, PQ_RPB_LIMIT);
+    KEY_REQUIRE_ROWS_PER_BLOCK(rows_per_block);
     if (n_queries == 0) return ARX_OK;
     ARX_REQUIRE(lut && out_cand && out_count && ws && (codes || n_rows == 0), "null pointer argument");
     ARX_REQUIRE(((uintptr_t)codes | (uintptr_t)lut | (uintptr_t)ws) % 16 == 0, "codes, lut and ws must be 16-byte aligned");
     ARX_REQUIRE(((uintptr_t)allow | (uintptr_t)out_count) % 8 == 0, "allow and out_count must be 8-byte aligned");
     ARX_REQUIRE(((uintptr_t)out_cand | (uintptr_t)out_sum) % 4 == 0, "out_cand and out_sum must be 4-byte aligned");
-    const KeyWs L = key_layout(n_rows, n_queries, R);
-    ARX_REQUIRE(ws_bytes >= L.total, "workspace too small: %lld < %lld (arx_pq_workspace_bytes)", (long long)ws_bytes, (long long)L.total);
-    hipStream_t st = (hipStream_t)stream;
-    const int M = dim / dsub, QT = pq_tile(M);
-    unsigned long long* part_k = (unsigned long long*)ws;
-    for (int q0 = 0; q0 < n_queries; q0 += KEY_QBATCH) {
-        const int nq = (n_queries - q0) < KEY_QBATCH ? (n_queries - q0) : KEY_QBATCH;
-        const int tiles = (nq + QT - 1) / QT;
-        int64_t parts = 0;                                     // an empty shard launches no scan: the merge of no parts writes -1 and 0
-        if (n_rows > 0) {
-            int64_t rpb = rows_per_block;
-            if (rpb == 0) {
-                const int64_t want = PQ_BLOCKS_TARGET / tiles > 0 ? PQ_BLOCKS_TARGET / tiles : 1;
-                rpb = round_up64((n_rows + want - 1) / want, 256);
-                if (rpb < PQ_RPB_MIN_DEFAULT) rpb = PQ_RPB_MIN_DEFAULT;
-            }
-            const int64_t max_parts = L.slots / nq;             // >= 1: the partial lists the workspace holds per query
-            if ((n_rows + rpb - 1) / rpb > max_parts) rpb = round_up64((n_rows + max_parts - 1) / max_parts, 64);
-            parts = (n_rows + rpb - 1) / rpb;
-            ARX_REQUIRE(parts <= max_parts && parts < (1ll << 31), "grid too large");
-            const dim3 grid((unsigned)parts, (unsigned)tiles);
-            const uint8_t* T = lut + (int64_t)q0 * M * PQ_CODES;
-            int32_t rc;
-            switch (QT) {
-                case 8: rc = pq_launch_scan_v<8>(M, grid, st, codes, n_rows, M, T, nq, allow, R, rpb, part_k); break;
-                case 4: rc = pq_launch_scan_v<4>(M, grid, st, codes, n_rows, M, T, nq, allow, R, rpb, part_k); break;
-                case 2: rc = pq_launch_scan_v<2>(M, grid, st, codes, n_rows, M, T, nq, allow, R, rpb, part_k); break;
-                default: rc = pq_launch_scan_v<1>(M, grid, st, codes, n_rows, M, T, nq, allow, R, rpb, part_k); break;
-            }
-            if (rc != ARX_OK) return rc;
-        }
-        key_merge_kernel<true><<<nq, PQ_NT, 0, st>>>(part_k, parts, nq, R, out_cand + (int64_t)q0 * R,
-                                                     out_sum ? out_sum + (int64_t)q0 * R : nullptr, out_count + q0);
-        ARX_HIP_CHECK(hipGetLastError());
-    }
-    return ARX_OK;
+    return key_scan(PqScan{codes, lut, dim / dsub}, n_rows, n_queries, allow, R, rows_per_block, ws, ws_bytes, out_cand, out_sum, out_count,
+                    (hipStream_t)stream);
 }
 
 extern "C" int32_t arx_pq_candidates(const uint8_t* codes, int64_t n_rows, int32_t dim, int32_t dsub, const uint8_t* lut, int32_t n_queries,

@@ -60,7 +60,7 @@ def pq_tile(M):
 
 
 def instantiation(M):
-    """(QT, V) of pq_scan_kernel for M subspaces: pq_tile and pq_launch_scan_v"""
+    """(QT, V) of key_scan_kernel<PqCode<QT, V>> for M subspaces: pq_tile and PqScan::launch"""
     return pq_tile(M), 16 if M % 16 == 0 else 4 if M % 4 == 0 else 1
 
 
